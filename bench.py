@@ -9,10 +9,14 @@ conv_nonsquare_top.cpp:295-357) on synthetic 4K RGB images, one process per GPU.
 A "step" = one pass of the hot path over this rank's batch of IMAGES_PER_GPU 3840x2160x3 uint8
 images, already resident in HBM (BASELINE.json configs[3]: 64 images over 8 GPUs = 8 per GPU; weak
 scaling: every rank always owns 8 images, no data-path collective — images are independent).
-Rank 0 prints ONE JSON line:
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times --steps steps and reports only
 
   value / ms_per_step   the timed transform (headline, as BASELINE.json's metric)
-  output_bit_exact      SHA-256 of every rank's latents and reconstructions of the TIMED run against
+
+--dump-outputs DIR writes rank 0's reconstruction and latent of the last timed step (see dump_outputs).
+--full adds everything else, each with a run of its own behind the timed loop:
+
+  output_bit_exact     SHA-256 of every rank's latents and reconstructions of the TIMED run against
                         tests/golden/bench_4k_hashes.json (made by the oracle, tests/golden/make_bench_hashes.py)
   rank_checksums        adler32 of each rank's output batch, gathered on rank 0 (every shard ran, shards differ)
   roofline              the dominant kernel, timed live with hipEvents recorded by the library on the launch
@@ -167,6 +171,10 @@ def parse():
     ap.add_argument("--width", type=int, default=3840)
     ap.add_argument("--height", type=int, default=2160)
     ap.add_argument("--images-per-gpu", type=int, default=8)
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write rank 0's outputs of the last timed step as DIR/<name>.npy (float32; "
+                                                           "arrays larger than DUMP_SAMPLE elements as a fixed, seeded sample)")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline: output check against the oracle's hashes, "
+                                                         "per-layer table and roofline, clocks, sustained region and the secondary legs")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-coder", action="store_true", help="skip the secondary with_coder measurement")
     ap.add_argument("--no-hyperprior", action="store_true", help="skip the secondary hyperprior (configs[4]) measurement")
@@ -176,12 +184,32 @@ def parse():
     ap.add_argument("--sustained", action="store_true", help="with --headline-only: keep the >= 2 s sustained region (its clock / power "
                                                              "samples are the steady-state ones; it launches nothing but the 8 layers)")
     ap.add_argument("--headline-only", action="store_true",
-                    help="the timed loop and the per-layer table only (what profiles/collect_pmc.sh runs under rocprofv3)")
+                    help="implies --full: the timed loop and the per-layer table only (what profiles/collect_pmc.sh runs under rocprofv3)")
     ap.add_argument("--cpu-sample", type=int, nargs=2, default=[256, 256], metavar=("W", "H"))
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl (= RCCL, one GPU per rank) is the real thing; gloo lets several ranks share one GPU "
                          "to rehearse the multi-rank path on a 1-GPU box")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
+
+
+DUMP_SAMPLE = 1 << 22   # elements written per output array at most: 2 arrays x 16 MiB of float32 stay under the 64 MB a dump may take
+
+
+def dump_outputs(directory, arrays: dict) -> None:
+    """Writes each tensor of `arrays` as <directory>/<name>.npy in float32 (the outputs are uint8: exact).  An array of at most
+    DUMP_SAMPLE elements is written whole, in its own shape; a larger one as the 1-D sample at DUMP_SAMPLE flat indices drawn,
+    sorted, from numpy default_rng(0), so that the same arguments give the same positions in every run and every build."""
+    import torch
+    d = Path(directory)
+    d.mkdir(parents=True, exist_ok=True)
+    for name, t in arrays.items():
+        if t.numel() > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(0).integers(0, t.numel(), DUMP_SAMPLE, dtype=np.int64))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(d / f"{name}.npy", t.cpu().numpy().astype(np.float32))
 
 
 def cpu_baseline(image0: np.ndarray, sample_wh, gpu_latent0, gpu_out0):
@@ -319,6 +347,7 @@ def small_configs(api, codec, dev):
 def main():
     args = parse()
     if args.headline_only:
+        args.full = True
         args.no_coder = args.no_hyperprior = args.no_host_io = args.no_cpu_baseline = args.no_configs = True
         args.no_sustained = not args.sustained
     import torch
@@ -360,7 +389,7 @@ def main():
         rank_devices = [bytes(b.cpu().tolist()).rstrip(b"\0").decode() for b in bufs]
         if args.backend == "nccl" and len(set(rank_devices)) != world:
             raise SystemExit(f"rank {rank}: {world} ranks on {len(set(rank_devices))} distinct device(s): {rank_devices}")
-    sampler = ClockPowerSampler(ident.split("|")[1]).start() if rank == 0 else None
+    sampler = ClockPowerSampler(ident.split("|")[1]).start() if rank == 0 and args.full else None
 
     W, H, B = args.width, args.height, args.images_per_gpu
     # synthetic inputs: uint8 NHWC, i.i.d. uniform 0..255, one seed per global image index
@@ -455,6 +484,32 @@ def main():
         step()
     torch.cuda.synchronize()
     dt = timed(step, args.steps, "timed")   # the headline: nothing but the 8 launches per step on the stream
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"reconstruction": out, "latent": latent})
+
+    def headline():
+        res = {
+            "metric": "Mpixels/s encode+decode (4K RGB)", "value": round(world * B * W * H * args.steps / dt / 1e6, 2), "unit": "Mpixels/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8",
+            "data": "synthetic", "config": {"workload": f"{B} x {W}x{H} RGB uint8 images per GPU, eight_layers_net (PARAM weights), "
+                                                        f"BASELINE.json configs[3] shard; transform only (the reference has no coder)",
+                                            "images_per_gpu": B, "global_images": world * B, "parallelism": f"image-sharded x{world}",
+                                            "partition": "image i -> rank i mod world (dist.shard_indices)", "image_ids_rank0": image_ids},
+            "rank_devices": rank_devices, "distinct_devices": len(set(rank_devices)),
+            "world_size": (dist.get_world_size() if use_dist else 1),
+        }
+        if use_dist:
+            res["config"]["collectives"] = (f"torch.distributed backend {dist.get_backend()} (bookkeeping only: weight broadcast, barrier, "
+                                            f"MAX of the timed region{', checksum all-gather' if args.full else ''})")
+        return res
+
+    if not args.full:   # a plain run: the headline and nothing else
+        if rank == 0:
+            print(json.dumps(headline()))
+        if use_dist:
+            dist.destroy_process_group()
+        return
     # the per-layer table comes from a separate short loop (2 hipEvents per layer and step would sit inside `value` otherwise)
     net.profile(True)
     net.layer_ms(reset=True)
@@ -682,8 +737,6 @@ def main():
         return
 
     import ctypes
-    px_per_step = world * B * W * H
-    value = px_per_step * args.steps / dt / 1e6
     # ---- roofline of the dominant kernel (largest share of device time) ----------------------
     avg_ms = [m / max(c, 1) for m, c in zip(layer_ms, launches)]
     names = [api._lib.lib().sicn_kernel_for(ctypes.byref(d.to_c())).decode() for d in net.descs]
@@ -737,19 +790,11 @@ def main():
                  "kernel": f"layer {dom} ({names[dom]})", "avg_launch_ms": round(avg_ms[dom], 4),
                  "note": "int8 MAC = 2 ops, counted in the TFLOP/s unit; algorithmic (zero-skipped) work"})
     net_ops = sum(2.0 * dd.algorithmic_macs for dd in net.descs) * B
-    res = {
-        "metric": "Mpixels/s encode+decode (4K RGB)", "value": round(value, 2), "unit": "Mpixels/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3),
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8",
-        "data": "synthetic", "config": {"workload": f"{B} x {W}x{H} RGB uint8 images per GPU, eight_layers_net (PARAM weights), "
-                                                    f"BASELINE.json configs[3] shard; transform only (the reference has no coder)",
-                                        "images_per_gpu": B, "global_images": world * B, "parallelism": f"image-sharded x{world}",
-                                        "partition": "image i -> rank i mod world (dist.shard_indices)", "image_ids_rank0": image_ids},
+    res = headline()
+    res.update({
         "output_bit_exact": (None if any(v < 0 for v in verdicts) and all(v != 0 for v in verdicts) else all(v == 1 for v in verdicts)),
         "output_check": "sha256 of every latent and reconstruction of the timed run vs tests/golden/bench_4k_hashes.json (oracle direct form)",
         "rank_checksums": rank_checksums,
-        "rank_devices": rank_devices, "distinct_devices": len(set(rank_devices)),
-        "world_size": (dist.get_world_size() if use_dist else 1),
         "clocks": {"timed": clk_t, "layers": clk_l, "sustained": clk_s},
         "roofline": roof, "layers": layers,
         "kernel_source_fingerprint": fp, "secondary_source_fingerprint": kernel_source_fingerprint(SECONDARY_SOURCES),
@@ -758,7 +803,7 @@ def main():
         # SURVEY.md 8(d), the memory view: layer-wise algorithmic bytes (every activation written once and read once)
         "whole_net_hbm_frac": round(sum(l["GBs"] * l["ms"] * 1e-3 for l in layers) / (dt / args.steps) / PEAK_HBM_GBS, 4)
         if all("GBs" in l for l in layers) else None,
-    }
+    })
     if sustained is not None:
         res["sustained"] = sustained
     if strong is not None:
@@ -776,8 +821,6 @@ def main():
     if world == 1 and not args.no_cpu_baseline:
         res["cpu_baseline"] = secondary("cpu_baseline", lambda: cpu_baseline(host[0], args.cpu_sample, lat_h[0], out_h[0]))
     res["secondary_errors"] = secondary_errors
-    if use_dist:
-        res["config"]["collectives"] = f"torch.distributed backend {dist.get_backend()} (bookkeeping only: weight broadcast, barrier, MAX of the timed region, checksum all-gather)"
     print(json.dumps(res))
     if use_dist:
         dist.destroy_process_group()

@@ -742,7 +742,7 @@ def test_bench_two_ranks_on_one_gpu_rehearsal():
     import sys
     from conftest import ROOT
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", "29533", str(ROOT / "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--backend", "gloo",
+           "--master-port", "29533", str(ROOT / "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--backend", "gloo",
            "--width", "256", "--height", "128", "--images-per-gpu", "2"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=str(ROOT))
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
@@ -771,7 +771,7 @@ def test_bench_rccl_code_path_single_rank():
     import sys
     from conftest import ROOT
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
-           "--master-port", "29547", str(ROOT / "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
+           "--master-port", "29547", str(ROOT / "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline",
            "--no-hyperprior", "--width", "512", "--height", "256", "--images-per-gpu", "2"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=str(ROOT),
                        env=dict(os.environ, SICN_BENCH_FORCE_DIST="1", SICN_FORCE_COLLECTIVES="1"))
@@ -782,6 +782,32 @@ def test_bench_rccl_code_path_single_rank():
     assert d["strong_scaling"]["images_per_gpu"] == 64 and d["strong_scaling"]["value"] > 0
     assert d["banded"]["bands"] == 1 and d["banded"]["equals_one_gpu_bytes"] is True
     assert not [k for k, v in d.items() if isinstance(v, dict) and "error" in v], d
+
+
+def test_bench_plain_run_dumps_the_timed_outputs(tmp_path):
+    """A plain bench.py run prints the headline line and nothing of --full; --dump-outputs writes the timed step's reconstruction and
+    latent (whole at this size) as float32, equal to the oracle's for the same seeded images."""
+    from conftest import ROOT
+    from simple_image_compression_network_amd.config import eight_layer_descs
+    W, H, B = 256, 128, 2
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--width", str(W), "--height", str(H),
+           "--images-per-gpu", str(B), "--dump-outputs", str(tmp_path)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=str(ROOT))
+    assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0
+    assert d["unit"] == "Mpixels/s" and d["higher_is_better"] is True and d["dtype"] == "u8"
+    assert not {"layers", "roofline", "output_bit_exact", "with_coder", "hyperprior", "cpu_baseline", "configs"} & set(d), d
+    z = np.load(GOLDEN / "param_weights.npz")
+    words, bias = [z[f"w{n}_words"] for n in range(8)], [z[f"b{n}"] for n in range(8)]
+    rec, lat = np.load(tmp_path / "reconstruction.npy"), np.load(tmp_path / "latent.npy")
+    assert rec.dtype == lat.dtype == np.float32 and rec.shape == (B, H, W, 3)
+    for i in range(B):
+        x = np.random.default_rng(i).integers(0, 256, (H, W, 3), dtype=np.uint8)
+        ref = c_oracle.run_net(eight_layer_descs(W, H), words, bias, x, "direct", threads=4)
+        assert np.array_equal(lat[i], ref[3]) and np.array_equal(rec[i], ref[7]), i
 
 
 def test_committed_small_vectors_on_gpu(api):

@@ -1,12 +1,12 @@
 #!/bin/bash
-# Instruction-cache counters of the headline run (bench.py --headline-only: nothing but the 8 layers): the wide persistent kernels' tile loop is
+# Instruction-cache counters of the headline run (bench.py --full --headline-only: nothing but the 8 layers): the wide persistent kernels' tile loop is
 # 87 - 103 KB of code against a 64 KB instruction cache shared by two CUs.  One --pmc pass (kernel trace only).  usage: bash tools/icache_pmc.sh <tag>
 tag=${1:-icache}
 root=${GRAFT_REPO_ROOT:-$(pwd)}
 out=$root/gpurun_out/prof_$tag
 mkdir -p "$out"
 cd "$root" && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --pmc SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQC_ICACHE_MISSES_DUPLICATE SQ_IFETCH SQ_IFETCH_LEVEL SQ_WAVE_CYCLES GRBM_GUI_ACTIVE -d "$out" -o pmc --output-format csv -- python3 bench.py --headline-only --steps 3 --warmup 1 > /dev/null 2> "$out/err.txt"
+rocprofv3 --kernel-trace --pmc SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQC_ICACHE_MISSES_DUPLICATE SQ_IFETCH SQ_IFETCH_LEVEL SQ_WAVE_CYCLES GRBM_GUI_ACTIVE -d "$out" -o pmc --output-format csv -- python3 bench.py --full --headline-only --steps 3 --warmup 1 > /dev/null 2> "$out/err.txt"
 python3 - "$out" <<'PY' | tee $root/gpurun_out/${tag}_icache.txt
 import collections, csv, glob, sys
 rows = []

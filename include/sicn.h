@@ -88,7 +88,7 @@ typedef struct sicn_layer_desc {
 typedef struct sicn_options {
     int32_t struct_bytes;    /* sizeof(sicn_options) of the caller's build                          */
     int32_t force_generic;   /* 1: the shape-agnostic kernel (k_generic) for every layer            */
-    int32_t mfma_shape;      /* 0 / 16: v_mfma_i32_16x16x64_i8 kernels; 32: the 32x32x32 kernels (ALT build only) */
+    int32_t mfma_shape;      /* 0 / 16: the v_mfma_i32_16x16x64_i8 kernels (the only ones; see the note below)      */
     int32_t tile_x;          /* 0: by layer shape and grid size; 16 / 32: force that M-tile width   */
     int32_t strip_chunks;    /* 0: automatic; n: cut the vertical strips of the RGB layers into n   */
     int32_t no_phase_layout; /* 0: default; 1: never use the PHASE layout; 2: not towards layer 7   */
@@ -104,20 +104,14 @@ typedef struct sicn_options {
     int32_t persistent_grid; /* 0: one workgroup per CU; n: at most n (rounded down to a multiple of the XCD count)       */
                              /*    workgroups for the wide persistent kernels — tests use it to make every workgroup    */
                              /*    walk through many tiles of a small input                                            */
-    /* The four forms below MEASURED A LOSS against the defaults on MI355X and are built into the ALT  */
-    /* library only (libsicn_alt.so, `make ALT=1`; sicn_has_alt_kernels() == 1), where their parity tests run.  The product library     */
-    /* (libsicn.so) answers split_k > 1, l7_loader = 2, l0_form = 2 and gdn_fuse = 2 with SICN_EINVAL.                                   */
-    int32_t split_k;         /* 0 / 1: never split K (there is no automatic K split: it measured a loss at every size); > 1 (ALT only): */
-                             /*    forced where the form exists (the channel-split 8 x 16 kernels inside a net chain, whose workspace   */
-                             /*    holds the partial tensors) — K is split into channel-group pairs over IFM_CH / 64 workgroups, exact  */
-    int32_t l7_loader;       /* layer 7 (k_l7): 0 / 1: four waves, every wave requests its share of a step's rows; 2 (ALT only): the     */
-                             /*    loader-wave form k_l7s (a fifth wave issues all row requests; 8 % slower)      */
-    int32_t l0_form;         /* layer 0: 0 / 1: one workgroup per run of tiles (k_l0); 2 (ALT only): the persistent kernel k_l0p (two    */
-                             /*    workgroups per CU walk many runs, persistent_grid caps them; measured 11 % slower)        */
-    int32_t gdn_fuse;        /* layers with a sicn_gdn: 0: layer 0 with 128 channels applies its activation itself, before its          */
-                             /*    one store (k_l0g); 1: never (layer kernel, then k_gdn in place); 2 (ALT only): 0 + the 128 -> RGB     */
-                             /*    layer of a chain applies the activation of the layer before it on the way in (k_l7g: measured no      */
-                             /*    faster than k_gdn + k_l7)                                                              */
+    /* Removed forms: mfma_shape = 32, split_k > 1 and the value 2 of l7_loader / l0_form / gdn_fuse selected kernel forms that    */
+    /* were removed in library 0.3.x (a second implementation, or a measured loss: DESIGN.md 3.1d, 3.2, 3.3, 11).  The fields keep */
+    /* their places; any value outside the ones listed is SICN_EINVAL.                                                           */
+    int32_t split_k;         /* 0 / 1: K is never split                                                                  */
+    int32_t l7_loader;       /* 0 / 1: layer 7 (k_l7): four waves, every wave requests its share of a step's rows        */
+    int32_t l0_form;         /* 0 / 1: layer 0 (k_l0): one workgroup per run of tiles                                     */
+    int32_t gdn_fuse;        /* layers with a sicn_gdn: 0: layer 0 with 128 channels applies its activation itself, before */
+                             /*    its one store (k_l0g); 1: never (layer kernel, then k_gdn in place)                    */
     int32_t reserved[2];
 } sicn_options;
 
@@ -126,9 +120,7 @@ typedef struct sicn_net sicn_net;         /* a chain of layers (the 8-layer net,
 
 /* Library / device ------------------------------------------------------------------------- */
 int sicn_version(void);                  /* 1000*major + minor                                 */
-int sicn_has_alt_kernels(void);          /* 1: this build carries the alternate kernel families (the 32x32x32 MFMA kernels of
-                                          * k_mfma.hip, `make ALT=1` -> libsicn_alt.so: parity tests only); 0: the product build,
-                                          * which rejects sicn_options.mfma_shape = 32 with SICN_EINVAL */
+int sicn_has_alt_kernels(void);          /* always 0: the alternate kernel build was removed in 0.3.x; kept so that callers link */
 const char *sicn_strerror(int code);
 /* Device rule.  The library holds gfx950 code objects only: an entry point that would touch a device whose gcnArchName does not
  * start with "gfx950" returns SICN_ENODEV (one line on stderr) — weights upload, layers, nets.  Grids, strip cuts and the
@@ -137,7 +129,7 @@ const char *sicn_strerror(int code);
  * 64 -> 2, CPX 32 -> 1; hipDeviceProp_t carries no XCD count, and the value only steers which tiles share an L2).
  * sicn_debug_plan shows what a layer would launch on a chip of n_cu CUs, without a GPU: out[] = { n_cu, n_xcd, kernel kind
  * (0 generic, 1 mfma conv, 2 mfma deconv, 3 layer 0, 4 layer 7), mfma family (0 plain, 1 pipelined, 2 wide persistent), tile_x,
- * split_n, split_k, grid x, grid y, grid z, strip chunks (wide persistent: 1 = part of the tiles dealt dynamically), layer-0 tiles per
+ * split_n, split_k (always 1), grid x, grid y, grid z, strip chunks (wide persistent: 1 = part of the tiles dealt dynamically), layer-0 tiles per
  * run }.  sicn_debug_xcd_item is the host mirror of
  * the kernels' workgroup -> work item mapping (-1: padding workgroup). */
 /* dst[n][h][w][c] = the top-left h x w corner of every image of src[n][src_h][src_w][c] (device pointers, one launch, enqueue
@@ -190,13 +182,10 @@ int sicn_net_create(const sicn_layer_desc *descs, sicn_weights *const *weights, 
 int sicn_net_create_opt(const sicn_layer_desc *descs, sicn_weights *const *weights, int n_layers,
                         const sicn_options *opt, sicn_net **out);
 void sicn_net_free(sicn_net *net);
-/* Bytes of DEVICE scratch `sicn_net_forward` needs for a batch of n_images: two ping-pong activation buffers and, for chains
- * whose grids are small enough for the K split (sicn_options.split_k), the slices' partial output tensors and one arrival word
- * per workgroup.  The scratch needs NO initialisation: an arrival word only counts when it carries the net's random 56-bit tag,
- * and the workgroup that finishes a tile clears it (any other content, e.g. uninitialised memory, reads as "nobody arrived").
- * Depends on the current device's CU count (K split is a small-grid measure); asked without a device it assumes 256 CUs.
- * Behind those: 528 words per layer for the wide persistent kernels' tile deal (one ticket counter per XCD + one mailbox per
- * workgroup, k_mfma16x.hip DealX), which sicn_net_forward zeroes itself (one small kernel at the head of the call).  A workspace
+/* Bytes of DEVICE scratch `sicn_net_forward` needs for a batch of n_images: two ping-pong activation buffers (library 0.2 also
+ * reserved room there for the K split when sicn_options.split_k > 1 was set; the K split was removed, and no device is needed
+ * to ask).  Behind the buffers: 528 words per layer for the wide persistent kernels' tile deal (one ticket counter per XCD + one
+ * mailbox per workgroup, k_mfma16x.hip DealX), which sicn_net_forward zeroes itself (one small kernel at the head of the call).  A workspace
  * without room for them (a size computed by library 0.2) still works: those kernels then deal all their tiles statically.
  * Like the ping-pong buffers, a workspace serves ONE call in flight at a time. */
 size_t sicn_net_workspace_bytes(const sicn_net *net, int n_images);

@@ -54,9 +54,8 @@ int sicn_deconv522_gdn(const sicn_layer_desc *desc, const sicn_weights *w, const
                        uint8_t *out_nhwc, int n_images, const sicn_options *opt, void *hip_stream);
 
 /* A chain whose layer i uses gdn[i] (NULL entries: the reference ReLU); gdn[i]'s channel count must equal
- * descs[i].OFM_CH.  The net keeps references to the activations (caller keeps them alive).  With sicn_options.gdn_fuse = 2 an
- * intermediate layer's activation may be applied by the NEXT layer's kernel on the way in (128 channels -> RGB); a tapped layer's
- * output and the chain's last output are always the activated bytes. */
+ * descs[i].OFM_CH.  The net keeps references to the activations (caller keeps them alive).  A tapped layer's output and the
+ * chain's last output are always the activated bytes. */
 int sicn_net_create_gdn(const sicn_layer_desc *descs, sicn_weights *const *weights, const sicn_gdn *const *gdn,
                         int n_layers, const sicn_options *opt, sicn_net **out);
 

@@ -1,4 +1,4 @@
-// Device-side helpers shared by the MFMA kernels (k_mfma.hip, k_rgb.hip).
+// Device-side helpers shared by the MFMA kernels (k_mfma16*.hip, k_rgb.hip, k_l0g.hip, k_gdn.hip).
 #pragma once
 #include "sicn_internal.h"
 #include "sicn_plan.h"

@@ -1,4 +1,4 @@
-// Layer 0 (RGB -> channels): the RGBX patch geometry and the raw-rows -> patch expansion shared by k_rgb.hip (k_l0, k_l0p) and
+// Layer 0 (RGB -> channels): the RGBX patch geometry and the raw-rows -> patch expansion shared by k_rgb.hip (k_l0) and
 // k_l0g.hip (layer 0 with the GDN applied before its one store).
 #pragma once
 #include "k_common.hpp"
@@ -30,10 +30,6 @@ constexpr int L0_RAW_BYTES = (L0_RAW_ROWS * L0_RAW_DW * 4 + 12 + 255) / 256 * 25
 // bytes into dwords 3g .. 3g+3 of the raw row (sh = byte phase of the row's first dword),
 // re-aligned in registers; pixels outside the image become 0 (the raw row holds the neighbouring
 // row's bytes there).  `raw` points at the raw row of patch row 0.
-// ASM_STORE (k_l0p): the patch store is an asm statement.  With LDS-DMA in flight (the next run's raw rows) hipcc orders every LDS
-// store it knows about behind the pending DMA with an s_waitcnt vmcnt(0) — which is also a wait for the tile's output stores; an
-// asm store it does not track, and the barrier that publishes the patch waits for lgkmcnt(0) anyway.
-template <bool ASM_STORE = false>
 __device__ __forceinline__ void l0_expand(const uint8_t *raw, uint8_t *patch, int img_byte0, int quad, int Y0, int X0,
                                           int IW, int IH)
 {
@@ -52,12 +48,7 @@ __device__ __forceinline__ void l0_expand(const uint8_t *raw, uint8_t *patch, in
     v.y = (row_ok && ix0 + 1 >= 0 && ix0 + 1 < IW) ? (__builtin_amdgcn_alignbyte(w1, w0, 3) & 0xFFFFFFu) : 0u;
     v.z = (row_ok && ix0 + 2 >= 0 && ix0 + 2 < IW) ? (__builtin_amdgcn_alignbyte(w2, w1, 2) & 0xFFFFFFu) : 0u;
     v.w = (row_ok && ix0 + 3 >= 0 && ix0 + 3 < IW) ? (w2 >> 8) : 0u;
-    if constexpr (ASM_STORE) {
-        const uint32_t a = (uint32_t)(uintptr_t)LDS_PTR(patch + quad * 16);
-        const v4i d = {(int)v.x, (int)v.y, (int)v.z, (int)v.w};
-        asm volatile("ds_write_b128 %0, %1" ::"v"(a), "v"(d) : "memory");
-    } else
-        *(uint4 *)(patch + quad * 16) = v;
+    *(uint4 *)(patch + quad * 16) = v;
 }
 
 }  // namespace sicn

@@ -1,11 +1,11 @@
 // conv2d<> / deconv522<> implicit GEMM on v_mfma_i32_16x16x64_i8 — same decomposition, LDS patch,
-// weight ring and layouts as k_mfma.hip (read its header first), different MFMA shape.
+// weight ring and layouts as the first, 32x32x32 kernels (removed in 0.3.x; see the git history of k_mfma.hip), different MFMA shape.
 //
 // Why: on this power-limited chip the 32x32x32 int8 MFMA loop tops out at ~2.93 POP/s and the
 // 16x16x64 loop at ~3.45 POP/s with identical LDS traffic per MAC (tools/microbench/mfma_shape.hip,
-// profiles/r01_microbench_mfma_shape.txt); k_mfma.hip already sits on the 32x32x32 ceiling.
+// profiles/r01_microbench_mfma_shape.txt); the 32x32x32 kernels sat on that ceiling.
 //
-// One "pass" = TWO K steps of k_mfma.hip (2 x 32 channel bytes = the 64-deep K of the instruction):
+// One "pass" = TWO K steps of 32 channel bytes (= the 64-deep K of the instruction):
 // lanes 0..31 (K bytes 0..31 of the MFMA) read step A's operands, lanes 32..63 step B's.
 //   conv  : A, B = two consecutive taps of the plane-ordered walk (possibly two different planes)
 //   deconv: A, B = channel groups q, q+1 of the same tap
@@ -18,7 +18,7 @@
 // C/D layout (col = l & 15 = position, row = 4g + r): weight row (4g + r) of tile j holds channel
 // 64*(j>>2) + 16g + 4*(j&3) + r, so the four accumulators of tiles 4J..4J+3 of a lane are 16
 // consecutive channels of one pixel: one 16-byte store per (column tile, J), no transpose.
-// A barrier per pass (not per step) halves the barrier count of k_mfma.hip.
+// A barrier per pass (not per step) halves the barrier count of the 32x32x32 form.
 #include <cstdlib>
 
 #include "k_common.hpp"
@@ -403,7 +403,7 @@ MfmaPlan plan_mfma(const LayerGeom &g, int n_images, const sicn_options &o, cons
     const bool deconv = g.transposed != 0;
     const int nq = g.CIN / 32, nt16 = g.COUT / 16;
     const int MW = deconv ? g.IW : g.OW, MH = deconv ? g.IH : g.OH;
-    MfmaPlan p{0, 32, 1, 1, 0, 1, 1};
+    MfmaPlan p{0, 32, 1, 0, 1, 1, 0};
     if (wide_supported(g) && o.tile_x != 16) {
         const long tiles_w = (long)((MW + 31) / 32) * ((MH + 15) / 16) * n_images;
         // measured r03 (tools/ab_options.py, 1080p x 4 and 4K x 1 = 1020 tiles of 256 CUs): layer 1 131 - 140 against 144 - 149 us;
@@ -430,14 +430,7 @@ MfmaPlan plan_mfma(const LayerGeom &g, int n_images, const sicn_options &o, cons
         // grids that leave half of the CUs without a workgroup: split the output channels over 2 / 3 workgroups
         // (measured, r02: at 192 - 255 tiles the split is a wash or a loss; at <= 72 it takes 20 - 35 % off the layer)
         if (p.tile_x == 16 && (o.split_n > 1 || (o.split_n == 0 && split_n_automatic(tiles, chip)))) p.split_n = nt16 / 4;
-        // ... and the ones that are still small then: split K as well (round 4; only the channel-split 8 x 16 kernels have the form)
-        if (p.split_n > 1) {
-            const size_t out_bytes = (size_t)g.OH * g.OW * g.COUT * n_images;
-            int ks = o.split_k > 1 ? nq / 2 : (o.split_k == 0 ? split_k_automatic(tiles * p.split_n, nq, deconv, out_bytes, chip) : 1);
-            p.split_k = ks;
-        }
         p.grid_y = p.split_n;
-        p.grid_z = p.split_k;
     }
     return p;
 }
@@ -445,16 +438,15 @@ MfmaPlan plan_mfma(const LayerGeom &g, int n_images, const sicn_options &o, cons
 template <int NQ, int NT16, bool DECONV>
 static hipError_t launch16(const LayerGeom &g, const sicn_weights &w, const uint8_t *in, uint8_t *out, int n_images,
                            hipStream_t stream, int in_layout, int out_layout, const sicn_options &o, const ChipGeom &chip, bool relu,
-                           const KSplitScratch *ks)
+                           unsigned long long *deal)
 {
-    MfmaPlan p = plan_mfma(g, n_images, o, chip);
-    if (p.family == 2) return launch_wide(g, w, in, out, n_images, stream, in_layout, out_layout, relu, o.persistent_grid, chip, ks ? ks->deal : nullptr);
+    const MfmaPlan p = plan_mfma(g, n_images, o, chip);
+    if (p.family == 2) return launch_wide(g, w, in, out, n_images, stream, in_layout, out_layout, relu, o.persistent_grid, chip, deal);
     if (p.family == 1) {
         // (round 2 sent the deconv 192 -> 128 on full grids back to the plain kernel: the pipelined one was 7 % slower there.  The
         // reason was the v_mov copies hipcc made for its run-time buffer parity — right around the asm MFMAs, where
         // tools/isa_hazards.py found them; with the parity static the pipelined form is 17 % FASTER: layer 4 0.158 -> 0.131 ms.)
-        if (p.split_k > 1 && !ksplit_scratch_fits(g, n_images, p, ks)) p.split_k = 1;   // no scratch (single-layer entry points): unsplit
-        return launch_pipelined(g, w, in, out, n_images, stream, in_layout, out_layout, relu, p.tile_x, p.split_n > 1, chip, p.split_k, ks);
+        return launch_pipelined(g, w, in, out, n_images, stream, in_layout, out_layout, relu, p.tile_x, p.split_n > 1, chip);
     }
     return p.tile_x == 16 ? launch16_tx<NQ, NT16, DECONV, 16>(g, w, in, out, n_images, stream, in_layout, out_layout, relu, chip)
                           : launch16_tx<NQ, NT16, DECONV, 32>(g, w, in, out, n_images, stream, in_layout, out_layout, relu, chip);
@@ -469,23 +461,23 @@ bool mfma_supported(int cin, int cout, int transposed)
 
 hipError_t launch_mfma16(const LayerGeom &g, const sicn_weights &w, const uint8_t *in, uint8_t *out, int n_images,
                          hipStream_t stream, int in_layout, int out_layout, const sicn_options &o, const ChipGeom &chip, bool relu,
-                         const KSplitScratch *ks)
+                         unsigned long long *deal)
 {
     if ((size_t)g.IH * g.IW * g.CIN >= (size_t)OOB) return hipErrorInvalidValue;          // 31-bit patch offsets
     if ((size_t)g.OH * g.OW * g.COUT >= (size_t)OOB) return hipErrorInvalidValue;         // buffer-descriptor stores
     if (g.transposed) {
-        if (g.CIN == 128 && g.COUT == 128) return launch16<4, 8, true>(g, w, in, out, n_images, stream, in_layout, out_layout, o, chip, relu, ks);
-        if (g.CIN == 192 && g.COUT == 128) return launch16<6, 8, true>(g, w, in, out, n_images, stream, in_layout, out_layout, o, chip, relu, ks);
-        if (g.CIN == 128 && g.COUT == 192) return launch16<4, 12, true>(g, w, in, out, n_images, stream, in_layout, out_layout, o, chip, relu, ks);
+        if (g.CIN == 128 && g.COUT == 128) return launch16<4, 8, true>(g, w, in, out, n_images, stream, in_layout, out_layout, o, chip, relu, deal);
+        if (g.CIN == 192 && g.COUT == 128) return launch16<6, 8, true>(g, w, in, out, n_images, stream, in_layout, out_layout, o, chip, relu, deal);
+        if (g.CIN == 128 && g.COUT == 192) return launch16<4, 12, true>(g, w, in, out, n_images, stream, in_layout, out_layout, o, chip, relu, deal);
     } else {
-        if (g.CIN == 192 && g.COUT == 128) return launch16<6, 8, false>(g, w, in, out, n_images, stream, in_layout, out_layout, o, chip, relu, ks);
-        if (g.CIN == 128 && g.COUT == 128) return launch16<4, 8, false>(g, w, in, out, n_images, stream, in_layout, out_layout, o, chip, relu, ks);
-        if (g.CIN == 128 && g.COUT == 192) return launch16<4, 12, false>(g, w, in, out, n_images, stream, in_layout, out_layout, o, chip, relu, ks);
+        if (g.CIN == 192 && g.COUT == 128) return launch16<6, 8, false>(g, w, in, out, n_images, stream, in_layout, out_layout, o, chip, relu, deal);
+        if (g.CIN == 128 && g.COUT == 128) return launch16<4, 8, false>(g, w, in, out, n_images, stream, in_layout, out_layout, o, chip, relu, deal);
+        if (g.CIN == 128 && g.COUT == 192) return launch16<4, 12, false>(g, w, in, out, n_images, stream, in_layout, out_layout, o, chip, relu, deal);
     }
     return hipErrorInvalidValue;
 }
 
-// ---- host-side weight packing: the same tile sequence as pack_mfma_stream, rows in the 16x16 C/D
+// ---- host-side weight packing: the tile sequence of the 32x32x32 form, rows in the 16x16 C/D
 // ---- order (LDS row j*16 + rho holds channel 64*(j>>2) + 16*(rho>>2) + 4*(j&3) + (rho&3)), no swizzle
 // zero tiles behind the stream: the deepest prefetch of any kernel that walks it (k_mfma16: PF16 = 6, k_mfma16w: 8, k_mfma16p: 12)
 constexpr int PAD16 = 24;

@@ -9,7 +9,6 @@
 #include <memory>
 #include <mutex>
 #include <new>
-#include <random>
 #include <vector>
 
 #include "sicn_gdn_internal.h"
@@ -49,26 +48,17 @@ const sicn_options &default_options()
             fprintf(stderr, "libsicn: ignoring out-of-range %s=%d\n", name, (int)v);
             v = 0;
         };
-        if (d.mfma_shape != 0 && d.mfma_shape != 16 && d.mfma_shape != 32) bad("SICN_MFMA_SHAPE", d.mfma_shape);
-#ifndef SICN_ALT_KERNELS
-        if (d.mfma_shape == 32) bad("SICN_MFMA_SHAPE", d.mfma_shape);
-#endif
+        if (d.mfma_shape != 0 && d.mfma_shape != 16) bad("SICN_MFMA_SHAPE", d.mfma_shape);
         if (d.tile_x != 0 && d.tile_x != 16 && d.tile_x != 32) bad("SICN_TILE_X", d.tile_x);
         if (d.strip_chunks < 0) bad("SICN_STRIP_CHUNKS", d.strip_chunks);
         if (d.no_phase_layout < 0 || d.no_phase_layout > 2) bad("SICN_NO_PHASE_LAYOUT", d.no_phase_layout);
         if (d.split_n < 0 || d.split_n > 4) bad("SICN_SPLIT_N", d.split_n);
         if (d.wave_tile != 0 && d.wave_tile != 64 && d.wave_tile != 128) bad("SICN_WAVE_TILE", d.wave_tile);
         if (d.prefetch < 0 || d.prefetch > 3) bad("SICN_PREFETCH", d.prefetch);
-        if (d.split_k < 0 || d.split_k > 4) bad("SICN_SPLIT_K", d.split_k);
-        if (d.l7_loader < 0 || d.l7_loader > 2) bad("SICN_L7_LOADER", d.l7_loader);
-        if (d.l0_form < 0 || d.l0_form > 2) bad("SICN_L0_FORM", d.l0_form);
-        if (d.gdn_fuse < 0 || d.gdn_fuse > 2) bad("SICN_GDN_FUSE", d.gdn_fuse);
-#ifndef SICN_ALT_KERNELS   // forms that measured a loss live in the ALT build only
-        if (d.split_k > 1) bad("SICN_SPLIT_K", d.split_k);
-        if (d.l7_loader == 2) bad("SICN_L7_LOADER", d.l7_loader);
-        if (d.l0_form == 2) bad("SICN_L0_FORM", d.l0_form);
-        if (d.gdn_fuse == 2) bad("SICN_GDN_FUSE", d.gdn_fuse);
-#endif
+        if (d.split_k < 0 || d.split_k > 1) bad("SICN_SPLIT_K", d.split_k);
+        if (d.l7_loader < 0 || d.l7_loader > 1) bad("SICN_L7_LOADER", d.l7_loader);
+        if (d.l0_form < 0 || d.l0_form > 1) bad("SICN_L0_FORM", d.l0_form);
+        if (d.gdn_fuse < 0 || d.gdn_fuse > 1) bad("SICN_GDN_FUSE", d.gdn_fuse);
         return d;
     }();
     return o;
@@ -102,7 +92,7 @@ int chip_geom(ChipGeom *out)
 
 const DebugEnv &debug_env()
 {
-    static const DebugEnv d{env_int("SICN_MFMA_VARIANT"), env_int("SICN_DEBUG_KERNEL"), env_int("SICN_DEBUG_EXTRA_LDS"), env_int("SICN_NO_DEAL")};
+    static const DebugEnv d{env_int("SICN_NO_DEAL")};
     return d;
 }
 }  // namespace sicn
@@ -117,23 +107,16 @@ static int resolve_options(const sicn_options *in, sicn_options *out)
     std::memset(&o, 0, sizeof o);
     std::memcpy(&o, in, (size_t)in->struct_bytes);
     o.struct_bytes = (int32_t)sizeof(sicn_options);
-    if (o.mfma_shape != 0 && o.mfma_shape != 16 && o.mfma_shape != 32) return SICN_EINVAL;
-#ifndef SICN_ALT_KERNELS
-    if (o.mfma_shape == 32) return SICN_EINVAL;   // the 32x32x32 family lives in the ALT build only (libsicn_alt.so)
-#endif
+    if (o.mfma_shape != 0 && o.mfma_shape != 16) return SICN_EINVAL;
     if (o.tile_x != 0 && o.tile_x != 16 && o.tile_x != 32) return SICN_EINVAL;
     if (o.strip_chunks < 0 || o.no_phase_layout < 0 || o.no_phase_layout > 2) return SICN_EINVAL;
     if (o.split_n < 0 || o.split_n > 4) return SICN_EINVAL;
     if (o.wave_tile != 0 && o.wave_tile != 64 && o.wave_tile != 128) return SICN_EINVAL;
     if (o.prefetch < 0 || o.prefetch > 3 || o.persistent_grid < 0) return SICN_EINVAL;
-    if (o.split_k < 0 || o.split_k > 4 || o.l7_loader < 0 || o.l7_loader > 2 || o.l0_form < 0 || o.l0_form > 2 || o.gdn_fuse < 0 ||
-        o.gdn_fuse > 2)
+    // the forms that took split_k > 1, l7_loader / l0_form / gdn_fuse = 2 and mfma_shape = 32 were removed (include/sicn.h)
+    if (o.split_k < 0 || o.split_k > 1 || o.l7_loader < 0 || o.l7_loader > 1 || o.l0_form < 0 || o.l0_form > 1 || o.gdn_fuse < 0 ||
+        o.gdn_fuse > 1)
         return SICN_EINVAL;
-#ifndef SICN_ALT_KERNELS
-    // k_l0p, k_l7s, k_l7g and the K split measured a loss against the defaults: they are built into
-    // libsicn_alt.so only, where their parity tests run (tests/alt_kernels_check.py)
-    if (o.split_k > 1 || o.l7_loader == 2 || o.l0_form == 2 || o.gdn_fuse == 2) return SICN_EINVAL;
-#endif
     *out = o;
     return SICN_OK;
 }
@@ -149,14 +132,7 @@ extern "C" void sicn_options_init(sicn_options *opt)
 extern "C" int sicn_version(void) { return 1000 * 0 + 3; }
 extern "C" int sicn_gdn_spec_version(void) { return 2; }
 
-extern "C" int sicn_has_alt_kernels(void)
-{
-#ifdef SICN_ALT_KERNELS
-    return 1;
-#else
-    return 0;
-#endif
-}
+extern "C" int sicn_has_alt_kernels(void) { return 0; }   // kept for callers that probe it: the alternate kernel build is gone
 
 extern "C" const char *sicn_strerror(int code)
 {
@@ -235,7 +211,6 @@ extern "C" void sicn_weights_free(sicn_weights *w)
     if (!w) return;
     if (w->d_w_okc) (void)hipFree(w->d_w_okc);
     if (w->d_bias) (void)hipFree(w->d_bias);
-    if (w->d_w_mfma) (void)hipFree(w->d_w_mfma);
     if (w->d_w_mfma16) (void)hipFree(w->d_w_mfma16);
     if (w->d_w_mfma16x) (void)hipFree(w->d_w_mfma16x);
     if (w->d_w_l0) (void)hipFree(w->d_w_l0);
@@ -292,19 +267,9 @@ extern "C" int sicn_weights_from_finn_tiles(const sicn_layer_desc *d, const void
     }
     try {
         if (ok && mfma_supported(cin, cout, d->transposed)) {
-#ifdef SICN_ALT_KERNELS
-            if (mfma32_supported(cin, cout, d->transposed)) {   // second implementation (sicn_options.mfma_shape = 32), ALT build only
-                std::vector<int8_t> s(mfma_stream_bytes(cin, cout));
-                pack_mfma_stream(w_okc.data(), cin, cout, d->transposed, s.data());
-                w->mfma_steps = mfma_stream_steps(cin);
-                ok = upload(s.data(), s.size(), &w->d_w_mfma);
-            }
-#endif
-            if (ok) {
-                std::vector<int8_t> s16(mfma16_stream_bytes(cin, cout));
-                pack_mfma16_stream(w_okc.data(), cin, cout, d->transposed, s16.data());
-                ok = upload(s16.data(), s16.size(), &w->d_w_mfma16);
-            }
+            std::vector<int8_t> s16(mfma16_stream_bytes(cin, cout));
+            pack_mfma16_stream(w_okc.data(), cin, cout, d->transposed, s16.data());
+            ok = upload(s16.data(), s16.size(), &w->d_w_mfma16);
             if (ok && d->transposed && mfma16x_deconv_stream_bytes(cin, cout)) {   // the wide persistent deconv walks the taps in its own order
                 std::vector<int8_t> sx(mfma16x_deconv_stream_bytes(cin, cout));
                 pack_mfma16x_deconv_stream(w_okc.data(), cin, cout, sx.data());
@@ -361,12 +326,11 @@ static int link_layout(const sicn_layer_desc &p, const sicn_layer_desc &c, const
 }
 
 // gdn != nullptr: the layer stores its lanes BEFORE the sign-bit ReLU and the GDN / IGDN kernel then rewrites them in
-// place, in whatever layout the layer wrote (include/sicn_gdn.h; extension beyond the reference).  defer_gdn: the rewrite is
-// left to the NEXT layer of a chain, which gets this layer's activation as its in_gdn (sicn_net_forward decides).
+// place, in whatever layout the layer wrote (include/sicn_gdn.h; extension beyond the reference).  deal: the layer's tile-deal
+// words in the workspace of a chain (launch_mfma16), or nullptr.
 static int run_layer(const sicn_layer_desc *d, const sicn_weights *w, const uint8_t *in, uint8_t *out,
                      int n_images, hipStream_t stream, int want_transposed, const sicn_options &o, int in_layout = 0,
-                     int out_layout = 0, const sicn_gdn *gdn = nullptr, const KSplitScratch *ks = nullptr, bool defer_gdn = false,
-                     const sicn_gdn *in_gdn = nullptr)
+                     int out_layout = 0, const sicn_gdn *gdn = nullptr, unsigned long long *deal = nullptr)
 {
     int rc = sicn_validate_desc(d);
     if (rc) return rc;
@@ -378,7 +342,6 @@ static int run_layer(const sicn_layer_desc *d, const sicn_weights *w, const uint
     if (gdn && gdn->channels != d->OFM_CH) return SICN_EINVAL;
     const LayerGeom g = geom_of(*d);
     const bool relu = gdn == nullptr;
-    if (in_gdn && layer_kernel(*d, o, gdn != nullptr) != KK_L7_RGB) return SICN_EINVAL;   // only that kernel takes one — checked BEFORE anything is enqueued
     ChipGeom chip;
     if ((rc = chip_geom(&chip)) != SICN_OK) return rc;   // no device, or not a gfx950 one
     hipError_t e;
@@ -393,32 +356,15 @@ static int run_layer(const sicn_layer_desc *d, const sicn_weights *w, const uint
         e = launch_l0(g, *w, in, out, n_images, stream, out_layout, o, chip, relu);
         break;
     case KK_L7_RGB:
-        // in_gdn: the input holds the previous layer's pre-activation lanes, its activation is applied on the way in (k_l7g.hip)
-#ifdef SICN_ALT_KERNELS
-        if (in_gdn) {
-            e = launch_l7_gdn(g, *w, *in_gdn, in, out, n_images, stream, in_layout, o, chip);
-            break;
-        }
-#else
-        if (in_gdn) return SICN_EINVAL;   // k_l7g: ALT build only (gdn_fuse = 2 is rejected, so no chain ever defers an activation)
-#endif
         e = launch_l7(g, *w, in, out, n_images, stream, in_layout, o, chip);
         break;
     case KK_MFMA_CONV:
     case KK_MFMA_DECONV:
-        // MFMA shape: 16x16x64 by default (higher sustained clock, k_mfma16.hip); mfma_shape = 32 selects
-        // the 32x32x32 kernels of k_mfma.hip (a second implementation kept under test; reference shapes, ReLU only)
-#ifdef SICN_ALT_KERNELS
-        if (o.mfma_shape == 32 && relu && mfma32_supported(d->IFM_CH, d->OFM_CH, d->transposed)) {
-            e = launch_mfma(g, *w, in, out, n_images, stream, in_layout, out_layout);
-            break;
-        }
-#endif
-        e = launch_mfma16(g, *w, in, out, n_images, stream, in_layout, out_layout, o, chip, relu, ks);
+        e = launch_mfma16(g, *w, in, out, n_images, stream, in_layout, out_layout, o, chip, relu, deal);
         break;
     default: e = launch_generic(g, *w, in, out, n_images, stream, relu); break;
     }
-    if (e == hipSuccess && gdn && !defer_gdn) e = launch_gdn(*gdn, out, out_layout, d->OFM_ROW, d->OFM_COL, n_images, stream);
+    if (e == hipSuccess && gdn) e = launch_gdn(*gdn, out, out_layout, d->OFM_ROW, d->OFM_COL, n_images, stream);
     if (e == hipErrorInvalidValue) return SICN_EINVAL;
     return e == hipSuccess ? SICN_OK : SICN_ENODEV;
 }
@@ -457,7 +403,6 @@ struct sicn_net {
     std::vector<const sicn_weights *> weights;
     std::vector<const sicn_gdn *> gdn;         // per layer, nullptr = the reference's ReLU
     sicn_options opt;                          // fixed at creation
-    unsigned long long ks_tag;                 // K-split arrival words of this net carry this random tag (k_mfma16p.hip); low byte 0
     // profiling: the only state a launch changes.  One flat ring of event pairs; a forward call reserves the
     // slots of its layers with one atomic fetch_add, so calls on several streams / threads never share a slot.
     static constexpr int EV_RING = 8192;
@@ -511,10 +456,6 @@ extern "C" int sicn_net_create_gdn(const sicn_layer_desc *descs, sicn_weights *c
         net->gdn.assign((size_t)n_layers, nullptr);
         if (gdn) net->gdn.assign(gdn, gdn + n_layers);
         net->opt = o;
-        std::random_device rd;
-        do {
-            net->ks_tag = (((unsigned long long)rd() << 32) | (unsigned long long)rd()) & ~0xffull;
-        } while (net->ks_tag == 0);
     } catch (const std::exception &) {
         delete net;
         return SICN_ENOMEM;
@@ -539,50 +480,13 @@ static size_t pingpong_slot_bytes(const sicn_net *net, int n_images)
     return align256(mx * (size_t)n_images);
 }
 
-// K-split scratch behind the ping-pong buffers (k_mfma16p.hip): KSPLIT_MAX partial tensors of the largest output any layer of the
-// chain would compute K-split on this chip, and one arrival word per workgroup of the largest such grid.  Small by construction:
-// the split is only taken by grids of at most half a workgroup per CU.
-struct KsNeed { size_t partial, words; };
-static KsNeed ksplit_need(const sicn_net *net, int n_images, const ChipGeom &chip)
-{
-    KsNeed n{0, 0};
-    for (size_t l = 0; l < net->descs.size(); l++) {
-        const sicn_layer_desc &d = net->descs[l];
-        const KernelKind k = pick_kernel(d, net->opt);
-        if (k != KK_MFMA_CONV && k != KK_MFMA_DECONV) continue;
-        const MfmaPlan p = plan_mfma(geom_of(d), n_images, net->opt, chip);
-        if (p.split_k <= 1) continue;
-        const size_t ob = align256(out_bytes(d) * (size_t)n_images), words = (size_t)p.grid_x * p.grid_y;
-        n.partial = n.partial > ob ? n.partial : ob;
-        n.words = n.words > words ? n.words : words;
-    }
-    return n;
-}
-static ChipGeom chip_or_default()
-{
-    ChipGeom c;
-    return chip_geom(&c) == SICN_OK ? c : chip_from_cus(256);   // sizes can be asked for without a device: the whole MI355X
-}
-
-// round 5: the wide persistent kernels' tile deal (k_mfma16x.hip: DealX) — DEAL_WORDS zeroed words per layer, behind everything else
+// round 5: the wide persistent kernels' tile deal (k_mfma16x.hip: DealX) — DEAL_WORDS zeroed words per layer, behind the ping-pong buffers
 static size_t deal_bytes(const sicn_net *net) { return align256(net->descs.size() * (size_t)DEAL_WORDS * sizeof(unsigned long long)); }
 
 extern "C" size_t sicn_net_workspace_bytes(const sicn_net *net, int n_images)
 {
     if (!net || n_images <= 0) return 0;
-    const KsNeed ks = ksplit_need(net, n_images, chip_or_default());
-    return 2 * pingpong_slot_bytes(net, n_images) + KSPLIT_MAX * ks.partial + align256(ks.words * sizeof(unsigned long long)) + deal_bytes(net);
-}
-
-// Layer l's GDN / IGDN is applied by layer l + 1's kernel (k_l7g.hip) instead of k_gdn (sicn_options.gdn_fuse = 2): l + 1 is part of this call, takes the RGB
-// deconv kernel, has no activation of its own, and layer l's output is an intermediate nobody else reads.
-static bool gdn_moves_to_next(const sicn_net *net, int l, int last, int tap_layer)
-{
-    if (l >= last || l == tap_layer || !net->gdn[l] || net->gdn[l + 1]) return false;
-    if (net->opt.gdn_fuse != 2) return false;   // measured: no gain over k_gdn + k_l7 (k_l7g.hip), so only on request
-    const sicn_gdn *g = net->gdn[l];
-    return layer_kernel(net->descs[l + 1], net->opt, false) == KK_L7_RGB && g->channels == 128 && g->d_gamma_mfma != nullptr &&
-           net->weights[l + 1]->d_w_l7 != nullptr;
+    return 2 * pingpong_slot_bytes(net, n_images) + deal_bytes(net);
 }
 
 extern "C" int sicn_net_forward(const sicn_net *net, int first, int last, const uint8_t *in, uint8_t *out,
@@ -598,37 +502,20 @@ extern "C" int sicn_net_forward(const sicn_net *net, int first, int last, const 
     if (last > first && (!workspace || workspace_bytes < 2 * slot)) return SICN_ENOSPC;
     hipStream_t stream = (hipStream_t)hip_stream;
     uint8_t *pp[2] = {(uint8_t *)workspace, (uint8_t *)workspace + slot};
-    // K-split scratch: behind the ping-pong buffers when the workspace is of the size sicn_net_workspace_bytes asks for.  A smaller
-    // (older-sized) or absent workspace only switches the automatic split off; a forced one (options.split_k > 1) is SICN_ENOSPC.
-    KSplitScratch ks_store{nullptr, 0, nullptr, 0, net->ks_tag, nullptr};
-    const KSplitScratch *ks = nullptr;
     unsigned long long *deal_base = nullptr;   // the tile-deal words of this call's layers, zeroed below (a smaller / absent workspace: static deal)
     {
         ChipGeom chip;
         if (int rc = chip_geom(&chip)) return rc;
-        const KsNeed need = ksplit_need(net, n_images, chip);
-        const size_t ks_total = 2 * slot + KSPLIT_MAX * need.partial + align256(need.words * sizeof(unsigned long long));
-        if (need.partial) {
-            if (workspace && workspace_bytes >= ks_total) {
-                ks_store.partials = (uint8_t *)workspace + 2 * slot;
-                ks_store.partial_stride = need.partial;
-                ks_store.flags = (unsigned long long *)((uint8_t *)workspace + 2 * slot + KSPLIT_MAX * need.partial);
-                ks_store.n_flags = need.words;
-                ks = &ks_store;
-            } else if (net->opt.split_k > 1)
-                return SICN_ENOSPC;
-        }
         // does a layer of this call deal tiles dynamically?  (small inputs never do: no zeroing launch in front of them)
         bool any_deal = false;
         for (int l = first; l <= last && !any_deal; l++) {
             const KernelKind k = pick_kernel(net->descs[l], net->opt);
             any_deal = (k == KK_MFMA_CONV || k == KK_MFMA_DECONV) && plan_mfma(geom_of(net->descs[l]), n_images, net->opt, chip).deal;
         }
-        if (any_deal && workspace && workspace_bytes >= ks_total + deal_bytes(net) && !debug_env().no_deal) {
-            deal_base = (unsigned long long *)((uint8_t *)workspace + ks_total);
+        if (any_deal && workspace && workspace_bytes >= 2 * slot + deal_bytes(net) && !debug_env().no_deal) {
+            deal_base = (unsigned long long *)((uint8_t *)workspace + 2 * slot);
             // zeroed once per forward pass, by a kernel; every layer of the call gets its own DEAL_WORDS
             if (launch_zero_words(deal_base, deal_bytes(net) / sizeof(unsigned long long), stream) != hipSuccess) return SICN_ENODEV;
-            ks = &ks_store;
         }
     }
     const uint8_t *cur = in;
@@ -640,7 +527,6 @@ extern "C" int sicn_net_forward(const sicn_net *net, int first, int last, const 
         const int at = net->ev_next.fetch_add(need, std::memory_order_relaxed);
         if (at + need <= sicn_net::EV_RING) slot0 = at;   // ring full: this call is not timed
     }
-    const sicn_gdn *deferred = nullptr;    // the previous layer's activation, when it is this layer's to apply
     for (int l = first; l <= last; l++) {
         // a tapped layer (the latent) is written straight into the caller's buffer and the next layer reads it there: no copy
         // (round 3 copied it device-to-device behind the layer: 4.8 us per forward pass on small inputs, 15 us on 8 x 4K)
@@ -654,13 +540,8 @@ extern "C" int sicn_net_forward(const sicn_net *net, int first, int last, const 
             net->ev_layer[slot].store(-1, std::memory_order_relaxed);   // becomes l once both events are recorded
             if (hipEventRecord(net->ev_begin[slot], stream) != hipSuccess) return SICN_ENODEV;
         }
-        // the activation of layer l moves into layer l + 1's kernel where that kernel exists (128 channels -> RGB, k_l7g) and nobody
-        // else sees layer l's output: the activated tensor is then never written
-        const bool defer = gdn_moves_to_next(net, l, last, tap_layer);
-        ks_store.deal = deal_base ? deal_base + (size_t)l * DEAL_WORDS : nullptr;
         int rc = run_layer(&net->descs[l], net->weights[l], cur, dst, n_images, stream, -1, net->opt, cur_layout, out_layout,
-                           net->gdn[l], ks, defer, deferred);
-        deferred = defer ? net->gdn[l] : nullptr;
+                           net->gdn[l], deal_base ? deal_base + (size_t)l * DEAL_WORDS : nullptr);
         if (rc) return rc;
         if (slot >= 0) {
             if (hipEventRecord(net->ev_end[slot], stream) != hipSuccess) return SICN_ENODEV;
@@ -772,13 +653,9 @@ extern "C" int sicn_debug_plan(const sicn_layer_desc *d, int n_images, const sic
     out[2] = (int)k;
     if (k == KK_MFMA_CONV || k == KK_MFMA_DECONV) {
         const MfmaPlan p = plan_mfma(g, n_images, o, chip);
-        out[3] = p.family; out[4] = p.tile_x; out[5] = p.split_n; out[6] = p.split_k;
+        out[3] = p.family; out[4] = p.tile_x; out[5] = p.split_n; out[6] = 1;   // out[6]: the K split, removed in 0.3.x
         out[7] = (int)p.grid_x; out[8] = (int)p.grid_y; out[9] = (int)p.grid_z;
         out[10] = p.deal;
-    } else if (k == KK_L7_RGB && o.gdn_fuse == 2) {   // as the layer runs behind a layer with an activation in a chain (k_l7g)
-        const int tiles_x = (g.IW + L7G_PLAN_COLS - 1) / L7G_PLAN_COLS, steps_y = (g.IH + L7G_PLAN_ROWS - 1) / L7G_PLAN_ROWS;
-        const int yc = l7g_chunks(tiles_x, n_images, steps_y, o.strip_chunks, 1, chip);
-        out[7] = tiles_x * yc * n_images; out[8] = 1; out[9] = 1; out[10] = yc; out[11] = (steps_y + yc - 1) / yc;
     } else if (k == KK_L7_RGB) {
         const int tiles_x = (g.IW + 31) / 32, steps_y = (g.IH + 3) / 4;
         const int yc = l7_chunks(tiles_x, n_images, steps_y, o.strip_chunks, chip);

@@ -74,19 +74,6 @@ inline bool wide_automatic(long tiles_w, bool deconv, const ChipGeom &c)
 inline bool narrow_tile_wanted(long tiles32, const ChipGeom &c) { return tiles32 * 16 < 13L * 2 * c.n_cu; }
 // output-channel split of the 8 x 16 kernels: grids that leave half of the CUs without a workgroup (measured r02: <= 128 of 256)
 inline bool split_n_automatic(long tiles16, const ChipGeom &c) { return tiles16 * 2 <= c.n_cu; }
-// K split (input-channel group pairs over workgroups of blockIdx.z; every slice stores its partial output bytes, the last one to
-// arrive adds them mod 256 and applies the activation — k_mfma16p.hip).  Built in round 4 for grids that, even after the
-// output-channel split, leave most CUs idle — and MEASURED A LOSS on this chip, so it is never automatic (sicn_options.split_k > 1
-// forces it; the parity suite runs it on every MFMA shape): a 256 x 256 image, layers 1 - 5, 25-pass chains instead of 50 / 75:
-// 11.6 -> 23.2, 11.5 -> 13.6, 11.6 -> 15.1, 16.9 -> 20.4, 14.5 -> 19.2 us (profiles/r04_ksplit_small_configs.txt).  Halving a
-// 50-pass chain saves 2.3 us; making one workgroup's stores visible to a workgroup on another XCD costs an L2 write-back, a
-// device-scope compare-and-swap and an L2-bypassing read — three dependent trips to memory, more than the 4.5 us of a kernel
-// boundary, and the write-backs of the 16 workgroups an XCD holds queue up behind one another.
-// Returns the number of K slices (1 = no split); the kernels split into nq / 2 slices of one channel-group pair each.
-inline int split_k_automatic(long /*workgroups_after_split_n*/, int /*nq*/, bool /*deconv*/, size_t /*out_bytes*/, const ChipGeom &)
-{
-    return 1;
-}
 
 // ---- layer 7 (k_l7): vertical strips of 32 input columns, cut into y_chunks runs ----------------------------------------------
 // just under TWO workgroups per CU in all (measured r03: 510 of 512 best); every cut re-fetches six halo rows and the weights
@@ -96,27 +83,6 @@ inline int l7_chunks(int tiles_x, int n_images, int steps_y, int forced, const C
     if (y < 1) y = 1;
     if (y > steps_y) y = steps_y;
     return (int)y;
-}
-
-// ---- the RGB layer with the previous layer's activation (k_l7g): strips of 62 columns, steps of 4 rows, wgs_per_cu (1 or 2) workgroups per CU at a
-// time.  Every cut costs about two steps (the prologue activates six rows, two rounds of items): the cut with the fewest
-// step-times on the busiest CU, the smallest such
-constexpr int L7G_PLAN_COLS = 62, L7G_PLAN_ROWS = 4;   // the geometry k_l7g.hip instantiates (static_assert there)
-inline int l7g_chunks(int tiles_x, int n_images, int steps_y, int forced, int wgs_per_cu, const ChipGeom &c)
-{
-    if (forced > 0) return forced < steps_y ? forced : steps_y;
-    const long strips = (long)tiles_x * n_images;
-    int best = 1;
-    long best_cost = -1;
-    for (int y = 1; y <= steps_y && y <= 64; y++) {
-        const long per = (steps_y + y - 1) / y, rounds = (strips * y + (long)wgs_per_cu * c.n_cu - 1) / ((long)wgs_per_cu * c.n_cu),
-                   cost = rounds * (per + 2);
-        if (best_cost < 0 || cost < best_cost) {
-            best_cost = cost;
-            best = y;
-        }
-    }
-    return best;
 }
 
 // ---- layer 0 (k_l0): vertical runs of at most `max_run` tiles per workgroup, about four workgroups per CU on small images -----

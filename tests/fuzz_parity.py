@@ -20,8 +20,7 @@ ap.add_argument("--cases", type=int, default=200)
 ap.add_argument("--seed", type=int, default=1)
 ap.add_argument("--big", action="store_true", help="image sizes up to 600 x 400 (slow on the CPU side)")
 ap.add_argument("--chains", type=int, default=0, help="additionally: whole 8-layer chains (internal layouts) on random sizes")
-ap.add_argument("--gdn", type=int, default=0, help="additionally: layer 0 + GDN in one kernel (k_l0g) and (layer + GDN) -> RGB layer chains with the "
-                "activation applied by the RGB layer (k_l7g), random sizes, against the C oracle of the GDN")
+ap.add_argument("--gdn", type=int, default=0, help="additionally: layer 0 + GDN in one kernel (k_l0g), random sizes, against the C oracle of the GDN")
 ap.add_argument("--deal", type=int, default=0, help="additionally: one-layer nets of conv / deconv 128 -> 128 on few wide persistent workgroups that walk >= 16 "
                 "tiles each, so that the dynamic part of the tile deal (k_mfma16x.hip DealX: tickets, stealing across XCDs) is what runs; three "
                 "calls + a graph replay each")
@@ -30,7 +29,6 @@ rng = np.random.default_rng(args.seed)
 
 FAMILIES = [  # (cin, cout, simd, pe, transposed)
     (3, 128, 3, 8, 0), (128, 128, 8, 16, 0), (128, 192, 8, 24, 0), (192, 128, 12, 16, 1), (128, 128, 8, 16, 1), (128, 3, 8, 3, 1)]
-HAS_ALT = api._lib.lib().sicn_has_alt_kernels() == 1   # SICN_LIB=.../libsicn_alt.so: also draws the forms that live in the ALT build only
 bad = 0
 for case in range(args.cases):
     cin, cout, simd, pe, tr = FAMILIES[rng.integers(len(FAMILIES))]
@@ -51,10 +49,6 @@ for case in range(args.cases):
         env["tile_x"] = int(rng.choice([16, 32]))
     if rng.random() < 0.3:
         env["split_n"] = int(rng.choice([1, 2, 4]))
-    if HAS_ALT and cin == 3 and rng.random() < 0.3:      # the persistent layer-0 kernel (k_l0p, ALT build only), 1 .. all workgroups
-        env["l0_form"] = 2
-        env.pop("strip_chunks", None)
-        env["persistent_grid"] = int(rng.choice([1, 3, 8, 64, 0]))
     if cin != 3 and rng.random() < 0.4:       # the wide persistent kernels (only conv / deconv 128 -> 128 take them; others ignore the request)
         env["wave_tile"] = 128
         env["tile_x"] = 32
@@ -142,27 +136,13 @@ for case in range(args.gdn):
         Wt = rng.integers(-8, 8, (cout, 5, 5, cin)).astype(np.int8)
         bt = rng.integers(-128, 128, cout).astype(np.int8)
         return d, Wt, bt
-    if case % 2 == 0 or not HAS_ALT:     # k_l0g (k_l7g below exists in the ALT build only)
-        d, Wt, bt = mk(3, 128, 3, 8, int(rng.integers(1, 300)), int(rng.integers(1, 200)), 0)
-        x = rng.integers(0, 256, (n,) + d.in_shape, dtype=np.uint8)
-        g = api.GDN(beta, gamma, inverse, 12)
-        fpw = api.FixedPointWeights(d.SIMD, 4, d.PE, d.W_TILES, sicn_ref.pack_finn_tiles(Wt, d.SIMD, d.PE))
-        got = api.conv2d(d, fpw, bt, torch.from_numpy(x).cuda(), None, n, gdn=g, options=env or None).cpu().numpy()
-        ok = all(np.array_equal(got[i], c_oracle.gdn(sicn_ref.layer_preact_ref(x[i], Wt, bt, 0), beta, gamma, inverse, 12)) for i in range(n))
-        what = f"k_l0g {d.IFM_ROW}x{d.IFM_COL}"
-    else:                 # (conv or deconv 128 -> 128, GDN) -> 128 -> RGB with gdn_fuse = 2
-        tr = int(rng.integers(2))
-        d0, W0, b0 = mk(128, 128, 8, 16, int(rng.integers(1, 70)), int(rng.integers(1, 40)), tr)
-        d1, W1, b1 = mk(128, 3, 8, 3, d0.OFM_ROW, d0.OFM_COL, 1)
-        params = [(api.FixedPointWeights(d.SIMD, 4, d.PE, d.W_TILES, sicn_ref.pack_finn_tiles(Wt, d.SIMD, d.PE)),
-                   api.FixedPointWeights(1, 8, 1, d.OFM_CH, bt.view(np.uint8).astype(np.uint64))) for d, Wt, bt in ((d0, W0, b0), (d1, W1, b1))]
-        env["gdn_fuse"] = 2
-        net = api.EightLayersNet(descs=[d0, d1], params=params, gdn=[api.GDN(beta, gamma, inverse, 12), None], options=env)
-        x = rng.integers(0, 128, (n,) + d0.in_shape, dtype=np.uint8)
-        got = net.run_layers(0, 1, torch.from_numpy(x).cuda())[0].cpu().numpy()
-        ok = all(np.array_equal(got[i], sicn_ref.deconv522_ref(c_oracle.gdn(sicn_ref.layer_preact_ref(x[i], W0, b0, tr), beta, gamma, inverse, 12), W1, b1))
-                 for i in range(n))
-        what = f"k_l7g behind {'deconv' if tr else 'conv'} {d0.IFM_ROW}x{d0.IFM_COL}"
+    d, Wt, bt = mk(3, 128, 3, 8, int(rng.integers(1, 300)), int(rng.integers(1, 200)), 0)
+    x = rng.integers(0, 256, (n,) + d.in_shape, dtype=np.uint8)
+    g = api.GDN(beta, gamma, inverse, 12)
+    fpw = api.FixedPointWeights(d.SIMD, 4, d.PE, d.W_TILES, sicn_ref.pack_finn_tiles(Wt, d.SIMD, d.PE))
+    got = api.conv2d(d, fpw, bt, torch.from_numpy(x).cuda(), None, n, gdn=g, options=env or None).cpu().numpy()
+    ok = all(np.array_equal(got[i], c_oracle.gdn(sicn_ref.layer_preact_ref(x[i], Wt, bt, 0), beta, gamma, inverse, 12)) for i in range(n))
+    what = f"k_l0g {d.IFM_ROW}x{d.IFM_COL}"
     if not ok:
         gbad += 1
         print(f"GDN MISMATCH {case}: {what} n={n} inverse={inverse} env={env}", flush=True)

@@ -115,42 +115,6 @@ def test_strip_kernels_long_strips(api, case, chunks):
 MFMA_CASES = [c for c in SPECIAL if c[0] != 3 and c[1] != 3]
 
 
-def test_alt_build_32x32x32_kernels(api):
-    """k_mfma.hip (v_mfma_i32_32x32x32_i8), round 1's kernel family, is a second implementation of L1-L6 that lives in the ALT
-    build only (make ALT=1 -> libsicn_alt.so; the product library rejects mfma_shape = 32).  It must stay bit-exact: the check
-    runs in a process of its own that loads the ALT library (tests/alt_kernels_check.py: every MFMA shape standalone against
-    the oracle and a whole chain against the Appendix-A hashes)."""
-    import os
-    alt = ROOT / "simple_image_compression_network_amd" / "libsicn_alt.so"
-    assert alt.exists(), "build() makes libsicn_alt.so"
-    assert api._lib.lib().sicn_has_alt_kernels() == 0
-    o = api._lib.make_options(mfma_shape=32)
-    d = _mk_desc(128, 128, 8, 16, 8, 8, 0).to_c()
-    assert api._lib.lib().sicn_conv2d_opt(ctypes.byref(d), None, None, None, 1, ctypes.byref(o), None) == -22
-    r = subprocess.run([sys.executable, str(ROOT / "tests" / "alt_kernels_check.py")], capture_output=True, text=True,
-                       env=dict(os.environ, SICN_LIB=str(alt)), timeout=600)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
-    assert "alt kernels ok" in r.stdout
-
-
-def test_alt_build_measured_loss_kernels(api):
-    """k_l0p (l0_form = 2), k_l7s (l7_loader = 2), k_l7g (gdn_fuse = 2) and the K split (split_k > 1) measured a loss against the
-    defaults and live in libsicn_alt.so only: the product library rejects their
-    options with SICN_EINVAL, and their parity tests — every test marked `alt` in this directory — run here, in a child pytest
-    whose library is the ALT build, so they stay bit-exact without being product surface."""
-    from conftest import run_alt_session
-    L = api._lib.lib()
-    d = _mk_desc(128, 128, 8, 16, 8, 8, 0).to_c()
-    out = ctypes.c_void_p()
-    for opt in ({"l0_form": 2}, {"l7_loader": 2}, {"gdn_fuse": 2}, {"split_k": 2}, {"split_k": 3}):
-        o = api._lib.make_options(**opt)
-        assert L.sicn_conv2d_opt(ctypes.byref(d), None, None, None, 1, ctypes.byref(o), None) == -22, opt
-        assert L.sicn_net_create_opt(ctypes.byref(d), ctypes.byref(out), 1, ctypes.byref(o), ctypes.byref(out)) == -22, opt
-    r = run_alt_session("alt and gpu")
-    assert r.returncode == 0, r.stdout[-4000:] + r.stderr[-2000:]
-    assert " passed" in r.stdout and "failed" not in r.stdout, r.stdout[-1000:]
-
-
 @pytest.mark.parametrize("prefetch", [1, 2])
 @pytest.mark.parametrize("tile_x", ["16", "32"])
 @pytest.mark.parametrize("case", MFMA_CASES + [(128, 128, 8, 16, 50, 20, 0), (192, 128, 12, 16, 37, 21, 1), (128, 192, 8, 24, 47, 18, 0),
@@ -196,100 +160,6 @@ def test_output_channel_split_in_chain(api, split_n):
     torch.cuda.synchronize()
     assert _sha(out[0].cpu().numpy()) == HASHES["layers"]["rng768"][7]
     assert _sha(latent[0].cpu().numpy()) == HASHES["layers"]["rng768"][3]
-
-
-def _run_layer_in_net(api, d, words, b, x_np, **options):
-    """One layer as a one-layer net chain (sicn_net_forward): the K split lives there, its scratch is part of the net's workspace."""
-    fpw = api.FixedPointWeights(d.SIMD, 4, d.PE, d.W_TILES, words)
-    net = api.EightLayersNet(descs=[d], params=[(fpw, b)], options=options or None)
-    out, _ = net.run_layers(0, 0, _dev(x_np))
-    torch.cuda.synchronize()
-    return out.cpu().numpy(), net
-
-
-KSPLIT_CASES = MFMA_CASES + [(128, 128, 8, 16, 50, 20, 0), (192, 128, 12, 16, 37, 21, 1), (128, 192, 8, 24, 47, 18, 0),
-                             (192, 128, 12, 16, 45, 19, 0), (128, 192, 8, 24, 21, 13, 1), (128, 128, 8, 16, 33, 9, 1),
-                             (128, 128, 8, 16, 1, 1, 0), (192, 128, 12, 16, 1, 1, 1), (128, 192, 8, 24, 16, 8, 0)]
-
-
-@pytest.mark.alt
-@pytest.mark.parametrize("case", KSPLIT_CASES)
-def test_k_split_matches_oracle(api, case):
-    """K split (round 4): the channel-group pairs of a layer over 2 / 3 workgroups, every slice stores its
-    partial output bytes, the last one to arrive adds them mod 256 (exact: the reference's accumulator is ap_uint<8>,
-    mvau.hpp:112,160-170) and applies bias / ReLU — forced on EVERY MFMA shape, conv and deconv, batches, ragged edges, pixels
-    and activations >= 128, against the oracle."""
-    rng = np.random.default_rng(abs(hash(case)) % (1 << 31) + 4242)
-    d = _mk_desc(*case)
-    W, b, words = _rand_params(rng, d)
-    x = rng.integers(0, 128, (3,) + d.in_shape, dtype=np.uint8)
-    x[1].reshape(-1)[::5] |= 0x80
-    got, net = _run_layer_in_net(api, d, words, b, x, tile_x=16, split_n=2, split_k=2)
-    plan = (ctypes.c_int32 * 12)()
-    from simple_image_compression_network_amd import _lib
-    o = _lib.make_options(tile_x=16, split_n=2, split_k=2)
-    assert _lib.lib().sicn_debug_plan(ctypes.byref(d.to_c()), 3, ctypes.byref(o), 256, plan) == 0
-    assert plan[6] == d.IFM_CH // 64 and plan[9] == plan[6]          # the K split really is what ran: IFM_CH / 64 slices
-    ref_fn = sicn_ref.deconv522_ref if d.transposed else sicn_ref.conv2d_ref
-    for i in range(3):
-        ref = ref_fn(x[i], W, b)
-        assert np.array_equal(got[i], ref), (i, np.count_nonzero(got[i] != ref))
-    # the unsplit kernel, same net shape: identical bytes
-    same, _ = _run_layer_in_net(api, d, words, b, x, tile_x=16, split_n=2, split_k=1)
-    assert np.array_equal(got, same)
-
-
-@pytest.mark.alt
-def test_k_split_scratch_needs_no_initialisation_and_cleans_up(api):
-    """The K-split arrival words live in the caller's workspace, which nobody initialises: whatever it holds — zeros, 0xFF,
-    random bytes, the leftovers of earlier launches — reads as "nobody has arrived" unless it carries the net's random 56-bit
-    tag, and the workgroup that finishes a tile clears its word.  Repeated calls, a captured graph replayed several times, and
-    poisoned scratch all give the same bytes."""
-    rng = np.random.default_rng(99)
-    d = _mk_desc(128, 192, 8, 24, 40, 24, 0)
-    W, b, words = _rand_params(rng, d)
-    x = rng.integers(0, 256, (2,) + d.in_shape, dtype=np.uint8)
-    ref = np.stack([sicn_ref.conv2d_ref(x[i], W, b) for i in range(2)])
-    fpw = api.FixedPointWeights(d.SIMD, 4, d.PE, d.W_TILES, words)
-    net = api.EightLayersNet(descs=[d], params=[(fpw, b)], options={"tile_x": 16, "split_n": 2, "split_k": 2})
-    xin = _dev(x)
-    ws = net.workspace(2)
-    for fill in ("zeros", "ones", "random", "leftover", "leftover"):
-        if fill == "zeros":
-            ws.zero_()
-        elif fill == "ones":
-            ws.fill_(0xFF)
-        elif fill == "random":
-            ws.copy_(torch.randint(0, 256, (ws.numel(),), dtype=torch.uint8, device="cuda"))
-        out, _ = net.run_layers(0, 0, xin)
-        torch.cuda.synchronize()
-        assert np.array_equal(out.cpu().numpy(), ref), fill
-    out = torch.zeros_like(out)
-    g = torch.cuda.CUDAGraph()
-    side = torch.cuda.Stream()
-    torch.cuda.synchronize()
-    with torch.cuda.stream(side):
-        with torch.cuda.graph(g, stream=side):
-            net.run_layers(0, 0, xin, out=out)
-    for _ in range(4):
-        out.zero_()
-        g.replay()
-        torch.cuda.synchronize()
-        assert np.array_equal(out.cpu().numpy(), ref)
-
-
-@pytest.mark.alt
-@pytest.mark.parametrize("size", [(768, 512, "rng768"), (256, 256, "rng256")])
-def test_k_split_in_chain(api, size):
-    """The whole net with the K split forced wherever the form exists (layers 1 - 6 at 8 x 16 tiles)."""
-    w, h, name = size
-    xin = _dev(_input(name)[None])
-    net = api.EightLayersNet(w, h, options={"tile_x": 16, "split_n": 2, "split_k": 2})
-    for _ in range(3):                      # the scratch is reused from layer to layer and from call to call
-        out, latent = net.forward(xin)
-        torch.cuda.synchronize()
-        assert _sha(out[0].cpu().numpy()) == HASHES["layers"][name][7]
-        assert _sha(latent[0].cpu().numpy()) == HASHES["layers"][name][3]
 
 
 @pytest.mark.parametrize("grid", [8, 16, 24])
@@ -961,69 +831,3 @@ def test_crop_nhwc_one_launch(api, shape):
     torch.cuda.synchronize()
     assert np.array_equal(d_dst.cpu().numpy(), src[:, :h, :w, :])
     assert _lib.lib().sicn_crop_nhwc(ctypes.c_void_p(d_src.data_ptr()), ctypes.c_void_p(d_dst.data_ptr()), n, hs, ws, hs + 1, w, c, None) == -22
-
-
-@pytest.mark.alt
-@pytest.mark.parametrize("chunks", [0, 1, 3])
-@pytest.mark.parametrize("case", [(128, 3, 8, 3, 70, 45, 1), (128, 3, 8, 3, 64, 32, 1), (128, 3, 8, 3, 1, 1, 1), (128, 3, 8, 3, 33, 7, 1), (128, 3, 8, 3, 96, 130, 1)])
-def test_layer7_loader_wave_form_matches_oracle(api, case, chunks):
-    """k_l7s (sicn_options.l7_loader = 2): a fifth wave issues all row requests of a step, four consumer waves
-    do reads + MFMAs + stores — same bytes as the oracle on ragged strips, single pixels, long strips cut into runs, batches."""
-    rng = np.random.default_rng(abs(hash(case)) % (1 << 31) + chunks)
-    d = _mk_desc(*case)
-    W, b, words = _rand_params(rng, d)
-    x = rng.integers(0, 128, (2,) + d.in_shape, dtype=np.uint8)
-    x[1].reshape(-1)[::7] |= 0x80
-    got = _run_layer(api, d, words, b, x, l7_loader=2, strip_chunks=chunks)
-    for i in range(2):
-        assert np.array_equal(got[i], sicn_ref.deconv522_ref(x[i], W, b)), i
-
-
-@pytest.mark.alt
-def test_layer7_loader_wave_form_in_chain(api):
-    xin = _dev(_input("rng768")[None])
-    net = api.EightLayersNet(768, 512, options={"l7_loader": 2})
-    out, latent = net.forward(xin)
-    torch.cuda.synchronize()
-    assert _sha(out[0].cpu().numpy()) == HASHES["layers"]["rng768"][7]
-
-
-@pytest.mark.alt
-@pytest.mark.parametrize("grid", [0, 1, 3, 8])
-@pytest.mark.parametrize("case", [(3, 128, 3, 8, 140, 150, 0), (3, 128, 3, 8, 64, 48, 0), (3, 128, 3, 8, 2, 2, 0), (3, 128, 3, 8, 70, 290, 0), (3, 128, 3, 8, 513, 31, 0)])
-def test_layer0_persistent_form_matches_oracle(api, case, grid):
-    """k_l0p (sicn_options.l0_form = 2): two workgroups per CU walk many runs of <= 7 tiles, the next run's raw pixels arriving by
-    LDS-DMA under the current one — forced here on small images with 1 / 3 / 8 workgroups so that every workgroup crosses run,
-    strip and image boundaries; pixels >= 128; the first unit of the tensor (the corner patched by ordinary loads) included."""
-    rng = np.random.default_rng(abs(hash(case)) % (1 << 31) + grid)
-    d = _mk_desc(*case)
-    W, b, words = _rand_params(rng, d)
-    x = rng.integers(0, 256, (3,) + d.in_shape, dtype=np.uint8)
-    got = _run_layer(api, d, words, b, x, l0_form=2, persistent_grid=grid)
-    for i in range(3):
-        assert np.array_equal(got[i], sicn_ref.conv2d_ref(x[i], W, b)), i
-    assert np.array_equal(got, _run_layer(api, d, words, b, x, l0_form=1))
-
-
-@pytest.mark.alt
-def test_layer0_persistent_form_in_chain(api):
-    xin = _dev(np.stack([_input("rng768"), _input("ones768")]))
-    net = api.EightLayersNet(768, 512, options={"l0_form": 2, "persistent_grid": 16})
-    out, latent = net.forward(xin)
-    torch.cuda.synchronize()
-    for i, name in enumerate(("rng768", "ones768")):
-        assert _sha(out[i].cpu().numpy()) == HASHES["layers"][name][7]
-        assert _sha(latent[i].cpu().numpy()) == HASHES["layers"][name][3]
-
-
-@pytest.mark.alt
-def test_layer0_persistent_form_two_workgroups_per_cu(api):
-    """3 x 1080p = 900 runs: 512 workgroups, two on every CU, most with two runs.  (The first build of k_l0p sized its raw buffers
-    by rows, and the idle lanes of the last request instruction wrote zeros past the workgroup's LDS — into the weights of the
-    CU's other workgroup; invisible to every test that puts one workgroup on a CU.)"""
-    rng = np.random.default_rng(77)
-    d = _mk_desc(3, 128, 3, 8, 1920, 1080, 0)
-    _, b, words = _rand_params(rng, d)
-    x = rng.integers(0, 256, (3,) + d.in_shape, dtype=np.uint8)
-    a = _run_layer(api, d, words, b, x, l0_form=2)
-    assert np.array_equal(a, _run_layer(api, d, words, b, x, l0_form=1))

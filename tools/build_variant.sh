@@ -14,7 +14,7 @@ if [ $# -eq 0 ]; then
   make -C "$CSRC" -j4 ARCH=gfx950 OBJDIR="$OUT" OUT="$OUT/libsicn.so" EXTRA="$FLAGS" >/dev/null
 else
   rm -f "$OUT"/*.o
-  # every object of the product build (the Makefile's SRCS, whatever they are this round: a fixed list once missed k_l0g / k_l7g and the
+  # every object of the product build (the Makefile's SRCS, whatever they are this round: a fixed list once missed k_l0g and the
   # variant failed at dlopen with undefined symbols)
   for o in $(make -s -C "$CSRC" print-objs); do cp "$CSRC/$o" "$OUT"/; done
   for f in "$@"; do

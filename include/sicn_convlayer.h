@@ -17,9 +17,11 @@
  *
  * In the reference this surface is only instantiated in a commented-out line
  * (conv_nonsquare_top.cpp:223), so there are no reference outputs to pin it with: parity status
- * UNPINNED (restated from the cited source; GPU == CPU restatement in the tests).  It is served by
- * an int8 MFMA implicit-GEMM kernel when IFM_CH is a multiple of 16 and by a shape-agnostic direct
- * kernel otherwise — a functional surface, not a tuned hot path (the hot path is sicn.h).
+ * UNPINNED (restated from the cited source; GPU == CPU restatement in the tests).  Every descriptor,
+ * sub-byte lanes and any channel count included, is served by an int8 MFMA implicit-GEMM kernel that
+ * unpacks the input stream into an LDS patch and packs the output lanes in its epilogue; a direct
+ * kernel (one thread per output byte) is the cross-check — a functional surface, not a tuned hot path
+ * (the hot path is sicn.h).
  *
  * Data model = the reference's stream words, byte for byte (round 5: sub-byte lanes).  Input: per pixel one word
  * `ap_uint<IFM_CH * IN_BIT>` (convlayer.h:100: hls::stream<ap_uint<IFMChannels * TSrcI::width>>), lane c in bits
@@ -77,13 +79,19 @@ void sicn_convlayer_params_free(sicn_convlayer_params *p);
 int sicn_conv_layer_batch(const sicn_convlayer_desc *desc, const sicn_convlayer_params *params, const uint8_t *in,
                           void *out, int reps, void *hip_stream);
 
-/* The same with the kernel chosen by the caller (tests compare the two): AUTO = the implicit-GEMM MFMA kernel
- * when the shape allows it (IFM_CH % 16 == 0, IN_BIT = 8, OUT_BIT >= 8), DIRECT = always the direct kernel (one thread per output
- * byte or container; the only one that reads and writes sub-byte lanes). */
+/* The same with the kernel chosen by the caller (tests compare the two): AUTO = an int8 MFMA implicit-GEMM kernel for every valid
+ * descriptor whose input image holds fewer than 2^31 - 1 lanes — k_convlayer_mfma for IN_BIT = 8, OUT_BIT >= 8 and IFM_CH % 16 == 0,
+ * k_convlayer_patch for every other shape (any IN_BIT, OUT_BIT, IFM_CH, OFM_CH) — and the direct kernel for larger images;
+ * DIRECT = always the direct kernel (one thread per output byte or container). */
 #define SICN_CONVLAYER_KERNEL_AUTO 0
 #define SICN_CONVLAYER_KERNEL_DIRECT 1
 int sicn_conv_layer_batch_kernel(const sicn_convlayer_desc *desc, const sicn_convlayer_params *params, const uint8_t *in,
                                  void *out, int reps, int kernel, void *hip_stream);
+
+/* Pure host: the name of the kernel SICN_CONVLAYER_KERNEL_AUTO launches for this descriptor ("k_convlayer_patch", "k_convlayer_mfma"
+ * or "k_convlayer"),
+ * NULL if sicn_convlayer_validate rejects it.  Since library 0.4 (sicn_version() >= 4). */
+const char *sicn_convlayer_kernel_for(const sicn_convlayer_desc *desc);
 
 #ifdef __cplusplus
 }

@@ -83,6 +83,7 @@ CONVLAYER_ABI = {
     "sicn_convlayer_params_free": (None, [_vp]),
     "sicn_conv_layer_batch": (_i, [_cldp, _vp, _vp, _vp, _i, _vp]),
     "sicn_conv_layer_batch_kernel": (_i, [_cldp, _vp, _vp, _vp, _i, _i, _vp]),
+    "sicn_convlayer_kernel_for": (ctypes.c_char_p, [_cldp]),
 }
 
 # include/sicn_gdn.h (extension beyond the reference: fixed-point GDN / IGDN in place of the ReLU)

@@ -17,7 +17,7 @@ import numpy as np
 from . import _lib
 from .api import FixedPointWeights, _stream_ptr
 
-__all__ = ["ConvLayerDesc", "PassThroughActivation", "ThresholdsActivation", "ConvLayer", "ConvLayer_Batch"]
+__all__ = ["ConvLayerDesc", "PassThroughActivation", "ThresholdsActivation", "ConvLayer", "ConvLayer_Batch", "kernel_for"]
 
 
 @dataclass(frozen=True)
@@ -68,11 +68,19 @@ class ConvLayerDesc:
                                    ACT_VAL=int(activation.ACT_VAL) if th else 0)
 
 
+def kernel_for(desc: ConvLayerDesc, activation):
+    """Name of the kernel that the automatic choice (`kernel=0`) launches for this layer — `sicn_convlayer_kernel_for`, a pure host
+    call: "k_convlayer_patch" or "k_convlayer_mfma" (the int8 MFMA implicit GEMMs) or "k_convlayer" (the direct kernel, for input images of
+    2^31 - 1 lanes or more); None for an invalid layer."""
+    name = _lib.lib().sicn_convlayer_kernel_for(ctypes.byref(desc.to_c(activation)))
+    return None if name is None else name.decode()
+
+
 class ConvLayer:
     """A layer with its parameters resident on the device: descriptor, weights and activation are validated and uploaded ONCE (the reference's
     weights and thresholds are objects the caller builds once and passes by reference, convlayer.h:89-111), every call only enqueues.
     `layer(in_, out=None, reps=1, stream=None, kernel=0)` — tensors as for ConvLayer_Batch.  `close()` (or garbage collection) frees the handle;
-    the caller keeps it alive until the last enqueued call has run."""
+    the caller keeps it alive until the last enqueued call has run.  `layer.kernel`: the kernel a call with `kernel=0` launches (`kernel_for`)."""
 
     def __init__(self, desc: ConvLayerDesc, weights: FixedPointWeights, activation):
         L = _lib.lib()
@@ -87,6 +95,7 @@ class ConvLayer:
             thr = np.ascontiguousarray(activation.m_thresholds, dtype=np.int32)
             if thr.shape[:2] != (desc.PE, desc.OFM_CH // desc.PE):
                 raise ValueError("m_thresholds must be [PE][NF][NumTH]")
+        self.kernel = kernel_for(desc, activation)
         self._h = ctypes.c_void_p()
         _lib.check(L.sicn_convlayer_params_create(ctypes.byref(self._cd), words.ctypes.data_as(ctypes.c_void_p), 8,
                                                   thr.ctypes.data_as(ctypes.c_void_p) if thr is not None else None,
@@ -133,7 +142,9 @@ def ConvLayer_Batch(desc: ConvLayerDesc, in_, out, weights: FixedPointWeights, a
     (one byte per lane at IN_BIT = 8); out: CUDA tensor [reps][OFM_DIM][OFM_DIM][OFM_CH] of dtype uint8 / int16 / int32 matching OUT_BIT
     (8 / 16 / 32), or uint8 [reps][OFM_DIM][OFM_DIM][OFM_CH * OUT_BIT / 8] for OUT_BIT 2 / 4 (packed exactly like an input stream, so it
     can be handed to the next layer as it is), or None to allocate.  Returns `out`.
-    kernel: 0 = automatic (MFMA kernel when the shape allows), 1 = the direct kernel (tests compare the two).
+    kernel: 0 = automatic (an int8 MFMA kernel for every layer whose input image holds fewer than 2^31 - 1 lanes: k_convlayer_mfma for byte
+    lanes in, OUT_BIT >= 8 and IFM_CH % 16 == 0, k_convlayer_patch for every other shape; see `kernel_for`), 1 = the direct kernel (one
+    thread per output byte or container; tests compare the two).
     The reference's calling convention: parameters travel with every call (uploaded, used, freed; the call returns when the layer has run).
     `ConvLayer` keeps them resident."""
     import torch

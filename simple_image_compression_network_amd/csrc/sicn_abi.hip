@@ -129,7 +129,8 @@ extern "C" void sicn_options_init(sicn_options *opt)
 // 0.2: sicn_options.split_k (a reserved slot), sicn_net_workspace_bytes grows by the K-split scratch, sicn_codec_info is 44 bytes
 // (stream_symbols), SICN_ENODEV for a device that is not gfx950
 // 0.3: GDN / IGDN specification version 2 (include/sicn_gdn.h): the activation's BYTES change, sicn_gdn_selftest_roots_narrow is gone
-extern "C" int sicn_version(void) { return 1000 * 0 + 3; }
+// 0.4: sicn_convlayer_kernel_for; ConvLayer_Batch serves every descriptor (sub-byte lanes, any channel count) on the MFMA kernel
+extern "C" int sicn_version(void) { return 1000 * 0 + 4; }
 extern "C" int sicn_gdn_spec_version(void) { return 2; }
 
 extern "C" int sicn_has_alt_kernels(void) { return 0; }   // kept for callers that probe it: the alternate kernel build is gone

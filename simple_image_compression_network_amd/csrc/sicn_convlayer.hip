@@ -1,18 +1,18 @@
 // Generic finn-hlslib ConvLayer_Batch surface (include/sicn_convlayer.h): any kernel size, channel
-// count, fold, accumulator width, pass-through or multi-threshold activation.  One thread per output
-// lane, direct evaluation:
+// count, fold, accumulator width, pass-through or multi-threshold activation, 1- / 2- / 4- / 8-bit input lanes, 2- to 32-bit output lanes:
 //   acc  = wrap_TA( sum_{ky,kx,c} x[y+ky][x+kx][c] * W[o][(ky*K+kx)*C + c] )      mvau.hpp:87-179
 //   out  = low OUT_BIT bits of  activation(acc)                                    activations.hpp:127-190
 // Stride 1, no padding, square image (convlayer.h:116-118).  Parity unpinned (no reference outputs
 // exist for this surface, sicn_convlayer.h).
 //
-// Two kernels.  k_convlayer_mfma (IFM_CH a multiple of 16): implicit GEMM on v_mfma_i32_16x16x64_i8 —
-// a wave owns 64 consecutive output positions x 64 output channels (16 accumulator tiles); a K step is
-// 64 channel bytes of ONE kernel tap, read straight from the NHWC image (16 bytes per lane, the cache
-// hierarchy serves the K*K-fold reuse), weights from a zero-padded [O/16][tap][C/64][16][64] image.
-// int8 x int8 is signed x signed: unsigned inputs are read as x - 128 (one v_xor per dword) and
-// 128 * sum_k W[o][k] is the accumulators' start value.  k_convlayer: one thread per output lane, direct
-// evaluation, for every other shape.  Neither is a tuned hot path (that is sicn.h).
+// Three kernels.  k_convlayer_patch (every descriptor): implicit GEMM on v_mfma_i32_16x16x64_i8 with the input patch of a 16 x 16 output
+// tile unpacked into LDS (int8 lanes padded to 64 channels, double-buffered), the output lanes packed in the epilogue.
+// k_convlayer_mfma (IN_BIT 8, OUT_BIT >= 8, IFM_CH a multiple of 16 — where it measured faster): a wave owns 64 consecutive
+// output positions x 64 output channels (16 accumulator tiles); a K step is 64 channel bytes of ONE kernel tap, read straight from the
+// NHWC image (16 bytes per lane, the cache hierarchy serves the K*K-fold reuse).  Both take the weights from a zero-padded
+// [O/16][tap][C/64][16][64] image; int8 x int8 is signed x signed: 8-bit unsigned inputs are read as x - 128 (one v_xor per dword) and
+// 128 * sum_k W[o][k] is the accumulators' start value.  k_convlayer: one thread per output byte or container, direct evaluation — the
+// cross-check (SICN_CONVLAYER_KERNEL_DIRECT).  None is a tuned hot path (that is sicn.h).
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
@@ -26,7 +26,7 @@ struct sicn_convlayer_params {
     sicn_convlayer_desc d;
     int8_t *d_w_okc;     // [OFM_CH][K*K*IFM_CH] sign-extended weights
     int32_t *d_thr;      // [OFM_CH][NUM_TH] thresholds in channel order, or nullptr
-    int8_t *d_w_mfma;    // [ceil(O/16)][K*K][ceil(C/64)][16 rows][64 bytes], zero padded; nullptr if C % 16 != 0
+    int8_t *d_w_mfma;    // [ceil(O/16)][K*K][ceil(C/64)][16 rows][64 bytes], zero padded
     int32_t *d_wsum;     // [ceil(O/16)*16] sum_k W[o][k]
 };
 
@@ -218,6 +218,213 @@ __global__ __launch_bounds__(256) void k_convlayer_mfma(const uint8_t *__restric
     }
 }
 
+// ---- k_convlayer_patch: every descriptor, any IN_BIT / OUT_BIT / IFM_CH / OFM_CH (LDS-staged implicit GEMM) ----------------------------
+// A workgroup = a PT x PT tile of output positions of one image x 64 output channels (blockIdx.y); wave wv owns tile rows 4 wv .. 4 wv + 3,
+// one 16-position column tile per row.  K walk: 64-channel chunks outside, the K x K taps inside.  For each chunk the input patch of
+// (PT + K - 1)^2 pixels sits in LDS as 64 int8 lanes per pixel (64 bytes), 0 for channels >= IFM_CH and pixels outside the image; the
+// B operand of tap (ky, kx) is 16 lanes of the patch pixel (row + ky, col + kx), the A operand comes from the weight image as in
+// k_convlayer_mfma.  The patch is double-buffered: the next chunk is staged in pieces of PIECE dwords per thread, a piece's global loads
+// issued before one tap's MFMAs and its LDS writes after them.
+constexpr int PT = 16;      // output tile edge (positions)
+constexpr int PIECE = 4;    // patch dwords per thread per staging piece
+
+__host__ __device__ constexpr int patch_edge(int K) { return PT + K - 1; }
+__host__ __device__ constexpr size_t patch_lds_bytes(int K) { return 2 * (size_t)patch_edge(K) * patch_edge(K) * 64; }   // two buffers
+
+// Patch dword u of chunk n = lanes n*64 + 4q .. +3 (q = u & 15) of patch pixel u >> 4.  The stream is read as aligned dwords (a pixel can be
+// 1, 2 or 3 bytes): the nl * IN_BIT bits of the unit start at bit `bit` of the batch, in the dword that holds it and, when they cross into
+// it, the next one.  Both hold stream bits, so a load never leaves the aligned dwords of the buffer.
+struct PatchUnit {
+    uint32_t lo, hi, meta;   // meta = shift | nbits << 8; nbits 0: a zero dword (padding channel or a pixel outside the image)
+};
+
+__device__ __forceinline__ PatchUnit patch_request(const uint32_t *__restrict__ base32, uint64_t img_bit0, int u, int n, int y0, int x0, int PW,
+                                                   const sicn_convlayer_desc &d)
+{
+    PatchUnit r{0u, 0u, 0u};
+    const int pp = u >> 4, c = n * 64 + 4 * (u & 15);   // pp < PW * PW
+    const int pr = pp / PW, pc = pp - pr * PW;
+    const int y = y0 + pr, x = x0 + pc;
+    if (y < d.IFM_DIM && x < d.IFM_DIM && c < d.IFM_CH) {
+        const int nb = (d.IFM_CH - c < 4 ? d.IFM_CH - c : 4) * d.IN_BIT;
+        const uint64_t bit = img_bit0 + ((uint64_t)(y * d.IFM_DIM + x) * d.IFM_CH + c) * d.IN_BIT;
+        const uint32_t sh = (uint32_t)bit & 31;
+        r.lo = base32[bit >> 5];
+        if (sh + nb > 32) r.hi = base32[(bit >> 5) + 1];
+        r.meta = sh | (uint32_t)nb << 8;
+    }
+    return r;
+}
+
+// the unit's lanes as 4 int8 (byte i = lane i): ap_int lanes sign-extended, ap_uint sub-byte lanes as they are, 8-bit ap_uint lanes as
+// x - 128 (k_convlayer_mfma's convention); lanes past IFM_CH are 0
+__device__ __forceinline__ uint32_t patch_lanes(const PatchUnit &r, int in_bit, int in_signed)
+{
+    const int sh = r.meta & 255, nb = r.meta >> 8;
+    if (nb == 0) return 0u;
+    const uint64_t v = ((((uint64_t)r.hi << 32) | r.lo) >> sh) & ((1ull << nb) - 1);
+    if (in_bit == 8) return (uint32_t)v ^ (in_signed ? 0u : 0x80808080u & (uint32_t)((1ull << nb) - 1));
+    uint32_t out = 0;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        int l = (int)(v >> (i * in_bit)) & ((1 << in_bit) - 1);
+        if (in_signed) l = (int)((uint32_t)l << (32 - in_bit)) >> (32 - in_bit);
+        out |= ((uint32_t)l & 255u) << (8 * i);
+    }
+    return out;   // lanes past nb read as 0 bits: 0
+}
+
+__global__ __launch_bounds__(256) void k_convlayer_patch(const uint8_t *__restrict__ in, void *__restrict__ out,
+                                                         const int8_t *__restrict__ wm, const int32_t *__restrict__ wsum,
+                                                         const int32_t *__restrict__ thr, sicn_convlayer_desc d)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int col = lane & 15, g = lane >> 4;
+    const int C = d.IFM_CH, K = d.K, D = d.IFM_DIM, OD = d.OFM_DIM, O = d.OFM_CH;
+    const int PW = patch_edge(K), KK = K * K, nchunk = (C + 63) / 64, ntile = (O + 15) / 16;
+    const int tiles_x = (OD + PT - 1) / PT;
+    const int y0 = (int)(blockIdx.x / tiles_x) * PT, x0 = (int)(blockIdx.x % tiles_x) * PT;
+    const int j0 = blockIdx.y * 4;                                   // first 16-channel weight tile
+    const int nt = ntile - j0 < 4 ? ntile - j0 : 4;                  // weight tiles of this workgroup (uniform)
+    const int img = blockIdx.z;
+    const size_t buf_bytes = (size_t)PW * PW * 64;
+    const int units = PW * PW * 16, npieces = (units + 256 * PIECE - 1) / (256 * PIECE);
+
+    const uint32_t *base32 = reinterpret_cast<const uint32_t *>((uintptr_t)in & ~(uintptr_t)3);
+    const uint64_t img_bit0 = ((uintptr_t)in & 3) * 8 + (uint64_t)img * D * D * C * d.IN_BIT;
+
+    // one piece of chunk n: PIECE dwords per thread, requested, then written to buffer `dst`
+    auto piece_request = [&](PatchUnit (&pu)[PIECE], int piece, int n) {
+#pragma unroll
+        for (int i = 0; i < PIECE; i++) {
+            const int u = (piece * PIECE + i) * 256 + tid;
+            pu[i] = u < units ? patch_request(base32, img_bit0, u, n, y0, x0, PW, d) : PatchUnit{0u, 0u, 0u};
+        }
+    };
+    auto piece_write = [&](const PatchUnit (&pu)[PIECE], int piece, uint8_t *dst) {
+#pragma unroll
+        for (int i = 0; i < PIECE; i++) {
+            const int u = (piece * PIECE + i) * 256 + tid;
+            if (u < units) reinterpret_cast<uint32_t *>(dst)[u] = patch_lanes(pu[i], d.IN_BIT, d.IN_SIGNED);
+        }
+    };
+
+    v4i_t acc[4][4];
+    const bool bias = !d.IN_SIGNED && d.IN_BIT == 8;                // x - 128 lanes: 128 * sum_k W[o][k] to start with
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        v4i_t b;
+#pragma unroll
+        for (int r = 0; r < 4; r++) b[r] = (bias && j < nt) ? 128 * wsum[(j0 + j) * 16 + 4 * g + r] : 0;
+#pragma unroll
+        for (int c = 0; c < 4; c++) acc[c][j] = b;
+    }
+
+    for (int piece = 0; piece < npieces; piece++) {                   // chunk 0 into buffer 0
+        PatchUnit pu[PIECE];
+        piece_request(pu, piece, 0);
+        piece_write(pu, piece, smem);
+    }
+    __syncthreads();
+
+    for (int n = 0; n < nchunk; n++) {
+        const uint8_t *cur = smem + (n & 1) * buf_bytes;
+        uint8_t *nxt = smem + ((n + 1) & 1) * buf_bytes;
+        const bool stage = n + 1 < nchunk;
+        int piece = 0;
+        // B of tap t: 16 lanes (16 g ..) of patch pixel (4 wv + c + ky, col + kx); A: the weight image's 16 x 64 block (tile, tap, chunk)
+        auto request = [&](int t, v4i_t (&bf)[4], v4i_t (&af)[4]) {
+            const int ky = t / K, kx = t - ky * K;
+#pragma unroll
+            for (int c = 0; c < 4; c++)
+                bf[c] = *reinterpret_cast<const v4i_t *>(cur + ((size_t)(4 * wv + c + ky) * PW + col + kx) * 64 + 16 * g);
+#pragma unroll
+            for (int j = 0; j < 4; j++)
+                if (j < nt) af[j] = *reinterpret_cast<const v4i_t *>(wm + ((((size_t)(j0 + j) * KK + t) * nchunk + n) * 16 + col) * 64 + 16 * g);
+        };
+        auto multiply = [&](const v4i_t (&bf)[4], const v4i_t (&af)[4]) {
+#pragma unroll
+            for (int j = 0; j < 4; j++)
+                if (j < nt)
+#pragma unroll
+                    for (int c = 0; c < 4; c++) acc[c][j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(af[j], bf[c], acc[c][j], 0, 0, 0);
+        };
+        // one tap: the next piece's loads go out before the MFMAs, its LDS writes follow them
+        auto tap = [&](const v4i_t (&bf)[4], const v4i_t (&af)[4]) {
+            const bool go = stage && piece < npieces;                   // uniform
+            PatchUnit pu[PIECE];
+            if (go) piece_request(pu, piece, n + 1);
+            multiply(bf, af);
+            if (go) piece_write(pu, piece++, nxt);
+        };
+        v4i_t bf0[4], af0[4], bf1[4], af1[4];
+        request(0, bf0, af0);
+        for (int t = 0; t < KK; t += 2) {
+            if (t + 1 < KK) request(t + 1, bf1, af1);
+            tap(bf0, af0);
+            if (t + 1 < KK) {
+                if (t + 2 < KK) request(t + 2, bf0, af0);
+                tap(bf1, af1);
+            }
+        }
+        for (; stage && piece < npieces; piece++) {                    // what the taps did not cover (K <= 2)
+            PatchUnit pu[PIECE];
+            piece_request(pu, piece, n + 1);
+            piece_write(pu, piece, nxt);
+        }
+        __syncthreads();
+    }
+
+    // epilogue: lane holds, per (tile row c, weight tile j), channels 16 (j0 + j) + 4 g .. + 3 of position (y0 + 4 wv + c, x0 + col)
+    const int word_units = d.OUT_BIT < 8 ? O * d.OUT_BIT / 8 : O;     // bytes (OUT_BIT 2 / 4) or containers per pixel
+#pragma unroll
+    for (int c = 0; c < 4; c++) {
+        const int oy = y0 + 4 * wv + c, ox = x0 + col;
+        if (oy >= OD || ox >= OD) continue;
+        const size_t pix = ((size_t)img * OD + oy) * OD + ox;
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            if (j >= nt) continue;
+            uint32_t res[4];
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                const int o = (j0 + j) * 16 + 4 * g + r;
+                const long long a = wrap_acc((long long)acc[c][j][r], d.ACC_BIT, d.ACC_SIGNED);
+                long long v = a;
+                if (d.activation == SICN_ACT_THRESHOLDS) {
+                    v = d.ACT_VAL;
+                    if (o < O) {
+                        const int32_t *tt = thr + (size_t)o * d.NUM_TH;
+                        for (int i = 0; i < d.NUM_TH; i++) v += (wrap_acc((long long)tt[i], d.ACC_BIT, d.ACC_SIGNED) < a) ? 1 : 0;
+                    }
+                }
+                res[r] = (uint32_t)v;
+            }
+            const int o0 = (j0 + j) * 16 + 4 * g;
+            uint8_t *ob = (uint8_t *)out + pix * word_units;
+            if (d.OUT_BIT == 2) {                                       // lanes o0 .. o0 + 3 = byte o0 / 4 of the pixel word
+                if (o0 / 4 < word_units)
+                    ob[o0 / 4] = (uint8_t)((res[0] & 3) | (res[1] & 3) << 2 | (res[2] & 3) << 4 | (res[3] & 3) << 6);
+            } else if (d.OUT_BIT == 4) {                                // bytes o0 / 2 and o0 / 2 + 1
+                if (o0 / 2 < word_units) ob[o0 / 2] = (uint8_t)((res[0] & 15) | (res[1] & 15) << 4);
+                if (o0 / 2 + 1 < word_units) ob[o0 / 2 + 1] = (uint8_t)((res[2] & 15) | (res[3] & 15) << 4);
+            } else {
+#pragma unroll
+                for (int r = 0; r < 4; r++) {
+                    if (o0 + r >= O) continue;
+                    if (d.OUT_BIT == 8)
+                        ob[o0 + r] = (uint8_t)res[r];
+                    else if (d.OUT_BIT == 16)
+                        ((uint16_t *)out)[pix * O + o0 + r] = (uint16_t)res[r];
+                    else
+                        ((uint32_t *)out)[pix * O + o0 + r] = res[r];
+                }
+            }
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" int sicn_convlayer_validate(const sicn_convlayer_desc *d)
@@ -240,6 +447,29 @@ extern "C" int sicn_convlayer_validate(const sicn_convlayer_desc *d)
     } else
         return SICN_EINVAL;
     return SICN_OK;
+}
+
+namespace {
+enum ConvLayerKernel { CL_DIRECT, CL_MFMA, CL_PATCH };
+
+// what SICN_CONVLAYER_KERNEL_AUTO launches for a valid descriptor.  Byte lanes in, containers out and IFM_CH % 16 == 0 stay on
+// k_convlayer_mfma: it measured faster than k_convlayer_patch on every such shape timed
+ConvLayerKernel pick_kernel(const sicn_convlayer_desc &d)
+{
+    if ((size_t)d.IFM_DIM * d.IFM_DIM * d.IFM_CH >= 0x7fffffffu) return CL_DIRECT;   // 31-bit per-image lane offsets
+    if (d.IN_BIT == 8 && d.OUT_BIT >= 8 && d.IFM_CH % 16 == 0) return CL_MFMA;
+    return CL_PATCH;
+}
+}  // namespace
+
+extern "C" const char *sicn_convlayer_kernel_for(const sicn_convlayer_desc *d)
+{
+    if (sicn_convlayer_validate(d)) return nullptr;
+    switch (pick_kernel(*d)) {
+    case CL_MFMA: return "k_convlayer_mfma";
+    case CL_PATCH: return "k_convlayer_patch";
+    default: return "k_convlayer";
+    }
 }
 
 extern "C" void sicn_convlayer_params_free(sicn_convlayer_params *p)
@@ -298,7 +528,7 @@ extern "C" int sicn_convlayer_params_create(const sicn_convlayer_desc *d, const 
     p->d_wsum = nullptr;
     bool ok = hipMalloc((void **)&p->d_w_okc, w.size()) == hipSuccess &&
               hipMemcpy(p->d_w_okc, w.data(), w.size(), hipMemcpyHostToDevice) == hipSuccess;
-    if (ok && d->IFM_CH % 16 == 0 && d->IN_BIT == 8 && d->OUT_BIT >= 8) {   // the MFMA image (byte lanes only): [O/16][tap][C/64][16 rows][64 bytes], zero padded
+    if (ok) {   // the MFMA image: [O/16][tap][C/64][16 rows][64 bytes], zero padded
         const int KK = d->K * d->K, nchunk = (d->IFM_CH + 63) / 64, ntile = (d->OFM_CH + 15) / 16;
         std::vector<int8_t> wm;
         std::vector<int32_t> ws;
@@ -354,11 +584,21 @@ extern "C" int sicn_conv_layer_batch_kernel(const sicn_convlayer_desc *d, const 
     const size_t per_img = (size_t)d->OFM_DIM * d->OFM_DIM * (d->OUT_BIT < 8 ? d->OFM_CH * d->OUT_BIT / 8 : d->OFM_CH);   // output units
     const size_t blocks = (per_img + 255) / 256;
     if (blocks > 0x7fffffffu) return SICN_EINVAL;
-    if (p->d_w_mfma && d->IN_BIT == 8 && d->OUT_BIT >= 8 && (size_t)d->IFM_DIM * d->IFM_DIM * d->IFM_CH < 0x7fffffffu && kernel != SICN_CONVLAYER_KERNEL_DIRECT) {
+    const ConvLayerKernel k = kernel == SICN_CONVLAYER_KERNEL_DIRECT ? CL_DIRECT : pick_kernel(*d);
+    if (k == CL_MFMA) {
         const unsigned npos = (unsigned)(d->OFM_DIM * d->OFM_DIM);
         dim3 grid((npos + 255) / 256, (unsigned)((d->OFM_CH + 63) / 64), (unsigned)reps);
         hipLaunchKernelGGL(k_convlayer_mfma, grid, dim3(256), 0, (hipStream_t)hip_stream, in, out, p->d_w_mfma, p->d_wsum,
                            p->d_thr, *d);
+        return hipGetLastError() == hipSuccess ? SICN_OK : SICN_ENODEV;
+    }
+    if (k == CL_PATCH) {
+        const unsigned tiles_x = (unsigned)((d->OFM_DIM + PT - 1) / PT);
+        dim3 grid(tiles_x * tiles_x, (unsigned)((d->OFM_CH + 63) / 64), (unsigned)reps);
+        const size_t lds = patch_lds_bytes(d->K);
+        if (hipFuncSetAttribute((const void *)k_convlayer_patch, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+            return SICN_ENODEV;
+        hipLaunchKernelGGL(k_convlayer_patch, grid, dim3(256), lds, (hipStream_t)hip_stream, in, out, p->d_w_mfma, p->d_wsum, p->d_thr, *d);
         return hipGetLastError() == hipSuccess ? SICN_OK : SICN_ENODEV;
     }
     hipLaunchKernelGGL(k_convlayer, dim3((unsigned)blocks, (unsigned)reps), dim3(256), 0, (hipStream_t)hip_stream, in, out,

@@ -89,7 +89,8 @@ typedef struct sicn_options {
     int32_t struct_bytes;    /* sizeof(sicn_options) of the caller's build                          */
     int32_t force_generic;   /* 1: the shape-agnostic kernel (k_generic) for every layer            */
     int32_t mfma_shape;      /* 0 / 16: the v_mfma_i32_16x16x64_i8 kernels (the only ones; see the note below)      */
-    int32_t tile_x;          /* 0: by layer shape and grid size; 16 / 32: force that M-tile width   */
+    int32_t tile_x;          /* 0: by layer shape and grid size; 16 / 32: force that M-tile width wherever it exists   */
+                             /*    (the 192-channel layers have 8 x 16 tiles only: 32 gives them 16)                   */
     int32_t strip_chunks;    /* 0: automatic; n: cut the vertical strips of the RGB layers into n   */
     int32_t no_phase_layout; /* 0: default; 1: never use the PHASE layout; 2: not towards layer 7   */
     int32_t split_n;         /* 0: automatic (grids of at most 128 tiles: half the CUs idle); 1: never; > 1: always — the */
@@ -99,8 +100,9 @@ typedef struct sicn_options {
                              /*    WIDE PERSISTENT kernels (k_mfma16x.hip: one workgroup of 4 waves per CU walks through */
                              /*    16 x 32 tiles, 128 x 128 outputs per wave) wherever they exist (conv / deconv        */
                              /*    128 -> 128), whatever the grid size; automatic: from 4 tiles per CU on              */
-    int32_t prefetch;        /* 0: automatic; 1: never, 2 / 3: wherever it exists — the software-pipelined kernels      */
-                             /*    (k_mfma16p.hip) for the shapes and grids the wide kernels do not take               */
+    int32_t prefetch;        /* 0: automatic — the software-pipelined kernels (k_mfma16p.hip) for the shapes and grids */
+                             /*    the wide kernels do not take; 1 / 2 / 3: the pipelined kernels wherever the wide     */
+                             /*    ones are not forced (wave_tile = 128), i.e. never the automatic wide form            */
     int32_t persistent_grid; /* 0: one workgroup per CU; n: at most n (rounded down to a multiple of the XCD count)       */
                              /*    workgroups for the wide persistent kernels — tests use it to make every workgroup    */
                              /*    walk through many tiles of a small input                                            */
@@ -128,10 +130,10 @@ const char *sicn_strerror(int code);
  * n_xcd = the largest power of two <= 8 that leaves at least 20 CUs per XCD (256 CUs -> 8, a DPX partition of 128 -> 4, QPX
  * 64 -> 2, CPX 32 -> 1; hipDeviceProp_t carries no XCD count, and the value only steers which tiles share an L2).
  * sicn_debug_plan shows what a layer would launch on a chip of n_cu CUs, without a GPU: out[] = { n_cu, n_xcd, kernel kind
- * (0 generic, 1 mfma conv, 2 mfma deconv, 3 layer 0, 4 layer 7), mfma family (0 plain, 1 pipelined, 2 wide persistent), tile_x,
- * split_n, split_k (always 1), grid x, grid y, grid z, strip chunks (wide persistent: 1 = part of the tiles dealt dynamically), layer-0 tiles per
- * run }.  sicn_debug_xcd_item is the host mirror of
- * the kernels' workgroup -> work item mapping (-1: padding workgroup). */
+ * (0 generic, 1 mfma conv, 2 mfma deconv, 3 layer 0, 4 layer 7), mfma family (1 pipelined, 2 wide persistent; 0 only for the
+ * other kinds: the plain kernels of family 0 were removed), tile_x, split_n, split_k (always 1), grid x, grid y, grid z, strip
+ * chunks (wide persistent: 1 = part of the tiles dealt dynamically), layer-0 tiles per run }.  sicn_debug_xcd_item is the host
+ * mirror of the kernels' workgroup -> work item mapping (-1: padding workgroup). */
 /* dst[n][h][w][c] = the top-left h x w corner of every image of src[n][src_h][src_w][c] (device pointers, one launch, enqueue
  * only).  A deconv522 doubles a size that a conv2d rounded up, so a tensor rebuilt by deconvs can be one row / column larger than
  * the one it mirrors (the hyperprior's scale map against the latent); this is the crop. */

@@ -3,18 +3,6 @@
 #include "sicn_internal.h"
 #include "sicn_plan.h"
 
-// Timing-experiment switches that make a kernel give WRONG results on purpose (what does the barrier / the wait / the pack cost?)
-// live in the kernel sources because they must cut into the middle of a pass; none of them can reach a product build by
-// accident: they refuse to compile without -DSICN_ALLOW_WRONG_RESULTS.
-#if defined(SICN_EXP_NOWAIT) || defined(SICN_EXP_NO_PASS_BARRIER) || defined(SICN_X_NOBAR) || defined(SICN_X_NOWAIT) ||         \
-    defined(SICN_XW_NOREAD) || defined(SICN_XW_NOPACK) || defined(SICN_XW_NOSTORE) || defined(SICN_XW_NOWAIT) ||                \
-    defined(SICN_EXP_L7_DMA_ONLY) || defined(SICN_EXP_L7_READS_ONLY) || defined(SICN_EXP_L7_MFMA_ONLY) ||                      \
-    defined(SICN_EXP_L7_NO_MFMA) || defined(SICN_EXP_L7_NO_BARRIER) || (defined(SICN_EXP_L7_STORE) && SICN_EXP_L7_STORE != 0)
-#ifndef SICN_ALLOW_WRONG_RESULTS
-#error "this switch builds kernels that give wrong results on purpose (timing experiments): add -DSICN_ALLOW_WRONG_RESULTS"
-#endif
-#endif
-
 namespace sicn {
 
 typedef int v4i __attribute__((ext_vector_type(4)));
@@ -29,14 +17,9 @@ typedef int v16i __attribute__((ext_vector_type(16)));
 constexpr int SUB_BYTES = PATCH_PIX * KSTEP;  // 10880
 constexpr int SUB_PIECES = 12;
 constexpr int SUB_ALLOC = SUB_PIECES * 1024;  // 12288
-#ifndef SICN_RING
-#define SICN_RING 4
-#endif
-#ifndef SICN_PF
-#define SICN_PF 3
-#endif
-constexpr int RING = SICN_RING;               // weight-tile ring slots
-constexpr int PF = SICN_PF;                   // weight tiles in flight ahead of the consumer
+constexpr int RING = 4;                       // weight-tile ring slots
+constexpr int PF = 3;                         // weight tiles in flight ahead of the consumer
+constexpr int PAD16 = 24;                     // zero tiles behind a 16x16x64 weight stream (pack_mfma16_stream): room for the prefetch
 constexpr uint32_t OOB = 0x80000000u;         // beyond any image: the buffer range check returns 0
 
 template <int N>
@@ -64,11 +47,9 @@ typedef short v2s __attribute__((ext_vector_type(2)));
 constexpr uint32_t ACT_FLOOR_RELU = 0u, ACT_FLOOR_RAW = 0x80008000u;
 // the same kernel argument carries one more flag in a bit that is 0 in both floors: store the output non-temporal
 constexpr uint32_t ACT_NT_STORE = 1u, ACT_FLOOR_MASK = 0x80008000u;
-#ifndef SICN_NT_MIN_MB
-#define SICN_NT_MIN_MB 128
-#endif
+constexpr int NT_MIN_MB = 128;
 // outputs that cannot stay in L2 / Infinity Cache anyway (>= 128 MiB per launch) bypass them
-__host__ inline bool nt_store_wanted(size_t out_bytes) { return out_bytes >= ((size_t)SICN_NT_MIN_MB << 20); }
+__host__ inline bool nt_store_wanted(size_t out_bytes) { return out_bytes >= ((size_t)NT_MIN_MB << 20); }
 __device__ __forceinline__ uint32_t pack4_relu7(int a, int b, int c, int d, uint32_t floor2 = ACT_FLOOR_RELU)
 {
     const uint32_t ab = __builtin_amdgcn_perm((uint32_t)b, (uint32_t)a, 0x040c000cu);  // [0, a.b0, 0, b.b0]

@@ -1,11 +1,30 @@
-// conv2d<> / deconv522<> with 128 / 192 channels — k_mfma16.hip's kernels with an explicit software pipeline.
-// Same decomposition (conv: 4 parity planes with rolling refresh; deconv: 4 output phases over a resident patch), same
-// 8 x TX-position workgroup tiles (wave w = rows 2w, 2w+1; TX = 32, or 16 for the 192-channel layers and small grids),
-// two workgroups per CU = two waves per SIMD, same LDS images, same weight stream; read k_mfma16.hip first.
+// conv2d<> / deconv522<> with 128 / 192 channels: implicit GEMM on v_mfma_i32_16x16x64_i8 with an explicit software pipeline.
+// Decomposition: conv = 4 parity planes with rolling refresh; deconv = 4 output phases over a resident patch.  Workgroup tiles
+// of 8 x TX positions (wave w = rows 2w, 2w+1; TX = 32, or 16 for the 192-channel layers and small grids), two workgroups per
+// CU = two waves per SIMD; the weight stream is packed by k_mfma16.hip.
 //
-// What changes: in k_mfma16 a pass is  fragment reads -> MFMAs -> counted wait + barrier,  and the only thing that hides a
-// wave's LDS round trip and barrier is its partner wave (measured MFMA pipe utilisation 0.61 on layer 6) — and on small
-// grids, where a CU holds a single workgroup, nothing does.  The fragments cannot simply be double-buffered there:
+// Why 16x16x64: on this power-limited chip the 32x32x32 int8 MFMA loop tops out at ~2.93 POP/s and the 16x16x64 loop at
+// ~3.45 POP/s with identical LDS traffic per MAC (tools/microbench/mfma_shape.hip, profiles/r01_microbench_mfma_shape.txt); the
+// first, 32x32x32 kernels (removed in 0.3.x; see the git history of k_mfma.hip) sat on that ceiling.
+//
+// One "pass" = TWO K steps of 32 channel bytes (= the 64-deep K of the instruction):
+// lanes 0..31 (K bytes 0..31 of the MFMA) read step A's operands, lanes 32..63 step B's.
+//   conv  : A, B = two consecutive taps of the plane-ordered walk (possibly two different planes)
+//   deconv: A, B = channel groups q, q+1 of the same tap
+// Lane roles (l = lane): pos/row = l & 15, g = l >> 4: step = g >> 1, 16-byte half = g & 1.
+//   pixel fragment c (NC = 2 * TX/16 per wave: row i = c / (TX/16) of the wave's two rows, column tile c % (TX/16)):
+//       16 bytes at patch[sub_step][(2w + i + oy_step) * (TX+2) + 16*(c % (TX/16)) + pos + ox_step][half]
+//   weight fragment j (COUT/16 per pass): 16 bytes at ring[step][row j*16 + pos][half]
+// Neither image is swizzled: the hardware's 16-lane ds_read_b128 groups pair positions {0-3,12-15}
+// of one half with positions {4-11} of the other, which already covers 16 distinct 16-byte slots.
+// C/D layout (col = l & 15 = position, row = 4g + r): weight row (4g + r) of tile j holds channel
+// 64*(j>>2) + 16g + 4*(j&3) + r, so the four accumulators of tiles 4J..4J+3 of a lane are 16
+// consecutive channels of one pixel: one 16-byte store per (column tile, J), no transpose.
+// A barrier per pass (not per step) halves the barrier count of the 32x32x32 form.
+//
+// The pipeline: in a plain pass  fragment reads -> MFMAs -> counted wait + barrier  the only thing that hides a wave's LDS
+// round trip and barrier is its partner wave (measured MFMA pipe utilisation 0.61 on layer 6) — and on small grids, where a
+// CU holds a single workgroup, nothing does.  The fragments cannot simply be double-buffered there:
 // 128 accumulators + 2 x 48 fragment registers + addressing do not fit 256 VGPRs (and hipcc splits a 256-register budget
 // 128 / 128 between VGPRs and AGPRs as soon as an AGPR is used).  Here
 //   * the MFMAs are inline-asm statements with the accumulator tied ("+v"): volatile, so the order written is the order
@@ -14,15 +33,14 @@
 //     second set; only the pixel fragments (used by every weight tile of the pass) are double-buffered (+16 VGPRs);
 //   * the barrier that ends pass k therefore publishes the weight tiles of pass k+2: the ring runs 4 passes ahead (PFP = 8);
 //   * a pass's LDS-DMA requests are issued behind its first MFMA group: the MFMA pipe restarts right after the barrier.
-// Also in this file: the output-channel split of the 8 x 16 kernels for grids smaller than the chip (NT16 < NTF, launch_p) and,
-// under -DSICN_STAMP only, in-kernel s_memtime stamps for tools/*_stamps.py.  (Round 2's persistent conv kernel k_conv_pp, with
-// its per-XCD ticket scheduler in device memory owned by the weights handle, is gone: full-size grids now run the wide persistent
-// kernels of k_mfma16x.hip, which deal their tiles statically and keep no scheduler state at all.)
+// Also in this file: the output-channel split of the 8 x 16 kernels for grids smaller than the chip (NT16 < NTF, launch_p).
+// (Round 2's persistent conv kernel k_conv_pp, with its per-XCD ticket scheduler in device memory owned by the weights handle, is
+// gone: full-size grids now run the wide persistent kernels of k_mfma16x.hip, which deal their tiles statically and keep no
+// scheduler state at all.)
 // Hazards hipcc cannot see inside asm are covered by hand: s_nop between a VALU write and an asm MFMA that reads it as C, an
 // asm statement that keeps the C operand's registers live (and waits) behind the MFMAs that read them, s_nop before the
 // epilogue reads the accumulators.
 #include <algorithm>
-#include <cstdlib>
 #include <type_traits>
 
 #include "k_common.hpp"
@@ -50,7 +68,6 @@ struct Ring {
 #define SICN_MFMA_V(ACC, A, B) asm volatile("v_mfma_i32_16x16x64_i8 %0, %1, %2, %0" : "+v"(ACC) : "v"(A), "v"(B))
 #define SICN_MFMA_V_C(ACC, A, B, C) asm volatile("v_mfma_i32_16x16x64_i8 %0, %1, %2, %3" : "=&v"(ACC) : "v"(A), "v"(B), "v"(C))
 
-constexpr int PAD_TILES_P = 24;   // zero tiles behind a weight stream (k_mfma16.hip: PAD16)
 template <int NT16>
 struct WTile {
     static constexpr int TB = NT16 * 16 * KSTEP;     // 4096 / 6144 bytes
@@ -89,16 +106,9 @@ __device__ __forceinline__ void load_wtile_p(uint8_t *ring, const int8_t *wstrea
 template <int TX, int NT16, int VMCNT, int EXTRA, bool FIRST, bool WDB, typename Dma>
 __device__ __forceinline__ void pass_p(v4i (&acc)[Geo<TX>::NC][NT16], const v4i (&wc)[NT16], v4i (&wn)[NT16], const v4i (&pc)[Geo<TX>::NC],
                                        v4i (&pn)[Geo<TX>::NC], const uint8_t *pix_next, const uint8_t *wt_next, bool extra,
-                                       const v4i (&bias4)[NT16 / 4], Dma dma, unsigned long long *st = nullptr)
+                                       const v4i (&bias4)[NT16 / 4], Dma dma)
 {
     constexpr int PX = Geo<TX>::PX, NC = Geo<TX>::NC, XT = Geo<TX>::XT;
-#if defined(SICN_STAMP) && SICN_STAMP > 1   // diagnostic build only (tools/pass_stamps.py): st = {last stamp, sum of issue phases, sum of wait + barrier phases}; level 2 stamps every pass (and slows the kernel 2.4 x: an s_memtime drains lgkmcnt)
-    if (st) {
-        const unsigned long long now = __builtin_amdgcn_s_memtime();
-        st[2] += now - st[0];
-        st[0] = now;
-    }
-#endif
     // WDB: weights double-buffered (wn != wc)
     auto fetch = [&](auto r_tag) {           // read number r of the next pass: the NC pixel fragments first, then the weights
         constexpr int r = decltype(r_tag)::value;
@@ -143,45 +153,18 @@ __device__ __forceinline__ void pass_p(v4i (&acc)[Geo<TX>::NC][NT16], const v4i 
 #undef SICN_F
             }
         }
-#ifndef SICN_X_DMA_AT
-#define SICN_X_DMA_AT 0   // the MFMA group behind which a pass issues its LDS-DMA requests (experiment knob: 2 / 4 / 7 measured within 1 % of 0)
-#endif
-        if (j == (SICN_X_DMA_AT < NT16 ? SICN_X_DMA_AT : NT16 - 1)) dma();
+        // the MFMA group behind which a pass issues its LDS-DMA requests (groups 2 / 4 / 7 measured within 1 % of 0)
+        if (j == 0) dma();
     }
-#if defined(SICN_STAMP) && SICN_STAMP > 1
-    if (st) {
-        const unsigned long long now = __builtin_amdgcn_s_memtime();
-        st[1] += now - st[0];
-        st[0] = now;
-    }
-#endif
     if (EXTRA > 0 && extra)
         wait_vmcnt<VMCNT + EXTRA>();
     else
         wait_vmcnt<VMCNT>();
-#if defined(SICN_X_NOBAR)      // experiment (wrong results): what does the per-pass workgroup barrier cost?
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#elif defined(SICN_X_NOWAIT)   // experiment (wrong results): neither the counted wait's effect nor the barrier
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#else
     block_barrier();
-#endif
 }
 
-#ifdef SICN_STAMP
-__device__ unsigned long long *g_sicn_stamp = nullptr;   // [workgroup][wave][4]: total, prologue, issue, wait (cycles)
-__device__ unsigned long long g_sicn_stagger = 0;
-extern "C" int sicn_debug_stamp_buffer(void *p)
-{
-    return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_sicn_stamp), &p, sizeof p);
-}
-extern "C" int sicn_debug_stagger(unsigned long long cycles)
-{
-    return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_sicn_stagger), &cycles, sizeof cycles);
-}
-#endif
-
-// ReLU / pack / store of one accumulator set (as store_tiles16 of k_mfma16.hip); always NC * NT16 / 4 stores per wave
+// ReLU / pack / store of one accumulator set; always NC * NT16 / 4 stores per wave (positions outside the image go to an
+// out-of-range offset of a buffer descriptor, which drops them): the counted waits of the following passes rely on it
 template <int TX, int NT16>
 __device__ __forceinline__ void store_tiles_p(v4i (&acc)[Geo<TX>::NC][NT16], uint8_t *out_img, int out_img_bytes, const TensorMap &om,
                                               int MW, int MH, int Y0, int X0, int w, int pos, int g, bool deconv, int py, int px,
@@ -207,6 +190,8 @@ __device__ __forceinline__ void store_tiles_p(v4i (&acc)[Geo<TX>::NC][NT16], uin
             for (int d = 0; d < 4; d++)
                 v[d] = (int)pack4_relu7(acc[c][4 * J + d][0], acc[c][4 * J + d][1], acc[c][4 * J + d][2], acc[c][4 * J + d][3],
                                         act_floor & ACT_FLOOR_MASK);
+            // outputs far larger than the caches are stored non-temporal (aux bit 1): measured on 8 x 4K (A/B in one process,
+            // profiles/r02_ab_nt_stores.txt) layer 6 -6 % and — its consumer finds less of its own input evicted — layer 7 -8 %
             if (act_floor & ACT_NT_STORE)
                 __builtin_amdgcn_raw_buffer_store_b128(v, ro, ok ? off0 + (uint32_t)(2 * J) * om.grp : OOB, 0, 2);
             else
@@ -258,10 +243,6 @@ __global__ __launch_bounds__(256, 2) void k_deconv_p(const uint8_t *__restrict__
     const int pos = lane & 15, g = lane >> 4, hi = g >> 1, half = g & 1;
     const TileCoord tc = tile_coord<TX>(tiles_x, n_tiles, n_images, n_xcd);
     if (!tc.valid) return;   // before any LDS-DMA is issued
-#ifdef SICN_STAMP
-    unsigned long long dst[10];   // start, loop start, then (passes done, epilogue done) per phase
-    dst[0] = __builtin_amdgcn_s_memtime();
-#endif
     const int Y0 = tc.Y0, X0 = tc.X0;
     const int in_img_bytes = IH * IW * CIN, out_img_bytes = OH * OW * COUT;
     const uint8_t *in_img = in + (size_t)tc.img * in_img_bytes;
@@ -345,9 +326,6 @@ __global__ __launch_bounds__(256, 2) void k_deconv_p(const uint8_t *__restrict__
         }
         step += NQ;
     };
-#ifdef SICN_STAMP
-    dst[1] = __builtin_amdgcn_s_memtime();
-#endif
     // With an odd number of passes per tap (192 input channels) the two pixel buffers swap roles from tap to tap.  The parity
     // is kept STATIC — taps are walked in pairs, and a phase's first parity is a constant of the phase (9 / 6 / 6 / 4 taps) —
     // because a run-time parity made hipcc reconcile the two register assignments with v_mov copies right in front of and
@@ -394,29 +372,20 @@ SICN_DECONV_TAP_LOOP
                 if (t < ntap) one(std::integral_constant<int, 1>{}, t);
             }
         }
-#ifdef SICN_STAMP
-        dst[2 + 2 * ph] = __builtin_amdgcn_s_memtime();
-#endif
         if (ph == 3) wait_vmcnt<0>();  // the padded tail of the weight prefetch must land before exit
         store_tiles_p<TX, NT16>(acc, out_img, out_img_bytes, om, IW, IH, Y0, X0, w, pos, g, true, py, px, act_floor,
                                 (uint32_t)(split * (COUTW / 32)));
-#ifdef SICN_STAMP
-        dst[3 + 2 * ph] = __builtin_amdgcn_s_memtime();
-#endif
     }
-#ifdef SICN_STAMP
-    if (g_sicn_stamp && lane == 0) {
-        unsigned long long *o = g_sicn_stamp + ((size_t)blockIdx.x * 4 + w) * 12;
-#pragma unroll
-        for (int i = 0; i < 10; i++) o[i] = dst[i];
-    }
-#endif
 }
 
 // =====================================================================================================================
-// conv2d<>: K walk, parity planes and their rolling refresh as in k_mfma16.hip; all 25 NQ / 2 passes of a tile unrolled (tap
-// offsets and refresh slots are compile-time, and the two pixel buffers alternate while a 25-pass window is odd)
+// conv2d<>: K walk over the 4 parity planes of a channel group, with their rolling refresh; all 25 NQ / 2 passes of a tile
+// unrolled (tap offsets and refresh slots are compile-time, and the two pixel buffers alternate while a 25-pass window is odd)
 // =====================================================================================================================
+// refresh schedule of the 4 parity planes in a 25-step channel group, S = Geo::SLOTS steps per plane (one piece per wave and
+// step).  A plane may only be re-filled from the pass AFTER the one that holds its last read, whatever the step parity of the
+// group is, i.e. from (last read step + 2): plane 0 (last read 8) from step 10, plane 1 (14) from 16, plane 2 (20) from 22,
+// plane 3 (24) from step 1 of the NEXT group.
 __host__ __device__ constexpr int refresh_start_p(int plane) { return plane == 3 ? 1 : plane == 0 ? 10 : plane == 1 ? 16 : 22; }
 __host__ __device__ constexpr int refresh_plane_p(int t, int S)
 {
@@ -453,7 +422,6 @@ struct ConvPCtx {
     const uint8_t *lane_pix, *lane_wt;
     uint32_t qstride;
     int lane, w, hi;
-    unsigned long long *st;   // SICN_STAMP builds: this wave's stamp sums (nullptr otherwise)
 };
 
 template <int TX, int NT16, int NTF, int PF, int P, int NPASS>
@@ -481,7 +449,7 @@ __device__ __forceinline__ void conv_pass_p(v4i (&acc)[Geo<TX>::NC][NT16], const
     const v4i none[NT16 / 4] = {};
     // everything but the requests of the last FLIGHT passes has landed at the barrier (= what pass P+2's fetch needs; a plane
     // refresh piece is requested at least 8 passes before its first read)
-    pass_p<TX, NT16, conv_in_flight_p<TX, NT16>(P, Ring<PF>::FLIGHT), 0, false, TX == 16>(acc, wc, wn, pc, pn, pixn, wtn, false, none, dma, c.st);
+    pass_p<TX, NT16, conv_in_flight_p<TX, NT16>(P, Ring<PF>::FLIGHT), 0, false, TX == 16>(acc, wc, wn, pc, pn, pixn, wtn, false, none, dma);
 }
 
 template <int TX, int NT16, int NTF, int PF, int P, int NPASS>
@@ -529,19 +497,8 @@ __global__ __launch_bounds__(256, 2) void k_conv_p(const uint8_t *__restrict__ i
             const PieceSrc ps = piece_src<TX>(im, slot * 4 + w, lane, Y0 - 1, X0 - 1, 2, pl >> 1, pl & 1, IW, IH);
             poff[pl][slot] = ps.ok ? ps.off : OOB;
         }
-#ifdef SICN_STAMP
-    unsigned long long st[3] = {0, 0, 0};
-    if (g_sicn_stagger && blockIdx.x >= 256 && blockIdx.x < 512) {   // experiment: put a CU's two workgroups out of phase
-        const unsigned long long t_wait = __builtin_amdgcn_s_memtime() + g_sicn_stagger;
-        while (__builtin_amdgcn_s_memtime() < t_wait) __builtin_amdgcn_s_sleep(32);
-    }
-    const unsigned long long t_start = __builtin_amdgcn_s_memtime();
-    unsigned long long *stp = st;
-#else
-    unsigned long long *stp = nullptr;
-#endif
     const ConvPCtx ctx{patch, ring, wstream, in_img, in_img_bytes, patch + (uint32_t)(((2 * w) * PX + pos) * 32 + half * 16),
-                       ring + (uint32_t)(pos * 32 + half * 16), im.grp, lane, w, hi, stp};
+                       ring + (uint32_t)(pos * 32 + half * 16), im.grp, lane, w, hi};
     // ---- prologue: planes 0..2 of group 0 (plane 3 arrives in steps 1..) + PFP weight tiles ------------------------------
 #pragma unroll
     for (int pl = 0; pl < 3; pl++)
@@ -581,37 +538,10 @@ __global__ __launch_bounds__(256, 2) void k_conv_p(const uint8_t *__restrict__ i
 #pragma unroll
         for (int j = 0; j < NT16; j++) asm volatile("" : "+v"(acc[c][j]));
     asm volatile("s_nop 3" ::: "memory");
-#ifdef SICN_STAMP
-    st[0] = __builtin_amdgcn_s_memtime();
-    const unsigned long long t_loop = st[0], r_loop = __builtin_amdgcn_s_memrealtime();
-#endif
     conv_passes_p<TX, NT16, NTF, PF, 0, NPASS>(acc, wbuf, pa, pb, ctx, poff);
-#ifdef SICN_STAMP
-    const unsigned long long t_loop_end = __builtin_amdgcn_s_memtime(), r_loop_end = __builtin_amdgcn_s_memrealtime();
-#endif
     wait_vmcnt<0>();
     store_tiles_p<TX, NT16>(acc, out_img, out_img_bytes, om, OW, OH, Y0, X0, w, pos, g, false, 0, 0, act_floor,
                             (uint32_t)(split * (COUTW / 32)));
-#ifdef SICN_STAMP
-    if (g_sicn_stamp && lane == 0) {
-        const unsigned long long t_end = __builtin_amdgcn_s_memtime();
-        unsigned long long *o = g_sicn_stamp + ((size_t)blockIdx.x * 4 + w) * 8;
-        o[6] = __builtin_amdgcn_s_getreg(4 | (31 << 11));    // HW_REG_HW_ID: wave[3:0] simd[5:4] pipe[7:6] cu[11:8] sh[12] se[15:13] ..
-        o[7] = __builtin_amdgcn_s_getreg(20 | (31 << 11));   // HW_REG_XCC_ID
-        o[0] = t_end - t_start;      // whole workgroup life of this wave
-        o[1] = t_loop - t_start;     // prologue (patch + weight ring requests, their latency, first fragments)
-#if SICN_STAMP > 1
-        o[2] = st[1];                // passes: first MFMA .. last fragment read issued
-        o[3] = st[2] + (t_end - st[0]);   // passes: vmcnt wait + barrier; + the epilogue (ReLU, pack, stores issued)
-        o[4] = t_end - st[0];        // the epilogue alone
-#else
-        o[2] = t_loop_end - t_loop;  // all passes (level 1: two stamps around the loop, no perturbation inside)
-        o[3] = r_loop_end - r_loop;  // the loop again, in 100 MHz ticks (-> the clock the chip held)
-        o[4] = t_end - t_loop_end;   // epilogue: last barrier .. stores issued
-#endif
-        o[5] = t_start;
-    }
-#endif
 }
 
 // ---- launchers ---------------------------------------------------------------------------------------------------------
@@ -627,17 +557,11 @@ static hipError_t launch_p(const LayerGeom &g, const sicn_weights &w, const uint
     // (1080p: layer 6 51 vs 48 us; round 4, the channel-split kernels at 256^2 ... 1080p with 12 / 16 / 24 slots: no gain either):
     // the weight stream's latency is not what bounds a pass there
     constexpr int PF = 8;
-    static_assert(PF <= PAD_TILES_P, "prefetch would run off the weight stream");
+    static_assert(PF <= PAD16, "prefetch would run off the weight stream");
     const int MW = DECONV ? g.IW : g.OW, MH = DECONV ? g.IH : g.OH;
     const int tiles_x = (MW + TX - 1) / TX, tiles_y = (MH + TILE_Y - 1) / TILE_Y;
-    constexpr size_t lds_need = (size_t)NSUB * Geo<TX>::ALLOC + (size_t)PF * WTile<NT16>::TB;
-    static_assert(lds_need <= 80 * 1024, "two workgroups per CU");
-#ifdef SICN_STAMP   // diagnostic build: SICN_X_LDS_PAD bytes of unused LDS force one workgroup per CU (a wave's solo pass rate)
-    static const size_t lds_pad = getenv("SICN_X_LDS_PAD") ? (size_t)atoi(getenv("SICN_X_LDS_PAD")) : 0;
-    const size_t lds = lds_need + lds_pad;
-#else
-    constexpr size_t lds = lds_need;
-#endif
+    constexpr size_t lds = (size_t)NSUB * Geo<TX>::ALLOC + (size_t)PF * WTile<NT16>::TB;
+    static_assert(lds <= 80 * 1024, "two workgroups per CU");
     const uint32_t flags = (relu ? ACT_FLOOR_RELU : ACT_FLOOR_RAW) |
                            (nt_store_wanted((size_t)g.OH * g.OW * g.COUT * n_images) ? ACT_NT_STORE : 0u);
     const dim3 grid(xcd_grid_size((long)tiles_x * tiles_y * n_images, chip.n_xcd), NTF / NT16);

@@ -66,11 +66,6 @@ __device__ __forceinline__ v4i lds_read(uint32_t addr)
     return v;
 }
 
-#ifdef SICN_STAMP   // diagnostic build only (tools/x_stamps.py): per workgroup {cycles, 100 MHz ticks, tiles, hand-over cycles, start, HW_ID, XCC_ID}
-__device__ unsigned long long *g_sicn_stamp_x = nullptr;
-extern "C" int sicn_debug_stamp_buffer_x(void *p) { return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_sicn_stamp_x), &p, sizeof p); }
-#endif
-
 // ---- what an accumulator hand-over needs ------------------------------------------------------------------------------------
 struct HandX {
     __amdgpu_buffer_rsrc_t ro;   // the output image
@@ -167,10 +162,8 @@ __device__ __forceinline__ void pass_x(v4i (&acc)[8][8], const v4i (&pc)[8], con
             for (int J = 0; J < 2; J++) {
                 const int k = 2 * i + J;
                 v4i old[4];
-#ifndef SICN_XW_NOREAD
 #pragma unroll
                 for (int d = 0; d < 4; d++) old[d] = acc[i][4 * J + d];   // read out (v_accvgpr_read) in front of the tied MFMA below
-#endif
                 v4i v;
                 // a tile that lives in VGPRs is packed straight from its registers, BEFORE the tied MFMA overwrites them (packed
                 // behind it, hipcc would copy the four registers first)
@@ -187,21 +180,10 @@ __device__ __forceinline__ void pass_x(v4i (&acc)[8][8], const v4i (&pc)[8], con
                     else
                         SICN_MFMA_VC(acc[i][4 * J + d], wc[4 * J + d], pc[i], bias.c[4 * J + d]);
                 }
-#if defined(SICN_XW_NOPACK)    // timing experiments (wrong results): what of the hand-over costs what
-#pragma unroll
-                for (int d = 0; d < 4; d++) v[d] = old[d][0] ^ old[d][1] ^ old[d][2] ^ old[d][3];
-#elif defined(SICN_XW_NOREAD)
-                v = v4i{1, 2, 3, 4};
-#else
 #pragma unroll
                 for (int d = 0; d < 4; d++)
                     if (4 * J + d < JV) v[d] = (int)pack4_sdwa(old[d], (int)h.floor2);
-#endif
-#ifdef SICN_XW_NOSTORE
-                asm volatile("" ::"v"(v));
-#else
                 __builtin_amdgcn_raw_buffer_store_b128(v, h.ro, h.off[i], h.soff + (uint32_t)J * h.grp2, NT ? 2 : 0);
-#endif
                 switch (k) {
 #define SICN_R(R) case R: rd(std::integral_constant<int, R>{}); break;
                     SICN_R(0) SICN_R(1) SICN_R(2) SICN_R(3) SICN_R(4) SICN_R(5) SICN_R(6) SICN_R(7)
@@ -216,18 +198,10 @@ __device__ __forceinline__ void pass_x(v4i (&acc)[8][8], const v4i (&pc)[8], con
             }
         }
     }
-#if defined(SICN_XW_NOWAIT)   // timing experiment (wrong results): never wait for a request
-    wait_vmcnt<48>();
-#else
-#ifdef SICN_XW_NOSTORE
-    if (false)
-#else
     if (EXTRA > 0 && stores)
-#endif
         wait_vmcnt<VM + EXTRA>();
     else
         wait_vmcnt<VM>();
-#endif
     block_barrier();   // lgkmcnt(0) (this wave's reads of the next pass are complete) + s_barrier
 }
 
@@ -238,14 +212,12 @@ struct TileX {
 // Workgroups of a persistent launch start together and take the same time per tile: without help all 256 CUs reach their
 // accumulator hand-overs at the same moment and 16 MB of output stores hit the memory system in one burst (in-kernel stamps:
 // a hand-over pass took 5600 - 8300 cycles against ~2900 of instruction issue).  Each workgroup therefore starts a different
-// fraction of SICN_XW_STAGGER x 2048 cycles late (slot s of an XCD's 32: s / 32 of it), which spreads the bursts for good.
-#ifndef SICN_XW_STAGGER
-#define SICN_XW_STAGGER 8
-#endif
+// fraction of STAGGER x 2048 cycles late (slot s of an XCD's 32: s / 32 of it), which spreads the bursts for good.
+constexpr int STAGGER = 8;
 __device__ __forceinline__ void stagger_x(int n_xcd)
 {
     const int slot = ((int)blockIdx.x / n_xcd) & 31;
-    for (int i = 0; i < slot * SICN_XW_STAGGER; i++) __builtin_amdgcn_s_sleep(1);   // 64 cycles each
+    for (int i = 0; i < slot * STAGGER; i++) __builtin_amdgcn_s_sleep(1);   // 64 cycles each
 }
 
 // per-fragment output offsets of a tile: pixel fragment c = row 4 w + (c >> 1), column tile c & 1 of the 16 x 32 positions;
@@ -532,12 +504,7 @@ __device__ __forceinline__ void conv_pass_x(v4i (&acc)[8][8], const v4i (&pc)[8]
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, c.ring_w + slot * TB, 16, c.lane_w16, (uint32_t)(step * TB), 0, 0);
         } else {
             constexpr Refresh r = refresh_x(P, idx - 2);
-#ifdef SICN_XW_NOPLANE   // timing experiment (wrong results): the passes without their plane requests
-            constexpr bool plane_dma = false;
-#else
-            constexpr bool plane_dma = true;
-#endif
-            if constexpr (r.plane >= 0 && plane_dma) {
+            if constexpr (r.plane >= 0) {
                 // group of the piece: window WIN holds groups 2 WIN, 2 WIN + 1; NEXT0 of the second window = group 0 (of the next tile)
                 constexpr int q = r.kind == K_CUR0 ? 2 * WIN : r.kind == K_CUR1 ? 2 * WIN + 1 : (2 * WIN + 2) % 4;
                 __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)c.dma_img, 0, c.img_bytes, 0x00020000);
@@ -546,11 +513,7 @@ __device__ __forceinline__ void conv_pass_x(v4i (&acc)[8][8], const v4i (&pc)[8]
             }
         }
     };
-#ifdef SICN_XW_NOPLANE
-    constexpr int VM = 2 * FLIGHT;
-#else
     constexpr int VM = in_flight_x(P);
-#endif
     pass_x<KIND, VM, (T < FLIGHT ? NSTORE : 0), NT>(acc, pc, wc, rd, dma, stores, h, bias);
 }
 
@@ -657,11 +620,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         }
     asm volatile("s_nop 3" ::: "memory");   // v_accvgpr_write / v_mov -> asm MFMA reading it as SrcC
     conv_pass_x<0, 0, NT>(acc, pa, wa, pb, wb, ctx, poff, false, h, bias);
-#ifdef SICN_STAMP
-    const unsigned long long st_t0 = __builtin_amdgcn_s_memtime(), st_r0 = __builtin_amdgcn_s_memrealtime();
-    unsigned long long st_hand = 0;
-    int st_tiles = 1;
-#endif
     bool stores = false;   // a hand-over's stores may be in flight (not in the first tile)
     int tile_no = 0;         // tiles this workgroup has finished (DealX: the mailbox's sequence numbers)
     uint32_t deal_tk = DEAL_PENDING;
@@ -707,34 +665,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         // pass 0 of the next tile with the hand-over of this one woven in (after the last tile: the same pass on zero-filled
         // planes, whose results nobody reads — one pass in 32 tiles, and the tile loop stays one body)
         asm volatile("s_nop 7" ::: "memory");   // the last MFMAs' results -> v_accvgpr_read
-#ifdef SICN_STAMP
-        const unsigned long long st_p0 = __builtin_amdgcn_s_memtime();
-#endif
         conv_pass_x<0, 2, NT>(acc, pa, wa, pb, wb, ctx, poff, true, h, bias);
         stores = true;
-#ifdef SICN_STAMP
-        st_hand += __builtin_amdgcn_s_memtime() - st_p0;
-#endif
         if (!has_next) break;
         item = next;
         tc = tn;
         tile_no++;
-#ifdef SICN_STAMP
-        st_tiles++;
-#endif
     }
-#ifdef SICN_STAMP
-    if (g_sicn_stamp_x && tid == 0) {
-        unsigned long long *o = g_sicn_stamp_x + (size_t)blockIdx.x * 8 + 2048 * (n_tiles > 500 ? 0 : 1);   // slot 0 / 1: the larger / smaller conv of the 8 x 4K net
-        o[0] = __builtin_amdgcn_s_memtime() - st_t0;
-        o[1] = __builtin_amdgcn_s_memrealtime() - st_r0;
-        o[2] = (unsigned long long)st_tiles;
-        o[3] = st_hand;
-        o[4] = st_t0;
-        o[5] = __builtin_amdgcn_s_getreg(4 | (31 << 11));    // HW_REG_HW_ID
-        o[6] = __builtin_amdgcn_s_getreg(20 | (31 << 11));   // HW_REG_XCC_ID
-    }
-#endif
     wait_vmcnt<0>();   // the wrapped tail of the prefetch (weights, out-of-range plane pieces) must land before the LDS is released
 }
 
@@ -977,11 +914,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         }
     asm volatile("s_nop 3" ::: "memory");   // v_accvgpr_write / v_mov -> asm MFMA reading it as SrcC
     deconv_pass_x<0, 0, NT>(acc, pa, wa, pb, wb, ctx, poff_cur, poff_next, false, h, bias);
-#ifdef SICN_STAMP
-    const unsigned long long st_t0 = __builtin_amdgcn_s_memtime(), st_r0 = __builtin_amdgcn_s_memrealtime();
-    unsigned long long st_hand = 0;
-    int st_tiles = 1;
-#endif
     bool stores = false;   // a hand-over's stores may be in flight (in the first tile: from its phase 1 on)
     int tile_no = 0;         // tiles this workgroup has finished (DealX: the mailbox's sequence numbers)
     uint32_t deal_tk = DEAL_PENDING;
@@ -1061,16 +993,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         ctx.cur_img = ctx.next_img;
 #pragma unroll
         for (int s = 0; s < SLOTS; s++) poff_cur[s] = poff_next[s];
-#ifdef SICN_STAMP
-        const unsigned long long st_p0 = __builtin_amdgcn_s_memtime();
-#endif
         // pass 0 of the next tile with the hand-over of this tile's phase 3 woven in (after the last tile: on a zero-filled patch)
         deconv_pass_x<0, 2, NT>(acc, pa, wa, pb, wb, ctx, poff_cur, poff_next, true, h, bias);
 #undef SICN_DP
         stores = true;
-#ifdef SICN_STAMP
-        st_hand += __builtin_amdgcn_s_memtime() - st_p0;
-#endif
         if (!has_next) break;
         item = next;
         tc = tn;
@@ -1080,22 +1006,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             has_next = next < item_end;
             tn = coord(has_next ? next : item);
         }
-#ifdef SICN_STAMP
-        st_tiles++;
-#endif
     }
-#ifdef SICN_STAMP
-    if (g_sicn_stamp_x && tid == 0) {
-        unsigned long long *o = g_sicn_stamp_x + (size_t)blockIdx.x * 8 + 2048 * (n_tiles > 500 ? 2 : 3);   // slot 2 / 3: the larger / smaller deconv
-        o[0] = __builtin_amdgcn_s_memtime() - st_t0;
-        o[1] = __builtin_amdgcn_s_memrealtime() - st_r0;
-        o[2] = (unsigned long long)st_tiles;
-        o[3] = st_hand;
-        o[4] = st_t0;
-        o[5] = __builtin_amdgcn_s_getreg(4 | (31 << 11));
-        o[6] = __builtin_amdgcn_s_getreg(20 | (31 << 11));
-    }
-#endif
     wait_vmcnt<0>();
 }
 

@@ -108,7 +108,6 @@ __global__ __launch_bounds__(256, 2) void k_l0(const uint8_t *__restrict__ in, u
                 acc[1][j][r] = bv;
             }
         }
-#ifndef SICN_EXP_L0_NO_MFMA   // experiment builds only (tools/ab_libs.sh)
 #pragma unroll
         for (int ky = 0; ky < 5; ky++) {
             v4i wf[NTJ], pf[2];
@@ -126,7 +125,6 @@ __global__ __launch_bounds__(256, 2) void k_l0(const uint8_t *__restrict__ in, u
                 for (int i = 0; i < 2; i++)
                     acc[i][j] = __builtin_amdgcn_mfma_i32_32x32x32_i8(wf[j], pf[i], acc[i][j], 0, 0, 0);
         }
-#endif
         __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc((void *)out_img, 0, OH * OW * COUT, 0x00020000);
 #pragma unroll
         for (int i = 0; i < 2; i++) {
@@ -141,12 +139,7 @@ __global__ __launch_bounds__(256, 2) void k_l0(const uint8_t *__restrict__ in, u
                 v[2] = (int)pack4_relu7(a[8], a[9], a[10], a[11], act_floor & ACT_FLOOR_MASK);
                 v[3] = (int)pack4_relu7(a[12], a[13], a[14], a[15], act_floor & ACT_FLOOR_MASK);
                 const uint32_t off = ok ? tensor_offset(om, gy, gx, (uint32_t)j) + 16u * kh : OOB;
-#ifdef SICN_L0_NT
-                if (act_floor & ACT_NT_STORE)
-                    __builtin_amdgcn_raw_buffer_store_b128(v, ro, off, 0, 2);
-                else
-#endif
-                    __builtin_amdgcn_raw_buffer_store_b128(v, ro, off, 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b128(v, ro, off, 0, 0);
             }
         }
         block_barrier();  // next patch complete, this patch free (raw barrier: the stores stay in flight)
@@ -227,22 +220,13 @@ hipError_t launch_l0(const LayerGeom &g, const sicn_weights &w, const uint8_t *i
 //     through a buffer descriptor (masked lanes = out of range), so a step always issues exactly
 //     two stores and the wait for the prefetched rows is a counted vmcnt that leaves them in flight.
 // =============================================================================================
-#ifndef SICN_L7_AUX
-#define SICN_L7_AUX 0
-#endif
-#ifndef SICN_EXP_L7_STORE
-#define SICN_EXP_L7_STORE 0
-#endif
-constexpr int L7_AUX = SICN_L7_AUX;                       // cache policy of the input stream (2 = nt)
+constexpr int L7_AUX = 0;                                // cache policy of the input stream (2 = nt)
 constexpr int L7_PITCH = 36;                             // positions per window row (34 used)
 constexpr int L7_ROWS = 4;                               // input rows per step
 constexpr int L7_STEP_PIECES = L7_ROWS * L7_PITCH / 16;  // 9 LDS-DMA pieces per region per step
-#ifndef SICN_L7_AHEAD
-#define SICN_L7_AHEAD 1
-#endif
-constexpr int L7_AHEAD = SICN_L7_AHEAD;                  // steps of rows in flight ahead of the step being computed
+constexpr int L7_AHEAD = 1;                              // steps of rows in flight ahead of the step being computed
 constexpr int L7_RING_PIECES = ((4 * L7_AHEAD + 6) * L7_PITCH + 15) / 16;   // 1 ahead: 23 pieces = 368 positions >= 10 rows
-constexpr int L7_WGS = L7_AHEAD == 1 ? 3 : 2;            // workgroups per CU the LDS ring allows
+constexpr int L7_WGS = 3;                                // workgroups per CU the LDS ring allows (1 step ahead)
 constexpr int L7_RING_POS = L7_RING_PIECES * 16;
 constexpr int L7_REGION = L7_RING_PIECES * 1024;
 constexpr int L7_STAGE = 2 * 192;                        // 2 output rows x 64 pixels x 3 B per wave
@@ -279,12 +263,6 @@ __device__ __forceinline__ void l7_load_rows(uint8_t *patch, uint8_t *scratch, c
     }
 }
 
-#ifdef SICN_EXP_L7_STAMP   // diagnostic build: cycles per phase of a step, summed over all waves and steps (s_memtime)
-__device__ unsigned long long g_l7_stamp[8];
-#define L7_T(i) { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); st_[i] += t_ - tp_; tp_ = t_; }
-#else
-#define L7_T(i)
-#endif
 __device__ __forceinline__ void l7_body(const uint8_t *__restrict__ in, uint8_t *__restrict__ out, const int8_t *__restrict__ w_l7,
                                         const int8_t *__restrict__ bias, int IW, int IH, int OW, int OH, int steps_y, int y_chunks,
                                         int tiles_x, int n_images, int in_layout, int n_xcd)
@@ -351,25 +329,12 @@ __device__ __forceinline__ void l7_body(const uint8_t *__restrict__ in, uint8_t 
     block_barrier();
 
     int base = 0;                          // (144 t) mod ring: ring slot of window row 4t, column 0
-#ifdef SICN_EXP_L7_STAMP
-    unsigned long long st_[6] = {0, 0, 0, 0, 0, 0}, tp_ = __builtin_amdgcn_s_memtime();
-#endif
     for (int s = s_begin; s < s_end; s++) {
         const int Y = 4 * s;               // first input row of this step
         // always issued (rows past the chunk are zero fill): the counted waits below rely on it
         l7_load_rows<5>(patch, scratch, in_img, in_img_bytes, w, lane, L7_STEP_PIECES, ynext, 0, iy_max, pnext, X0, IW, tm);
         ynext += L7_ROWS;
-        L7_T(0)   // the row requests (address arithmetic + issue)
 
-#ifdef SICN_EXP_L7_DMA_ONLY   // timing experiment (wrong bytes): the row requests, their counted wait and the barrier, nothing else
-        wait_vmcnt<5 * (L7_AHEAD - 1)>();
-        block_barrier();
-        base += L7_ROWS * L7_PITCH;
-        base = base >= L7_RING_POS ? base - L7_RING_POS : base;
-        pnext += L7_STEP_PIECES;
-        pnext = pnext >= L7_RING_PIECES ? pnext - L7_RING_PIECES : pnext;
-        continue;
-#endif
         v4i acc[2];
         acc[0] = acc[1] = v4i{b0, b1, b2, 0};  // C row 4*kg + r = phase kg, channel r
 #pragma unroll
@@ -379,25 +344,13 @@ __device__ __forceinline__ void l7_body(const uint8_t *__restrict__ in, uint8_t 
                 uint32_t slot = (uint32_t)base + fa[tap] + 16u * c;
                 slot = min(slot, slot - (uint32_t)L7_RING_POS);   // one wrap at most
                 const uint32_t addr = slot * 64u + fs[tap];
-#if defined(SICN_EXP_L7_READS_ONLY)   // timing experiments (wrong bytes): the fragment reads without the MFMAs ...
-                const v4i p0 = *(const v4i *)(patch + addr);
-                const v4i p1 = *(const v4i *)(patch + (addr ^ 32u));
-                acc[c][0] ^= p0[0] ^ p1[3];
-                acc[c][1] ^= p0[1] ^ p1[2];
-#elif defined(SICN_EXP_L7_MFMA_ONLY)    // ... and the MFMAs without the fragment reads
-                acc[c] = __builtin_amdgcn_mfma_i32_16x16x64_i8(wf[tap * 2 + 0], wf[(tap * 2 + 5) % 18], acc[c], 0, 0, 0);
-                acc[c] = __builtin_amdgcn_mfma_i32_16x16x64_i8(wf[tap * 2 + 1], wf[(tap * 2 + 7) % 18], acc[c], 0, 0, 0);
-                (void)addr;
-#elif !defined(SICN_EXP_L7_NO_MFMA)
                 const v4i p0 = *(const v4i *)(patch + addr);
                 const v4i p1 = *(const v4i *)(patch + (addr ^ 32u));   // channels 64..127: c2 ^ 2
                 acc[c] = __builtin_amdgcn_mfma_i32_16x16x64_i8(wf[tap * 2 + 0], p0, acc[c], 0, 0, 0);
                 acc[c] = __builtin_amdgcn_mfma_i32_16x16x64_i8(wf[tap * 2 + 1], p1, acc[c], 0, 0, 0);
-#endif
             }
         }
         asm volatile("" :: "v"(acc[0]), "v"(acc[1]));
-        L7_T(1)   // fragment reads + MFMAs issued
         // ---- epilogue ----------------------------------------------------------------------
         const int gy = Y + w;
         if (fast_rows) {
@@ -418,21 +371,11 @@ __device__ __forceinline__ void l7_body(const uint8_t *__restrict__ in, uint8_t 
                 const int row = idx >= 48 ? 1 : 0, col = idx - 48 * row;
                 const bool ok = idx < 96 && gy < IH;
                 const uint32_t v = *(const uint32_t *)(my_stage + (idx < 96 ? idx : 0) * 4);
-                uint32_t off = ok ? (uint32_t)(((2 * gy + row) * OW + 2 * X0) * 3 + col * 4) : OOB;
-#if SICN_EXP_L7_STORE == 2   // timing experiment (wrong bytes): the same stores, all into the first 256 KiB (no HBM write traffic)
-                off = ok ? (off & 0x3FFFCu) : OOB;
-#endif
-#if SICN_EXP_L7_STORE != 1   // 1 = timing experiment without the stores
+                const uint32_t off = ok ? (uint32_t)(((2 * gy + row) * OW + 2 * X0) * 3 + col * 4) : OOB;
                 __builtin_amdgcn_raw_buffer_store_b32(v, ro, off, 0, 0);
-#endif
             }
-            L7_T(2)   // pack, staging, stores issued
             // leave in flight: this step's 2 stores and the AHEAD-1 younger row blocks (5 loads + 2 stores each)
-#if SICN_EXP_L7_STORE == 1
-            wait_vmcnt<5 * (L7_AHEAD - 1)>();
-#else
             wait_vmcnt<2 + 7 * (L7_AHEAD - 1)>();
-#endif
         } else {
 #pragma unroll
             for (int c = 0; c < 2; c++) {
@@ -447,23 +390,13 @@ __device__ __forceinline__ void l7_body(const uint8_t *__restrict__ in, uint8_t 
             }
             wait_vmcnt<0>();
         }
-        L7_T(3)   // counted wait for the next rows
-#ifndef SICN_EXP_L7_NO_BARRIER   // timing experiment only (races)
         block_barrier();   // next rows landed for every wave, this step's rows are free
-#endif
-        L7_T(4)   // barrier
         base += L7_ROWS * L7_PITCH;
         base = base >= L7_RING_POS ? base - L7_RING_POS : base;
         pnext += L7_STEP_PIECES;
         pnext = pnext >= L7_RING_PIECES ? pnext - L7_RING_PIECES : pnext;
     }
     wait_vmcnt<0>();   // the zero-fill tail of the prefetch must land before the LDS is released
-#ifdef SICN_EXP_L7_STAMP
-    if (lane == 0) {
-        for (int i = 0; i < 5; i++) atomicAdd(&g_l7_stamp[i], st_[i]);
-        atomicAdd(&g_l7_stamp[5], (unsigned long long)(s_end - s_begin));
-    }
-#endif
 }
 __global__ __launch_bounds__(256, L7_WGS) void k_l7(const uint8_t *__restrict__ in, uint8_t *__restrict__ out, const int8_t *__restrict__ w_l7,
                                                     const int8_t *__restrict__ bias, int IW, int IH, int OW, int OH, int steps_y, int y_chunks,
@@ -471,15 +404,6 @@ __global__ __launch_bounds__(256, L7_WGS) void k_l7(const uint8_t *__restrict__ 
 {
     l7_body(in, out, w_l7, bias, IW, IH, OW, OH, steps_y, y_chunks, tiles_x, n_images, in_layout, n_xcd);
 }
-
-#ifdef SICN_EXP_L7_STAMP
-extern "C" int sicn_debug_l7_stamps(unsigned long long *out8)   // reads and clears the sums
-{
-    unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (hipMemcpyFromSymbol(out8, HIP_SYMBOL(g_l7_stamp), sizeof z) != hipSuccess) return -1;
-    return hipMemcpyToSymbol(HIP_SYMBOL(g_l7_stamp), z, sizeof z) == hipSuccess ? 0 : -1;
-}
-#endif
 
 size_t l7_bytes(int cin) { return (size_t)18 * 16 * 64 * (cin / 128); }
 

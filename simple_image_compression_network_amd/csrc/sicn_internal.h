@@ -57,8 +57,8 @@ hipError_t launch_zero_words(unsigned long long *p, size_t words, hipStream_t st
 
 // what plan_mfma (k_mfma16.hip) decides for a conv / deconv layer of the 128 / 192-channel shapes
 struct MfmaPlan {
-    int family;      // 0: k_mfma16_t, 1: the software-pipelined kernels (k_mfma16p.hip), 2: the wide persistent kernels (k_mfma16x.hip)
-    int tile_x;      // 16 | 32 (families 0, 1)
+    int family;      // 1: the software-pipelined kernels (k_mfma16p.hip), 2: the wide persistent kernels (k_mfma16x.hip)
+    int tile_x;      // 16 | 32 (family 1)
     int split_n;     // output-channel slices (workgroups of blockIdx.y), 1 = none
     unsigned grid_x, grid_y, grid_z;
     int deal;        // family 2: 1 where the tile deal has its dynamic part (sicn_plan.h wide_deal_pays), given a workspace with room for it

@@ -161,6 +161,35 @@ def test_launch_planning_follows_the_chip_size_without_gpu():
     assert _plan(d768[0], 1, 256)["gy"] == 32 and _plan(d768[0], 1, 32)["gy"] == 11
 
 
+def test_mfma_plans_run_only_the_pipelined_and_wide_kernels():
+    """The plain 16x16x64 kernels (family 0) are gone: every MFMA shape plans family 1 or 2 under every tile_x / prefetch /
+    wave_tile, prefetch = 1 plans exactly what prefetch = 2 does, and the 192-channel shapes (8 x 16 tiles only) plan tile_x = 16
+    even when 32 is asked for — no GPU needed."""
+    from simple_image_compression_network_amd.config import LayerDesc
+
+    def desc(cin, cout, simd, pe, w, h, tr):
+        ow, oh = (2 * w, 2 * h) if tr else ((w + 1) // 2, (h + 1) // 2)
+        return LayerDesc(IFM_CH=cin, IFM_ROW=w, IFM_COL=h, OFM_CH=cout, OFM_ROW=ow, OFM_COL=oh, SIMD=simd, PE=pe,
+                         W_TILES=(cout // pe) * (25 * cin // simd), transposed=tr)
+
+    shapes = [(128, 128, 8, 16), (192, 128, 12, 16), (128, 192, 8, 24)]
+    for cin, cout, simd, pe in shapes:
+        for tr in (0, 1):
+            for w, h in ((7, 5), (120, 68), (480, 270)):
+                d = desc(cin, cout, simd, pe, w, h, tr)
+                for n_images in (1, 8):
+                    for n_cu in (256, 128, 32):
+                        for tile_x in (0, 16, 32):
+                            for wave_tile in (0, 64, 128):
+                                plans = {pf: _plan(d, n_images, n_cu, tile_x=tile_x, prefetch=pf, wave_tile=wave_tile) for pf in range(4)}
+                                where = (cin, cout, tr, w, h, n_images, n_cu, tile_x, wave_tile)
+                                assert plans[1] == plans[2], where
+                                for p in plans.values():
+                                    assert p["kind"] == (2 if tr else 1) and p["family"] in (1, 2), (where, p)
+                                    if cin == 192 or cout == 192:
+                                        assert p["family"] == 1 and p["tile_x"] == 16, (where, p)
+
+
 def test_product_library_rejects_the_removed_forms():
     """The kernel forms that measured a loss (the persistent layer 0, the loader-wave layer 7, the RGB layer applying the previous
     activation, the K split) and the 32x32x32 kernels were removed in 0.3.x: their options are SICN_EINVAL, "never" stays a valid

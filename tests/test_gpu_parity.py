@@ -120,10 +120,11 @@ MFMA_CASES = [c for c in SPECIAL if c[0] != 3 and c[1] != 3]
 @pytest.mark.parametrize("case", MFMA_CASES + [(128, 128, 8, 16, 50, 20, 0), (192, 128, 12, 16, 37, 21, 1), (128, 192, 8, 24, 47, 18, 0),
                                   (192, 128, 12, 16, 45, 19, 0), (128, 192, 8, 24, 21, 13, 1), (192, 128, 12, 16, 9, 40, 0)])
 def test_both_tile_widths_match_oracle(api, case, tile_x, prefetch):
-    """The 16x16x64 kernels exist for 8 x 32 and 8 x 16 position tiles (the launcher picks by layer shape and grid size) and
-    in a plain (k_mfma16.hip) and a software-pipelined form (k_mfma16p.hip, the default wherever it exists: every shape at
-    8 x 16, the 128 -> 128 shapes also at 8 x 32); force each combination on every shape, incl. the hyperprior stacks'
-    conv 192 -> 128 and deconv 128 -> 192."""
+    """The software-pipelined 16x16x64 kernels (k_mfma16p.hip) exist for 8 x 16 position tiles on every shape and for 8 x 32
+    tiles on the 128 -> 128 shapes (the launcher picks by layer shape and grid size; tile_x = 32 on a 192-channel shape still
+    gets 8 x 16); force each width on every shape, incl. the hyperprior stacks' conv 192 -> 128 and deconv 128 -> 192.
+    prefetch = 1 and 2 both keep the automatic wide form out; 1 selected the plain kernels until they were removed and must
+    now run exactly the pipelined ones."""
     rng = np.random.default_rng(abs(hash(case)) % (1 << 31) + int(tile_x))
     d = _mk_desc(*case)
     W, b, words = _rand_params(rng, d)
@@ -265,7 +266,7 @@ WIDE_CASES = [(128, 128, 8, 16, 66, 18, 0), (128, 128, 8, 16, 7, 5, 0), (128, 12
 @pytest.mark.parametrize("wave_tile,grid", [(64, 0), (128, 0), (128, 8), (128, 16)])
 @pytest.mark.parametrize("case", WIDE_CASES)
 def test_wide_wave_tile_conv_matches_oracle(api, case, wave_tile, grid):
-    """conv 128 -> 128 exists in two forms: 64 x 128 outputs per wave at two waves per SIMD (k_mfma16.hip / k_mfma16p.hip) and
+    """conv 128 -> 128 exists in two forms: 64 x 128 outputs per wave at two waves per SIMD (k_mfma16p.hip) and
     128 x 128 per wave with AGPR-pinned accumulators at one wave per SIMD, by PERSISTENT workgroups that walk through 16 x 32
     tiles (k_mfma16x.hip, the default on full-size grids).  Force each on odd sizes, single pixels, several tiles, pixels with
     the high bit; the persistent form also with 8 / 16 workgroups, so that every one of them walks through several tiles —
@@ -318,9 +319,9 @@ PIPE_CASES = [(128, 128, 8, 16, 34, 10, 1), (128, 128, 8, 16, 1, 1, 1), (128, 12
 @pytest.mark.parametrize("prefetch", [1, 2])
 @pytest.mark.parametrize("case", PIPE_CASES + WIDE_CASES)
 def test_pipelined_kernels_match_oracle(api, case, prefetch):
-    """conv / deconv 128 -> 128 exist as k_mfma16.hip's kernels (prefetch = 1) and as the software-pipelined k_mfma16p.hip
-    (prefetch = 2, the default on full-size grids): force each, with the wide tile, on odd sizes / single pixels / several
-    tiles / high-bit inputs."""
+    """conv / deconv 128 -> 128 on the software-pipelined k_mfma16p.hip (prefetch = 1 | 2: never the automatic wide form; 1 selected
+    the plain kernels until they were removed), with the 8 x 32 tile, on odd sizes / single pixels / several tiles / high-bit
+    inputs."""
     rng = np.random.default_rng(abs(hash(case)) % (1 << 31) + prefetch)
     d = _mk_desc(*case)
     W, b, words = _rand_params(rng, d)

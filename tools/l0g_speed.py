@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Layer 0 + its GDN in one kernel (k_l0g) on 8 x 4K, alone: ms per launch (events).  SICN_LIB selects an experiment build
-(tools/build_variant.sh NAME "-DSICN_EXP_L0G_..." k_l0g.hip).  usage: l0g_speed.py [gdn_fuse=0|1]"""
+"""Layer 0 + its GDN in one kernel (k_l0g) on 8 x 4K, alone: ms per launch (events).  SICN_LIB selects another build of
+libsicn.so.  usage: l0g_speed.py [gdn_fuse=0|1]"""
 import os
 import sys
 

@@ -130,7 +130,8 @@ const char *sicn_strerror(int code);
  * n_xcd = the largest power of two <= 8 that leaves at least 20 CUs per XCD (256 CUs -> 8, a DPX partition of 128 -> 4, QPX
  * 64 -> 2, CPX 32 -> 1; hipDeviceProp_t carries no XCD count, and the value only steers which tiles share an L2).
  * sicn_debug_plan shows what a layer would launch on a chip of n_cu CUs, without a GPU: out[] = { n_cu, n_xcd, kernel kind
- * (0 generic, 1 mfma conv, 2 mfma deconv, 3 layer 0, 4 layer 7), mfma family (1 pipelined, 2 wide persistent; 0 only for the
+ * (0 generic, 1 mfma conv, 2 mfma deconv, 3 layer 0, 4 layer 7, 5 / 6 the channel-generic mfma conv / deconv: for these
+ * out[4] = the tile edge and out[7..9] the grid, the rest 0), mfma family (1 pipelined, 2 wide persistent; 0 only for the
  * other kinds: the plain kernels of family 0 were removed), tile_x, split_n, split_k (always 1), grid x, grid y, grid z, strip
  * chunks (wide persistent: 1 = part of the tiles dealt dynamically), layer-0 tiles per run }.  sicn_debug_xcd_item is the host
  * mirror of the kernels' workgroup -> work item mapping (-1: padding workgroup). */
@@ -172,7 +173,9 @@ int sicn_conv2d_opt(const sicn_layer_desc *desc, const sicn_weights *w, const ui
 int sicn_deconv522_opt(const sicn_layer_desc *desc, const sicn_weights *w, const uint8_t *in_nhwc,
                        uint8_t *out_nhwc, int n_images, const sicn_options *opt, void *hip_stream);
 /* Name of the kernel family that will serve `desc` under the default options ("l0_rgb", "mfma_conv",
- * "mfma_deconv", "l7_rgb", "generic"); static string. */
+ * "mfma_deconv", "l7_rgb", "mfma_conv_any", "mfma_deconv_any", "generic"); static string.  The "_any" kernels take the channel
+ * widths the others do not: IFM_CH % 32 == 0 and OFM_CH % 16 == 0 (both <= 1024), conv 3 -> N (N % 16 == 0) and deconv N -> 3
+ * (N % 32 == 0); every other valid descriptor runs on "generic".  All of them produce the same bytes. */
 const char *sicn_kernel_for(const sicn_layer_desc *desc);
 
 /* Layer chains ----------------------------------------------------------------------------- */

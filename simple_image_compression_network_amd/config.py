@@ -16,7 +16,7 @@ import ctypes
 from dataclasses import dataclass, fields
 from typing import List, Sequence, Tuple
 
-__all__ = ["LayerDesc", "CLayerDesc", "eight_layer_descs", "REFERENCE_DESCS", "NET_CHANNELS"]
+__all__ = ["LayerDesc", "CLayerDesc", "eight_layer_descs", "net_channels", "REFERENCE_DESCS", "NET_CHANNELS"]
 
 
 class CLayerDesc(ctypes.Structure):
@@ -110,12 +110,33 @@ NET_CHANNELS: Sequence[Tuple[int, int, int, int, int]] = (
 )
 
 
-def eight_layer_descs(width: int, height: int) -> List[LayerDesc]:
+def net_channels(n_ch: int = 128, m_ch: int = 192) -> Sequence[Tuple[int, int, int, int, int]]:
+    """`NET_CHANNELS` at other widths: `n_ch` channels in the transforms, `m_ch` in the latent.  The folds keep the
+    reference's values where they divide the channel counts (PE = 24 / SIMD = 12 around the latent) and fall back to
+    16 / 8; they only shape the weight tiles, never the result."""
+    if n_ch <= 0 or m_ch <= 0 or n_ch % 16 or m_ch % 16:
+        raise ValueError("n_ch and m_ch must be positive multiples of 16")
+    pe_m = 24 if m_ch % 24 == 0 else 16
+    simd_m = 12 if m_ch % 12 == 0 else 8
+    return (
+        (3, n_ch, 3, 8, 0),
+        (n_ch, n_ch, 8, 16, 0),
+        (n_ch, n_ch, 8, 16, 0),
+        (n_ch, m_ch, 8, pe_m, 0),
+        (m_ch, n_ch, simd_m, 16, 1),
+        (n_ch, n_ch, 8, 16, 1),
+        (n_ch, n_ch, 8, 16, 1),
+        (n_ch, 3, 8, 3, 1),
+    )
+
+
+def eight_layer_descs(width: int, height: int, n_ch: int = 128, m_ch: int = 192) -> List[LayerDesc]:
     """The reference's 8-layer net (conv_nonsquare_top.cpp:295-357) re-dimensioned for a
-    `height x width` RGB image: conv out = ceil(in/2), deconv out = 2*in."""
+    `height x width` RGB image: conv out = ceil(in/2), deconv out = 2*in.  `n_ch` / `m_ch`: the same topology at
+    other channel widths (the defaults are the reference's 128 / 192)."""
     descs = []
     w, h = width, height
-    for cin, cout, simd, pe, tr in NET_CHANNELS:
+    for cin, cout, simd, pe, tr in net_channels(n_ch, m_ch):
         ow, oh = (2 * w, 2 * h) if tr else ((w + 1) // 2, (h + 1) // 2)
         d = LayerDesc(IFM_CH=cin, IFM_ROW=w, IFM_COL=h, OFM_CH=cout, OFM_ROW=ow, OFM_COL=oh,
                       SIMD=simd, PE=pe, W_TILES=(cout // pe) * (25 * cin // simd), transposed=tr)

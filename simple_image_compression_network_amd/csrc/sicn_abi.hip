@@ -130,7 +130,9 @@ extern "C" void sicn_options_init(sicn_options *opt)
 // (stream_symbols), SICN_ENODEV for a device that is not gfx950
 // 0.3: GDN / IGDN specification version 2 (include/sicn_gdn.h): the activation's BYTES change, sicn_gdn_selftest_roots_narrow is gone
 // 0.4: sicn_convlayer_kernel_for; ConvLayer_Batch serves every descriptor (sub-byte lanes, any channel count) on the MFMA kernel
-extern "C" int sicn_version(void) { return 1000 * 0 + 4; }
+// 0.5: conv2d<> / deconv522<> at other channel widths run on the channel-generic MFMA kernels ("mfma_conv_any" / "mfma_deconv_any",
+// kinds 5 / 6) instead of k_generic: same bytes, another kernel for valid descriptors
+extern "C" int sicn_version(void) { return 1000 * 0 + 5; }
 extern "C" int sicn_gdn_spec_version(void) { return 2; }
 
 extern "C" int sicn_has_alt_kernels(void) { return 0; }   // kept for callers that probe it: the alternate kernel build is gone
@@ -183,6 +185,8 @@ KernelKind pick_kernel(const sicn_layer_desc &d, const sicn_options &o)
     if (!d.transposed && d.IFM_CH == 3 && d.OFM_CH == 128) return KK_L0_RGB;
     if (d.transposed && d.IFM_CH == 128 && d.OFM_CH == 3) return KK_L7_RGB;
     if (mfma_supported(d.IFM_CH, d.OFM_CH, d.transposed)) return d.transposed ? KK_MFMA_DECONV : KK_MFMA_CONV;
+    // every other width the matrix cores can take (k_mfma16c.hip); small and ragged shapes stay on k_generic
+    if (any_supported(d.IFM_CH, d.OFM_CH, d.transposed)) return d.transposed ? KK_MFMA_DECONV_ANY : KK_MFMA_CONV_ANY;
     return KK_GENERIC;
 }
 }  // namespace sicn
@@ -195,6 +199,8 @@ extern "C" const char *sicn_kernel_for(const sicn_layer_desc *d)
     case KK_L7_RGB: return "l7_rgb";
     case KK_MFMA_CONV: return "mfma_conv";
     case KK_MFMA_DECONV: return "mfma_deconv";
+    case KK_MFMA_CONV_ANY: return "mfma_conv_any";
+    case KK_MFMA_DECONV_ANY: return "mfma_deconv_any";
     default: return "generic";
     }
 }
@@ -217,6 +223,7 @@ extern "C" void sicn_weights_free(sicn_weights *w)
     if (w->d_w_l0) (void)hipFree(w->d_w_l0);
     if (w->d_w_l0g) (void)hipFree(w->d_w_l0g);
     if (w->d_w_l7) (void)hipFree(w->d_w_l7);
+    if (w->d_w_any) (void)hipFree(w->d_w_any);
     delete w;
 }
 
@@ -292,6 +299,11 @@ extern "C" int sicn_weights_from_finn_tiles(const sicn_layer_desc *d, const void
             pack_l7(w_okc.data(), cin, s.data());
             ok = upload(s.data(), s.size(), &w->d_w_l7);
         }
+        if (ok && any_supported(cin, cout, d->transposed)) {
+            std::vector<int8_t> s(any_bytes(cin, cout));
+            pack_any(w_okc.data(), cin, cout, s.data());
+            ok = upload(s.data(), s.size(), &w->d_w_any);
+        }
     } catch (const std::bad_alloc &) { ok = false; }
     if (!ok) {
         sicn_weights_free(w);
@@ -362,6 +374,10 @@ static int run_layer(const sicn_layer_desc *d, const sicn_weights *w, const uint
     case KK_MFMA_CONV:
     case KK_MFMA_DECONV:
         e = launch_mfma16(g, *w, in, out, n_images, stream, in_layout, out_layout, o, chip, relu, deal);
+        break;
+    case KK_MFMA_CONV_ANY:
+    case KK_MFMA_DECONV_ANY:
+        e = launch_any(g, *w, in, out, n_images, stream, relu);   // NHWC in and out: link_layout puts NHWC next to these kinds
         break;
     default: e = launch_generic(g, *w, in, out, n_images, stream, relu); break;
     }
@@ -657,6 +673,9 @@ extern "C" int sicn_debug_plan(const sicn_layer_desc *d, int n_images, const sic
         out[3] = p.family; out[4] = p.tile_x; out[5] = p.split_n; out[6] = 1;   // out[6]: the K split, removed in 0.3.x
         out[7] = (int)p.grid_x; out[8] = (int)p.grid_y; out[9] = (int)p.grid_z;
         out[10] = p.deal;
+    } else if (k == KK_MFMA_CONV_ANY || k == KK_MFMA_DECONV_ANY) {
+        const AnyPlan p = plan_any(g.transposed ? g.IW : g.OW, g.transposed ? g.IH : g.OH, g.COUT, g.transposed, n_images);
+        out[4] = p.tile; out[7] = (int)p.grid_x; out[8] = (int)p.grid_y; out[9] = (int)p.grid_z;
     } else if (k == KK_L7_RGB) {
         const int tiles_x = (g.IW + 31) / 32, steps_y = (g.IH + 3) / 4;
         const int yc = l7_chunks(tiles_x, n_images, steps_y, o.strip_chunks, chip);

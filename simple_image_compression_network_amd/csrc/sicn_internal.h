@@ -19,7 +19,7 @@ constexpr int PATCH_X = TILE_X + 2;
 constexpr int PATCH_PIX = PATCH_Y * PATCH_X;  // 340
 constexpr int KSTEP = 32;                      // bytes of K per MFMA (v_mfma_i32_32x32x32_i8)
 
-enum KernelKind : int { KK_GENERIC = 0, KK_MFMA_CONV, KK_MFMA_DECONV, KK_L0_RGB, KK_L7_RGB };
+enum KernelKind : int { KK_GENERIC = 0, KK_MFMA_CONV, KK_MFMA_DECONV, KK_L0_RGB, KK_L7_RGB, KK_MFMA_CONV_ANY, KK_MFMA_DECONV_ANY };
 
 struct LayerGeom {
     int IW, IH, CIN, OW, OH, COUT, transposed;
@@ -44,6 +44,7 @@ struct sicn_weights {
     int8_t *d_w_l0;
     int8_t *d_w_l0g;       // layer 0, 128 channels: the A-operand image of the kernel that applies a GDN before its store (k_l0g.hip)
     int8_t *d_w_l7;
+    int8_t *d_w_any;       // the channel-generic MFMA kernels' weight image (k_mfma16c.hip: pack_any), or nullptr when they do not serve the shape
 };
 
 namespace sicn {
@@ -107,6 +108,13 @@ hipError_t launch_l7(const LayerGeom &g, const sicn_weights &w, const uint8_t *i
 bool mfma_supported(int cin, int cout, int transposed);
 size_t mfma16_stream_bytes(int cin, int cout);
 void pack_mfma16_stream(const int8_t *w_okc, int cin, int cout, int transposed, int8_t *dst);
+
+// k_mfma16c.hip: conv2d<> / deconv522<> at any served channel width (run-time channel counts), NHWC in and out
+bool any_supported(int cin, int cout, int transposed);
+size_t any_bytes(int cin, int cout);
+void pack_any(const int8_t *w_okc, int cin, int cout, int8_t *dst);
+hipError_t launch_any(const LayerGeom &g, const sicn_weights &w, const uint8_t *in, uint8_t *out, int n_images, hipStream_t stream,
+                      bool relu = true);
 
 size_t l0_bytes(int cout);
 void pack_l0(const int8_t *w_okc, int cout, int8_t *dst);

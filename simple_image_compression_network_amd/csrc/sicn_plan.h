@@ -75,6 +75,19 @@ inline bool narrow_tile_wanted(long tiles32, const ChipGeom &c) { return tiles32
 // output-channel split of the 8 x 16 kernels: grids that leave half of the CUs without a workgroup (measured r02: <= 128 of 256)
 inline bool split_n_automatic(long tiles16, const ChipGeom &c) { return tiles16 * 2 <= c.n_cu; }
 
+// ---- the channel-generic kernels (k_mfma16c.hip): 16 x 16 M positions x 64 output channels per workgroup ---------------------
+// grid x = tiles (x 4 phases for the deconv, the phase in the low two bits so that the four workgroups of a tile run together and
+// share its input lines), y = blocks of 64 output channels, z = images.  The served form has one tile size and no persistent grid,
+// so nothing here depends on the chip.  grid_x == 0: the layer does not fit a launch.
+struct AnyPlan { int tile, tiles_x, tiles_y; unsigned grid_x, grid_y, grid_z; };
+inline AnyPlan plan_any(int m_w, int m_h, int cout, int deconv, int n_images)
+{
+    AnyPlan p{16, (m_w + 15) / 16, (m_h + 15) / 16, 0u, (unsigned)((cout + 63) / 64), (unsigned)n_images};
+    const long long gx = (long long)p.tiles_x * p.tiles_y * (deconv ? 4 : 1);
+    if (gx > 0 && gx < 0x7fffffffLL && n_images > 0 && n_images <= 65535) p.grid_x = (unsigned)gx;
+    return p;
+}
+
 // ---- layer 7 (k_l7): vertical strips of 32 input columns, cut into y_chunks runs ----------------------------------------------
 // just under TWO workgroups per CU in all (measured r03: 510 of 512 best); every cut re-fetches six halo rows and the weights
 inline int l7_chunks(int tiles_x, int n_images, int steps_y, int forced, const ChipGeom &c)

@@ -143,9 +143,9 @@ int sicn_crop_nhwc(const uint8_t *src, uint8_t *dst, int n_images, int src_h, in
 int sicn_debug_plan(const sicn_layer_desc *desc, int n_images, const sicn_options *opt, int n_cu, int32_t out[12]);
 long long sicn_debug_xcd_item(long long block, long long n_items, int n_xcd);
 int sicn_validate_desc(const sicn_layer_desc *desc); /* pure host check, no GPU needed         */
-/* Fills *opt with the library defaults (= all zero, overridden by the SICN_MFMA_SHAPE, SICN_TILE_X,
- * SICN_STRIP_CHUNKS, SICN_NO_PHASE_LAYOUT, SICN_SPLIT_N, SICN_SPLIT_K, SICN_L7_LOADER, SICN_L0_FORM, SICN_GDN_FUSE, SICN_WAVE_TILE, SICN_PREFETCH, SICN_FORCE_GENERIC environment
- * variables as they were when the library was loaded; out-of-range values are ignored with one warning on stderr). */
+/* Fills *opt with the library defaults: all zero, overridden by the environment as it was when the library was loaded.  The variable
+ * of a field is SICN_ + its name in capitals (SICN_TILE_X, SICN_FORCE_GENERIC, ...; persistent_grid has none); a value the field
+ * does not admit is ignored with one warning on stderr. */
 void sicn_options_init(sicn_options *opt);
 
 /* Weights ---------------------------------------------------------------------------------- */
@@ -187,8 +187,7 @@ int sicn_net_create(const sicn_layer_desc *descs, sicn_weights *const *weights, 
 int sicn_net_create_opt(const sicn_layer_desc *descs, sicn_weights *const *weights, int n_layers,
                         const sicn_options *opt, sicn_net **out);
 void sicn_net_free(sicn_net *net);
-/* Bytes of DEVICE scratch `sicn_net_forward` needs for a batch of n_images: two ping-pong activation buffers (library 0.2 also
- * reserved room there for the K split when sicn_options.split_k > 1 was set; the K split was removed, and no device is needed
+/* Bytes of DEVICE scratch `sicn_net_forward` needs for a batch of n_images: two ping-pong activation buffers (no device is needed
  * to ask).  Behind the buffers: 528 words per layer for the wide persistent kernels' tile deal (one ticket counter per XCD + one
  * mailbox per workgroup, k_mfma16x.hip DealX), which sicn_net_forward zeroes itself (one small kernel at the head of the call).  A workspace
  * without room for them (a size computed by library 0.2) still works: those kernels then deal all their tiles statically.

@@ -251,8 +251,8 @@ class EightLayersNet:
 
     def workspace(self, n_images: int):
         import torch
-        # sized per batch size (the K-split scratch of a small batch may exceed what a larger one asks for); never shrinks.
-        # No initialisation is needed (sicn.h: the arrival words carry the net's random tag).
+        # the size the library asks for per batch size, cached; the buffer never shrinks.  No initialisation is needed
+        # (sicn.h: sicn_net_forward zeroes the tile-deal words behind the ping-pong buffers itself).
         nbytes = self._ws_bytes.get(n_images)
         if nbytes is None:
             nbytes = self._ws_bytes[n_images] = max(int(_lib.lib().sicn_net_workspace_bytes(self._h, n_images)), 256)

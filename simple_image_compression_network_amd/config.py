@@ -93,6 +93,15 @@ class LayerDesc:
         if (self.OFM_ROW, self.OFM_COL) != exp:
             raise ValueError(f"OFM dims {(self.OFM_ROW, self.OFM_COL)} != {exp}")
 
+    @classmethod
+    def make(cls, cin: int, cout: int, simd: int, pe: int, width: int, height: int, transposed: int = 0) -> "LayerDesc":
+        """A valid layer on a `height x width` input: conv out = ceil(in/2), deconv out = 2*in; W_TILES from the folds."""
+        ow, oh = (2 * width, 2 * height) if transposed else ((width + 1) // 2, (height + 1) // 2)
+        d = cls(IFM_CH=cin, IFM_ROW=width, IFM_COL=height, OFM_CH=cout, OFM_ROW=ow, OFM_COL=oh, SIMD=simd, PE=pe,
+                W_TILES=(cout // pe) * (25 * cin // simd), transposed=transposed)
+        d.validate()
+        return d
+
     def to_c(self) -> CLayerDesc:
         return CLayerDesc(**{f.name: getattr(self, f.name) for f in fields(self)})
 
@@ -137,12 +146,9 @@ def eight_layer_descs(width: int, height: int, n_ch: int = 128, m_ch: int = 192)
     descs = []
     w, h = width, height
     for cin, cout, simd, pe, tr in net_channels(n_ch, m_ch):
-        ow, oh = (2 * w, 2 * h) if tr else ((w + 1) // 2, (h + 1) // 2)
-        d = LayerDesc(IFM_CH=cin, IFM_ROW=w, IFM_COL=h, OFM_CH=cout, OFM_ROW=ow, OFM_COL=oh,
-                      SIMD=simd, PE=pe, W_TILES=(cout // pe) * (25 * cin // simd), transposed=tr)
-        d.validate()
+        d = LayerDesc.make(cin, cout, simd, pe, w, h, tr)
         descs.append(d)
-        w, h = ow, oh
+        w, h = d.OFM_ROW, d.OFM_COL
     return descs
 
 

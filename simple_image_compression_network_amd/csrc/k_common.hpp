@@ -11,14 +11,6 @@ typedef int v16i __attribute__((ext_vector_type(16)));
 #define LDS_PTR(p) ((__attribute__((address_space(3))) void *)(p))
 #define GLB_PTR(p) ((const __attribute__((address_space(1))) void *)(p))
 
-// One sub-patch = (TILE_Y+2) x (TILE_X+2) positions x 32 channel bytes = 10880 B, filled by 1-KiB
-// LDS-DMA pieces (one wave-wide 16-byte load each) and padded to 12 pieces so that every wave of a
-// 4-wave workgroup issues the same number of pieces (3) per sub-patch.
-constexpr int SUB_BYTES = PATCH_PIX * KSTEP;  // 10880
-constexpr int SUB_PIECES = 12;
-constexpr int SUB_ALLOC = SUB_PIECES * 1024;  // 12288
-constexpr int RING = 4;                       // weight-tile ring slots
-constexpr int PF = 3;                         // weight tiles in flight ahead of the consumer
 constexpr int PAD16 = 24;                     // zero tiles behind a 16x16x64 weight stream (pack_mfma16_stream): room for the prefetch
 constexpr uint32_t OOB = 0x80000000u;         // beyond any image: the buffer range check returns 0
 
@@ -70,17 +62,7 @@ __device__ __forceinline__ uint32_t pack4_relu7(int a, int b, int c, int d, uint
 //                  parity), instead of 32-byte pieces at a 64-byte stride
 constexpr int LAYOUT_NHWC = 0, LAYOUT_GROUP = 1, LAYOUT_PHASE = 2;
 
-// byte offset of channel group g of pixel (y, x) in an image of W x H pixels, C channels
-__device__ __forceinline__ uint32_t tensor_offset(int layout, int y, int x, uint32_t g, int C, int W, int H)
-{
-    if (layout == LAYOUT_NHWC) return (uint32_t)(y * W + x) * (uint32_t)C + g * 32u;
-    if (layout == LAYOUT_GROUP) return (g * (uint32_t)(W * H) + (uint32_t)(y * W + x)) * 32u;
-    const uint32_t hw = (uint32_t)((W >> 1) * (H >> 1));
-    const uint32_t plane = (uint32_t)((y & 1) * 2 + (x & 1)) * (uint32_t)(C >> 5) + g;
-    return (plane * hw + (uint32_t)((y >> 1) * (W >> 1) + (x >> 1))) * 32u;
-}
-
-// The same three layouts as strides (wave-uniform), for kernels that compute many offsets per step:
+// The layouts as strides (wave-uniform): byte offset of channel group g of pixel (y, x) in an image of W x H pixels, C channels
 //   offset = ((y>>sh)*row + (x>>sh))*pix + g*grp + ((y&sh)*2 + (x&sh))*ph          (no branches)
 struct TensorMap {
     uint32_t sh, row, pix, grp, ph;
@@ -98,23 +80,6 @@ __device__ __forceinline__ uint32_t tensor_offset(const TensorMap &t, int y, int
            (((uint32_t)y & t.sh) * 2u + ((uint32_t)x & t.sh)) * t.ph;
 }
 
-// Source offset (bytes from the image base) of this lane's 16 bytes of LDS-DMA piece `k` of a
-// sub-patch: position p = k*32 + lane/2 of the (TILE_Y+2) x (TILE_X+2) window whose origin is
-// (Yb, Xb) in "patch coordinates"; patch coordinate (ty,tx) maps to input pixel
-// (s*(Yb+ty)+ay, s*(Xb+tx)+ax).  The LDS image keeps logical half h of position p at physical
-// half h ^ ((p>>3)&1) (bank-conflict-free ds_read_b128).
-__device__ __forceinline__ uint32_t piece_src_offset(int k, int lane, int Yb, int Xb, int s, int ay, int ax,
-                                                     int IW, int IH, int layout, uint32_t g, int C, bool swizzle = true)
-{
-    const int p = k * 32 + (lane >> 1);
-    const int ty = p / PATCH_X, tx = p - ty * PATCH_X;
-    // 32x32x32 fragments want half h of position p at h ^ ((p>>3)&1); 16x16x64 fragments want it plain
-    const int hlog = swizzle ? (lane & 1) ^ ((p >> 3) & 1) : (lane & 1);
-    const int iy = s * (Yb + ty) + ay, ix = s * (Xb + tx) + ax;
-    const bool ok = p < PATCH_PIX && iy >= 0 && iy < IH && ix >= 0 && ix < IW;
-    return ok ? tensor_offset(layout, iy, ix, g, C, IW, IH) + hlog * 16 : OOB;
-}
-
 // Tile geometry of the 16x16x64 kernels: TILE_Y x TX positions (TX = 32, or 16 for the layers whose
 // accumulators / patch allow only one 8 x 32 workgroup per CU), sub-patch of (TILE_Y+2) x (TX+2)
 // positions x 32 B, padded to SLOTS pieces per wave so that every wave issues the same number.
@@ -128,8 +93,9 @@ struct Geo {
     static constexpr int NC = 2 * XT;                              // column tiles per wave (2 rows)
 };
 
-// The same with the layout as strides: patch position and validity of this lane in piece `k`
-// (unswizzled image, 16x16x64 kernels), channel group 0; group g is `+ g * tm.grp`.
+// Patch position and validity of this lane's 16 bytes of LDS-DMA piece `k` of a sub-patch: position p = k*32 + lane/2 of
+// the window whose origin is (Yb, Xb) in "patch coordinates"; patch coordinate (ty,tx) maps to input pixel
+// (s*(Yb+ty)+ay, s*(Xb+tx)+ax).  Unswizzled image, channel group 0; group g is `+ g * tm.grp`.
 struct PieceSrc {
     uint32_t off;   // byte offset of channel group 0 (meaningless if !ok)
     bool ok;
@@ -148,7 +114,7 @@ __device__ __forceinline__ PieceSrc piece_src(const TensorMap &tm, int k, int la
 }
 
 // one LDS-DMA piece (1 KiB) of sub-patch `sub` (sub-patches are ALLOC bytes apart)
-template <int ALLOC = SUB_ALLOC>
+template <int ALLOC>
 __device__ __forceinline__ void load_piece(uint8_t *patch, const uint8_t *in_img, int in_img_bytes, int sub,
                                            int k, uint32_t off)
 {

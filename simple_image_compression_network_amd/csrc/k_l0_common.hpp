@@ -13,12 +13,10 @@ namespace sicn {
 // Same work split as k_mfma: 8 x 32 output tile, wave w = rows 2w, 2w+1, all output channels.
 // =============================================================================================
 constexpr int L0_QUADS = 18;                  // 4-pixel groups per patch row: 72 slots >= 2*31+4+4
-constexpr int L0_PITCH = L0_QUADS * 16;       // 288 bytes, 16-byte aligned rows
-constexpr int L0_TY = 8;                      // output rows per tile (wave w = rows 2w, 2w+1)
+constexpr int L0_PITCH = L0_QUADS * 16;       // 288 bytes, 16-byte aligned rows (L0_TY, L0_CHUNK: sicn_plan.h)
 constexpr int L0_ROWS = 2 * L0_TY + 3;        // 19 input rows per tile
 constexpr int L0_NQUAD = L0_ROWS * L0_QUADS;  // 342 quads per tile, <= 2 per thread
 constexpr int L0_PATCH = L0_ROWS * L0_PITCH;  // 5472 bytes
-constexpr int L0_CHUNK = 9;                   // tiles a workgroup walks at most (its raw pixels are LDS-resident)
 constexpr int L0_RAW_DW = 52;                 // dwords kept per input row: 67 pixels = 201 B + 3 B of alignment slack
 constexpr int L0_RAW_ROWS = 2 * L0_TY * L0_CHUNK + 3;
 constexpr int L0_RAW_BYTES = (L0_RAW_ROWS * L0_RAW_DW * 4 + 12 + 255) / 256 * 256;   // + the 3 dwords the last quad over-reads

@@ -25,8 +25,7 @@
 
 namespace sicn {
 
-constexpr int L0G_CHUNK = 8;                                   // tiles per run (8 is the most two workgroups' LDS holds)
-constexpr int L0G_RAW_ROWS = 2 * L0_TY * L0G_CHUNK + 3;        // 131 (round 5: runs of 8 tiles instead of 4: 1.31 -> 1.27 ms on 8 x 4K, profiles/r05_l0g_parts.txt)
+constexpr int L0G_RAW_ROWS = 2 * L0_TY * L0G_CHUNK + 3;        // 131: runs of L0G_CHUNK tiles, sicn_plan.h (round 5: runs of 8 tiles instead of 4: 1.31 -> 1.27 ms on 8 x 4K, profiles/r05_l0g_parts.txt)
 constexpr int L0G_RAW_BYTES = (L0G_RAW_ROWS * L0_RAW_DW + 63) / 64 * 256;   // whole request instructions (64 lanes x 4 B)
 static_assert(L0G_RAW_BYTES >= L0G_RAW_ROWS * L0_RAW_DW * 4 + 12, "the last quad over-reads 3 dwords");
 constexpr int L0G_KSTEPS = 3;                                  // kernel rows (0,1), (2,3), (4, -)
@@ -181,17 +180,16 @@ hipError_t launch_l0_gdn(const LayerGeom &g, const sicn_weights &w, const sicn_g
                          hipStream_t stream, int out_layout, const sicn_options &o, const ChipGeom &chip)
 {
     if (g.COUT != 128 || gdn.channels != 128 || !w.d_w_l0g || !gdn.d_gamma_mfma) return hipErrorInvalidValue;
-    const int tiles_x = (g.OW + TILE_X - 1) / TILE_X, tiles_y = (g.OH + L0_TY - 1) / L0_TY;
-    const L0Cut cut = l0_chunks(tiles_x, tiles_y, n_images, L0G_CHUNK, o.strip_chunks, chip);
+    const L0Plan p = plan_l0(g.OW, g.OH, n_images, true, o.strip_chunks, chip);
     if ((size_t)g.IH * g.IW * 3 * (size_t)n_images + 4 >= (size_t)OOB) return hipErrorInvalidValue;
     if ((size_t)g.OH * g.OW * g.COUT >= (size_t)OOB) return hipErrorInvalidValue;   // buffer-descriptor stores
-    if (cut.ty_per > L0G_CHUNK) return hipErrorInvalidValue;
-    dim3 grid((unsigned)tiles_x, (unsigned)cut.y_chunks, (unsigned)n_images);
+    if (p.ty_per > L0G_CHUNK) return hipErrorInvalidValue;
+    dim3 grid((unsigned)p.tiles_x, (unsigned)p.y_chunks, (unsigned)n_images);
     auto go = [&](auto kernel) -> hipError_t {
         hipError_t e = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, L0G_LDS);
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL(kernel, grid, dim3(512), L0G_LDS, stream, in, out, w.d_w_l0g, w.d_bias, gdn.d_gamma_mfma, gdn.d_beta_mfma, g.IW, g.IH,
-                           g.OW, g.OH, tiles_y, cut.ty_per, out_layout, gdn.kc);
+                           g.OW, g.OH, p.tiles_y, p.ty_per, out_layout, gdn.kc);
         return hipGetLastError();
     };
     return gdn.inverse ? go(k_l0g<true>) : go(k_l0g<false>);

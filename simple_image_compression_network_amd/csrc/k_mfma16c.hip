@@ -185,17 +185,17 @@ __global__ __launch_bounds__(256) void k_any(const uint8_t *__restrict__ in, uin
     }
 }
 
-// ---- which layers come here (pick_kernel asks after the specialised families said no) ----------------------------------------------
+// ---- which shapes these kernels take.  Which layers come here is the order of the family list (sicn_abi.hip): the specialised
+// ---- families stand before this one, so the reference shapes never do
 //   tier A: IFM_CH % 32 == 0 and OFM_CH % 16 == 0, both <= 1024
-//   tier B: the RGB ends at other widths — conv 3 -> N (N % 16 == 0), deconv N -> 3 (N % 32 == 0)
+//   tier B: the RGB ends — conv 3 -> N (N % 16 == 0), deconv N -> 3 (N % 32 == 0)
 // Small and ragged shapes stay on k_generic, the independent second implementation.
 bool any_supported(int cin, int cout, int transposed)
 {
-    if (mfma_supported(cin, cout, transposed)) return false;
     if (cin > ANY_MAX_CH || cout > ANY_MAX_CH) return false;
     if (cin % 32 == 0 && cout % 16 == 0) return true;
-    if (!transposed && cin == 3 && cout % 16 == 0 && cout != 128) return true;
-    if (transposed && cin % 32 == 0 && cout == 3 && cin != 128) return true;
+    if (!transposed && cin == 3 && cout % 16 == 0) return true;
+    if (transposed && cin % 32 == 0 && cout == 3) return true;
     return false;
 }
 

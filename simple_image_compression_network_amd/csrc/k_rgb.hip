@@ -174,12 +174,10 @@ void pack_l0(const int8_t *w_okc, int cout, int8_t *dst)
 hipError_t launch_l0(const LayerGeom &g, const sicn_weights &w, const uint8_t *in, uint8_t *out,
                      int n_images, hipStream_t stream, int out_layout, const sicn_options &o, const ChipGeom &chip, bool relu)
 {
-    const int tiles_x = (g.OW + TILE_X - 1) / TILE_X, tiles_y = (g.OH + L0_TY - 1) / L0_TY;
     // runs of at most L0_CHUNK tiles (the LDS holds a run's pixels), evened out; small images: shorter runs, enough workgroups
     // (about four per CU, sicn_plan.h); the test hook (strip_chunks) can only shorten them
-    const L0Cut cut = l0_chunks(tiles_x, tiles_y, n_images, L0_CHUNK, o.strip_chunks, chip);
-    const int y_chunks = cut.y_chunks, ty_per = cut.ty_per;
-    dim3 grid((unsigned)tiles_x, (unsigned)y_chunks, (unsigned)n_images);
+    const L0Plan p = plan_l0(g.OW, g.OH, n_images, false, o.strip_chunks, chip);
+    dim3 grid((unsigned)p.tiles_x, (unsigned)p.y_chunks, (unsigned)n_images);
     if ((size_t)g.IH * g.IW * 3 * (size_t)n_images + 4 >= (size_t)OOB) return hipErrorInvalidValue;
     if ((size_t)g.OH * g.OW * g.COUT >= (size_t)OOB) return hipErrorInvalidValue;   // buffer-descriptor stores
     if (g.COUT == 128) {
@@ -187,7 +185,7 @@ hipError_t launch_l0(const LayerGeom &g, const sicn_weights &w, const uint8_t *i
         hipError_t e = hipFuncSetAttribute((const void *)k_l0<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL(k_l0<4>, grid, dim3(256), lds, stream, in, out, w.d_w_l0, w.d_bias, g.IW, g.IH,
-                           g.OW, g.OH, tiles_y, ty_per, out_layout,
+                           g.OW, g.OH, p.tiles_y, p.ty_per, out_layout,
                            (relu ? ACT_FLOOR_RELU : ACT_FLOOR_RAW) | (nt_store_wanted((size_t)g.OH * g.OW * g.COUT * n_images) ? ACT_NT_STORE : 0u));
     } else
         return hipErrorInvalidValue;
@@ -222,8 +220,7 @@ hipError_t launch_l0(const LayerGeom &g, const sicn_weights &w, const uint8_t *i
 // =============================================================================================
 constexpr int L7_AUX = 0;                                // cache policy of the input stream (2 = nt)
 constexpr int L7_PITCH = 36;                             // positions per window row (34 used)
-constexpr int L7_ROWS = 4;                               // input rows per step
-constexpr int L7_STEP_PIECES = L7_ROWS * L7_PITCH / 16;  // 9 LDS-DMA pieces per region per step
+constexpr int L7_STEP_PIECES = L7_ROWS * L7_PITCH / 16;  // L7_ROWS = 4 input rows per step (sicn_plan.h): 9 LDS-DMA pieces per region per step
 constexpr int L7_AHEAD = 1;                              // steps of rows in flight ahead of the step being computed
 constexpr int L7_RING_PIECES = ((4 * L7_AHEAD + 6) * L7_PITCH + 15) / 16;   // 1 ahead: 23 pieces = 368 positions >= 10 rows
 constexpr int L7_WGS = 3;                                // workgroups per CU the LDS ring allows (1 step ahead)
@@ -433,19 +430,18 @@ hipError_t launch_l7(const LayerGeom &g, const sicn_weights &w, const uint8_t *i
     if (g.CIN != 128 || g.COUT != 3) return hipErrorInvalidValue;
     if ((size_t)g.IH * g.IW * g.CIN >= (size_t)OOB) return hipErrorInvalidValue;
     if ((size_t)g.OH * g.OW * 3 >= (size_t)OOB) return hipErrorInvalidValue;   // buffer-descriptor stores
-    const int tiles_x = (g.IW + TILE_X - 1) / TILE_X, steps_y = (g.IH + L7_ROWS - 1) / L7_ROWS;
     // about two workgroups per CU in all (three would fit) — measured
     // r02 (tools/strip_sweep.py): 1080p x 1 best at 16 - 24 chunks of 30 strips, x 4 at 4 - 6 of 120, 4K x 8 at 1 of 480;
     // every extra chunk re-fetches six halo rows and re-loads the 18 KB of weights
     // (r03, re-measured on one 1080p image, 30 strips: 13 / 15 / 17 / 19 / 21 / 25 chunks -> 23 / 22 / 19 / 24 / 23 / 21 us: the best
     // cut is the one that stays just under TWO workgroups per CU, 510 of 512; the 640 of round 2 was the middle of a flat region)
-    const int y_chunks = l7_chunks(tiles_x, n_images, steps_y, o.strip_chunks, chip);
+    const L7Plan p = plan_l7(g.IW, g.IH, n_images, o.strip_chunks, chip);
     const size_t lds = 2 * L7_REGION + 4 * L7_STAGE + 1024;
-    const dim3 grid(xcd_grid_size((long)tiles_x * y_chunks * n_images, chip.n_xcd));
+    const dim3 grid(p.grid_x);
     hipError_t e = hipFuncSetAttribute((const void *)k_l7, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_l7, grid, dim3(256), lds, stream, in, out, w.d_w_l7, w.d_bias, g.IW, g.IH, g.OW, g.OH, steps_y, y_chunks,
-                       tiles_x, n_images, in_layout, chip.n_xcd);
+    hipLaunchKernelGGL(k_l7, grid, dim3(256), lds, stream, in, out, w.d_w_l7, w.d_bias, g.IW, g.IH, g.OW, g.OH, p.steps_y, p.y_chunks,
+                       p.tiles_x, n_images, in_layout, chip.n_xcd);
     return hipGetLastError();
 }
 

@@ -13,6 +13,7 @@
 
 #include "sicn_gdn_internal.h"
 #include "sicn_internal.h"
+#include "sicn_weights_io.h"
 
 using namespace sicn;
 
@@ -25,40 +26,42 @@ static int env_int(const char *name)
     const char *e = getenv(name);
     return (e && *e) ? atoi(e) : 0;
 }
+// Every field of sicn_options that is checked, in struct order: its environment variable (library defaults; nullptr = none) and its
+// admissible values.  default_options ignores an inadmissible variable, loudly; resolve_options refuses an inadmissible field.
+template <int32_t... V> static bool one_of(int32_t v) { return ((v == V) || ...); }
+template <int32_t LO, int32_t HI> static bool within(int32_t v) { return v >= LO && v <= HI; }
+struct OptionField { int32_t sicn_options::*member; const char *env; bool (*admissible)(int32_t); };
+static const OptionField OPTION_FIELDS[] = {
+    {&sicn_options::force_generic, "SICN_FORCE_GENERIC", within<INT32_MIN, INT32_MAX>},
+    {&sicn_options::mfma_shape, "SICN_MFMA_SHAPE", one_of<0, 16>},
+    {&sicn_options::tile_x, "SICN_TILE_X", one_of<0, 16, 32>},
+    {&sicn_options::strip_chunks, "SICN_STRIP_CHUNKS", within<0, INT32_MAX>},
+    {&sicn_options::no_phase_layout, "SICN_NO_PHASE_LAYOUT", within<0, 2>},
+    {&sicn_options::split_n, "SICN_SPLIT_N", within<0, 4>},
+    {&sicn_options::wave_tile, "SICN_WAVE_TILE", one_of<0, 64, 128>},
+    {&sicn_options::prefetch, "SICN_PREFETCH", within<0, 3>},
+    {&sicn_options::persistent_grid, nullptr, within<0, INT32_MAX>},
+    // the forms that took split_k > 1, l7_loader / l0_form / gdn_fuse = 2 and mfma_shape = 32 were removed (include/sicn.h)
+    {&sicn_options::split_k, "SICN_SPLIT_K", within<0, 1>},
+    {&sicn_options::l7_loader, "SICN_L7_LOADER", within<0, 1>},
+    {&sicn_options::l0_form, "SICN_L0_FORM", within<0, 1>},
+    {&sicn_options::gdn_fuse, "SICN_GDN_FUSE", within<0, 1>},
+};
 const sicn_options &default_options()
 {
     static const sicn_options o = [] {
         sicn_options d;
         std::memset(&d, 0, sizeof d);
         d.struct_bytes = (int32_t)sizeof(sicn_options);
-        d.force_generic = env_int("SICN_FORCE_GENERIC") != 0;
-        d.mfma_shape = env_int("SICN_MFMA_SHAPE");
-        d.tile_x = env_int("SICN_TILE_X");
-        d.strip_chunks = env_int("SICN_STRIP_CHUNKS");
-        d.no_phase_layout = env_int("SICN_NO_PHASE_LAYOUT");
-        d.split_n = env_int("SICN_SPLIT_N");
-        d.wave_tile = env_int("SICN_WAVE_TILE");
-        d.prefetch = env_int("SICN_PREFETCH");
-        d.split_k = env_int("SICN_SPLIT_K");
-        d.l7_loader = env_int("SICN_L7_LOADER");
-        d.l0_form = env_int("SICN_L0_FORM");
-        d.gdn_fuse = env_int("SICN_GDN_FUSE");
-        // the same range checks a caller's struct gets (resolve_options): an out-of-range variable is ignored, loudly, once
-        auto bad = [](const char *name, int32_t &v) {
-            fprintf(stderr, "libsicn: ignoring out-of-range %s=%d\n", name, (int)v);
+        for (const OptionField &f : OPTION_FIELDS) {
+            if (!f.env) continue;
+            int32_t &v = d.*f.member;
+            v = env_int(f.env);
+            if (f.admissible(v)) continue;
+            fprintf(stderr, "libsicn: ignoring out-of-range %s=%d\n", f.env, (int)v);
             v = 0;
-        };
-        if (d.mfma_shape != 0 && d.mfma_shape != 16) bad("SICN_MFMA_SHAPE", d.mfma_shape);
-        if (d.tile_x != 0 && d.tile_x != 16 && d.tile_x != 32) bad("SICN_TILE_X", d.tile_x);
-        if (d.strip_chunks < 0) bad("SICN_STRIP_CHUNKS", d.strip_chunks);
-        if (d.no_phase_layout < 0 || d.no_phase_layout > 2) bad("SICN_NO_PHASE_LAYOUT", d.no_phase_layout);
-        if (d.split_n < 0 || d.split_n > 4) bad("SICN_SPLIT_N", d.split_n);
-        if (d.wave_tile != 0 && d.wave_tile != 64 && d.wave_tile != 128) bad("SICN_WAVE_TILE", d.wave_tile);
-        if (d.prefetch < 0 || d.prefetch > 3) bad("SICN_PREFETCH", d.prefetch);
-        if (d.split_k < 0 || d.split_k > 1) bad("SICN_SPLIT_K", d.split_k);
-        if (d.l7_loader < 0 || d.l7_loader > 1) bad("SICN_L7_LOADER", d.l7_loader);
-        if (d.l0_form < 0 || d.l0_form > 1) bad("SICN_L0_FORM", d.l0_form);
-        if (d.gdn_fuse < 0 || d.gdn_fuse > 1) bad("SICN_GDN_FUSE", d.gdn_fuse);
+        }
+        d.force_generic = d.force_generic != 0;
         return d;
     }();
     return o;
@@ -107,16 +110,8 @@ static int resolve_options(const sicn_options *in, sicn_options *out)
     std::memset(&o, 0, sizeof o);
     std::memcpy(&o, in, (size_t)in->struct_bytes);
     o.struct_bytes = (int32_t)sizeof(sicn_options);
-    if (o.mfma_shape != 0 && o.mfma_shape != 16) return SICN_EINVAL;
-    if (o.tile_x != 0 && o.tile_x != 16 && o.tile_x != 32) return SICN_EINVAL;
-    if (o.strip_chunks < 0 || o.no_phase_layout < 0 || o.no_phase_layout > 2) return SICN_EINVAL;
-    if (o.split_n < 0 || o.split_n > 4) return SICN_EINVAL;
-    if (o.wave_tile != 0 && o.wave_tile != 64 && o.wave_tile != 128) return SICN_EINVAL;
-    if (o.prefetch < 0 || o.prefetch > 3 || o.persistent_grid < 0) return SICN_EINVAL;
-    // the forms that took split_k > 1, l7_loader / l0_form / gdn_fuse = 2 and mfma_shape = 32 were removed (include/sicn.h)
-    if (o.split_k < 0 || o.split_k > 1 || o.l7_loader < 0 || o.l7_loader > 1 || o.l0_form < 0 || o.l0_form > 1 || o.gdn_fuse < 0 ||
-        o.gdn_fuse > 1)
-        return SICN_EINVAL;
+    for (const OptionField &f : OPTION_FIELDS)
+        if (!f.admissible(o.*f.member)) return SICN_EINVAL;
     *out = o;
     return SICN_OK;
 }
@@ -178,41 +173,161 @@ extern "C" int sicn_validate_desc(const sicn_layer_desc *d)
     return SICN_OK;
 }
 
-namespace sicn {
-KernelKind pick_kernel(const sicn_layer_desc &d, const sicn_options &o)
+// ---- kernel families ------------------------------------------------------------------------------
+// Everything the host layer knows about a kernel family is one row of FAMILIES.  The rows are in PRIORITY order: a layer runs on the
+// first family that serves its shape, and the last row serves every shape.  A new family is a new row (and its launcher).
+namespace {
+enum : unsigned { GROUP = 1u << 1, PHASE = 1u << 2 };   // bit l = internal layout l of k_common.hpp (NHWC, layout 0, is everybody's)
+
+struct LaunchArgs {
+    const LayerGeom &g;
+    const sicn_weights &w;
+    const uint8_t *in;
+    uint8_t *out;
+    int n_images;
+    hipStream_t stream;
+    int in_layout, out_layout;
+    const sicn_options &o;
+    const ChipGeom &chip;
+    const sicn_gdn *gdn;       // the layer's activation, nullptr = the reference's ReLU
+    unsigned long long *deal;
+};
+
+struct Family {
+    KernelKind kind;           // ABI: out[2] of sicn_debug_plan
+    const char *name;          // ABI: sicn_kernel_for
+    int transposed;            // the direction it serves; -1: both
+    bool (*shape)(int cin, int cout, int transposed);
+    unsigned reads, writes;    // the internal layouts its kernels take and produce
+    bool rgb_sink;             // no_phase_layout = 2 keeps the PHASE layout away from its input
+    bool pre_relu;             // can store the lane before the ReLU (a layer with a GDN on a family that cannot runs on the last row)
+    // packs and uploads the weight images it reads besides d_w_okc and the bias (the shape is in w); may throw std::bad_alloc
+    bool (*upload_images)(const int8_t *w_okc, sicn_weights &w);
+    // *act_done = true: the kernel applied a.gdn itself
+    hipError_t (*launch)(const LaunchArgs &a, bool *act_done);
+    void (*plan)(const LayerGeom &g, int n_images, const sicn_options &o, const ChipGeom &chip, int32_t out[12]);   // out[3..11] of sicn_debug_plan
+    bool (*deals)(const LayerGeom &g, int n_images, const sicn_options &o, const ChipGeom &chip);   // wants zeroed tile-deal words
+};
+
+template <class Pack>
+bool upload_image(size_t bytes, int8_t **dev, Pack pack)
 {
-    if (o.force_generic) return KK_GENERIC;
-    if (!d.transposed && d.IFM_CH == 3 && d.OFM_CH == 128) return KK_L0_RGB;
-    if (d.transposed && d.IFM_CH == 128 && d.OFM_CH == 3) return KK_L7_RGB;
-    if (mfma_supported(d.IFM_CH, d.OFM_CH, d.transposed)) return d.transposed ? KK_MFMA_DECONV : KK_MFMA_CONV;
-    // every other width the matrix cores can take (k_mfma16c.hip); small and ragged shapes stay on k_generic
-    if (any_supported(d.IFM_CH, d.OFM_CH, d.transposed)) return d.transposed ? KK_MFMA_DECONV_ANY : KK_MFMA_CONV_ANY;
-    return KK_GENERIC;
+    std::vector<int8_t> s(bytes);
+    pack(s.data());
+    return upload(s.data(), s.size(), dev);
 }
-}  // namespace sicn
+
+// layer 0 (k_rgb.hip k_l0, k_l0g.hip)
+bool l0_shape(int cin, int cout, int) { return cin == 3 && cout == 128; }
+bool l0_images(const int8_t *k, sicn_weights &w)
+{
+    return upload_image(l0_bytes(w.cout), &w.d_w_l0, [&](int8_t *s) { pack_l0(k, w.cout, s); }) &&
+           upload_image(l0g_bytes(), &w.d_w_l0g, [&](int8_t *s) { pack_l0g(k, s); });   // the kernel that applies a GDN before its store
+}
+hipError_t l0_launch(const LaunchArgs &a, bool *act_done)
+{
+    // layer 0 + activation in one kernel: the pre-activation tensor never reaches HBM
+    if (a.gdn && a.o.gdn_fuse != 1 && a.w.d_w_l0g && a.gdn->d_gamma_mfma) {
+        *act_done = true;
+        return launch_l0_gdn(a.g, a.w, *a.gdn, a.in, a.out, a.n_images, a.stream, a.out_layout, a.o, a.chip);
+    }
+    return launch_l0(a.g, a.w, a.in, a.out, a.n_images, a.stream, a.out_layout, a.o, a.chip, a.gdn == nullptr);
+}
+void l0_plan(const LayerGeom &g, int n_images, const sicn_options &o, const ChipGeom &chip, int32_t out[12])
+{
+    const L0Plan p = plan_l0(g.OW, g.OH, n_images, false, o.strip_chunks, chip);
+    out[7] = p.tiles_x; out[8] = p.y_chunks; out[9] = n_images; out[10] = p.y_chunks; out[11] = p.ty_per;
+}
+
+// layer 7 (k_rgb.hip k_l7)
+bool l7_shape(int cin, int cout, int) { return cin == 128 && cout == 3; }
+bool l7_images(const int8_t *k, sicn_weights &w)
+{
+    return upload_image(l7_bytes(w.cin), &w.d_w_l7, [&](int8_t *s) { pack_l7(k, w.cin, s); });
+}
+hipError_t l7_launch(const LaunchArgs &a, bool *)
+{
+    return launch_l7(a.g, a.w, a.in, a.out, a.n_images, a.stream, a.in_layout, a.o, a.chip);
+}
+void l7_plan(const LayerGeom &g, int n_images, const sicn_options &o, const ChipGeom &chip, int32_t out[12])
+{
+    const L7Plan p = plan_l7(g.IW, g.IH, n_images, o.strip_chunks, chip);
+    out[7] = (int)p.grid_x; out[8] = 1; out[9] = 1; out[10] = p.y_chunks;
+}
+
+// the 128 / 192-channel implicit-GEMM kernels (k_mfma16.hip: pipelined k_mfma16p.hip, wide persistent k_mfma16x.hip)
+bool mfma_images(const int8_t *k, sicn_weights &w)
+{
+    bool ok = upload_image(mfma16_stream_bytes(w.cin, w.cout), &w.d_w_mfma16,
+                           [&](int8_t *s) { pack_mfma16_stream(k, w.cin, w.cout, w.transposed, s); });
+    if (ok && w.transposed && mfma16x_deconv_stream_bytes(w.cin, w.cout))   // the wide persistent deconv walks the taps in its own order
+        ok = upload_image(mfma16x_deconv_stream_bytes(w.cin, w.cout), &w.d_w_mfma16x,
+                          [&](int8_t *s) { pack_mfma16x_deconv_stream(k, w.cin, w.cout, s); });
+    return ok;
+}
+hipError_t mfma_launch(const LaunchArgs &a, bool *)
+{
+    return launch_mfma16(a.g, a.w, a.in, a.out, a.n_images, a.stream, a.in_layout, a.out_layout, a.o, a.chip, a.gdn == nullptr, a.deal);
+}
+void mfma_plan(const LayerGeom &g, int n_images, const sicn_options &o, const ChipGeom &chip, int32_t out[12])
+{
+    const MfmaPlan p = plan_mfma(g, n_images, o, chip);
+    out[3] = p.family; out[4] = p.tile_x; out[5] = p.split_n; out[6] = 1;   // out[6]: the K split, removed in 0.3.x
+    out[7] = (int)p.grid_x; out[8] = (int)p.grid_y; out[9] = (int)p.grid_z;
+    out[10] = p.deal;
+}
+bool mfma_deals(const LayerGeom &g, int n_images, const sicn_options &o, const ChipGeom &chip) { return plan_mfma(g, n_images, o, chip).deal; }
+
+// every other width the matrix cores can take (k_mfma16c.hip), NHWC in and out
+bool any_images(const int8_t *k, sicn_weights &w)
+{
+    return upload_image(any_bytes(w.cin, w.cout), &w.d_w_any, [&](int8_t *s) { pack_any(k, w.cin, w.cout, s); });
+}
+hipError_t any_launch(const LaunchArgs &a, bool *) { return launch_any(a.g, a.w, a.in, a.out, a.n_images, a.stream, a.gdn == nullptr); }
+void any_plan(const LayerGeom &g, int n_images, const sicn_options &, const ChipGeom &, int32_t out[12])
+{
+    const AnyPlan p = plan_any(g.transposed ? g.IW : g.OW, g.transposed ? g.IH : g.OH, g.COUT, g.transposed, n_images);
+    out[4] = p.tile; out[7] = (int)p.grid_x; out[8] = (int)p.grid_y; out[9] = (int)p.grid_z;
+}
+
+// the shape-agnostic kernel (k_generic.hip): small and ragged shapes, force_generic, and the independent second implementation
+bool every_shape(int, int, int) { return true; }
+hipError_t generic_launch(const LaunchArgs &a, bool *) { return launch_generic(a.g, a.w, a.in, a.out, a.n_images, a.stream, a.gdn == nullptr); }
+
+const Family FAMILIES[] = {
+    // kind, name, direction, shape | reads, writes, rgb_sink, pre_relu | images, launch, plan, deals
+    {KK_L0_RGB, "l0_rgb", 0, l0_shape, 0, GROUP, false, true, l0_images, l0_launch, l0_plan, nullptr},
+    {KK_L7_RGB, "l7_rgb", 1, l7_shape, GROUP | PHASE, 0, true, false, l7_images, l7_launch, l7_plan, nullptr},
+    {KK_MFMA_CONV, "mfma_conv", 0, mfma_supported, GROUP, GROUP, false, true, mfma_images, mfma_launch, mfma_plan, mfma_deals},
+    // the deconv's outputs come one pixel parity at a time
+    {KK_MFMA_DECONV, "mfma_deconv", 1, mfma_supported, GROUP | PHASE, GROUP | PHASE, false, true, mfma_images, mfma_launch, mfma_plan, mfma_deals},
+    {KK_MFMA_CONV_ANY, "mfma_conv_any", 0, any_supported, 0, 0, false, true, any_images, any_launch, any_plan, nullptr},
+    {KK_MFMA_DECONV_ANY, "mfma_deconv_any", 1, any_supported, 0, 0, false, true, any_images, any_launch, any_plan, nullptr},
+    {KK_GENERIC, "generic", -1, every_shape, 0, 0, false, true, nullptr, generic_launch, nullptr, nullptr},
+};
+const Family &GENERIC = FAMILIES[sizeof FAMILIES / sizeof *FAMILIES - 1];
+
+const Family &pick_family(const sicn_layer_desc &d, const sicn_options &o)
+{
+    if (o.force_generic) return GENERIC;
+    for (const Family &f : FAMILIES)
+        if ((f.transposed < 0 || f.transposed == d.transposed) && f.shape(d.IFM_CH, d.OFM_CH, d.transposed)) return f;
+    return GENERIC;
+}
+// the family a layer of a chain runs on, given its activation
+const Family &layer_family(const sicn_layer_desc &d, const sicn_options &o, bool has_gdn)
+{
+    const Family &f = pick_family(d, o);
+    return (has_gdn && !f.pre_relu) ? GENERIC : f;
+}
+}  // namespace
 
 extern "C" const char *sicn_kernel_for(const sicn_layer_desc *d)
 {
-    if (sicn_validate_desc(d)) return "invalid";
-    switch (pick_kernel(*d, default_options())) {
-    case KK_L0_RGB: return "l0_rgb";
-    case KK_L7_RGB: return "l7_rgb";
-    case KK_MFMA_CONV: return "mfma_conv";
-    case KK_MFMA_DECONV: return "mfma_deconv";
-    case KK_MFMA_CONV_ANY: return "mfma_conv_any";
-    case KK_MFMA_DECONV_ANY: return "mfma_deconv_any";
-    default: return "generic";
-    }
+    return sicn_validate_desc(d) ? "invalid" : pick_family(*d, default_options()).name;
 }
 
 // ---- weights ----------------------------------------------------------------------------------
-static bool upload(const void *host, size_t bytes, int8_t **dev)
-{
-    if (hipMalloc((void **)dev, bytes) != hipSuccess) { *dev = nullptr; return false; }
-    if (hipMemcpy(*dev, host, bytes, hipMemcpyHostToDevice) != hipSuccess) return false;
-    return true;
-}
-
 extern "C" void sicn_weights_free(sicn_weights *w)
 {
     if (!w) return;
@@ -237,29 +352,12 @@ extern "C" int sicn_weights_from_finn_tiles(const sicn_layer_desc *d, const void
     if (chip_geom(nullptr) != SICN_OK) return SICN_ENODEV;   // no device, or not a gfx950 one: refuse before anything is uploaded
     if (word_bytes != 1 && word_bytes != 2 && word_bytes != 4 && word_bytes != 8) return SICN_EINVAL;
     if (d->SIMD * 4 > word_bytes * 8) return SICN_EINVAL;
-    const int cin = d->IFM_CH, cout = d->OFM_CH, simd = d->SIMD, pe_n = d->PE, tiles = d->W_TILES;
-    const int kk = 25 * cin, sf_n = kk / simd, nf_n = cout / pe_n;
-
-    // FixedPointWeights (weights.hpp:110-150): W[o = nf*PE + pe][k = sf*SIMD + s] = sign-extended
-    // nibble s of m_weights[pe][nf*SF + sf]; k = (ky*5 + kx)*IFM_CH + c (slidingwindow.h:1304-1325,
-    // cross-checked by conv3_nonsquare_tb.cpp:546-571).
+    const int cin = d->IFM_CH, cout = d->OFM_CH, kk = 25 * cin;
     std::vector<int8_t> w_okc;
     try {
         w_okc.resize((size_t)cout * kk);
     } catch (const std::bad_alloc &) { return SICN_ENOMEM; }
-    const uint8_t *raw = (const uint8_t *)m_weights;
-    for (int pe = 0; pe < pe_n; pe++)
-        for (int nf = 0; nf < nf_n; nf++)
-            for (int sf = 0; sf < sf_n; sf++) {
-                const size_t idx = (size_t)pe * tiles + (size_t)nf * sf_n + sf;
-                uint64_t word = 0;
-                for (int b = 0; b < word_bytes; b++) word |= (uint64_t)raw[idx * word_bytes + b] << (8 * b);
-                for (int s = 0; s < simd; s++) {
-                    int v = (int)((word >> (4 * s)) & 15u);
-                    if (v > 7) v -= 16;
-                    w_okc[(size_t)(nf * pe_n + pe) * kk + sf * simd + s] = (int8_t)v;
-                }
-            }
+    decode_finn_tiles(m_weights, word_bytes, 4, d->SIMD, d->PE, d->W_TILES, kk, cout, w_okc.data());
 
     sicn_weights *w = new (std::nothrow) sicn_weights();
     if (!w) return SICN_ENOMEM;
@@ -273,37 +371,11 @@ extern "C" int sicn_weights_from_finn_tiles(const sicn_layer_desc *d, const void
         for (int i = 0; i < cout; i++) b[i] = bias[i];
         ok = ok && upload(b.data(), b.size(), &w->d_bias);
     }
+    // d_w_okc and the bias always (force_generic, and a layer whose family cannot store the lane before the ReLU, run on them);
+    // besides them the images of the family the shape runs on
     try {
-        if (ok && mfma_supported(cin, cout, d->transposed)) {
-            std::vector<int8_t> s16(mfma16_stream_bytes(cin, cout));
-            pack_mfma16_stream(w_okc.data(), cin, cout, d->transposed, s16.data());
-            ok = upload(s16.data(), s16.size(), &w->d_w_mfma16);
-            if (ok && d->transposed && mfma16x_deconv_stream_bytes(cin, cout)) {   // the wide persistent deconv walks the taps in its own order
-                std::vector<int8_t> sx(mfma16x_deconv_stream_bytes(cin, cout));
-                pack_mfma16x_deconv_stream(w_okc.data(), cin, cout, sx.data());
-                ok = upload(sx.data(), sx.size(), &w->d_w_mfma16x);
-            }
-        }
-        if (ok && !d->transposed && cin == 3 && cout % 32 == 0) {
-            std::vector<int8_t> s(l0_bytes(cout));
-            pack_l0(w_okc.data(), cout, s.data());
-            ok = upload(s.data(), s.size(), &w->d_w_l0);
-            if (ok && cout == 128) {   // the image of the kernel that applies a GDN before its store
-                std::vector<int8_t> sg(l0g_bytes());
-                pack_l0g(w_okc.data(), sg.data());
-                ok = upload(sg.data(), sg.size(), &w->d_w_l0g);
-            }
-        }
-        if (ok && d->transposed && cin == 128 && cout == 3) {
-            std::vector<int8_t> s(l7_bytes(cin));
-            pack_l7(w_okc.data(), cin, s.data());
-            ok = upload(s.data(), s.size(), &w->d_w_l7);
-        }
-        if (ok && any_supported(cin, cout, d->transposed)) {
-            std::vector<int8_t> s(any_bytes(cin, cout));
-            pack_any(w_okc.data(), cin, cout, s.data());
-            ok = upload(s.data(), s.size(), &w->d_w_any);
-        }
+        const Family &f = pick_family(*d, sicn_options{});
+        if (ok && f.upload_images) ok = f.upload_images(w_okc.data(), *w);
     } catch (const std::bad_alloc &) { ok = false; }
     if (!ok) {
         sicn_weights_free(w);
@@ -316,25 +388,14 @@ extern "C" int sicn_weights_from_finn_tiles(const sicn_layer_desc *d, const void
 // ---- single layers ------------------------------------------------------------------------------
 // Layout of the tensor between layer `p` (producer) and layer `c` (consumer) of a chain: the best
 // one both kernels implement (k_common.hpp).  0 = NHWC, 1 = GROUP, 2 = PHASE.
-// the kernel family a layer runs on: the RGB deconv kernel has no pre-ReLU output, so a layer-7-shaped layer with a
-// GDN goes to the shape-agnostic kernel
-static KernelKind layer_kernel(const sicn_layer_desc &d, const sicn_options &o, bool has_gdn)
-{
-    const KernelKind k = pick_kernel(d, o);
-    return (has_gdn && k == KK_L7_RGB) ? KK_GENERIC : k;
-}
-
 static int link_layout(const sicn_layer_desc &p, const sicn_layer_desc &c, const sicn_options &o, bool p_gdn, bool c_gdn)
 {
-    const KernelKind kp = layer_kernel(p, o, p_gdn), kc = layer_kernel(c, o, c_gdn);
-    const bool w_group = kp == KK_MFMA_CONV || kp == KK_MFMA_DECONV || kp == KK_L0_RGB;
-    const bool w_phase = kp == KK_MFMA_DECONV;   // its outputs come one pixel parity at a time
-    const bool r_group = kc == KK_MFMA_CONV || kc == KK_MFMA_DECONV || kc == KK_L7_RGB;
-    const bool r_phase = kc == KK_MFMA_DECONV || kc == KK_L7_RGB;
+    const Family &fc = layer_family(c, o, c_gdn);
+    const unsigned common = layer_family(p, o, p_gdn).writes & fc.reads;
     // experiments: no_phase_layout 1 = never, 2 = not towards the RGB layer
-    const bool phase_ok = o.no_phase_layout == 0 || (o.no_phase_layout == 2 && kc != KK_L7_RGB);
-    if (w_phase && r_phase && phase_ok) return 2;
-    if (w_group && r_group) return 1;
+    const bool phase_ok = o.no_phase_layout == 0 || (o.no_phase_layout == 2 && !fc.rgb_sink);
+    if ((common & PHASE) && phase_ok) return 2;
+    if (common & GROUP) return 1;
     return 0;
 }
 
@@ -354,33 +415,12 @@ static int run_layer(const sicn_layer_desc *d, const sicn_weights *w, const uint
     if (n_images > 65535) return SICN_EINVAL;
     if (gdn && gdn->channels != d->OFM_CH) return SICN_EINVAL;
     const LayerGeom g = geom_of(*d);
-    const bool relu = gdn == nullptr;
     ChipGeom chip;
     if ((rc = chip_geom(&chip)) != SICN_OK) return rc;   // no device, or not a gfx950 one
-    hipError_t e;
-    switch (layer_kernel(*d, o, gdn != nullptr)) {
-    case KK_L0_RGB:
-        // layer 0 + activation in one kernel where it exists (128 channels): the pre-activation tensor never reaches HBM
-        if (gdn && o.gdn_fuse != 1 && w->d_w_l0g && gdn->d_gamma_mfma && gdn->channels == 128) {
-            e = launch_l0_gdn(g, *w, *gdn, in, out, n_images, stream, out_layout, o, chip);
-            gdn = nullptr;
-            break;
-        }
-        e = launch_l0(g, *w, in, out, n_images, stream, out_layout, o, chip, relu);
-        break;
-    case KK_L7_RGB:
-        e = launch_l7(g, *w, in, out, n_images, stream, in_layout, o, chip);
-        break;
-    case KK_MFMA_CONV:
-    case KK_MFMA_DECONV:
-        e = launch_mfma16(g, *w, in, out, n_images, stream, in_layout, out_layout, o, chip, relu, deal);
-        break;
-    case KK_MFMA_CONV_ANY:
-    case KK_MFMA_DECONV_ANY:
-        e = launch_any(g, *w, in, out, n_images, stream, relu);   // NHWC in and out: link_layout puts NHWC next to these kinds
-        break;
-    default: e = launch_generic(g, *w, in, out, n_images, stream, relu); break;
-    }
+    bool act_done = false;
+    const LaunchArgs args{g, *w, in, out, n_images, stream, in_layout, out_layout, o, chip, gdn, deal};
+    hipError_t e = layer_family(*d, o, gdn != nullptr).launch(args, &act_done);
+    if (act_done) gdn = nullptr;
     if (e == hipSuccess && gdn) e = launch_gdn(*gdn, out, out_layout, d->OFM_ROW, d->OFM_COL, n_images, stream);
     if (e == hipErrorInvalidValue) return SICN_EINVAL;
     return e == hipSuccess ? SICN_OK : SICN_ENODEV;
@@ -431,7 +471,6 @@ struct sicn_net {
 };
 
 static size_t out_bytes(const sicn_layer_desc &d) { return (size_t)d.OFM_COL * d.OFM_ROW * d.OFM_CH; }
-static size_t in_bytes(const sicn_layer_desc &d) { return (size_t)d.IFM_COL * d.IFM_ROW * d.IFM_CH; }
 static size_t align256(size_t v) { return (v + 255) / 256 * 256; }
 
 extern "C" int sicn_net_create(const sicn_layer_desc *descs, sicn_weights *const *weights, int n_layers,
@@ -526,8 +565,8 @@ extern "C" int sicn_net_forward(const sicn_net *net, int first, int last, const 
         // does a layer of this call deal tiles dynamically?  (small inputs never do: no zeroing launch in front of them)
         bool any_deal = false;
         for (int l = first; l <= last && !any_deal; l++) {
-            const KernelKind k = pick_kernel(net->descs[l], net->opt);
-            any_deal = (k == KK_MFMA_CONV || k == KK_MFMA_DECONV) && plan_mfma(geom_of(net->descs[l]), n_images, net->opt, chip).deal;
+            const Family &f = pick_family(net->descs[l], net->opt);
+            any_deal = f.deals && f.deals(geom_of(net->descs[l]), n_images, net->opt, chip);
         }
         if (any_deal && workspace && workspace_bytes >= 2 * slot + deal_bytes(net) && !debug_env().no_deal) {
             deal_base = (unsigned long long *)((uint8_t *)workspace + 2 * slot);
@@ -552,17 +591,17 @@ extern "C" int sicn_net_forward(const sicn_net *net, int first, int last, const 
         const int out_layout = (l < last && l != tap_layer)
                                    ? link_layout(net->descs[l], net->descs[l + 1], net->opt, net->gdn[l] != nullptr, net->gdn[l + 1] != nullptr)
                                    : 0;
-        const int slot = slot0 >= 0 ? slot0 + (l - first) : -1;
-        if (slot >= 0) {
-            net->ev_layer[slot].store(-1, std::memory_order_relaxed);   // becomes l once both events are recorded
-            if (hipEventRecord(net->ev_begin[slot], stream) != hipSuccess) return SICN_ENODEV;
+        const int ev = slot0 >= 0 ? slot0 + (l - first) : -1;
+        if (ev >= 0) {
+            net->ev_layer[ev].store(-1, std::memory_order_relaxed);   // becomes l once both events are recorded
+            if (hipEventRecord(net->ev_begin[ev], stream) != hipSuccess) return SICN_ENODEV;
         }
         int rc = run_layer(&net->descs[l], net->weights[l], cur, dst, n_images, stream, -1, net->opt, cur_layout, out_layout,
                            net->gdn[l], deal_base ? deal_base + (size_t)l * DEAL_WORDS : nullptr);
         if (rc) return rc;
-        if (slot >= 0) {
-            if (hipEventRecord(net->ev_end[slot], stream) != hipSuccess) return SICN_ENODEV;
-            net->ev_layer[slot].store(l, std::memory_order_release);
+        if (ev >= 0) {
+            if (hipEventRecord(net->ev_end[ev], stream) != hipSuccess) return SICN_ENODEV;
+            net->ev_layer[ev].store(l, std::memory_order_release);
         }
         if (l == tap_layer && tap_out != dst) {
             if (hipMemcpyAsync(tap_out, dst, out_bytes(net->descs[l]) * (size_t)n_images, hipMemcpyDeviceToDevice,
@@ -572,7 +611,6 @@ extern "C" int sicn_net_forward(const sicn_net *net, int first, int last, const 
         cur = dst;
         cur_layout = out_layout;
     }
-    (void)in_bytes;
     return SICN_OK;
 }
 
@@ -666,25 +704,9 @@ extern "C" int sicn_debug_plan(const sicn_layer_desc *d, int n_images, const sic
     for (int i = 0; i < 12; i++) out[i] = 0;
     out[0] = chip.n_cu;
     out[1] = chip.n_xcd;
-    const KernelKind k = pick_kernel(*d, o);
-    out[2] = (int)k;
-    if (k == KK_MFMA_CONV || k == KK_MFMA_DECONV) {
-        const MfmaPlan p = plan_mfma(g, n_images, o, chip);
-        out[3] = p.family; out[4] = p.tile_x; out[5] = p.split_n; out[6] = 1;   // out[6]: the K split, removed in 0.3.x
-        out[7] = (int)p.grid_x; out[8] = (int)p.grid_y; out[9] = (int)p.grid_z;
-        out[10] = p.deal;
-    } else if (k == KK_MFMA_CONV_ANY || k == KK_MFMA_DECONV_ANY) {
-        const AnyPlan p = plan_any(g.transposed ? g.IW : g.OW, g.transposed ? g.IH : g.OH, g.COUT, g.transposed, n_images);
-        out[4] = p.tile; out[7] = (int)p.grid_x; out[8] = (int)p.grid_y; out[9] = (int)p.grid_z;
-    } else if (k == KK_L7_RGB) {
-        const int tiles_x = (g.IW + 31) / 32, steps_y = (g.IH + 3) / 4;
-        const int yc = l7_chunks(tiles_x, n_images, steps_y, o.strip_chunks, chip);
-        out[7] = (int)xcd_grid_size((long)tiles_x * yc * n_images, chip.n_xcd); out[8] = 1; out[9] = 1; out[10] = yc;
-    } else if (k == KK_L0_RGB) {
-        const int tiles_x = (g.OW + 31) / 32, tiles_y = (g.OH + 7) / 8;
-        const L0Cut c = l0_chunks(tiles_x, tiles_y, n_images, 9, o.strip_chunks, chip);
-        out[7] = tiles_x; out[8] = c.y_chunks; out[9] = n_images; out[10] = c.y_chunks; out[11] = c.ty_per;
-    }
+    const Family &f = pick_family(*d, o);
+    out[2] = (int)f.kind;
+    if (f.plan) f.plan(g, n_images, o, chip, out);
     return SICN_OK;
 }
 // host mirror of the kernels' XCD-aware work list: the item of workgroup `block`, or -1 (a bijection for every XCD count)
@@ -727,7 +749,7 @@ extern "C" int sicn_gdn_create(int channels, int inverse, int shift, const uint3
     if (!g) return SICN_ENOMEM;
     // kc = 2^s (1 + b 2^-16), s = 16 - shift / 8 - shift, b = 5 / 33 (oracle/sicn_gdn_oracle.c): 17 significant bits, exact in binary32
     *g = sicn_gdn{channels, inverse, shift, std::ldexp((float)(65536 + (inverse ? 33 : 5)), (inverse ? 8 : 16) - shift - 16), nullptr, nullptr, nullptr, nullptr};
-    bool ok = upload(beta, (size_t)channels * 4, (int8_t **)&g->d_beta) &&
+    bool ok = upload(beta, (size_t)channels * 4, &g->d_beta) &&
               upload(gamma, (size_t)channels * channels, &g->d_gamma);
     if (ok && (channels == 128 || channels == 192)) {
         try {
@@ -739,7 +761,7 @@ extern "C" int sicn_gdn_create(int channels, int inverse, int shift, const uint3
                 for (int j = 0; j < channels; j++) row += gamma[(size_t)i * channels + j];
                 beta_mfma[(size_t)i] = beta[i] + 128u * row;
             }
-            ok = upload(img.data(), img.size(), &g->d_gamma_mfma) && upload(beta_mfma.data(), beta_mfma.size() * 4, (int8_t **)&g->d_beta_mfma);
+            ok = upload(img.data(), img.size(), &g->d_gamma_mfma) && upload(beta_mfma.data(), beta_mfma.size() * 4, &g->d_beta_mfma);
         } catch (const std::bad_alloc &) { ok = false; }
     }
     if (!ok) {

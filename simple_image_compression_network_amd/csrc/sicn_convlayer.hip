@@ -21,6 +21,7 @@
 
 #include "../../include/sicn.h"
 #include "../../include/sicn_convlayer.h"
+#include "sicn_weights_io.h"
 
 struct sicn_convlayer_params {
     sicn_convlayer_desc d;
@@ -492,33 +493,19 @@ extern "C" int sicn_convlayer_params_create(const sicn_convlayer_desc *d, const 
     if (!m_weights || (word_bytes != 1 && word_bytes != 2 && word_bytes != 4 && word_bytes != 8)) return SICN_EINVAL;
     if (d->SIMD * d->W_BIT > word_bytes * 8) return SICN_EINVAL;
     if ((d->activation == SICN_ACT_THRESHOLDS) != (thresholds != nullptr)) return SICN_EINVAL;
-    const int kk = d->K * d->K * d->IFM_CH, sf_n = kk / d->SIMD, nf_n = d->OFM_CH / d->PE;
+    const int kk = d->K * d->K * d->IFM_CH, nf_n = d->OFM_CH / d->PE;
     std::vector<int8_t> w;
     std::vector<int32_t> t;
     try {
         w.resize((size_t)d->OFM_CH * kk);
         if (thresholds) t.resize((size_t)d->OFM_CH * d->NUM_TH);
     } catch (const std::bad_alloc &) { return SICN_ENOMEM; }
-    // FixedPointWeights: W[o = nf*PE + pe][k = sf*SIMD + s] = sign-extended element s of m_weights[pe][nf*SF + sf]
-    const uint8_t *raw = (const uint8_t *)m_weights;
-    const int wb = d->W_BIT;
-    for (int pe = 0; pe < d->PE; pe++)
-        for (int nf = 0; nf < nf_n; nf++) {
-            for (int sf = 0; sf < sf_n; sf++) {
-                const size_t idx = (size_t)pe * d->W_TILES + (size_t)nf * sf_n + sf;
-                uint64_t word = 0;
-                for (int b = 0; b < word_bytes; b++) word |= (uint64_t)raw[idx * word_bytes + b] << (8 * b);
-                for (int s = 0; s < d->SIMD; s++) {
-                    int v = (int)((word >> (wb * s)) & ((1u << wb) - 1));
-                    if (v >> (wb - 1)) v -= 1 << wb;
-                    w[(size_t)(nf * d->PE + pe) * kk + sf * d->SIMD + s] = (int8_t)v;
-                }
-            }
-            // ThresholdsActivation::m_thresholds[PE][NF][NumTH] -> [o][i]
-            if (thresholds)
+    sicn::decode_finn_tiles(m_weights, word_bytes, d->W_BIT, d->SIMD, d->PE, d->W_TILES, kk, d->OFM_CH, w.data());
+    if (thresholds)   // ThresholdsActivation::m_thresholds[PE][NF][NumTH] -> [o][i]
+        for (int pe = 0; pe < d->PE; pe++)
+            for (int nf = 0; nf < nf_n; nf++)
                 for (int i = 0; i < d->NUM_TH; i++)
                     t[(size_t)(nf * d->PE + pe) * d->NUM_TH + i] = thresholds[((size_t)pe * nf_n + nf) * d->NUM_TH + i];
-        }
     sicn_convlayer_params *p = new (std::nothrow) sicn_convlayer_params();
     if (!p) return SICN_ENOMEM;
     p->d = *d;
@@ -526,8 +513,7 @@ extern "C" int sicn_convlayer_params_create(const sicn_convlayer_desc *d, const 
     p->d_thr = nullptr;
     p->d_w_mfma = nullptr;
     p->d_wsum = nullptr;
-    bool ok = hipMalloc((void **)&p->d_w_okc, w.size()) == hipSuccess &&
-              hipMemcpy(p->d_w_okc, w.data(), w.size(), hipMemcpyHostToDevice) == hipSuccess;
+    bool ok = sicn::upload(w.data(), w.size(), &p->d_w_okc);
     if (ok) {   // the MFMA image: [O/16][tap][C/64][16 rows][64 bytes], zero padded
         const int KK = d->K * d->K, nchunk = (d->IFM_CH + 63) / 64, ntile = (d->OFM_CH + 15) / 16;
         std::vector<int8_t> wm;
@@ -546,14 +532,9 @@ extern "C" int sicn_convlayer_params_create(const sicn_convlayer_desc *d, const 
                     wm[((((size_t)(o / 16) * KK + t) * nchunk + c / 64) * 16 + o % 16) * 64 + c % 64] = v;
                     ws[o] += v;
                 }
-        ok = hipMalloc((void **)&p->d_w_mfma, wm.size()) == hipSuccess &&
-             hipMemcpy(p->d_w_mfma, wm.data(), wm.size(), hipMemcpyHostToDevice) == hipSuccess &&
-             hipMalloc((void **)&p->d_wsum, ws.size() * 4) == hipSuccess &&
-             hipMemcpy(p->d_wsum, ws.data(), ws.size() * 4, hipMemcpyHostToDevice) == hipSuccess;
+        ok = sicn::upload(wm.data(), wm.size(), &p->d_w_mfma) && sicn::upload(ws.data(), ws.size() * 4, &p->d_wsum);
     }
-    if (ok && thresholds)
-        ok = hipMalloc((void **)&p->d_thr, t.size() * 4) == hipSuccess &&
-             hipMemcpy(p->d_thr, t.data(), t.size() * 4, hipMemcpyHostToDevice) == hipSuccess;
+    if (ok && thresholds) ok = sicn::upload(t.data(), t.size() * 4, &p->d_thr);
     if (!ok) {
         sicn_convlayer_params_free(p);
         return SICN_ENOMEM;

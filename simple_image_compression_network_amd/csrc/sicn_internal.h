@@ -12,11 +12,8 @@ namespace sicn {
 // Geometry of the implicit-GEMM kernels (k_mfma16*.hip).  One workgroup owns an "M tile" of
 // TILE_Y x TILE_X positions of the M grid (conv: output pixels; deconv: input pixels) and all
 // output channels.  LDS holds sub-patches of (TILE_Y+2) x (TILE_X+2) positions x 32 bytes.
-constexpr int TILE_Y = 8;
-constexpr int TILE_X = 32;
+constexpr int TILE_Y = 8;                      // TILE_X = 32: sicn_plan.h
 constexpr int PATCH_Y = TILE_Y + 2;
-constexpr int PATCH_X = TILE_X + 2;
-constexpr int PATCH_PIX = PATCH_Y * PATCH_X;  // 340
 constexpr int KSTEP = 32;                      // bytes of K per MFMA (v_mfma_i32_32x32x32_i8)
 
 enum KernelKind : int { KK_GENERIC = 0, KK_MFMA_CONV, KK_MFMA_DECONV, KK_L0_RGB, KK_L7_RGB, KK_MFMA_CONV_ANY, KK_MFMA_DECONV_ANY };
@@ -39,7 +36,6 @@ struct sicn_weights {
     int8_t *d_bias;       // [cout] int8
     int8_t *d_w_mfma16;    // implicit-GEMM tile stream for v_mfma_i32_16x16x64_i8 (k_mfma16.hip), or nullptr when the shape is not served by it
     int8_t *d_w_mfma16x;   // deconv 128 -> 128: the tiles in the order the wide persistent kernel walks them (k_mfma16x.hip), or nullptr
-    int8_t *d_bias_sigma;  // [cout] bias in sigma order == natural order (kept for clarity)
     // layer-0 (RGB -> cout) and layer-7 (cin -> RGB) layouts, or nullptr
     int8_t *d_w_l0;
     int8_t *d_w_l0g;       // layer 0, 128 channels: the A-operand image of the kernel that applies a GDN before its store (k_l0g.hip)
@@ -48,8 +44,6 @@ struct sicn_weights {
 };
 
 namespace sicn {
-
-KernelKind pick_kernel(const sicn_layer_desc &d, const sicn_options &o);
 
 // the tile deal of the wide persistent kernels: 16 ticket counters (one per XCD) + one mailbox per workgroup
 constexpr int DEAL_MAX_WORKGROUPS = WIDE_DEAL_MAX_WORKGROUPS;

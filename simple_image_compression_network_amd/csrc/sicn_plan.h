@@ -88,26 +88,40 @@ inline AnyPlan plan_any(int m_w, int m_h, int cout, int deconv, int n_images)
     return p;
 }
 
-// ---- layer 7 (k_l7): vertical strips of 32 input columns, cut into y_chunks runs ----------------------------------------------
-// just under TWO workgroups per CU in all (measured r03: 510 of 512 best); every cut re-fetches six halo rows and the weights
-inline int l7_chunks(int tiles_x, int n_images, int steps_y, int forced, const ChipGeom &c)
+// ---- the RGB layers (k_rgb.hip, k_l0g.hip): vertical strips of TILE_X columns, each cut into runs ---------------------------------
+// The tile sizes are here, once, for the kernels and for the planning; the launchers and sicn_debug_plan call the same functions.
+constexpr int TILE_X = 32;     // columns of a strip (and of an M tile of the 8 x 32 implicit-GEMM kernels, sicn_internal.h)
+constexpr int L0_TY = 8;       // layer 0: output rows per tile (wave w = rows 2w, 2w+1)
+constexpr int L0_CHUNK = 9;    // layer 0: tiles a workgroup walks at most (its raw pixels are LDS-resident)
+constexpr int L0G_CHUNK = 8;   // the same for layer 0 fused with its GDN (8 is the most two workgroups' LDS holds)
+constexpr int L7_ROWS = 4;     // layer 7: input rows per step
+
+// layer 7: y_chunks runs per strip, just under TWO workgroups per CU in all (measured r03: 510 of 512 best); every cut re-fetches
+// six halo rows and the weights.  forced > 0 (sicn_options.strip_chunks): that many runs.  A 1-D XCD-aware grid.
+struct L7Plan { int tiles_x, steps_y, y_chunks; unsigned grid_x; };
+inline L7Plan plan_l7(int iw, int ih, int n_images, int forced, const ChipGeom &c)
 {
-    long y = forced > 0 ? forced : (2L * c.n_cu) / ((long)tiles_x * n_images);
+    L7Plan p{(iw + TILE_X - 1) / TILE_X, (ih + L7_ROWS - 1) / L7_ROWS, 0, 0u};
+    long y = forced > 0 ? forced : (2L * c.n_cu) / ((long)p.tiles_x * n_images);
     if (y < 1) y = 1;
-    if (y > steps_y) y = steps_y;
-    return (int)y;
+    if (y > p.steps_y) y = p.steps_y;
+    p.y_chunks = (int)y;
+    p.grid_x = xcd_grid_size((long)p.tiles_x * p.y_chunks * n_images, c.n_xcd);
+    return p;
 }
 
-// ---- layer 0 (k_l0): vertical runs of at most `max_run` tiles per workgroup, about four workgroups per CU on small images -----
-struct L0Cut { int y_chunks, ty_per; };
-inline L0Cut l0_chunks(int tiles_x, int tiles_y, int n_images, int max_run, int forced, const ChipGeom &c)
+// layer 0: vertical runs of at most L0_CHUNK (fused with a GDN: L0G_CHUNK) tiles per workgroup, evened out; about four workgroups
+// per CU on small images; forced > 0 can only shorten the runs.  Grid = tiles_x x y_chunks x n_images.
+struct L0Plan { int tiles_x, tiles_y, y_chunks, ty_per; };
+inline L0Plan plan_l0(int ow, int oh, int n_images, bool gdn_fused, int forced, const ChipGeom &c)
 {
+    const int tiles_x = (ow + TILE_X - 1) / TILE_X, tiles_y = (oh + L0_TY - 1) / L0_TY, max_run = gdn_fused ? L0G_CHUNK : L0_CHUNK;
     int y_chunks = (tiles_y + max_run - 1) / max_run;
     long want = (4L * c.n_cu + (long)tiles_x * n_images - 1) / ((long)tiles_x * n_images);
     if (forced > 0) want = forced;
     if (want > y_chunks) y_chunks = want > tiles_y ? tiles_y : (int)want;
     const int ty_per = (tiles_y + y_chunks - 1) / y_chunks;
-    return L0Cut{(tiles_y + ty_per - 1) / ty_per, ty_per};
+    return L0Plan{tiles_x, tiles_y, (tiles_y + ty_per - 1) / ty_per, ty_per};
 }
 
 }  // namespace sicn

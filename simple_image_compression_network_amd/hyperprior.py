@@ -63,12 +63,7 @@ def random_layer_params(rng, d: LayerDesc):
 
 def hyper_descs(lat_w: int, lat_h: int):
     """([h_a descs], [h_s descs]) for a latent of lat_h x lat_w x 192."""
-    def mk(cin, cout, simd, pe, w, h, tr):
-        ow, oh = (2 * w, 2 * h) if tr else ((w + 1) // 2, (h + 1) // 2)
-        d = LayerDesc(IFM_CH=cin, IFM_ROW=w, IFM_COL=h, OFM_CH=cout, OFM_ROW=ow, OFM_COL=oh, SIMD=simd, PE=pe,
-                      W_TILES=(cout // pe) * (25 * cin // simd), transposed=tr)
-        d.validate()
-        return d
+    mk = LayerDesc.make
     a0 = mk(192, 128, 12, 16, lat_w, lat_h, 0)
     a1 = mk(128, 128, 8, 16, a0.OFM_ROW, a0.OFM_COL, 0)
     s0 = mk(128, 128, 8, 16, a1.OFM_ROW, a1.OFM_COL, 1)

@@ -11,8 +11,7 @@ from simple_image_compression_network_amd import api
 from simple_image_compression_network_amd.config import LayerDesc
 w, h, tr = int(sys.argv[1]), int(sys.argv[2]), int(sys.argv[3])
 grid = int(sys.argv[4]) if len(sys.argv) > 4 else 0
-ow, oh = (2 * w, 2 * h) if tr else ((w + 1) // 2, (h + 1) // 2)
-d = LayerDesc(IFM_CH=128, IFM_ROW=w, IFM_COL=h, OFM_CH=128, OFM_ROW=ow, OFM_COL=oh, SIMD=8, PE=16, W_TILES=8 * 400, transposed=tr)
+d = LayerDesc.make(128, 128, 8, 16, w, h, tr)
 rng = np.random.default_rng(1)
 W = rng.integers(-8, 8, (128, 5, 5, 128)).astype(np.int8)
 b = rng.integers(-128, 128, 128).astype(np.int8)

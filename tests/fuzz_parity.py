@@ -38,10 +38,7 @@ for case in range(args.cases):
     if cin == 3:
         w, h = w * 2 + int(rng.integers(2)), h * 2 + int(rng.integers(2))
     n = int(rng.integers(1, 4))
-    ow, oh = (2 * w, 2 * h) if tr else ((w + 1) // 2, (h + 1) // 2)
-    d = LayerDesc(IFM_CH=cin, IFM_ROW=w, IFM_COL=h, OFM_CH=cout, OFM_ROW=ow, OFM_COL=oh, SIMD=simd, PE=pe,
-                  W_TILES=(cout // pe) * (25 * cin // simd), transposed=tr)
-    d.validate()
+    d = LayerDesc.make(cin, cout, simd, pe, w, h, tr)
     env = {}                     # sicn_options fields, per call
     if rng.random() < 0.5:
         env["strip_chunks"] = int(rng.integers(1, 9))
@@ -129,10 +126,7 @@ for case in range(args.gdn):
         env["strip_chunks"] = int(rng.integers(1, 7))
     n = int(rng.integers(1, 4))
     def mk(cin, cout, simd, pe, w, h, tr):
-        ow, oh = (2 * w, 2 * h) if tr else ((w + 1) // 2, (h + 1) // 2)
-        d = LayerDesc(IFM_CH=cin, IFM_ROW=w, IFM_COL=h, OFM_CH=cout, OFM_ROW=ow, OFM_COL=oh, SIMD=simd, PE=pe,
-                      W_TILES=(cout // pe) * (25 * cin // simd), transposed=tr)
-        d.validate()
+        d = LayerDesc.make(cin, cout, simd, pe, w, h, tr)
         Wt = rng.integers(-8, 8, (cout, 5, 5, cin)).astype(np.int8)
         bt = rng.integers(-128, 128, cout).astype(np.int8)
         return d, Wt, bt
@@ -165,9 +159,7 @@ for case in range(args.deal):
     mw, mh = 32 * (tx - 1) + int(rng.integers(1, 33)), 16 * (ty - 1) + int(rng.integers(1, 17))
     assert ((mw + 31) // 32) * ((mh + 15) // 16) * n >= 16 * grid
     w, h = (mw, mh) if tr else (2 * mw - int(rng.integers(2)), 2 * mh - int(rng.integers(2)))
-    ow, oh = (2 * w, 2 * h) if tr else ((w + 1) // 2, (h + 1) // 2)
-    d = LayerDesc(IFM_CH=128, IFM_ROW=w, IFM_COL=h, OFM_CH=128, OFM_ROW=ow, OFM_COL=oh, SIMD=8, PE=16, W_TILES=8 * 400, transposed=tr)
-    d.validate()
+    d = LayerDesc.make(128, 128, 8, 16, w, h, tr)
     Wt = rng.integers(-8, 8, (128, 5, 5, 128)).astype(np.int8)
     bt = rng.integers(-128, 128, 128).astype(np.int8)
     fpw = api.FixedPointWeights(8, 4, 16, d.W_TILES, sicn_ref.pack_finn_tiles(Wt, 8, 16))

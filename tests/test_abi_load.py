@@ -167,10 +167,7 @@ def test_mfma_plans_run_only_the_pipelined_and_wide_kernels():
     even when 32 is asked for — no GPU needed."""
     from simple_image_compression_network_amd.config import LayerDesc
 
-    def desc(cin, cout, simd, pe, w, h, tr):
-        ow, oh = (2 * w, 2 * h) if tr else ((w + 1) // 2, (h + 1) // 2)
-        return LayerDesc(IFM_CH=cin, IFM_ROW=w, IFM_COL=h, OFM_CH=cout, OFM_ROW=ow, OFM_COL=oh, SIMD=simd, PE=pe,
-                         W_TILES=(cout // pe) * (25 * cin // simd), transposed=tr)
+    desc = LayerDesc.make
 
     shapes = [(128, 128, 8, 16), (192, 128, 12, 16), (128, 192, 8, 24)]
     for cin, cout, simd, pe in shapes:

@@ -16,11 +16,7 @@ def _simd_pe(cin, cout):
 
 def _desc(cin, cout, tr, w=40, h=24):
     simd, pe = _simd_pe(cin, cout)
-    ow, oh = (2 * w, 2 * h) if tr else ((w + 1) // 2, (h + 1) // 2)
-    d = LayerDesc(IFM_CH=cin, IFM_ROW=w, IFM_COL=h, OFM_CH=cout, OFM_ROW=ow, OFM_COL=oh, SIMD=simd, PE=pe,
-                  W_TILES=(cout // pe) * (25 * cin // simd), transposed=tr)
-    d.validate()
-    return d
+    return LayerDesc.make(cin, cout, simd, pe, w, h, tr)
 
 
 def _name(d):

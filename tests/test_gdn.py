@@ -195,12 +195,7 @@ def test_gdn_abi_symbols_exported():
 
 
 # ------------------------------------------------------------------------------------------ GPU
-def _mk_desc(cin, cout, simd, pe, w, h, tr):
-    ow, oh = (2 * w, 2 * h) if tr else ((w + 1) // 2, (h + 1) // 2)
-    d = LayerDesc(IFM_CH=cin, IFM_ROW=w, IFM_COL=h, OFM_CH=cout, OFM_ROW=ow, OFM_COL=oh, SIMD=simd, PE=pe,
-                  W_TILES=(cout // pe) * (25 * cin // simd), transposed=tr)
-    d.validate()
-    return d
+_mk_desc = LayerDesc.make
 
 
 @gpu

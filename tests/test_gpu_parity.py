@@ -39,12 +39,7 @@ def _dev(a):
     return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
-def _mk_desc(cin, cout, simd, pe, w, h, tr):
-    ow, oh = (2 * w, 2 * h) if tr else ((w + 1) // 2, (h + 1) // 2)
-    d = LayerDesc(IFM_CH=cin, IFM_ROW=w, IFM_COL=h, OFM_CH=cout, OFM_ROW=ow, OFM_COL=oh, SIMD=simd, PE=pe,
-                  W_TILES=(cout // pe) * (25 * cin // simd), transposed=tr)
-    d.validate()
-    return d
+_mk_desc = LayerDesc.make
 
 
 def _rand_params(rng, d):

@@ -90,10 +90,7 @@ def test_reference_selfcheck_restated_all_ones(param_words):
 
 
 def _rand_layer(rng, cin, cout, simd, pe, w, h, tr):
-    ow, oh = (2 * w, 2 * h) if tr else ((w + 1) // 2, (h + 1) // 2)
-    d = LayerDesc(IFM_CH=cin, IFM_ROW=w, IFM_COL=h, OFM_CH=cout, OFM_ROW=ow, OFM_COL=oh, SIMD=simd,
-                  PE=pe, W_TILES=(cout // pe) * (25 * cin // simd), transposed=tr)
-    d.validate()
+    d = LayerDesc.make(cin, cout, simd, pe, w, h, tr)
     W = rng.integers(-8, 8, (cout, 5, 5, cin)).astype(np.int8)
     b = rng.integers(-128, 128, cout).astype(np.int8)
     x = rng.integers(0, 256, (h, w, cin), dtype=np.uint8)          # includes pixels >= 128

@@ -61,11 +61,7 @@ def run_step(name):
     rng = np.random.default_rng(0)
 
     def make(w, h):
-        ow, oh = (2 * w, 2 * h) if tr else ((w + 1) // 2, (h + 1) // 2)
-        d = LayerDesc(IFM_CH=ci, IFM_ROW=w, IFM_COL=h, OFM_CH=co, OFM_ROW=ow, OFM_COL=oh, SIMD=simd, PE=pe,
-                      W_TILES=(co // pe) * (25 * ci // simd), transposed=tr)
-        d.validate()
-        return d
+        return LayerDesc.make(ci, co, simd, pe, w, h, tr)
 
     def timed(fn, warmup, reps):
         for _ in range(warmup):

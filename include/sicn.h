@@ -134,7 +134,8 @@ const char *sicn_strerror(int code);
  * out[4] = the tile edge and out[7..9] the grid, the rest 0), mfma family (1 pipelined, 2 wide persistent; 0 only for the
  * other kinds: the plain kernels of family 0 were removed), tile_x, split_n, split_k (always 1), grid x, grid y, grid z, strip
  * chunks (wide persistent: 1 = part of the tiles dealt dynamically), layer-0 tiles per run }.  sicn_debug_xcd_item is the host
- * mirror of the kernels' workgroup -> work item mapping (-1: padding workgroup). */
+ * mirror of the kernels' workgroup -> work item mapping (-1: padding workgroup).  sicn_debug_chip: out[] = { n_cu, n_xcd } the
+ * library plans with on the CURRENT device (the device's own, or SICN_N_CU read at load); SICN_ENODEV without a gfx950 device. */
 /* dst[n][h][w][c] = the top-left h x w corner of every image of src[n][src_h][src_w][c] (device pointers, one launch, enqueue
  * only).  A deconv522 doubles a size that a conv2d rounded up, so a tensor rebuilt by deconvs can be one row / column larger than
  * the one it mirrors (the hyperprior's scale map against the latent); this is the crop. */
@@ -142,6 +143,7 @@ int sicn_crop_nhwc(const uint8_t *src, uint8_t *dst, int n_images, int src_h, in
                    void *hip_stream);
 int sicn_debug_plan(const sicn_layer_desc *desc, int n_images, const sicn_options *opt, int n_cu, int32_t out[12]);
 long long sicn_debug_xcd_item(long long block, long long n_items, int n_xcd);
+int sicn_debug_chip(int32_t out[2]);
 int sicn_validate_desc(const sicn_layer_desc *desc); /* pure host check, no GPU needed         */
 /* Fills *opt with the library defaults: all zero, overridden by the environment as it was when the library was loaded.  The variable
  * of a field is SICN_ + its name in capitals (SICN_TILE_X, SICN_FORCE_GENERIC, ...; persistent_grid has none); a value the field

@@ -69,7 +69,8 @@ const sicn_options &default_options()
 // Geometry of the current device, read once per device ordinal from hipDeviceProp_t (immutable afterwards).  The code objects in
 // this library are gfx950 only: any other architecture is SICN_ENODEV here, with one line on stderr, instead of a failed code
 // object load at the first launch (the reference's error path is exit(-1), bnn-library.h:55).  SICN_N_CU (read at load) overrides
-// the CU count — experiments only: e.g. what the launch planning of a 128-CU partition does on a whole chip.
+// the CU count: what the launch planning of a 128-CU partition does on a whole chip (tests/test_partition_plans.py runs the suite's
+// plan-dependent tests that way; sicn_debug_chip shows the count in force).
 int chip_geom(ChipGeom *out)
 {
     constexpr int MAX_DEV = 64;
@@ -707,6 +708,16 @@ extern "C" int sicn_debug_plan(const sicn_layer_desc *d, int n_images, const sic
     const Family &f = pick_family(*d, o);
     out[2] = (int)f.kind;
     if (f.plan) f.plan(g, n_images, o, chip, out);
+    return SICN_OK;
+}
+// the chip the launchers plan with on the current device (the device's own CU count, or SICN_N_CU): what a test that forces a count asserts first
+extern "C" int sicn_debug_chip(int32_t out[2])
+{
+    if (!out) return SICN_EINVAL;
+    ChipGeom chip;
+    if (int rc = chip_geom(&chip)) return rc;
+    out[0] = chip.n_cu;
+    out[1] = chip.n_xcd;
     return SICN_OK;
 }
 // host mirror of the kernels' XCD-aware work list: the item of workgroup `block`, or -1 (a bijection for every XCD count)

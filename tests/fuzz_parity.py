@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Randomised parity sweep: every kernel family on random image sizes / batch sizes / strip cuts / tile widths against
-the numpy closed form (oracle/sicn_ref.py), bit for bit.  usage: fuzz_parity.py [--cases N] [--seed S]"""
+the numpy closed form (oracle/sicn_ref.py), bit for bit; where that form's float32 sums would not be exact (many channels, input
+bytes above 127) against the C oracle's direct form, which is integer.  usage: fuzz_parity.py [--cases N] [--seed S]"""
 import argparse
+import ctypes
 import os
 import sys
 from pathlib import Path
@@ -11,8 +13,8 @@ import torch
 
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
-from oracle import sicn_ref  # noqa: E402  (checker)
-from simple_image_compression_network_amd import api  # noqa: E402
+from oracle import c_oracle, sicn_ref  # noqa: E402  (checkers)
+from simple_image_compression_network_amd import _lib, api  # noqa: E402
 from simple_image_compression_network_amd.config import LayerDesc  # noqa: E402
 
 ap = argparse.ArgumentParser()
@@ -27,18 +29,43 @@ ap.add_argument("--deal", type=int, default=0, help="additionally: one-layer net
 args = ap.parse_args()
 rng = np.random.default_rng(args.seed)
 
+THREADS = min(16, os.cpu_count() or 1)
+
+
+def layer_ref(d, W, b, words, x):
+    """One image through one layer: the numpy closed form while its float32 GEMM is exact (sicn_ref._exact_gemm_ok), else the C oracle."""
+    if 25 * d.IFM_CH * (int(x.max()) if x.size else 0) * 8 < (1 << 24):
+        return (sicn_ref.deconv522_ref if d.transposed else sicn_ref.conv2d_ref)(x, W, b)
+    return c_oracle.run_layer(d, words, b, x, form="direct", threads=THREADS)
+
+
+def kernel_for(d):
+    return _lib.lib().sicn_kernel_for(ctypes.byref(d.to_c())).decode()
+
+
 FAMILIES = [  # (cin, cout, simd, pe, transposed)
     (3, 128, 3, 8, 0), (128, 128, 8, 16, 0), (128, 192, 8, 24, 0), (192, 128, 12, 16, 1), (128, 128, 8, 16, 1), (128, 3, 8, 3, 1)]
 bad = 0
 for case in range(args.cases):
-    cin, cout, simd, pe, tr = FAMILIES[rng.integers(len(FAMILIES))]
-    big = rng.random() < 0.25
+    any_width = rng.random() < 0.3          # the channel-generic kernels (k_mfma16c.hip): IFM_CH a multiple of 32, OFM_CH of 16, up to 1024
+    if any_width:
+        tr = int(rng.integers(2))
+        cin, cout = 32 * int(rng.integers(1, 33)), 16 * int(rng.integers(1, 65))
+        end = rng.random()
+        if end < 0.15:                      # the RGB ends at other widths
+            (cin, cout) = (cin, 3) if tr else (3, cout)
+        simd, pe = (3 if cin == 3 else 8), (3 if cout == 3 else 16)
+    else:
+        cin, cout, simd, pe, tr = FAMILIES[rng.integers(len(FAMILIES))]
+    big = rng.random() < 0.25 and not (any_width and cin * cout > 256 * 256)      # the CPU side of a wide layer is slow
     w = int(rng.integers(1, 600 if args.big else 200 if big else 70))
     h = int(rng.integers(1, 400 if args.big else 120 if big else 40))
     if cin == 3:
         w, h = w * 2 + int(rng.integers(2)), h * 2 + int(rng.integers(2))
     n = int(rng.integers(1, 4))
     d = LayerDesc.make(cin, cout, simd, pe, w, h, tr)
+    if any_width and kernel_for(d) in ("generic", "invalid", "mfma_conv", "mfma_deconv", "l0_rgb", "l7_rgb"):
+        any_width = False        # a draw that hit one of the specialised shapes: it runs, as one of theirs
     env = {}                     # sicn_options fields, per call
     if rng.random() < 0.5:
         env["strip_chunks"] = int(rng.integers(1, 9))
@@ -53,7 +80,7 @@ for case in range(args.cases):
     W = rng.integers(-8, 8, (cout, 5, 5, cin)).astype(np.int8)
     b = rng.integers(-128, 128, cout).astype(np.int8)
     words = sicn_ref.pack_finn_tiles(W, simd, pe)
-    x = rng.integers(0, 256 if cin == 3 else 128, (n,) + d.in_shape, dtype=np.uint8)
+    x = rng.integers(0, 256 if cin == 3 or (any_width and rng.random() < 0.5) else 128, (n,) + d.in_shape, dtype=np.uint8)
     if cin != 3 and rng.random() < 0.3:
         x.reshape(-1)[::5] |= 0x80
     fpw = api.FixedPointWeights(simd, 4, pe, d.W_TILES, words)
@@ -61,8 +88,7 @@ for case in range(args.cases):
     got = fn(d, fpw, b, torch.from_numpy(x).cuda(), None, n, options=env or None)
     torch.cuda.synchronize()
     got = got.cpu().numpy()
-    ref_fn = sicn_ref.deconv522_ref if tr else sicn_ref.conv2d_ref
-    ok = all(np.array_equal(got[i], ref_fn(x[i], W, b)) for i in range(n))
+    ok = all(np.array_equal(got[i], layer_ref(d, W, b, words, x[i])) for i in range(n))
     if not ok:
         bad += 1
         print(f"MISMATCH case {case}: cin={cin} cout={cout} tr={tr} w={w} h={h} n={n} env={env}", flush=True)
@@ -72,6 +98,7 @@ print(f"{args.cases - bad}/{args.cases} cases bit-exact")
 
 # whole chains: random image sizes, random nibble weights, latent + reconstruction against the closed form
 from simple_image_compression_network_amd.config import eight_layer_descs  # noqa: E402
+CHAIN_WIDTHS = [(128, 192), (128, 256), (192, 128), (64, 96), (128, 64)]
 cbad = 0
 for case in range(args.chains):
     env = {}
@@ -86,35 +113,37 @@ for case in range(args.chains):
         env["tile_x"] = 32
         env["persistent_grid"] = int(rng.choice([8, 16, 64, 0]))
     w, h, n = int(rng.integers(1, 26)) * 16, int(rng.integers(1, 20)) * 16, int(rng.integers(1, 3))
-    descs = eight_layer_descs(w, h)
+    # the reference widths, nets that mix the specialised kernel families with the channel-generic ones, and one all channel-generic
+    n_ch, m_ch = CHAIN_WIDTHS[rng.integers(len(CHAIN_WIDTHS))]
+    descs = eight_layer_descs(w, h, n_ch, m_ch)
     params_np, params = [], []
     for d in descs:
         Wt = rng.integers(-8, 8, (d.OFM_CH, 5, 5, d.IFM_CH)).astype(np.int8)
         bt = rng.integers(-128, 128, d.OFM_CH).astype(np.int8)
-        params_np.append((Wt, bt, d.transposed))
-        params.append((api.FixedPointWeights(d.SIMD, 4, d.PE, d.W_TILES, sicn_ref.pack_finn_tiles(Wt, d.SIMD, d.PE)),
+        params_np.append((Wt, bt, sicn_ref.pack_finn_tiles(Wt, d.SIMD, d.PE)))
+        params.append((api.FixedPointWeights(d.SIMD, 4, d.PE, d.W_TILES, params_np[-1][2]),
                        api.FixedPointWeights(1, 8, 1, d.OFM_CH, bt.view(np.uint8).astype(np.uint64))))
-    net = api.EightLayersNet(w, h, params=params, options=env or None)
+    net = api.EightLayersNet(descs=descs, params=params, options=env or None)
     x = rng.integers(0, 256, (n, h, w, 3), dtype=np.uint8)
     out, lat = net.forward(torch.from_numpy(x).cuda())
     torch.cuda.synchronize()
     out, lat = out.cpu().numpy(), lat.cpu().numpy()
     ok = True
     for i in range(n):
-        ref = sicn_ref.eight_layers_net_ref(x[i], params_np)
-        ok = ok and np.array_equal(out[i], ref[7]) and np.array_equal(lat[i], ref[3])
+        ref = [x[i]]
+        for d, (Wt, bt, words) in zip(descs, params_np):
+            ref.append(layer_ref(d, Wt, bt, words, ref[-1]))
+        ok = ok and np.array_equal(out[i], ref[8]) and np.array_equal(lat[i], ref[4])
     if not ok:
         cbad += 1
-        print(f"CHAIN MISMATCH {case}: {w}x{h} n={n} env={env}", flush=True)
+        print(f"CHAIN MISMATCH {case}: {w}x{h} n={n} widths=({n_ch}, {m_ch}) env={env}", flush=True)
     elif case % 5 == 0:
-        print(f"chain {case}: ok ({w}x{h} n={n})", flush=True)
+        print(f"chain {case}: ok ({w}x{h} n={n} widths=({n_ch}, {m_ch}))", flush=True)
 if args.chains:
     print(f"{args.chains - cbad}/{args.chains} chains bit-exact")
 
 # the activation inside the layer kernels (extension beyond the reference): against oracle/sicn_gdn_oracle.c
 gbad = 0
-if args.gdn:
-    from oracle import c_oracle  # noqa: E402  (checker)
 for case in range(args.gdn):
     inverse = bool(rng.integers(2))
     beta = rng.integers(1, 65536, 128).astype(np.uint32)
@@ -146,11 +175,14 @@ if args.gdn:
     print(f"{args.gdn - gbad}/{args.gdn} fused-activation cases bit-exact")
 # the wide kernels' dynamic tile deal: every tile exactly once, whoever takes it
 dbad = 0
+chip = (ctypes.c_int32 * 2)()
 if args.deal:
-    from oracle import c_oracle  # noqa: E402,F811  (checker)
+    # the chip the library plans with (the device's, or a forced CU count): persistent_grid is rounded down to a multiple of its
+    # XCD count, and the case is sized from the grid that is left so that every workgroup walks >= 16 tiles on every chip
+    _lib.check(_lib.lib().sicn_debug_chip(chip), "sicn_debug_chip")
 for case in range(args.deal):
     tr = int(rng.integers(2))
-    grid = int(rng.choice([8, 16]))
+    grid = max(int(rng.choice([8, 16])) // chip[1] * chip[1], chip[1])
     # position grid (output for the conv, input for the deconv) of tx x ty tiles of 16 x 32, ragged at both edges, with >= 16 tiles per workgroup
     n = int(rng.integers(1, 4))
     need = (16 * grid + n - 1) // n                      # tiles per image
@@ -160,6 +192,10 @@ for case in range(args.deal):
     assert ((mw + 31) // 32) * ((mh + 15) // 16) * n >= 16 * grid
     w, h = (mw, mh) if tr else (2 * mw - int(rng.integers(2)), 2 * mh - int(rng.integers(2)))
     d = LayerDesc.make(128, 128, 8, 16, w, h, tr)
+    plan = (ctypes.c_int32 * 12)()
+    _lib.check(_lib.lib().sicn_debug_plan(ctypes.byref(d.to_c()), n, ctypes.byref(_lib.make_options(wave_tile=128, persistent_grid=grid)),
+                                          chip[0], plan), "sicn_debug_plan")
+    assert (plan[1], plan[3], plan[7], plan[10]) == (chip[1], 2, grid, 1), list(plan)      # wide persistent, `grid` workgroups, dealt dynamically
     Wt = rng.integers(-8, 8, (128, 5, 5, 128)).astype(np.int8)
     bt = rng.integers(-128, 128, 128).astype(np.int8)
     fpw = api.FixedPointWeights(8, 4, 16, d.W_TILES, sicn_ref.pack_finn_tiles(Wt, 8, 16))
@@ -168,7 +204,7 @@ for case in range(args.deal):
     x = rng.integers(0, 128, (n,) + d.in_shape, dtype=np.uint8)
     xin = torch.from_numpy(x).cuda()
     words = sicn_ref.pack_finn_tiles(Wt, 8, 16)
-    ref = np.stack([c_oracle.run_layer(d, words, bt, x[i], form="direct", threads=os.cpu_count() or 1) for i in range(n)])   # the C closed form: these are big
+    ref = np.stack([c_oracle.run_layer(d, words, bt, x[i], form="direct", threads=THREADS) for i in range(n)])   # the C closed form: these are big
     ok = True
     out = None
     for _ in range(3):
@@ -189,7 +225,7 @@ for case in range(args.deal):
         dbad += 1
         print(f"DEAL MISMATCH {case}: tr={tr} {w}x{h} n={n} grid={grid}", flush=True)
     else:
-        print(f"deal {case}: ok ({'deconv' if tr else 'conv'} {w}x{h} n={n}, {grid} workgroups)", flush=True)
+        print(f"deal {case}: ok ({'deconv' if tr else 'conv'} {w}x{h} n={n}, {grid} workgroups, {chip[1]} ticket counters)", flush=True)
 if args.deal:
     print(f"{args.deal - dbad}/{args.deal} dynamic-deal cases bit-exact")
 sys.exit(1 if (bad or cbad or gbad or dbad) else 0)

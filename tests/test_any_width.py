@@ -84,6 +84,39 @@ def test_version_says_the_dispatch_changed():
     assert _lib.lib().sicn_version() >= 5
 
 
+# nets whose layers come from both kinds of family (tests/test_any_width_gpu.py runs them): the dispatch, pinned
+MIXED_DISPATCH = {
+    (128, 256): ["l0_rgb", "mfma_conv", "mfma_conv", "mfma_conv_any", "mfma_deconv_any", "mfma_deconv", "mfma_deconv", "l7_rgb"],
+    (192, 128): ["mfma_conv_any", "mfma_conv_any", "mfma_conv_any", "mfma_conv", "mfma_deconv", "mfma_deconv_any", "mfma_deconv_any",
+                 "mfma_deconv_any"],
+    (128, 64): ["l0_rgb", "mfma_conv", "mfma_conv", "mfma_conv_any", "mfma_deconv_any", "mfma_deconv", "mfma_deconv", "l7_rgb"],
+}
+
+
+def _mixed_links(names):
+    """links that join a specialised family to a channel-generic one (the tensor changes between an internal layout and NHWC)"""
+    return sum(a.endswith("_any") != b.endswith("_any") for a, b in zip(names, names[1:]))
+
+
+@pytest.mark.parametrize("size", [(96, 64), (250, 131), (1920, 1080)])
+def test_dispatch_of_the_nets_that_mix_kernel_families(size):
+    for widths, want in MIXED_DISPATCH.items():
+        assert [_name(d) for d in eight_layer_descs(size[0], size[1], *widths)] == want, widths
+    # every width pair the GPU tests run: how many links join the two kinds of family
+    links = {widths: _mixed_links([_name(d) for d in eight_layer_descs(size[0], size[1], *widths)])
+             for widths in [(64, 96), (192, 320), (256, 256), (128, 256), (192, 128), (128, 64), (128, 192)]}
+    assert links == {(64, 96): 0, (192, 320): 0, (256, 256): 0, (128, 256): 2, (192, 128): 2, (128, 64): 2, (128, 192): 0}
+
+
+def test_wide_channel_counts_are_served_up_to_1024():
+    for cin, cout, tr in ((1024, 1024, 0), (992, 1008, 1), (512, 640, 0), (640, 512, 1), (1024, 16, 0), (32, 1024, 1), (704, 448, 0),
+                          (448, 704, 1), (512, 512, 0)):
+        assert _name(_desc(cin, cout, tr)) == ("mfma_deconv_any" if tr else "mfma_conv_any")
+    assert _name(LayerDesc.make(3, 1024, 3, 16, 37, 21, 0)) == "mfma_conv_any"
+    assert _name(LayerDesc.make(1024, 3, 16, 3, 18, 7, 1)) == "mfma_deconv_any"
+    assert _name(_desc(1056, 1024, 0)) == "generic" and _name(_desc(1024, 1040, 1)) == "generic"
+
+
 def test_eight_layer_descs_at_other_widths():
     assert eight_layer_descs(768, 512) == REFERENCE_DESCS
     assert eight_layer_descs(768, 512, 128, 192) == REFERENCE_DESCS

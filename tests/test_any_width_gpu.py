@@ -2,6 +2,7 @@
 channel widths the reference net does not instantiate, against the oracle and against k_generic — byte equality, the path is
 integer.  Every case first asserts that the layer is NOT served by k_generic, so none of them can pass without the kernels."""
 import ctypes
+import os
 
 import numpy as np
 import pytest
@@ -95,6 +96,36 @@ def test_layer_matches_oracle_random_weights(api, case):
         assert np.array_equal(got[i], ref), f"image {i}: {np.count_nonzero(got[i] != ref)} of {ref.size} bytes differ"
 
 
+# Widths the numpy reference cannot take (its float32 GEMM is exact only while 25 * IFM_CH * max(x) * 8 < 2^24): up to the 1024
+# channels any_supported() serves — the longest K walks, up to 16 blocks of 64 output channels in grid.y,
+# OFM_CH = 16 (mod 64) near the top (1008), an odd multiple of 32 near the top (992), the RGB ends at 1024, one-pixel layers —
+# against the C oracle's direct form, which is integer arithmetic, with input bytes over all of 0 .. 255.
+TIER_WIDE = [
+    (1024, 1024, 16, 16, 19, 9, 0), (992, 1008, 16, 16, 17, 5, 1), (512, 640, 8, 16, 33, 18, 0), (640, 512, 16, 16, 20, 11, 1),
+    (3, 1024, 3, 16, 37, 21, 0), (1024, 3, 16, 3, 18, 7, 1), (1024, 16, 16, 16, 33, 17, 0), (32, 1024, 8, 16, 18, 33, 1),
+    (704, 448, 16, 16, 1, 1, 0), (448, 704, 16, 16, 1, 1, 1),
+]
+# three TIER_A cases again with the 227 cap lifted
+TIER_A_FULL_RANGE = [(256, 256, 8, 16, 131, 33, 0), (352, 48, 16, 16, 19, 7, 1), (192, 320, 8, 16, 9, 40, 1)]
+ORACLE_THREADS = min(16, os.cpu_count() or 1)
+
+
+@pytest.mark.parametrize("case", TIER_WIDE + TIER_A_FULL_RANGE)
+def test_wide_layer_matches_the_exact_oracle_on_full_range_bytes(api, case):
+    rng = np.random.default_rng([37] + list(case))
+    d = _mk_desc(*case)
+    _assert_any(api, d)
+    _, b, words = _rand_params(rng, d)
+    n = 2
+    x = rng.integers(0, 256, (n,) + d.in_shape, dtype=np.uint8)
+    got = _run_layer(api, d, words, b, x)
+    for i in range(n):
+        ref = c_oracle.run_layer(d, words, b, x[i], "direct", threads=ORACLE_THREADS)
+        assert np.count_nonzero(ref) > ref.size // 8            # not a comparison of zeros
+        assert got[i].shape == ref.shape
+        assert np.array_equal(got[i], ref), f"image {i}: {np.count_nonzero(got[i] != ref)} of {ref.size} bytes differ"
+
+
 @pytest.mark.parametrize("case", [(256, 256, 8, 16, 480, 270, 0), (192, 320, 8, 16, 480, 270, 0),
                                   (256, 256, 8, 16, 240, 135, 1), (192, 320, 8, 16, 240, 135, 1)])
 def test_full_chip_grid_agrees_with_the_generic_kernel(api, case):
@@ -110,7 +141,7 @@ def test_full_chip_grid_agrees_with_the_generic_kernel(api, case):
     assert np.array_equal(fast, slow), f"{np.count_nonzero(fast != slow)} of {fast.size} bytes differ"
 
 
-@pytest.mark.parametrize("case", [(64, 64, 8, 16, 50, 20, 0), (192, 192, 12, 24, 21, 13, 1)])
+@pytest.mark.parametrize("case", [(64, 64, 8, 16, 50, 20, 0), (192, 192, 12, 24, 21, 13, 1), (512, 512, 16, 16, 20, 11, 0)])
 def test_pre_activation_mode_with_a_gdn(api, case):
     """relu off: the layer stores the raw byte and the GDN of matching width rewrites it (k_gdn_generic, NHWC)."""
     from simple_image_compression_network_amd.hyperprior import random_gdn_params
@@ -120,10 +151,10 @@ def test_pre_activation_mode_with_a_gdn(api, case):
     _, b, words = _rand_params(rng, d)
     beta, gamma = random_gdn_params(rng, d.OFM_CH)
     inverse = bool(d.transposed)
-    x = _input(rng, d, 2)
+    x = _input(rng, d, 2) if d.IFM_CH <= 352 else rng.integers(0, 256, (2,) + d.in_shape, dtype=np.uint8)
     got = _run_layer(api, d, words, b, x, gdn=api.GDN(beta, gamma, inverse=inverse, shift=12))
     for i in range(2):
-        pre = c_oracle.run_layer_preact(d, words, b, x[i])
+        pre = c_oracle.run_layer_preact(d, words, b, x[i], threads=ORACLE_THREADS)
         assert np.count_nonzero(pre & 0x80) > pre.size // 8   # the lanes the ReLU would have cleared are there
         ref = c_oracle.gdn(pre, beta, gamma, inverse, 12)
         assert np.array_equal(got[i], ref), f"image {i}: {np.count_nonzero(got[i] != ref)} bytes differ"
@@ -178,6 +209,120 @@ def test_whole_net_captured_and_replayed(api):
         ref = c_oracle.run_net(descs, words, biases, x[0], form="direct")
         assert np.array_equal(lat[0].cpu().numpy(), ref[3])
         assert np.array_equal(out[0].cpu().numpy(), ref[7])
+
+
+# ---- nets that mix the specialised kernel families with the channel-generic ones -------------------------------------------------
+# l0_rgb / mfma_conv / mfma_deconv / l7_rgb exchange tensors in the internal GROUP / PHASE layouts, the *_any kernels read and
+# write NHWC only, and link_layout (sicn_abi.hip) picks the layout of every link from the family rows.  In the nets above every
+# layer is an *_any kernel; in these a GROUP-writing kernel feeds an NHWC-only one and back.
+MIXED_WIDTHS = [(128, 256), (192, 128), (128, 64)]
+
+
+def _mixed_links(names):
+    return sum(a.endswith("_any") != b.endswith("_any") for a, b in zip(names, names[1:]))
+
+
+def _assert_prefixes(net, xin, ref_layers, what):
+    """Every prefix 0 .. l of the chain against the reference's layer l (ref_layers[image][l]): the last layer of a call writes NHWC,
+    every link in front of it carries the layout the chain picked, so a wrong link names its layer."""
+    for l in range(len(net.descs)):
+        got, _ = net.run_layers(0, l, xin)
+        torch.cuda.synchronize()
+        got = got.cpu().numpy()
+        for i, ref in enumerate(ref_layers):
+            assert np.array_equal(got[i], ref[l]), \
+                f"{what}: layers 0..{l}, image {i}: {np.count_nonzero(got[i] != ref[l])} of {ref[l].size} bytes differ"
+
+
+@pytest.mark.parametrize("size", [(96, 64), (250, 131)])
+@pytest.mark.parametrize("widths", MIXED_WIDTHS)
+def test_mixed_family_net_matches_oracle_layer_by_layer(api, widths, size):
+    descs = eight_layer_descs(size[0], size[1], *widths)
+    names = [_kernel(api, d) for d in descs]
+    assert "generic" not in names and "invalid" not in names, names
+    assert _mixed_links(names) == 2, names
+    net, words, biases = _random_net(api, descs, [43, *widths, *size])
+    x = np.random.default_rng([47, *widths, *size]).integers(0, 256, (2, size[1], size[0], 3), dtype=np.uint8)
+    xin = _dev(x)
+    ref = [c_oracle.run_net(descs, words, biases, x[i], form="direct", threads=ORACLE_THREADS) for i in range(2)]
+    assert all(np.count_nonzero(r[3]) > r[3].size // 8 and np.count_nonzero(r[7]) > r[7].size // 8 for r in ref)
+    _assert_prefixes(net, xin, ref, f"{widths} {size}")
+    out, latent = net.forward(xin)
+    torch.cuda.synchronize()
+    for i in range(2):
+        assert np.array_equal(latent[i].cpu().numpy(), ref[i][3]), f"image {i}: latent differs from the oracle"
+        assert np.array_equal(out[i].cpu().numpy(), ref[i][7]), f"image {i}: reconstruction differs from the oracle"
+
+
+def test_mixed_family_net_captured_and_replayed(api):
+    w, h, widths = 250, 131, (128, 256)
+    descs = eight_layer_descs(w, h, *widths)
+    assert _mixed_links([_kernel(api, d) for d in descs]) == 2
+    net, words, biases = _random_net(api, descs, 53)
+    rng = np.random.default_rng(59)
+    xin = _dev(rng.integers(0, 256, (2, h, w, 3), dtype=np.uint8))
+    out = torch.empty((2,) + descs[7].out_shape, dtype=torch.uint8, device="cuda")
+    lat = torch.empty((2,) + descs[3].out_shape, dtype=torch.uint8, device="cuda")
+    graph = net.capture(xin, out, lat)
+    for _ in range(2):
+        x = rng.integers(0, 256, (2, h, w, 3), dtype=np.uint8)
+        xin.copy_(_dev(x))
+        out.zero_()
+        lat.zero_()
+        graph.replay()
+        torch.cuda.synchronize()
+        for i in range(2):
+            ref = c_oracle.run_net(descs, words, biases, x[i], form="direct", threads=ORACLE_THREADS)
+            assert np.array_equal(lat[i].cpu().numpy(), ref[3])
+            assert np.array_equal(out[i].cpu().numpy(), ref[7])
+
+
+@pytest.mark.parametrize("igdn_on_layer_7", [False, True], ids=["relu_on_7", "igdn_on_7"])
+def test_mixed_family_net_with_activations(api, igdn_on_layer_7):
+    """A (128, 256) net with a GDN behind layers 0 .. 2 and an IGDN behind 4 .. 6, as hyperprior.py builds them: the activation
+    kernel rewrites the lanes in whatever layout the layer wrote — GROUP behind layers 0 and 1, NHWC behind 2 and 4, PHASE or
+    GROUP behind 5 and 6.  With an IGDN on layer 7 as well, l7_rgb (the only family that cannot store the lane before the ReLU)
+    gives way to the generic kernel, and the link in front of it changes to NHWC."""
+    from simple_image_compression_network_amd.hyperprior import random_gdn_params, random_layer_params
+    w, h, widths = 96, 64, (128, 256)
+    descs = eight_layer_descs(w, h, *widths)
+    names = [_kernel(api, d) for d in descs]
+    assert names == ["l0_rgb", "mfma_conv", "mfma_conv", "mfma_conv_any", "mfma_deconv_any", "mfma_deconv", "mfma_deconv", "l7_rgb"]
+    rng = np.random.default_rng([61, int(igdn_on_layer_7)])
+    params, words, biases, gdns, gdn_np = [], [], [], [], []
+    for l, d in enumerate(descs):
+        (fw, fb), (wt, bt) = random_layer_params(rng, d)
+        params.append((fw, fb))
+        words.append(sicn_ref.pack_finn_tiles(wt, d.SIMD, d.PE))
+        biases.append(bt)
+        if l in (0, 1, 2, 4, 5, 6) or (l == 7 and igdn_on_layer_7):
+            beta, gamma = random_gdn_params(rng, d.OFM_CH)
+            gdn_np.append((beta, gamma, l >= 4))
+            gdns.append(api.GDN(beta, gamma, inverse=l >= 4, shift=12))
+        else:
+            gdn_np.append(None)
+            gdns.append(None)
+    net = api.EightLayersNet(descs=descs, params=params, gdn=gdns)
+    x = rng.integers(0, 256, (2, h, w, 3), dtype=np.uint8)
+    ref = []
+    for i in range(2):
+        a, layers = x[i], []
+        for l, d in enumerate(descs):
+            if gdn_np[l] is None:
+                a = c_oracle.run_layer(d, words[l], biases[l], a, "direct", threads=ORACLE_THREADS)
+            else:
+                beta, gamma, inverse = gdn_np[l]
+                a = c_oracle.gdn(c_oracle.run_layer_preact(d, words[l], biases[l], a, threads=ORACLE_THREADS), beta, gamma, inverse, 12)
+            layers.append(a)
+        ref.append(layers)
+    assert all(np.count_nonzero(r[3]) > r[3].size // 8 and np.count_nonzero(r[7]) > r[7].size // 8 for r in ref)
+    xin = _dev(x)
+    _assert_prefixes(net, xin, ref, "activations" + (" + IGDN on layer 7" if igdn_on_layer_7 else ""))
+    out, latent = net.forward(xin)
+    torch.cuda.synchronize()
+    for i in range(2):
+        assert np.array_equal(latent[i].cpu().numpy(), ref[i][3]), f"image {i}: latent differs from the oracle"
+        assert np.array_equal(out[i].cpu().numpy(), ref[i][7]), f"image {i}: reconstruction differs from the oracle"
 
 
 def test_batch_is_a_true_batch(api):

@@ -124,6 +124,16 @@ CODEC_ABI = {
     "sicn_codec_selftest_div": (ctypes.c_longlong, [_u32, _u32, ctypes.POINTER(ctypes.c_ulonglong)]),
 }
 
+_i32p, _i64p = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int64)
+# include/sicn_ragged.h (ragged batches: images of different sizes through one launch per layer)
+RAGGED_ABI = {
+    "sicn_ragged_layout": (_i, [_descp, _i, _i32p, _i32p, _i, _i, _i, _i64p]),
+    "sicn_ragged_net_create": (_i, [_descp, ctypes.POINTER(_vp), _i, _i32p, _i32p, _i, ctypes.POINTER(_vp)]),
+    "sicn_ragged_net_free": (None, [_vp]),
+    "sicn_ragged_net_workspace_bytes": (_sz, [_vp]),
+    "sicn_ragged_net_forward": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _vp, _sz, _vp]),
+}
+
 _lib = None
 
 
@@ -149,7 +159,7 @@ def lib() -> ctypes.CDLL:
         except ImportError:      # symbol checks etc. work without it
             pass
         L = ctypes.CDLL(str(LIB_PATH))
-        for name, (res, args) in {**ABI, **CODEC_ABI, **CONVLAYER_ABI, **GDN_ABI}.items():
+        for name, (res, args) in {**ABI, **CODEC_ABI, **CONVLAYER_ABI, **GDN_ABI, **RAGGED_ABI}.items():
             fn = getattr(L, name)          # AttributeError if the ABI is incomplete
             fn.restype = res
             fn.argtypes = args

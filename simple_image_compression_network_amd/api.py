@@ -27,7 +27,7 @@ from . import _lib
 from .config import CLayerDesc, LayerDesc, REFERENCE_DESCS, eight_layer_descs
 
 __all__ = ["FixedPointWeights", "DeviceWeights", "conv2d", "deconv522", "conv2d_layer0", "deconv2d_layer4",
-           "eight_layers_net", "EightLayersNet", "load_param_weights", "PARAM", "GDN"]
+           "eight_layers_net", "EightLayersNet", "RaggedNet", "load_param_weights", "PARAM", "GDN"]
 
 _DATA = Path(__file__).resolve().parent / "data" / "param_weights.npz"
 
@@ -341,6 +341,119 @@ class EightLayersNet:
         cnt = (ctypes.c_int * n)()
         _lib.check(_lib.lib().sicn_net_layer_ms(self._h, int(reset), ms, cnt), "sicn_net_layer_ms")
         return list(ms), list(cnt)
+
+
+class RaggedNet:
+    """The 8-layer chain over images of DIFFERENT sizes, one kernel launch per layer for the whole batch (include/sicn_ragged.h).
+    `sizes`: [(width, height)] per image.  A ragged tensor is a flat uint8 CUDA tensor: the images' [H][W][C] arrays back to back;
+    `layer` -1 names the input, l the output of layer l.  Same bytes as `EightLayersNet(w, h).forward` of every image alone."""
+
+    def __init__(self, sizes, params=None, device=None, n_ch: int = 128, m_ch: int = 192,
+                 shared_weights: Optional[Sequence[DeviceWeights]] = None):
+        import torch
+        L = _lib.lib()
+        self.sizes = [(int(w), int(h)) for w, h in sizes]
+        n_img = len(self.sizes)
+        w0, h0 = self.sizes[0] if self.sizes else (1, 1)
+        self.descs: List[LayerDesc] = eight_layer_descs(max(w0, 1), max(h0, 1), n_ch, m_ch)    # the library ignores their spatial fields
+        self.device = torch.device(device if device is not None else "cuda")
+        if shared_weights is not None:
+            self.weights = list(shared_weights)
+        else:
+            params = params if params is not None else load_param_weights()
+            with torch.cuda.device(self.device):
+                self.weights = [DeviceWeights(d, w, b) for d, (w, b) in zip(self.descs, params)]
+        n = len(self.descs)
+        self._cdescs = (CLayerDesc * n)(*[d.to_c() for d in self.descs])
+        self._widths = (ctypes.c_int32 * max(n_img, 1))(*[w for w, _ in self.sizes])
+        self._heights = (ctypes.c_int32 * max(n_img, 1))(*[h for _, h in self.sizes])
+        handles = (ctypes.c_void_p * n)(*[w.handle for w in self.weights])
+        self._h = ctypes.c_void_p()
+        with torch.cuda.device(self.device):
+            _lib.check(L.sicn_ragged_net_create(self._cdescs, handles, n, self._widths, self._heights, n_img, ctypes.byref(self._h)),
+                       "sicn_ragged_net_create")
+        # per boundary (-1 .. n - 1, index layer + 1): the images' shapes and byte offsets, as the library lays them out
+        self._shapes, self._offsets, self._nbytes = [], [], []
+        q = (ctypes.c_int64 * 8)()
+        for layer in range(-1, n):
+            shapes, offs = [], []
+            for i in range(n_img):
+                _lib.check(L.sicn_ragged_layout(self._cdescs, n, self._widths, self._heights, n_img, layer, i, q), "sicn_ragged_layout")
+                shapes.append((int(q[1]), int(q[0]), int(q[2])))
+                offs.append(int(q[3]))
+            self._shapes.append(shapes)
+            self._offsets.append(offs)
+            self._nbytes.append(int(q[4]))
+        self._ws = None
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None) and _lib._lib is not None:
+                _lib._lib.sicn_ragged_net_free(self._h)
+                self._h = None
+        except Exception:       # interpreter shutdown
+            pass
+
+    def shapes(self, layer: int):
+        """[(H, W, C)] of every image at boundary `layer`."""
+        return list(self._shapes[layer + 1])
+
+    def nbytes(self, layer: int) -> int:
+        return self._nbytes[layer + 1]
+
+    def pack(self, images, layer: int = -1):
+        """[H][W][C] uint8 tensors (any device), one per image -> the ragged tensor of boundary `layer` on the net's device."""
+        import torch
+        shapes = self._shapes[layer + 1]
+        if len(images) != len(shapes):
+            raise ValueError(f"need {len(shapes)} images")
+        packed = torch.empty(self.nbytes(layer), dtype=torch.uint8, device=self.device)
+        for t, v, shp in zip(images, self.views(layer, packed), shapes):
+            if tuple(t.shape) != shp or t.dtype != torch.uint8:
+                raise ValueError(f"image shape {tuple(t.shape)} / dtype {t.dtype}: need uint8 {shp}")
+            v.copy_(t)
+        return packed
+
+    def views(self, layer: int, packed):
+        """Per-image [H][W][C] views of a ragged tensor of boundary `layer` (no copy; each one is contiguous)."""
+        _check_tensor(packed, (self.nbytes(layer),), "packed")
+        return [packed[o:o + h * w * c].view(h, w, c) for o, (h, w, c) in zip(self._offsets[layer + 1], self._shapes[layer + 1])]
+
+    def workspace(self):
+        import torch
+        if self._ws is None:
+            nbytes = max(int(_lib.lib().sicn_ragged_net_workspace_bytes(self._h)), 256)
+            self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        return self._ws
+
+    def run_layers(self, first: int, last: int, packed_in, tap_layer: int = -1, out=None, tap=None, stream=None):
+        """Layers [first, last] over the whole batch (sicn_ragged_net_forward); returns (out, tap or None), ragged tensors."""
+        import torch
+        if not 0 <= first <= last < len(self.descs):
+            raise ValueError("layer range")
+        _check_tensor(packed_in, (self.nbytes(first - 1),), "in")
+        if out is None:
+            out = torch.empty(self.nbytes(last), dtype=torch.uint8, device=packed_in.device)
+        _check_tensor(out, (self.nbytes(last),), "out")
+        tap_ptr = ctypes.c_void_p(0)
+        if tap_layer >= 0:
+            if tap is None:
+                tap = torch.empty(self.nbytes(tap_layer), dtype=torch.uint8, device=packed_in.device)
+            _check_tensor(tap, (self.nbytes(tap_layer),), "tap")
+            tap_ptr = ctypes.c_void_p(tap.data_ptr())
+        else:
+            tap = None
+        ws = self.workspace()
+        _lib.check(_lib.lib().sicn_ragged_net_forward(self._h, first, last, ctypes.c_void_p(packed_in.data_ptr()),
+                                                      ctypes.c_void_p(out.data_ptr()), tap_layer, tap_ptr,
+                                                      ctypes.c_void_p(ws.data_ptr()), ws.numel(), _stream_ptr(stream)),
+                   "sicn_ragged_net_forward")
+        return out, tap
+
+    def forward(self, packed_in, out=None, latent=None, stream=None):
+        """All layers; returns (reconstructions, latents) as ragged tensors (the latent is layer 3's output)."""
+        n = len(self.descs)
+        return self.run_layers(0, n - 1, packed_in, tap_layer=3 if n > 3 else -1, out=out, tap=latent, stream=stream)
 
 
 _DEFAULT_NETS = {}

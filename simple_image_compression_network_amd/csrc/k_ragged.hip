@@ -1,0 +1,290 @@
+// Ragged batches (include/sicn_ragged.h): the channel-generic MFMA kernels of k_mfma16c.hip over n images of n different sizes,
+// one launch per layer for the whole batch.  The tile body is any_tile() (k_any_body.hpp), the weight image is pack_any()'s; what
+// is new is how a workgroup finds its image.
+//
+// Grid: x = the layer's work items over all images (a work item = one 16 x 16 tile of one image's M grid; the deconv has 4 per tile,
+// the phase in the low two bits), y = blocks of 64 output channels, z = 1.  Two tables per layer, built on the host at net creation:
+//   tile_image[tile]  : the image a tile belongs to (one entry per tile, not per phase) — ONE load resolves item -> image
+//   rows[image]       : { IW, IH, OW, OH, tiles_x, first_item, in_off, out_off }, the image's sizes in this layer, its first work item
+//                       and its 64-bit byte offsets in the layer's input and output tensors
+// Both loads are wave-uniform (they depend on blockIdx.x only) and stay in scalar registers.
+#include <new>
+#include <vector>
+
+#include "../../include/sicn_ragged.h"
+#include "k_any_body.hpp"
+#include "sicn_weights_io.h"
+
+namespace sicn {
+
+struct RaggedRow {
+    int32_t IW, IH, OW, OH, tiles_x, first_item;
+    int64_t in_off, out_off;
+};
+
+template <bool DECONV, int NT>
+__global__ __launch_bounds__(256) void k_any_ragged(const uint8_t *__restrict__ in, uint8_t *__restrict__ out, const int8_t *__restrict__ wimg,
+                                                    const int8_t *__restrict__ bias, const RaggedRow *__restrict__ rows,
+                                                    const uint32_t *__restrict__ tile_image, int C, int O, uint32_t floor2)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    const int item = (int)blockIdx.x;
+    const int img = __builtin_amdgcn_readfirstlane((int)tile_image[DECONV ? item >> 2 : item]);
+    const RaggedRow *row = rows + img;
+    const int IW = __builtin_amdgcn_readfirstlane(row->IW), IH = __builtin_amdgcn_readfirstlane(row->IH);
+    const int OW = __builtin_amdgcn_readfirstlane(row->OW), OH = __builtin_amdgcn_readfirstlane(row->OH);
+    const int tiles_x = __builtin_amdgcn_readfirstlane(row->tiles_x);
+    int local = item - __builtin_amdgcn_readfirstlane(row->first_item), qy = 0, qx = 0;
+    const uint64_t in_off = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)row->in_off) |
+                            (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(row->in_off >> 32)) << 32;
+    const uint64_t out_off = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)row->out_off) |
+                             (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(row->out_off >> 32)) << 32;
+    if (DECONV) {
+        qy = (local >> 1) & 1;
+        qx = local & 1;
+        local >>= 2;
+    }
+    const int ty = local / tiles_x, tx = local - ty * tiles_x;
+    any_tile<DECONV, NT>(in + in_off, out + out_off, wimg, bias, IW, IH, C, OW, OH, O, ty * ANY_T, tx * ANY_T, qy, qx, (int)blockIdx.y,
+                         floor2, smem);
+}
+
+// ---- the layout of a ragged chain: pure host ----------------------------------------------------------------------------------
+struct RaggedBoundary {                     // one layer boundary: -1 (index 0) = the input, l (index l + 1) = the output of layer l
+    int C;
+    std::vector<int32_t> W, H;
+    std::vector<int64_t> off;               // [n_images + 1]: byte offsets, the last one = the tensor's bytes
+};
+struct RaggedLayerPlan {
+    std::vector<int32_t> tiles_x;
+    std::vector<int64_t> first_item;        // [n_images + 1]: the last one = the layer's work items
+};
+struct RaggedPlan {
+    std::vector<RaggedBoundary> bounds;     // [n_layers + 1]
+    std::vector<RaggedLayerPlan> layers;    // [n_layers]
+};
+
+constexpr int64_t RAGGED_MAX_ITEMS = 0x7fffffffLL;   // a layer has fewer work items than this (grid.x)
+
+static int ragged_plan(const sicn_layer_desc *descs, int n_layers, const int32_t *widths, const int32_t *heights, int n_images,
+                       RaggedPlan *plan)
+{
+    if (!descs || !widths || !heights || n_layers <= 0 || n_layers > 64 || n_images < 1) return SICN_EINVAL;
+    for (int i = 0; i < n_images; i++)
+        if (widths[i] < 1 || heights[i] < 1 || widths[i] > (1 << 20) || heights[i] > (1 << 20)) return SICN_EINVAL;
+    try {
+        plan->bounds.assign((size_t)n_layers + 1, RaggedBoundary{});
+        plan->layers.assign((size_t)n_layers, RaggedLayerPlan{});
+        RaggedBoundary &b0 = plan->bounds[0];
+        b0.C = descs[0].IFM_CH;
+        b0.W.assign(widths, widths + n_images);
+        b0.H.assign(heights, heights + n_images);
+        for (int l = 0; l < n_layers; l++) {
+            // the descriptor's own checks, on the sizes of image 0 (the spatial fields the caller passed are ignored)
+            const RaggedBoundary &bi = plan->bounds[(size_t)l];
+            sicn_layer_desc d = descs[l];
+            const bool tr = d.transposed == 1;
+            d.IFM_ROW = bi.W[0];
+            d.IFM_COL = bi.H[0];
+            d.OFM_ROW = tr ? 2 * bi.W[0] : (bi.W[0] + 1) / 2;
+            d.OFM_COL = tr ? 2 * bi.H[0] : (bi.H[0] + 1) / 2;
+            if (int rc = sicn_validate_desc(&d)) return rc;
+            if (l > 0 && d.IFM_CH != descs[l - 1].OFM_CH) return SICN_EINVAL;
+            if (!any_supported(d.IFM_CH, d.OFM_CH, d.transposed)) return SICN_EINVAL;   // no other kernel to fall back on
+            RaggedBoundary &bo = plan->bounds[(size_t)l + 1];
+            RaggedLayerPlan &lp = plan->layers[(size_t)l];
+            bo.C = d.OFM_CH;
+            bo.W.resize((size_t)n_images);
+            bo.H.resize((size_t)n_images);
+            lp.tiles_x.resize((size_t)n_images);
+            lp.first_item.assign((size_t)n_images + 1, 0);
+            for (int i = 0; i < n_images; i++) {
+                const int64_t iw = bi.W[(size_t)i], ih = bi.H[(size_t)i];
+                const int64_t ow = tr ? 2 * iw : (iw + 1) / 2, oh = tr ? 2 * ih : (ih + 1) / 2;
+                if (iw > (1 << 20) || ih > (1 << 20)) return SICN_EINVAL;
+                if (ih * iw * d.IFM_CH >= (int64_t)OOB || oh * ow * d.OFM_CH >= (int64_t)OOB) return SICN_EINVAL;   // launch_any's limit
+                bo.W[(size_t)i] = (int32_t)ow;
+                bo.H[(size_t)i] = (int32_t)oh;
+                const int64_t mw = tr ? iw : ow, mh = tr ? ih : oh;
+                const int64_t tx = (mw + ANY_T - 1) / ANY_T, ty = (mh + ANY_T - 1) / ANY_T;
+                lp.tiles_x[(size_t)i] = (int32_t)tx;
+                lp.first_item[(size_t)i + 1] = lp.first_item[(size_t)i] + tx * ty * (tr ? 4 : 1);
+                if (lp.first_item[(size_t)i + 1] >= RAGGED_MAX_ITEMS) return SICN_EINVAL;
+            }
+        }
+        for (RaggedBoundary &b : plan->bounds) {
+            b.off.assign((size_t)n_images + 1, 0);
+            for (int i = 0; i < n_images; i++) b.off[(size_t)i + 1] = b.off[(size_t)i] + (int64_t)b.H[(size_t)i] * b.W[(size_t)i] * b.C;
+        }
+    } catch (const std::bad_alloc &) { return SICN_ENOMEM; }
+    return SICN_OK;
+}
+
+template <bool DECONV, int NT>
+static hipError_t launch_ragged_as(const uint8_t *in, uint8_t *out, const int8_t *wimg, const int8_t *bias, const RaggedRow *rows,
+                                   const uint32_t *tile_image, int cin, int cout, unsigned items, hipStream_t stream)
+{
+    const size_t lds = any_lds_bytes(DECONV);
+    if (lds > 64 * 1024) {
+        hipError_t e = hipFuncSetAttribute((const void *)k_any_ragged<DECONV, NT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL((k_any_ragged<DECONV, NT>), dim3(items, (unsigned)((cout + 63) / 64), 1), dim3(256), lds, stream, in, out, wimg, bias,
+                       rows, tile_image, cin, cout, ACT_FLOOR_RELU);
+    return hipGetLastError();
+}
+
+}  // namespace sicn
+
+using namespace sicn;
+
+struct sicn_ragged_net {
+    int n_layers = 0, n_images = 0;
+    RaggedPlan plan;
+    std::vector<sicn_layer_desc> descs;
+    std::vector<const sicn_weights *> weights;
+    std::vector<const int8_t *> wimg;       // per layer: the weights' own pack_any image, or one of `owned`
+    std::vector<int8_t *> owned;            // images packed here for weights whose family is another one (the reference's widths)
+    RaggedRow *d_rows = nullptr;            // [n_layers][n_images]
+    uint32_t *d_tile_image = nullptr;       // the layers' tile -> image maps back to back
+    std::vector<size_t> map_at;             // per layer: its first entry in d_tile_image
+    size_t slot = 0;                        // bytes of one ping-pong buffer
+};
+
+extern "C" int sicn_ragged_layout(const sicn_layer_desc *descs, int n_layers, const int32_t *widths, const int32_t *heights, int n_images,
+                                  int layer, int image, int64_t out[8])
+{
+    if (!out) return SICN_EINVAL;
+    RaggedPlan p;
+    if (int rc = ragged_plan(descs, n_layers, widths, heights, n_images, &p)) return rc;
+    if (layer < -1 || layer >= n_layers || image < 0 || image >= n_images) return SICN_EINVAL;
+    const RaggedBoundary &b = p.bounds[(size_t)(layer + 1)];
+    out[0] = b.W[(size_t)image];
+    out[1] = b.H[(size_t)image];
+    out[2] = b.C;
+    out[3] = b.off[(size_t)image];
+    out[4] = b.off[(size_t)n_images];
+    out[5] = out[6] = out[7] = 0;
+    if (layer >= 0) {
+        const RaggedLayerPlan &lp = p.layers[(size_t)layer];
+        out[5] = lp.first_item[(size_t)image];
+        out[6] = lp.tiles_x[(size_t)image];
+        out[7] = lp.first_item[(size_t)n_images];
+    }
+    return SICN_OK;
+}
+
+extern "C" void sicn_ragged_net_free(sicn_ragged_net *net)
+{
+    if (!net) return;
+    for (int8_t *p : net->owned) (void)hipFree(p);
+    if (net->d_rows) (void)hipFree(net->d_rows);
+    if (net->d_tile_image) (void)hipFree(net->d_tile_image);
+    delete net;
+}
+
+extern "C" int sicn_ragged_net_create(const sicn_layer_desc *descs, sicn_weights *const *weights, int n_layers, const int32_t *widths,
+                                      const int32_t *heights, int n_images, sicn_ragged_net **out)
+{
+    if (!out) return SICN_EINVAL;
+    *out = nullptr;
+    if (!weights) return SICN_EINVAL;
+    sicn_ragged_net *net = new (std::nothrow) sicn_ragged_net();
+    if (!net) return SICN_ENOMEM;
+    int rc = ragged_plan(descs, n_layers, widths, heights, n_images, &net->plan);
+    for (int l = 0; !rc && l < n_layers; l++) {
+        const sicn_weights *w = weights[l];
+        if (!w || w->cin != descs[l].IFM_CH || w->cout != descs[l].OFM_CH || w->transposed != descs[l].transposed) rc = SICN_EINVAL;
+    }
+    if (!rc) rc = chip_geom(nullptr);       // no device, or not a gfx950 one
+    if (!rc) try {
+        net->n_layers = n_layers;
+        net->n_images = n_images;
+        net->descs.assign(descs, descs + n_layers);
+        net->weights.assign(weights, weights + n_layers);
+        // the tables: one row per (layer, image), one tile -> image entry per tile
+        std::vector<RaggedRow> rows((size_t)n_layers * n_images);
+        std::vector<uint32_t> map;
+        size_t mx = 0;
+        for (int l = 0; l < n_layers; l++) {
+            const RaggedBoundary &bi = net->plan.bounds[(size_t)l], &bo = net->plan.bounds[(size_t)l + 1];
+            const RaggedLayerPlan &lp = net->plan.layers[(size_t)l];
+            const int per_tile = descs[l].transposed ? 4 : 1;
+            net->map_at.push_back(map.size());
+            for (int i = 0; i < n_images; i++) {
+                rows[(size_t)l * n_images + i] = RaggedRow{bi.W[(size_t)i], bi.H[(size_t)i], bo.W[(size_t)i], bo.H[(size_t)i], lp.tiles_x[(size_t)i],
+                                                           (int32_t)lp.first_item[(size_t)i], bi.off[(size_t)i], bo.off[(size_t)i]};
+                map.insert(map.end(), (size_t)((lp.first_item[(size_t)i + 1] - lp.first_item[(size_t)i]) / per_tile), (uint32_t)i);
+            }
+            if (l + 1 < n_layers && (size_t)bo.off[(size_t)n_images] > mx) mx = (size_t)bo.off[(size_t)n_images];
+        }
+        net->slot = (mx + 255) / 256 * 256;
+        if (!upload(rows.data(), rows.size() * sizeof(RaggedRow), &net->d_rows) ||
+            !upload(map.data(), map.size() * sizeof(uint32_t), &net->d_tile_image))
+            rc = SICN_ENOMEM;
+        // the weight image: weights of a width the specialised families serve were uploaded without one (sicn_weights_from_finn_tiles
+        // packs the images of the family the shape runs on); pack it here from the plain [cout][25 cin] copy every handle has
+        for (int l = 0; !rc && l < n_layers; l++) {
+            const sicn_weights *w = weights[l];
+            if (w->d_w_any) {
+                net->wimg.push_back(w->d_w_any);
+                continue;
+            }
+            std::vector<int8_t> okc((size_t)w->cout * 25 * w->cin), img(any_bytes(w->cin, w->cout));
+            if (hipMemcpy(okc.data(), w->d_w_okc, okc.size(), hipMemcpyDeviceToHost) != hipSuccess) {
+                rc = SICN_ENODEV;
+                break;
+            }
+            pack_any(okc.data(), w->cin, w->cout, img.data());
+            int8_t *dev = nullptr;
+            const bool ok = upload(img.data(), img.size(), &dev);
+            if (dev) net->owned.push_back(dev);
+            if (!ok) rc = SICN_ENOMEM;
+            net->wimg.push_back(dev);
+        }
+    } catch (const std::bad_alloc &) { rc = SICN_ENOMEM; }
+    if (rc) {
+        sicn_ragged_net_free(net);
+        return rc;
+    }
+    *out = net;
+    return SICN_OK;
+}
+
+extern "C" size_t sicn_ragged_net_workspace_bytes(const sicn_ragged_net *net) { return net ? 2 * net->slot : 0; }
+
+extern "C" int sicn_ragged_net_forward(const sicn_ragged_net *net, int first, int last, const uint8_t *in, uint8_t *out, int tap_layer,
+                                       uint8_t *tap_out, void *workspace, size_t workspace_bytes, void *hip_stream)
+{
+    if (!net || !in || !out) return SICN_EINVAL;
+    if (first < 0 || last >= net->n_layers || first > last) return SICN_EINVAL;
+    if (tap_layer >= 0 && (tap_layer < first || tap_layer > last || !tap_out)) return SICN_EINVAL;
+    if (last > first && (!workspace || workspace_bytes < 2 * net->slot)) return SICN_ENOSPC;
+    if (int rc = chip_geom(nullptr)) return rc;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    uint8_t *pp[2] = {(uint8_t *)workspace, (uint8_t *)workspace + net->slot};
+    const uint8_t *cur = in;
+    for (int l = first; l <= last; l++) {
+        // a tapped layer is written straight into the caller's buffer and the next layer reads it there, as in sicn_net_forward
+        uint8_t *dst = (l == last) ? out : (l == tap_layer ? tap_out : pp[(l - first) & 1]);
+        const sicn_layer_desc &d = net->descs[(size_t)l];
+        const sicn_weights *w = net->weights[(size_t)l];
+        const RaggedRow *rows = net->d_rows + (size_t)l * net->n_images;
+        const uint32_t *map = net->d_tile_image + net->map_at[(size_t)l];
+        const unsigned items = (unsigned)net->plan.layers[(size_t)l].first_item[(size_t)net->n_images];
+        const int8_t *wimg = net->wimg[(size_t)l];
+        hipError_t e;
+        if (d.transposed)
+            e = d.OFM_CH == 3 ? launch_ragged_as<true, 1>(cur, dst, wimg, w->d_bias, rows, map, d.IFM_CH, d.OFM_CH, items, stream)
+                              : launch_ragged_as<true, 4>(cur, dst, wimg, w->d_bias, rows, map, d.IFM_CH, d.OFM_CH, items, stream);
+        else
+            e = launch_ragged_as<false, 4>(cur, dst, wimg, w->d_bias, rows, map, d.IFM_CH, d.OFM_CH, items, stream);
+        if (e != hipSuccess) return SICN_ENODEV;
+        if (l == tap_layer && tap_out != dst) {
+            const size_t bytes = (size_t)net->plan.bounds[(size_t)l + 1].off[(size_t)net->n_images];
+            if (hipMemcpyAsync(tap_out, dst, bytes, hipMemcpyDeviceToDevice, stream) != hipSuccess) return SICN_ENODEV;
+        }
+        cur = dst;
+    }
+    return SICN_OK;
+}

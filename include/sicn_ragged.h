@@ -7,7 +7,9 @@
  * l >= 0 the output of layer l.  The sizes follow the chain rule of sicn_layer_desc: conv ceil(in / 2), deconv 2 * in (the
  * reconstruction of a 100 x 36 image is 112 x 48).  With equal sizes the layout is the [n][H][W][C] batch of sicn.h, byte for byte.
  * Inner tensors have C % 16 == 0, so every image starts 16-byte aligned when the tensor does; tensors handed to the library must be
- * 16-byte aligned.  One image's slice is a plain contiguous NHWC array: whatever takes one (the coder of sicn_codec.h) takes it.
+ * 16-byte aligned.  One image's slice is a plain contiguous NHWC array: whatever takes one (the coder of sicn_codec.h) takes it; the
+ * whole ragged latent (boundary 3) is coded in one go, three launches for the batch, by sicn_ragged_coder_encode_async
+ * (sicn_ragged_codec.h, library 0.7).
  *
  * Kernels.  Every layer runs on the channel-generic MFMA kernels ("mfma_conv_any" / "mfma_deconv_any" of sicn.h) in their ragged
  * form: a workgroup is one 16 x 16 tile of positions x 64 output channels of one image and finds that image through tables the net

@@ -134,6 +134,25 @@ RAGGED_ABI = {
     "sicn_ragged_net_forward": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _vp, _sz, _vp]),
 }
 
+
+
+class RaggedCodecImage(ctypes.Structure):
+    """ctypes image of `sicn_ragged_codec_image` (include/sicn_ragged_codec.h)."""
+    _fields_ = [(n, ctypes.c_uint64) for n in ("latent_offset", "slot_offset", "workspace_offset")] + \
+               [(n, ctypes.c_uint32) for n in ("slot_bytes", "n_symbols", "n_streams", "stream_symbols")]
+
+
+_u32p, _u64p = ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint64)
+# include/sicn_ragged_codec.h (the rANS-W coder over latents of different shapes: 3 + 2 launches for the whole batch)
+RAGGED_CODEC_ABI = {
+    "sicn_ragged_codec_layout": (_i, [_u32p, _u32p, _u32, _u32p, _i, ctypes.POINTER(RaggedCodecImage), _u64p]),
+    "sicn_ragged_coder_create": (_i, [_u32p, _u32p, _u32, _u32p, _u32p, _u32p, _i, ctypes.POINTER(_vp)]),
+    "sicn_ragged_coder_free": (None, [_vp]),
+    "sicn_ragged_coder_workspace_bytes": (_sz, [_vp]),
+    "sicn_ragged_coder_encode_async": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "sicn_ragged_coder_decode_async": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+}
+
 _lib = None
 
 
@@ -159,7 +178,7 @@ def lib() -> ctypes.CDLL:
         except ImportError:      # symbol checks etc. work without it
             pass
         L = ctypes.CDLL(str(LIB_PATH))
-        for name, (res, args) in {**ABI, **CODEC_ABI, **CONVLAYER_ABI, **GDN_ABI, **RAGGED_ABI}.items():
+        for name, (res, args) in {**ABI, **CODEC_ABI, **CONVLAYER_ABI, **GDN_ABI, **RAGGED_ABI, **RAGGED_CODEC_ABI}.items():
             fn = getattr(L, name)          # AttributeError if the ABI is incomplete
             fn.restype = res
             fn.argtypes = args

@@ -385,6 +385,7 @@ class RaggedNet:
             self._offsets.append(offs)
             self._nbytes.append(int(q[4]))
         self._ws = None
+        self._coders = {}           # compress()'s RaggedLatentCoders by stream length, made on first use
 
     def __del__(self):
         try:
@@ -454,6 +455,39 @@ class RaggedNet:
         """All layers; returns (reconstructions, latents) as ragged tensors (the latent is layer 3's output)."""
         n = len(self.descs)
         return self.run_layers(0, n - 1, packed_in, tap_layer=3 if n > 3 else -1, out=out, tap=latent, stream=stream)
+
+    def latent_coder(self, stream_symbols=None):
+        """A codec.RaggedLatentCoder for this net's latents (boundary 3) and image sizes: the whole batch in 3 + 2 launches."""
+        from . import codec
+        return codec.RaggedLatentCoder([(h, w) for h, w, _ in self.shapes(3)], self.shapes(3)[0][2], self.sizes,
+                                       stream_symbols=stream_symbols, device=self.device)
+
+    def compress(self, packed_in, stream_symbols=16384, stream=None):
+        """Ragged input -> one rANS-W container (`bytes`) per image: layers 0-3, then the ragged encoder, enqueued back to back;
+        the only host synchronisation is the read-back of the containers at the end.  stream_symbols: 16384, the format's default,
+        gives the bytes of `EightLayersNet(w, h)` + `codec.encode_latent` on every image alone; "auto" or a shorter power of two
+        (codec.RaggedLatentCoder) shortens the serial chain of small latents at 260 bytes per extra stream."""
+        key = stream_symbols if isinstance(stream_symbols, (int, str)) else tuple(stream_symbols)
+        if key not in self._coders:
+            self._coders[key] = self.latent_coder(stream_symbols)
+        coder = self._coders[key]
+        latent, _ = self.run_layers(0, 3, packed_in, stream=stream)
+        coder.encode(latent, stream=stream)
+        return coder.containers()
+
+    def decompress(self, containers, out=None, stream=None):
+        """Containers of this net's images (e.g. from `compress`) -> the reconstructions as a ragged tensor of boundary 7: the ragged
+        decoder, then layers 4-7, enqueued back to back.  A container that fails to decode raises when the work has finished."""
+        import torch
+        from . import codec
+        coder = codec.RaggedLatentCoder.for_containers(containers, device=self.device)
+        if [(h, w, coder.lat_c) for h, w in coder.shapes] != self.shapes(3):
+            raise ValueError("the containers' latent shapes are not this net's")
+        latent = torch.empty(self.nbytes(3), dtype=torch.uint8, device=self.device)
+        coder.decode(latent, stream=stream)
+        out, _ = self.run_layers(4, len(self.descs) - 1, latent, out=out, stream=stream)
+        coder.check()
+        return out
 
 
 _DEFAULT_NETS = {}

@@ -10,7 +10,7 @@ from . import _lib
 
 RAW8, PACKED7, RANS, RANSW, RANSWC = 0, 1, 2, 3, 4
 __all__ = ["RAW8", "PACKED7", "RANS", "RANSW", "RANSWC", "encode_latent", "decode_latent", "parse_header", "encode_latents",
-           "decode_latents", "LatentCoder", "ContextCoder", "auto_stream_symbols", "WSTREAM_SYMBOLS"]
+           "decode_latents", "LatentCoder", "RaggedLatentCoder", "ContextCoder", "auto_stream_symbols", "WSTREAM_SYMBOLS"]
 
 
 WSTREAM_SYMBOLS = 16384   # SICN_CODEC_WSTREAM_SYMBOLS: the default (and longest) rANS-W stream
@@ -204,6 +204,134 @@ class LatentCoder:
             raise _lib.SicnError(-22, f"rANS-W encode status {e}")
         if any(d):
             raise _lib.SicnError(-22 if any(v & ~128 for v in d) else -74, f"rANS-W decode status {d}")
+
+
+class RaggedLatentCoder:
+    """The ragged rANS-W pair (include/sicn_ragged_codec.h): n latents of n DIFFERENT shapes -> n containers with three launches for
+    the whole batch, and back with two.  `shapes`: [(lat_h, lat_w)] per image, `lat_c` channels in all of them; `image_sizes`:
+    [(width, height)], header fields only.  Latents travel as a ragged tensor — a flat CUDA uint8 tensor, the images' [h][w][c]
+    arrays back to back (api.RaggedNet's boundary 3) — containers in one flat slot buffer, image i's slot at `images[i].slot_offset`.
+    stream_symbols: None or "auto" = `auto_stream_symbols` of EACH image's own latent, one value for all, or one per image.
+    Container i is byte-identical to `LatentCoder(1, h_i, w_i, lat_c, stream_symbols=...)`'s and decodes with `decode_latent`.
+    Same conventions as LatentCoder: enqueue only; verdicts and sizes stay on the device until `check()` / `sizes()` fetch them."""
+
+    def __init__(self, shapes, lat_c: int, image_sizes=None, stream_symbols=None, device=None):
+        import torch
+        L = _lib.lib()
+        self.shapes = [(int(h), int(w)) for h, w in shapes]
+        self.lat_c = int(lat_c)
+        n = len(self.shapes)
+        self.image_sizes = [(int(w), int(h)) for w, h in image_sizes] if image_sizes is not None else [(0, 0)] * n
+        if len(self.image_sizes) != n:
+            raise ValueError("image_sizes: one (width, height) per shape")
+        if stream_symbols in (None, "auto"):
+            self.stream_symbols = [auto_stream_symbols(h * w * self.lat_c) for h, w in self.shapes]
+        elif isinstance(stream_symbols, int):
+            self.stream_symbols = [stream_symbols] * n
+        else:
+            self.stream_symbols = [int(v) for v in stream_symbols]
+            if len(self.stream_symbols) != n:
+                raise ValueError("stream_symbols: one value, or one per shape")
+        u32 = ctypes.c_uint32 * max(n, 1)
+        self._lat_w, self._lat_h = u32(*[w for _, w in self.shapes]), u32(*[h for h, _ in self.shapes])
+        self._wss = u32(*self.stream_symbols)
+        self._img_w, self._img_h = u32(*[w for w, _ in self.image_sizes]), u32(*[h for _, h in self.image_sizes])
+        self.images = (_lib.RaggedCodecImage * max(n, 1))()          # where image i lies: offsets, slot capacity, stream cut
+        totals = (ctypes.c_uint64 * 3)()
+        _lib.check(L.sicn_ragged_codec_layout(self._lat_w, self._lat_h, self.lat_c, self._wss, n, self.images, totals),
+                   "sicn_ragged_codec_layout")
+        self.latent_bytes, self.slot_bytes = int(totals[0]), int(totals[1])
+        self.device = torch.device(device if device is not None else "cuda")
+        self._h = ctypes.c_void_p()
+        with torch.cuda.device(self.device):
+            _lib.check(L.sicn_ragged_coder_create(self._lat_w, self._lat_h, self.lat_c, self._wss, self._img_w, self._img_h, n,
+                                                  ctypes.byref(self._h)), "sicn_ragged_coder_create")
+        self.slot_buffer = torch.empty(self.slot_bytes, dtype=torch.uint8, device=self.device)
+        self.ws = torch.empty(max(int(L.sicn_ragged_coder_workspace_bytes(self._h)), 256), dtype=torch.uint8, device=self.device)
+        self.enc_status = torch.zeros((n, 2), dtype=torch.int32, device=self.device)   # sicn_codec_status {error, bytes}
+        self.dec_status = torch.zeros((n, 2), dtype=torch.int32, device=self.device)
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None) and _lib._lib is not None:
+                _lib._lib.sicn_ragged_coder_free(self._h)
+                self._h = None
+        except Exception:       # interpreter shutdown
+            pass
+
+    @classmethod
+    def for_containers(cls, containers, device=None):
+        """A coder for rANS-W containers that came from somewhere else (a list of `bytes`): shapes, image sizes and stream lengths
+        are READ from the 48-byte headers, the containers are copied into the coder's slots and their lengths into its encoder
+        status, so that `decode(out)` reads exactly them."""
+        import torch
+        infos = [parse_header(bytes(c[:48])) for c in containers]
+        if not infos:
+            raise ValueError("no containers")
+        if any(int(i.mode) != RANSW for i in infos) or len({int(i.lat_c) for i in infos}) != 1:
+            raise ValueError("containers must all be rANS-W and of one channel count")
+        coder = cls([(int(i.lat_h), int(i.lat_w)) for i in infos], int(infos[0].lat_c),
+                    [(int(i.image_width), int(i.image_height)) for i in infos], [int(i.stream_symbols) for i in infos], device=device)
+        host = torch.zeros(coder.slot_bytes, dtype=torch.uint8)
+        for c, im in zip(containers, coder.images):
+            if len(c) > int(im.slot_bytes):
+                raise ValueError(f"a container of {len(c)} bytes is longer than the {int(im.slot_bytes)} its shape may take")
+            host[int(im.slot_offset):int(im.slot_offset) + len(c)] = torch.frombuffer(bytearray(c), dtype=torch.uint8)
+        coder.slot_buffer.copy_(host)
+        coder.enc_status.copy_(torch.tensor([[0, len(c)] for c in containers], dtype=torch.int32))
+        return coder
+
+    def slots(self, slot_buffer=None):
+        """Per-image views of the slot buffer (default: this object's own), each the slot's whole capacity."""
+        buf = self.slot_buffer if slot_buffer is None else slot_buffer
+        return [buf[int(im.slot_offset):int(im.slot_offset) + int(im.slot_bytes)] for im in self.images[:len(self.shapes)]]
+
+    def views(self, latents):
+        """Per-image [h][w][c] views of a ragged latent tensor."""
+        return [latents[int(im.latent_offset):int(im.latent_offset) + h * w * self.lat_c].view(h, w, self.lat_c)
+                for im, (h, w) in zip(self.images, self.shapes)]
+
+    def _flat(self, t, nbytes, what):
+        import torch
+        if not (t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and tuple(t.shape) == (nbytes,)):
+            raise TypeError(f"{what} must be a contiguous CUDA uint8 tensor of {nbytes} bytes")
+
+    def encode(self, latents, stream=None):
+        """latents: ragged CUDA uint8 tensor -> self.slot_buffer (containers), self.enc_status.  Enqueue only."""
+        self._flat(latents, self.latent_bytes, "latents")
+        _lib.check(_lib.lib().sicn_ragged_coder_encode_async(
+            self._h, ctypes.c_void_p(latents.data_ptr()), ctypes.c_void_p(self.slot_buffer.data_ptr()),
+            ctypes.c_void_p(self.enc_status.data_ptr()), ctypes.c_void_p(self.ws.data_ptr()), self.ws.numel(), _stream_ptr(stream)),
+            "sicn_ragged_coder_encode_async")
+        return self.slot_buffer
+
+    def decode(self, out_latents, slots=None, valid=None, stream=None):
+        """slots (a flat slot buffer; default: this object's own) -> out_latents (ragged), self.dec_status.  `valid` as in
+        LatentCoder.decode: default this object's encoder status for its OWN slots, the whole slot for external ones; a device
+        int32 [n][2] status array, or False to trust the whole slot.  Enqueue only."""
+        slots = self.slot_buffer if slots is None else slots
+        self._flat(out_latents, self.latent_bytes, "out_latents")
+        self._flat(slots, self.slot_bytes, "slots")
+        own = slots is self.slot_buffer
+        vptr = None if (valid is False or (valid is None and not own)) else ctypes.c_void_p((self.enc_status if valid is None else valid).data_ptr())
+        _lib.check(_lib.lib().sicn_ragged_coder_decode_async(
+            self._h, ctypes.c_void_p(slots.data_ptr()), vptr, ctypes.c_void_p(out_latents.data_ptr()),
+            ctypes.c_void_p(self.dec_status.data_ptr()), ctypes.c_void_p(self.ws.data_ptr()), self.ws.numel(), _stream_ptr(stream)),
+            "sicn_ragged_coder_decode_async")
+        return out_latents
+
+    sizes = LatentCoder.sizes
+    check = LatentCoder.check
+
+    def containers(self):
+        """The containers of the last encode as `bytes`, one per image (synchronises; raises if the encode reported an error)."""
+        import torch
+        torch.cuda.synchronize(self.device)
+        status = self.enc_status.cpu().tolist()
+        if any(e for e, _ in status):
+            raise _lib.SicnError(-22, f"rANS-W encode status {[e for e, _ in status]}")
+        host = self.slot_buffer.cpu().numpy()
+        return [host[int(im.slot_offset):int(im.slot_offset) + size].tobytes() for im, (_, size) in zip(self.images, status)]
 
 
 class ContextCoder:

@@ -1,0 +1,291 @@
+// Ragged latent coder (include/sicn_ragged_codec.h): the rANS-W stages of k_codec_body.hpp over n latents of n different shapes, three
+// launches per encode and two per decode for the whole batch.  The stage bodies are the uniform coder's (sicn_codec.hip); what is
+// new is how a workgroup finds its image.
+//
+// Grid: flat over work items — k_ragged_stats: the statistics rows of all images (min(max(n_i / 16384, 1), STAT_ROWS) each, the
+// uniform coder's rule); encode, compaction and decode: the streams of all images; the decoder's finish: one workgroup per image.
+// Two kinds of table, built on the host at creation:
+//   row_image[row], stream_image[stream] : the image a work item belongs to — ONE load resolves item -> image
+//   rows[image]                          : RaggedCoderRow, the image's sizes, its first work items and its 64-bit byte offsets in
+//                                          the latent tensor, the slot buffer and the workspace
+// Both loads are wave-uniform (they depend on blockIdx.x only) and stay in scalar registers.  The workspace block of an image is
+// what carve() gives for (ns_i, wstream_cap(wss_i)), the same function the uniform coder calls on the host.
+#include <new>
+#include <vector>
+
+#include "../../include/sicn_ragged_codec.h"
+#include "k_codec_body.hpp"
+#include "sicn_internal.h"
+#include "sicn_weights_io.h"
+
+namespace {
+
+struct RaggedCoderRow {
+    uint64_t lat_off, slot_off, ws_off;
+    uint32_t n, ns, wss, slot_cap;
+    uint32_t lat_w, lat_h, lat_c, img_w, img_h;
+    uint32_t first_stream, first_row, n_rows;
+};
+
+__device__ __forceinline__ uint32_t uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+__device__ __forceinline__ uint64_t uni(uint64_t v) { return (uint64_t)uni((uint32_t)v) | (uint64_t)uni((uint32_t)(v >> 32)) << 32; }
+
+// the image's row, every field wave-uniform
+__device__ __forceinline__ RaggedCoderRow load_row(const RaggedCoderRow *__restrict__ rows, uint32_t img)
+{
+    const RaggedCoderRow *r = rows + img;
+    return RaggedCoderRow{uni(r->lat_off), uni(r->slot_off), uni(r->ws_off), uni(r->n), uni(r->ns), uni(r->wss), uni(r->slot_cap),
+                          uni(r->lat_w), uni(r->lat_h), uni(r->lat_c), uni(r->img_w), uni(r->img_h), uni(r->first_stream),
+                          uni(r->first_row), uni(r->n_rows)};
+}
+
+__device__ __forceinline__ EncImage enc_image(const RaggedCoderRow &r, const uint8_t *latents, uint8_t *containers, uint32_t *status,
+                                              uint8_t *workspace, uint32_t img)
+{
+    Workspace w;
+    carve(w, workspace + r.ws_off, r.ns, wstream_cap(r.wss));
+    EncImage im;
+    im.lat = latents + r.lat_off;
+    im.n = r.n; im.ns = r.ns; im.wss = r.wss;
+    im.scratch = w.scratch;
+    im.lens = w.lens;
+    im.rows = w.rows;
+    im.freq = nullptr;
+    im.n_rows = r.n_rows;
+    im.out = containers + r.slot_off;
+    im.status = status + 2 * (size_t)img;
+    im.lat_w = r.lat_w; im.lat_h = r.lat_h; im.lat_c = r.lat_c; im.img_w = r.img_w; im.img_h = r.img_h;
+    return im;
+}
+
+__device__ __forceinline__ DecImage dec_image(const RaggedCoderRow &r, const uint8_t *containers, const uint32_t *valid, uint8_t *latents,
+                                              uint32_t *status, uint8_t *workspace, uint32_t img)
+{
+    Workspace w;
+    carve(w, workspace + r.ws_off, r.ns, wstream_cap(r.wss));
+    DecImage im;
+    im.c = containers + r.slot_off;
+    im.pbf = im.c + 40;
+    im.freq_bytes = im.c + SICN_CODEC_HEADER_BYTES;
+    im.payload = im.freq_bytes + 256 + 4 * (size_t)r.ns;
+    im.slot_cap = r.slot_cap;
+    im.valid = valid ? valid + 2 * (size_t)img + 1 : nullptr;   // sicn_codec_status.bytes
+    im.lat = latents + r.lat_off;
+    im.n = r.n; im.ns = r.ns; im.wss = r.wss;
+    im.lat_w = r.lat_w; im.lat_h = r.lat_h; im.lat_c = r.lat_c;
+    im.err = w.lens;                                   // [ns] per-stream verdicts
+    im.sums = (unsigned long long *)w.scratch;         // [2 ns]; the scratch slots (>= 2304 B each) are idle in a decode
+    im.offsets = nullptr;
+    im.meta = nullptr;
+    im.status = status + 2 * (size_t)img;
+    return im;
+}
+
+__global__ __launch_bounds__(256) void k_ragged_stats(const uint8_t *__restrict__ latents, uint8_t *__restrict__ workspace,
+                                                      const RaggedCoderRow *__restrict__ rows, const uint32_t *__restrict__ row_image)
+{
+    const uint32_t img = uni(row_image[blockIdx.x]);
+    const RaggedCoderRow r = load_row(rows, img);
+    const uint32_t local = blockIdx.x - r.first_row;
+    Workspace w;
+    carve(w, workspace + r.ws_off, r.ns, wstream_cap(r.wss));
+    stats_body(latents + r.lat_off, r.n, w.hist, w.sums, w.rows + (size_t)local * STAT_ROW_WORDS, local, r.n_rows);
+}
+
+__global__ __launch_bounds__(64) void k_ragged_encode(const uint8_t *__restrict__ latents, uint8_t *__restrict__ containers,
+                                                      uint32_t *__restrict__ status, uint8_t *__restrict__ workspace,
+                                                      const RaggedCoderRow *__restrict__ rows, const uint32_t *__restrict__ stream_image)
+{
+    const uint32_t img = uni(stream_image[blockIdx.x]);
+    const RaggedCoderRow r = load_row(rows, img);
+    ransw_encode_body(enc_image(r, latents, containers, status, workspace, img), blockIdx.x - r.first_stream);
+}
+
+__global__ __launch_bounds__(256) void k_ragged_compact(uint8_t *__restrict__ containers, uint32_t *__restrict__ status,
+                                                        uint8_t *__restrict__ workspace, const RaggedCoderRow *__restrict__ rows,
+                                                        const uint32_t *__restrict__ stream_image)
+{
+    const uint32_t img = uni(stream_image[blockIdx.x]);
+    const RaggedCoderRow r = load_row(rows, img);
+    compact_self_body(enc_image(r, nullptr, containers, status, workspace, img), blockIdx.x - r.first_stream, wstream_cap(r.wss),
+                      (uint32_t)(SICN_CODEC_HEADER_BYTES + 256) + 4 * r.ns);
+}
+
+template <bool BIGTAB>
+__global__ __launch_bounds__(64) void k_ragged_decode(const uint8_t *__restrict__ containers, const uint32_t *__restrict__ valid,
+                                                      uint8_t *__restrict__ latents, uint8_t *__restrict__ workspace,
+                                                      const RaggedCoderRow *__restrict__ rows, const uint32_t *__restrict__ stream_image)
+{
+    const uint32_t img = uni(stream_image[blockIdx.x]);
+    const RaggedCoderRow r = load_row(rows, img);
+    ransw_decode_body<BIGTAB>(dec_image(r, containers, valid, latents, nullptr, workspace, img), blockIdx.x - r.first_stream, 1);
+}
+
+__global__ __launch_bounds__(256) void k_ragged_dec_finish(const uint8_t *__restrict__ containers, const uint32_t *__restrict__ valid,
+                                                           uint32_t *__restrict__ status, uint8_t *__restrict__ workspace,
+                                                           const RaggedCoderRow *__restrict__ rows)
+{
+    const uint32_t img = blockIdx.x;
+    const RaggedCoderRow r = load_row(rows, img);
+    dec_finish_self_body(dec_image(r, containers, valid, nullptr, status, workspace, img));
+}
+
+// ---- the layout: pure host --------------------------------------------------------------------------------------------------
+constexpr uint64_t RAGGED_MAX_STREAMS = 0x7fffffffull;   // fewer streams than this in all (grid.x)
+
+struct Plan {
+    std::vector<RaggedCoderRow> rows;
+    uint64_t lat_bytes = 0, slot_bytes = 0, ws_bytes = 0, streams = 0, stat_rows = 0;
+};
+
+// keep_rows = false: totals only (nothing is allocated)
+int plan_coder(const uint32_t *lat_w, const uint32_t *lat_h, uint32_t lat_c, const uint32_t *wss_or_null, const uint32_t *img_w,
+               const uint32_t *img_h, int n_images, bool keep_rows, sicn_ragged_codec_image *images, Plan *p)
+{
+    if (!lat_w || !lat_h || n_images < 1 || lat_c < 1) return SICN_EINVAL;
+    if (keep_rows) p->rows.reserve((size_t)n_images);
+    for (int i = 0; i < n_images; i++) {
+        const uint32_t wss = wss_or_null ? wss_or_null[i] : WSS;
+        if (lat_w[i] < 1 || lat_h[i] < 1 || !wstream_ok(wss)) return SICN_EINVAL;
+        const uint64_t most = (uint64_t)SELF_SCAN_MAX * wss;            // <= 2^25: the products below cannot wrap
+        const uint64_t positions = (uint64_t)lat_w[i] * lat_h[i];
+        if (positions > most || positions * lat_c > most) return SICN_EINVAL;
+        const uint32_t n = (uint32_t)(positions * lat_c), ns = (n + wss - 1) / wss;
+        Workspace w;
+        RaggedCoderRow r{};
+        r.lat_off = p->lat_bytes;
+        r.slot_off = p->slot_bytes;
+        r.ws_off = p->ws_bytes;
+        r.n = n; r.ns = ns; r.wss = wss;
+        r.slot_cap = (uint32_t)align_up(SICN_CODEC_HEADER_BYTES + 256 + 4 * (size_t)ns + 2 * (size_t)n + 256 * (size_t)ns, 16);   // sicn_codec_max_bytes_sl
+        r.lat_w = lat_w[i]; r.lat_h = lat_h[i]; r.lat_c = lat_c;
+        r.img_w = img_w ? img_w[i] : 0; r.img_h = img_h ? img_h[i] : 0;
+        r.first_stream = (uint32_t)p->streams;
+        r.first_row = (uint32_t)p->stat_rows;
+        r.n_rows = std::min(std::max(n / 16384u, 1u), STAT_ROWS);
+        p->lat_bytes += n;
+        p->slot_bytes += r.slot_cap;
+        p->ws_bytes += align_up(carve(w, nullptr, ns, wstream_cap(wss)), 256);
+        p->streams += ns;
+        p->stat_rows += r.n_rows;
+        if (p->streams >= RAGGED_MAX_STREAMS) return SICN_EINVAL;
+        if (images) images[i] = sicn_ragged_codec_image{r.lat_off, r.slot_off, r.ws_off, r.slot_cap, n, ns, wss};
+        if (keep_rows) p->rows.push_back(r);
+    }
+    return SICN_OK;
+}
+
+}  // namespace
+
+struct sicn_ragged_coder {
+    int n_images = 0;
+    Plan plan;
+    RaggedCoderRow *d_rows = nullptr;       // [n_images]
+    uint32_t *d_stream_image = nullptr;     // [streams]
+    uint32_t *d_row_image = nullptr;        // [stat_rows]
+};
+
+extern "C" int sicn_ragged_codec_layout(const uint32_t *lat_w, const uint32_t *lat_h, uint32_t lat_c, const uint32_t *stream_symbols_or_null,
+                                        int n_images, sicn_ragged_codec_image *images_or_null, uint64_t totals[3])
+{
+    Plan p;
+    if (int rc = plan_coder(lat_w, lat_h, lat_c, stream_symbols_or_null, nullptr, nullptr, n_images, false, images_or_null, &p)) return rc;
+    if (totals) {
+        totals[0] = p.lat_bytes;
+        totals[1] = p.slot_bytes;
+        totals[2] = p.ws_bytes;
+    }
+    return SICN_OK;
+}
+
+extern "C" void sicn_ragged_coder_free(sicn_ragged_coder *coder)
+{
+    if (!coder) return;
+    if (coder->d_rows) (void)hipFree(coder->d_rows);
+    if (coder->d_stream_image) (void)hipFree(coder->d_stream_image);
+    if (coder->d_row_image) (void)hipFree(coder->d_row_image);
+    delete coder;
+}
+
+extern "C" int sicn_ragged_coder_create(const uint32_t *lat_w, const uint32_t *lat_h, uint32_t lat_c, const uint32_t *stream_symbols_or_null,
+                                        const uint32_t *image_w_or_null, const uint32_t *image_h_or_null, int n_images,
+                                        sicn_ragged_coder **out)
+{
+    if (!out) return SICN_EINVAL;
+    *out = nullptr;
+    sicn_ragged_coder *coder = new (std::nothrow) sicn_ragged_coder();
+    if (!coder) return SICN_ENOMEM;
+    int rc = SICN_OK;
+    try {
+        rc = plan_coder(lat_w, lat_h, lat_c, stream_symbols_or_null, image_w_or_null, image_h_or_null, n_images, true, nullptr, &coder->plan);
+        if (!rc) rc = sicn::chip_geom(nullptr);       // no device, or not a gfx950 one
+        if (!rc) {
+            coder->n_images = n_images;
+            std::vector<uint32_t> stream_image, row_image;
+            stream_image.reserve((size_t)coder->plan.streams);
+            row_image.reserve((size_t)coder->plan.stat_rows);
+            for (int i = 0; i < n_images; i++) {
+                const RaggedCoderRow &r = coder->plan.rows[(size_t)i];
+                stream_image.insert(stream_image.end(), (size_t)r.ns, (uint32_t)i);
+                row_image.insert(row_image.end(), (size_t)r.n_rows, (uint32_t)i);
+            }
+            if (!sicn::upload(coder->plan.rows.data(), coder->plan.rows.size() * sizeof(RaggedCoderRow), &coder->d_rows) ||
+                !sicn::upload(stream_image.data(), stream_image.size() * sizeof(uint32_t), &coder->d_stream_image) ||
+                !sicn::upload(row_image.data(), row_image.size() * sizeof(uint32_t), &coder->d_row_image))
+                rc = SICN_ENOMEM;
+        }
+    } catch (const std::bad_alloc &) { rc = SICN_ENOMEM; }
+    if (rc) {
+        sicn_ragged_coder_free(coder);
+        return rc;
+    }
+    *out = coder;
+    return SICN_OK;
+}
+
+extern "C" size_t sicn_ragged_coder_workspace_bytes(const sicn_ragged_coder *coder) { return coder ? (size_t)coder->plan.ws_bytes : 0; }
+
+extern "C" int sicn_ragged_coder_encode_async(const sicn_ragged_coder *coder, const uint8_t *latents, uint8_t *containers,
+                                              sicn_codec_status *status_dev, void *workspace, size_t workspace_bytes, void *hip_stream)
+{
+    if (!coder || !latents || !containers || !status_dev) return SICN_EINVAL;
+    if (!workspace || workspace_bytes < coder->plan.ws_bytes) return SICN_ENOSPC;
+    if (reinterpret_cast<uintptr_t>(workspace) & 15) return SICN_EINVAL;
+    if (int rc = sicn::chip_geom(nullptr)) return rc;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    uint8_t *ws = (uint8_t *)workspace;
+    uint32_t *status = (uint32_t *)status_dev;
+    const unsigned streams = (unsigned)coder->plan.streams, stat_rows = (unsigned)coder->plan.stat_rows;
+    // the uniform coder's three stages (sicn_codec_encode_batch_async_sl, self-scanning form): statistics in rows -> streams, every
+    // wave making the frequency table itself and stream 0's wave of an image writing its header -> compaction with its own scan
+    hipLaunchKernelGGL(k_ragged_stats, dim3(stat_rows), dim3(256), 0, stream, latents, ws, coder->d_rows, coder->d_row_image);
+    hipLaunchKernelGGL(k_ragged_encode, dim3(streams), dim3(64), 0, stream, latents, containers, status, ws, coder->d_rows,
+                       coder->d_stream_image);
+    hipLaunchKernelGGL(k_ragged_compact, dim3(streams), dim3(256), 0, stream, containers, status, ws, coder->d_rows, coder->d_stream_image);
+    return hipGetLastError() == hipSuccess ? SICN_OK : SICN_ENODEV;
+}
+
+extern "C" int sicn_ragged_coder_decode_async(const sicn_ragged_coder *coder, const uint8_t *containers,
+                                              const sicn_codec_status *valid_dev_or_null, uint8_t *latents, sicn_codec_status *status_dev,
+                                              void *workspace, size_t workspace_bytes, void *hip_stream)
+{
+    if (!coder || !containers || !latents || !status_dev) return SICN_EINVAL;
+    if (!workspace || workspace_bytes < coder->plan.ws_bytes) return SICN_ENOSPC;
+    if (reinterpret_cast<uintptr_t>(workspace) & 15) return SICN_EINVAL;
+    sicn::ChipGeom chip;
+    if (int rc = sicn::chip_geom(&chip)) return rc;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    uint8_t *ws = (uint8_t *)workspace;
+    const uint32_t *valid = (const uint32_t *)valid_dev_or_null;
+    const unsigned streams = (unsigned)coder->plan.streams;
+    // the latency form (one 16 KB table) while all waves of the BATCH fit the chip at five per CU, as in the uniform decoder
+    if (coder->plan.streams <= 5ull * (unsigned)chip.n_cu)
+        hipLaunchKernelGGL(k_ragged_decode<true>, dim3(streams), dim3(64), 0, stream, containers, valid, latents, ws, coder->d_rows,
+                           coder->d_stream_image);
+    else
+        hipLaunchKernelGGL(k_ragged_decode<false>, dim3(streams), dim3(64), 0, stream, containers, valid, latents, ws, coder->d_rows,
+                           coder->d_stream_image);
+    hipLaunchKernelGGL(k_ragged_dec_finish, dim3((unsigned)coder->n_images), dim3(256), 0, stream, containers, valid, (uint32_t *)status_dev,
+                       ws, coder->d_rows);
+    return hipGetLastError() == hipSuccess ? SICN_OK : SICN_ENODEV;
+}

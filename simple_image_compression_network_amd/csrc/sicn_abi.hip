@@ -129,7 +129,7 @@ extern "C" void sicn_options_init(sicn_options *opt)
 // 0.5: conv2d<> / deconv522<> at other channel widths run on the channel-generic MFMA kernels ("mfma_conv_any" / "mfma_deconv_any",
 // kinds 5 / 6) instead of k_generic: same bytes, another kernel for valid descriptors
 // 0.6: ragged batches (include/sicn_ragged.h, k_ragged.hip): images of different sizes through one launch per layer
-extern "C" int sicn_version(void) { return 1000 * 0 + 6; }
+extern "C" int sicn_version(void) { return 1000 * 0 + 7; }
 extern "C" int sicn_gdn_spec_version(void) { return 2; }
 
 extern "C" int sicn_has_alt_kernels(void) { return 0; }   // kept for callers that probe it: the alternate kernel build is gone

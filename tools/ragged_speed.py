@@ -14,7 +14,7 @@ over the rounds) of any variant.
 
   python tools/ragged_speed.py                                  the table
   python tools/ragged_speed.py --only ragged --calls 20         just that variant, for a profiler run of its own:
-      rocprofv3 --kernel-trace --stats -d DIR -- python tools/ragged_speed.py --only ragged --calls 20
+      rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/ragged_speed.py --only ragged --calls 20
   python tools/ragged_speed.py --kernel-trace DIR/.../*_kernel_trace.csv     adds the per-layer table of that run
 """
 import argparse

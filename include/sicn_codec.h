@@ -57,7 +57,10 @@ typedef struct sicn_codec_info {
 
 /* Upper bound of the container size / device scratch needed for n_symbols latent bytes.  sicn_codec_workspace_bytes(mode 3) covers
  * a container of ANY admissible stream length (the decoders read the length from the header), sicn_codec_max_bytes(mode 3) the
- * default length of 16384 (the _sl functions size a given length exactly). */
+ * default length of 16384 (the _sl functions size a given length exactly).  In mode 3 sicn_codec_encode / sicn_codec_decode are the
+ * asynchronous pair below with ONE image plus the read-back of its status, so the mode-3 workspace is the largest
+ * sicn_codec_batch_workspace_bytes_sl(n_symbols, 1, length) over the admissible lengths (the per-image block rounded up to 256 bytes
+ * + the status words); sicn_codec_decode accepts that value of the container's own length. */
 size_t sicn_codec_max_bytes(int mode, uint32_t n_symbols);
 size_t sicn_codec_workspace_bytes(int mode, uint32_t n_symbols);
 

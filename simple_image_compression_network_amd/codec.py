@@ -66,8 +66,7 @@ def decode_latent(container, stream=None):
     info = parse_header(bytes(container[:48].cpu().numpy().tobytes()))
     n = int(info.n_symbols)
     latent = torch.empty((int(info.lat_h), int(info.lat_w), int(info.lat_c)), dtype=torch.uint8, device=container.device)
-    need = L.sicn_codec_workspace_bytes_sl(n, int(info.stream_symbols)) if int(info.mode) == RANSW else L.sicn_codec_workspace_bytes(int(info.mode), n)
-    ws = torch.empty(max(need, 64), dtype=torch.uint8, device=container.device)
+    ws = torch.empty(max(L.sicn_codec_workspace_bytes(int(info.mode), n), 64), dtype=torch.uint8, device=container.device)
     container = container.contiguous()
     _lib.check(L.sicn_codec_decode(ctypes.c_void_p(container.data_ptr()), container.numel(),
                                    ctypes.c_void_p(latent.data_ptr()), max(n, 1), ctypes.byref(info),

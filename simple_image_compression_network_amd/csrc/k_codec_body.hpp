@@ -2,7 +2,8 @@
 // pointers advancing by uniform strides) and the ragged ones (k_ragged_codec.hip: a flat grid over the work items of n images of n
 // shapes, each image found through a table).  Every stage is a __device__ function of a small per-image context (EncImage /
 // DecImage: the image's latent, sizes, workspace block, container slot and status entry, already resolved to pointers) and of the
-// stream or statistics-row index INSIDE the image; the kernels differ only in how they fill that context.
+// stream or statistics-row index INSIDE the image.  Both kinds of kernel name an image by one CoderRow and turn it into that context
+// with enc_image() / dec_image(); they differ only in where the row comes from (UniformBatch: computed; ragged: loaded).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -19,7 +20,6 @@ constexpr uint32_t WSS = SICN_CODEC_WSTREAM_SYMBOLS;   // mode 3: 64 lanes x 256
 constexpr uint32_t WCAP = 2 * WSS + 256;               // at most one 16-bit word per symbol + the 64 final states
 constexpr uint32_t RANSW_L = 1u << 16;
 inline uint32_t stream_symbols(int mode) { return mode == SICN_CODEC_RANSW ? WSS : SS; }
-inline uint32_t stream_cap(int mode) { return mode == SICN_CODEC_RANSW ? WCAP : CAP; }
 // mode 3 with the encoder's choice of stream length (header dword 9): a power of two, 1024 .. 16384 symbols.  Shorter streams =
 // more waves = a shorter serial chain for a small latent, + 260 bytes per stream (64 final states, one length entry).
 __host__ __device__ inline bool wstream_ok(uint32_t wss) { return wss >= 1024u && wss <= WSS && (wss & (wss - 1u)) == 0; }
@@ -39,6 +39,7 @@ static_assert((unsigned long long)(MAX_RANS_SYMBOLS / SS) * CAP < (1ull << 32), 
 constexpr uint32_t SELF_SCAN_MAX = 2048;
 constexpr uint32_t STAT_ROWS = 64;                 // at most this many statistics workgroups (rows) per image in row mode
 constexpr uint32_t STAT_ROW_WORDS = 256 + 4;       // hist[256], then s1, s2 as two u64
+inline uint32_t stat_rows(uint32_t n) { const uint32_t r = n / 16384u; return r < 1 ? 1 : r > STAT_ROWS ? STAT_ROWS : r; }   // rows of an n-symbol image
 
 struct Workspace {  // device pointers carved out of the caller's workspace
     uint32_t *hist;                // [256]
@@ -91,11 +92,79 @@ struct DecImage {
     uint8_t *lat;                  // [n] symbols out
     uint32_t n, ns, wss, lat_w, lat_h, lat_c;
     uint32_t *err;                 // self form: [ns] per-stream verdicts; else one word of error flags (atomics)
-    unsigned long long *sums;      // self form: [2 ns] per-stream checksum sums; else [2] (atomics), or nullptr
+    unsigned long long *sums;      // self form: [2 ns] per-stream checksum sums; else [2] (atomics)
     const uint32_t *offsets;       // [ns + 1] from k_scan (not in the self form)
-    const uint32_t *meta;          // k_dec_parse's verdict (not in the self form), or nullptr
+    const uint32_t *meta;          // k_dec_parse's verdict (not in the self form)
     uint32_t *status;              // sicn_codec_status {error, bytes} of this image
 };
+
+// ---- one image as the kernels name it -------------------------------------------------------------------------------------
+// Sizes and 64-bit byte offsets into the latent tensor, the slot buffer and the workspace; the workspace block of an image is what
+// carve() gives for (ns, wstream_cap(wss)).  The ragged coder keeps a table of these (k_ragged_codec.hip).
+struct CoderRow {
+    uint64_t lat_off, slot_off, ws_off;
+    uint32_t n, ns, wss, slot_cap;
+    uint32_t lat_w, lat_h, lat_c, img_w, img_h;
+    uint32_t first_stream, first_row, n_rows;   // ragged: the image's first work items in the flat grids; n_rows: its statistics rows
+};
+// A uniform batch (sicn_codec.hip: blockIdx.y = image, every image of one shape) is image 0's row and three byte strides.  Passed by
+// value, so it lives in kernel-argument SGPRs.  `scan`: the form above SELF_SCAN_MAX streams (no statistics rows; k_scan in front).
+struct UniformBatch {
+    CoderRow row0;
+    uint64_t s_lat, s_slot, s_ws;
+    uint32_t scan;
+};
+__device__ __forceinline__ CoderRow batch_row(const UniformBatch &b)
+{
+    CoderRow r = b.row0;
+    r.lat_off += blockIdx.y * b.s_lat; r.slot_off += blockIdx.y * b.s_slot; r.ws_off += blockIdx.y * b.s_ws;
+    return r;
+}
+
+// scan: the table comes from k_enc_header's `freq`, not from statistics rows
+__device__ __forceinline__ EncImage enc_image(const CoderRow &r, const uint8_t *latents, uint8_t *containers, uint32_t *status,
+                                              uint8_t *workspace, uint32_t img, bool scan = false)
+{
+    Workspace w;
+    carve(w, workspace + r.ws_off, r.ns, wstream_cap(r.wss));
+    EncImage im;
+    im.lat = latents + r.lat_off;
+    im.n = r.n; im.ns = r.ns; im.wss = r.wss;
+    im.scratch = w.scratch;
+    im.lens = w.lens;
+    im.rows = scan ? nullptr : w.rows;
+    im.freq = scan ? w.freq : nullptr;
+    im.n_rows = r.n_rows;
+    im.out = containers + r.slot_off;
+    im.status = status + 2 * (size_t)img;
+    im.lat_w = r.lat_w; im.lat_h = r.lat_h; im.lat_c = r.lat_c; im.img_w = r.img_w; im.img_h = r.img_h;
+    return im;
+}
+
+// valid: a sicn_codec_status array whose .bytes bound the slots, or nullptr.  scan: k_dec_parse and k_scan ran in front, the
+// streams report through the statistics block (meta[3], sums) instead of per-stream words
+__device__ __forceinline__ DecImage dec_image(const CoderRow &r, const uint8_t *containers, const uint32_t *valid, uint8_t *latents,
+                                              uint32_t *status, uint8_t *workspace, uint32_t img, bool scan = false)
+{
+    Workspace w;
+    carve(w, workspace + r.ws_off, r.ns, wstream_cap(r.wss));
+    DecImage im;
+    im.c = containers + r.slot_off;
+    im.pbf = im.c + 40;
+    im.freq_bytes = im.c + SICN_CODEC_HEADER_BYTES;
+    im.payload = im.freq_bytes + 256 + 4 * (size_t)r.ns;
+    im.slot_cap = r.slot_cap;
+    im.valid = valid ? valid + 2 * (size_t)img + 1 : nullptr;   // sicn_codec_status.bytes
+    im.lat = latents + r.lat_off;
+    im.n = r.n; im.ns = r.ns; im.wss = r.wss;
+    im.lat_w = r.lat_w; im.lat_h = r.lat_h; im.lat_c = r.lat_c;
+    im.err = scan ? w.meta + 3 : w.lens;                                   // self: [ns] per-stream verdicts
+    im.sums = scan ? w.sums : (unsigned long long *)w.scratch;            // self: [2 ns]; the scratch slots (>= 2304 B each) are idle in a decode
+    im.offsets = scan ? w.offsets : nullptr;
+    im.meta = scan ? w.meta : nullptr;
+    im.status = status + 2 * (size_t)img;
+    return im;
+}
 
 // ---- stages ---------------------------------------------------------------------------------------------------------------
 // histogram (256 bins) + the two sums adler32 is made of; grid-stride over 16-byte groups (consecutive lanes read
@@ -461,8 +530,8 @@ __device__ __forceinline__ void ransw_decode_body(const DecImage &im, uint32_t s
     const uint32_t lane = threadIdx.x;
     const uint32_t n = im.n, ns = im.ns, wss = im.wss;
     const uint8_t *__restrict__ payload = im.payload, *__restrict__ freq_bytes = im.freq_bytes;
-    // header field "payload bytes" of this image's container (the host has checked it against the bytes it was
-    // given): no stream may reach beyond it, whatever the untrusted length table says
+    // header field "payload bytes" of this image's container: no stream may reach beyond it (nor beyond the slot's valid bytes, which
+    // bound the field below), whatever the untrusted length table says
     const uint8_t *__restrict__ pbf = im.pbf;
     uint32_t *__restrict__ err = im.err;
     if (self) {
@@ -475,7 +544,7 @@ __device__ __forceinline__ void ransw_decode_body(const DecImage &im, uint32_t s
         }
     }
     uint32_t payload_bytes = pbf[0] | ((uint32_t)pbf[1] << 8) | ((uint32_t)pbf[2] << 16) | ((uint32_t)pbf[3] << 24);
-    if (im.meta) payload_bytes = min(payload_bytes, im.meta[1]);   // async path: clamped by the parse stage
+    if (!self) payload_bytes = min(payload_bytes, im.meta[1]);   // scan form: clamped by the parse stage
     if (self) {
         const size_t fixed = SICN_CODEC_HEADER_BYTES + 256 + 4 * (size_t)ns;
         const uint32_t valid = im.valid ? min(*im.valid, im.slot_cap) : im.slot_cap;
@@ -561,7 +630,7 @@ __device__ __forceinline__ void ransw_decode_body(const DecImage &im, uint32_t s
     const unsigned long long below = (1ull << lane) - 1;
     const bool aligned = (reinterpret_cast<uintptr_t>(lat) & 3) == 0;
     bool bad = false;
-    // im.sums (async path): the two sums adler32 is made of, taken from the symbols as they are decoded — the separate
+    // im.sums: the two sums adler32 is made of, taken from the symbols as they are decoded — the separate
     // statistics pass over the decoded latent (17 us on a 1080p latent, a tenth of a small image's whole decode) goes away
     unsigned long long s1 = 0, s2 = 0;
     for (uint32_t q = 0; q < blocks; q++) {
@@ -611,22 +680,20 @@ __device__ __forceinline__ void ransw_decode_body(const DecImage &im, uint32_t s
         if (lane == 0) *err = any_bad ? 1u : 0u;
     } else if (bad || x != RANSW_L || wpos != nwords)
         atomicOr(err, 1u);
-    if (im.sums) {
-        unsigned long long *__restrict__ sums = im.sums;
-        s2 %= ADLER_MOD;
+    unsigned long long *__restrict__ sums = im.sums;
+    s2 %= ADLER_MOD;
 #pragma unroll
-        for (int d = 32; d > 0; d >>= 1) {
-            s1 += __shfl_down(s1, d);
-            s2 += __shfl_down(s2, d);
-        }
-        if (lane == 0) {
-            if (self) {   // per-stream partial sums: a failed stream leaves garbage here, but then the checksum is never looked at
-                sums[2 * st] = s1;
-                sums[2 * st + 1] = s2 % ADLER_MOD;
-            } else {
-                if (s1) atomicAdd(&sums[0], s1);
-                if (s2) atomicAdd(&sums[1], s2 % ADLER_MOD);
-            }
+    for (int d = 32; d > 0; d >>= 1) {
+        s1 += __shfl_down(s1, d);
+        s2 += __shfl_down(s2, d);
+    }
+    if (lane == 0) {
+        if (self) {   // per-stream partial sums: a failed stream leaves garbage here, but then the checksum is never looked at
+            sums[2 * st] = s1;
+            sums[2 * st + 1] = s2 % ADLER_MOD;
+        } else {
+            if (s1) atomicAdd(&sums[0], s1);
+            if (s2) atomicAdd(&sums[1], s2 % ADLER_MOD);
         }
     }
 }

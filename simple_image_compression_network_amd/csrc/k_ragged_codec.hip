@@ -6,8 +6,8 @@
 // uniform coder's rule); encode, compaction and decode: the streams of all images; the decoder's finish: one workgroup per image.
 // Two kinds of table, built on the host at creation:
 //   row_image[row], stream_image[stream] : the image a work item belongs to — ONE load resolves item -> image
-//   rows[image]                          : RaggedCoderRow, the image's sizes, its first work items and its 64-bit byte offsets in
-//                                          the latent tensor, the slot buffer and the workspace
+//   rows[image]                          : CoderRow (k_codec_body.hpp, with enc_image() / dec_image()), the image's sizes, its first
+//                                          work items and its 64-bit byte offsets in the latent tensor, the slot buffer and the workspace
 // Both loads are wave-uniform (they depend on blockIdx.x only) and stay in scalar registers.  The workspace block of an image is
 // what carve() gives for (ns_i, wstream_cap(wss_i)), the same function the uniform coder calls on the host.
 #include <new>
@@ -20,72 +20,23 @@
 
 namespace {
 
-struct RaggedCoderRow {
-    uint64_t lat_off, slot_off, ws_off;
-    uint32_t n, ns, wss, slot_cap;
-    uint32_t lat_w, lat_h, lat_c, img_w, img_h;
-    uint32_t first_stream, first_row, n_rows;
-};
-
 __device__ __forceinline__ uint32_t uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
 __device__ __forceinline__ uint64_t uni(uint64_t v) { return (uint64_t)uni((uint32_t)v) | (uint64_t)uni((uint32_t)(v >> 32)) << 32; }
 
 // the image's row, every field wave-uniform
-__device__ __forceinline__ RaggedCoderRow load_row(const RaggedCoderRow *__restrict__ rows, uint32_t img)
+__device__ __forceinline__ CoderRow load_row(const CoderRow *__restrict__ rows, uint32_t img)
 {
-    const RaggedCoderRow *r = rows + img;
-    return RaggedCoderRow{uni(r->lat_off), uni(r->slot_off), uni(r->ws_off), uni(r->n), uni(r->ns), uni(r->wss), uni(r->slot_cap),
+    const CoderRow *r = rows + img;
+    return CoderRow{uni(r->lat_off), uni(r->slot_off), uni(r->ws_off), uni(r->n), uni(r->ns), uni(r->wss), uni(r->slot_cap),
                           uni(r->lat_w), uni(r->lat_h), uni(r->lat_c), uni(r->img_w), uni(r->img_h), uni(r->first_stream),
                           uni(r->first_row), uni(r->n_rows)};
 }
 
-__device__ __forceinline__ EncImage enc_image(const RaggedCoderRow &r, const uint8_t *latents, uint8_t *containers, uint32_t *status,
-                                              uint8_t *workspace, uint32_t img)
-{
-    Workspace w;
-    carve(w, workspace + r.ws_off, r.ns, wstream_cap(r.wss));
-    EncImage im;
-    im.lat = latents + r.lat_off;
-    im.n = r.n; im.ns = r.ns; im.wss = r.wss;
-    im.scratch = w.scratch;
-    im.lens = w.lens;
-    im.rows = w.rows;
-    im.freq = nullptr;
-    im.n_rows = r.n_rows;
-    im.out = containers + r.slot_off;
-    im.status = status + 2 * (size_t)img;
-    im.lat_w = r.lat_w; im.lat_h = r.lat_h; im.lat_c = r.lat_c; im.img_w = r.img_w; im.img_h = r.img_h;
-    return im;
-}
-
-__device__ __forceinline__ DecImage dec_image(const RaggedCoderRow &r, const uint8_t *containers, const uint32_t *valid, uint8_t *latents,
-                                              uint32_t *status, uint8_t *workspace, uint32_t img)
-{
-    Workspace w;
-    carve(w, workspace + r.ws_off, r.ns, wstream_cap(r.wss));
-    DecImage im;
-    im.c = containers + r.slot_off;
-    im.pbf = im.c + 40;
-    im.freq_bytes = im.c + SICN_CODEC_HEADER_BYTES;
-    im.payload = im.freq_bytes + 256 + 4 * (size_t)r.ns;
-    im.slot_cap = r.slot_cap;
-    im.valid = valid ? valid + 2 * (size_t)img + 1 : nullptr;   // sicn_codec_status.bytes
-    im.lat = latents + r.lat_off;
-    im.n = r.n; im.ns = r.ns; im.wss = r.wss;
-    im.lat_w = r.lat_w; im.lat_h = r.lat_h; im.lat_c = r.lat_c;
-    im.err = w.lens;                                   // [ns] per-stream verdicts
-    im.sums = (unsigned long long *)w.scratch;         // [2 ns]; the scratch slots (>= 2304 B each) are idle in a decode
-    im.offsets = nullptr;
-    im.meta = nullptr;
-    im.status = status + 2 * (size_t)img;
-    return im;
-}
-
 __global__ __launch_bounds__(256) void k_ragged_stats(const uint8_t *__restrict__ latents, uint8_t *__restrict__ workspace,
-                                                      const RaggedCoderRow *__restrict__ rows, const uint32_t *__restrict__ row_image)
+                                                      const CoderRow *__restrict__ rows, const uint32_t *__restrict__ row_image)
 {
     const uint32_t img = uni(row_image[blockIdx.x]);
-    const RaggedCoderRow r = load_row(rows, img);
+    const CoderRow r = load_row(rows, img);
     const uint32_t local = blockIdx.x - r.first_row;
     Workspace w;
     carve(w, workspace + r.ws_off, r.ns, wstream_cap(r.wss));
@@ -94,19 +45,19 @@ __global__ __launch_bounds__(256) void k_ragged_stats(const uint8_t *__restrict_
 
 __global__ __launch_bounds__(64) void k_ragged_encode(const uint8_t *__restrict__ latents, uint8_t *__restrict__ containers,
                                                       uint32_t *__restrict__ status, uint8_t *__restrict__ workspace,
-                                                      const RaggedCoderRow *__restrict__ rows, const uint32_t *__restrict__ stream_image)
+                                                      const CoderRow *__restrict__ rows, const uint32_t *__restrict__ stream_image)
 {
     const uint32_t img = uni(stream_image[blockIdx.x]);
-    const RaggedCoderRow r = load_row(rows, img);
+    const CoderRow r = load_row(rows, img);
     ransw_encode_body(enc_image(r, latents, containers, status, workspace, img), blockIdx.x - r.first_stream);
 }
 
 __global__ __launch_bounds__(256) void k_ragged_compact(uint8_t *__restrict__ containers, uint32_t *__restrict__ status,
-                                                        uint8_t *__restrict__ workspace, const RaggedCoderRow *__restrict__ rows,
+                                                        uint8_t *__restrict__ workspace, const CoderRow *__restrict__ rows,
                                                         const uint32_t *__restrict__ stream_image)
 {
     const uint32_t img = uni(stream_image[blockIdx.x]);
-    const RaggedCoderRow r = load_row(rows, img);
+    const CoderRow r = load_row(rows, img);
     compact_self_body(enc_image(r, nullptr, containers, status, workspace, img), blockIdx.x - r.first_stream, wstream_cap(r.wss),
                       (uint32_t)(SICN_CODEC_HEADER_BYTES + 256) + 4 * r.ns);
 }
@@ -114,19 +65,19 @@ __global__ __launch_bounds__(256) void k_ragged_compact(uint8_t *__restrict__ co
 template <bool BIGTAB>
 __global__ __launch_bounds__(64) void k_ragged_decode(const uint8_t *__restrict__ containers, const uint32_t *__restrict__ valid,
                                                       uint8_t *__restrict__ latents, uint8_t *__restrict__ workspace,
-                                                      const RaggedCoderRow *__restrict__ rows, const uint32_t *__restrict__ stream_image)
+                                                      const CoderRow *__restrict__ rows, const uint32_t *__restrict__ stream_image)
 {
     const uint32_t img = uni(stream_image[blockIdx.x]);
-    const RaggedCoderRow r = load_row(rows, img);
+    const CoderRow r = load_row(rows, img);
     ransw_decode_body<BIGTAB>(dec_image(r, containers, valid, latents, nullptr, workspace, img), blockIdx.x - r.first_stream, 1);
 }
 
 __global__ __launch_bounds__(256) void k_ragged_dec_finish(const uint8_t *__restrict__ containers, const uint32_t *__restrict__ valid,
                                                            uint32_t *__restrict__ status, uint8_t *__restrict__ workspace,
-                                                           const RaggedCoderRow *__restrict__ rows)
+                                                           const CoderRow *__restrict__ rows)
 {
     const uint32_t img = blockIdx.x;
-    const RaggedCoderRow r = load_row(rows, img);
+    const CoderRow r = load_row(rows, img);
     dec_finish_self_body(dec_image(r, containers, valid, nullptr, status, workspace, img));
 }
 
@@ -134,7 +85,7 @@ __global__ __launch_bounds__(256) void k_ragged_dec_finish(const uint8_t *__rest
 constexpr uint64_t RAGGED_MAX_STREAMS = 0x7fffffffull;   // fewer streams than this in all (grid.x)
 
 struct Plan {
-    std::vector<RaggedCoderRow> rows;
+    std::vector<CoderRow> rows;
     uint64_t lat_bytes = 0, slot_bytes = 0, ws_bytes = 0, streams = 0, stat_rows = 0;
 };
 
@@ -152,7 +103,7 @@ int plan_coder(const uint32_t *lat_w, const uint32_t *lat_h, uint32_t lat_c, con
         if (positions > most || positions * lat_c > most) return SICN_EINVAL;
         const uint32_t n = (uint32_t)(positions * lat_c), ns = (n + wss - 1) / wss;
         Workspace w;
-        RaggedCoderRow r{};
+        CoderRow r{};
         r.lat_off = p->lat_bytes;
         r.slot_off = p->slot_bytes;
         r.ws_off = p->ws_bytes;
@@ -162,7 +113,7 @@ int plan_coder(const uint32_t *lat_w, const uint32_t *lat_h, uint32_t lat_c, con
         r.img_w = img_w ? img_w[i] : 0; r.img_h = img_h ? img_h[i] : 0;
         r.first_stream = (uint32_t)p->streams;
         r.first_row = (uint32_t)p->stat_rows;
-        r.n_rows = std::min(std::max(n / 16384u, 1u), STAT_ROWS);
+        r.n_rows = stat_rows(n);
         p->lat_bytes += n;
         p->slot_bytes += r.slot_cap;
         p->ws_bytes += align_up(carve(w, nullptr, ns, wstream_cap(wss)), 256);
@@ -180,7 +131,7 @@ int plan_coder(const uint32_t *lat_w, const uint32_t *lat_h, uint32_t lat_c, con
 struct sicn_ragged_coder {
     int n_images = 0;
     Plan plan;
-    RaggedCoderRow *d_rows = nullptr;       // [n_images]
+    CoderRow *d_rows = nullptr;       // [n_images]
     uint32_t *d_stream_image = nullptr;     // [streams]
     uint32_t *d_row_image = nullptr;        // [stat_rows]
 };
@@ -225,11 +176,11 @@ extern "C" int sicn_ragged_coder_create(const uint32_t *lat_w, const uint32_t *l
             stream_image.reserve((size_t)coder->plan.streams);
             row_image.reserve((size_t)coder->plan.stat_rows);
             for (int i = 0; i < n_images; i++) {
-                const RaggedCoderRow &r = coder->plan.rows[(size_t)i];
+                const CoderRow &r = coder->plan.rows[(size_t)i];
                 stream_image.insert(stream_image.end(), (size_t)r.ns, (uint32_t)i);
                 row_image.insert(row_image.end(), (size_t)r.n_rows, (uint32_t)i);
             }
-            if (!sicn::upload(coder->plan.rows.data(), coder->plan.rows.size() * sizeof(RaggedCoderRow), &coder->d_rows) ||
+            if (!sicn::upload(coder->plan.rows.data(), coder->plan.rows.size() * sizeof(CoderRow), &coder->d_rows) ||
                 !sicn::upload(stream_image.data(), stream_image.size() * sizeof(uint32_t), &coder->d_stream_image) ||
                 !sicn::upload(row_image.data(), row_image.size() * sizeof(uint32_t), &coder->d_row_image))
                 rc = SICN_ENOMEM;

@@ -129,6 +129,9 @@ extern "C" void sicn_options_init(sicn_options *opt)
 // 0.5: conv2d<> / deconv522<> at other channel widths run on the channel-generic MFMA kernels ("mfma_conv_any" / "mfma_deconv_any",
 // kinds 5 / 6) instead of k_generic: same bytes, another kernel for valid descriptors
 // 0.6: ragged batches (include/sicn_ragged.h, k_ragged.hip): images of different sizes through one launch per layer
+// 0.7: ragged latent coder (include/sicn_ragged_codec.h, k_ragged_codec.hip).  Still 0.7 (no symbol, struct or byte changed): the
+// synchronous rANS-W calls are the asynchronous pair with one image, so sicn_codec_workspace_bytes(SICN_CODEC_RANSW, n) also holds
+// that pair's status words (it grew by less than 1 KiB) and sicn_codec_decode needs sicn_codec_batch_workspace_bytes_sl(n, 1, length)
 extern "C" int sicn_version(void) { return 1000 * 0 + 7; }
 extern "C" int sicn_gdn_spec_version(void) { return 2; }
 

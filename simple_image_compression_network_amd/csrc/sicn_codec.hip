@@ -2,17 +2,23 @@
 // oracle/sicn_codec_oracle.c).  New functionality: nothing in the reference corresponds to it
 // (SURVEY.md §8f rows 1-2), parity status "unpinned".
 //
-// Two rANS forms.  Mode 3 ("rANS-W") is the wavefront form: a stream of 16384 symbols is coded by ONE
-// WAVE, its 64 lanes holding 64 interleaved rANS states that share one stream of 16-bit words; in every
-// step each lane codes one symbol and the lanes that renormalise find their word by a wavefront-level
-// scan of one ballot (rank = popcount of the emitting lanes below).  Symbols are read and written 64
-// consecutive bytes at a time.  Mode 2 is the first, lane-serial form, kept for compatibility:
-// the latent is cut into independent streams of 1024 symbols; ONE LANE encodes or
-// decodes one stream (rANS is inherently serial inside a stream), so a 4K latent (6.2 M symbols)
-// is 6 075 lanes.  Stream sizes are data dependent: every lane writes its stream backwards into a
-// fixed-capacity scratch slot, a wavefront-level prefix scan (k_scan: __shfl_up inside a wave,
-// LDS across the 16 waves of one workgroup, running carry across chunks) turns the sizes into
-// offsets, and a copy kernel compacts the streams into the container.
+// Two rANS forms.  Mode 3 ("rANS-W") is the wavefront form: a stream of up to 16384 symbols is coded by ONE WAVE, its 64 lanes holding
+// 64 interleaved rANS states that share one stream of 16-bit words (stages in k_codec_body.hpp).  Mode 2 is the first, lane-serial
+// form, kept for compatibility: streams of 1024 symbols, ONE LANE per stream, every lane writing its stream backwards into a
+// fixed-capacity scratch slot; k_scan (wavefront-level prefix scan) turns the sizes into offsets and k_compact copies the streams.
+//
+// Which entry point runs which launches (mode 3 has ONE host path per direction, the asynchronous pair):
+//   sicn_codec_encode_batch_async[_sl]   up to SELF_SCAN_MAX streams per image, "self" form: k_stats (rows) -> k_ransw_encode (table,
+//                                        header and status made by the waves) -> k_compact_self;  above, or with no stream, "scan"
+//                                        form: k_clear_stats -> k_stats (atomics) -> k_enc_header -> k_ransw_encode -> k_scan -> k_compact
+//   sicn_codec_decode_batch_async[_sl]   self form: k_ransw_decode<BIGTAB> -> k_dec_finish_self;  scan form: k_dec_parse -> k_scan ->
+//                                        k_ransw_decode<false> -> k_dec_finish
+//   sicn_codec_encode_batch, sicn_codec_encode(mode 3)   ransw_encode_sync: the asynchronous encoder + one read-back of the status
+//   sicn_codec_decode_batch, sicn_codec_decode(mode 3)   one header read-back (shape, stream length), then ransw_decode_sync: the
+//                                        asynchronous decoder + one read-back of the status
+//   sicn_codec_encode / _decode, modes 0 - 2   on the host's schedule: k_stats (atomics), host normalize(), k_pack7 / k_unpack7 or
+//                                        k_rans_encode -> k_scan -> k_compact / k_scan -> k_rans_decode, k_stats again for the checksum
+//   mode 4 (sicn_codec_ctx.inc)          its own kernels + k_clear_stats, k_stats (atomics), k_scan, k_compact, k_dec_finish
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -32,17 +38,12 @@ namespace {
 // serialise in L2.  Measured r02 (tools/coder_speed.py, encode of a 1080p / of 8 4K latents): 32 workgroups 78 / 146 us,
 // 128: 80 / 126, 512: 103 / 215.  (Per-workgroup partial histograms summed by the last workgroup to finish were slower
 // still: 91 / 203 us — one workgroup walking 128 rows is a serial chain of its own.)
-static inline unsigned stats_blocks(uint32_t n, uint32_t n_images)
-{
-    (void)n_images;
-    return std::min((n / 16 + 255u) / 256u + 1u, 128u);
-}
+static inline unsigned stats_blocks(uint32_t n) { return std::min((n / 16 + 255u) / 256u + 1u, 128u); }
 
 // ---- kernels ----------------------------------------------------------------------------------
-// histogram (256 bins) + the two sums adler32 is made of; grid-stride over 16-byte groups (consecutive lanes read
-// consecutive groups); zeros — half of a ReLU latent — are counted in a register instead of hammering one LDS bin
-// Batches: blockIdx.y = image; pointers into the latent tensor / the per-image workspace / the container
-// slots advance by the given byte strides (0 for single-image calls).
+// Batches: blockIdx.y = image.  The rANS-W kernels name their image by a UniformBatch (k_codec_body.hpp); k_scan, k_compact,
+// k_clear_stats, the header / parse / finish kernels of the scan form, mode 2 and the context coder take pointers into the latent
+// tensor / the per-image workspace / the container slots that advance by the given byte strides.
 template <typename T>
 __device__ __forceinline__ T *img_ptr(T *p, size_t stride)
 {
@@ -54,69 +55,45 @@ __device__ __forceinline__ const T *img_ptr(const T *p, size_t stride)
     return (const T *)((const uint8_t *)p + (size_t)blockIdx.y * stride);
 }
 
-__global__ __launch_bounds__(256) void k_stats(const uint8_t *__restrict__ lat_, uint32_t n, uint32_t *__restrict__ hist_,
-                                               unsigned long long *__restrict__ sums_, size_t s_lat, size_t s_ws,
-                                               uint32_t *__restrict__ rows_ = nullptr)
+// A uniform batch on the host: image 0's row (its offsets are 0: the kernels get the base pointers) and the strides.
+// scan = the form without statistics rows (n_rows = 0).  stats_batch: all k_stats needs outside the rANS-W coder (atomic mode on
+// the statistics block at the head of a workspace block).
+UniformBatch uniform_batch(uint32_t lat_w, uint32_t lat_h, uint32_t lat_c, uint32_t img_w, uint32_t img_h, uint32_t wss,
+                           size_t s_lat, size_t s_slot, size_t s_ws, bool scan)
 {
-    stats_body(img_ptr(lat_, s_lat), n, img_ptr(hist_, s_ws), img_ptr(sums_, s_ws),
-               rows_ ? img_ptr(rows_, s_ws) + (size_t)blockIdx.x * STAT_ROW_WORDS : nullptr, blockIdx.x, gridDim.x);
+    UniformBatch b{};
+    CoderRow &r = b.row0;
+    r.n = lat_w * lat_h * lat_c; r.ns = (r.n + wss - 1) / wss; r.wss = wss;
+    r.slot_cap = (uint32_t)std::min(s_slot, (size_t)0xFFFFFFFFu);
+    r.lat_w = lat_w; r.lat_h = lat_h; r.lat_c = lat_c; r.img_w = img_w; r.img_h = img_h;
+    r.n_rows = scan ? 0u : stat_rows(r.n);
+    b.s_lat = s_lat; b.s_slot = s_slot; b.s_ws = s_ws;
+    b.scan = scan;
+    return b;
+}
+UniformBatch stats_batch(uint32_t n, size_t s_lat, size_t s_ws) { return uniform_batch(n, 1, 1, 0, 0, WSS, s_lat, 0, s_ws, true); }
+
+// histogram (256 bins) + the two sums adler32 is made of (stats_body); scan form: atomics on a cleared block, else one row per workgroup
+__global__ __launch_bounds__(256) void k_stats(const uint8_t *__restrict__ latents, uint8_t *__restrict__ workspace, UniformBatch b)
+{
+    const CoderRow r = batch_row(b);
+    Workspace w;
+    carve(w, workspace + r.ws_off, r.ns, wstream_cap(r.wss));
+    stats_body(latents + r.lat_off, r.n, w.hist, w.sums, b.scan ? nullptr : w.rows + (size_t)blockIdx.x * STAT_ROW_WORDS, blockIdx.x, gridDim.x);
 }
 
 // ---- rANS-W: one wave (= one 64-lane workgroup) per stream; the stages are in k_codec_body.hpp ---------------------------
-// what the asynchronous encoder's streams need to make the frequency table THEMSELVES from the statistics rows (row mode)
-struct EncSelfHeader {
-    const uint32_t *rows;     // [n_rows][STAT_ROW_WORDS] per image (stride s_ws), or nullptr: the table comes from freq_g
-    uint32_t n_rows;
-    uint8_t *out;             // containers (stride s_slot)
-    size_t s_slot;
-    uint32_t *status;         // sicn_codec_status[n_images]
-    uint32_t lat_w, lat_h, lat_c, img_w, img_h;
-};
-
-__global__ __launch_bounds__(64) void k_ransw_encode(const uint8_t *__restrict__ lat_, uint32_t n, uint32_t ns,
-                                                     const uint16_t *__restrict__ freq_g_, uint8_t *__restrict__ scratch_,
-                                                     uint32_t *__restrict__ lens_, size_t s_lat, size_t s_ws, uint32_t wss,
-                                                     EncSelfHeader sh = EncSelfHeader{})
+__global__ __launch_bounds__(64) void k_ransw_encode(const uint8_t *__restrict__ latents, uint8_t *__restrict__ containers,
+                                                     uint32_t *__restrict__ status, uint8_t *__restrict__ workspace, UniformBatch b)
 {
-    EncImage im;
-    im.lat = img_ptr(lat_, s_lat);
-    im.n = n; im.ns = ns; im.wss = wss;
-    im.scratch = img_ptr(scratch_, s_ws);
-    im.lens = img_ptr(lens_, s_ws);
-    im.rows = sh.rows ? img_ptr(sh.rows, s_ws) : nullptr;
-    im.freq = img_ptr(freq_g_, s_ws);
-    im.n_rows = sh.n_rows;
-    im.out = img_ptr(sh.out, sh.s_slot);
-    im.status = sh.status + 2 * blockIdx.y;
-    im.lat_w = sh.lat_w; im.lat_h = sh.lat_h; im.lat_c = sh.lat_c; im.img_w = sh.img_w; im.img_h = sh.img_h;
-    ransw_encode_body(im, blockIdx.x);
+    ransw_encode_body(enc_image(batch_row(b), latents, containers, status, workspace, blockIdx.y, b.scan), blockIdx.x);
 }
 
 template <bool BIGTAB>
-__global__ __launch_bounds__(64) void k_ransw_decode(const uint8_t *__restrict__ payload_, const uint8_t *__restrict__ freq_bytes_,
-                                                     const uint32_t *__restrict__ offsets_, uint32_t n, uint32_t ns,
-                                                     uint8_t *__restrict__ lat_, uint32_t *__restrict__ err_, size_t s_slot,
-                                                     size_t s_ws, size_t s_lat, const uint8_t *__restrict__ payload_bytes_field_,
-                                                     const uint32_t *__restrict__ meta_, unsigned long long *__restrict__ sums_, uint32_t wss,
-                                                     const uint32_t *__restrict__ self_valid_ = nullptr, uint32_t self_valid_stride = 0,
-                                                     int self = 0)
+__global__ __launch_bounds__(64) void k_ransw_decode(const uint8_t *__restrict__ containers, const uint32_t *__restrict__ valid,
+                                                     uint8_t *__restrict__ latents, uint8_t *__restrict__ workspace, UniformBatch b)
 {
-    DecImage im;
-    im.c = nullptr;
-    im.pbf = img_ptr(payload_bytes_field_, s_slot);
-    im.freq_bytes = img_ptr(freq_bytes_, s_slot);
-    im.payload = img_ptr(payload_, s_slot);
-    im.slot_cap = (uint32_t)min(s_slot, (size_t)0xFFFFFFFFu);
-    im.valid = self_valid_ ? self_valid_ + (size_t)blockIdx.y * self_valid_stride : nullptr;
-    im.lat = img_ptr(lat_, s_lat);
-    im.n = n; im.ns = ns; im.wss = wss;
-    im.lat_w = im.lat_h = im.lat_c = 0;
-    im.err = img_ptr(err_, s_ws);
-    im.sums = sums_ ? img_ptr(sums_, s_ws) : nullptr;
-    im.offsets = img_ptr(offsets_, s_ws);
-    im.meta = meta_ ? img_ptr(meta_, s_ws) : nullptr;
-    im.status = nullptr;
-    ransw_decode_body<BIGTAB>(im, blockIdx.x, self);
+    ransw_decode_body<BIGTAB>(dec_image(batch_row(b), containers, valid, latents, nullptr, workspace, blockIdx.y, b.scan), blockIdx.x, !b.scan);
 }
 
 
@@ -238,17 +215,12 @@ __global__ __launch_bounds__(256) void k_compact(const uint8_t *__restrict__ scr
 }
 
 // The same without a scan kernel in front (asynchronous encoder, up to SELF_SCAN_MAX streams per image): compact_self_body
-__global__ __launch_bounds__(256) void k_compact_self(const uint8_t *__restrict__ scratch_, const uint32_t *__restrict__ lens_,
-                                                      uint8_t *__restrict__ out_, uint32_t cap, uint32_t ns, size_t s_ws, size_t s_slot,
-                                                      uint32_t *__restrict__ status_bytes_, uint32_t fixed_bytes)
+__global__ __launch_bounds__(256) void k_compact_self(uint8_t *__restrict__ containers, uint32_t *__restrict__ status,
+                                                      uint8_t *__restrict__ workspace, UniformBatch b)
 {
-    EncImage im{};
-    im.scratch = const_cast<uint8_t *>(img_ptr(scratch_, s_ws));
-    im.lens = const_cast<uint32_t *>(img_ptr(lens_, s_ws));
-    im.ns = ns;
-    im.out = img_ptr(out_, s_slot);
-    im.status = status_bytes_ + 2 * blockIdx.y;
-    compact_self_body(im, blockIdx.x, cap, fixed_bytes);
+    const CoderRow r = batch_row(b);
+    compact_self_body(enc_image(r, nullptr, containers, status, workspace, blockIdx.y), blockIdx.x, wstream_cap(r.wss),
+                      (uint32_t)(SICN_CODEC_HEADER_BYTES + 256) + 4 * r.ns);
 }
 
 
@@ -334,8 +306,7 @@ __device__ __forceinline__ void clear_stats_in_parse(uint32_t *meta, int lane)
 __global__ __launch_bounds__(256) void k_enc_header(const uint32_t *__restrict__ hist_, const unsigned long long *__restrict__ sums_,
                                                    uint16_t *__restrict__ freq_, uint8_t *__restrict__ out_, uint32_t *__restrict__ status_,
                                                    uint32_t n, uint32_t ns, uint32_t lat_w, uint32_t lat_h, uint32_t lat_c,
-                                                   uint32_t img_w, uint32_t img_h, size_t s_ws, size_t s_slot, uint32_t wss,
-                                                   const uint32_t *__restrict__ rows_ = nullptr, uint32_t n_rows = 0)
+                                                   uint32_t img_w, uint32_t img_h, size_t s_ws, size_t s_slot, uint32_t wss)
 {
     const uint32_t *hist = img_ptr(hist_, s_ws);
     const unsigned long long *sums = img_ptr(sums_, s_ws);
@@ -344,50 +315,8 @@ __global__ __launch_bounds__(256) void k_enc_header(const uint32_t *__restrict__
     uint32_t *status = status_ + 2 * blockIdx.y;
     const int lane = threadIdx.x;
     uint32_t err = 0;
-    uint32_t hh[2], hi = 0;
-    unsigned long long s1 = 0, s2 = 0;
-    if (rows_) {   // row mode (launched with 4 waves): the statistics workgroups' rows are summed here, wave w = rows w, w + 4, ..
-        const uint32_t *rows = img_ptr(rows_, s_ws);
-        __shared__ uint32_t part[4][260];
-        const int l = threadIdx.x & 63, wv = threadIdx.x >> 6;
-        uint32_t a0 = 0, a1 = 0, a2 = 0, a3 = 0;
-        unsigned long long p1 = 0, p2 = 0;
-#pragma unroll 4
-        for (uint32_t r = wv; r < n_rows; r += 4) {
-            const uint32_t *row = rows + (size_t)r * STAT_ROW_WORDS;
-            a0 += row[l];
-            a1 += row[64 + l];
-            a2 += row[128 + l];
-            a3 += row[192 + l];
-            if (l == 0) {
-                const unsigned long long *q = (const unsigned long long *)(row + 256);
-                p1 += q[0];
-                p2 += q[1];
-            }
-        }
-        part[wv][l] = a0; part[wv][64 + l] = a1; part[wv][128 + l] = a2; part[wv][192 + l] = a3;
-        if (l == 0) {
-            part[wv][256] = (uint32_t)p1; part[wv][257] = (uint32_t)(p1 >> 32);
-            part[wv][258] = (uint32_t)p2; part[wv][259] = (uint32_t)(p2 >> 32);
-        }
-        __syncthreads();
-        if (wv) return;
-        auto tot = [&](int i) { return part[0][i] + part[1][i] + part[2][i] + part[3][i]; };
-        hh[0] = tot(2 * lane);
-        hh[1] = tot(2 * lane + 1);
-        hi = tot(128 + lane) | tot(192 + lane);
-        for (int k = 0; k < 4; k++) {
-            s1 += part[k][256] | ((unsigned long long)part[k][257] << 32);
-            s2 += part[k][258] | ((unsigned long long)part[k][259] << 32);
-        }
-    } else {
-        hh[0] = hist[2 * lane];
-        hh[1] = hist[2 * lane + 1];
-        hi = hist[128 + lane] | hist[192 + lane];
-        s1 = sums[0];
-        s2 = sums[1];
-    }
-    if (hi) err = 1;
+    const uint32_t hh[2] = {hist[2 * lane], hist[2 * lane + 1]};
+    if (hist[128 + lane] | hist[192 + lane]) err = 1;
     uint32_t f[2];
     err |= normalize_wave(hh, n, f, lane);
 #pragma unroll
@@ -395,7 +324,7 @@ __global__ __launch_bounds__(256) void k_enc_header(const uint32_t *__restrict__
     if (err) f[0] = f[1] = 0;   // the encode kernel skips zero-frequency symbols: it stays memory-safe
     freq[2 * lane] = (uint16_t)f[0];
     freq[2 * lane + 1] = (uint16_t)f[1];
-    write_header_wave(out, f, s1, s2, n, ns, lat_w, lat_h, lat_c, img_w, img_h, wss, lane);
+    write_header_wave(out, f, sums[0], sums[1], n, ns, lat_w, lat_h, lat_c, img_w, img_h, wss, lane);
     if (lane == 0) status[0] = err;
 }
 
@@ -438,13 +367,12 @@ __global__ __launch_bounds__(64) void k_dec_parse(const uint8_t *__restrict__ co
 }
 
 // Decoder back end: stream-level errors, table total, checksum -> status {error, n_symbols}.
-__global__ __launch_bounds__(64) void k_dec_finish(const uint32_t *__restrict__ meta_, const uint32_t *__restrict__ hist_,
-                                                   const unsigned long long *__restrict__ sums_, const uint32_t *__restrict__ offsets_,
-                                                   uint32_t *__restrict__ status_, uint32_t n, uint32_t ns, size_t s_ws)
+__global__ __launch_bounds__(64) void k_dec_finish(const uint32_t *__restrict__ meta_, const unsigned long long *__restrict__ sums_,
+                                                   const uint32_t *__restrict__ offsets_, uint32_t *__restrict__ status_, uint32_t n,
+                                                   uint32_t ns, size_t s_ws)
 {
     if (threadIdx.x) return;
     const uint32_t *meta = img_ptr(meta_, s_ws), *offsets = img_ptr(offsets_, s_ws);
-    (void)hist_;
     const unsigned long long *sums = img_ptr(sums_, s_ws);
     uint32_t err = meta[0];
     if (meta[3]) err |= 32;                          // a stream overran / underran (k_ransw_decode, k_scan)
@@ -456,22 +384,10 @@ __global__ __launch_bounds__(64) void k_dec_finish(const uint32_t *__restrict__ 
 }
 
 // The asynchronous decoder's ONLY other kernel when the streams were decoded in self mode: dec_finish_self_body
-__global__ __launch_bounds__(256) void k_dec_finish_self(const uint8_t *__restrict__ containers_, const uint32_t *__restrict__ valid_bytes_,
-                                                         uint32_t valid_stride, const uint32_t *__restrict__ serr_,
-                                                         const unsigned long long *__restrict__ ssum_, uint32_t *__restrict__ status_,
-                                                         uint32_t n, uint32_t ns, uint32_t lat_w, uint32_t lat_h, uint32_t lat_c,
-                                                         size_t s_slot, size_t s_ws, uint32_t wss)
+__global__ __launch_bounds__(256) void k_dec_finish_self(const uint8_t *__restrict__ containers, const uint32_t *__restrict__ valid,
+                                                         uint32_t *__restrict__ status, uint8_t *__restrict__ workspace, UniformBatch b)
 {
-    DecImage im{};
-    im.c = img_ptr(containers_, s_slot);
-    im.slot_cap = (uint32_t)min(s_slot, (size_t)0xFFFFFFFFu);
-    im.valid = valid_bytes_ ? valid_bytes_ + (size_t)blockIdx.y * valid_stride : nullptr;
-    im.n = n; im.ns = ns; im.wss = wss;
-    im.lat_w = lat_w; im.lat_h = lat_h; im.lat_c = lat_c;
-    im.err = const_cast<uint32_t *>(img_ptr(serr_, s_ws));
-    im.sums = const_cast<unsigned long long *>(img_ptr(ssum_, s_ws));
-    im.status = status_ + 2 * blockIdx.y;
-    dec_finish_self_body(im);
+    dec_finish_self_body(dec_image(batch_row(b), containers, valid, nullptr, status, workspace, blockIdx.y));
 }
 
 
@@ -577,25 +493,30 @@ extern "C" size_t sicn_codec_batch_workspace_bytes_sl(uint32_t n_symbols, uint32
 
 extern "C" size_t sicn_codec_max_bytes(int mode, uint32_t n)
 {
-    const uint32_t ns = (n + stream_symbols(mode) - 1) / stream_symbols(mode);
-    if (mode == SICN_CODEC_RANSW) return SICN_CODEC_HEADER_BYTES + 256 + 4 * (size_t)ns + 2 * (size_t)n + 256 * (size_t)ns;
+    if (mode == SICN_CODEC_RANSW) return sicn_codec_max_bytes_sl(n, WSS);
     if (mode == SICN_CODEC_RAW8) return SICN_CODEC_HEADER_BYTES + (size_t)n;
     if (mode == SICN_CODEC_PACKED7) return SICN_CODEC_HEADER_BYTES + ((size_t)n + 7) / 8 * 7;
-    if (mode == SICN_CODEC_RANS) return SICN_CODEC_HEADER_BYTES + 256 + 4 * (size_t)ns + 2 * (size_t)n + 8 * (size_t)ns;
+    if (mode == SICN_CODEC_RANS) return SICN_CODEC_HEADER_BYTES + 256 + 4 * (size_t)((n + SS - 1) / SS) + 2 * (size_t)n + 8 * (size_t)((n + SS - 1) / SS);
     return 0;
+}
+
+// Mode 3: per-image blocks, then room for the synchronous wrappers' status arrays (2 x 8 bytes per image) — enough for a
+// container of ANY admissible stream length (the synchronous decoders read it from the header)
+extern "C" size_t sicn_codec_batch_workspace_bytes(int mode, uint32_t n_symbols, uint32_t n_images)
+{
+    if (mode != SICN_CODEC_RANSW)
+        return (size_t)n_images * align_up(sicn_codec_workspace_bytes(mode, n_symbols), 256) + align_up(16 * (size_t)n_images, 256);
+    size_t mx = 0;
+    for (uint32_t wss = 1024; wss <= WSS; wss <<= 1)
+        if (wstream_fits(n_symbols, wss)) mx = std::max(mx, sicn_codec_batch_workspace_bytes_sl(n_symbols, n_images, wss));
+    return mx;
 }
 
 extern "C" size_t sicn_codec_workspace_bytes(int mode, uint32_t n)
 {
+    if (mode == SICN_CODEC_RANSW) return sicn_codec_batch_workspace_bytes(mode, n, 1);   // the synchronous calls are batches of one
     Workspace w;
-    if (mode == SICN_CODEC_RANSW) {   // enough for a container of ANY admissible stream length (sicn_codec_decode reads it from the header)
-        size_t mx = 0;
-        for (uint32_t wss = 1024; wss <= WSS; wss <<= 1)
-            if (wstream_fits(n, wss)) mx = std::max(mx, carve(w, nullptr, (n + wss - 1) / wss, wstream_cap(wss)) + 64);
-        return mx;
-    }
-    const uint32_t ns = (n + stream_symbols(mode) - 1) / stream_symbols(mode);
-    return carve(w, nullptr, ns, mode >= SICN_CODEC_RANS ? stream_cap(mode) : 0) + 64;
+    return carve(w, nullptr, (n + SS - 1) / SS, mode == SICN_CODEC_RANS ? CAP : 0) + 64;
 }
 
 extern "C" int sicn_codec_parse_header(const uint8_t *h, size_t bytes, sicn_codec_info *info)
@@ -630,6 +551,70 @@ extern "C" int sicn_codec_parse_header(const uint8_t *h, size_t bytes, sicn_code
     return SICN_OK;
 }
 
+static int status_to_rc(uint32_t err)
+{
+    if (!err) return SICN_OK;
+    return (err & ~128u) ? SICN_EINVAL : SICN_EBADMSG;
+}
+
+// ---- rANS-W: the synchronous calls = the asynchronous pair + one read-back of the status array, which lives behind the
+// ---- per-image blocks of the caller's workspace (sicn_codec_batch_workspace_bytes[_sl]) --------------------------
+static int ransw_encode_sync(const uint8_t *latents, uint32_t n_images, uint32_t lat_w, uint32_t lat_h, uint32_t lat_c, uint32_t img_w,
+                             uint32_t img_h, uint8_t *out, size_t slot_bytes, size_t *out_bytes_host, void *workspace,
+                             size_t workspace_bytes, void *hip_stream)
+{
+    if (!out || !out_bytes_host) return SICN_EINVAL;
+    if (n_images == 0) return SICN_OK;
+    const unsigned long long n64 = (unsigned long long)lat_w * lat_h * lat_c;
+    if (n64 > MAX_RANS_SYMBOLS) return SICN_EINVAL;
+    const size_t blocks = (size_t)n_images * align_up(sicn_codec_workspace_bytes_sl((uint32_t)n64, WSS), 256);
+    if (!workspace || workspace_bytes < sicn_codec_batch_workspace_bytes(SICN_CODEC_RANSW, (uint32_t)n64, n_images)) return SICN_ENOSPC;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    sicn_codec_status *st_dev = (sicn_codec_status *)((uint8_t *)workspace + blocks);
+    std::vector<sicn_codec_status> st;
+    try { st.resize(n_images); } catch (const std::bad_alloc &) { return SICN_ENOMEM; }
+    int rc = sicn_codec_encode_batch_async(latents, n_images, lat_w, lat_h, lat_c, img_w, img_h, out, slot_bytes, st_dev, workspace,
+                                           workspace_bytes, hip_stream);
+    if (rc == SICN_OK && hipMemcpyAsync(st.data(), st_dev, sizeof(sicn_codec_status) * n_images, hipMemcpyDeviceToHost, stream) != hipSuccess)
+        rc = SICN_ENODEV;
+    if (hipStreamSynchronize(stream) != hipSuccess) return SICN_ENODEV;
+    if (rc) return rc;
+    for (uint32_t i = 0; i < n_images; i++) {
+        if (st[i].error) return SICN_EINVAL;
+        out_bytes_host[i] = st[i].bytes;
+    }
+    return SICN_OK;
+}
+
+// n containers of the shape and stream length of `info` (parsed from their headers by the caller), bytes_host[i] valid bytes each
+static int ransw_decode_sync(const uint8_t *containers, size_t slot_bytes, const size_t *bytes_host, uint32_t n_images,
+                             const sicn_codec_info &info, uint8_t *latents, size_t latent_stride, void *workspace, size_t workspace_bytes,
+                             void *hip_stream)
+{
+    const uint32_t n = info.n_symbols, wss = info.stream_symbols;
+    const size_t blocks = (size_t)n_images * align_up(sicn_codec_workspace_bytes_sl(n, wss), 256);
+    if (!workspace || workspace_bytes < sicn_codec_batch_workspace_bytes_sl(n, n_images, wss)) return SICN_ENOSPC;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    std::vector<sicn_codec_status> st;
+    try { st.resize(2 * (size_t)n_images); } catch (const std::bad_alloc &) { return SICN_ENOMEM; }
+    for (uint32_t i = 0; i < n_images; i++) st[i] = sicn_codec_status{0, (uint32_t)std::min(bytes_host[i], (size_t)0xFFFFFFFFu)};
+    sicn_codec_status *st_dev = (sicn_codec_status *)((uint8_t *)workspace + blocks);   // [0, n): valid bytes in, [n, 2n): verdicts out
+    int rc = hipMemcpyAsync(st_dev, st.data(), sizeof(sicn_codec_status) * n_images, hipMemcpyHostToDevice, stream) == hipSuccess
+                 ? SICN_OK : SICN_ENODEV;
+    if (rc == SICN_OK)
+        rc = sicn_codec_decode_batch_async_sl(containers, slot_bytes, st_dev, n_images, info.lat_w, info.lat_h, info.lat_c, latents,
+                                              latent_stride, st_dev + n_images, workspace, workspace_bytes, hip_stream, wss);
+    if (rc == SICN_OK && hipMemcpyAsync(st.data() + n_images, st_dev + n_images, sizeof(sicn_codec_status) * n_images,
+                                        hipMemcpyDeviceToHost, stream) != hipSuccess)
+        rc = SICN_ENODEV;
+    if (hipStreamSynchronize(stream) != hipSuccess) return SICN_ENODEV;
+    if (rc) return rc;
+    for (uint32_t i = 0; i < n_images; i++)
+        if (int e = status_to_rc(st[n_images + i].error)) return e;
+    return SICN_OK;
+}
+
+// ---- single images: modes 0 - 2 on the host's schedule, mode 3 as a batch of one ---------------------------------
 extern "C" int sicn_codec_encode(int mode, const uint8_t *latent, uint32_t lat_w, uint32_t lat_h, uint32_t lat_c,
                                  uint32_t img_w, uint32_t img_h, uint8_t *out, size_t out_capacity, size_t *out_bytes,
                                  void *workspace, size_t workspace_bytes, void *hip_stream)
@@ -638,17 +623,19 @@ extern "C" int sicn_codec_encode(int mode, const uint8_t *latent, uint32_t lat_w
     const unsigned long long n64 = (unsigned long long)lat_w * lat_h * lat_c;
     if (n64 > 0x7fffffffull || (n64 && !latent)) return SICN_EINVAL;
     if (mode >= SICN_CODEC_RANS && n64 > MAX_RANS_SYMBOLS) return SICN_EINVAL;
-    const uint32_t n = (uint32_t)n64, ss = stream_symbols(mode), ns = (n + ss - 1) / ss;
+    const uint32_t n = (uint32_t)n64, ns = (n + SS - 1) / SS;
     if (out_capacity < sicn_codec_max_bytes(mode, n)) return SICN_ENOSPC;
+    if (mode == SICN_CODEC_RANSW)   // (slots are even: the bound above is)
+        return ransw_encode_sync(latent, 1, lat_w, lat_h, lat_c, img_w, img_h, out, out_capacity & ~(size_t)1, out_bytes, workspace,
+                                 workspace_bytes, hip_stream);
     if (!workspace || workspace_bytes < sicn_codec_workspace_bytes(mode, n)) return SICN_ENOSPC;
     hipStream_t stream = (hipStream_t)hip_stream;
     Workspace w;
-    carve(w, workspace, ns, mode >= SICN_CODEC_RANS ? stream_cap(mode) : 0);
+    carve(w, workspace, ns, mode == SICN_CODEC_RANS ? CAP : 0);
 
     // statistics (also the checksum and the symbol-range check) -------------------------------
     HIP_TRY(hipMemsetAsync(w.hist, 0, 1024 + 64, stream));
-    if (n)
-        hipLaunchKernelGGL(k_stats, dim3(stats_blocks(n, 1)), dim3(256), 0, stream, latent, n, w.hist, w.sums, (size_t)0, (size_t)0);
+    if (n) hipLaunchKernelGGL(k_stats, dim3(stats_blocks(n)), dim3(256), 0, stream, latent, (uint8_t *)workspace, stats_batch(n, 0, 0));
     uint32_t hist[256];
     unsigned long long sums[2];
     HIP_TRY(hipMemcpyAsync(hist, w.hist, sizeof hist, hipMemcpyDeviceToHost, stream));
@@ -669,7 +656,7 @@ extern "C" int sicn_codec_encode(int mode, const uint8_t *latent, uint32_t lat_w
     put32(head + 24, lat_c);
     put32(head + 28, n);
     put32(head + 32, ns);
-    put32(head + 36, ss);
+    put32(head + 36, SS);
     put32(head + 44, adler_from_sums(sums[0], sums[1], n));
 
     size_t total;
@@ -695,13 +682,10 @@ extern "C" int sicn_codec_encode(int mode, const uint8_t *latent, uint32_t lat_w
         HIP_TRY(hipMemcpyAsync(w.freq, freq, sizeof freq, hipMemcpyHostToDevice, stream));
         uint8_t *table = out + SICN_CODEC_HEADER_BYTES + 256;
         uint8_t *payload = table + 4 * (size_t)ns;
-        if (ns && mode == SICN_CODEC_RANSW)
-            hipLaunchKernelGGL(k_ransw_encode, dim3(ns), dim3(64), 0, stream, latent, n, ns, w.freq, w.scratch, w.lens, (size_t)0, (size_t)0, WSS);
-        else if (ns)
-            hipLaunchKernelGGL(k_rans_encode, dim3((ns + 255) / 256), dim3(256), 0, stream, latent, n, ns, w.freq, w.scratch, w.lens);
+        if (ns) hipLaunchKernelGGL(k_rans_encode, dim3((ns + 255) / 256), dim3(256), 0, stream, latent, n, ns, w.freq, w.scratch, w.lens);
         hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, stream, w.lens, (const uint8_t *)nullptr, ns, w.offsets, table, out + 40, (size_t)0, (size_t)0,
                            0xFFFFFFFFu, (uint32_t *)nullptr);
-        if (ns) hipLaunchKernelGGL(k_compact, dim3(ns), dim3(256), 0, stream, w.scratch, w.lens, w.offsets, payload, stream_cap(mode), (size_t)0, (size_t)0);
+        if (ns) hipLaunchKernelGGL(k_compact, dim3(ns), dim3(256), 0, stream, w.scratch, w.lens, w.offsets, payload, CAP, (size_t)0, (size_t)0);
         uint32_t payload_bytes = 0;
         HIP_TRY(hipMemcpyAsync(&payload_bytes, w.offsets + ns, 4, hipMemcpyDeviceToHost, stream));
         HIP_TRY(hipStreamSynchronize(stream));
@@ -728,12 +712,12 @@ extern "C" int sicn_codec_decode(const uint8_t *container, size_t bytes, uint8_t
     const uint32_t n = info.n_symbols, ns = info.n_streams;
     if (n > 0x7fffffffu || (info.mode >= SICN_CODEC_RANS && n > MAX_RANS_SYMBOLS)) return SICN_EINVAL;
     if (n && (!latent || latent_capacity < n)) return SICN_ENOSPC;
-    const bool wmode = info.mode == SICN_CODEC_RANSW;
-    if (wmode && !wstream_fits(n, info.stream_symbols)) return SICN_EINVAL;
-    // (a caller that sized the workspace for the default stream length needs sicn_codec_workspace_bytes_sl for shorter streams)
-    if (!workspace || workspace_bytes < (wmode ? sicn_codec_workspace_bytes_sl(n, info.stream_symbols)
-                                               : sicn_codec_workspace_bytes((int)info.mode, n)))
-        return SICN_ENOSPC;
+    if (info.mode == SICN_CODEC_RANSW) {   // the slot is the caller's bytes (rounded up to the even size slots have; `bytes` bound every read)
+        if (!wstream_fits(n, info.stream_symbols)) return SICN_EINVAL;
+        return ransw_decode_sync(container, (bytes + 1) & ~(size_t)1, &bytes, 1, info, latent, latent_capacity, workspace, workspace_bytes,
+                                 hip_stream);
+    }
+    if (!workspace || workspace_bytes < sicn_codec_workspace_bytes((int)info.mode, n)) return SICN_ENOSPC;
     Workspace w;
     carve(w, workspace, ns, 0);
     HIP_TRY(hipMemsetAsync(w.hist, 0, 1024 + 64, stream));
@@ -761,16 +745,12 @@ extern "C" int sicn_codec_decode(const uint8_t *container, size_t bytes, uint8_t
             if (sum != 4096) return SICN_EINVAL;
         }
         hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, stream, (const uint32_t *)nullptr, table, ns, w.offsets,
-                           (uint8_t *)nullptr, (uint8_t *)nullptr, (size_t)0, (size_t)0,
-                           wmode ? wstream_cap(info.stream_symbols) : stream_cap((int)info.mode), err);
+                           (uint8_t *)nullptr, (uint8_t *)nullptr, (size_t)0, (size_t)0, CAP, err);
         uint32_t total = 0;
         HIP_TRY(hipMemcpyAsync(&total, w.offsets + ns, 4, hipMemcpyDeviceToHost, stream));
         HIP_TRY(hipStreamSynchronize(stream));
         if (total != info.payload_bytes) return SICN_EINVAL;
-        if (ns && info.mode == SICN_CODEC_RANSW)
-            hipLaunchKernelGGL(k_ransw_decode<false>, dim3(ns), dim3(64), 0, stream, payload, freq_bytes, w.offsets, n, ns, latent, err, (size_t)0, (size_t)0, (size_t)0,
-                               container + 40, (const uint32_t *)nullptr, (unsigned long long *)nullptr, info.stream_symbols);
-        else if (ns)
+        if (ns)
             hipLaunchKernelGGL(k_rans_decode, dim3((ns + 255) / 256), dim3(256), 0, stream, payload, freq_bytes, w.offsets, n, ns, latent, err,
                                info.payload_bytes);
     }
@@ -780,7 +760,7 @@ extern "C" int sicn_codec_decode(const uint8_t *container, size_t bytes, uint8_t
     HIP_TRY(hipStreamSynchronize(stream));
     if (flag) return SICN_EINVAL;
     HIP_TRY(hipMemsetAsync(w.hist, 0, 1024 + 64, stream));
-    if (n) hipLaunchKernelGGL(k_stats, dim3(stats_blocks(n, 1)), dim3(256), 0, stream, latent, n, w.hist, w.sums, (size_t)0, (size_t)0);
+    if (n) hipLaunchKernelGGL(k_stats, dim3(stats_blocks(n)), dim3(256), 0, stream, latent, (uint8_t *)workspace, stats_batch(n, 0, 0));
     unsigned long long sums[2];
     HIP_TRY(hipMemcpyAsync(sums, w.sums, sizeof sums, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
@@ -789,17 +769,10 @@ extern "C" int sicn_codec_decode(const uint8_t *container, size_t bytes, uint8_t
 }
 
 
-// ---- batches -------------------------------------------------------------------------------------------------
-// The asynchronous pair does everything on the device (statistics -> frequency table -> header -> streams -> offsets
-// -> compaction; parse -> offsets -> streams -> checksum) and reports through a device status array: no host
-// synchronisation, no allocation, capturable in a hipGraph.  The synchronous batch calls are thin wrappers that add
-// the read-back.
-extern "C" size_t sicn_codec_batch_workspace_bytes(int mode, uint32_t n_symbols, uint32_t n_images)
-{
-    // per-image blocks, then room for the synchronous wrappers' status arrays (2 x 8 bytes per image)
-    return (size_t)n_images * align_up(sicn_codec_workspace_bytes(mode, n_symbols), 256) + align_up(16 * (size_t)n_images, 256);
-}
-
+// ---- rANS-W: the asynchronous pair ---------------------------------------------------------------------------
+// Everything runs on the device (statistics -> frequency table -> header -> streams -> offsets -> compaction; parse ->
+// offsets -> streams -> checksum) and reports through a device status array: no host synchronisation, no allocation,
+// capturable in a hipGraph.  Every synchronous rANS-W call is this pair plus the read-back (further down).
 extern "C" int sicn_codec_encode_batch_async_sl(const uint8_t *latents, uint32_t n_images, uint32_t lat_w, uint32_t lat_h,
                                                 uint32_t lat_c, uint32_t img_w, uint32_t img_h, uint8_t *out, size_t slot_bytes,
                                                 sicn_codec_status *status_dev, void *workspace, size_t workspace_bytes,
@@ -814,33 +787,28 @@ extern "C" int sicn_codec_encode_batch_async_sl(const uint8_t *latents, uint32_t
     const size_t ws1 = align_up(sicn_codec_workspace_bytes_sl(n, wss), 256);
     if (!workspace || workspace_bytes < ws1 * n_images) return SICN_ENOSPC;
     hipStream_t stream = (hipStream_t)hip_stream;
-    Workspace w;
-    carve(w, workspace, ns, wcap);
+    uint8_t *ws = (uint8_t *)workspace;
     uint32_t *status = (uint32_t *)status_dev;
-    uint8_t *table = out + SICN_CODEC_HEADER_BYTES + 256, *payload = table + 4 * (size_t)ns;
-    const uint32_t fixed = (uint32_t)(SICN_CODEC_HEADER_BYTES + 256 + 4 * (size_t)ns);
-    if (ns && ns <= SELF_SCAN_MAX) {
+    const bool scan = ns == 0 || ns > SELF_SCAN_MAX;
+    const UniformBatch b = uniform_batch(lat_w, lat_h, lat_c, img_w, img_h, wss, n, slot_bytes, ws1, scan);
+    if (!scan) {
         // three launches (round 4; four in round 3, six in round 2): statistics in rows (no clear, no atomics) -> streams, every
         // wave making the frequency table from the rows itself and stream 0's wave writing header, table and status ->
         // compaction with its own scan
-        const uint32_t n_rows = std::min(std::max(n / 16384u, 1u), STAT_ROWS);
-        hipLaunchKernelGGL(k_stats, dim3(n_rows, n_images), dim3(256), 0, stream, latents, n, w.hist, w.sums, (size_t)n, ws1, w.rows);
-        const EncSelfHeader sh{w.rows, n_rows, out, slot_bytes, status, lat_w, lat_h, lat_c, img_w, img_h};
-        hipLaunchKernelGGL(k_ransw_encode, dim3(ns, n_images), dim3(64), 0, stream, latents, n, ns, w.freq, w.scratch, w.lens,
-                           (size_t)n, ws1, wss, sh);
-        hipLaunchKernelGGL(k_compact_self, dim3(ns, n_images), dim3(256), 0, stream, w.scratch, w.lens, out, wcap, ns, ws1, slot_bytes,
-                           status, fixed);
+        hipLaunchKernelGGL(k_stats, dim3(b.row0.n_rows, n_images), dim3(256), 0, stream, latents, ws, b);
+        hipLaunchKernelGGL(k_ransw_encode, dim3(ns, n_images), dim3(64), 0, stream, latents, out, status, ws, b);
+        hipLaunchKernelGGL(k_compact_self, dim3(ns, n_images), dim3(256), 0, stream, out, status, ws, b);
         return hipGetLastError() == hipSuccess ? SICN_OK : SICN_ENODEV;
     }
+    Workspace w;
+    carve(w, workspace, ns, wcap);
+    uint8_t *table = out + SICN_CODEC_HEADER_BYTES + 256, *payload = table + 4 * (size_t)ns;
+    const uint32_t fixed = (uint32_t)(SICN_CODEC_HEADER_BYTES + 256 + 4 * (size_t)ns);
     hipLaunchKernelGGL(k_clear_stats, dim3(1, n_images), dim3(64), 0, stream, w.hist, ws1);
-    if (n)
-        hipLaunchKernelGGL(k_stats, dim3(stats_blocks(n, n_images), n_images), dim3(256), 0, stream, latents, n, w.hist,
-                           w.sums, (size_t)n, ws1);
+    if (n) hipLaunchKernelGGL(k_stats, dim3(stats_blocks(n), n_images), dim3(256), 0, stream, latents, ws, b);
     hipLaunchKernelGGL(k_enc_header, dim3(1, n_images), dim3(64), 0, stream, w.hist, w.sums, w.freq, out, status, n, ns, lat_w,
                        lat_h, lat_c, img_w, img_h, ws1, slot_bytes, wss);
-    if (ns)
-        hipLaunchKernelGGL(k_ransw_encode, dim3(ns, n_images), dim3(64), 0, stream, latents, n, ns, w.freq, w.scratch, w.lens,
-                           (size_t)n, ws1, wss);
+    if (ns) hipLaunchKernelGGL(k_ransw_encode, dim3(ns, n_images), dim3(64), 0, stream, latents, out, status, ws, b);
     hipLaunchKernelGGL(k_scan, dim3(1, n_images), dim3(1024), 0, stream, w.lens, (const uint8_t *)nullptr, ns, w.offsets, table,
                        out + 40, ws1, slot_bytes, 0xFFFFFFFFu, (uint32_t *)nullptr, status, fixed);
     if (ns)
@@ -872,44 +840,38 @@ extern "C" int sicn_codec_decode_batch_async_sl(const uint8_t *containers, size_
     const size_t ws1 = align_up(sicn_codec_workspace_bytes_sl(n, wss), 256);
     if (!workspace || workspace_bytes < ws1 * n_images) return SICN_ENOSPC;
     hipStream_t stream = (hipStream_t)hip_stream;
-    Workspace w;
-    carve(w, workspace, ns, 0);
-    const uint8_t *freq_bytes = containers + SICN_CODEC_HEADER_BYTES, *table = freq_bytes + 256, *payload = table + 4 * (size_t)ns;
-    if (ns <= SELF_SCAN_MAX) {
+    uint8_t *ws = (uint8_t *)workspace;
+    const uint32_t *valid = (const uint32_t *)valid_dev_or_null;
+    const bool scan = ns > SELF_SCAN_MAX;
+    const UniformBatch b = uniform_batch(lat_w, lat_h, lat_c, 0, 0, wss, latent_stride, slot_bytes, ws1, scan);
+    if (!scan) {
         // two launches instead of four: the streams bound and place themselves (self mode), the finish kernel validates header
         // and table and folds the per-stream verdicts / checksum sums (a small image's decode is mostly launch latency)
-        uint32_t *serr = w.lens;                                           // [ns]
-        unsigned long long *ssum = (unsigned long long *)w.scratch;        // [2 ns]; the scratch slots (>= 2304 B each) are idle in a decode
-        const uint32_t *vb = valid_dev_or_null ? &valid_dev_or_null->bytes : (const uint32_t *)nullptr;
         if (ns) {
             // the latency form (one 16 KB table, one LDS round trip less per step) while all waves of the batch fit the chip at
             // five per CU; beyond that the two-table form, whose lookups the other eleven waves of a CU hide
             sicn::ChipGeom chip;
             const bool big = sicn::chip_geom(&chip) == SICN_OK && (unsigned long long)ns * n_images <= 5ull * (unsigned)chip.n_cu;
             if (big)
-                hipLaunchKernelGGL(k_ransw_decode<true>, dim3(ns, n_images), dim3(64), 0, stream, payload, freq_bytes, (const uint32_t *)nullptr, n, ns,
-                                   latents, serr, slot_bytes, ws1, latent_stride, containers + 40, (const uint32_t *)nullptr, ssum, wss, vb, 2u, 1);
+                hipLaunchKernelGGL(k_ransw_decode<true>, dim3(ns, n_images), dim3(64), 0, stream, containers, valid, latents, ws, b);
             else
-                hipLaunchKernelGGL(k_ransw_decode<false>, dim3(ns, n_images), dim3(64), 0, stream, payload, freq_bytes, (const uint32_t *)nullptr, n, ns,
-                                   latents, serr, slot_bytes, ws1, latent_stride, containers + 40, (const uint32_t *)nullptr, ssum, wss, vb, 2u, 1);
+                hipLaunchKernelGGL(k_ransw_decode<false>, dim3(ns, n_images), dim3(64), 0, stream, containers, valid, latents, ws, b);
         }
-        hipLaunchKernelGGL(k_dec_finish_self, dim3(1, n_images), dim3(256), 0, stream, containers, vb, 2u, serr, ssum, (uint32_t *)status_dev,
-                           n, ns, lat_w, lat_h, lat_c, slot_bytes, ws1, wss);
+        hipLaunchKernelGGL(k_dec_finish_self, dim3(1, n_images), dim3(256), 0, stream, containers, valid, (uint32_t *)status_dev, ws, b);
         return hipGetLastError() == hipSuccess ? SICN_OK : SICN_ENODEV;
     }
+    Workspace w;
+    carve(w, workspace, ns, 0);
     hipLaunchKernelGGL(k_dec_parse, dim3(1, n_images), dim3(64), 0, stream, containers,
                        valid_dev_or_null ? &valid_dev_or_null->bytes : (const uint32_t *)nullptr, 2u, w.meta, n, ns, lat_w, lat_h,
                        lat_c, slot_bytes, ws1, wss);
     // a slot the parse stage rejected as too short is never read: its table counts as empty (ns_eff = 0 via meta[1] = 0 and
     // the per-stream bound off + len <= payload bytes, so every stream of it flags an error and returns)
-    hipLaunchKernelGGL(k_scan, dim3(1, n_images), dim3(1024), 0, stream, (const uint32_t *)nullptr, table, ns, w.offsets,
-                       (uint8_t *)nullptr, (uint8_t *)nullptr, ws1, slot_bytes, wstream_cap(wss), w.meta + 3, (uint32_t *)nullptr, 0u,
-                       (const uint32_t *)w.meta);
-    if (ns)
-        hipLaunchKernelGGL(k_ransw_decode<false>, dim3(ns, n_images), dim3(64), 0, stream, payload, freq_bytes, w.offsets, n, ns, latents,
-                           w.meta + 3, slot_bytes, ws1, latent_stride, containers + 40, w.meta, w.sums, wss);
-    hipLaunchKernelGGL(k_dec_finish, dim3(1, n_images), dim3(64), 0, stream, w.meta, w.hist, w.sums, w.offsets, (uint32_t *)status_dev,
-                       n, ns, ws1);
+    hipLaunchKernelGGL(k_scan, dim3(1, n_images), dim3(1024), 0, stream, (const uint32_t *)nullptr,
+                       containers + SICN_CODEC_HEADER_BYTES + 256, ns, w.offsets, (uint8_t *)nullptr, (uint8_t *)nullptr, ws1, slot_bytes,
+                       wstream_cap(wss), w.meta + 3, (uint32_t *)nullptr, 0u, (const uint32_t *)w.meta);
+    hipLaunchKernelGGL(k_ransw_decode<false>, dim3(ns, n_images), dim3(64), 0, stream, containers, valid, latents, ws, b);
+    hipLaunchKernelGGL(k_dec_finish, dim3(1, n_images), dim3(64), 0, stream, w.meta, w.sums, w.offsets, (uint32_t *)status_dev, n, ns, ws1);
     return hipGetLastError() == hipSuccess ? SICN_OK : SICN_ENODEV;
 }
 
@@ -922,38 +884,13 @@ extern "C" int sicn_codec_decode_batch_async(const uint8_t *containers, size_t s
                                             latent_stride, status_dev, workspace, workspace_bytes, hip_stream, WSS);
 }
 
-static int status_to_rc(uint32_t err)
-{
-    if (!err) return SICN_OK;
-    return (err & ~128u) ? SICN_EINVAL : SICN_EBADMSG;
-}
-
 extern "C" int sicn_codec_encode_batch(int mode, const uint8_t *latents, uint32_t n_images, uint32_t lat_w, uint32_t lat_h,
                                        uint32_t lat_c, uint32_t img_w, uint32_t img_h, uint8_t *out, size_t slot_bytes,
                                        size_t *out_bytes_host, void *workspace, size_t workspace_bytes, void *hip_stream)
 {
-    if (mode != SICN_CODEC_RANSW || !out || !out_bytes_host) return SICN_EINVAL;
-    if (n_images == 0) return SICN_OK;
-    // the status array lives behind the per-image blocks of the caller's workspace (sicn_codec_batch_workspace_bytes)
-    const unsigned long long n64 = (unsigned long long)lat_w * lat_h * lat_c;
-    if (n64 > MAX_RANS_SYMBOLS) return SICN_EINVAL;
-    const size_t blocks = (size_t)n_images * align_up(sicn_codec_workspace_bytes(mode, (uint32_t)n64), 256);
-    if (!workspace || workspace_bytes < sicn_codec_batch_workspace_bytes(mode, (uint32_t)n64, n_images)) return SICN_ENOSPC;
-    hipStream_t stream = (hipStream_t)hip_stream;
-    sicn_codec_status *st_dev = (sicn_codec_status *)((uint8_t *)workspace + blocks);
-    std::vector<sicn_codec_status> st;
-    try { st.resize(n_images); } catch (const std::bad_alloc &) { return SICN_ENOMEM; }
-    int rc = sicn_codec_encode_batch_async(latents, n_images, lat_w, lat_h, lat_c, img_w, img_h, out, slot_bytes, st_dev, workspace,
-                                           workspace_bytes, hip_stream);
-    if (rc == SICN_OK && hipMemcpyAsync(st.data(), st_dev, sizeof(sicn_codec_status) * n_images, hipMemcpyDeviceToHost, stream) != hipSuccess)
-        rc = SICN_ENODEV;
-    if (hipStreamSynchronize(stream) != hipSuccess) return SICN_ENODEV;
-    if (rc) return rc;
-    for (uint32_t i = 0; i < n_images; i++) {
-        if (st[i].error) return SICN_EINVAL;
-        out_bytes_host[i] = st[i].bytes;
-    }
-    return SICN_OK;
+    if (mode != SICN_CODEC_RANSW) return SICN_EINVAL;
+    return ransw_encode_sync(latents, n_images, lat_w, lat_h, lat_c, img_w, img_h, out, slot_bytes, out_bytes_host, workspace,
+                             workspace_bytes, hip_stream);
 }
 
 extern "C" int sicn_codec_decode_batch(const uint8_t *containers, size_t slot_bytes, const size_t *bytes_host, uint32_t n_images,
@@ -965,11 +902,9 @@ extern "C" int sicn_codec_decode_batch(const uint8_t *containers, size_t slot_by
     hipStream_t stream = (hipStream_t)hip_stream;
     std::vector<uint8_t> head;
     std::vector<sicn_codec_info> info;
-    std::vector<sicn_codec_status> st;
     try {
         head.resize((size_t)n_images * SICN_CODEC_HEADER_BYTES);
         info.resize(n_images);
-        st.resize(2 * (size_t)n_images);
     } catch (const std::bad_alloc &) { return SICN_ENOMEM; }
     // first synchronisation: the shape comes out of the containers (the async entry point takes it from the caller)
     for (uint32_t i = 0; i < n_images; i++) {
@@ -986,26 +921,9 @@ extern "C" int sicn_codec_decode_batch(const uint8_t *containers, size_t slot_by
         if (info[i].stream_symbols != info[0].stream_symbols) return SICN_EINVAL;   // one batch = one stream length
         if (info[i].n_symbols > MAX_RANS_SYMBOLS) return SICN_EINVAL;
         if (infos_or_null) infos_or_null[i] = info[i];
-        st[i].error = 0;
-        st[i].bytes = (uint32_t)bytes_host[i];
     }
-    const uint32_t wss = info[0].stream_symbols;
-    const size_t blocks = (size_t)n_images * align_up(sicn_codec_workspace_bytes_sl(info[0].n_symbols, wss), 256);
-    if (!workspace || workspace_bytes < sicn_codec_batch_workspace_bytes_sl(info[0].n_symbols, n_images, wss)) return SICN_ENOSPC;
-    sicn_codec_status *st_dev = (sicn_codec_status *)((uint8_t *)workspace + blocks);   // [0, n): valid bytes in, [n, 2n): verdicts out
-    int rc = hipMemcpyAsync(st_dev, st.data(), sizeof(sicn_codec_status) * n_images, hipMemcpyHostToDevice, stream) == hipSuccess
-                 ? SICN_OK : SICN_ENODEV;
-    if (rc == SICN_OK)
-        rc = sicn_codec_decode_batch_async_sl(containers, slot_bytes, st_dev, n_images, info[0].lat_w, info[0].lat_h, info[0].lat_c,
-                                              latents, latent_stride, st_dev + n_images, workspace, workspace_bytes, hip_stream, wss);
-    if (rc == SICN_OK && hipMemcpyAsync(st.data() + n_images, st_dev + n_images, sizeof(sicn_codec_status) * n_images,
-                                        hipMemcpyDeviceToHost, stream) != hipSuccess)
-        rc = SICN_ENODEV;
-    if (hipStreamSynchronize(stream) != hipSuccess) return SICN_ENODEV;
-    if (rc) return rc;
-    for (uint32_t i = 0; i < n_images; i++)
-        if (int e = status_to_rc(st[n_images + i].error)) return e;
-    return SICN_OK;
+    return ransw_decode_sync(containers, slot_bytes, bytes_host, n_images, info[0], latents, latent_stride, workspace, workspace_bytes,
+                             hip_stream);
 }
 
 #include "sicn_codec_ctx.inc"   // container mode 4: class-conditional rANS-W with a checkerboard context model

@@ -502,8 +502,7 @@ extern "C" int sicn_codec_ctx_encode_batch_async(const uint8_t *latents, const u
     const uint32_t fixed = (uint32_t)(SICN_CODEC_HEADER_BYTES + CTX_TABLE_BYTES + 4 * (size_t)ns);
     hipLaunchKernelGGL(k_clear_stats, dim3(1, n_images), dim3(64), 0, stream, w.hist, ws1);
     HIP_TRY(hipMemset2DAsync(w.chist, ws1, 0, NCLS * 128 * 4, n_images, stream));
-    hipLaunchKernelGGL(k_stats, dim3(stats_blocks(n, n_images), n_images), dim3(256), 0, stream, latents, n, w.hist, w.sums,
-                       (size_t)n, ws1);
+    hipLaunchKernelGGL(k_stats, dim3(stats_blocks(n), n_images), dim3(256), 0, stream, latents, (uint8_t *)workspace, stats_batch(n, n, ws1));
     hipLaunchKernelGGL(k_ctx_hist, dim3(min((n / 4 + 255u) / 256u, 256u), n_images), dim3(256), 0, stream, latents, scales, g, w.chist,
                        w.meta, (size_t)n, ws1);
     hipLaunchKernelGGL(k_ctx_tables, dim3(1, n_images), dim3(1024), 0, stream, w.chist, w.sums, w.meta, w.tfc, w.trcp, w.tst, out, status,
@@ -548,9 +547,7 @@ extern "C" int sicn_codec_ctx_decode_batch_async(const uint8_t *containers, size
         if (g.nst[set])
             hipLaunchKernelGGL(k_ctx_decode, dim3((g.nst[set] + CTX_WPB_DEC - 1) / CTX_WPB_DEC, n_images), dim3(64 * CTX_WPB_DEC), 0, stream, payload, scales, set, g, w.tfc, w.tst,
                                w.offsets, latents, w.meta, slot_bytes, ws1, (size_t)n);
-    hipLaunchKernelGGL(k_stats, dim3(stats_blocks(n, n_images), n_images), dim3(256), 0, stream, latents, n, w.hist, w.sums,
-                       (size_t)n, ws1);
-    hipLaunchKernelGGL(k_dec_finish, dim3(1, n_images), dim3(64), 0, stream, w.meta, w.hist, w.sums, w.offsets, (uint32_t *)status_dev, n,
-                       ns, ws1);
+    hipLaunchKernelGGL(k_stats, dim3(stats_blocks(n), n_images), dim3(256), 0, stream, latents, (uint8_t *)workspace, stats_batch(n, n, ws1));
+    hipLaunchKernelGGL(k_dec_finish, dim3(1, n_images), dim3(64), 0, stream, w.meta, w.sums, w.offsets, (uint32_t *)status_dev, n, ns, ws1);
     return hipGetLastError() == hipSuccess ? SICN_OK : SICN_ENODEV;
 }

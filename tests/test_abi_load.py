@@ -89,6 +89,17 @@ def test_options_defaults_and_validation_without_gpu():
     assert not hasattr(L, "sicn_set_force_generic")
 
 
+def test_ransw_workspace_bound_covers_every_stream_length_without_gpu():
+    """The synchronous rANS-W calls are the asynchronous pair with one image: the workspace sicn_codec_workspace_bytes(3, n) promises
+    holds a batch of one (blocks + status words) at every admissible stream length, and the mode-3 container bound is the default
+    length's."""
+    L = _lib.lib()
+    for n in (0, 1, 16384, 16385, 6220800):
+        for wss in (1024, 2048, 4096, 8192, 16384):
+            assert L.sicn_codec_workspace_bytes(3, n) >= L.sicn_codec_batch_workspace_bytes_sl(n, 1, wss), (n, wss)
+        assert L.sicn_codec_max_bytes(3, n) == L.sicn_codec_max_bytes_sl(n, 16384), n
+
+
 def test_isa_hazard_checker_flags_the_known_bugs():
     """tools/isa_hazards.py (run over the asm kernels' ISA by build()): its self-test holds the two round-2 bugs and the round-3
     one as ISA snippets — a VALU-unpacked bias read as an asm MFMA's C operand, an asm atomic whose address SGPRs come from a

@@ -510,6 +510,61 @@ def test_gpu_async_decode_with_many_streams_takes_the_scan_path():
 
 
 @gpu
+@pytest.mark.parametrize("n_streams", [2048, 2049])
+def test_gpu_form_boundary_through_every_entry_point(n_streams):
+    """2048 streams of 1024 symbols is the last size of the self-scanning form, 2049 the first of the scan form (parse, scan,
+    streams, finish).  On both sides of it the asynchronous encoder writes the oracle's bytes, the asynchronous decoder and the
+    synchronous single-container decoder — a batch of one through the same launches — round-trip, and a hostile length-table
+    entry is SICN_EINVAL from the synchronous decoder."""
+    import torch
+    from simple_image_compression_network_amd import _lib, codec
+    shape = (1, 2048 * 1024 + (n_streams - 2048), 1)
+    lat = _mock_latent(np.random.default_rng(n_streams), shape)
+    dev = torch.from_numpy(lat).cuda()
+    coder = codec.LatentCoder(1, *shape, stream_symbols=1024)
+    coder.encode(dev[None])
+    back = torch.empty_like(dev[None])
+    coder.decode(back)
+    coder.check()
+    assert torch.equal(back[0], dev)
+    blob = coder.slots[0, :coder.sizes()[0]].clone()
+    assert blob.cpu().numpy().tobytes() == c_oracle.codec_encode(lat, (0, 0), 3, stream_symbols=1024)
+    got, info = codec.decode_latent(blob)
+    assert int(info.n_streams) == n_streams and int(info.stream_symbols) == 1024 and torch.equal(got, dev)
+    bad = blob.clone()
+    bad[48 + 256 + 4 * (n_streams - 3) + 2] ^= 0x7F         # one length entry far above the cap of 2304 bytes
+    with pytest.raises(_lib.SicnError) as e:
+        codec.decode_latent(bad)
+    assert e.value.code == -22
+
+
+@gpu
+@pytest.mark.parametrize("shape", [(1, 1, 65), (9, 10, 192), (0, 4, 4)])
+def test_gpu_sync_encode_equals_oracle_and_async_pair(shape):
+    """codec.encode_latent in mode 3 is the asynchronous encoder with one image at the default stream length: the oracle's bytes
+    and LatentCoder's, byte for byte (one short stream, two streams, the empty latent); a symbol >= 128 is SICN_EINVAL."""
+    import torch
+    from simple_image_compression_network_amd import _lib, codec
+    lat = _mock_latent(np.random.default_rng(7 + sum(shape)), shape)
+    dev = torch.from_numpy(lat).cuda()
+    wh = (shape[1] * 16, shape[0] * 16)
+    blob = codec.encode_latent(dev, *wh, codec.RANSW).cpu().numpy().tobytes()
+    assert blob == c_oracle.codec_encode(lat, wh, 3)
+    coder = codec.LatentCoder(1, *shape, image_width=wh[0], image_height=wh[1], stream_symbols=16384)
+    coder.encode(dev[None])
+    coder.check()
+    assert blob == coder.slots[0, :coder.sizes()[0]].cpu().numpy().tobytes()
+    if lat.size == 0:
+        assert len(blob) == 304
+        return
+    bad = dev.clone()
+    bad.view(-1)[lat.size // 2] = 200
+    with pytest.raises(_lib.SicnError) as e:
+        codec.encode_latent(bad, *wh, codec.RANSW)
+    assert e.value.code == -22
+
+
+@gpu
 def test_gpu_async_reports_errors_in_device_status():
     import torch
     from simple_image_compression_network_amd import _lib, codec

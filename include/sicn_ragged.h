@@ -16,6 +16,16 @@
  * uploads once, at creation.  A layer these kernels do not serve (sicn_kernel_for's width rules: IFM_CH % 32 == 0 and
  * OFM_CH % 16 == 0, both <= 1024, conv 3 -> N, deconv N -> 3) is SICN_EINVAL: the ragged net has no other kernel to fall back on.
  *
+ * Activations (library 0.8, sicn_version() >= 8; declared in sicn_ragged_hyper.h).  sicn_ragged_net_create_gdn gives layer i the
+ * GDN / IGDN of sicn_gdn.h in place of the reference ReLU: the layer kernel stores its pre-activation lanes and the activation
+ * rewrites the whole boundary tensor in place, [tensor bytes / OFM_CH positions][OFM_CH] — a ragged tensor is exactly what
+ * sicn_gdn_apply takes, so the image tables play no part.  Two launches for such a layer (one more per 2 GiB of tensor), for the
+ * whole batch; the bytes are sicn_net_create_gdn's on every image alone.
+ *
+ * Crop (library 0.8, sicn_ragged_hyper.h).  The chain rule rounds up: a deconv doubles what a conv halved towards the ceiling, so
+ * h_s(z) of the hyperprior is 4 * ceil(./4) per image and a reconstruction 16 * ceil(./16).  sicn_ragged_crop_* cuts every image of
+ * a ragged tensor to its top-left [dst_h][dst_w][C], one launch for the batch, into another ragged tensor.
+ *
  * Limits (SICN_EINVAL): n_images < 1, a width or height < 1 or > 2^20, one image's tensor at any boundary >= 2^31 bytes, a layer
  * with >= 2^31 - 1 work items.  The whole ragged tensor may exceed 2 GiB: offsets are 64-bit.  SICN_ENODEV off gfx950.
  */

@@ -133,6 +133,15 @@ RAGGED_ABI = {
     "sicn_ragged_net_workspace_bytes": (_sz, [_vp]),
     "sicn_ragged_net_forward": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _vp, _sz, _vp]),
 }
+# include/sicn_ragged_hyper.h (library 0.8: GDN / IGDN layers in a ragged net, and the crop of every image of a ragged tensor in one launch)
+RAGGED_HYPER_ABI = {
+    "sicn_ragged_net_create_gdn": (_i, [_descp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _i, _i32p, _i32p, _i, ctypes.POINTER(_vp)]),
+    "sicn_ragged_crop_layout": (_i, [_i32p, _i32p, _i32p, _i32p, _i, _i, _i, _i64p]),
+    "sicn_ragged_crop_create": (_i, [_i32p, _i32p, _i32p, _i32p, _i, _i, ctypes.POINTER(_vp)]),
+    "sicn_ragged_crop_free": (None, [_vp]),
+    "sicn_ragged_crop_run": (_i, [_vp, _vp, _vp, _vp]),
+}
+RAGGED_CROP_ROWS = 8      # SICN_RAGGED_CROP_ROWS: destination rows of one work item of the crop
 
 
 
@@ -178,7 +187,7 @@ def lib() -> ctypes.CDLL:
         except ImportError:      # symbol checks etc. work without it
             pass
         L = ctypes.CDLL(str(LIB_PATH))
-        for name, (res, args) in {**ABI, **CODEC_ABI, **CONVLAYER_ABI, **GDN_ABI, **RAGGED_ABI, **RAGGED_CODEC_ABI}.items():
+        for name, (res, args) in {**ABI, **CODEC_ABI, **CONVLAYER_ABI, **GDN_ABI, **RAGGED_ABI, **RAGGED_HYPER_ABI, **RAGGED_CODEC_ABI}.items():
             fn = getattr(L, name)          # AttributeError if the ABI is incomplete
             fn.restype = res
             fn.argtypes = args

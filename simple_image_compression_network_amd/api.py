@@ -27,7 +27,7 @@ from . import _lib
 from .config import CLayerDesc, LayerDesc, REFERENCE_DESCS, eight_layer_descs
 
 __all__ = ["FixedPointWeights", "DeviceWeights", "conv2d", "deconv522", "conv2d_layer0", "deconv2d_layer4",
-           "eight_layers_net", "EightLayersNet", "RaggedNet", "load_param_weights", "PARAM", "GDN"]
+           "eight_layers_net", "EightLayersNet", "RaggedNet", "RaggedCrop", "load_param_weights", "PARAM", "GDN"]
 
 _DATA = Path(__file__).resolve().parent / "data" / "param_weights.npz"
 
@@ -343,19 +343,83 @@ class EightLayersNet:
         return list(ms), list(cnt)
 
 
+class RaggedCrop:
+    """Every image of a ragged tensor cut to its top-left corner, ONE launch for the batch (sicn_ragged_crop_*, include/sicn_ragged.h).
+    src_shapes / dst_shapes: [(h, w)] per image, dst no larger than src; both tensors are flat uint8 CUDA tensors, the images'
+    [h][w][channels] arrays back to back.  What the chain rule rounds up is cut back with it: h_s(z) to the latent's shape, a
+    reconstruction to the image's size."""
+
+    def __init__(self, src_shapes, dst_shapes, channels: int, device=None):
+        import torch
+        L = _lib.lib()
+        self.src_shapes = [(int(h), int(w)) for h, w in src_shapes]
+        self.dst_shapes = [(int(h), int(w)) for h, w in dst_shapes]
+        self.channels = int(channels)
+        n = len(self.src_shapes)
+        if len(self.dst_shapes) != n:
+            raise ValueError("dst_shapes: one (h, w) per source shape")
+        i32 = ctypes.c_int32 * max(n, 1)
+        sw, sh = i32(*[w for _, w in self.src_shapes]), i32(*[h for h, _ in self.src_shapes])
+        dw, dh = i32(*[w for _, w in self.dst_shapes]), i32(*[h for h, _ in self.dst_shapes])
+        self.device = torch.device(device if device is not None else "cuda")
+        self._h = ctypes.c_void_p()
+        with torch.cuda.device(self.device):
+            _lib.check(L.sicn_ragged_crop_create(sw, sh, dw, dh, self.channels, n, ctypes.byref(self._h)), "sicn_ragged_crop_create")
+        self._src_off, self._dst_off = [], []
+        q = (ctypes.c_int64 * 4)()
+        for i in range(n):
+            _lib.check(L.sicn_ragged_crop_layout(sw, sh, dw, dh, self.channels, n, i, q), "sicn_ragged_crop_layout")
+            self._src_off.append(int(q[0]))
+            self._dst_off.append(int(q[1]))
+        self.src_bytes, self.dst_bytes = int(q[2]), int(q[3])
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None) and _lib._lib is not None:
+                _lib._lib.sicn_ragged_crop_free(self._h)
+                self._h = None
+        except Exception:       # interpreter shutdown
+            pass
+
+    def views(self, packed, which: str = "dst"):
+        """Per-image [h][w][channels] views of a destination (which="dst") or source (which="src") tensor (no copy)."""
+        shapes, offs, nbytes = ((self.dst_shapes, self._dst_off, self.dst_bytes) if which == "dst" else
+                                (self.src_shapes, self._src_off, self.src_bytes))
+        _check_tensor(packed, (nbytes,), which)
+        c = self.channels
+        return [packed[o:o + h * w * c].view(h, w, c) for o, (h, w) in zip(offs, shapes)]
+
+    def run(self, src, dst=None, stream=None):
+        """src (ragged, source shapes) -> dst (ragged, destination shapes; allocated when None).  Enqueue only."""
+        import torch
+        _check_tensor(src, (self.src_bytes,), "src")
+        if dst is None:
+            dst = torch.empty(self.dst_bytes, dtype=torch.uint8, device=src.device)
+        _check_tensor(dst, (self.dst_bytes,), "dst")
+        _lib.check(_lib.lib().sicn_ragged_crop_run(self._h, ctypes.c_void_p(src.data_ptr()), ctypes.c_void_p(dst.data_ptr()),
+                                                   _stream_ptr(stream)), "sicn_ragged_crop_run")
+        return dst
+
+
 class RaggedNet:
-    """The 8-layer chain over images of DIFFERENT sizes, one kernel launch per layer for the whole batch (include/sicn_ragged.h).
-    `sizes`: [(width, height)] per image.  A ragged tensor is a flat uint8 CUDA tensor: the images' [H][W][C] arrays back to back;
-    `layer` -1 names the input, l the output of layer l.  Same bytes as `EightLayersNet(w, h).forward` of every image alone."""
+    """A layer chain over images of DIFFERENT sizes, one kernel launch per layer for the whole batch (include/sicn_ragged.h); by
+    default the 8-layer chain.  `sizes`: [(width, height)] per image at the chain's input.  A ragged tensor is a flat uint8 CUDA
+    tensor: the images' [H][W][C] arrays back to back; `layer` -1 names the input, l the output of layer l.  Same bytes as
+    `EightLayersNet(w, h).forward` of every image alone.
+    `descs`: any chain the ragged kernels serve instead of the eight layers (its spatial fields are ignored; `params` or
+    `shared_weights` must match it, as in `EightLayersNet(descs=...)`).  `gdn`: a list of `GDN | None`, one per layer — the
+    activation in place of that layer's ReLU (sicn_ragged_net_create_gdn); one more launch per such layer, for the whole batch."""
 
     def __init__(self, sizes, params=None, device=None, n_ch: int = 128, m_ch: int = 192,
-                 shared_weights: Optional[Sequence[DeviceWeights]] = None):
+                 shared_weights: Optional[Sequence[DeviceWeights]] = None, descs: Optional[Sequence[LayerDesc]] = None,
+                 gdn: Optional[Sequence[Optional["GDN"]]] = None):
         import torch
         L = _lib.lib()
         self.sizes = [(int(w), int(h)) for w, h in sizes]
         n_img = len(self.sizes)
         w0, h0 = self.sizes[0] if self.sizes else (1, 1)
-        self.descs: List[LayerDesc] = eight_layer_descs(max(w0, 1), max(h0, 1), n_ch, m_ch)    # the library ignores their spatial fields
+        # the library ignores the descriptors' spatial fields
+        self.descs: List[LayerDesc] = list(descs) if descs is not None else eight_layer_descs(max(w0, 1), max(h0, 1), n_ch, m_ch)
         self.device = torch.device(device if device is not None else "cuda")
         if shared_weights is not None:
             self.weights = list(shared_weights)
@@ -369,9 +433,17 @@ class RaggedNet:
         self._heights = (ctypes.c_int32 * max(n_img, 1))(*[h for _, h in self.sizes])
         handles = (ctypes.c_void_p * n)(*[w.handle for w in self.weights])
         self._h = ctypes.c_void_p()
+        self.gdn = list(gdn) if gdn is not None else None      # keeps the activations alive
+        if self.gdn is not None and len(self.gdn) != n:
+            raise ValueError("gdn must have one entry (or None) per layer")
         with torch.cuda.device(self.device):
-            _lib.check(L.sicn_ragged_net_create(self._cdescs, handles, n, self._widths, self._heights, n_img, ctypes.byref(self._h)),
-                       "sicn_ragged_net_create")
+            if self.gdn is not None:
+                ghandles = (ctypes.c_void_p * n)(*[(g.handle if g is not None else None) for g in self.gdn])
+                _lib.check(L.sicn_ragged_net_create_gdn(self._cdescs, handles, ghandles, n, self._widths, self._heights, n_img,
+                                                        ctypes.byref(self._h)), "sicn_ragged_net_create_gdn")
+            else:
+                _lib.check(L.sicn_ragged_net_create(self._cdescs, handles, n, self._widths, self._heights, n_img, ctypes.byref(self._h)),
+                           "sicn_ragged_net_create")
         # per boundary (-1 .. n - 1, index layer + 1): the images' shapes and byte offsets, as the library lays them out
         self._shapes, self._offsets, self._nbytes = [], [], []
         q = (ctypes.c_int64 * 8)()
@@ -386,6 +458,7 @@ class RaggedNet:
             self._nbytes.append(int(q[4]))
         self._ws = None
         self._coders = {}           # compress()'s RaggedLatentCoders by stream length, made on first use
+        self._crop = None           # cropped()'s RaggedCrop, made on first use
 
     def __del__(self):
         try:
@@ -455,6 +528,22 @@ class RaggedNet:
         """All layers; returns (reconstructions, latents) as ragged tensors (the latent is layer 3's output)."""
         n = len(self.descs)
         return self.run_layers(0, n - 1, packed_in, tap_layer=3 if n > 3 else -1, out=out, tap=latent, stream=stream)
+
+    def cropped(self, out, dst=None, stream=None):
+        """The chain's last output (boundary n - 1, every size rounded up by the chain rule: 112 x 48 for a 100 x 36 image) cut to the
+        images' own sizes: a ragged tensor laid out as boundary -1 with the output's channels.  One launch.  Needs a chain that
+        ends no smaller than it began (the eight layers do)."""
+        last = len(self.descs) - 1
+        if self._crop is None:
+            self._crop = RaggedCrop([(h, w) for h, w, _ in self.shapes(last)], [(h, w) for w, h in self.sizes],
+                                    self.shapes(last)[0][2], device=self.device)
+        return self._crop.run(out, dst, stream=stream)
+
+    def crop_views(self, cropped):
+        """Per-image [height][width][C] views of what `cropped` returned."""
+        if self._crop is None:
+            raise ValueError("cropped() has not run")
+        return self._crop.views(cropped)
 
     def latent_coder(self, stream_symbols=None):
         """A codec.RaggedLatentCoder for this net's latents (boundary 3) and image sizes: the whole batch in 3 + 2 launches."""

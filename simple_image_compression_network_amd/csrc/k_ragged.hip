@@ -1,4 +1,4 @@
-// Ragged batches (include/sicn_ragged.h): the channel-generic MFMA kernels of k_mfma16c.hip over n images of n different sizes,
+// Ragged batches (include/sicn_ragged.h, _hyper.h): the channel-generic MFMA kernels of k_mfma16c.hip over n images of n different sizes,
 // one launch per layer for the whole batch.  The tile body is any_tile() (k_any_body.hpp), the weight image is pack_any()'s; what
 // is new is how a workgroup finds its image.
 //
@@ -8,11 +8,16 @@
 //   rows[image]       : { IW, IH, OW, OH, tiles_x, first_item, in_off, out_off }, the image's sizes in this layer, its first work item
 //                       and its 64-bit byte offsets in the layer's input and output tensors
 // Both loads are wave-uniform (they depend on blockIdx.x only) and stay in scalar registers.
+//
+// A layer with a GDN / IGDN (sicn_ragged_net_create_gdn) runs the same kernel with ACT_FLOOR_RAW and then the activation of k_gdn.hip in
+// place over the whole boundary tensor: [bytes / OFM_CH][OFM_CH], no table needed.  The ragged crop at the end of this file follows the
+// same pattern as k_any_ragged with a work item of CROP_ROWS destination rows of one image.
 #include <new>
 #include <vector>
 
-#include "../../include/sicn_ragged.h"
+#include "../../include/sicn_ragged_hyper.h"
 #include "k_any_body.hpp"
+#include "sicn_gdn_internal.h"
 #include "sicn_weights_io.h"
 
 namespace sicn {
@@ -122,7 +127,7 @@ static int ragged_plan(const sicn_layer_desc *descs, int n_layers, const int32_t
 
 template <bool DECONV, int NT>
 static hipError_t launch_ragged_as(const uint8_t *in, uint8_t *out, const int8_t *wimg, const int8_t *bias, const RaggedRow *rows,
-                                   const uint32_t *tile_image, int cin, int cout, unsigned items, hipStream_t stream)
+                                   const uint32_t *tile_image, int cin, int cout, unsigned items, uint32_t floor2, hipStream_t stream)
 {
     const size_t lds = any_lds_bytes(DECONV);
     if (lds > 64 * 1024) {
@@ -130,8 +135,90 @@ static hipError_t launch_ragged_as(const uint8_t *in, uint8_t *out, const int8_t
         if (e != hipSuccess) return e;
     }
     hipLaunchKernelGGL((k_any_ragged<DECONV, NT>), dim3(items, (unsigned)((cout + 63) / 64), 1), dim3(256), lds, stream, in, out, wimg, bias,
-                       rows, tile_image, cin, cout, ACT_FLOOR_RELU);
+                       rows, tile_image, cin, cout, floor2);
     return hipGetLastError();
+}
+
+// ---- ragged crop: dst image i = the top-left [dst_h][dst_w][C] of src image i -----------------------------------------------------------
+// Grid: x = work items over all images, a work item = CROP_ROWS destination rows of one image (the image's last item: the rest).
+//   item_image[item] : the image of an item
+//   rows[image]      : { source / destination row bytes, destination rows, first item, vec, 64-bit offsets in src and dst }
+// As in k_any_ragged both loads depend on blockIdx.x only.  `vec` (per image, host-made): both row lengths and both offsets are
+// multiples of 16; `ptr16` (per launch): so are both base pointers.  Then a row is copied as uint4, otherwise byte by byte.
+constexpr int CROP_ROWS = SICN_RAGGED_CROP_ROWS;
+
+struct CropRow {
+    uint32_t src_row, dst_row, dst_h, first_item, vec, pad;
+    int64_t src_off, dst_off;
+};
+
+__global__ __launch_bounds__(256) void k_ragged_crop(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, const CropRow *__restrict__ rows,
+                                                     const uint32_t *__restrict__ item_image, int ptr16)
+{
+    const uint32_t item = blockIdx.x;
+    const int img = __builtin_amdgcn_readfirstlane((int)item_image[item]);
+    const CropRow *row = rows + img;
+    const uint32_t src_row = (uint32_t)__builtin_amdgcn_readfirstlane((int)row->src_row);
+    const uint32_t dst_row = (uint32_t)__builtin_amdgcn_readfirstlane((int)row->dst_row);
+    const uint32_t dst_h = (uint32_t)__builtin_amdgcn_readfirstlane((int)row->dst_h);
+    const uint32_t y0 = (item - (uint32_t)__builtin_amdgcn_readfirstlane((int)row->first_item)) * (uint32_t)CROP_ROWS;
+    const int vec = __builtin_amdgcn_readfirstlane((int)row->vec) & ptr16;
+    const uint64_t src_off = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)row->src_off) |
+                             (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(row->src_off >> 32)) << 32;
+    const uint64_t dst_off = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)row->dst_off) |
+                             (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(row->dst_off >> 32)) << 32;
+    if (y0 >= dst_h) return;                                  // cannot happen with the host's tables
+    const uint32_t n_rows = dst_h - y0 < (uint32_t)CROP_ROWS ? dst_h - y0 : (uint32_t)CROP_ROWS;
+    // one image's tensor is < 2^31 bytes (host check), so every index below fits 32 bits
+    const uint8_t *s = src + src_off + (size_t)y0 * src_row;
+    uint8_t *d = dst + dst_off + (size_t)y0 * dst_row;
+    if (vec) {
+        const uint32_t q_row = dst_row / 16, total = n_rows * q_row;
+        for (uint32_t i = threadIdx.x; i < total; i += 256) {
+            const uint32_t r = i / q_row, q = i - r * q_row;
+            reinterpret_cast<uint4 *>(d + (size_t)r * dst_row)[q] = reinterpret_cast<const uint4 *>(s + (size_t)r * src_row)[q];
+        }
+    } else {
+        const uint32_t total = n_rows * dst_row;
+        for (uint32_t i = threadIdx.x; i < total; i += 256) {
+            const uint32_t r = i / dst_row, b = i - r * dst_row;
+            d[(size_t)r * dst_row + b] = s[(size_t)r * src_row + b];
+        }
+    }
+}
+
+struct CropPlan {
+    std::vector<CropRow> rows;              // [n_images]
+    std::vector<int64_t> first_item;        // [n_images + 1]
+    int64_t src_bytes = 0, dst_bytes = 0;
+};
+
+static int crop_plan(const int32_t *src_w, const int32_t *src_h, const int32_t *dst_w, const int32_t *dst_h, int channels, int n_images,
+                     CropPlan *plan)
+{
+    if (!src_w || !src_h || !dst_w || !dst_h || n_images < 1 || channels < 1) return SICN_EINVAL;
+    for (int i = 0; i < n_images; i++) {
+        if (dst_w[i] < 1 || dst_h[i] < 1 || src_w[i] > (1 << 20) || src_h[i] > (1 << 20)) return SICN_EINVAL;
+        if (dst_w[i] > src_w[i] || dst_h[i] > src_h[i]) return SICN_EINVAL;
+        if ((double)src_h[i] * src_w[i] * channels >= (double)OOB) return SICN_EINVAL;   // before the 64-bit product can overflow
+    }
+    try {
+        plan->rows.resize((size_t)n_images);
+        plan->first_item.assign((size_t)n_images + 1, 0);
+        int64_t so = 0, dof = 0;
+        for (int i = 0; i < n_images; i++) {
+            const int64_t srow = (int64_t)src_w[i] * channels, drow = (int64_t)dst_w[i] * channels;
+            const uint32_t vec = ((srow | drow | so | dof) & 15) == 0;
+            plan->rows[(size_t)i] = CropRow{(uint32_t)srow, (uint32_t)drow, (uint32_t)dst_h[i], (uint32_t)plan->first_item[(size_t)i], vec, 0u, so, dof};
+            plan->first_item[(size_t)i + 1] = plan->first_item[(size_t)i] + (dst_h[i] + CROP_ROWS - 1) / CROP_ROWS;
+            if (plan->first_item[(size_t)i + 1] >= RAGGED_MAX_ITEMS) return SICN_EINVAL;
+            so += srow * src_h[i];
+            dof += drow * dst_h[i];
+        }
+        plan->src_bytes = so;
+        plan->dst_bytes = dof;
+    } catch (const std::bad_alloc &) { return SICN_ENOMEM; }
+    return SICN_OK;
 }
 
 }  // namespace sicn
@@ -143,6 +230,7 @@ struct sicn_ragged_net {
     RaggedPlan plan;
     std::vector<sicn_layer_desc> descs;
     std::vector<const sicn_weights *> weights;
+    std::vector<const sicn_gdn *> gdn;      // per layer: the activation in place of the ReLU, or nullptr
     std::vector<const int8_t *> wimg;       // per layer: the weights' own pack_any image, or one of `owned`
     std::vector<int8_t *> owned;            // images packed here for weights whose family is another one (the reference's widths)
     RaggedRow *d_rows = nullptr;            // [n_layers][n_images]
@@ -186,6 +274,12 @@ extern "C" void sicn_ragged_net_free(sicn_ragged_net *net)
 extern "C" int sicn_ragged_net_create(const sicn_layer_desc *descs, sicn_weights *const *weights, int n_layers, const int32_t *widths,
                                       const int32_t *heights, int n_images, sicn_ragged_net **out)
 {
+    return sicn_ragged_net_create_gdn(descs, weights, nullptr, n_layers, widths, heights, n_images, out);
+}
+
+extern "C" int sicn_ragged_net_create_gdn(const sicn_layer_desc *descs, sicn_weights *const *weights, const sicn_gdn *const *gdn, int n_layers,
+                                          const int32_t *widths, const int32_t *heights, int n_images, sicn_ragged_net **out)
+{
     if (!out) return SICN_EINVAL;
     *out = nullptr;
     if (!weights) return SICN_EINVAL;
@@ -195,6 +289,7 @@ extern "C" int sicn_ragged_net_create(const sicn_layer_desc *descs, sicn_weights
     for (int l = 0; !rc && l < n_layers; l++) {
         const sicn_weights *w = weights[l];
         if (!w || w->cin != descs[l].IFM_CH || w->cout != descs[l].OFM_CH || w->transposed != descs[l].transposed) rc = SICN_EINVAL;
+        if (gdn && gdn[l] && gdn[l]->channels != descs[l].OFM_CH) rc = SICN_EINVAL;
     }
     if (!rc) rc = chip_geom(nullptr);       // no device, or not a gfx950 one
     if (!rc) try {
@@ -202,6 +297,8 @@ extern "C" int sicn_ragged_net_create(const sicn_layer_desc *descs, sicn_weights
         net->n_images = n_images;
         net->descs.assign(descs, descs + n_layers);
         net->weights.assign(weights, weights + n_layers);
+        net->gdn.assign((size_t)n_layers, nullptr);
+        if (gdn) net->gdn.assign(gdn, gdn + n_layers);
         // the tables: one row per (layer, image), one tile -> image entry per tile
         std::vector<RaggedRow> rows((size_t)n_layers * n_images);
         std::vector<uint32_t> map;
@@ -273,18 +370,91 @@ extern "C" int sicn_ragged_net_forward(const sicn_ragged_net *net, int first, in
         const uint32_t *map = net->d_tile_image + net->map_at[(size_t)l];
         const unsigned items = (unsigned)net->plan.layers[(size_t)l].first_item[(size_t)net->n_images];
         const int8_t *wimg = net->wimg[(size_t)l];
+        const sicn_gdn *g = net->gdn[(size_t)l];
+        const uint32_t floor2 = g ? ACT_FLOOR_RAW : ACT_FLOOR_RELU;
+        const size_t out_bytes = (size_t)net->plan.bounds[(size_t)l + 1].off[(size_t)net->n_images];
         hipError_t e;
         if (d.transposed)
-            e = d.OFM_CH == 3 ? launch_ragged_as<true, 1>(cur, dst, wimg, w->d_bias, rows, map, d.IFM_CH, d.OFM_CH, items, stream)
-                              : launch_ragged_as<true, 4>(cur, dst, wimg, w->d_bias, rows, map, d.IFM_CH, d.OFM_CH, items, stream);
+            e = d.OFM_CH == 3 ? launch_ragged_as<true, 1>(cur, dst, wimg, w->d_bias, rows, map, d.IFM_CH, d.OFM_CH, items, floor2, stream)
+                              : launch_ragged_as<true, 4>(cur, dst, wimg, w->d_bias, rows, map, d.IFM_CH, d.OFM_CH, items, floor2, stream);
         else
-            e = launch_ragged_as<false, 4>(cur, dst, wimg, w->d_bias, rows, map, d.IFM_CH, d.OFM_CH, items, stream);
+            e = launch_ragged_as<false, 4>(cur, dst, wimg, w->d_bias, rows, map, d.IFM_CH, d.OFM_CH, items, floor2, stream);
         if (e != hipSuccess) return SICN_ENODEV;
+        // the activation, in place wherever the layer wrote: the ragged tensor is [positions of all images][OFM_CH]
+        if (g)
+            if (int rc = gdn_apply_lanes(*g, dst, (long long)(out_bytes / (size_t)d.OFM_CH), stream)) return rc;
         if (l == tap_layer && tap_out != dst) {
-            const size_t bytes = (size_t)net->plan.bounds[(size_t)l + 1].off[(size_t)net->n_images];
-            if (hipMemcpyAsync(tap_out, dst, bytes, hipMemcpyDeviceToDevice, stream) != hipSuccess) return SICN_ENODEV;
+            if (hipMemcpyAsync(tap_out, dst, out_bytes, hipMemcpyDeviceToDevice, stream) != hipSuccess) return SICN_ENODEV;
         }
         cur = dst;
     }
     return SICN_OK;
+}
+
+// ---- ragged crop --------------------------------------------------------------------------------------------------------------------
+struct sicn_ragged_crop {
+    int n_images = 0;
+    unsigned items = 0;
+    CropRow *d_rows = nullptr;              // [n_images]
+    uint32_t *d_item_image = nullptr;       // [items]
+};
+
+extern "C" int sicn_ragged_crop_layout(const int32_t *src_w, const int32_t *src_h, const int32_t *dst_w, const int32_t *dst_h, int channels,
+                                       int n_images, int image, int64_t out[4])
+{
+    if (!out) return SICN_EINVAL;
+    CropPlan p;
+    if (int rc = crop_plan(src_w, src_h, dst_w, dst_h, channels, n_images, &p)) return rc;
+    if (image < 0 || image >= n_images) return SICN_EINVAL;
+    out[0] = p.rows[(size_t)image].src_off;
+    out[1] = p.rows[(size_t)image].dst_off;
+    out[2] = p.src_bytes;
+    out[3] = p.dst_bytes;
+    return SICN_OK;
+}
+
+extern "C" void sicn_ragged_crop_free(sicn_ragged_crop *crop)
+{
+    if (!crop) return;
+    if (crop->d_rows) (void)hipFree(crop->d_rows);
+    if (crop->d_item_image) (void)hipFree(crop->d_item_image);
+    delete crop;
+}
+
+extern "C" int sicn_ragged_crop_create(const int32_t *src_w, const int32_t *src_h, const int32_t *dst_w, const int32_t *dst_h, int channels,
+                                       int n_images, sicn_ragged_crop **out)
+{
+    if (!out) return SICN_EINVAL;
+    *out = nullptr;
+    CropPlan p;
+    if (int rc = crop_plan(src_w, src_h, dst_w, dst_h, channels, n_images, &p)) return rc;
+    if (int rc = chip_geom(nullptr)) return rc;      // no device, or not a gfx950 one
+    sicn_ragged_crop *crop = new (std::nothrow) sicn_ragged_crop();
+    if (!crop) return SICN_ENOMEM;
+    int rc = SICN_OK;
+    try {
+        crop->n_images = n_images;
+        crop->items = (unsigned)p.first_item[(size_t)n_images];
+        std::vector<uint32_t> map;
+        map.reserve((size_t)crop->items);
+        for (int i = 0; i < n_images; i++) map.insert(map.end(), (size_t)(p.first_item[(size_t)i + 1] - p.first_item[(size_t)i]), (uint32_t)i);
+        if (!upload(p.rows.data(), p.rows.size() * sizeof(CropRow), &crop->d_rows) ||
+            !upload(map.data(), map.size() * sizeof(uint32_t), &crop->d_item_image))
+            rc = SICN_ENOMEM;
+    } catch (const std::bad_alloc &) { rc = SICN_ENOMEM; }
+    if (rc) {
+        sicn_ragged_crop_free(crop);
+        return rc;
+    }
+    *out = crop;
+    return SICN_OK;
+}
+
+extern "C" int sicn_ragged_crop_run(const sicn_ragged_crop *crop, const uint8_t *src, uint8_t *dst, void *hip_stream)
+{
+    if (!crop || !src || !dst) return SICN_EINVAL;
+    if (int rc = chip_geom(nullptr)) return rc;
+    const int ptr16 = ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0;
+    hipLaunchKernelGGL(k_ragged_crop, dim3(crop->items), dim3(256), 0, (hipStream_t)hip_stream, src, dst, crop->d_rows, crop->d_item_image, ptr16);
+    return hipGetLastError() == hipSuccess ? SICN_OK : SICN_ENODEV;
 }

@@ -132,7 +132,7 @@ extern "C" void sicn_options_init(sicn_options *opt)
 // 0.7: ragged latent coder (include/sicn_ragged_codec.h, k_ragged_codec.hip).  Still 0.7 (no symbol, struct or byte changed): the
 // synchronous rANS-W calls are the asynchronous pair with one image, so sicn_codec_workspace_bytes(SICN_CODEC_RANSW, n) also holds
 // that pair's status words (it grew by less than 1 KiB) and sicn_codec_decode needs sicn_codec_batch_workspace_bytes_sl(n, 1, length)
-extern "C" int sicn_version(void) { return 1000 * 0 + 7; }
+extern "C" int sicn_version(void) { return 1000 * 0 + 8; }
 extern "C" int sicn_gdn_spec_version(void) { return 2; }
 
 extern "C" int sicn_has_alt_kernels(void) { return 0; }   // kept for callers that probe it: the alternate kernel build is gone
@@ -787,19 +787,25 @@ extern "C" int sicn_gdn_create(int channels, int inverse, int shift, const uint3
     return SICN_OK;
 }
 
-extern "C" int sicn_gdn_apply(const sicn_gdn *g, uint8_t *lanes, long long n_positions, void *hip_stream)
+namespace sicn {
+int gdn_apply_lanes(const sicn_gdn &g, uint8_t *lanes, long long n_positions, hipStream_t stream)
 {
-    if (!g || n_positions < 0 || (n_positions && !lanes)) return SICN_EINVAL;
-    hipStream_t stream = (hipStream_t)hip_stream;
     // chunks of < 2 GiB (the kernel addresses a chunk through one buffer descriptor with 31-bit offsets)
-    const long long chunk = ((1LL << 31) - 4096) / g->channels;
+    const long long chunk = ((1LL << 31) - 4096) / g.channels;
     for (long long p = 0; p < n_positions; p += chunk) {
         const long long n = n_positions - p < chunk ? n_positions - p : chunk;
-        hipError_t e = launch_gdn(*g, lanes + (size_t)p * g->channels, 0 /* NHWC */, (int)n, 1, 1, stream);
+        hipError_t e = launch_gdn(g, lanes + (size_t)p * g.channels, 0 /* NHWC */, (int)n, 1, 1, stream);
         if (e == hipErrorInvalidValue) return SICN_EINVAL;
         if (e != hipSuccess) return SICN_ENODEV;
     }
     return SICN_OK;
+}
+}  // namespace sicn
+
+extern "C" int sicn_gdn_apply(const sicn_gdn *g, uint8_t *lanes, long long n_positions, void *hip_stream)
+{
+    if (!g || n_positions < 0 || (n_positions && !lanes)) return SICN_EINVAL;
+    return gdn_apply_lanes(*g, lanes, n_positions, (hipStream_t)hip_stream);
 }
 
 extern "C" int sicn_conv2d_gdn(const sicn_layer_desc *d, const sicn_weights *w, const sicn_gdn *gdn, const uint8_t *in,

@@ -30,7 +30,7 @@ import numpy as np
 from . import api, codec
 from .config import LayerDesc
 
-__all__ = ["HyperpriorCodec", "random_gdn_params", "random_layer_params", "hyper_descs", "hyper_parameters"]
+__all__ = ["HyperpriorCodec", "RaggedHyperpriorCodec", "random_gdn_params", "random_layer_params", "hyper_descs", "hyper_parameters"]
 
 
 def random_gdn_params(rng, channels: int):
@@ -162,3 +162,139 @@ class HyperpriorCodec:
 
     def bytes_per_image(self):
         return [a + b for a, b in zip(self.z_coder.sizes(), self.y_coder.sizes())]
+
+
+class RaggedHyperpriorCodec:
+    """The same configuration over n images of n DIFFERENT sizes (`sizes`: [(width, height)]), every stage but the y coder one set of
+    launches for the whole batch (include/sicn_ragged.h, sicn_ragged_codec.h):
+
+        main, h_a, h_s : api.RaggedNet (GDN / IGDN layers: the layer kernel, then the activation over the whole boundary tensor)
+        z bitstream     : codec.RaggedLatentCoder, 3 launches to encode and 2 to decode
+        scale map       : api.RaggedCrop cuts h_s(z), 4 * ceil(./4) per image, to every latent's own shape in one launch
+        y bitstream     : one codec.ContextCoder(1, ...) PER IMAGE, fed that image's slice of the ragged y, s and y_hat (a slice is a plain
+                          contiguous NHWC array); a ragged form of rANS-WC does not exist yet
+
+    Image i's containers are `HyperpriorCodec(w_i, h_i, 1, seed)`'s, byte for byte: hyper_parameters draws depend on channel counts
+    only, so every image gets that codec's parameters.  Stage tensors (y, z, z_hat, s, y_hat) are ragged tensors; `main.views(3, y)`,
+    `h_a.views(1, z)` give the per-image arrays.  Parity UNPINNED, as everything in this module."""
+
+    def __init__(self, sizes, seed: int = 0, device="cuda", use_gdn: bool = True, main_params=None, z_stream_symbols=None):
+        import torch
+        self.sizes = [(int(w), int(h)) for w, h in sizes]
+        if not self.sizes:
+            raise ValueError("no images")
+        self.device = torch.device(device)
+        hp = hyper_parameters(*self.sizes[0], seed, use_gdn)
+        self.gdn_np = hp["gdn_np"]
+        with torch.cuda.device(self.device):
+            gdn = [None if g is None else api.GDN(g[0], g[1], inverse=g[2], shift=g[3]) for g in self.gdn_np]
+        self.main = api.RaggedNet(self.sizes, params=main_params, device=self.device, gdn=gdn if use_gdn else None)
+        self.ha_np, self.hs_np = hp["ha_np"], hp["hs_np"]
+        lat = self.main.shapes(3)                                           # [(h, w, 192)]
+        self.h_a = api.RaggedNet([(w, h) for h, w, _ in lat], params=list(hp["pa"]), device=self.device, descs=hp["da"])
+        hyp = self.h_a.shapes(1)                                            # [(h, w, 128)]
+        self.h_s = api.RaggedNet([(w, h) for h, w, _ in hyp], params=list(hp["ps"]), device=self.device, descs=hp["ds"])
+        self.crop = api.RaggedCrop([(h, w) for h, w, _ in self.h_s.shapes(1)], [(h, w) for h, w, _ in lat], lat[0][2], device=self.device)
+        # the stream length of z: codec.auto_stream_symbols of EACH image's own hyper-latent, HyperpriorCodec's rule
+        self.z_coder = codec.RaggedLatentCoder([(h, w) for h, w, _ in hyp], hyp[0][2], self.sizes, stream_symbols=z_stream_symbols or "auto",
+                                               device=self.device)
+        self.y_coders = [codec.ContextCoder(1, h, w, c, iw, ih, device=self.device) for (h, w, c), (iw, ih) in zip(lat, self.sizes)]
+        u8 = dict(dtype=torch.uint8, device=self.device)
+        self.y = torch.empty(self.main.nbytes(3), **u8)
+        self.z = torch.empty(self.h_a.nbytes(1), **u8)
+        self.z_hat = torch.empty_like(self.z)
+        self.s_full = torch.empty(self.h_s.nbytes(1), **u8)
+        self.s = torch.empty_like(self.y)
+        self.y_hat = torch.empty_like(self.y)
+        for net in (self.main, self.h_a, self.h_s):
+            net.workspace()
+        self._external = None       # the device copies of decode()'s external containers: alive until the next decode
+
+    def _per_image(self, t):
+        """[1][h][w][c] views of a ragged tensor of the latents' layout: what one image's ContextCoder takes."""
+        return [v.unsqueeze(0) for v in self.main.views(3, t)]
+
+    def _scale_map(self, z):
+        self.h_s.run_layers(0, 1, z, out=self.s_full)
+        return self.crop.run(self.s_full, self.s)
+
+    def encode(self, packed_x):
+        """packed_x: the ragged input (main.pack) -> one z and one y container per image.  Enqueue only, on the current stream."""
+        self.main.run_layers(0, 3, packed_x, out=self.y)
+        self.h_a.run_layers(0, 1, self.y, out=self.z)
+        self.z_coder.encode(self.z)
+        self._scale_map(self.z)                 # z itself: the z coder is lossless (HyperpriorCodec.encode)
+        for coder, y, s in zip(self.y_coders, self._per_image(self.y), self._per_image(self.s)):
+            coder.encode(y, s)
+        return self.z_coder.slot_buffer, [c.slots for c in self.y_coders]
+
+    def _upload(self, containers, capacities, what):
+        """Lists of `bytes` -> ([device uint8 slot of the coder's capacity], [device int32 [1][2] status {0, length}])."""
+        import torch
+        if len(containers) != len(capacities):
+            raise ValueError(f"{what}: need {len(capacities)} containers")
+        slots, valid = [], []
+        for i, (c, cap) in enumerate(zip(containers, capacities)):
+            if len(c) > cap:
+                raise ValueError(f"{what}[{i}]: {len(c)} bytes are more than the {cap} a container of this shape may take")
+            host = torch.zeros(cap, dtype=torch.uint8)
+            host[:len(c)] = torch.frombuffer(bytearray(c), dtype=torch.uint8)
+            slots.append(host.to(self.device))
+            valid.append(torch.tensor([[0, len(c)]], dtype=torch.int32).to(self.device))
+        return slots, valid
+
+    def decode(self, out=None, z_containers=None, y_containers=None):
+        """Containers (default: the last encode's; else lists of `bytes`, one per image) -> the reconstructions, a ragged tensor of
+        main's boundary 7 (`main.cropped(out)` cuts them to the images' sizes).  Enqueue only."""
+        import torch
+        keep = []
+        if z_containers is None:
+            self.z_coder.decode(self.z_hat)
+        else:
+            n = len(self.sizes)
+            slots, valid = self._upload(z_containers, [int(im.slot_bytes) for im in self.z_coder.images[:n]], "z_containers")
+            buf = torch.zeros(self.z_coder.slot_bytes, dtype=torch.uint8, device=self.device)
+            for s, v in zip(slots, self.z_coder.slots(buf)):
+                v.copy_(s)
+            status = torch.cat(valid)
+            keep += [buf, status]
+            self.z_coder.decode(self.z_hat, slots=buf, valid=status)
+        self._scale_map(self.z_hat)
+        ys, ss = self._per_image(self.y_hat), self._per_image(self.s)
+        if y_containers is None:
+            for coder, y, s in zip(self.y_coders, ys, ss):
+                coder.decode(y, s)
+        else:
+            slots, valid = self._upload(y_containers, [c.slot for c in self.y_coders], "y_containers")
+            keep += slots + valid
+            for coder, y, s, slot, v in zip(self.y_coders, ys, ss, slots, valid):
+                coder.decode(y, s, slots=slot.unsqueeze(0), valid=v)
+        self._external = keep
+        out, _ = self.main.run_layers(4, 7, self.y_hat, out=out)
+        return out
+
+    def containers(self):
+        """[(z container, y container)] of the last encode as `bytes` (synchronises; raises if the encode reported an error)."""
+        z = self.z_coder.containers()
+        y = []
+        for i, c in enumerate(self.y_coders):
+            err, size = c.enc_status[0].cpu().tolist()
+            if err:
+                raise api._lib.SicnError(-22, f"image {i}: rANS-WC encode status {err}")
+            y.append(c.slots[0, :size].cpu().numpy().tobytes())
+        return list(zip(z, y))
+
+    def check(self):
+        """Raises SicnError if the last encode / decode reported an error (synchronises); a y coder's error names its image
+        (`.image` of the exception, and in its text)."""
+        self.z_coder.check()
+        for i, c in enumerate(self.y_coders):
+            try:
+                c.check()
+            except api._lib.SicnError as e:
+                err = api._lib.SicnError(e.code, f"image {i} {self.sizes[i]}: {e}")
+                err.image = i
+                raise err from None
+
+    def bytes_per_image(self):
+        return [a + c.sizes()[0] for a, c in zip(self.z_coder.sizes(), self.y_coders)]

@@ -162,6 +162,23 @@ RAGGED_CODEC_ABI = {
     "sicn_ragged_coder_decode_async": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
+
+class RaggedCtxImage(ctypes.Structure):
+    """ctypes image of `sicn_ragged_ctx_image` (include/sicn_ragged_ctx.h)."""
+    _fields_ = [(n, ctypes.c_uint64) for n in ("latent_offset", "slot_offset", "workspace_offset", "slot_bytes")] + \
+               [(n, ctypes.c_uint32) for n in ("n_symbols", "anchor_streams", "nonanchor_streams")]
+
+
+# include/sicn_ragged_ctx.h (library 0.9: the rANS-WC coder over latents of different shapes, 6 + 8 launches for the whole batch)
+RAGGED_CTX_ABI = {
+    "sicn_ragged_ctx_layout": (_i, [_u32p, _u32p, _u32, _i, ctypes.POINTER(RaggedCtxImage), _u64p]),
+    "sicn_ragged_ctx_coder_create": (_i, [_u32p, _u32p, _u32, _u32p, _u32p, _i, ctypes.POINTER(_vp)]),
+    "sicn_ragged_ctx_coder_free": (None, [_vp]),
+    "sicn_ragged_ctx_coder_workspace_bytes": (_sz, [_vp]),
+    "sicn_ragged_ctx_encode_async": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "sicn_ragged_ctx_decode_async": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+}
+
 _lib = None
 
 
@@ -187,7 +204,7 @@ def lib() -> ctypes.CDLL:
         except ImportError:      # symbol checks etc. work without it
             pass
         L = ctypes.CDLL(str(LIB_PATH))
-        for name, (res, args) in {**ABI, **CODEC_ABI, **CONVLAYER_ABI, **GDN_ABI, **RAGGED_ABI, **RAGGED_HYPER_ABI, **RAGGED_CODEC_ABI}.items():
+        for name, (res, args) in {**ABI, **CODEC_ABI, **CONVLAYER_ABI, **GDN_ABI, **RAGGED_ABI, **RAGGED_HYPER_ABI, **RAGGED_CODEC_ABI, **RAGGED_CTX_ABI}.items():
             fn = getattr(L, name)          # AttributeError if the ABI is incomplete
             fn.restype = res
             fn.argtypes = args

@@ -10,7 +10,7 @@ from . import _lib
 
 RAW8, PACKED7, RANS, RANSW, RANSWC = 0, 1, 2, 3, 4
 __all__ = ["RAW8", "PACKED7", "RANS", "RANSW", "RANSWC", "encode_latent", "decode_latent", "parse_header", "encode_latents",
-           "decode_latents", "LatentCoder", "RaggedLatentCoder", "ContextCoder", "auto_stream_symbols", "WSTREAM_SYMBOLS"]
+           "decode_latents", "LatentCoder", "RaggedLatentCoder", "ContextCoder", "RaggedContextCoder", "auto_stream_symbols", "WSTREAM_SYMBOLS"]
 
 
 WSTREAM_SYMBOLS = 16384   # SICN_CODEC_WSTREAM_SYMBOLS: the default (and longest) rANS-W stream
@@ -381,3 +381,123 @@ class ContextCoder:
 
     sizes = LatentCoder.sizes
     check = LatentCoder.check
+
+
+class RaggedContextCoder:
+    """The ragged rANS-WC pair (include/sicn_ragged_ctx.h): n latents of n DIFFERENT shapes, each with its scale map -> n mode-4
+    containers with six launches for the whole batch, and back with eight.  `shapes`: [(lat_h, lat_w)] per image, `lat_c` channels
+    (a multiple of 4) in all of them; `image_sizes`: [(width, height)], header fields only.  Latents and scales travel as two ragged
+    tensors of one layout — flat CUDA uint8 tensors, the images' [h][w][c] arrays back to back — containers in one flat slot buffer,
+    image i's slot at `images[i].slot_offset`.  Container i is byte-identical to `ContextCoder(1, h_i, w_i, lat_c)`'s and decodes
+    with it.  Same conventions as RaggedLatentCoder: enqueue only; verdicts and sizes stay on the device until `check()` / `sizes()`."""
+
+    def __init__(self, shapes, lat_c: int, image_sizes=None, device=None):
+        import torch
+        L = _lib.lib()
+        self.shapes = [(int(h), int(w)) for h, w in shapes]
+        self.lat_c = int(lat_c)
+        n = len(self.shapes)
+        self.image_sizes = [(int(w), int(h)) for w, h in image_sizes] if image_sizes is not None else [(0, 0)] * n
+        if len(self.image_sizes) != n:
+            raise ValueError("image_sizes: one (width, height) per shape")
+        u32 = ctypes.c_uint32 * max(n, 1)
+        self._lat_w, self._lat_h = u32(*[w for _, w in self.shapes]), u32(*[h for h, _ in self.shapes])
+        self._img_w, self._img_h = u32(*[w for w, _ in self.image_sizes]), u32(*[h for _, h in self.image_sizes])
+        self.images = (_lib.RaggedCtxImage * max(n, 1))()            # where image i lies: offsets, slot capacity, streams of the two sets
+        totals = (ctypes.c_uint64 * 3)()
+        _lib.check(L.sicn_ragged_ctx_layout(self._lat_w, self._lat_h, self.lat_c, n, self.images, totals), "sicn_ragged_ctx_layout")
+        self.latent_bytes, self.slot_bytes = int(totals[0]), int(totals[1])
+        self.device = torch.device(device if device is not None else "cuda")
+        self._h = ctypes.c_void_p()
+        with torch.cuda.device(self.device):
+            _lib.check(L.sicn_ragged_ctx_coder_create(self._lat_w, self._lat_h, self.lat_c, self._img_w, self._img_h, n,
+                                                      ctypes.byref(self._h)), "sicn_ragged_ctx_coder_create")
+        self.slot_buffer = torch.empty(self.slot_bytes, dtype=torch.uint8, device=self.device)
+        self.ws = torch.empty(max(int(L.sicn_ragged_ctx_coder_workspace_bytes(self._h)), 256), dtype=torch.uint8, device=self.device)
+        self.enc_status = torch.zeros((n, 2), dtype=torch.int32, device=self.device)   # sicn_codec_status {error, bytes}
+        self.dec_status = torch.zeros((n, 2), dtype=torch.int32, device=self.device)
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None) and _lib._lib is not None:
+                _lib._lib.sicn_ragged_ctx_coder_free(self._h)
+                self._h = None
+        except Exception:       # interpreter shutdown
+            pass
+
+    @classmethod
+    def for_containers(cls, containers, device=None):
+        """A coder for rANS-WC containers that came from somewhere else (a list of `bytes`): shapes and image sizes are READ from
+        the 48-byte headers, the containers are copied into the coder's slots and their lengths into its encoder status, so that
+        `decode(out, scales)` reads exactly them."""
+        import torch
+        infos = [parse_header(bytes(c[:48])) for c in containers]
+        if not infos:
+            raise ValueError("no containers")
+        if any(int(i.mode) != RANSWC for i in infos) or len({int(i.lat_c) for i in infos}) != 1:
+            raise ValueError("containers must all be rANS-WC and of one channel count")
+        coder = cls([(int(i.lat_h), int(i.lat_w)) for i in infos], int(infos[0].lat_c),
+                    [(int(i.image_width), int(i.image_height)) for i in infos], device=device)
+        host = torch.zeros(coder.slot_bytes, dtype=torch.uint8)
+        for c, im in zip(containers, coder.images):
+            if len(c) > int(im.slot_bytes):
+                raise ValueError(f"a container of {len(c)} bytes is longer than the {int(im.slot_bytes)} its shape may take")
+            host[int(im.slot_offset):int(im.slot_offset) + len(c)] = torch.frombuffer(bytearray(c), dtype=torch.uint8)
+        coder.slot_buffer.copy_(host)
+        coder.enc_status.copy_(torch.tensor([[0, len(c)] for c in containers], dtype=torch.int32))
+        return coder
+
+    slots = RaggedLatentCoder.slots
+    views = RaggedLatentCoder.views
+    _flat = RaggedLatentCoder._flat
+
+    def encode(self, latents, scales, stream=None):
+        """latents, scales: ragged CUDA uint8 tensors -> self.slot_buffer (containers), self.enc_status.  Enqueue only."""
+        self._flat(latents, self.latent_bytes, "latents")
+        self._flat(scales, self.latent_bytes, "scales")
+        _lib.check(_lib.lib().sicn_ragged_ctx_encode_async(
+            self._h, ctypes.c_void_p(latents.data_ptr()), ctypes.c_void_p(scales.data_ptr()), ctypes.c_void_p(self.slot_buffer.data_ptr()),
+            ctypes.c_void_p(self.enc_status.data_ptr()), ctypes.c_void_p(self.ws.data_ptr()), self.ws.numel(), _stream_ptr(stream)),
+            "sicn_ragged_ctx_encode_async")
+        return self.slot_buffer
+
+    def decode(self, out_latents, scales, slots=None, valid=None, stream=None):
+        """slots (a flat slot buffer; default: this object's own) -> out_latents (ragged), self.dec_status.  `valid` as in
+        RaggedLatentCoder.decode.  Enqueue only."""
+        slots = self.slot_buffer if slots is None else slots
+        self._flat(out_latents, self.latent_bytes, "out_latents")
+        self._flat(scales, self.latent_bytes, "scales")
+        self._flat(slots, self.slot_bytes, "slots")
+        own = slots is self.slot_buffer
+        vptr = None if (valid is False or (valid is None and not own)) else ctypes.c_void_p((self.enc_status if valid is None else valid).data_ptr())
+        _lib.check(_lib.lib().sicn_ragged_ctx_decode_async(
+            self._h, ctypes.c_void_p(slots.data_ptr()), vptr, ctypes.c_void_p(scales.data_ptr()), ctypes.c_void_p(out_latents.data_ptr()),
+            ctypes.c_void_p(self.dec_status.data_ptr()), ctypes.c_void_p(self.ws.data_ptr()), self.ws.numel(), _stream_ptr(stream)),
+            "sicn_ragged_ctx_decode_async")
+        return out_latents
+
+    sizes = LatentCoder.sizes
+
+    def check(self):
+        """Raises SicnError if the last encode / decode reported an error (synchronises); the exception's `.image` is the first
+        image that failed."""
+        e = self.enc_status[:, 0].cpu().tolist()
+        d = self.dec_status[:, 0].cpu().tolist()
+        for what, st in (("encode", e), ("decode", d)):
+            if any(st):
+                code = -74 if what == "decode" and not any(v & ~128 for v in st) else -22
+                err = _lib.SicnError(code, f"rANS-WC {what} status {st}")
+                err.image = next(i for i, v in enumerate(st) if v)
+                raise err
+
+    def containers(self):
+        """The containers of the last encode as `bytes`, one per image (synchronises; raises if the encode reported an error)."""
+        import torch
+        torch.cuda.synchronize(self.device)
+        status = self.enc_status.cpu().tolist()
+        if any(e for e, _ in status):
+            err = _lib.SicnError(-22, f"rANS-WC encode status {[e for e, _ in status]}")
+            err.image = next(i for i, (e, _) in enumerate(status) if e)
+            raise err
+        host = self.slot_buffer.cpu().numpy()
+        return [host[int(im.slot_offset):int(im.slot_offset) + size].tobytes() for im, (_, size) in zip(self.images, status)]

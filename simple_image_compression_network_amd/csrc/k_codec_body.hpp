@@ -813,4 +813,105 @@ __device__ __forceinline__ void dec_finish_self_body(const DecImage &im)
     }
 }
 
+// ---- the bookkeeping stages of the scan form (mode 2, mode 3 above SELF_SCAN_MAX streams, mode 4) -------------------------------
+// Uniform kernels (sicn_codec.hip, sicn_codec_ctx.inc) resolve an image's pointers from strides, the ragged context coder
+// (k_ragged_ctx.hip) from its row; the stages themselves are these.
+
+// Exclusive prefix sum of `in[0..n)` into out[0..n], out[n] = total.  One workgroup of 1024 lanes:
+// wavefront-level scan with __shfl_up, wave totals combined through LDS, carry across chunks.
+// `in` may be unaligned container bytes (read byte-wise when `in_bytes` != nullptr).
+// Entries above `cap` (only possible in an untrusted container) raise `*err` and count as 0, so with
+// n * cap < 2^32 (the n_symbols limit of the rANS modes, MAX_RANS_SYMBOLS) the 32-bit sums cannot wrap.
+// skip: a slot the parse stage found shorter than its own fixed part is never read.  status_bytes: sicn_codec_status.bytes or nullptr.
+__device__ __forceinline__ void scan_body(const uint32_t *__restrict__ in, const uint8_t *__restrict__ in_bytes, uint32_t n,
+                                          uint32_t *__restrict__ out, uint8_t *__restrict__ table_out, uint8_t *__restrict__ total_out,
+                                          uint32_t cap, uint32_t *__restrict__ err, uint32_t *__restrict__ status_bytes,
+                                          uint32_t fixed_bytes, bool skip)
+{
+    __shared__ uint32_t wave_tot[16];
+    __shared__ uint32_t carry_s;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    if (threadIdx.x == 0) carry_s = 0;
+    __syncthreads();
+    for (uint32_t base = 0; base < n; base += 1024) {
+        const uint32_t i = base + threadIdx.x;
+        uint32_t v = 0;
+        if (i < n && !skip) {
+            if (in_bytes) {
+                const uint8_t *p = in_bytes + 4 * (size_t)i;
+                v = p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
+            } else
+                v = in[i];
+            if (v > cap) {
+                if (err) atomicOr(err, 1u);
+                v = 0;
+            }
+        }
+        uint32_t incl = v;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint32_t t = __shfl_up(incl, d);
+            if (lane >= d) incl += t;
+        }
+        if (lane == 63) wave_tot[wv] = incl;
+        __syncthreads();
+        uint32_t wave_off = 0;
+        for (int k = 0; k < wv; k++) wave_off += wave_tot[k];
+        const uint32_t carry = carry_s;
+        if (i < n) {
+            out[i] = carry + wave_off + incl - v;
+            if (table_out) {  // the container's per-stream byte counts, little-endian
+                uint8_t *p = table_out + 4 * (size_t)i;
+                p[0] = (uint8_t)v; p[1] = (uint8_t)(v >> 8); p[2] = (uint8_t)(v >> 16); p[3] = (uint8_t)(v >> 24);
+            }
+        }
+        __syncthreads();
+        if (threadIdx.x == 1023) carry_s = carry + wave_off + incl;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const uint32_t tot = carry_s;
+        out[n] = tot;
+        if (total_out) {
+            total_out[0] = (uint8_t)tot; total_out[1] = (uint8_t)(tot >> 8);
+            total_out[2] = (uint8_t)(tot >> 16); total_out[3] = (uint8_t)(tot >> 24);
+        }
+        if (status_bytes) *status_bytes = fixed_bytes + tot;
+    }
+}
+
+// one workgroup of 256 per stream: scratch tail -> payload
+__device__ __forceinline__ void compact_body(const uint8_t *__restrict__ scratch, const uint32_t *__restrict__ lens,
+                                             const uint32_t *__restrict__ offsets, uint8_t *__restrict__ payload, uint32_t cap, uint32_t st)
+{
+    const uint32_t len = lens[st];
+    const uint8_t *src = scratch + (size_t)st * cap + (cap - len);
+    uint8_t *dst = payload + offsets[st];
+    for (uint32_t i = threadIdx.x; i < len; i += 256) dst[i] = src[i];
+}
+
+// the statistics block at the head of a workspace block: hist[256] + sums (64 B) + freq (256 B), then meta (64 B), contiguous
+constexpr uint32_t STATS_WORDS = (1024 + 64 + 256) / 4;
+// the decoders' parse kernels are the first thing on the stream that touches the workspace: they clear the block themselves
+// (one launch less, about 4.5 us of a small image's decode) — everything but meta[0..3], which lane 0 then writes
+__device__ __forceinline__ void clear_stats_in_parse(uint32_t *meta, int lane)
+{
+    uint32_t *h = meta - STATS_WORDS;
+    for (uint32_t i = lane; i < STATS_WORDS + 16; i += 64)
+        if (i < STATS_WORDS || i >= STATS_WORDS + 4) h[i] = 0;
+}
+
+// Decoder back end, ONE lane: stream-level errors, table total, checksum -> status {error, n_symbols}.
+__device__ __forceinline__ void dec_finish_body(const uint32_t *__restrict__ meta, const unsigned long long *__restrict__ sums,
+                                                const uint32_t *__restrict__ offsets, uint32_t *__restrict__ status, uint32_t n, uint32_t ns)
+{
+    uint32_t err = meta[0];
+    if (meta[3]) err |= 32;                          // a stream overran / underran (the stream decoders, the scan)
+    if (offsets[ns] != meta[1]) err |= 64;           // the length table does not add up to the payload
+    const uint32_t a = (uint32_t)((1 + sums[0]) % ADLER_MOD), b = (uint32_t)((n % ADLER_MOD + sums[1]) % ADLER_MOD);
+    if (!err && ((b << 16) | a) != meta[2]) err |= 128;   // checksum (SICN_EBADMSG)
+    status[0] = err;
+    status[1] = n;
+}
+
 }  // namespace

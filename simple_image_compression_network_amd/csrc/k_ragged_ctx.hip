@@ -1,0 +1,350 @@
+// Ragged context coder (include/sicn_ragged_ctx.h): the rANS-WC stages of k_ctx_body.hpp over n latents of n different shapes, six
+// launches per encode and eight per decode for the whole batch.  The stages are the uniform coder's (sicn_codec_ctx.inc); what is
+// new is how a workgroup finds its image.
+//
+// Grids: flat over work items.
+//   statistics          chunks of an image's dwords, ctx_hist_blocks(n_i) per image (the uniform coder's rule); one workgroup takes the
+//                       byte statistics (stats_body) and the class histograms (ctx_hist_body) of its chunk
+//   encode              groups of CTX_WPB streams, rounded up per image: a workgroup shares one copy of its image's class tables
+//   decode              groups of CTX_WPB_DEC streams, rounded up per image AND per set: anchors of every image, then non-anchors
+//   compaction          single streams
+//   clear, tables, parse, scan + verdict, finish   one workgroup per image
+// Two kinds of table, built on the host at creation:
+//   chunk_image[], enc_image[], dec_image[2][], stream_image[] : the image a work item belongs to — ONE load resolves item -> image
+//   rows[image]                                                : CtxRow, the image's geometry, its first work items and its 64-bit
+//                                                                byte offsets in the latent / scale tensors, the slot buffer and the workspace
+// Both loads are wave-uniform (they depend on blockIdx.x only) and stay in scalar registers.  The workspace block of an image is
+// what ctx_carve() gives for its stream count, the same function the uniform coder calls on the host.
+#include <new>
+#include <vector>
+
+#include "../../include/sicn_ragged_ctx.h"
+#include "k_ctx_body.hpp"
+#include "sicn_internal.h"
+#include "sicn_weights_io.h"
+
+namespace {
+
+struct CtxRow {
+    uint64_t lat_off, slot_off, ws_off;
+    CtxGeom g;
+    uint32_t slot_cap;                 // min(slot bytes, 2^32 - 1), as the uniform parse stage bounds a slot
+    uint32_t img_w, img_h;
+    uint32_t first_chunk, n_chunks;    // the image's first work items in the flat grids
+    uint32_t first_enc, first_dec[2], first_stream;
+};
+
+__device__ __forceinline__ uint32_t uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+__device__ __forceinline__ uint64_t uni(uint64_t v) { return (uint64_t)uni((uint32_t)v) | (uint64_t)uni((uint32_t)(v >> 32)) << 32; }
+
+// the image's row, every field wave-uniform
+__device__ __forceinline__ CtxRow load_row(const CtxRow *__restrict__ rows, uint32_t img)
+{
+    const CtxRow *r = rows + img;
+    return CtxRow{uni(r->lat_off), uni(r->slot_off), uni(r->ws_off),
+                  CtxGeom{uni(r->g.W), uni(r->g.H), uni(r->g.C), {uni(r->g.nsym[0]), uni(r->g.nsym[1])}, {uni(r->g.nst[0]), uni(r->g.nst[1])}},
+                  uni(r->slot_cap), uni(r->img_w), uni(r->img_h), uni(r->first_chunk), uni(r->n_chunks), uni(r->first_enc),
+                  {uni(r->first_dec[0]), uni(r->first_dec[1])}, uni(r->first_stream)};
+}
+__device__ __forceinline__ CtxWorkspace row_workspace(const CtxRow &r, uint8_t *workspace)
+{
+    CtxWorkspace w;
+    ctx_carve(w, workspace + r.ws_off, r.g.nst[0] + r.g.nst[1], WCAP);
+    return w;
+}
+
+// encoder, first on the stream: the statistics block and the class histograms of every image, which the next stage adds to
+__global__ __launch_bounds__(256) void k_ragged_ctx_clear(uint8_t *__restrict__ workspace, const CtxRow *__restrict__ rows)
+{
+    const CtxRow r = load_row(rows, blockIdx.x);
+    const CtxWorkspace w = row_workspace(r, workspace);
+    for (uint32_t i = threadIdx.x; i < STATS_WORDS + 16 + NCLS * 128; i += 256) w.hist[i] = 0;   // hist .. meta, then chist: contiguous
+}
+
+// CLASSES: the encoder's statistics (byte histogram, checksum sums, class histograms); else the decoder's (checksum sums of what it decoded)
+template <bool CLASSES>
+__global__ __launch_bounds__(256) void k_ragged_ctx_stats(const uint8_t *__restrict__ latents, const uint8_t *__restrict__ scales,
+                                                          uint8_t *__restrict__ workspace, const CtxRow *__restrict__ rows,
+                                                          const uint32_t *__restrict__ chunk_image)
+{
+    const CtxRow r = load_row(rows, uni(chunk_image[blockIdx.x]));
+    const CtxWorkspace w = row_workspace(r, workspace);
+    const uint32_t local = blockIdx.x - r.first_chunk;
+    stats_body(latents + r.lat_off, r.g.W * r.g.H * r.g.C, w.hist, w.sums, nullptr, local, r.n_chunks);
+    if constexpr (CLASSES) ctx_hist_body(CtxResolved{}, latents + r.lat_off, scales + r.lat_off, r.g, w.chist, w.meta, local, r.n_chunks);
+}
+
+__global__ __launch_bounds__(64) void k_ragged_ctx_parse(const uint8_t *__restrict__ containers, const uint32_t *__restrict__ valid,
+                                                         uint8_t *__restrict__ workspace, const CtxRow *__restrict__ rows)
+{
+    const CtxRow r = load_row(rows, blockIdx.x);
+    const CtxWorkspace w = row_workspace(r, workspace);
+    const uint32_t bytes = valid ? min(valid[2 * (size_t)blockIdx.x + 1], r.slot_cap) : r.slot_cap;   // sicn_codec_status.bytes
+    ctx_parse_body(CtxResolved{}, containers + r.slot_off, bytes, w.meta, r.g);
+}
+
+// dec: the tables are read from the containers (and checked); else made from the class histograms and written to them, with the header
+__global__ __launch_bounds__(1024) void k_ragged_ctx_tables(uint8_t *__restrict__ containers, uint8_t *__restrict__ workspace,
+                                                            const CtxRow *__restrict__ rows, int dec)
+{
+    const CtxRow r = load_row(rows, blockIdx.x);
+    const CtxWorkspace w = row_workspace(r, workspace);
+    uint8_t *c = containers + r.slot_off;
+    ctx_tables_body(CtxResolved{}, w.chist, w.sums, w.meta, w.tfc, w.trcp, w.tst, c, r.g, r.img_w, r.img_h,
+                    dec ? c + SICN_CODEC_HEADER_BYTES : (const uint8_t *)nullptr);
+}
+
+__global__ __launch_bounds__(64 * CTX_WPB) void k_ragged_ctx_encode(const uint8_t *__restrict__ latents, const uint8_t *__restrict__ scales,
+                                                                    uint8_t *__restrict__ workspace, const CtxRow *__restrict__ rows,
+                                                                    const uint32_t *__restrict__ enc_image)
+{
+    const CtxRow r = load_row(rows, uni(enc_image[blockIdx.x]));
+    const CtxWorkspace w = row_workspace(r, workspace);
+    const CtxGeom &g = r.g;
+    const uint8_t *lat = latents + r.lat_off, *scale = scales + r.lat_off;
+    uint8_t *scratch = w.scratch;
+    uint32_t *lens = w.lens;
+    const uint32_t *tfc = w.tfc, *trcp = w.trcp;
+    const uint32_t grp = blockIdx.x - r.first_enc;
+#include "k_ctx_encode_steps.inc"
+}
+
+// One workgroup per image.  Encoder: stream lengths -> offsets, the container's length table and payload-bytes field, and the image's
+// status {error, container bytes}.  Decoder: the container's length table -> offsets (entries above a stream's cap are an error).
+__global__ __launch_bounds__(1024) void k_ragged_ctx_scan(uint8_t *__restrict__ containers, uint32_t *__restrict__ status,
+                                                          uint8_t *__restrict__ workspace, const CtxRow *__restrict__ rows, int dec)
+{
+    const CtxRow r = load_row(rows, blockIdx.x);
+    const CtxWorkspace w = row_workspace(r, workspace);
+    const uint32_t ns = r.g.nst[0] + r.g.nst[1];
+    uint8_t *c = containers + r.slot_off, *table = c + SICN_CODEC_HEADER_BYTES + CTX_TABLE_BYTES;
+    if (dec) {
+        scan_body(nullptr, table, ns, w.offsets, nullptr, nullptr, WCAP, w.meta + 3, nullptr, 0u, (w.meta[0] & 0x100u) != 0);
+        return;
+    }
+    if (threadIdx.x == 0) status[2 * (size_t)blockIdx.x] = ctx_enc_verdict(w.meta, w.hist);
+    scan_body(w.lens, nullptr, ns, w.offsets, table, c + 40, 0xFFFFFFFFu, nullptr, status + 2 * (size_t)blockIdx.x + 1,
+              (uint32_t)(SICN_CODEC_HEADER_BYTES + CTX_TABLE_BYTES) + 4 * ns, false);
+}
+
+__global__ __launch_bounds__(256) void k_ragged_ctx_compact(uint8_t *__restrict__ containers, uint8_t *__restrict__ workspace,
+                                                            const CtxRow *__restrict__ rows, const uint32_t *__restrict__ stream_image)
+{
+    const CtxRow r = load_row(rows, uni(stream_image[blockIdx.x]));
+    const CtxWorkspace w = row_workspace(r, workspace);
+    const uint32_t ns = r.g.nst[0] + r.g.nst[1];
+    compact_body(w.scratch, w.lens, w.offsets, containers + r.slot_off + SICN_CODEC_HEADER_BYTES + CTX_TABLE_BYTES + 4 * (size_t)ns, WCAP,
+                 blockIdx.x - r.first_stream);
+}
+
+// one set per launch (anchors first): dec_image is the table of that set.  SET is a template parameter so that the row's per-set
+// fields are picked at compile time (indexed by a kernel argument, the row went to scratch memory)
+template <int SET>
+__global__ __launch_bounds__(64 * CTX_WPB_DEC) void k_ragged_ctx_decode(const uint8_t *__restrict__ containers, const uint8_t *__restrict__ scales,
+                                                                        uint8_t *__restrict__ latents, uint8_t *__restrict__ workspace,
+                                                                        const CtxRow *__restrict__ rows, const uint32_t *__restrict__ dec_image)
+{
+    constexpr int set = SET;
+    const CtxRow r = load_row(rows, uni(dec_image[blockIdx.x]));
+    const CtxWorkspace w = row_workspace(r, workspace);
+    const CtxGeom &g = r.g;
+    const uint8_t *payload = containers + r.slot_off + SICN_CODEC_HEADER_BYTES + CTX_TABLE_BYTES + 4 * (size_t)(g.nst[0] + g.nst[1]);
+    const uint8_t *scale = scales + r.lat_off, *tst = w.tst;
+    const uint32_t *offsets = w.offsets, *tfc = w.tfc;
+    uint8_t *lat = latents + r.lat_off;
+    uint32_t *meta = w.meta;
+    const uint32_t grp = blockIdx.x - r.first_dec[set];
+#include "k_ctx_decode_steps.inc"
+}
+
+__global__ __launch_bounds__(64) void k_ragged_ctx_finish(uint32_t *__restrict__ status, uint8_t *__restrict__ workspace,
+                                                          const CtxRow *__restrict__ rows)
+{
+    if (threadIdx.x) return;
+    const CtxRow r = load_row(rows, blockIdx.x);
+    const CtxWorkspace w = row_workspace(r, workspace);
+    dec_finish_body(w.meta, w.sums, w.offsets, status + 2 * (size_t)blockIdx.x, r.g.W * r.g.H * r.g.C, r.g.nst[0] + r.g.nst[1]);
+}
+
+// ---- the layout: pure host --------------------------------------------------------------------------------------------------
+constexpr uint64_t RAGGED_MAX_ITEMS = 0x7fffffffull;   // fewer work items of a kind than this in all (grid.x)
+
+struct Plan {
+    std::vector<CtxRow> rows;
+    uint64_t lat_bytes = 0, slot_bytes = 0, ws_bytes = 0, streams = 0, chunks = 0, enc_groups = 0, dec_groups[2] = {0, 0};
+};
+
+// keep_rows = false: totals only (nothing is allocated)
+int plan_ctx(const uint32_t *lat_w, const uint32_t *lat_h, uint32_t lat_c, const uint32_t *img_w, const uint32_t *img_h, int n_images,
+             bool keep_rows, sicn_ragged_ctx_image *images, Plan *p)
+{
+    if (!lat_w || !lat_h || n_images < 1 || lat_c < 1 || (lat_c & 3)) return SICN_EINVAL;
+    if (keep_rows) p->rows.reserve((size_t)n_images);
+    for (int i = 0; i < n_images; i++) {
+        if (lat_w[i] < 1 || lat_h[i] < 1) return SICN_EINVAL;
+        const uint64_t positions = (uint64_t)lat_w[i] * lat_h[i];
+        if (positions > MAX_RANS_SYMBOLS || positions * lat_c > MAX_RANS_SYMBOLS) return SICN_EINVAL;   // (the products cannot wrap)
+        CtxRow r{};
+        r.g = ctx_geom(lat_w[i], lat_h[i], lat_c);
+        const uint32_t n = (uint32_t)(positions * lat_c), ns = r.g.nst[0] + r.g.nst[1];
+        const uint64_t slot = align_up(sicn_codec_ctx_max_bytes(lat_w[i], lat_h[i], lat_c), 16);
+        r.lat_off = p->lat_bytes;
+        r.slot_off = p->slot_bytes;
+        r.ws_off = p->ws_bytes;
+        r.slot_cap = (uint32_t)(slot < 0xFFFFFFFFull ? slot : 0xFFFFFFFFull);
+        r.img_w = img_w ? img_w[i] : 0; r.img_h = img_h ? img_h[i] : 0;
+        r.first_chunk = (uint32_t)p->chunks;
+        r.n_chunks = ctx_hist_blocks(n);
+        r.first_enc = (uint32_t)p->enc_groups;
+        r.first_dec[0] = (uint32_t)p->dec_groups[0];
+        r.first_dec[1] = (uint32_t)p->dec_groups[1];
+        r.first_stream = (uint32_t)p->streams;
+        p->lat_bytes += n;
+        p->slot_bytes += slot;
+        p->ws_bytes += ctx_ws_bytes(ns);
+        p->streams += ns;
+        p->chunks += r.n_chunks;
+        p->enc_groups += (ns + CTX_WPB - 1) / CTX_WPB;
+        for (int s = 0; s < 2; s++) p->dec_groups[s] += (r.g.nst[s] + CTX_WPB_DEC - 1) / CTX_WPB_DEC;
+        if (p->streams >= RAGGED_MAX_ITEMS || p->chunks >= RAGGED_MAX_ITEMS) return SICN_EINVAL;
+        if (images) images[i] = sicn_ragged_ctx_image{r.lat_off, r.slot_off, r.ws_off, slot, n, r.g.nst[0], r.g.nst[1]};
+        if (keep_rows) p->rows.push_back(r);
+    }
+    return SICN_OK;
+}
+
+}  // namespace
+
+struct sicn_ragged_ctx_coder {
+    int n_images = 0;
+    Plan plan;
+    CtxRow *d_rows = nullptr;                 // [n_images]
+    uint32_t *d_chunk_image = nullptr;        // [chunks]
+    uint32_t *d_enc_image = nullptr;          // [enc_groups]
+    uint32_t *d_dec_image[2] = {nullptr, nullptr};   // [dec_groups[set]]
+    uint32_t *d_stream_image = nullptr;       // [streams]
+};
+
+extern "C" int sicn_ragged_ctx_layout(const uint32_t *lat_w, const uint32_t *lat_h, uint32_t lat_c, int n_images,
+                                      sicn_ragged_ctx_image *images_or_null, uint64_t totals[3])
+{
+    Plan p;
+    if (int rc = plan_ctx(lat_w, lat_h, lat_c, nullptr, nullptr, n_images, false, images_or_null, &p)) return rc;
+    if (totals) {
+        totals[0] = p.lat_bytes;
+        totals[1] = p.slot_bytes;
+        totals[2] = p.ws_bytes;
+    }
+    return SICN_OK;
+}
+
+extern "C" void sicn_ragged_ctx_coder_free(sicn_ragged_ctx_coder *coder)
+{
+    if (!coder) return;
+    for (void *p : {(void *)coder->d_rows, (void *)coder->d_chunk_image, (void *)coder->d_enc_image, (void *)coder->d_dec_image[0],
+                    (void *)coder->d_dec_image[1], (void *)coder->d_stream_image})
+        if (p) (void)hipFree(p);
+    delete coder;
+}
+
+extern "C" int sicn_ragged_ctx_coder_create(const uint32_t *lat_w, const uint32_t *lat_h, uint32_t lat_c, const uint32_t *image_w_or_null,
+                                            const uint32_t *image_h_or_null, int n_images, sicn_ragged_ctx_coder **out)
+{
+    if (!out) return SICN_EINVAL;
+    *out = nullptr;
+    sicn_ragged_ctx_coder *coder = new (std::nothrow) sicn_ragged_ctx_coder();
+    if (!coder) return SICN_ENOMEM;
+    int rc = SICN_OK;
+    try {
+        rc = plan_ctx(lat_w, lat_h, lat_c, image_w_or_null, image_h_or_null, n_images, true, nullptr, &coder->plan);
+        if (!rc) rc = sicn::chip_geom(nullptr);       // no device, or not a gfx950 one
+        if (!rc) {
+            coder->n_images = n_images;
+            const Plan &p = coder->plan;
+            std::vector<uint32_t> chunk_image, enc_image, dec_image[2], stream_image;
+            chunk_image.reserve((size_t)p.chunks);
+            enc_image.reserve((size_t)p.enc_groups);
+            stream_image.reserve((size_t)p.streams);
+            for (int i = 0; i < n_images; i++) {
+                const CtxRow &r = p.rows[(size_t)i];
+                const uint32_t ns = r.g.nst[0] + r.g.nst[1];
+                chunk_image.insert(chunk_image.end(), (size_t)r.n_chunks, (uint32_t)i);
+                enc_image.insert(enc_image.end(), (size_t)((ns + CTX_WPB - 1) / CTX_WPB), (uint32_t)i);
+                for (int s = 0; s < 2; s++)
+                    dec_image[s].insert(dec_image[s].end(), (size_t)((r.g.nst[s] + CTX_WPB_DEC - 1) / CTX_WPB_DEC), (uint32_t)i);
+                stream_image.insert(stream_image.end(), (size_t)ns, (uint32_t)i);
+            }
+            auto up = [](const std::vector<uint32_t> &v, uint32_t **dev) { return v.empty() || sicn::upload(v.data(), v.size() * sizeof(uint32_t), dev); };
+            if (!sicn::upload(p.rows.data(), p.rows.size() * sizeof(CtxRow), &coder->d_rows) || !up(chunk_image, &coder->d_chunk_image) ||
+                !up(enc_image, &coder->d_enc_image) || !up(dec_image[0], &coder->d_dec_image[0]) ||
+                !up(dec_image[1], &coder->d_dec_image[1]) || !up(stream_image, &coder->d_stream_image))
+                rc = SICN_ENOMEM;
+        }
+    } catch (const std::bad_alloc &) { rc = SICN_ENOMEM; }
+    if (rc) {
+        sicn_ragged_ctx_coder_free(coder);
+        return rc;
+    }
+    *out = coder;
+    return SICN_OK;
+}
+
+extern "C" size_t sicn_ragged_ctx_coder_workspace_bytes(const sicn_ragged_ctx_coder *coder) { return coder ? (size_t)coder->plan.ws_bytes : 0; }
+
+extern "C" int sicn_ragged_ctx_encode_async(const sicn_ragged_ctx_coder *coder, const uint8_t *latents, const uint8_t *scales,
+                                            uint8_t *containers, sicn_codec_status *status_dev, void *workspace, size_t workspace_bytes,
+                                            void *hip_stream)
+{
+    if (!coder || !latents || !scales || !containers || !status_dev) return SICN_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(latents) | reinterpret_cast<uintptr_t>(scales)) & 3) return SICN_EINVAL;   // dword gathers
+    if (!workspace || workspace_bytes < coder->plan.ws_bytes) return SICN_ENOSPC;
+    if (reinterpret_cast<uintptr_t>(workspace) & 15) return SICN_EINVAL;
+    if (int rc = sicn::chip_geom(nullptr)) return rc;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    uint8_t *ws = (uint8_t *)workspace;
+    const Plan &p = coder->plan;
+    const unsigned n = (unsigned)coder->n_images;
+    // the uniform coder's stages (sicn_codec_ctx_encode_batch_async), its two statistics kernels as one and its verdict in the scan
+    hipLaunchKernelGGL(k_ragged_ctx_clear, dim3(n), dim3(256), 0, stream, ws, coder->d_rows);
+    hipLaunchKernelGGL(k_ragged_ctx_stats<true>, dim3((unsigned)p.chunks), dim3(256), 0, stream, latents, scales, ws, coder->d_rows,
+                       coder->d_chunk_image);
+    hipLaunchKernelGGL(k_ragged_ctx_tables, dim3(n), dim3(1024), 0, stream, containers, ws, coder->d_rows, 0);
+    hipLaunchKernelGGL(k_ragged_ctx_encode, dim3((unsigned)p.enc_groups), dim3(64 * CTX_WPB), 0, stream, latents, scales, ws, coder->d_rows,
+                       coder->d_enc_image);
+    hipLaunchKernelGGL(k_ragged_ctx_scan, dim3(n), dim3(1024), 0, stream, containers, (uint32_t *)status_dev, ws, coder->d_rows, 0);
+    hipLaunchKernelGGL(k_ragged_ctx_compact, dim3((unsigned)p.streams), dim3(256), 0, stream, containers, ws, coder->d_rows,
+                       coder->d_stream_image);
+    return hipGetLastError() == hipSuccess ? SICN_OK : SICN_ENODEV;
+}
+
+extern "C" int sicn_ragged_ctx_decode_async(const sicn_ragged_ctx_coder *coder, const uint8_t *containers,
+                                            const sicn_codec_status *valid_dev_or_null, const uint8_t *scales, uint8_t *latents,
+                                            sicn_codec_status *status_dev, void *workspace, size_t workspace_bytes, void *hip_stream)
+{
+    if (!coder || !containers || !scales || !latents || !status_dev) return SICN_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(latents) | reinterpret_cast<uintptr_t>(scales)) & 3) return SICN_EINVAL;
+    if (reinterpret_cast<uintptr_t>(containers) & 1) return SICN_EINVAL;   // the streams are read as 16-bit words (slot offsets are even)
+    if (!workspace || workspace_bytes < coder->plan.ws_bytes) return SICN_ENOSPC;
+    if (reinterpret_cast<uintptr_t>(workspace) & 15) return SICN_EINVAL;
+    if (int rc = sicn::chip_geom(nullptr)) return rc;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    uint8_t *ws = (uint8_t *)workspace;
+    uint8_t *slots = const_cast<uint8_t *>(containers);   // the tables and scan kernels write containers in the encoder only
+    const Plan &p = coder->plan;
+    const unsigned n = (unsigned)coder->n_images;
+    // a non-anchor's class reads its neighbours' bytes whatever they hold: start from zeros so that a rejected container
+    // cannot make the result depend on what the buffer held before.  First, so that a failure here leaves nothing enqueued.
+    if (hipMemsetAsync(latents, 0, (size_t)p.lat_bytes, stream) != hipSuccess) return SICN_ENODEV;
+    hipLaunchKernelGGL(k_ragged_ctx_parse, dim3(n), dim3(64), 0, stream, containers, (const uint32_t *)valid_dev_or_null, ws, coder->d_rows);
+    hipLaunchKernelGGL(k_ragged_ctx_tables, dim3(n), dim3(1024), 0, stream, slots, ws, coder->d_rows, 1);
+    hipLaunchKernelGGL(k_ragged_ctx_scan, dim3(n), dim3(1024), 0, stream, slots, (uint32_t *)nullptr, ws, coder->d_rows, 1);
+    hipLaunchKernelGGL(k_ragged_ctx_decode<0>, dim3((unsigned)p.dec_groups[0]), dim3(64 * CTX_WPB_DEC), 0, stream, containers, scales, latents, ws,
+                       coder->d_rows, coder->d_dec_image[0]);
+    if (p.dec_groups[1])   // (a batch of 1 x 1 latents has no non-anchors)
+        hipLaunchKernelGGL(k_ragged_ctx_decode<1>, dim3((unsigned)p.dec_groups[1]), dim3(64 * CTX_WPB_DEC), 0, stream, containers, scales, latents, ws,
+                           coder->d_rows, coder->d_dec_image[1]);
+    hipLaunchKernelGGL(k_ragged_ctx_stats<false>, dim3((unsigned)p.chunks), dim3(256), 0, stream, latents, scales, ws, coder->d_rows,
+                       coder->d_chunk_image);
+    hipLaunchKernelGGL(k_ragged_ctx_finish, dim3(n), dim3(64), 0, stream, (uint32_t *)status_dev, ws, coder->d_rows);
+    return hipGetLastError() == hipSuccess ? SICN_OK : SICN_ENODEV;
+}

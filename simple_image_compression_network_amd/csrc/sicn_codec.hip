@@ -31,6 +31,8 @@
 
 // constants, the workspace layout (carve) and the stages of the rANS-W coder that the ragged kernels (k_ragged_codec.hip) share
 #include "k_codec_body.hpp"
+// mode 4's constants, workspace layout and stages, shared with k_ragged_ctx.hip
+#include "k_ctx_body.hpp"
 
 namespace {
 
@@ -130,11 +132,7 @@ __global__ __launch_bounds__(256) void k_rans_encode(const uint8_t *__restrict__
     lens[st] = CAP - pos;
 }
 
-// Exclusive prefix sum of `in[0..n)` into out[0..n], out[n] = total.  One workgroup of 1024 lanes:
-// wavefront-level scan with __shfl_up, wave totals combined through LDS, carry across chunks.
-// `in` may be unaligned container bytes (read byte-wise when `in_bytes` != nullptr).
-// Entries above `cap` (only possible in an untrusted container) raise `*err` and count as 0, so with
-// n * cap < 2^32 (the n_symbols limit of the rANS modes, MAX_RANS_SYMBOLS) the 32-bit sums cannot wrap.
+// Exclusive prefix sum of a length table, one workgroup of 1024 per image: scan_body (k_codec_body.hpp)
 __global__ __launch_bounds__(1024) void k_scan(const uint32_t *__restrict__ in_, const uint8_t *__restrict__ in_bytes_,
                                                uint32_t n, uint32_t *__restrict__ out_, uint8_t *__restrict__ table_out_,
                                                uint8_t *__restrict__ total_out_, size_t s_ws, size_t s_slot, uint32_t cap,
@@ -143,61 +141,9 @@ __global__ __launch_bounds__(1024) void k_scan(const uint32_t *__restrict__ in_,
 {
     // async decode: a slot the parse stage found shorter than its own fixed part (meta[0] & 0x100) is never read
     const bool skip = skip_meta_ && (img_ptr(skip_meta_, s_ws)[0] & 0x100u);
-    const uint32_t *in = in_ ? img_ptr(in_, s_ws) : nullptr;
-    const uint8_t *in_bytes = in_bytes_ ? img_ptr(in_bytes_, s_slot) : nullptr;
-    uint32_t *out = img_ptr(out_, s_ws);
-    uint8_t *table_out = table_out_ ? img_ptr(table_out_, s_slot) : nullptr;
-    uint8_t *total_out = total_out_ ? img_ptr(total_out_, s_slot) : nullptr;
-    __shared__ uint32_t wave_tot[16];
-    __shared__ uint32_t carry_s;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    if (threadIdx.x == 0) carry_s = 0;
-    __syncthreads();
-    for (uint32_t base = 0; base < n; base += 1024) {
-        const uint32_t i = base + threadIdx.x;
-        uint32_t v = 0;
-        if (i < n && !skip) {
-            if (in_bytes) {
-                const uint8_t *p = in_bytes + 4 * (size_t)i;
-                v = p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
-            } else
-                v = in[i];
-            if (v > cap) {
-                if (err_) atomicOr(img_ptr(err_, s_ws), 1u);
-                v = 0;
-            }
-        }
-        uint32_t incl = v;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t t = __shfl_up(incl, d);
-            if (lane >= d) incl += t;
-        }
-        if (lane == 63) wave_tot[wv] = incl;
-        __syncthreads();
-        uint32_t wave_off = 0;
-        for (int k = 0; k < wv; k++) wave_off += wave_tot[k];
-        const uint32_t carry = carry_s;
-        if (i < n) {
-            out[i] = carry + wave_off + incl - v;
-            if (table_out) {  // the container's per-stream byte counts, little-endian
-                uint8_t *p = table_out + 4 * (size_t)i;
-                p[0] = (uint8_t)v; p[1] = (uint8_t)(v >> 8); p[2] = (uint8_t)(v >> 16); p[3] = (uint8_t)(v >> 24);
-            }
-        }
-        __syncthreads();
-        if (threadIdx.x == 1023) carry_s = carry + wave_off + incl;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        const uint32_t tot = carry_s;
-        out[n] = tot;
-        if (total_out) {
-            total_out[0] = (uint8_t)tot; total_out[1] = (uint8_t)(tot >> 8);
-            total_out[2] = (uint8_t)(tot >> 16); total_out[3] = (uint8_t)(tot >> 24);
-        }
-        if (status_bytes_) status_bytes_[2 * blockIdx.y + 1] = fixed_bytes + tot;   // sicn_codec_status.bytes
-    }
+    scan_body(in_ ? img_ptr(in_, s_ws) : nullptr, in_bytes_ ? img_ptr(in_bytes_, s_slot) : nullptr, n, img_ptr(out_, s_ws),
+              table_out_ ? img_ptr(table_out_, s_slot) : nullptr, total_out_ ? img_ptr(total_out_, s_slot) : nullptr, cap,
+              err_ ? img_ptr(err_, s_ws) : nullptr, status_bytes_ ? status_bytes_ + 2 * blockIdx.y + 1 : nullptr, fixed_bytes, skip);
 }
 
 // one workgroup per stream: scratch tail -> payload
@@ -205,13 +151,7 @@ __global__ __launch_bounds__(256) void k_compact(const uint8_t *__restrict__ scr
                                                  const uint32_t *__restrict__ offsets_, uint8_t *__restrict__ payload_, uint32_t cap,
                                                  size_t s_ws, size_t s_slot)
 {
-    const uint8_t *scratch = img_ptr(scratch_, s_ws);
-    const uint32_t *lens = img_ptr(lens_, s_ws), *offsets = img_ptr(offsets_, s_ws);
-    uint8_t *payload = img_ptr(payload_, s_slot);
-    const uint32_t st = blockIdx.x, len = lens[st];
-    const uint8_t *src = scratch + (size_t)st * cap + (cap - len);
-    uint8_t *dst = payload + offsets[st];
-    for (uint32_t i = threadIdx.x; i < len; i += 256) dst[i] = src[i];
+    compact_body(img_ptr(scratch_, s_ws), img_ptr(lens_, s_ws), img_ptr(offsets_, s_ws), img_ptr(payload_, s_slot), cap, blockIdx.x);
 }
 
 // The same without a scan kernel in front (asynchronous encoder, up to SELF_SCAN_MAX streams per image): compact_self_body
@@ -285,21 +225,11 @@ __global__ __launch_bounds__(256) void k_unpack7(const uint8_t *__restrict__ in,
 // ---- asynchronous batch path: everything the host did between two synchronisations, on the device -----------
 // blockIdx.y = image everywhere; per-image workspace stride s_ws, container slot stride s_slot.
 
-constexpr uint32_t STATS_WORDS = (1024 + 64 + 256) / 4;   // hist[256] + sums (64 B) + freq (256 B), then meta (64 B): contiguous
 __global__ __launch_bounds__(64) void k_clear_stats(uint32_t *__restrict__ hist_, size_t s_ws)
 {
     uint32_t *h = img_ptr(hist_, s_ws);
     for (uint32_t i = threadIdx.x; i < STATS_WORDS + 16; i += 64) h[i] = 0;
 }
-// the decoders' parse kernels are the first thing on the stream that touches the workspace: they clear the block themselves
-// (one launch less, about 4.5 us of a small image's decode) — everything but meta[0..3], which lane 0 then writes
-__device__ __forceinline__ void clear_stats_in_parse(uint32_t *meta, int lane)
-{
-    uint32_t *h = meta - STATS_WORDS;
-    for (uint32_t i = lane; i < STATS_WORDS + 16; i += 64)
-        if (i < STATS_WORDS || i >= STATS_WORDS + 4) h[i] = 0;
-}
-
 // Histogram -> 12-bit frequencies exactly as `normalize` / sicl_or_normalize do it (same floor, same "largest first,
 // lowest index on ties" correction walk), by one wave: lane l owns symbols 2l, 2l+1.  Then the container header and
 // frequency table.  status[0] = error flags (bit 0: symbol >= 128, bit 1: normalisation failed).
@@ -372,15 +302,7 @@ __global__ __launch_bounds__(64) void k_dec_finish(const uint32_t *__restrict__ 
                                                    uint32_t ns, size_t s_ws)
 {
     if (threadIdx.x) return;
-    const uint32_t *meta = img_ptr(meta_, s_ws), *offsets = img_ptr(offsets_, s_ws);
-    const unsigned long long *sums = img_ptr(sums_, s_ws);
-    uint32_t err = meta[0];
-    if (meta[3]) err |= 32;                          // a stream overran / underran (k_ransw_decode, k_scan)
-    if (offsets[ns] != meta[1]) err |= 64;           // the length table does not add up to the payload
-    const uint32_t a = (uint32_t)((1 + sums[0]) % ADLER_MOD), b = (uint32_t)((n % ADLER_MOD + sums[1]) % ADLER_MOD);
-    if (!err && ((b << 16) | a) != meta[2]) err |= 128;   // checksum (SICN_EBADMSG)
-    status_[2 * blockIdx.y] = err;
-    status_[2 * blockIdx.y + 1] = n;
+    dec_finish_body(img_ptr(meta_, s_ws), img_ptr(sums_, s_ws), img_ptr(offsets_, s_ws), status_ + 2 * blockIdx.y, n, ns);
 }
 
 // The asynchronous decoder's ONLY other kernel when the streams were decoded in self mode: dec_finish_self_body

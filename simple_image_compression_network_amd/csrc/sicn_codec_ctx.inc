@@ -7,229 +7,31 @@
 // Everything is asynchronous (device-side statistics / tables / validation, device status words), like the mode-3 pair.
 namespace {
 
-constexpr int NCLS = 16;
-constexpr uint32_t CTX_TABLE_BYTES = NCLS * 256;   // in the container: 16 x 128 x u16
-
-struct CtxGeom {
-    uint32_t W, H, C, nsym[2], nst[2];
+// The stages are in k_ctx_body.hpp and, the two step loops, in k_ctx_encode_steps.inc / k_ctx_decode_steps.inc (shared with the ragged
+// form, k_ragged_ctx.hip); a kernel here hands its stage image 0's pointers and the strides that img_ptr (blockIdx.y = image)
+// advances them by, or resolves them itself in front of an included step loop.
+struct CtxStrided {
+    size_t s_lat, s_ws, s_slot;
+    template <typename T> __device__ __forceinline__ T *lat(T *p) const { return img_ptr(p, s_lat); }
+    template <typename T> __device__ __forceinline__ T *ws(T *p) const { return img_ptr(p, s_ws); }
+    template <typename T> __device__ __forceinline__ T *slot(T *p) const { return img_ptr(p, s_slot); }
 };
-__host__ __device__ inline CtxGeom ctx_geom(uint32_t W, uint32_t H, uint32_t C)
-{
-    const uint32_t a = (W + 1) / 2, b = W / 2;
-    CtxGeom g;
-    g.W = W; g.H = H; g.C = C;
-    g.nsym[0] = ((H / 2) * W + ((H & 1) ? a : 0)) * C;
-    g.nsym[1] = ((H / 2) * W + ((H & 1) ? b : 0)) * C;
-    g.nst[0] = (g.nsym[0] + WSS - 1) / WSS;
-    g.nst[1] = (g.nsym[1] + WSS - 1) / WSS;
-    return g;
-}
 
-// pixel j of a set (0 = anchors: (x + y) even, 1 = non-anchors), raster order inside the set
-__device__ __forceinline__ void ctx_pixel(int set, uint32_t j, uint32_t W, uint32_t &y, uint32_t &x)
-{
-    const uint32_t a = (W + 1) / 2, b = W / 2, r = j / W, t = j - r * W;
-    if (set == 0) {
-        if (t < a) { y = 2 * r; x = 2 * t; } else { y = 2 * r + 1; x = 2 * (t - a) + 1; }
-    } else {
-        if (t < b) { y = 2 * r; x = 2 * t + 1; } else { y = 2 * r + 1; x = 2 * (t - b); }
-    }
-}
-
-// byte-wise max of two dwords whose bytes are all < 128
-__device__ __forceinline__ uint32_t max4_u7(uint32_t a, uint32_t b)
-{
-    const uint32_t d = (a | 0x80808080u) - b;                 // no borrow between bytes; bit 7 of a byte set iff a >= b there
-    const uint32_t m = ((d >> 7) & 0x01010101u) * 0xFFu;
-    return (a & m) | (b & ~m);
-}
-
-// classes (one per byte) of the 4 consecutive channels at byte offset `off` = ((y W + x) C + ch) of latent / scale
-__device__ __forceinline__ uint32_t ctx_class4(int set, const uint8_t *lat, const uint8_t *scale, uint32_t W, uint32_t H, uint32_t C,
-                                               uint32_t y, uint32_t x, uint32_t off)
-{
-    const uint32_t k0 = (*reinterpret_cast<const uint32_t *>(scale + off) >> 3) & 0x0F0F0F0Fu;   // s < 128
-    if (set == 0) return k0;
-    uint32_t m = 0;
-    if (y > 0) m = max4_u7(m, *reinterpret_cast<const uint32_t *>(lat + off - W * C) & 0x7F7F7F7Fu);
-    if (y + 1 < H) m = max4_u7(m, *reinterpret_cast<const uint32_t *>(lat + off + W * C) & 0x7F7F7F7Fu);
-    if (x > 0) m = max4_u7(m, *reinterpret_cast<const uint32_t *>(lat + off - C) & 0x7F7F7F7Fu);
-    if (x + 1 < W) m = max4_u7(m, *reinterpret_cast<const uint32_t *>(lat + off + C) & 0x7F7F7F7Fu);
-    return ((k0 + ((m >> 3) & 0x0F0F0F0Fu) + 0x01010101u) >> 1) & 0x0F0F0F0Fu;   // bytes <= 31 before the shift: no carries
-}
-
-struct CtxWorkspace {        // per image, carved out of the caller's workspace
-    uint32_t *hist;          // [256] + sums (64 B) + freq (256 B, unused) + meta (64 B): the block k_clear_stats zeroes
-    unsigned long long *sums;
-    uint32_t *meta;          // [0] error flags, [1] payload bytes the streams may use, [2] header adler32, [3] stream errors
-    uint32_t *chist;         // [16][128] class histograms
-    uint32_t *tfc;           // [16][128] freq | cum << 16
-    uint32_t *trcp;          // [16][128] reciprocals (encoder)
-    uint8_t *tst;            // [16][4096] slot -> symbol (decoder; round 3: [16][256], the first symbol of every 16-slot bucket + a search)
-    uint32_t *lens, *offsets;
-    uint8_t *scratch;
-};
-size_t ctx_carve(CtxWorkspace &w, void *base, uint32_t ns, size_t scratch_per_stream)
-{
-    uint8_t *p = (uint8_t *)base;
-    size_t off = 0;
-    w.hist = (uint32_t *)(p + off); off += 1024;
-    w.sums = (unsigned long long *)(p + off); off += 64;
-    off += 256;
-    w.meta = (uint32_t *)(p + off); off += 64;
-    w.chist = (uint32_t *)(p + off); off += NCLS * 128 * 4;
-    w.tfc = (uint32_t *)(p + off); off += NCLS * 128 * 4;
-    w.trcp = (uint32_t *)(p + off); off += NCLS * 128 * 4;
-    w.tst = p + off; off += NCLS * 4096;
-    w.lens = (uint32_t *)(p + off); off += align_up(4 * (size_t)ns + 4, 64);
-    w.offsets = (uint32_t *)(p + off); off += align_up(4 * (size_t)ns + 4, 64);
-    w.scratch = p + off;
-    off += (size_t)ns * scratch_per_stream;
-    return off;
-}
-size_t ctx_ws_bytes(uint32_t ns) { CtxWorkspace w; return align_up(ctx_carve(w, nullptr, ns, WCAP) + 64, 256); }
-
-// class histograms (+ range check of the scale map); one thread per dword of 4 channels
+// class histograms (+ range check of the scale map)
 __global__ __launch_bounds__(256) void k_ctx_hist(const uint8_t *__restrict__ lat_, const uint8_t *__restrict__ scale_, CtxGeom g,
                                                   uint32_t *__restrict__ chist_, uint32_t *__restrict__ meta_, size_t s_lat, size_t s_ws)
 {
-    const uint8_t *lat = img_ptr(lat_, s_lat), *scale = img_ptr(scale_, s_lat);
-    uint32_t *chist = img_ptr(chist_, s_ws), *meta = img_ptr(meta_, s_ws);
-    __shared__ uint32_t h[NCLS * 128];
-    for (int i = threadIdx.x; i < NCLS * 128; i += 256) h[i] = 0;
-    __syncthreads();
-    const uint32_t ndw = g.W * g.H * g.C / 4, cdw = g.C / 4;
-    bool bad = false;
-    for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < ndw; i += gridDim.x * 256) {
-        const uint32_t px = i / cdw, y = px / g.W, x = px - y * g.W, off = 4 * i;
-        const uint32_t v = *reinterpret_cast<const uint32_t *>(lat + off);
-        bad |= ((v | *reinterpret_cast<const uint32_t *>(scale + off)) & 0x80808080u) != 0;
-        const uint32_t k4 = ctx_class4((int)((x + y) & 1u), lat, scale, g.W, g.H, g.C, y, x, off);
-#pragma unroll
-        for (int b = 0; b < 4; b++) atomicAdd(&h[((k4 >> (8 * b)) & 15u) * 128 + ((v >> (8 * b)) & 127u)], 1u);
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < NCLS * 128; i += 256)
-        if (h[i]) atomicAdd(&chist[i], h[i]);
-    if (bad) atomicOr(&meta[0], 1u);
+    ctx_hist_body(CtxStrided{s_lat, s_ws, 0}, lat_, scale_, g, chist_, meta_, blockIdx.x, gridDim.x);
 }
 
-// 16 waves, one per class: histogram -> 12-bit table (the walk of k_enc_header), container bytes, and the encoder's /
-// decoder's lookup images.  Wave 0 also writes the header.
+// encoder: table_in_ == nullptr, tables come from chist and go to out_; decoder: tables are READ from the container
 __global__ __launch_bounds__(1024) void k_ctx_tables(const uint32_t *__restrict__ chist_, const unsigned long long *__restrict__ sums_,
                                                      uint32_t *__restrict__ meta_, uint32_t *__restrict__ tfc_, uint32_t *__restrict__ trcp_,
                                                      uint8_t *__restrict__ tst_, uint8_t *__restrict__ out_, uint32_t *__restrict__ status_,
                                                      CtxGeom g, uint32_t img_w, uint32_t img_h, const uint8_t *__restrict__ table_in_,
                                                      size_t s_ws, size_t s_slot)
 {
-    // encoder: table_in_ == nullptr, tables come from chist and go to out_; decoder: tables are READ from the container
-    const int lane = threadIdx.x & 63, cls = threadIdx.x >> 6;
-    uint32_t *meta = img_ptr(meta_, s_ws), *tfc = img_ptr(tfc_, s_ws) + cls * 128, *trcp = img_ptr(trcp_, s_ws) + cls * 128;
-    uint8_t *tst = img_ptr(tst_, s_ws) + cls * 4096;
-    uint32_t f[2], err = 0;
-    if (table_in_) {
-        const uint8_t *t = img_ptr(table_in_, s_slot) + cls * 256 + 4 * lane;
-        const bool readable = (meta[0] & 0x100u) == 0;
-        f[0] = readable ? (t[0] | ((uint32_t)t[1] << 8)) : 0u;
-        f[1] = readable ? (t[2] | ((uint32_t)t[3] << 8)) : 0u;
-        int sum = (int)(f[0] + f[1]);
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) sum += __shfl_xor(sum, d);
-        if (sum != 0 && sum != 4096) { err = 8; f[0] = f[1] = 0; }
-    } else {
-        const uint32_t *hist = img_ptr(chist_, s_ws) + cls * 128;
-        const uint32_t h0 = hist[2 * lane], h1 = hist[2 * lane + 1];
-        uint32_t n = h0 + h1;
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) n += (uint32_t)__shfl_xor((int)n, d);
-        const uint32_t hh[2] = {h0, h1};
-#pragma unroll
-        for (int k = 0; k < 2; k++) {
-            unsigned long long v = (hh[k] && n) ? ((unsigned long long)hh[k] * 4096u) / n : 0;
-            if (hh[k] && v == 0) v = 1;
-            f[k] = (uint32_t)v;
-        }
-        int sum = (int)(f[0] + f[1]);
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) sum += __shfl_xor(sum, d);
-        int diff = n ? 4096 - sum : 0;
-        for (int it = 0; it < 200 && diff != 0; it++) {
-            uint32_t key = 0;
-#pragma unroll
-            for (int k = 0; k < 2; k++)
-                if (f[k] > 0 && (diff > 0 || f[k] > 1)) key = max(key, (f[k] << 8) | (uint32_t)(255 - (2 * lane + k)));
-#pragma unroll
-            for (int d = 32; d > 0; d >>= 1) key = max(key, (uint32_t)__shfl_xor((int)key, d));
-            if (key == 0) break;
-            const int best = 255 - (int)(key & 255u), fb = (int)(key >> 8);
-            const int step = diff > 0 ? diff : (diff < 1 - fb ? 1 - fb : diff);
-            if ((best >> 1) == lane) f[best & 1] = (uint32_t)(fb + step);
-            diff -= step;
-        }
-        if (diff != 0) { err = 2; f[0] = f[1] = 0; }
-        uint8_t *ft = img_ptr(out_, s_slot) + SICN_CODEC_HEADER_BYTES + cls * 256 + 4 * lane;
-        ft[0] = (uint8_t)f[0]; ft[1] = (uint8_t)(f[0] >> 8); ft[2] = (uint8_t)f[1]; ft[3] = (uint8_t)(f[1] >> 8);
-    }
-    // exclusive prefix sums -> freq | cum << 16, reciprocals, bucket table
-    uint32_t incl = f[0] + f[1];
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t up = (uint32_t)__shfl_up((int)incl, d);
-        if (lane >= d) incl += up;
-    }
-    const uint32_t c0 = incl - f[0] - f[1], c1 = c0 + f[0];
-    tfc[2 * lane] = f[0] | (c0 << 16);
-    tfc[2 * lane + 1] = f[1] | (c1 << 16);
-    trcp[2 * lane] = ransw_rcp(f[0]);
-    trcp[2 * lane + 1] = ransw_rcp(f[1]);
-    if (table_in_) {   // decoder only: slot -> symbol, 4096 slots per class.  Lane l fills slots 64 l .. 64 l + 63: a binary search for the
-        // first one, then a walk along the cumulative table (filling "my symbol's range" instead left one lane with most of a
-        // peaked table: 38 us per image set)
-        __shared__ uint16_t cum[NCLS][130];
-        cum[cls][2 * lane] = (uint16_t)c0;
-        cum[cls][2 * lane + 1] = (uint16_t)c1;
-        if (lane == 63) cum[cls][128] = 0xFFFFu;   // sentinel: the walk stops at symbol 127
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        const uint16_t *cm = cum[cls];
-        const uint32_t v0 = 64u * (uint32_t)lane;
-        uint32_t lo = 0, hi = 128;                 // largest sy with cm[sy] <= v0 (cm[0] = 0): a zero-frequency run ends at the symbol that owns the slot
-        while (hi - lo > 1) {
-            const uint32_t mid = (lo + hi) >> 1;
-            if (cm[mid] <= v0) lo = mid; else hi = mid;
-        }
-        uint32_t sy = lo, nb = cm[sy + 1];
-        uint32_t outw[16];
-#pragma unroll
-        for (int i = 0; i < 16; i++) {
-            uint32_t wv4 = 0;
-#pragma unroll
-            for (int b = 0; b < 4; b++) {
-                const uint32_t v = v0 + 4u * (uint32_t)i + (uint32_t)b;
-                while (v >= nb) { sy++; nb = cm[sy + 1]; }
-                wv4 |= sy << (8 * b);
-            }
-            outw[i] = wv4;
-        }
-#pragma unroll
-        for (int i = 0; i < 4; i++)
-            *reinterpret_cast<uint4 *>(tst + v0 + 16 * i) = make_uint4(outw[4 * i], outw[4 * i + 1], outw[4 * i + 2], outw[4 * i + 3]);
-    }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) err |= (uint32_t)__shfl_xor((int)err, d);
-    if (lane == 0 && err) atomicOr(&meta[0], err);
-    if (!table_in_ && threadIdx.x < 12) {   // header (dword 10 = payload bytes comes from k_scan)
-        const unsigned long long *sums = img_ptr(sums_, s_ws);
-        const uint32_t n = g.W * g.H * g.C;
-        const uint32_t a = (uint32_t)((1 + sums[0]) % ADLER_MOD), b = (uint32_t)((n % ADLER_MOD + sums[1]) % ADLER_MOD);
-        const uint32_t words[12] = {0x4C434953u, 1u | (4u << 16), img_w, img_h, g.W, g.H, g.C, n, g.nst[0] + g.nst[1], WSS, 0u, (b << 16) | a};
-        if (threadIdx.x != 10) {
-            const uint32_t v = words[threadIdx.x];
-            uint8_t *p = img_ptr(out_, s_slot) + 4 * threadIdx.x;
-            p[0] = (uint8_t)v; p[1] = (uint8_t)(v >> 8); p[2] = (uint8_t)(v >> 16); p[3] = (uint8_t)(v >> 24);
-        }
-    }
+    ctx_tables_body(CtxStrided{0, s_ws, s_slot}, chist_, sums_, meta_, tfc_, trcp_, tst_, out_, g, img_w, img_h, table_in_);
     (void)status_;
 }
 
@@ -238,24 +40,7 @@ __global__ __launch_bounds__(64) void k_ctx_enc_status(const uint32_t *__restric
                                                        uint32_t *__restrict__ status_, size_t s_ws)
 {
     if (threadIdx.x) return;
-    const uint32_t *meta = img_ptr(meta_, s_ws), *hist = img_ptr(hist_, s_ws);
-    uint32_t err = meta[0];
-    for (int s = 128; s < 256; s++)
-        if (hist[s]) err |= 1u;
-    status_[2 * blockIdx.y] = err;
-}
-
-// Round 4: FOUR streams (waves) per workgroup share one copy of the class tables.  A one-wave workgroup carried 16 + 8 KB of LDS
-// (12 + 8 in the decoder): six / eight waves per CU — 1.5 / 2 per SIMD — for step loops that are chains of dependent LDS
-// round trips.  Shared, the tables cost 4 / 3 KB per wave and twelve waves fit.  A ring is private to its wave and a wave's LDS
-// operations execute in order, so the flush / fill points (data-dependent, different in every wave) need no block barrier — only
-// the compiler has to keep the order (wave_lds_sync).
-constexpr uint32_t CTX_WPB = 4;
-__device__ __forceinline__ void wave_lds_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    status_[2 * blockIdx.y] = ctx_enc_verdict(img_ptr(meta_, s_ws), img_ptr(hist_, s_ws));
 }
 
 __global__ __launch_bounds__(64 * CTX_WPB) void k_ctx_encode(const uint8_t *__restrict__ lat_, const uint8_t *__restrict__ scale_, CtxGeom g,
@@ -265,197 +50,32 @@ __global__ __launch_bounds__(64 * CTX_WPB) void k_ctx_encode(const uint8_t *__re
     const uint8_t *lat = img_ptr(lat_, s_lat), *scale = img_ptr(scale_, s_lat);
     uint8_t *scratch = img_ptr(scratch_, s_ws);
     uint32_t *lens = img_ptr(lens_, s_ws);
-    __shared__ uint32_t fc[NCLS * 128], rcp[NCLS * 128];
-    __shared__ __attribute__((aligned(16))) uint16_t words_all[CTX_WPB][RING_WORDS];   // one ring per wave, see k_ransw_encode
-    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6, st = blockIdx.x * CTX_WPB + wv;
-    {
-        const uint32_t *a = img_ptr(tfc_, s_ws), *b = img_ptr(trcp_, s_ws);
-        for (uint32_t i = threadIdx.x; i < NCLS * 128; i += 64 * CTX_WPB) { fc[i] = a[i]; rcp[i] = b[i]; }
-    }
-    __syncthreads();
-    if (st >= g.nst[0] + g.nst[1]) return;   // (no block barrier below this line)
-    uint16_t *words = words_all[wv];
-    const int set = st >= g.nst[0];
-    const uint32_t q0 = set ? st - g.nst[0] : st;
-    const uint32_t begin = q0 * WSS, cnt = min(WSS, g.nsym[set] - begin), blocks = (cnt + 255) / 256;
-    uint16_t *dst = (uint16_t *)(scratch + (size_t)st * WCAP);
-    uint32_t pos = WCAP / 2, top = WCAP / 2, x = RANSW_L;
-    const unsigned long long below = (1ull << lane) - 1;
-    auto load = [&](uint32_t q, uint32_t &sym4, uint32_t &cls4) {   // C % 4 == 0: a lane's 4 symbols are 4 channels of one pixel
-        const uint32_t j = q * 256 + lane * 4;
-        sym4 = cls4 = 0;
-        if (j >= cnt) return;
-        const uint32_t e = begin + j, px = e / g.C, ch = e - px * g.C;
-        uint32_t y, xx;
-        ctx_pixel(set, px, g.W, y, xx);
-        const uint32_t off = (y * g.W + xx) * g.C + ch;
-        sym4 = *reinterpret_cast<const uint32_t *>(lat + off);
-        cls4 = ctx_class4(set, lat, scale, g.W, g.H, g.C, y, xx, off);
-    };
-    uint32_t nsym = 0, ncls = 0;
-    if (blocks) load(blocks - 1, nsym, ncls);
-    for (uint32_t q = blocks; q-- > 0;) {
-        const uint32_t sym4 = nsym, cls4 = ncls;
-        if (q) load(q - 1, nsym, ncls);
-#pragma unroll
-        for (int k = 3; k >= 0; k--) {
-            const bool active0 = q * 256 + lane * 4 + k < cnt;
-            const uint32_t idx = ((cls4 >> (8 * k)) & 15u) * 128 + ((sym4 >> (8 * k)) & 127u);
-            const uint32_t t = fc[idx], c = t >> 16;
-            uint32_t f = t & 0xFFFFu;
-            const bool active = active0 && f != 0;      // f == 0 only for input the statistics stage rejected
-            f = active ? f : 1u;
-            const bool emit = active && (unsigned long long)x >= ((unsigned long long)f << 20);
-            const unsigned long long mask = __ballot(emit);
-            pos -= (uint32_t)__popcll(mask);
-            if (emit) {
-                words[(pos + (uint32_t)__popcll(mask & below)) & (RING_WORDS - 1)] = (uint16_t)x;
-                x >>= 16;
-            }
-            if (active) {
-                uint32_t r;
-                const uint32_t qq = ransw_div(x, f, rcp[idx], r);
-                x = (qq << PROB_BITS) + r + c;
-            }
-        }
-        if (top - pos > RING_WORDS - 4 * 64 - 128) {
-            wave_lds_sync();
-            ring_flush(words, dst, pos, top, lane);
-            wave_lds_sync();
-            top = pos;
-        }
-    }
-    pos -= 128;
-    words[(pos + 2 * lane) & (RING_WORDS - 1)] = (uint16_t)x;
-    words[(pos + 2 * lane + 1) & (RING_WORDS - 1)] = (uint16_t)(x >> 16);
-    wave_lds_sync();
-    ring_flush(words, dst, pos, top, lane);
-    if (lane == 0) lens[st] = (WCAP / 2 - pos) * 2;
+    const uint32_t *tfc = img_ptr(tfc_, s_ws), *trcp = img_ptr(trcp_, s_ws);
+    const uint32_t grp = blockIdx.x;
+#include "k_ctx_encode_steps.inc"
 }
 
-// one set per launch (anchors first): CTX_WPB_DEC streams of the set per workgroup.  The symbol of a slot comes from ONE table read
-// (16 classes x 4096 slots = 64 KB of LDS, shared by the workgroup's eight waves; round 3 read the first symbol of a 16-slot
-// bucket and walked the cumulative table from there — up to a dozen dependent LDS round trips per step on a flat class, with
-// six waves per CU to hide them behind).
-constexpr uint32_t CTX_WPB_DEC = 8;
+// one set per launch (anchors first)
 __global__ __launch_bounds__(64 * CTX_WPB_DEC) void k_ctx_decode(const uint8_t *__restrict__ payload_, const uint8_t *__restrict__ scale_, int set,
                                                    CtxGeom g, const uint32_t *__restrict__ tfc_, const uint8_t *__restrict__ tst_,
                                                    const uint32_t *__restrict__ offsets_, uint8_t *__restrict__ lat_,
                                                    uint32_t *__restrict__ meta_, size_t s_slot, size_t s_ws, size_t s_lat)
 {
-    const uint8_t *payload = img_ptr(payload_, s_slot), *scale = img_ptr(scale_, s_lat);
-    const uint32_t *offsets = img_ptr(offsets_, s_ws);
+    const uint8_t *payload = img_ptr(payload_, s_slot), *scale = img_ptr(scale_, s_lat), *tst = img_ptr(tst_, s_ws);
+    const uint32_t *offsets = img_ptr(offsets_, s_ws), *tfc = img_ptr(tfc_, s_ws);
     uint8_t *lat = img_ptr(lat_, s_lat);
     uint32_t *meta = img_ptr(meta_, s_ws);
-    __shared__ uint32_t fc[NCLS * 128];
-    __shared__ __attribute__((aligned(16))) uint8_t stb[NCLS * 4096];
-    __shared__ __attribute__((aligned(16))) uint16_t words_all[CTX_WPB_DEC][RING_WORDS];   // one ring per wave, see k_ransw_decode
-    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6, sidx = blockIdx.x * CTX_WPB_DEC + wv, st = sidx + (set ? g.nst[0] : 0);
-    {
-        const uint32_t *a = img_ptr(tfc_, s_ws);
-        const uint4 *b = reinterpret_cast<const uint4 *>(img_ptr(tst_, s_ws));   // the workspace block is 16-byte aligned (ctx_carve)
-        for (uint32_t i = threadIdx.x; i < NCLS * 128; i += 64 * CTX_WPB_DEC) fc[i] = a[i];
-        for (uint32_t i = threadIdx.x; i < NCLS * 256; i += 64 * CTX_WPB_DEC) reinterpret_cast<uint4 *>(stb)[i] = b[i];
-    }
-    __syncthreads();
-    if (sidx >= g.nst[set]) return;   // (no block barrier below this line)
-    uint16_t *words = words_all[wv];
-    const uint32_t begin = sidx * WSS, cnt = min(WSS, g.nsym[set] - begin), blocks = (cnt + 255) / 256;
-    const uint32_t off = offsets[st], len = offsets[st + 1] - off, payload_bytes = meta[1];
-    if (len < 256 || (len & 1) || (off & 1) || len > WCAP || (unsigned long long)off + len > payload_bytes) {
-        if (lane == 0) atomicOr(&meta[3], 1u);
-        return;
-    }
-    const uint32_t nwords = len / 2;
-    const uint16_t *src = (const uint16_t *)(payload + off);
-    uint32_t loaded = ring_fill(words, src, 0, min(nwords, RING_WORDS), lane);
-    wave_lds_sync();
-    uint32_t x = words[2 * lane] | ((uint32_t)words[2 * lane + 1] << 16), wpos = 128;
-    const unsigned long long below = (1ull << lane) - 1;
-    bool bad = false;
-    // the classes of a block come from global memory (the scale map and, for the non-anchors, the four anchor neighbours the
-    // previous launch decoded): requested ONE BLOCK AHEAD.  Round 3 fetched them at the top of the block they were needed in —
-    // with ~6 streams per CU in flight (a set of a 4K latent has 190 streams) that latency, 64 times per stream, was half of
-    // the kernel.
-    auto locate = [&](uint32_t q, uint32_t &o, uint32_t &cls4) -> bool {
-        const uint32_t j = q * 256 + lane * 4;
-        o = cls4 = 0;
-        if (j >= cnt) return false;      // cnt is a multiple of 4
-        const uint32_t e = begin + j, px = e / g.C, ch = e - px * g.C;
-        uint32_t y, xx;
-        ctx_pixel(set, px, g.W, y, xx);
-        o = (y * g.W + xx) * g.C + ch;
-        cls4 = ctx_class4(set, lat, scale, g.W, g.H, g.C, y, xx, o);
-        return true;
-    };
-    uint32_t o_next = 0, cls_next = 0;
-    bool mine_next = blocks ? locate(0, o_next, cls_next) : false;
-    for (uint32_t q = 0; q < blocks; q++) {
-        if (loaded < nwords && loaded - min(wpos, loaded) < 4 * 64) {
-            wave_lds_sync();
-            loaded = ring_fill(words, src, loaded, min(nwords, wpos + RING_WORDS), lane);
-            wave_lds_sync();
-        }
-        const bool mine = mine_next;
-        const uint32_t cls4 = cls_next, o = o_next;
-        mine_next = q + 1 < blocks ? locate(q + 1, o_next, cls_next) : false;
-        uint32_t out4 = 0;
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            if (mine) {
-                const uint32_t base = ((cls4 >> (8 * k)) & 15u) * 128, v = x & 4095u;
-                const uint32_t sy = stb[(base << 5) + v] & 127u;   // (a slot no symbol covers holds anything: caught by the range test)
-                const uint32_t t = fc[base + sy], f = t & 0xFFFFu;
-                bad |= f == 0 || v < (t >> 16) || v >= (t >> 16) + f;   // a class without a table, or a hole in it
-                out4 |= sy << (8 * k);
-                x = f * (x >> PROB_BITS) + v - (t >> 16);
-            }
-            const bool need = mine && x < RANSW_L;
-            const unsigned long long mask = __ballot(need);
-            if (need) {
-                const uint32_t idx = wpos + (uint32_t)__popcll(mask & below);
-                if (idx < loaded)
-                    x = (x << 16) | words[idx & (RING_WORDS - 1)];
-                else
-                    bad = true;
-            }
-            wpos += (uint32_t)__popcll(mask);
-        }
-        if (mine) *reinterpret_cast<uint32_t *>(lat + o) = out4;
-    }
-    if (bad || x != RANSW_L || wpos != nwords) atomicOr(&meta[3], 1u);
+    const uint32_t grp = blockIdx.x;
+#include "k_ctx_decode_steps.inc"
 }
 
 // header of a mode-4 container against the caller's shape (the tables are checked by k_ctx_tables)
 __global__ __launch_bounds__(64) void k_ctx_parse(const uint8_t *__restrict__ containers_, const uint32_t *__restrict__ valid_bytes_,
                                                   uint32_t valid_stride, uint32_t *__restrict__ meta_, CtxGeom g, size_t s_slot, size_t s_ws)
 {
-    const uint8_t *c = img_ptr(containers_, s_slot);
-    uint32_t *meta = img_ptr(meta_, s_ws);
-    const int lane = threadIdx.x;
-    const uint32_t ns = g.nst[0] + g.nst[1], n = g.W * g.H * g.C;
     const uint32_t valid = valid_bytes_ ? min(valid_bytes_[(size_t)blockIdx.y * valid_stride], (uint32_t)min(s_slot, (size_t)0xFFFFFFFFu))
                                         : (uint32_t)min(s_slot, (size_t)0xFFFFFFFFu);
-    const size_t fixed = SICN_CODEC_HEADER_BYTES + CTX_TABLE_BYTES + 4 * (size_t)ns;
-    clear_stats_in_parse(meta, lane);
-    if (valid < fixed) {
-        if (lane == 0) { meta[0] = 0x104u; meta[1] = 0; meta[2] = 0; meta[3] = 0; }
-        return;
-    }
-    auto rd32 = [&](int o) { return c[o] | ((uint32_t)c[o + 1] << 8) | ((uint32_t)c[o + 2] << 16) | ((uint32_t)c[o + 3] << 24); };
-    const uint32_t expect[10] = {0x4C434953u, 1u | (4u << 16), 0, 0, g.W, g.H, g.C, n, ns, WSS};
-    uint32_t err = 0;
-    if (lane < 10 && lane != 2 && lane != 3 && rd32(4 * lane) != expect[lane]) err = 4;
-    const uint32_t pb = rd32(40);
-    if ((size_t)pb > (size_t)valid - fixed) err |= 16;
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) err |= (uint32_t)__shfl_xor((int)err, d);
-    if (lane == 0) {
-        meta[0] = err;
-        meta[1] = (err & 16) ? 0u : pb;
-        meta[2] = rd32(44);
-        meta[3] = 0;
-    }
+    ctx_parse_body(CtxStrided{0, s_ws, s_slot}, containers_, valid, meta_, g);
 }
 
 }  // namespace
@@ -503,7 +123,7 @@ extern "C" int sicn_codec_ctx_encode_batch_async(const uint8_t *latents, const u
     hipLaunchKernelGGL(k_clear_stats, dim3(1, n_images), dim3(64), 0, stream, w.hist, ws1);
     HIP_TRY(hipMemset2DAsync(w.chist, ws1, 0, NCLS * 128 * 4, n_images, stream));
     hipLaunchKernelGGL(k_stats, dim3(stats_blocks(n), n_images), dim3(256), 0, stream, latents, (uint8_t *)workspace, stats_batch(n, n, ws1));
-    hipLaunchKernelGGL(k_ctx_hist, dim3(min((n / 4 + 255u) / 256u, 256u), n_images), dim3(256), 0, stream, latents, scales, g, w.chist,
+    hipLaunchKernelGGL(k_ctx_hist, dim3(ctx_hist_blocks(n), n_images), dim3(256), 0, stream, latents, scales, g, w.chist,
                        w.meta, (size_t)n, ws1);
     hipLaunchKernelGGL(k_ctx_tables, dim3(1, n_images), dim3(1024), 0, stream, w.chist, w.sums, w.meta, w.tfc, w.trcp, w.tst, out, status,
                        g, img_w, img_h, (const uint8_t *)nullptr, ws1, slot_bytes);

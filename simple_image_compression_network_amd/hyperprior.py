@@ -165,14 +165,13 @@ class HyperpriorCodec:
 
 
 class RaggedHyperpriorCodec:
-    """The same configuration over n images of n DIFFERENT sizes (`sizes`: [(width, height)]), every stage but the y coder one set of
-    launches for the whole batch (include/sicn_ragged.h, sicn_ragged_codec.h):
+    """The same configuration over n images of n DIFFERENT sizes (`sizes`: [(width, height)]), every stage one set of launches for the
+    whole batch (include/sicn_ragged.h, sicn_ragged_codec.h, sicn_ragged_ctx.h):
 
         main, h_a, h_s : api.RaggedNet (GDN / IGDN layers: the layer kernel, then the activation over the whole boundary tensor)
         z bitstream     : codec.RaggedLatentCoder, 3 launches to encode and 2 to decode
         scale map       : api.RaggedCrop cuts h_s(z), 4 * ceil(./4) per image, to every latent's own shape in one launch
-        y bitstream     : one codec.ContextCoder(1, ...) PER IMAGE, fed that image's slice of the ragged y, s and y_hat (a slice is a plain
-                          contiguous NHWC array); a ragged form of rANS-WC does not exist yet
+        y bitstream     : codec.RaggedContextCoder, 6 launches to encode and 8 to decode, fed the ragged y, s and y_hat as they lie
 
     Image i's containers are `HyperpriorCodec(w_i, h_i, 1, seed)`'s, byte for byte: hyper_parameters draws depend on channel counts
     only, so every image gets that codec's parameters.  Stage tensors (y, z, z_hat, s, y_hat) are ragged tensors; `main.views(3, y)`,
@@ -198,7 +197,7 @@ class RaggedHyperpriorCodec:
         # the stream length of z: codec.auto_stream_symbols of EACH image's own hyper-latent, HyperpriorCodec's rule
         self.z_coder = codec.RaggedLatentCoder([(h, w) for h, w, _ in hyp], hyp[0][2], self.sizes, stream_symbols=z_stream_symbols or "auto",
                                                device=self.device)
-        self.y_coders = [codec.ContextCoder(1, h, w, c, iw, ih, device=self.device) for (h, w, c), (iw, ih) in zip(lat, self.sizes)]
+        self.y_coder = codec.RaggedContextCoder([(h, w) for h, w, _ in lat], lat[0][2], self.sizes, device=self.device)
         u8 = dict(dtype=torch.uint8, device=self.device)
         self.y = torch.empty(self.main.nbytes(3), **u8)
         self.z = torch.empty(self.h_a.nbytes(1), **u8)
@@ -210,10 +209,6 @@ class RaggedHyperpriorCodec:
             net.workspace()
         self._external = None       # the device copies of decode()'s external containers: alive until the next decode
 
-    def _per_image(self, t):
-        """[1][h][w][c] views of a ragged tensor of the latents' layout: what one image's ContextCoder takes."""
-        return [v.unsqueeze(0) for v in self.main.views(3, t)]
-
     def _scale_map(self, z):
         self.h_s.run_layers(0, 1, z, out=self.s_full)
         return self.crop.run(self.s_full, self.s)
@@ -224,77 +219,57 @@ class RaggedHyperpriorCodec:
         self.h_a.run_layers(0, 1, self.y, out=self.z)
         self.z_coder.encode(self.z)
         self._scale_map(self.z)                 # z itself: the z coder is lossless (HyperpriorCodec.encode)
-        for coder, y, s in zip(self.y_coders, self._per_image(self.y), self._per_image(self.s)):
-            coder.encode(y, s)
-        return self.z_coder.slot_buffer, [c.slots for c in self.y_coders]
+        self.y_coder.encode(self.y, self.s)
+        return self.z_coder.slot_buffer, self.y_coder.slots()
 
-    def _upload(self, containers, capacities, what):
-        """Lists of `bytes` -> ([device uint8 slot of the coder's capacity], [device int32 [1][2] status {0, length}])."""
+    def _upload(self, containers, coder, what):
+        """A list of `bytes` -> (a device slot buffer of `coder`'s layout holding them, a device int32 [n][2] status {0, length})."""
         import torch
-        if len(containers) != len(capacities):
-            raise ValueError(f"{what}: need {len(capacities)} containers")
-        slots, valid = [], []
-        for i, (c, cap) in enumerate(zip(containers, capacities)):
-            if len(c) > cap:
-                raise ValueError(f"{what}[{i}]: {len(c)} bytes are more than the {cap} a container of this shape may take")
-            host = torch.zeros(cap, dtype=torch.uint8)
-            host[:len(c)] = torch.frombuffer(bytearray(c), dtype=torch.uint8)
-            slots.append(host.to(self.device))
-            valid.append(torch.tensor([[0, len(c)]], dtype=torch.int32).to(self.device))
-        return slots, valid
+        images = coder.images[:len(self.sizes)]
+        if len(containers) != len(images):
+            raise ValueError(f"{what}: need {len(images)} containers")
+        host = torch.zeros(coder.slot_bytes, dtype=torch.uint8)
+        for i, (c, im) in enumerate(zip(containers, images)):
+            if len(c) > int(im.slot_bytes):
+                raise ValueError(f"{what}[{i}]: {len(c)} bytes are more than the {int(im.slot_bytes)} a container of this shape may take")
+            host[int(im.slot_offset):int(im.slot_offset) + len(c)] = torch.frombuffer(bytearray(c), dtype=torch.uint8)
+        return host.to(self.device), torch.tensor([[0, len(c)] for c in containers], dtype=torch.int32).to(self.device)
 
     def decode(self, out=None, z_containers=None, y_containers=None):
         """Containers (default: the last encode's; else lists of `bytes`, one per image) -> the reconstructions, a ragged tensor of
         main's boundary 7 (`main.cropped(out)` cuts them to the images' sizes).  Enqueue only."""
-        import torch
         keep = []
         if z_containers is None:
             self.z_coder.decode(self.z_hat)
         else:
-            n = len(self.sizes)
-            slots, valid = self._upload(z_containers, [int(im.slot_bytes) for im in self.z_coder.images[:n]], "z_containers")
-            buf = torch.zeros(self.z_coder.slot_bytes, dtype=torch.uint8, device=self.device)
-            for s, v in zip(slots, self.z_coder.slots(buf)):
-                v.copy_(s)
-            status = torch.cat(valid)
+            buf, status = self._upload(z_containers, self.z_coder, "z_containers")
             keep += [buf, status]
             self.z_coder.decode(self.z_hat, slots=buf, valid=status)
         self._scale_map(self.z_hat)
-        ys, ss = self._per_image(self.y_hat), self._per_image(self.s)
         if y_containers is None:
-            for coder, y, s in zip(self.y_coders, ys, ss):
-                coder.decode(y, s)
+            self.y_coder.decode(self.y_hat, self.s)
         else:
-            slots, valid = self._upload(y_containers, [c.slot for c in self.y_coders], "y_containers")
-            keep += slots + valid
-            for coder, y, s, slot, v in zip(self.y_coders, ys, ss, slots, valid):
-                coder.decode(y, s, slots=slot.unsqueeze(0), valid=v)
+            buf, status = self._upload(y_containers, self.y_coder, "y_containers")
+            keep += [buf, status]
+            self.y_coder.decode(self.y_hat, self.s, slots=buf, valid=status)
         self._external = keep
         out, _ = self.main.run_layers(4, 7, self.y_hat, out=out)
         return out
 
     def containers(self):
         """[(z container, y container)] of the last encode as `bytes` (synchronises; raises if the encode reported an error)."""
-        z = self.z_coder.containers()
-        y = []
-        for i, c in enumerate(self.y_coders):
-            err, size = c.enc_status[0].cpu().tolist()
-            if err:
-                raise api._lib.SicnError(-22, f"image {i}: rANS-WC encode status {err}")
-            y.append(c.slots[0, :size].cpu().numpy().tobytes())
-        return list(zip(z, y))
+        return list(zip(self.z_coder.containers(), self.y_coder.containers()))
 
     def check(self):
         """Raises SicnError if the last encode / decode reported an error (synchronises); a y coder's error names its image
         (`.image` of the exception, and in its text)."""
         self.z_coder.check()
-        for i, c in enumerate(self.y_coders):
-            try:
-                c.check()
-            except api._lib.SicnError as e:
-                err = api._lib.SicnError(e.code, f"image {i} {self.sizes[i]}: {e}")
-                err.image = i
-                raise err from None
+        try:
+            self.y_coder.check()
+        except api._lib.SicnError as e:
+            err = api._lib.SicnError(e.code, f"image {e.image} {self.sizes[e.image]}: {e}")
+            err.image = e.image
+            raise err from None
 
     def bytes_per_image(self):
-        return [a + c.sizes()[0] for a, c in zip(self.z_coder.sizes(), self.y_coders)]
+        return [a + b for a, b in zip(self.z_coder.sizes(), self.y_coder.sizes())]

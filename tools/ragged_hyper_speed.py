@@ -3,16 +3,15 @@
 
 The workload of tools/ragged_speed.py: the seeded mix of 64 image sizes, W and H each drawn from {256, 384, 512, 640, 768}, PARAM
 weights in the main transform, seeded hyper stacks and GDN parameters; one step is encode + decode of the whole mix by
-  ragged   one hyperprior.RaggedHyperpriorCodec: main transform, hyper stacks, z coder and scale-map crop are per-BATCH launches, the y
-           coder (rANS-WC) is one codec.ContextCoder(1, ...) per image
+  ragged   one hyperprior.RaggedHyperpriorCodec: main transform, hyper stacks, both coders and the scale-map crop are per-BATCH launches
   loop     one hyperprior.HyperpriorCodec(w_i, h_i, 1) per image, created before timing, one encode + one decode call per image: every
            stage is per-image launches, on the tuned kernels of that size
 Both use each image's own automatic z stream length, so the two write the same bytes.
 
 Method: both variants are warmed up; then they ALTERNATE in one process for --rounds rounds, each timed with device events around
 enough back-to-back repetitions to fill --seconds.  Containers and reconstructions are compared byte for byte in the same run.
-There is NO acceptance ratio: the y coder is still per image and the ragged layers are the untuned channel-generic kernels
-(profiles/ragged_batch_speed.txt); the table says what was measured.
+There is NO acceptance ratio: the ragged layers are the untuned channel-generic kernels (profiles/ragged_batch_speed.txt) against the
+tuned ones of each size; the table says what was measured.  (The y coder alone: tools/ragged_ctx_speed.py.)
 
   python tools/ragged_hyper_speed.py --out profiles/ragged_hyper_speed.txt
 """
@@ -26,11 +25,11 @@ sys.path.insert(0, str(Path(__file__).resolve().parent))
 
 from ragged_speed import make_sizes  # noqa: E402  (the same seeded mix)
 
-# launches of one ContextCoder call (csrc/sicn_codec_ctx.inc): encode 8 kernels; decode 5 kernels + up to 2 k_ctx_decode + 1 memset node
-CTX_ENC, CTX_DEC = 8, 8
+# launches of one RaggedContextCoder call (csrc/k_ragged_ctx.hip): encode 6 kernels; decode 5 kernels + up to 2 k_ragged_ctx_decode + 1 memset node
+CTX_ENC, CTX_DEC = 6, 8
 
 
-def stage_launches(n_images, use_gdn=True):
+def stage_launches(use_gdn=True):
     """[(stage, encode launches, decode launches, per)] of RaggedHyperpriorCodec, from the launch functions' own structure."""
     act = 3 if use_gdn else 0
     return [("main analysis, layers 0-3" + (" + 3 GDN" if use_gdn else ""), 4 + act, 0, "batch"),
@@ -39,7 +38,7 @@ def stage_launches(n_images, use_gdn=True):
             ("h_s, 2 layers", 2, 2, "batch"),
             ("scale-map crop", 1, 1, "batch"),
             ("main synthesis, layers 4-7" + (" + 3 IGDN" if use_gdn else ""), 0, 4 + act, "batch"),
-            (f"y coder (rANS-WC), {n_images} x ContextCoder(1)", CTX_ENC * n_images, CTX_DEC * n_images, "image")]
+            ("y coder (ragged rANS-WC)", CTX_ENC, CTX_DEC, "batch")]
 
 
 def main():
@@ -127,16 +126,16 @@ def main():
         lines.append(f"{k:<9}{reps[k]:>6}{med[k]:>11.3f}{min(ms[k]):>9.3f}{max(ms[k]):>9.3f}{max(ms[k]) - min(ms[k]):>11.3f}{pixels / med[k] / 1e3:>10.0f}   "
                      + " ".join(f"{v:.3f}" for v in ms[k]))
     lines.append("")
-    lines.append(f"ragged / loop = {med['ragged'] / med['loop']:.2f} (no acceptance ratio: the y coder is per image in both, and the ragged layers are the "
-                 "untuned channel-generic kernels against the tuned ones of each size)")
+    lines.append(f"ragged / loop = {med['ragged'] / med['loop']:.2f} (no acceptance ratio: the ragged layers are the untuned channel-generic kernels "
+                 "against the tuned ones of each size)")
     lines.append("")
     lines.append("launches of one ragged step, per stage (from the launch functions; the y coder's decode includes its memset node):")
     lines.append(f"  {'stage':<52}{'encode':>8}{'decode':>8}   per")
-    stages = stage_launches(a.images)
+    stages = stage_launches()
     for name, e, d, per in stages:
         lines.append(f"  {name:<52}{e:>8}{d:>8}   {per}")
-    be, bd = (sum(s[i] for s in stages if s[3] == "batch") for i in (1, 2))
-    lines.append(f"  per batch: {be} + {bd}; per image: {CTX_ENC} + {CTX_DEC}; the loop launches every stage once per image")
+    be, bd = (sum(s[i] for s in stages) for i in (1, 2))
+    lines.append(f"  per batch: {be} + {bd}, whatever the number of images; the loop launches every stage once per image")
     text = "\n".join(lines)
     print(text)
     if a.out:

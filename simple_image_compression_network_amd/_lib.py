@@ -179,6 +179,33 @@ RAGGED_CTX_ABI = {
     "sicn_ragged_ctx_decode_async": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
+
+class RaggedArchiveInfo(ctypes.Structure):
+    """ctypes image of `sicn_ragged_archive_info` (include/sicn_ragged_archive.h)."""
+    _fields_ = [(n, ctypes.c_uint32) for n in ("version", "n_sections", "n_images", "tag")] + \
+               [(n, ctypes.c_uint64) for n in ("total_bytes", "payload_offset")]
+
+
+class RaggedArchiveStatus(ctypes.Structure):
+    """ctypes image of `sicn_ragged_archive_status` (include/sicn_ragged_archive.h); lives in device memory, 16 bytes."""
+    _fields_ = [("error", ctypes.c_uint32), ("first_bad", ctypes.c_uint32), ("bytes", ctypes.c_uint64)]
+
+
+_u64pp = ctypes.POINTER(_u64p)
+_vpp = ctypes.POINTER(_vp)
+# include/sicn_ragged_archive.h (library 0.10: the containers of a ragged batch as one byte string, 2 + 2 launches)
+RAGGED_ARCHIVE_ABI = {
+    "sicn_ragged_archive_layout": (_i, [_u32p, _u32, _u32, _u64p, _u64p]),
+    "sicn_ragged_archive_parse": (_i, [_vp, _sz, ctypes.POINTER(RaggedArchiveInfo), _u32p, _u64p]),
+    "sicn_ragged_archive_chunk_bytes": (_sz, []),
+    "sicn_ragged_archive_create": (_i, [_i, _i, _u64pp, _u64pp, ctypes.POINTER(_vp)]),
+    "sicn_ragged_archive_free": (None, [_vp]),
+    "sicn_ragged_archive_workspace_bytes": (_sz, [_vp]),
+    "sicn_ragged_archive_max_bytes": (_sz, [_vp]),
+    "sicn_ragged_archive_pack_async": (_i, [_vp, _vpp, _vpp, _u32, _vp, _sz, _vp, _vp, _sz, _vp]),
+    "sicn_ragged_archive_unpack_async": (_i, [_vp, _vp, _sz, _u32, _vpp, _vpp, _vp, _vp, _sz, _vp]),
+}
+
 _lib = None
 
 
@@ -204,7 +231,7 @@ def lib() -> ctypes.CDLL:
         except ImportError:      # symbol checks etc. work without it
             pass
         L = ctypes.CDLL(str(LIB_PATH))
-        for name, (res, args) in {**ABI, **CODEC_ABI, **CONVLAYER_ABI, **GDN_ABI, **RAGGED_ABI, **RAGGED_HYPER_ABI, **RAGGED_CODEC_ABI, **RAGGED_CTX_ABI}.items():
+        for name, (res, args) in {**ABI, **CODEC_ABI, **CONVLAYER_ABI, **GDN_ABI, **RAGGED_ABI, **RAGGED_HYPER_ABI, **RAGGED_CODEC_ABI, **RAGGED_CTX_ABI, **RAGGED_ARCHIVE_ABI}.items():
             fn = getattr(L, name)          # AttributeError if the ABI is incomplete
             fn.restype = res
             fn.argtypes = args

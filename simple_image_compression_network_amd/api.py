@@ -458,6 +458,7 @@ class RaggedNet:
             self._nbytes.append(int(q[4]))
         self._ws = None
         self._coders = {}           # compress()'s RaggedLatentCoders by stream length, made on first use
+        self._archives = {}         # compress_archive()'s RaggedArchives, one per coder
         self._crop = None           # cropped()'s RaggedCrop, made on first use
 
     def __del__(self):
@@ -576,6 +577,58 @@ class RaggedNet:
         coder.decode(latent, stream=stream)
         out, _ = self.run_layers(4, len(self.descs) - 1, latent, out=out, stream=stream)
         coder.check()
+        return out
+
+    def compress_archive(self, packed_in, stream_symbols=16384, stream=None):
+        """`compress` with the batch's containers as ONE byte string (codec.RaggedArchive, tag 0): layers 0-3, the ragged encoder and
+        the two launches that pack the archive on the device, enqueued back to back; exactly the archive's bytes travel to the host.
+        `codec.split_archive` of the result gives `compress`'s containers."""
+        from . import codec
+        key = stream_symbols if isinstance(stream_symbols, (int, str)) else tuple(stream_symbols)
+        if key not in self._coders:
+            self._coders[key] = self.latent_coder(stream_symbols)
+        coder = self._coders[key]
+        if key not in self._archives:
+            self._archives[key] = codec.RaggedArchive([coder], tag=0, device=self.device)
+        archive = self._archives[key]
+        latent, _ = self.run_layers(0, 3, packed_in, stream=stream)
+        coder.encode(latent, stream=stream)
+        archive.pack(stream=stream)
+        b = archive.bytes()
+        archive.check()             # an image the encoder refused (bit 0) raises, as compress does
+        return b
+
+    def decompress_archive(self, b, out=None, stream=None):
+        """An archive of this net's images (e.g. from `compress_archive`) -> the reconstructions as a ragged tensor of boundary 7:
+        upload, the two launches that unpack it, the ragged decoder, layers 4-7.  Raises when the work has finished if the archive
+        was refused or a container fails to decode."""
+        import torch
+        from . import codec
+        info = codec.archive_info(b)
+        heads = [h[0] for h in info["headers"]]
+        if info["n_sections"] != 1 or any(h is None or int(h.mode) != codec.RANSW for h in heads):
+            raise ValueError("not an archive of one rANS-W section")
+        if [s[0] for s in info["latent_shapes"]] != self.shapes(3) or info["image_sizes"] != self.sizes:
+            raise ValueError("the archive's image sizes or latent shapes are not this net's")
+        # one coder and one archive object per set of stream lengths, shared with compress_archive: creating them costs device
+        # allocations, table uploads and a synchronisation
+        lengths = [int(h.stream_symbols) for h in heads]
+        key = next((k for k, c in self._coders.items() if c.stream_symbols == lengths), None)
+        if key is None:
+            key = lengths[0] if len(set(lengths)) == 1 else tuple(lengths)
+            self._coders[key] = self.latent_coder(lengths)
+        coder = self._coders[key]
+        if key not in self._archives:
+            self._archives[key] = codec.RaggedArchive([coder], tag=0, device=self.device)
+        archive = self._archives[key]
+        valid, = archive.unpack(b, stream=stream)
+        latent = torch.empty(self.nbytes(3), dtype=torch.uint8, device=self.device)
+        coder.decode(latent, valid=valid, stream=stream)
+        out, _ = self.run_layers(4, len(self.descs) - 1, latent, out=out, stream=stream)
+        archive.check()
+        status = coder.dec_status[:, 0].cpu().tolist()      # the decoder's verdicts alone: the shared coder's encoder status is another call's
+        if any(status):
+            raise _lib.SicnError(-22 if any(v & ~128 for v in status) else -74, f"rANS-W decode status {status}")
         return out
 
 

@@ -10,7 +10,8 @@ from . import _lib
 
 RAW8, PACKED7, RANS, RANSW, RANSWC = 0, 1, 2, 3, 4
 __all__ = ["RAW8", "PACKED7", "RANS", "RANSW", "RANSWC", "encode_latent", "decode_latent", "parse_header", "encode_latents",
-           "decode_latents", "LatentCoder", "RaggedLatentCoder", "ContextCoder", "RaggedContextCoder", "auto_stream_symbols", "WSTREAM_SYMBOLS"]
+           "decode_latents", "LatentCoder", "RaggedLatentCoder", "ContextCoder", "RaggedContextCoder", "auto_stream_symbols", "WSTREAM_SYMBOLS",
+           "RaggedArchive", "split_archive", "archive_info"]
 
 
 WSTREAM_SYMBOLS = 16384   # SICN_CODEC_WSTREAM_SYMBOLS: the default (and longest) rANS-W stream
@@ -501,3 +502,157 @@ class RaggedContextCoder:
             raise err
         host = self.slot_buffer.cpu().numpy()
         return [host[int(im.slot_offset):int(im.slot_offset) + size].tobytes() for im, (_, size) in zip(self.images, status)]
+
+
+def _parse_archive(b):
+    """(RaggedArchiveInfo, sizes, offsets) of an archive held as `bytes` — sicn_ragged_archive_parse, host only.  The library reads
+    the caller's bytes in place: nothing is copied."""
+    L = _lib.lib()
+    if not isinstance(b, bytes):
+        b = bytes(b)
+    info = _lib.RaggedArchiveInfo()
+    _lib.check(L.sicn_ragged_archive_parse(b, len(b), ctypes.byref(info), None, None), "sicn_ragged_archive_parse")   # the counts
+    entries = int(info.n_images) * int(info.n_sections)
+    sizes, offsets = (ctypes.c_uint32 * entries)(), (ctypes.c_uint64 * entries)()
+    _lib.check(L.sicn_ragged_archive_parse(b, len(b), ctypes.byref(info), sizes, offsets), "sicn_ragged_archive_parse")
+    return info, list(sizes), list(offsets)
+
+
+def _split(b, info, sizes, offsets):
+    k = int(info.n_sections)
+    return [tuple(b[offsets[i * k + s]:offsets[i * k + s] + sizes[i * k + s]] for s in range(k)) for i in range(int(info.n_images))]
+
+
+def split_archive(b):
+    """An archive ("SICA", include/sicn_ragged_archive.h) -> per image, a tuple of its containers as `bytes`, one per section.
+    Host only; raises SicnError for a malformed archive."""
+    if not isinstance(b, bytes):
+        b = bytes(b)
+    return _split(b, *_parse_archive(b))
+
+
+def archive_info(b):
+    """What an archive says of itself: {"n_images", "n_sections", "tag", "total_bytes", "image_sizes": [(width, height)],
+    "latent_shapes": [per image, a tuple of (lat_h, lat_w, lat_c) per section], "headers": the CodecInfo of every container}.
+    Sizes and shapes are READ from each container's 48-byte header (an empty container gives None).  Host only; the archive is
+    parsed once."""
+    if not isinstance(b, bytes):
+        b = bytes(b)
+    info, sizes, offsets = _parse_archive(b)
+    k = int(info.n_sections)
+    headers = [tuple(parse_header(b[offsets[i * k + s]:offsets[i * k + s] + 48]) if sizes[i * k + s] else None for s in range(k))
+               for i in range(int(info.n_images))]
+    first = [next((h for h in hs if h is not None), None) for hs in headers]
+    return {"n_images": int(info.n_images), "n_sections": int(info.n_sections), "tag": int(info.tag), "total_bytes": int(info.total_bytes),
+            "image_sizes": [None if h is None else (int(h.image_width), int(h.image_height)) for h in first],
+            "latent_shapes": [tuple(None if h is None else (int(h.lat_h), int(h.lat_w), int(h.lat_c)) for h in hs) for hs in headers],
+            "headers": headers}
+
+
+class RaggedArchive:
+    """The containers of a ragged batch as ONE byte string (include/sicn_ragged_archive.h): packed on the device from the slot buffers
+    and encoder status arrays of one to four ragged coder objects of one batch as they lie — two launches, whatever the number of
+    images — and unpacked into those coders' own slot buffers with the `valid` arrays their `decode(..., valid=...)` takes, with two.
+    `coders`: RaggedLatentCoder / RaggedContextCoder objects (anything with `images[i].slot_offset / .slot_bytes`, `shapes`,
+    `slot_buffer` and `enc_status`), one section each, in the archive's section order.  `tag`: stored by pack, compared by unpack.
+    Same conventions as the coders: pack / unpack enqueue only; `bytes()` and `check()` synchronise."""
+
+    def __init__(self, coders, tag: int = 0, device=None):
+        import torch
+        L = _lib.lib()
+        self.coders = list(coders)
+        k = len(self.coders)
+        n = len(self.coders[0].shapes) if self.coders else 0
+        if not 1 <= k <= 4 or any(len(c.shapes) != n for c in self.coders):
+            raise ValueError("one to four coders of one batch")
+        self.n_images, self.n_sections, self.tag = n, k, int(tag) & 0xFFFFFFFF
+        u64 = ctypes.c_uint64 * max(n, 1)
+        self._off = [u64(*[int(im.slot_offset) for im in c.images[:n]]) for c in self.coders]
+        self._cap = [u64(*[int(im.slot_bytes) for im in c.images[:n]]) for c in self.coders]
+        pp = ctypes.POINTER(ctypes.c_uint64) * k
+        self.device = torch.device(device if device is not None else self.coders[0].device)
+        self._h = ctypes.c_void_p()
+        with torch.cuda.device(self.device):
+            _lib.check(L.sicn_ragged_archive_create(n, k, pp(*[ctypes.cast(a, ctypes.POINTER(ctypes.c_uint64)) for a in self._off]),
+                                                    pp(*[ctypes.cast(a, ctypes.POINTER(ctypes.c_uint64)) for a in self._cap]),
+                                                    ctypes.byref(self._h)), "sicn_ragged_archive_create")
+        self.max_bytes = int(L.sicn_ragged_archive_max_bytes(self._h))
+        self.ws = torch.empty(max(int(L.sicn_ragged_archive_workspace_bytes(self._h)), 256), dtype=torch.uint8, device=self.device)
+        self.status = torch.zeros(4, dtype=torch.int32, device=self.device)        # sicn_ragged_archive_status {error, first_bad, bytes}
+        self.buffer = None          # pack()'s device buffer of max_bytes, made on first use
+        self.valid = [torch.zeros((n, 2), dtype=torch.int32, device=self.device) for _ in range(k)]   # unpack()'s {error, bytes} per section
+        self._in = None             # the device copy of unpack()'s archive: alive until the next unpack
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None) and _lib._lib is not None:
+                _lib._lib.sicn_ragged_archive_free(self._h)
+                self._h = None
+        except Exception:       # interpreter shutdown
+            pass
+
+    def _ptrs(self, tensors):
+        return (ctypes.c_void_p * self.n_sections)(*[t.data_ptr() for t in tensors])
+
+    def pack(self, stream=None, out=None):
+        """The coders' slot buffers and encoder statuses -> `out` (default: this object's own buffer of `max_bytes`), self.status.
+        Enqueue only."""
+        import torch
+        if out is None:
+            if self.buffer is None:
+                self.buffer = torch.empty(self.max_bytes, dtype=torch.uint8, device=self.device)
+            out = self.buffer
+        if not (out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.dim() == 1):
+            raise TypeError("out must be a contiguous flat CUDA uint8 tensor")
+        self._out = out
+        _lib.check(_lib.lib().sicn_ragged_archive_pack_async(
+            self._h, self._ptrs([c.slot_buffer for c in self.coders]), self._ptrs([c.enc_status for c in self.coders]), self.tag,
+            ctypes.c_void_p(out.data_ptr()), out.numel(), ctypes.c_void_p(self.status.data_ptr()), ctypes.c_void_p(self.ws.data_ptr()),
+            self.ws.numel(), _stream_ptr(stream)), "sicn_ragged_archive_pack_async")
+        return out
+
+    def read_status(self):
+        """(error bits, first_bad, bytes) of the last pack / unpack (synchronises)."""
+        import torch
+        torch.cuda.synchronize(self.device)
+        e, bad, lo, hi = (int(v) & 0xFFFFFFFF for v in self.status.cpu().tolist())
+        return e, bad, lo | hi << 32
+
+    def check(self):
+        """Raises SicnError if the last pack / unpack reported an error (synchronises); the exception carries `.bits`, and `.first_bad`
+        (an entry, image * n_sections + section, or None) with `.image`."""
+        e, bad, _ = self.read_status()
+        if e:
+            err = _lib.SicnError(-28 if e == 4 else -22, f"ragged archive status bits {e:#x}, first bad entry {None if bad == 0xFFFFFFFF else bad}")
+            err.bits = e
+            err.first_bad = None if bad == 0xFFFFFFFF else bad
+            err.image = None if err.first_bad is None else err.first_bad // self.n_sections
+            raise err
+
+    def bytes(self):
+        """The archive of the last pack as `bytes`: exactly status.bytes travel to the host (synchronises; raises on bit 2)."""
+        e, _, nbytes = self.read_status()
+        if e & 4:
+            raise _lib.SicnError(-28, f"ragged archive: the output buffer is smaller than the {nbytes} bytes of the archive")
+        return self._out[:nbytes].cpu().numpy().tobytes()
+
+    def unpack(self, archive, stream=None):
+        """`archive` (`bytes`, or a flat CUDA uint8 tensor) -> the coders' own slot buffers; returns the `valid` arrays (device int32
+        [n][2], one per coder) to hand to `decode(..., valid=...)`.  A refused archive writes no slot byte and gives {error, 0} in every
+        entry, so the decoders report bit 8 per image; `check()` names the archive's own verdict.  Enqueue only."""
+        import torch
+        if not isinstance(archive, torch.Tensor):
+            host = torch.frombuffer(bytearray(archive), dtype=torch.uint8) if len(archive) else torch.empty(0, dtype=torch.uint8)
+            n_in = host.numel()
+            archive = torch.empty(max(n_in, 16), dtype=torch.uint8, device=self.device)
+            archive[:n_in].copy_(host)
+        else:
+            n_in = archive.numel()
+            if not (archive.is_cuda and archive.dtype == torch.uint8 and archive.is_contiguous() and archive.dim() == 1):
+                raise TypeError("archive must be bytes or a contiguous flat CUDA uint8 tensor")
+        self._in = archive
+        _lib.check(_lib.lib().sicn_ragged_archive_unpack_async(
+            self._h, ctypes.c_void_p(archive.data_ptr()), n_in, self.tag, self._ptrs([c.slot_buffer for c in self.coders]),
+            self._ptrs(self.valid), ctypes.c_void_p(self.status.data_ptr()), ctypes.c_void_p(self.ws.data_ptr()), self.ws.numel(),
+            _stream_ptr(stream)), "sicn_ragged_archive_unpack_async")
+        return list(self.valid)

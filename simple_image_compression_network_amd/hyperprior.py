@@ -208,6 +208,12 @@ class RaggedHyperpriorCodec:
         for net in (self.main, self.h_a, self.h_s):
             net.workspace()
         self._external = None       # the device copies of decode()'s external containers: alive until the next decode
+        # what an archive of this codec is tagged with: the GDN specification version (include/sicn_gdn.h) with GDN, 0 without — an
+        # archive written under another version of the activation, or by the other configuration, is refused (status bit 5)
+        self.use_gdn = bool(use_gdn)
+        self.archive_tag = int(api._lib.lib().sicn_gdn_spec_version()) if self.use_gdn else 0
+        self._archive = None        # codec.RaggedArchive over (z_coder, y_coder), made on first use
+        self._unpacked = False      # the last decode read an archive: check() reports its verdict first
 
     def _scale_map(self, z):
         self.h_s.run_layers(0, 1, z, out=self.s_full)
@@ -235,10 +241,49 @@ class RaggedHyperpriorCodec:
             host[int(im.slot_offset):int(im.slot_offset) + len(c)] = torch.frombuffer(bytearray(c), dtype=torch.uint8)
         return host.to(self.device), torch.tensor([[0, len(c)] for c in containers], dtype=torch.int32).to(self.device)
 
-    def decode(self, out=None, z_containers=None, y_containers=None):
-        """Containers (default: the last encode's; else lists of `bytes`, one per image) -> the reconstructions, a ragged tensor of
-        main's boundary 7 (`main.cropped(out)` cuts them to the images' sizes).  Enqueue only."""
+    def _ragged_archive(self):
+        if self._archive is None:
+            self._archive = codec.RaggedArchive([self.z_coder, self.y_coder], tag=self.archive_tag, device=self.device)
+        return self._archive
+
+    def archive(self):
+        """The containers of the last encode as ONE byte string (codec.RaggedArchive: sections z and y, tag = the GDN specification
+        version with GDN, 0 without), packed on the device; `codec.split_archive` gives `containers()`.  Synchronises; raises if the
+        encode reported an error."""
+        ar = self._ragged_archive()
+        ar.pack()
+        b = ar.bytes()
+        ar.check()
+        return b
+
+    @classmethod
+    def from_archive(cls, b, seed: int = 0, device="cuda", use_gdn=None, main_params=None):
+        """The codec for the images an archive names: sizes and the z stream lengths are READ from the z containers' headers, and
+        `use_gdn` (unless given) from the tag — 0 means an archive written without GDN.  `decode(archive=b)` then reads it."""
+        info = codec.archive_info(b)
+        heads = [h[0] for h in info["headers"]]
+        if info["n_sections"] != 2 or any(h is None for h in heads):
+            raise ValueError("not a hyperprior archive: need the sections z and y of every image")
+        return cls(info["image_sizes"], seed=seed, device=device, use_gdn=info["tag"] != 0 if use_gdn is None else use_gdn,
+                   main_params=main_params, z_stream_symbols=[int(h.stream_symbols) for h in heads])
+
+    def decode(self, out=None, z_containers=None, y_containers=None, archive=None):
+        """Containers (default: the last encode's; else lists of `bytes`, one per image; or `archive`, what `archive()` returned) ->
+        the reconstructions, a ragged tensor of main's boundary 7 (`main.cropped(out)` cuts them to the images' sizes).  An archive is
+        unpacked on the device into the coders' own slots; one whose tag is not this codec's (another GDN specification version, or
+        the other `use_gdn`) is refused as a whole: `check()` raises with bit 5.  Enqueue only."""
         keep = []
+        self._unpacked = archive is not None
+        if archive is not None:
+            if z_containers is not None or y_containers is not None:
+                raise ValueError("either an archive or lists of containers")
+            z_valid, y_valid = self._ragged_archive().unpack(archive)
+            self.z_coder.decode(self.z_hat, valid=z_valid)
+            self._scale_map(self.z_hat)
+            self.y_coder.decode(self.y_hat, self.s, valid=y_valid)
+            self._external = keep
+            out, _ = self.main.run_layers(4, 7, self.y_hat, out=out)
+            return out
         if z_containers is None:
             self.z_coder.decode(self.z_hat)
         else:
@@ -262,7 +307,9 @@ class RaggedHyperpriorCodec:
 
     def check(self):
         """Raises SicnError if the last encode / decode reported an error (synchronises); a y coder's error names its image
-        (`.image` of the exception, and in its text)."""
+        (`.image` of the exception, and in its text); a refused archive raises first, with its bits (`.bits`)."""
+        if self._unpacked:
+            self._archive.check()
         self.z_coder.check()
         try:
             self.y_coder.check()

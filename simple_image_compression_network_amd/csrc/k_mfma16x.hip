@@ -4,21 +4,32 @@
 // reads per 32 MFMAs, every workgroup streams its own copy of the weights; the passes are issue-bound and a bare loop of that
 // structure tops out at 3.44 POP/s (tools/microbench/wide_dma.hip, profiles/r03_microbench_wide_dma.txt).  The same
 // microbenchmark says what the alternative keeps once it carries a real pass's load: ONE wave per SIMD with 128 positions x 128
-// channels per wave (256 accumulators pinned in AGPRs, 16 fragment reads per 64 MFMAs), 4 LDS-DMA requests, a counted wait and a
+// channels per wave (256 accumulators pinned in registers, 16 fragment reads per 64 MFMAs), 4 LDS-DMA requests, a counted wait and a
 // workgroup barrier per pass: 3.75 POP/s, +9 %.  Round 2's k_conv128w had that tile but lost it all in its per-tile prologue and
 // epilogue, which nothing covers when a SIMD holds a single wave.  Here
 //   * one workgroup of 4 waves per CU owns 16 x 32 positions (wave w = rows 4w .. 4w+3) and is PERSISTENT: it walks through its
 //     share of the tile list, the input of the next tile arrives under the current one, the weight stream wraps: no prologue;
 //   * the ACCUMULATOR HAND-OVER (read, bias, ReLU, pack, store of a finished tile / deconv phase) is woven into the first pass
-//     of the next one: that pass's MFMAs take C = 0 and overwrite an accumulator right after it has been read out (in-kernel
+//     of the next one: that pass's MFMAs take C = bias and overwrite an accumulator right after it has been read out (in-kernel
 //     stamps: done as a block between two tiles the hand-over was 6350 cycles = 10 % of a conv tile, with a single wave per SIMD
-//     every VALU instruction costs 4 issue cycles).  The bias is added in the pack (v_pk_add_u16 on the byte that sits in the
-//     high half of a 16-bit lane), so the accumulators are never initialised at all;
+//     every VALU instruction costs 4 issue cycles).  The bias is that pass's C operand, so it costs no instruction at all;
+//   * the REGISTER FILES of k_deconv_x (four hand-overs per tile): the two operand-fragment sets pa / wa / pb / wb (32 x 4 = 128
+//     registers) live in AGPRs — nothing but ds_read_b128 ("=a") writes them and nothing but an MFMA's SrcA / SrcB ("a") reads them,
+//     both of which gfx950 takes from either file — and that frees the VGPRs for the accumulators, which the hand-over's pack
+//     (VALU: VGPR sources only) then reads in place.  Accumulator columns j >= JV and their bias sit in VGPRs (C and D of an MFMA
+//     share a file), columns j < JV in AGPRs:
+//         k_deconv_x  JV = 2, fragments in AGPRs:  255 VGPRs, 200 AGPRs (128 fragments + 2 x 36)
+//         k_conv_x    JV = 7, fragments in VGPRs:  225 VGPRs, 252 AGPRs (one hand-over per tile: with JV = 3 and the fragments in
+//                     AGPRs — 256 + 232 registers, no scratch — layers 1 / 2 measured the same to 0.1 %, so it keeps this map)
+//     Per hand-over (64 accumulator tiles, counted in this file's ISA): 256 v_max_i32_sdwa (the pack: one per register, the
+//     minimum) + v_accvgpr_read_b32: 64 (deconv), 224 (conv; the deconv's number too until its fragments moved); 16 stores.  No
+//     scratch, no VGPR spill, 38 / 40 spilled SGPRs (tests/test_wide_regfile_build.py holds all of that, and each kernel's
+//     fragment register file, to the shipped ISA);
 //   * the tile list is dealt STATICALLY (XCD x works through the contiguous range [x * per, (x + 1) * per) of the list, its 32
 //     workgroups interleaved): with one workgroup per CU all tiles take the same time, so there is no scheduler state at all;
 //   * one weight ring per CU (not two): half the weight requests per MFMA; a 16 x 32 tile has 10 % less halo than two 8 x 32;
 //   * every LDS read is an asm statement with an immediate offset (no address arithmetic in the loop) and hand-placed waits, the
-//     MFMAs are asm statements with the accumulator tied to an AGPR: the order written is the order issued;
+//     MFMAs are asm statements with the accumulator tied to its register ("+a" / "+v"): the order written is the order issued;
 //   * the ring has 10 slots = 5 passes: a 50-pass tile is 0 mod 5, so every slot and every offset of the unrolled tile is a
 //     compile-time constant, and 3 passes' requests may be in flight at a barrier.
 // Conv:   4 parity planes of one channel group (18 x 34 positions x 32 B, 20 KiB each) with a rolling refresh + ring = 120 KB.
@@ -44,25 +55,43 @@ constexpr int NPASS = 50;                                                 // pas
 
 typedef __attribute__((address_space(3))) uint8_t lds_u8;   // LDS pointers stay 32-bit (a generic pointer costs a null check per cast)
 
-#define SICN_MFMA_A(ACC, A, B) asm volatile("v_mfma_i32_16x16x64_i8 %0, %1, %2, %0" : "+a"(ACC) : "v"(A), "v"(B))
+#define SICN_MFMA_A(ACC, A, B) asm volatile("v_mfma_i32_16x16x64_i8 %0, %1, %2, %0" : "+a"(ACC) : "a"(A), "a"(B))
+#define SICN_MFMA_A_FV(ACC, A, B) asm volatile("v_mfma_i32_16x16x64_i8 %0, %1, %2, %0" : "+a"(ACC) : "v"(A), "v"(B))
 // C = bias: the accumulator starts here.  The D operand is tied all the same ("+a"): the new value must live in the AGPRs of the old
 // one, and whatever still wants the old value (the hand-over's reads) is thereby ordered in front of this statement.  (With an
 // output-only operand hipcc gave the new values other registers and moved them through VGPRs with v_accvgpr_read right behind the
 // MFMA — inside the MFMA's latency, where the hazard recogniser does not look for an asm statement: wrong bytes.)
-#define SICN_MFMA_AC(ACC, A, B, C) asm volatile("v_mfma_i32_16x16x64_i8 %0, %1, %2, %3" : "+a"(ACC) : "v"(A), "v"(B), "a"(C))
-// accumulator tiles j = 7 (8 of the 64) live in VGPRs: that leaves 28 AGPRs for the bias of tiles j = 0 .. 6, which the first pass
-// of a tile / phase takes as its C operand (C and D of an MFMA must sit in the same register file), and those 8 tiles need no
-// v_accvgpr_read at the hand-over
-#define SICN_MFMA_V(ACC, A, B) asm volatile("v_mfma_i32_16x16x64_i8 %0, %1, %2, %0" : "+v"(ACC) : "v"(A), "v"(B))
-#define SICN_MFMA_VC(ACC, A, B, C) asm volatile("v_mfma_i32_16x16x64_i8 %0, %1, %2, %3" : "+v"(ACC) : "v"(A), "v"(B), "v"(C))
-constexpr int JV = 7;   // accumulator tiles j >= JV live in VGPRs
+#define SICN_MFMA_AC(ACC, A, B, C) asm volatile("v_mfma_i32_16x16x64_i8 %0, %1, %2, %3" : "+a"(ACC) : "a"(A), "a"(B), "a"(C))
+#define SICN_MFMA_AC_FV(ACC, A, B, C) asm volatile("v_mfma_i32_16x16x64_i8 %0, %1, %2, %3" : "+a"(ACC) : "v"(A), "v"(B), "a"(C))
+// accumulator columns j >= JV (8 tiles each) live in VGPRs, with their 4 bias registers: the first pass of a tile / phase takes the
+// bias as its C operand (C and D of an MFMA must sit in the same register file), and the hand-over packs those tiles straight from
+// their registers, without a v_accvgpr_read.  A and B come from the fragments' register file: AGPRs (the plain macros) or VGPRs
+// (_FV), see frag_agpr.
+#define SICN_MFMA_V(ACC, A, B) asm volatile("v_mfma_i32_16x16x64_i8 %0, %1, %2, %0" : "+v"(ACC) : "a"(A), "a"(B))
+#define SICN_MFMA_V_FV(ACC, A, B) asm volatile("v_mfma_i32_16x16x64_i8 %0, %1, %2, %0" : "+v"(ACC) : "v"(A), "v"(B))
+#define SICN_MFMA_VC(ACC, A, B, C) asm volatile("v_mfma_i32_16x16x64_i8 %0, %1, %2, %3" : "+v"(ACC) : "a"(A), "a"(B), "v"(C))
+#define SICN_MFMA_VC_FV(ACC, A, B, C) asm volatile("v_mfma_i32_16x16x64_i8 %0, %1, %2, %3" : "+v"(ACC) : "v"(A), "v"(B), "v"(C))
+// the fragments' register file follows JV: with 6 or 7 columns in AGPRs there is no room for 128 fragment registers next to them
+__host__ __device__ constexpr bool frag_agpr(int JV) { return JV < 6; }
+// JV is a template parameter of the kernels: a column is 8 x 4 + 4 = 36 registers.  With the fragments in AGPRs the 256 VGPRs have
+// room for 6 columns in k_deconv_x next to its addresses, offsets and packed results (5 in k_conv_x, whose plane offsets poff[4][5]
+// take 20 more); with the fragments in VGPRs (JV = 7: the map both kernels had) for one.
+constexpr int JV_CONV = 7, JV_DECONV = 2;
 
-template <int OFF>
+// A fragment read.  AG: the result goes to AGPRs and stays there until the MFMAs of the NEXT pass read it.  Hazards: the pass's
+// lgkmcnt(0) + barrier covers the read before an MFMA uses it (isa_hazards.py rule F).  The other direction — the LDS return
+// writing a register an in-flight MFMA still reads as SrcA / SrcB — has no entry in LLVM's GCNHazardRecognizer for the gfx940
+// family (an MFMA reads A and B as it issues; the tables only know its SrcC / D), and the double buffer puts a whole pass (64
+// MFMAs and a barrier) between the last MFMA that reads a fragment set and the first read that overwrites it anyway.
+template <int OFF, bool AG>
 __device__ __forceinline__ v4i lds_read(uint32_t addr)
 {
     static_assert(OFF >= 0 && OFF < 65536, "ds_read offset field");
     v4i v;
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF));
+    if constexpr (AG)
+        asm volatile("ds_read_b128 %0, %1 offset:%2" : "=a"(v) : "v"(addr), "n"(OFF));
+    else
+        asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF));
     return v;
 }
 
@@ -94,6 +123,7 @@ __device__ __forceinline__ uint32_t pack4_sdwa(const v4i &a, int floor32)
 struct BiasX {
     v4i c[8];
 };
+template <int JV>
 __device__ __forceinline__ void load_bias_x(BiasX &b, const int8_t *bias, int g)
 {
 #pragma unroll
@@ -113,14 +143,14 @@ __device__ __forceinline__ void load_bias_x(BiasX &b, const int8_t *bias, int g)
 
 // ---- one pass: 64 MFMAs on the current fragments (pc, wc); rd(r) issues read r (0 .. 15) of the next pass's fragments, dma(k)
 // ---- request k (0 .. 3) of this pass ----------------------------------------------------------------------------------------
-//   KIND 0: accumulate.   KIND 2: the accumulators start here (C = 0), and every accumulator is read out, biased, packed and
+//   KIND 0: accumulate.   KIND 2: the accumulators start here (C = bias), and every accumulator is read out / packed in place and
 //   stored (hand-over of the tile / phase that has just ended) right before the MFMA that overwrites it.
 //   VM: requests that may stay in flight at the barrier; EXTRA: plus the hand-over's stores while `stores` (they are younger than
 //   what the wait is after during the first FLIGHT passes behind a hand-over: counted, not waited for)
 //   (Tried and removed: keeping the packed results in VGPRs and storing them two per pass behind the hand-over.  Once the
 //   bias registers were gone it fitted — 204 - 220 VGPRs, no scratch — and the hand-over pass did get 400 cycles shorter, but the
 //   deconv tile got 1300 cycles LONGER: a store costs its ~80 issue cycles wherever it sits.  The cost model is additive.)
-template <int KIND, int VM, int EXTRA, bool NT, class Rd, class Dma>
+template <int JV, int KIND, int VM, int EXTRA, bool NT, class Rd, class Dma>
 __device__ __forceinline__ void pass_x(v4i (&acc)[8][8], const v4i (&pc)[8], const v4i (&wc)[8], Rd rd, Dma dma, bool stores, const HandX &h,
                                        const BiasX &bias)
 {
@@ -131,10 +161,17 @@ __device__ __forceinline__ void pass_x(v4i (&acc)[8][8], const v4i (&pc)[8], con
 #pragma unroll
             for (int i = 0; i < 8; i++) {
                 const int m = j * 8 + i;
-                if (j < JV)
-                    SICN_MFMA_A(acc[i][j], wc[j], pc[i]);
-                else
-                    SICN_MFMA_V(acc[i][j], wc[j], pc[i]);
+                if constexpr (frag_agpr(JV)) {
+                    if (j < JV)
+                        SICN_MFMA_A(acc[i][j], wc[j], pc[i]);
+                    else
+                        SICN_MFMA_V(acc[i][j], wc[j], pc[i]);
+                } else {
+                    if (j < JV)
+                        SICN_MFMA_A_FV(acc[i][j], wc[j], pc[i]);
+                    else
+                        SICN_MFMA_V_FV(acc[i][j], wc[j], pc[i]);
+                }
                 // the 16 reads of the next pass: one behind every third MFMA, the last one behind MFMA 47
                 if (m % 3 == 2 && issued < 16) {
                     switch (issued) {
@@ -163,7 +200,7 @@ __device__ __forceinline__ void pass_x(v4i (&acc)[8][8], const v4i (&pc)[8], con
                 const int k = 2 * i + J;
                 v4i old[4];
 #pragma unroll
-                for (int d = 0; d < 4; d++) old[d] = acc[i][4 * J + d];   // read out (v_accvgpr_read) in front of the tied MFMA below
+                for (int d = 0; d < 4; d++) old[d] = acc[i][4 * J + d];   // AGPR tiles: read out (v_accvgpr_read) in front of the tied MFMA below
                 v4i v;
                 // a tile that lives in VGPRs is packed straight from its registers, BEFORE the tied MFMA overwrites them (packed
                 // behind it, hipcc would copy the four registers first)
@@ -175,10 +212,17 @@ __device__ __forceinline__ void pass_x(v4i (&acc)[8][8], const v4i (&pc)[8], con
                     }
 #pragma unroll
                 for (int d = 0; d < 4; d++) {
-                    if (4 * J + d < JV)
-                        SICN_MFMA_AC(acc[i][4 * J + d], wc[4 * J + d], pc[i], bias.c[4 * J + d]);
-                    else
-                        SICN_MFMA_VC(acc[i][4 * J + d], wc[4 * J + d], pc[i], bias.c[4 * J + d]);
+                    if constexpr (frag_agpr(JV)) {
+                        if (4 * J + d < JV)
+                            SICN_MFMA_AC(acc[i][4 * J + d], wc[4 * J + d], pc[i], bias.c[4 * J + d]);
+                        else
+                            SICN_MFMA_VC(acc[i][4 * J + d], wc[4 * J + d], pc[i], bias.c[4 * J + d]);
+                    } else {
+                        if (4 * J + d < JV)
+                            SICN_MFMA_AC_FV(acc[i][4 * J + d], wc[4 * J + d], pc[i], bias.c[4 * J + d]);
+                        else
+                            SICN_MFMA_VC_FV(acc[i][4 * J + d], wc[4 * J + d], pc[i], bias.c[4 * J + d]);
+                    }
                 }
 #pragma unroll
                 for (int d = 0; d < 4; d++)
@@ -476,7 +520,7 @@ __device__ __forceinline__ void set_poff_x(uint32_t (&poff)[4][SLOTS], const Ten
 }
 
 // pass T (0 .. 49) of a conv tile: the window pass is T % 25, the window T / 25
-template <int T, int KIND, bool NT>
+template <int T, int KIND, bool NT, int JV>
 __device__ __forceinline__ void conv_pass_x(v4i (&acc)[8][8], const v4i (&pc)[8], const v4i (&wc)[8], v4i (&pn)[8], v4i (&wn)[8],
                                             const ConvXCtx &c, const uint32_t (&poff)[4][SLOTS], bool stores, const HandX &h,
                                             const BiasX &bias)
@@ -491,9 +535,9 @@ __device__ __forceinline__ void conv_pass_x(v4i (&acc)[8][8], const v4i (&pc)[8]
     auto rd = [&](auto r_tag) {
         constexpr int R = decltype(r_tag)::value;
         if constexpr (R < 8)
-            pn[R] = lds_read<((R >> 1) * PX + (R & 1) * 16) * 32>(pixn);
+            pn[R] = lds_read<((R >> 1) * PX + (R & 1) * 16) * 32, frag_agpr(JV)>(pixn);
         else
-            wn[R - 8] = lds_read<slotN * TB + (R - 8) * 16 * 32>(wtn);
+            wn[R - 8] = lds_read<slotN * TB + (R - 8) * 16 * 32, frag_agpr(JV)>(wtn);
     };
     // ---- this pass's requests: weight tiles 5 passes ahead, the plane pieces of the schedule -------------------------------
     auto dma = [&](auto idx_tag) {
@@ -514,24 +558,24 @@ __device__ __forceinline__ void conv_pass_x(v4i (&acc)[8][8], const v4i (&pc)[8]
         }
     };
     constexpr int VM = in_flight_x(P);
-    pass_x<KIND, VM, (T < FLIGHT ? NSTORE : 0), NT>(acc, pc, wc, rd, dma, stores, h, bias);
+    pass_x<JV, KIND, VM, (T < FLIGHT ? NSTORE : 0), NT>(acc, pc, wc, rd, dma, stores, h, bias);
 }
 
-template <int T, int END, bool NT>
+template <int T, int END, bool NT, int JV>
 __device__ __forceinline__ void conv_passes_x(v4i (&acc)[8][8], v4i (&pa)[8], v4i (&wa)[8], v4i (&pb)[8], v4i (&wb)[8], const ConvXCtx &c,
                                               const uint32_t (&poff)[4][SLOTS], bool stores, const HandX &h, const BiasX &bias)
 {
     if constexpr ((T & 1) == 0)
-        conv_pass_x<T, 0, NT>(acc, pa, wa, pb, wb, c, poff, stores, h, bias);
+        conv_pass_x<T, 0, NT, JV>(acc, pa, wa, pb, wb, c, poff, stores, h, bias);
     else
-        conv_pass_x<T, 0, NT>(acc, pb, wb, pa, wa, c, poff, stores, h, bias);
-    if constexpr (T + 1 < END) conv_passes_x<T + 1, END, NT>(acc, pa, wa, pb, wb, c, poff, stores, h, bias);
+        conv_pass_x<T, 0, NT, JV>(acc, pb, wb, pa, wa, c, poff, stores, h, bias);
+    if constexpr (T + 1 < END) conv_passes_x<T + 1, END, NT, JV>(acc, pa, wa, pb, wb, c, poff, stores, h, bias);
 }
 
 constexpr size_t CONV_LDS = 4 * PLANE + RING * TB;
 constexpr int SWITCH_T = 25 + 16;                 // from this pass of a tile on, every plane request belongs to the next tile
 
-template <bool NT>
+template <bool NT, int JV>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void k_conv_x(
     const uint8_t *__restrict__ in, uint8_t *__restrict__ out, const int8_t *__restrict__ wstream, const int8_t *__restrict__ bias_g, int IW,
     int IH, int OW, int OH, int tiles_x, int n_tiles, int n_images, int in_layout, int out_layout, uint32_t act_floor, int n_xcd,
@@ -573,7 +617,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                  im.grp,
                  hi};
     BiasX bias;
-    load_bias_x(bias, bias_g, g);
+    load_bias_x<JV>(bias, bias_g, g);
     // ---- prologue of the FIRST tile only: what the previous window's NEXT0 requests would have brought (planes 0, 1 and
     // ---- slots 0 .. 2 of plane 2 of group 0) + the weight tiles of passes 0 .. 4 -------------------------------------------
     {
@@ -593,7 +637,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     v4i pa[8], wa[8], pb[8], wb[8];
     {   // fragments of pass 0: taps 0 / 1 of group 0, ring slots 0 / 1
         const uint32_t p0 = ctx.lane_pix + (hi ? tap_off_x(1) : tap_off_x(0));
-#define SICN_R(R) pa[R] = lds_read<((R >> 1) * PX + (R & 1) * 16) * 32>(p0); wa[R] = lds_read<R * 16 * 32>(ctx.lane_wt);
+#define SICN_R(R) pa[R] = lds_read<((R >> 1) * PX + (R & 1) * 16) * 32, frag_agpr(JV)>(p0); wa[R] = lds_read<R * 16 * 32, frag_agpr(JV)>(ctx.lane_wt);
         SICN_R(0) SICN_R(1) SICN_R(2) SICN_R(3) SICN_R(4) SICN_R(5) SICN_R(6) SICN_R(7)
 #undef SICN_R
         // pass 0's requests overwrite the ring slots just read (prefetch distance = ring size): all four waves must have read them
@@ -619,7 +663,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                 asm volatile("" : "+v"(acc[i][j]));
         }
     asm volatile("s_nop 3" ::: "memory");   // v_accvgpr_write / v_mov -> asm MFMA reading it as SrcC
-    conv_pass_x<0, 0, NT>(acc, pa, wa, pb, wb, ctx, poff, false, h, bias);
+    conv_pass_x<0, 0, NT, JV>(acc, pa, wa, pb, wb, ctx, poff, false, h, bias);
     bool stores = false;   // a hand-over's stores may be in flight (not in the first tile)
     int tile_no = 0;         // tiles this workgroup has finished (DealX: the mailbox's sequence numbers)
     uint32_t deal_tk = DEAL_PENDING;
@@ -637,21 +681,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         // the next tile: tile 1 is the static deal's; from then on it was published in the mailbox while the previous tile ran (DealX)
         int next = item + stride;
         const bool dyn = dl.ws != 0, later = dyn && tile_no > 0;
-        conv_passes_x<1, 3, NT>(acc, pa, wa, pb, wb, ctx, poff, stores, h, bias);
+        conv_passes_x<1, 3, NT, JV>(acc, pa, wa, pb, wb, ctx, poff, stores, h, bias);
         if (later) deal_request(dl, deal_mail);
-        conv_passes_x<3, 7, NT>(acc, pa, wa, pb, wb, ctx, poff, stores, h, bias);
+        conv_passes_x<3, 7, NT, JV>(acc, pa, wa, pb, wb, ctx, poff, stores, h, bias);
         if (later) next = deal_take(dl, deal_mail, (uint32_t)tile_no + 1u);
         // a ticket is only taken for a tile this workgroup will get to: the one behind `next`
         const bool has_next = dyn ? (next >= 0 && (tile_no > 0 || next < item_end)) : next < item_end;
         const bool goes_on = dyn && has_next && w == 0 && !deal_done;
         if (goes_on) deal_ticket_issue(dl, dl.xcd, deal_tk, lane);
-        conv_passes_x<7, 13, NT>(acc, pa, wa, pb, wb, ctx, poff, stores, h, bias);
+        conv_passes_x<7, 13, NT, JV>(acc, pa, wa, pb, wb, ctx, poff, stores, h, bias);
         if (goes_on) {
             const int it2 = deal_resolve(dl, deal_tk, lane);
             deal_publish(dl, (uint32_t)tile_no + 2u, it2, lane);
             deal_done = it2 < 0;
         }
-        conv_passes_x<13, SWITCH_T, NT>(acc, pa, wa, pb, wb, ctx, poff, stores, h, bias);
+        conv_passes_x<13, SWITCH_T, NT, JV>(acc, pa, wa, pb, wb, ctx, poff, stores, h, bias);
         // every plane request for THIS tile has been issued: the rest of the tile fetches the next tile's first group
         const TileX tn = coord(has_next ? next : item);
         int lane_l;   // recomputed, not kept
@@ -661,11 +705,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         // where the finished tile goes
         h.ro = __builtin_amdgcn_make_buffer_rsrc((void *)(out + (size_t)tc.img * out_img_bytes), 0, out_img_bytes, 0x00020000);
         set_out_off_x(h.off, om, tc, w, lane_l, OW, OH, 1);
-        conv_passes_x<SWITCH_T, NPASS, NT>(acc, pa, wa, pb, wb, ctx, poff, false, h, bias);
+        conv_passes_x<SWITCH_T, NPASS, NT, JV>(acc, pa, wa, pb, wb, ctx, poff, false, h, bias);
         // pass 0 of the next tile with the hand-over of this one woven in (after the last tile: the same pass on zero-filled
         // planes, whose results nobody reads — one pass in 32 tiles, and the tile loop stays one body)
-        asm volatile("s_nop 7" ::: "memory");   // the last MFMAs' results -> v_accvgpr_read
-        conv_pass_x<0, 2, NT>(acc, pa, wa, pb, wb, ctx, poff, true, h, bias);
+        asm volatile("s_nop 7" ::: "memory");   // the last MFMAs' results -> v_accvgpr_read (AGPR tiles) / the SDWA pack (VGPR tiles)
+        conv_pass_x<0, 2, NT, JV>(acc, pa, wa, pb, wb, ctx, poff, true, h, bias);
         stores = true;
         if (!has_next) break;
         item = next;
@@ -774,7 +818,7 @@ __device__ __forceinline__ void set_dpoff_x(uint32_t (&poff)[SLOTS], const Tenso
     }
 }
 
-template <int T, int KIND, bool NT>
+template <int T, int KIND, bool NT, int JV>
 __device__ __forceinline__ void deconv_pass_x(v4i (&acc)[8][8], const v4i (&pc)[8], const v4i (&wc)[8], v4i (&pn)[8], v4i (&wn)[8],
                                               const DeconvXCtx &c, const uint32_t (&poff_cur)[SLOTS], const uint32_t (&poff_next)[SLOTS],
                                               bool stores, const HandX &h, const BiasX &bias)
@@ -789,9 +833,9 @@ __device__ __forceinline__ void deconv_pass_x(v4i (&acc)[8][8], const v4i (&pc)[
     auto rd = [&](auto r_tag) {
         constexpr int R = decltype(r_tag)::value;
         if constexpr (R < 8)
-            pn[R] = lds_read<toffN + ((R >> 1) * PX + (R & 1) * 16) * 32>(pixn);
+            pn[R] = lds_read<toffN + ((R >> 1) * PX + (R & 1) * 16) * 32, frag_agpr(JV)>(pixn);
         else
-            wn[R - 8] = lds_read<slotN * TB + (R - 8) * 16 * 32>(wtn);
+            wn[R - 8] = lds_read<slotN * TB + (R - 8) * 16 * 32, frag_agpr(JV)>(wtn);
     };
     auto dma = [&](auto idx_tag) {
         constexpr int idx = decltype(idx_tag)::value;   // 0, 1: weight tiles; 2: the patch piece; 3: nothing
@@ -815,10 +859,10 @@ __device__ __forceinline__ void deconv_pass_x(v4i (&acc)[8][8], const v4i (&pc)[
     // stores of a hand-over are counted, not waited for, during the FLIGHT passes that start with it
     constexpr bool behind = dphase_start(T) || dphase_start((T + NPASS - 1) % NPASS) || dphase_start((T + NPASS - 2) % NPASS);
     static_assert(FLIGHT == 3, "`behind` spells out FLIGHT passes");
-    pass_x<KIND, d_in_flight(T), (behind ? NSTORE : 0), NT>(acc, pc, wc, rd, dma, stores, h, bias);
+    pass_x<JV, KIND, d_in_flight(T), (behind ? NSTORE : 0), NT>(acc, pc, wc, rd, dma, stores, h, bias);
 }
 
-template <bool NT>
+template <bool NT, int JV>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void k_deconv_x(
     const uint8_t *__restrict__ in, uint8_t *__restrict__ out, const int8_t *__restrict__ wstream, const int8_t *__restrict__ bias_g, int IW,
     int IH, int OW, int OH, int tiles_x, int n_tiles, int n_images, int in_layout, int out_layout, uint32_t act_floor, int n_xcd,
@@ -863,7 +907,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                    (uint32_t)PAIRBUF,
                    (uint32_t)(2 * PAIRBUF)};
     BiasX bias;
-    load_bias_x(bias, bias_g, g);
+    load_bias_x<JV>(bias, bias_g, g);
     // ---- prologue of the FIRST tile only: its pair 0, pieces 0 .. 4 of its pair 1, the weight tiles of passes 0 .. 4 --------
     {
         __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)ctx.cur_img, 0, in_img_bytes, 0x00020000);
@@ -883,7 +927,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     v4i pa[8], wa[8], pb[8], wb[8];
     {   // fragments of pass 0: phase 0, tap 0, pair 0 (buffer 0), ring slots 0 / 1
         const uint32_t p0 = ctx.lane_pix;
-#define SICN_R(R) pa[R] = lds_read<((R >> 1) * PX + (R & 1) * 16) * 32>(p0); wa[R] = lds_read<R * 16 * 32>(ctx.lane_wt);
+#define SICN_R(R) pa[R] = lds_read<((R >> 1) * PX + (R & 1) * 16) * 32, frag_agpr(JV)>(p0); wa[R] = lds_read<R * 16 * 32, frag_agpr(JV)>(ctx.lane_wt);
         SICN_R(0) SICN_R(1) SICN_R(2) SICN_R(3) SICN_R(4) SICN_R(5) SICN_R(6) SICN_R(7)
 #undef SICN_R
         // pass 0's requests overwrite the ring slots just read (prefetch distance = ring size): all four waves must have read them
@@ -913,7 +957,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                 asm volatile("" : "+v"(acc[i][j]));
         }
     asm volatile("s_nop 3" ::: "memory");   // v_accvgpr_write / v_mov -> asm MFMA reading it as SrcC
-    deconv_pass_x<0, 0, NT>(acc, pa, wa, pb, wb, ctx, poff_cur, poff_next, false, h, bias);
+    deconv_pass_x<0, 0, NT, JV>(acc, pa, wa, pb, wb, ctx, poff_cur, poff_next, false, h, bias);
     bool stores = false;   // a hand-over's stores may be in flight (in the first tile: from its phase 1 on)
     int tile_no = 0;         // tiles this workgroup has finished (DealX: the mailbox's sequence numbers)
     uint32_t deal_tk = DEAL_PENDING;
@@ -930,9 +974,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         // passes 1 .. 5; from pass 6 on the patch requests belong to the next tile
 #define SICN_DP(T, ST) \
     if constexpr (((T) & 1) == 0) \
-        deconv_pass_x<T, dphase_start(T) ? 2 : 0, NT>(acc, pa, wa, pb, wb, ctx, poff_cur, poff_next, ST, h, bias); \
+        deconv_pass_x<T, dphase_start(T) ? 2 : 0, NT, JV>(acc, pa, wa, pb, wb, ctx, poff_cur, poff_next, ST, h, bias); \
     else \
-        deconv_pass_x<T, dphase_start(T) ? 2 : 0, NT>(acc, pb, wb, pa, wa, ctx, poff_cur, poff_next, ST, h, bias);
+        deconv_pass_x<T, dphase_start(T) ? 2 : 0, NT, JV>(acc, pb, wb, pa, wa, ctx, poff_cur, poff_next, ST, h, bias);
         // `stores`: passes 1 .. 7 store the previous tile's last phase (none in the first tile), and a wait counts the stores of
         // the passes up to FLIGHT - 1 back
         // the next tile (its patch is requested from pass 6 on): tile 1 is the static deal's, from then on it comes from the mailbox,
@@ -971,7 +1015,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         }
         SICN_DP(15, true) SICN_DP(16, true) SICN_DP(17, true)
         h.soff = phase_soff(0);
-        asm volatile("s_nop 7" ::: "memory");   // the last MFMAs' results -> v_accvgpr_read
+        asm volatile("s_nop 7" ::: "memory");   // the last MFMAs' results -> v_accvgpr_read (AGPR tiles) / the SDWA pack (VGPR tiles)
         SICN_DP(18, true) SICN_DP(19, true) SICN_DP(20, true) SICN_DP(21, true) SICN_DP(22, true) SICN_DP(23, true) SICN_DP(24, true) SICN_DP(25, true)
         SICN_DP(26, true) SICN_DP(27, true) SICN_DP(28, true) SICN_DP(29, true)
         h.soff = phase_soff(1);
@@ -994,7 +1038,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 #pragma unroll
         for (int s = 0; s < SLOTS; s++) poff_cur[s] = poff_next[s];
         // pass 0 of the next tile with the hand-over of this tile's phase 3 woven in (after the last tile: on a zero-filled patch)
-        deconv_pass_x<0, 2, NT>(acc, pa, wa, pb, wb, ctx, poff_cur, poff_next, true, h, bias);
+        deconv_pass_x<0, 2, NT, JV>(acc, pa, wa, pb, wb, ctx, poff_cur, poff_next, true, h, bias);
 #undef SICN_DP
         stores = true;
         if (!has_next) break;
@@ -1053,8 +1097,8 @@ hipError_t launch_wide(const LayerGeom &g, const sicn_weights &w, const uint8_t 
     const uint32_t flags = relu ? ACT_FLOOR_RELU : ACT_FLOOR_RAW;
     const bool nt = nt_store_wanted((size_t)g.OH * g.OW * g.COUT * n_images);
     const unsigned grid = wide_grid(total, grid_cap, chip);   // one resident per CU, a multiple of the XCD count (sicn_plan.h)
-    const void *fn = g.transposed ? (nt ? (const void *)&k_deconv_x<true> : (const void *)&k_deconv_x<false>)
-                                  : (nt ? (const void *)&k_conv_x<true> : (const void *)&k_conv_x<false>);
+    const void *fn = g.transposed ? (nt ? (const void *)&k_deconv_x<true, JV_DECONV> : (const void *)&k_deconv_x<false, JV_DECONV>)
+                                  : (nt ? (const void *)&k_conv_x<true, JV_CONV> : (const void *)&k_conv_x<false, JV_CONV>);
     const size_t lds = g.transposed ? DECONV_LDS : CONV_LDS;
     hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;

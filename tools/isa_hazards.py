@@ -15,15 +15,17 @@ GCNHazardRecognizer, the same silicon rules as gfx950; P = passes of the MFMA: 4
                                  (SrcC == D exactly, the accumulate chain, may issue back to back)
   D  VALU writes a VGPR/AGPR  -> MFMA reading it (SrcA / SrcB / SrcC)                              needs 2
   E  MFMA reads SrcC != D     -> VALU writing SrcC                                                 needs P + 3 (conservative)
-  F  ds_read* writes v[..]    -> first use needs an s_waitcnt lgkmcnt(k) in between that covers it (LDS returns in order;
+  F  ds_read* writes v[..] / a[..] -> first use needs an s_waitcnt lgkmcnt(k) in between that covers it (LDS returns in order;
                                  any scalar load in flight makes anything but lgkmcnt(0) insufficient)
   G  VALU writes an SGPR (v_readlane, v_readfirstlane, v_cmp .. s[..]) -> VMEM / SMEM / LDS-DMA using it    needs 5
   H  s_mov / s_add .. m0      -> LDS-DMA (buffer_load .. lds, global_load_lds) or ds_* with M0 use  needs 1
+AGPRs are registers like any other here: an MFMA's SrcA / SrcB / SrcC may be a[..] (gfx90a and later), a ds_read may return into
+a[..], and rules A - F treat both files alike (k_mfma16x.hip keeps its fragments in AGPRs and most accumulators in VGPRs).
 Control flow: every function is checked in textual order, and every backward branch additionally with the loop tail glued to
 the loop head.  Calls do not occur in these kernels.
 
 usage: isa_hazards.py file.s [file.s ...]       exit status 1 on a violation
-       isa_hazards.py --selftest                the two round-2 bugs as ISA snippets: both must be flagged"""
+       isa_hazards.py --selftest                known bugs as ISA snippets: each must be flagged, the clean snippets must not"""
 from __future__ import annotations
 
 import re
@@ -360,6 +362,59 @@ f:
 	;;#ASMEND
 	s_endpgm
 """, "F"),
+}
+
+# the register-file cases (fragments in AGPRs, accumulators in VGPRs: k_mfma16x.hip).  Reported as "held" lines: tests/test_abi_load.py
+# counts the five "ok" lines of the table above.
+SELFTEST_REGFILE = {
+    "agpr_fragment_without_wait (fragments read straight into AGPRs, consumed as SrcA)": ("""
+f:
+	;;#ASMSTART
+	ds_read_b128 a[0:3], v1 offset:32
+	;;#ASMEND
+	s_waitcnt vmcnt(0)
+	;;#ASMSTART
+	v_mfma_i32_16x16x64_i8 v[2:5], a[0:3], a[4:7], v[2:5]
+	;;#ASMEND
+	s_endpgm
+""", "F"),
+    "vgpr_accumulator_written_in_front_of_mfma (first tile: accumulator = bias by v_mov, s_nop missing)": ("""
+f:
+	v_mov_b32_e32 v23, v13
+	v_mov_b32_e32 v40, v14
+	;;#ASMSTART
+	v_mfma_i32_16x16x64_i8 v[20:23], a[0:3], a[4:7], v[20:23]
+	;;#ASMEND
+	s_endpgm
+""", "D"),
+    "clean: AGPR fragments, VGPR accumulator chain, SDWA pack of the result behind its s_nop": ("""
+f:
+	;;#ASMSTART
+	ds_read_b128 a[0:3], v1 offset:32
+	;;#ASMEND
+	;;#ASMSTART
+	ds_read_b128 a[4:7], v1 offset:64
+	;;#ASMEND
+	v_mov_b32_e32 v23, v13
+	s_waitcnt lgkmcnt(0)
+	s_nop 3
+	;;#ASMSTART
+	v_mfma_i32_16x16x64_i8 v[20:23], a[0:3], a[4:7], v[20:23]
+	;;#ASMEND
+	;;#ASMSTART
+	v_mfma_i32_16x16x64_i8 v[20:23], a[0:3], a[4:7], v[20:23]
+	;;#ASMEND
+	s_nop 7
+	;;#ASMSTART
+	v_max_i32_sdwa v30, sext(v20), s25 dst_sel:BYTE_0 dst_unused:UNUSED_PAD src0_sel:BYTE_0 src1_sel:DWORD
+	;;#ASMEND
+	;;#ASMSTART
+	v_mfma_i32_16x16x64_i8 v[20:23], a[0:3], a[4:7], v[10:13]
+	;;#ASMEND
+	s_endpgm
+""", None),
+}
+SELFTEST.update({
     "clean accumulate chain": ("""
 f:
 	;;#ASMSTART
@@ -376,18 +431,18 @@ f:
 	v_accvgpr_read_b32 v1, a0
 	s_endpgm
 """, None),
-}
+})
 
 
 def selftest() -> int:
     bad = 0
-    for name, (text, want) in SELFTEST.items():
+    for name, (text, want) in list(SELFTEST.items()) + list(SELFTEST_REGFILE.items()):
         found = []
         for fn, seq in parse(text).items():
             found += check_function(fn, seq)
         rules = {re.search(r"rule (\w)", f).group(1) for f in found}
         ok = (want in rules) if want else not found
-        print(("ok   " if ok else "FAIL ") + name + (": flagged " + ", ".join(sorted(rules)) if rules else ": clean"))
+        print(("FAIL " if not ok else "held " if name in SELFTEST_REGFILE else "ok   ") + name + (": flagged " + ", ".join(sorted(rules)) if rules else ": clean"))
         bad += not ok
     return bad
 

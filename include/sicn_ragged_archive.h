@@ -73,7 +73,10 @@ typedef struct sicn_ragged_archive_info {
  *           bit 4  n_images or n_sections is not the object's
  *           bit 5  the tag differs from expected_tag
  *           bit 6  an index size exceeds its slot's capacity
- *           bit 7  the sizes do not add up to total_bytes, or total_bytes > in_bytes, or total_bytes is not a multiple of 16 */
+ *           bit 7  the sizes do not add up to total_bytes, or total_bytes > in_bytes, or total_bytes is not a multiple of 16
+ *   sicn_ragged_archive_unpack_select_async (sicn_ragged_archive_select.h, library 0.11) unpacks a SELECTION of an archive's images
+ *   and sets these bits with two differences, stated there: bit 4 means n_sections is not the object's or n_images is SMALLER than
+ *   the object's, and bit 8 is new, a selection that is not strictly ascending or names an image the archive does not hold */
 typedef struct sicn_ragged_archive_status {
     uint32_t error;
     uint32_t first_bad;

@@ -206,6 +206,12 @@ RAGGED_ARCHIVE_ABI = {
     "sicn_ragged_archive_unpack_async": (_i, [_vp, _vp, _sz, _u32, _vpp, _vpp, _vp, _vp, _sz, _vp]),
 }
 
+# include/sicn_ragged_archive_select.h (library 0.11: a selection of an archive's images unpacked with 2 launches; the selection's own archive on the host)
+RAGGED_ARCHIVE_SELECT_ABI = {
+    "sicn_ragged_archive_unpack_select_async": (_i, [_vp, _vp, _sz, _u32, _vp, _vpp, _vpp, _vp, _vp, _sz, _vp]),
+    "sicn_ragged_archive_subset": (_i, [_vp, _sz, _u32p, _u32, _vp, _sz, _u64p]),
+}
+
 _lib = None
 
 
@@ -231,7 +237,8 @@ def lib() -> ctypes.CDLL:
         except ImportError:      # symbol checks etc. work without it
             pass
         L = ctypes.CDLL(str(LIB_PATH))
-        for name, (res, args) in {**ABI, **CODEC_ABI, **CONVLAYER_ABI, **GDN_ABI, **RAGGED_ABI, **RAGGED_HYPER_ABI, **RAGGED_CODEC_ABI, **RAGGED_CTX_ABI, **RAGGED_ARCHIVE_ABI}.items():
+        for name, (res, args) in {**ABI, **CODEC_ABI, **CONVLAYER_ABI, **GDN_ABI, **RAGGED_ABI, **RAGGED_HYPER_ABI, **RAGGED_CODEC_ABI, **RAGGED_CTX_ABI, **RAGGED_ARCHIVE_ABI,
+                                  **RAGGED_ARCHIVE_SELECT_ABI}.items():
             fn = getattr(L, name)          # AttributeError if the ABI is incomplete
             fn.restype = res
             fn.argtypes = args

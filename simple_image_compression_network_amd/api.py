@@ -598,17 +598,34 @@ class RaggedNet:
         archive.check()             # an image the encoder refused (bit 0) raises, as compress does
         return b
 
-    def decompress_archive(self, b, out=None, stream=None):
+    @classmethod
+    def from_archive(cls, b, images=None, **net_kwargs):
+        """The net for the images an archive names — all of them, or the selection `images` (strictly ascending indices into the
+        archive): the sizes are READ from the containers' headers.  `decompress_archive(b, images=images)` then reads it."""
+        from . import codec
+        info = codec.archive_info(b)
+        sel = range(info["n_images"]) if images is None else codec._selection(images, n_archive=info["n_images"])
+        sizes = [info["image_sizes"][i] for i in sel]
+        if any(s is None for s in sizes):
+            raise ValueError("an image of the selection has no container to read its size from")
+        return cls(sizes, **net_kwargs)
+
+    def decompress_archive(self, b, out=None, stream=None, images=None):
         """An archive of this net's images (e.g. from `compress_archive`) -> the reconstructions as a ragged tensor of boundary 7:
         upload, the two launches that unpack it, the ragged decoder, layers 4-7.  Raises when the work has finished if the archive
-        was refused or a container fails to decode."""
+        was refused or a container fails to decode.
+        `images`: the archive may hold more images than this net; a strictly ascending sequence of len(self.sizes) indices into it
+        names the ones to decode (ValueError otherwise, before any launch), and the sizes and latent shapes of THOSE containers must
+        be this net's.  The whole archive is uploaded, two launches copy the selected containers alone, whatever it holds."""
         import torch
         from . import codec
         info = codec.archive_info(b)
-        heads = [h[0] for h in info["headers"]]
+        sel = None if images is None else codec._selection(images, n_archive=info["n_images"], n_expected=len(self.sizes))
+        chosen = range(info["n_images"]) if sel is None else sel
+        heads = [info["headers"][i][0] for i in chosen]
         if info["n_sections"] != 1 or any(h is None or int(h.mode) != codec.RANSW for h in heads):
             raise ValueError("not an archive of one rANS-W section")
-        if [s[0] for s in info["latent_shapes"]] != self.shapes(3) or info["image_sizes"] != self.sizes:
+        if [info["latent_shapes"][i][0] for i in chosen] != self.shapes(3) or [info["image_sizes"][i] for i in chosen] != self.sizes:
             raise ValueError("the archive's image sizes or latent shapes are not this net's")
         # one coder and one archive object per set of stream lengths, shared with compress_archive: creating them costs device
         # allocations, table uploads and a synchronisation
@@ -621,7 +638,7 @@ class RaggedNet:
         if key not in self._archives:
             self._archives[key] = codec.RaggedArchive([coder], tag=0, device=self.device)
         archive = self._archives[key]
-        valid, = archive.unpack(b, stream=stream)
+        valid, = archive.unpack(b, stream=stream, images=sel)
         latent = torch.empty(self.nbytes(3), dtype=torch.uint8, device=self.device)
         coder.decode(latent, valid=valid, stream=stream)
         out, _ = self.run_layers(4, len(self.descs) - 1, latent, out=out, stream=stream)

@@ -11,7 +11,7 @@ from . import _lib
 RAW8, PACKED7, RANS, RANSW, RANSWC = 0, 1, 2, 3, 4
 __all__ = ["RAW8", "PACKED7", "RANS", "RANSW", "RANSWC", "encode_latent", "decode_latent", "parse_header", "encode_latents",
            "decode_latents", "LatentCoder", "RaggedLatentCoder", "ContextCoder", "RaggedContextCoder", "auto_stream_symbols", "WSTREAM_SYMBOLS",
-           "RaggedArchive", "split_archive", "archive_info"]
+           "RaggedArchive", "split_archive", "archive_info", "subset_archive"]
 
 
 WSTREAM_SYMBOLS = 16384   # SICN_CODEC_WSTREAM_SYMBOLS: the default (and longest) rANS-W stream
@@ -549,6 +549,36 @@ def archive_info(b):
             "headers": headers}
 
 
+def _selection(images, n_archive=None, n_expected=None):
+    """`images` as a list of ints after the checks every caller makes before any launch: strictly ascending, each in [0, n_archive),
+    `n_expected` of them.  ValueError otherwise."""
+    sel = [int(i) for i in images]
+    if not sel:
+        raise ValueError("images: an empty selection")
+    if n_expected is not None and len(sel) != n_expected:
+        raise ValueError(f"images: {len(sel)} indices for {n_expected} images")
+    if sel[0] < 0 or any(b <= a for a, b in zip(sel, sel[1:])):
+        raise ValueError("images: the indices must be strictly ascending and not negative")
+    if sel[-1] >= (1 << 32 if n_archive is None else n_archive):
+        raise ValueError(f"images: index {sel[-1]} is beyond the archive's {n_archive} images" if n_archive is not None else "images: index beyond 2^32")
+    return sel
+
+
+def subset_archive(b, images):
+    """The archive of the selected images alone (sicn_ragged_archive_subset): same tag and sections, the containers copied byte for
+    byte.  `images`: strictly ascending indices into the archive.  Host only; SicnError for a malformed archive."""
+    L = _lib.lib()
+    if not isinstance(b, bytes):
+        b = bytes(b)
+    sel = _selection(images)
+    index = (ctypes.c_uint32 * len(sel))(*sel)
+    need = ctypes.c_uint64(0)
+    _lib.check(L.sicn_ragged_archive_subset(b, len(b), index, len(sel), None, 0, ctypes.byref(need)), "sicn_ragged_archive_subset")
+    out = ctypes.create_string_buffer(int(need.value))
+    _lib.check(L.sicn_ragged_archive_subset(b, len(b), index, len(sel), out, int(need.value), ctypes.byref(need)), "sicn_ragged_archive_subset")
+    return out.raw
+
+
 class RaggedArchive:
     """The containers of a ragged batch as ONE byte string (include/sicn_ragged_archive.h): packed on the device from the slot buffers
     and encoder status arrays of one to four ragged coder objects of one batch as they lie — two launches, whatever the number of
@@ -582,6 +612,7 @@ class RaggedArchive:
         self.buffer = None          # pack()'s device buffer of max_bytes, made on first use
         self.valid = [torch.zeros((n, 2), dtype=torch.int32, device=self.device) for _ in range(k)]   # unpack()'s {error, bytes} per section
         self._in = None             # the device copy of unpack()'s archive: alive until the next unpack
+        self._index = None          # ... and of its selection (unpack(images=...))
 
     def __del__(self):
         try:
@@ -636,11 +667,24 @@ class RaggedArchive:
             raise _lib.SicnError(-28, f"ragged archive: the output buffer is smaller than the {nbytes} bytes of the archive")
         return self._out[:nbytes].cpu().numpy().tobytes()
 
-    def unpack(self, archive, stream=None):
+    def unpack(self, archive, stream=None, images=None):
         """`archive` (`bytes`, or a flat CUDA uint8 tensor) -> the coders' own slot buffers; returns the `valid` arrays (device int32
         [n][2], one per coder) to hand to `decode(..., valid=...)`.  A refused archive writes no slot byte and gives {error, 0} in every
-        entry, so the decoders report bit 8 per image; `check()` names the archive's own verdict.  Enqueue only."""
+        entry, so the decoders report bit 8 per image; `check()` names the archive's own verdict.  Enqueue only.
+        `images`: the archive may hold MORE images than this object; container images[j] goes to slot j
+        (sicn_ragged_archive_unpack_select_async).  A strictly ascending sequence of `n_images` indices into the archive — ValueError
+        otherwise, before any launch — uploaded and kept alive like the archive; or a CUDA int32 tensor of `n_images` indices, taken
+        as it lies and read when the kernels run (under capture, a replay reads what it holds then): the device checks it, bit 8."""
         import torch
+        index = None
+        if isinstance(images, torch.Tensor):
+            if not (images.is_cuda and images.dtype == torch.int32 and images.is_contiguous() and tuple(images.shape) == (self.n_images,)):
+                raise TypeError(f"images as a tensor: a contiguous CUDA int32 tensor of {self.n_images} indices")
+            index = images
+        elif images is not None:
+            import numpy as np
+            sel = _selection(images, n_expected=self.n_images)
+            index = torch.from_numpy(np.asarray(sel, dtype=np.uint32).view(np.int32)).to(self.device)
         if not isinstance(archive, torch.Tensor):
             host = torch.frombuffer(bytearray(archive), dtype=torch.uint8) if len(archive) else torch.empty(0, dtype=torch.uint8)
             n_in = host.numel()
@@ -650,9 +694,15 @@ class RaggedArchive:
             n_in = archive.numel()
             if not (archive.is_cuda and archive.dtype == torch.uint8 and archive.is_contiguous() and archive.dim() == 1):
                 raise TypeError("archive must be bytes or a contiguous flat CUDA uint8 tensor")
-        self._in = archive
-        _lib.check(_lib.lib().sicn_ragged_archive_unpack_async(
-            self._h, ctypes.c_void_p(archive.data_ptr()), n_in, self.tag, self._ptrs([c.slot_buffer for c in self.coders]),
-            self._ptrs(self.valid), ctypes.c_void_p(self.status.data_ptr()), ctypes.c_void_p(self.ws.data_ptr()), self.ws.numel(),
-            _stream_ptr(stream)), "sicn_ragged_archive_unpack_async")
+        self._in, self._index = archive, index
+        if index is None:
+            _lib.check(_lib.lib().sicn_ragged_archive_unpack_async(
+                self._h, ctypes.c_void_p(archive.data_ptr()), n_in, self.tag, self._ptrs([c.slot_buffer for c in self.coders]),
+                self._ptrs(self.valid), ctypes.c_void_p(self.status.data_ptr()), ctypes.c_void_p(self.ws.data_ptr()), self.ws.numel(),
+                _stream_ptr(stream)), "sicn_ragged_archive_unpack_async")
+        else:
+            _lib.check(_lib.lib().sicn_ragged_archive_unpack_select_async(
+                self._h, ctypes.c_void_p(archive.data_ptr()), n_in, self.tag, ctypes.c_void_p(index.data_ptr()),
+                self._ptrs([c.slot_buffer for c in self.coders]), self._ptrs(self.valid), ctypes.c_void_p(self.status.data_ptr()),
+                ctypes.c_void_p(self.ws.data_ptr()), self.ws.numel(), _stream_ptr(stream)), "sicn_ragged_archive_unpack_select_async")
         return list(self.valid)

@@ -1,6 +1,7 @@
-// The "SICA" archive format (include/sicn_ragged_archive.h) on the host: its arithmetic and the parser of header and index.  Plain
-// C++ without HIP, so that it also compiles into a stand-alone program (tests/cpp/archive_parse_check.cpp runs it under the host
-// sanitizers).  k_ragged_archive.hip wraps these in the extern "C" entry points; the device parser (k_archive_parse) refuses exactly
+// The "SICA" archive format (include/sicn_ragged_archive.h) on the host: its arithmetic, the parser of header and index, and the
+// archive of a selection of an archive's images (include/sicn_ragged_archive_select.h).  Plain
+// C++ without HIP, so that it also compiles into a stand-alone program (tests/cpp/archive_parse_check.cpp and archive_subset_check.cpp
+// run it under the host sanitizers).  k_ragged_archive.hip wraps these in the extern "C" entry points; the device parser (k_archive_parse) refuses exactly
 // the archives this one refuses (given an object of the archive's own counts, slots that are large enough and the archive's tag).  It
 // walks the header in this order too, but where this parser returns at the first finding, the device parser goes on inside one
 // stage and may report several bits at once: the tag beside bit 7, and bits 6, 7 and the index's padding (bit 3) together.
@@ -11,6 +12,7 @@
 
 #include "../../include/sicn.h"
 #include "../../include/sicn_ragged_archive.h"
+#include "../../include/sicn_ragged_archive_select.h"
 
 namespace sicn_archive {
 
@@ -82,6 +84,56 @@ inline int parse(const uint8_t *b, size_t n, sicn_ragged_archive_info *info, uin
         if (sizes) sizes[e] = size;
         if (offsets) offsets[e] = at;
         at += a16(size);
+    }
+    return SICN_OK;
+}
+
+inline void put_le32(uint8_t *p, uint32_t v)
+{
+    for (int i = 0; i < 4; i++) p[i] = (uint8_t)(v >> (8 * i));
+}
+
+// The archive of the selected images alone (sicn_ragged_archive_subset).  Two walks over the SOURCE index with a cursor into the
+// ascending selection, no allocation: the first gives the size, the second writes.  Everything it reads was vouched for by parse.
+inline int subset(const uint8_t *b, size_t n, const uint32_t *image_index, uint32_t n_selected, uint8_t *out, size_t out_capacity,
+                  uint64_t *out_bytes)
+{
+    if (!b || !image_index || !out_bytes) return SICN_EINVAL;
+    *out_bytes = 0;
+    sicn_ragged_archive_info info;
+    if (int rc = parse(b, n, &info, nullptr, nullptr)) return rc;
+    if (n_selected < 1 || n_selected > info.n_images) return SICN_EINVAL;
+    for (uint32_t j = 0; j < n_selected; j++)
+        if (image_index[j] >= info.n_images || (j && image_index[j] <= image_index[j - 1])) return SICN_EINVAL;
+    const uint32_t k = info.n_sections;
+    const uint64_t entries = (uint64_t)n_selected * k, payload = payload_offset(entries);
+    const uint8_t *index = b + HEADER_BYTES;
+    uint64_t total = payload;
+    for (uint32_t j = 0; j < n_selected; j++)
+        for (uint32_t s = 0; s < k; s++) total += a16(le32(index + 4 * ((uint64_t)image_index[j] * k + s)));
+    *out_bytes = total;                              // <= the source's total_bytes: fewer index entries, a subset of its containers
+    if (!out) return SICN_OK;
+    if (out_capacity < total) return SICN_ENOSPC;
+    memcpy(out, b, HEADER_BYTES);                    // magic, version, n_sections, tag, reserved
+    put_le32(out + 8, n_selected);
+    put_le32(out + 16, (uint32_t)total);
+    put_le32(out + 20, (uint32_t)(total >> 32));
+    memset(out + HEADER_BYTES, 0, (size_t)(payload - HEADER_BYTES));
+    uint64_t from = info.payload_offset, to = payload;
+    uint32_t j = 0;
+    for (uint32_t img = 0; j < n_selected; img++) {  // image_index[n_selected - 1] < n_images ends it
+        const bool taken = img == image_index[j];
+        for (uint32_t s = 0; s < k; s++) {
+            const uint32_t size = le32(index + 4 * ((uint64_t)img * k + s));
+            if (taken) {
+                put_le32(out + HEADER_BYTES + 4 * ((uint64_t)j * k + s), size);
+                if (size) memcpy(out + to, b + from, size);
+                memset(out + to + size, 0, (size_t)(a16(size) - size));
+                to += a16(size);
+            }
+            from += a16(size);
+        }
+        j += taken;
     }
     return SICN_OK;
 }

@@ -14,6 +14,8 @@
 //   size returns at once.  `vecmask` bit s (per launch, host-made): section s's slot buffer and the archive buffer are both 16-byte
 //   aligned; then — slot offsets and archive offsets being multiples of 16 by construction — a chunk moves as uint4, 4 per lane,
 //   and only the container's last partial 16 bytes move bytewise.  Otherwise byte by byte.
+// k_archive_parse_select (include/sicn_ragged_archive_select.h): k_archive_parse for an object made for a SELECTION of the archive's
+//   images; then k_archive_copy<false> as it is, over the object's item grid.  Described at the kernel.
 #include <new>
 #include <vector>
 
@@ -204,6 +206,117 @@ __global__ __launch_bounds__(WG) void k_archive_parse(const uint8_t *__restrict_
              ws_off[e] = off;
              ws_size[e] = size;
          });
+}
+
+// The parser of sicn_ragged_archive_unpack_select_async (include/sicn_ragged_archive_select.h): k_archive_parse for an object made for
+// the n_sel SELECTED images of an archive of N >= n_sel.  The prefix sum runs over all N * k entries of the source index, pass by
+// pass through `walk`; what is written — ws_off / ws_size / valid, in the OBJECT's numbering j * k + section — is written for the
+// selected entries alone.  "Is this source image selected, and as which j" costs one coalesced load per thread and pass: the
+// selection ascends, so the selected images of a pass are the next ones behind a workgroup-uniform cursor `cur`, at most WG of
+// them (a pass covers at most WG consecutive images).  Thread t loads image_index[cur + t] and, when that image lies in the pass,
+// writes cur + t into the pass's LDS window win[image - first image of the pass]; an entry then looks its image up in the window.
+// The cursor moves on by the selected images that END in this pass (k = 3: an image may straddle two passes and stays for the next).
+template <bool WRITE, class Each>
+__device__ __forceinline__ uint64_t walk_selected(uint64_t *wave_total, uint32_t *win, uint32_t *taken, const uint8_t *index, bool al4,
+                                                  uint32_t entries, uint32_t k, uint64_t payload, const uint32_t *__restrict__ image_index,
+                                                  uint32_t n_sel, Each each)
+{
+    uint64_t carry = payload;
+    uint32_t cur = 0;
+    for (uint32_t base = 0; base < entries; base += WG) {
+        const uint32_t img0 = base / k, img_next = (base + WG) / k;      // the first image of this pass and of the next
+        win[threadIdx.x] = NO_ENTRY;
+        if (threadIdx.x == 0) *taken = 0;
+        __syncthreads();
+        const uint32_t j = cur + threadIdx.x;
+        const uint32_t image = j < n_sel ? image_index[j] : NO_ENTRY;    // >= img0: every image below it is behind the cursor
+        if (image - img0 < (uint32_t)WG) win[image - img0] = j;
+        const uint64_t ends_here = __ballot(image < img_next);
+        if ((threadIdx.x & 63) == 0 && ends_here) atomicAdd(taken, (uint32_t)__popcll(ends_here));
+        __syncthreads();
+        cur = uni(cur + *taken);
+        const uint32_t count = entries - base < (uint32_t)WG ? entries - base : (uint32_t)WG;
+        uint32_t oe = NO_ENTRY, sel = NO_ENTRY, section = 0;              // this thread's entry in the object's numbering: oe = sel * k + section
+        carry = walk(wave_total, count, carry,
+            [&](uint32_t t) {
+                const uint32_t e = base + t, img = e / k;
+                const uint32_t size = load32(index + 4 * (size_t)e, al4);
+                section = e - img * k;
+                sel = win[img - img0];
+                oe = sel == NO_ENTRY ? NO_ENTRY : sel * k + section;
+                if (!WRITE && oe != NO_ENTRY) each(oe, sel, section, size, (uint64_t)0);
+                return size;
+            },
+            [&](uint32_t, uint32_t size, uint64_t off) {
+                if (WRITE && oe != NO_ENTRY) each(oe, sel, section, size, off);
+            });
+    }
+    return carry;
+}
+
+__global__ __launch_bounds__(WG) void k_archive_parse_select(const uint8_t *__restrict__ in, uint64_t in_bytes, uint32_t expected_tag,
+                                                             const ArchRow *__restrict__ rows, uint32_t n_sel, uint32_t k,
+                                                             const uint32_t *__restrict__ image_index, Ptrs4 valid,
+                                                             sicn_ragged_archive_status *__restrict__ status,
+                                                             uint64_t *__restrict__ ws_off, uint32_t *__restrict__ ws_size)
+{
+    __shared__ uint64_t wave_total[WG / 64];
+    __shared__ uint32_t win[WG], taken;
+    const bool al4 = (reinterpret_cast<uintptr_t>(in) & 3) == 0;
+    const uint8_t *index = in + HEADER_BYTES;
+    uint32_t err = 0, bad = NO_ENTRY, n_images = 0;
+    uint64_t total = 0;
+    // k_archive_parse's stages in its order; the object's counts are the selection's, the archive's come from its header
+    if (in_bytes < HEADER_BYTES) err |= 8u;
+    else if (load32(in, al4) != MAGIC || (load32(in + 4, al4) & 0xFFFFu) != VERSION || load32(in + 24, al4) != 0 || load32(in + 28, al4) != 0) err |= 8u;
+    if (!err) {
+        n_images = load32(in + 8, al4);
+        if ((load32(in + 4, al4) >> 16) != k || n_images < n_sel || n_images > MAX_ENTRIES / k) err |= 16u;
+    }
+    if (!err) {                                              // the header is sound and the index can hold the selection
+        const uint32_t entries = n_images * k;               // <= 2^24
+        const uint64_t payload = payload_offset(entries);
+        total = (uint64_t)load32(in + 16, al4) | (uint64_t)load32(in + 20, al4) << 32;
+        if (load32(in + 12, al4) != expected_tag) err |= 32u;
+        if ((total & 15) || total > in_bytes || payload > total) err |= 128u;
+        for (uint32_t j = threadIdx.x; j < n_sel; j += WG) {  // the selection: image_index[0 .. n_sel) and nothing else
+            const uint32_t image = image_index[j];
+            if (image >= n_images || (j && image <= image_index[j - 1])) err |= 256u;
+        }
+        gather(err, bad);                                    // from here on err is the same in every thread
+        if (!(err & (128u | 256u))) {                        // [32, payload) lies inside [0, in_bytes), and the window can trust the selection
+            const uint64_t sum = walk_selected<false>(wave_total, win, &taken, index, al4, entries, k, payload, image_index, n_sel,
+                [&](uint32_t oe, uint32_t, uint32_t, uint32_t size, uint64_t) {
+                    if (size > rows[oe].slot_bytes) { err |= 64u; bad = min(bad, oe); }
+                });
+            if (threadIdx.x < (payload - HEADER_BYTES) / 4 - entries && load32(index + 4 * ((size_t)entries + threadIdx.x), al4) != 0) err |= 8u;
+            gather(err, bad);
+            if (sum != total) err |= 128u;
+        }
+    }
+    if (threadIdx.x == 0) {
+        status->error = err;
+        status->first_bad = bad;
+        status->bytes = (err & 24u) ? 0 : total;
+    }
+    if (err) {                                               // refused: every slot is empty for the decoders, and for the copy kernel —
+        for (uint32_t e = threadIdx.x; e < n_sel * k; e += WG) {   // bit 8 is not in its REFUSED mask, an entry of size 0 has no item to move
+            const uint32_t img = e / k, s = e - img * k;
+            uint32_t *v = reinterpret_cast<uint32_t *>(pick(valid, s)) + 2 * (size_t)img;
+            v[0] = err;
+            v[1] = 0;
+            ws_size[e] = 0;
+        }
+        return;
+    }
+    walk_selected<true>(wave_total, win, &taken, index, al4, n_images * k, k, payload_offset(n_images * k), image_index, n_sel,
+        [&](uint32_t oe, uint32_t sel, uint32_t section, uint32_t size, uint64_t off) {
+            uint32_t *v = reinterpret_cast<uint32_t *>(pick(valid, section)) + 2 * (size_t)sel;
+            v[0] = 0;
+            v[1] = size;
+            ws_off[oe] = off;
+            ws_size[oe] = size;
+        });
 }
 
 template <bool PACK>
@@ -402,4 +515,31 @@ extern "C" int sicn_ragged_archive_unpack_async(const sicn_ragged_archive *archi
     hipLaunchKernelGGL(k_archive_copy<false>, dim3(archive->items ? archive->items : 1u), dim3(WG), 0, stream, slots, const_cast<uint8_t *>(in),
                        archive->d_rows, archive->d_item_entry, archive->items, ws_off, ws_size, status_dev, vecmask);
     return hipGetLastError() == hipSuccess ? SICN_OK : SICN_ENODEV;
+}
+
+extern "C" int sicn_ragged_archive_unpack_select_async(const sicn_ragged_archive *archive, const uint8_t *in, size_t in_bytes,
+                                                       uint32_t expected_tag, const uint32_t *image_index_dev, uint8_t *const *slot_buffers,
+                                                       sicn_codec_status *const *valid_out, sicn_ragged_archive_status *status_dev,
+                                                       void *workspace, size_t workspace_bytes, void *hip_stream)
+{
+    Ptrs4 slots, valid;
+    uint32_t vecmask;
+    if (!image_index_dev || (reinterpret_cast<uintptr_t>(image_index_dev) & 3)) return SICN_EINVAL;
+    if (int rc = common_checks(archive, (const void *const *)slot_buffers, (const void *const *)valid_out, in, status_dev, workspace,
+                               workspace_bytes, &slots, &valid, &vecmask))
+        return rc;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    uint64_t *ws_off = (uint64_t *)workspace;
+    uint32_t *ws_size = (uint32_t *)(ws_off + archive->entries);
+    hipLaunchKernelGGL(k_archive_parse_select, dim3(1), dim3(WG), 0, stream, in, (uint64_t)in_bytes, expected_tag, archive->d_rows,
+                       archive->n_images, archive->k, image_index_dev, valid, status_dev, ws_off, ws_size);
+    hipLaunchKernelGGL(k_archive_copy<false>, dim3(archive->items ? archive->items : 1u), dim3(WG), 0, stream, slots, const_cast<uint8_t *>(in),
+                       archive->d_rows, archive->d_item_entry, archive->items, ws_off, ws_size, status_dev, vecmask);
+    return hipGetLastError() == hipSuccess ? SICN_OK : SICN_ENODEV;
+}
+
+extern "C" int sicn_ragged_archive_subset(const uint8_t *archive, size_t archive_bytes, const uint32_t *image_index, uint32_t n_selected,
+                                          uint8_t *out, size_t out_capacity, uint64_t *out_bytes)
+{
+    return subset(archive, archive_bytes, image_index, n_selected, out, out_capacity, out_bytes);
 }

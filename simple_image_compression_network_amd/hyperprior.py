@@ -257,27 +257,33 @@ class RaggedHyperpriorCodec:
         return b
 
     @classmethod
-    def from_archive(cls, b, seed: int = 0, device="cuda", use_gdn=None, main_params=None):
-        """The codec for the images an archive names: sizes and the z stream lengths are READ from the z containers' headers, and
-        `use_gdn` (unless given) from the tag — 0 means an archive written without GDN.  `decode(archive=b)` then reads it."""
+    def from_archive(cls, b, seed: int = 0, device="cuda", use_gdn=None, main_params=None, images=None):
+        """The codec for the images an archive names — all of them, or the selection `images` (strictly ascending indices into the
+        archive): sizes and the z stream lengths are READ from the z containers' headers, and `use_gdn` (unless given) from the tag —
+        0 means an archive written without GDN.  `decode(archive=b, images=images)` then reads it."""
         info = codec.archive_info(b)
-        heads = [h[0] for h in info["headers"]]
+        sel = range(info["n_images"]) if images is None else codec._selection(images, n_archive=info["n_images"])
+        heads = [info["headers"][i][0] for i in sel]
         if info["n_sections"] != 2 or any(h is None for h in heads):
             raise ValueError("not a hyperprior archive: need the sections z and y of every image")
-        return cls(info["image_sizes"], seed=seed, device=device, use_gdn=info["tag"] != 0 if use_gdn is None else use_gdn,
+        return cls([info["image_sizes"][i] for i in sel], seed=seed, device=device, use_gdn=info["tag"] != 0 if use_gdn is None else use_gdn,
                    main_params=main_params, z_stream_symbols=[int(h.stream_symbols) for h in heads])
 
-    def decode(self, out=None, z_containers=None, y_containers=None, archive=None):
+    def decode(self, out=None, z_containers=None, y_containers=None, archive=None, images=None):
         """Containers (default: the last encode's; else lists of `bytes`, one per image; or `archive`, what `archive()` returned) ->
         the reconstructions, a ragged tensor of main's boundary 7 (`main.cropped(out)` cuts them to the images' sizes).  An archive is
         unpacked on the device into the coders' own slots; one whose tag is not this codec's (another GDN specification version, or
-        the other `use_gdn`) is refused as a whole: `check()` raises with bit 5.  Enqueue only."""
+        the other `use_gdn`) is refused as a whole: `check()` raises with bit 5.  Enqueue only.
+        `images` (with `archive` only): the archive may hold more images than this codec; a strictly ascending sequence of
+        len(self.sizes) indices into it names the ones to decode (ValueError otherwise, before any launch)."""
         keep = []
+        if images is not None and archive is None:
+            raise ValueError("images= selects from an archive")
         self._unpacked = archive is not None
         if archive is not None:
             if z_containers is not None or y_containers is not None:
                 raise ValueError("either an archive or lists of containers")
-            z_valid, y_valid = self._ragged_archive().unpack(archive)
+            z_valid, y_valid = self._ragged_archive().unpack(archive, images=images)
             self.z_coder.decode(self.z_hat, valid=z_valid)
             self._scale_map(self.z_hat)
             self.y_coder.decode(self.y_hat, self.s, valid=y_valid)

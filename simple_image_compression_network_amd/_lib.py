@@ -212,6 +212,36 @@ RAGGED_ARCHIVE_SELECT_ABI = {
     "sicn_ragged_archive_subset": (_i, [_vp, _sz, _u32p, _u32, _vp, _sz, _u64p]),
 }
 
+class RaggedRect(ctypes.Structure):
+    """ctypes image of `sicn_ragged_rect` (include/sicn_ragged_window.h)."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("x0", "y0", "w", "h")]
+
+
+class RaggedRoiPlan(ctypes.Structure):
+    """ctypes image of `sicn_ragged_roi` (include/sicn_ragged_window.h)."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("c0", "r0", "cw", "rh", "x", "y", "margin_lo", "margin_hi")]
+
+
+class RaggedWindowImage(ctypes.Structure):
+    """ctypes image of `sicn_ragged_window_image` (include/sicn_ragged_window.h)."""
+    _fields_ = [("band_offset", ctypes.c_uint64)] + [(n, ctypes.c_uint32) for n in ("band_bytes", "first_stream", "end_stream", "lead")]
+
+
+_rectp = ctypes.POINTER(RaggedRect)
+# include/sicn_ragged_window.h (library 0.12: a pixel rectangle of each image from its streams — window decoder 2 launches, cut 1)
+RAGGED_WINDOW_ABI = {
+    "sicn_ragged_roi_plan": (_i, [_i, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _rectp, ctypes.POINTER(RaggedRoiPlan)]),
+    "sicn_ragged_window_layout": (_i, [_u32p, _u32p, _u32, _u32p, _u32p, _u32p, _i, ctypes.POINTER(RaggedWindowImage), _u64p]),
+    "sicn_ragged_window_create": (_i, [_vp, _u32p, _u32p, ctypes.POINTER(_vp)]),
+    "sicn_ragged_window_free": (None, [_vp]),
+    "sicn_ragged_window_workspace_bytes": (_sz, [_vp]),
+    "sicn_ragged_window_decode_async": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "sicn_ragged_cut_layout": (_i, [_i32p, _i32p, _rectp, _i, _u64p, _i, _i, _i64p]),
+    "sicn_ragged_cut_create": (_i, [_i32p, _i32p, _rectp, _i, _u64p, _i, ctypes.POINTER(_vp)]),
+    "sicn_ragged_cut_free": (None, [_vp]),
+    "sicn_ragged_cut_run": (_i, [_vp, _vp, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -238,7 +268,7 @@ def lib() -> ctypes.CDLL:
             pass
         L = ctypes.CDLL(str(LIB_PATH))
         for name, (res, args) in {**ABI, **CODEC_ABI, **CONVLAYER_ABI, **GDN_ABI, **RAGGED_ABI, **RAGGED_HYPER_ABI, **RAGGED_CODEC_ABI, **RAGGED_CTX_ABI, **RAGGED_ARCHIVE_ABI,
-                                  **RAGGED_ARCHIVE_SELECT_ABI}.items():
+                                  **RAGGED_ARCHIVE_SELECT_ABI, **RAGGED_WINDOW_ABI}.items():
             fn = getattr(L, name)          # AttributeError if the ABI is incomplete
             fn.restype = res
             fn.argtypes = args

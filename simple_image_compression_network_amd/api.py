@@ -27,7 +27,7 @@ from . import _lib
 from .config import CLayerDesc, LayerDesc, REFERENCE_DESCS, eight_layer_descs
 
 __all__ = ["FixedPointWeights", "DeviceWeights", "conv2d", "deconv522", "conv2d_layer0", "deconv2d_layer4",
-           "eight_layers_net", "EightLayersNet", "RaggedNet", "RaggedCrop", "load_param_weights", "PARAM", "GDN"]
+           "eight_layers_net", "EightLayersNet", "RaggedNet", "RaggedCrop", "RaggedCut", "RaggedRoi", "roi_plan", "load_param_weights", "PARAM", "GDN"]
 
 _DATA = Path(__file__).resolve().parent / "data" / "param_weights.npz"
 
@@ -401,6 +401,135 @@ class RaggedCrop:
         return dst
 
 
+class RaggedCut:
+    """A rectangle out of every image of a ragged tensor, ONE launch for the batch (sicn_ragged_cut_*, include/sicn_ragged_window.h).
+    src_shapes: [(h, w)] per image; rects: [(x0, y0, w, h)] per image, inside its source; both tensors are flat uint8 CUDA tensors, the
+    images' [h][w][channels] arrays back to back — or, for the source, at `src_offsets` (bytes, one per image).  RaggedCrop is the
+    case x0 = y0 = 0."""
+
+    def __init__(self, src_shapes, rects, channels: int, src_offsets=None, device=None):
+        import torch
+        L = _lib.lib()
+        self.src_shapes = [(int(h), int(w)) for h, w in src_shapes]
+        self.rects = [tuple(int(v) for v in r) for r in rects]
+        self.channels = int(channels)
+        n = len(self.src_shapes)
+        if len(self.rects) != n or any(len(r) != 4 for r in self.rects):
+            raise ValueError("rects: one (x0, y0, w, h) per source shape")
+        if src_offsets is not None and len(src_offsets) != n:
+            raise ValueError("src_offsets: one per source shape")
+        for (h, w), (x0, y0, rw, rh) in zip(self.src_shapes, self.rects):
+            if rw < 1 or rh < 1 or x0 < 0 or y0 < 0 or x0 + rw > w or y0 + rh > h:
+                raise ValueError(f"rectangle {(x0, y0, rw, rh)} is empty or outside its {w} x {h} source")
+        i32 = ctypes.c_int32 * max(n, 1)
+        sw, sh = i32(*[w for _, w in self.src_shapes]), i32(*[h for h, _ in self.src_shapes])
+        crects = (_lib.RaggedRect * max(n, 1))(*[_lib.RaggedRect(*r) for r in self.rects])
+        offs = None if src_offsets is None else (ctypes.c_uint64 * max(n, 1))(*[int(o) for o in src_offsets])
+        self.dst_shapes = [(rh, rw) for _, _, rw, rh in self.rects]
+        self._src_off, self._dst_off = [], []
+        q = (ctypes.c_int64 * 4)()
+        for i in range(n):
+            _lib.check(L.sicn_ragged_cut_layout(sw, sh, crects, self.channels, offs, n, i, q), "sicn_ragged_cut_layout")
+            self._src_off.append(int(q[0]))
+            self._dst_off.append(int(q[1]))
+        self.src_bytes, self.dst_bytes = int(q[2]), int(q[3])      # src_bytes: the furthest byte a source image reaches
+        self.device = torch.device(device if device is not None else "cuda")
+        self._h = ctypes.c_void_p()
+        with torch.cuda.device(self.device):
+            _lib.check(L.sicn_ragged_cut_create(sw, sh, crects, self.channels, offs, n, ctypes.byref(self._h)), "sicn_ragged_cut_create")
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None) and _lib._lib is not None:
+                _lib._lib.sicn_ragged_cut_free(self._h)
+                self._h = None
+        except Exception:       # interpreter shutdown
+            pass
+
+    def views(self, dst):
+        """Per-image [h][w][channels] views of a destination tensor (no copy)."""
+        _check_tensor(dst, (self.dst_bytes,), "dst")
+        c = self.channels
+        return [dst[o:o + h * w * c].view(h, w, c) for o, (h, w) in zip(self._dst_off, self.dst_shapes)]
+
+    def run(self, src, dst=None, stream=None):
+        """src (flat, at least src_bytes long) -> dst (ragged, the rectangles' shapes; allocated when None).  Enqueue only."""
+        import torch
+        if not (src.is_cuda and src.dtype == torch.uint8 and src.is_contiguous() and src.dim() == 1 and src.numel() >= self.src_bytes):
+            raise TypeError(f"src must be a flat contiguous CUDA uint8 tensor of at least {self.src_bytes} bytes")
+        if dst is None:
+            dst = torch.empty(self.dst_bytes, dtype=torch.uint8, device=src.device)
+        _check_tensor(dst, (self.dst_bytes,), "dst")
+        _lib.check(_lib.lib().sicn_ragged_cut_run(self._h, ctypes.c_void_p(src.data_ptr()), ctypes.c_void_p(dst.data_ptr()),
+                                                  _stream_ptr(stream)), "sicn_ragged_cut_run")
+        return dst
+
+
+def roi_plan(size, rect, n_up_layers: int = 4):
+    """What the pixel rectangle `rect` = (x0, y0, w, h) of an image of `size` = (width, height) needs of its latent
+    (sicn_ragged_roi_plan): a dict with the latent window `c0, r0, cw, rh`, the rectangle's corner `x, y` inside the window's
+    reconstruction, and the margins.  ValueError for a rectangle that is empty or reaches outside the image."""
+    w, h = int(size[0]), int(size[1])
+    if len(rect) != 4:
+        raise ValueError("rect: (x0, y0, w, h)")
+    r = _lib.RaggedRect(*[int(v) for v in rect])
+    s = 1 << n_up_layers
+    out = _lib.RaggedRoiPlan()
+    rc = _lib.lib().sicn_ragged_roi_plan(n_up_layers, w, h, (w + s - 1) // s, (h + s - 1) // s, ctypes.byref(r), ctypes.byref(out))
+    if rc == -22:
+        raise ValueError(f"rectangle {tuple(rect)} is empty or reaches outside the {w} x {h} image")
+    _lib.check(rc, "sicn_ragged_roi_plan")
+    return {k: int(getattr(out, k)) for k, _ in _lib.RaggedRoiPlan._fields_}
+
+
+class RaggedRoi:
+    """One pixel rectangle of every image of a RaggedNet's batch, decoded from the images' rANS-W containers without the rest of the
+    image (include/sicn_ragged_window.h): 2 + 1 + 4 + 1 launches whatever the number of images — the window decoder over the streams
+    that hold the latent rows, the cut of the latent columns, layers 4-7 of a second RaggedNet made for the windows' sizes
+    (16 cw, 16 rh) on `net`'s weights, the cut of the rectangle.  Same bytes as the full decode, sliced.
+    rects: one (x0, y0, w, h) per image, or None for that image whole.  One rectangle per image: two details of one photograph are
+    two objects (and, through an archive, two calls).  coder: the RaggedLatentCoder whose slots hold the containers (default: a new
+    one from net.latent_coder(stream_symbols))."""
+
+    def __init__(self, net, rects, coder=None, stream_symbols=16384):
+        n = len(net.sizes)
+        if len(rects) != n:
+            raise ValueError(f"rects: one per image, {n}")
+        self.net = net
+        self.rects = [(0, 0, w, h) if r is None else tuple(int(v) for v in r) for r, (w, h) in zip(rects, net.sizes)]
+        self.plans = [roi_plan(size, r) for size, r in zip(net.sizes, self.rects)]        # ValueError before anything is made
+        self.coder = coder if coder is not None else net.latent_coder(stream_symbols)
+        lat = net.shapes(3)
+        if [(h, w) for h, w, _ in lat] != self.coder.shapes or lat[0][2] != self.coder.lat_c:
+            raise ValueError("the coder's latent shapes are not the net's")
+        c = lat[0][2]
+        self.window = self.coder.window([(p["r0"], p["rh"]) for p in self.plans])
+        self.latent_cut = RaggedCut([(p["rh"], w) for p, (_, w, _) in zip(self.plans, lat)],
+                                    [(p["c0"], 0, p["cw"], p["rh"]) for p in self.plans], c,
+                                    src_offsets=[int(im.band_offset) + int(im.lead) for im in self.window.images[:n]], device=net.device)
+        self.window_net = RaggedNet([(16 * p["cw"], 16 * p["rh"]) for p in self.plans], device=net.device, shared_weights=net.weights,
+                                    descs=net.descs, gdn=net.gdn)
+        self.pixel_cut = RaggedCut([(16 * p["rh"], 16 * p["cw"]) for p in self.plans],
+                                   [(p["x"], p["y"], r[2], r[3]) for p, r in zip(self.plans, self.rects)],
+                                   net.shapes(len(net.descs) - 1)[0][2], device=net.device)
+        self.status = self.window.status
+
+    def decode(self, slots=None, valid=None, stream=None, out=None):
+        """The coder's slots (or `slots`, `valid` as in RaggedLatentCoder.decode) -> the ROI pixels, a ragged [h][w][3] tensor.
+        Enqueue only: eight launches.  `self.status` holds the window decoder's verdicts."""
+        import torch
+        dev = self.net.device
+        self.band = torch.empty(self.window.band_bytes, dtype=torch.uint8, device=dev)
+        self.window.decode(self.band, slots=slots, valid=valid, stream=stream)
+        self.latent = self.latent_cut.run(self.band, stream=stream)
+        recon, _ = self.window_net.run_layers(4, len(self.net.descs) - 1, self.latent, stream=stream)
+        return self.pixel_cut.run(recon, out, stream=stream)
+
+    def views(self, roi):
+        """Per-image [h][w][3] views of what `decode` returned."""
+        return self.pixel_cut.views(roi)
+
+
 class RaggedNet:
     """A layer chain over images of DIFFERENT sizes, one kernel launch per layer for the whole batch (include/sicn_ragged.h); by
     default the 8-layer chain.  `sizes`: [(width, height)] per image at the chain's input.  A ragged tensor is a flat uint8 CUDA
@@ -460,6 +589,8 @@ class RaggedNet:
         self._coders = {}           # compress()'s RaggedLatentCoders by stream length, made on first use
         self._archives = {}         # compress_archive()'s RaggedArchives, one per coder
         self._crop = None           # cropped()'s RaggedCrop, made on first use
+        self._rois = {}             # decompress_archive(rois=)'s RaggedRoi objects by coder and rectangles
+        self._last_roi = None
 
     def __del__(self):
         try:
@@ -546,6 +677,12 @@ class RaggedNet:
             raise ValueError("cropped() has not run")
         return self._crop.views(cropped)
 
+    def roi_views(self, roi_pixels):
+        """Per-image [h][w][3] views of what the last `decompress_archive(rois=...)` returned."""
+        if self._last_roi is None:
+            raise ValueError("decompress_archive(rois=...) has not run")
+        return self._last_roi.views(roi_pixels)
+
     def latent_coder(self, stream_symbols=None):
         """A codec.RaggedLatentCoder for this net's latents (boundary 3) and image sizes: the whole batch in 3 + 2 launches."""
         from . import codec
@@ -610,16 +747,27 @@ class RaggedNet:
             raise ValueError("an image of the selection has no container to read its size from")
         return cls(sizes, **net_kwargs)
 
-    def decompress_archive(self, b, out=None, stream=None, images=None):
+    def decompress_archive(self, b, out=None, stream=None, images=None, rois=None):
         """An archive of this net's images (e.g. from `compress_archive`) -> the reconstructions as a ragged tensor of boundary 7:
         upload, the two launches that unpack it, the ragged decoder, layers 4-7.  Raises when the work has finished if the archive
         was refused or a container fails to decode.
         `images`: the archive may hold more images than this net; a strictly ascending sequence of len(self.sizes) indices into it
         names the ones to decode (ValueError otherwise, before any launch), and the sizes and latent shapes of THOSE containers must
-        be this net's.  The whole archive is uploaded, two launches copy the selected containers alone, whatever it holds."""
+        be this net's.  The whole archive is uploaded, two launches copy the selected containers alone, whatever it holds.
+        `rois`: one (x0, y0, w, h) per decoded image, or None for that image whole — only the streams, latent columns and pixels the
+        rectangles need are decoded (RaggedRoi: eight launches behind the unpack), and the result is the ROI pixels as a ragged
+        [h][w][3] tensor (`roi_views` gives them per image), the bytes of the full decode sliced.  A wrong length or a rectangle
+        outside its image is a ValueError before any launch.  One rectangle per image per call: two details of one photograph are
+        two calls.  The window cannot check the checksum of the whole latent; every other verdict raises as without `rois`."""
         import torch
         from . import codec
         info = codec.archive_info(b)
+        if rois is not None:
+            if len(rois) != len(self.sizes):
+                raise ValueError(f"rois: one rectangle (or None) per decoded image, {len(self.sizes)}")
+            rois = tuple(None if r is None else tuple(int(v) for v in r) for r in rois)
+            for size, r in zip(self.sizes, rois):
+                roi_plan(size, (0, 0) + size if r is None else r)
         sel = None if images is None else codec._selection(images, n_archive=info["n_images"], n_expected=len(self.sizes))
         chosen = range(info["n_images"]) if sel is None else sel
         heads = [info["headers"][i][0] for i in chosen]
@@ -638,6 +786,17 @@ class RaggedNet:
         if key not in self._archives:
             self._archives[key] = codec.RaggedArchive([coder], tag=0, device=self.device)
         archive = self._archives[key]
+        if rois is not None:
+            if (key, rois) not in self._rois:
+                self._rois[(key, rois)] = RaggedRoi(self, rois, coder=coder)
+            roi = self._last_roi = self._rois[(key, rois)]
+            valid, = archive.unpack(b, stream=stream, images=sel)
+            out = roi.decode(valid=valid, stream=stream, out=out)
+            archive.check()
+            status = roi.status[:, 0].cpu().tolist()
+            if any(status):
+                raise _lib.SicnError(-22, f"rANS-W window decode status {status}")
+            return out
         valid, = archive.unpack(b, stream=stream, images=sel)
         latent = torch.empty(self.nbytes(3), dtype=torch.uint8, device=self.device)
         coder.decode(latent, valid=valid, stream=stream)

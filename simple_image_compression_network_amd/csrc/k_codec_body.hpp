@@ -813,6 +813,70 @@ __device__ __forceinline__ void dec_finish_self_body(const DecImage &im)
     }
 }
 
+// dec_finish_self_body for a WINDOW of the image's streams (k_ragged_window.hip): only the streams [first, end) ran.  The fixed
+// part is checked as above — header, frequency table, payload field, every entry of the length table and their sum — the
+// per-stream verdicts are folded over [first, end) alone, and the checksum of the whole latent, which a window cannot make, is
+// never looked at: bit 7 is never set.  status.bytes = `symbols`, what the selected streams hold.
+__device__ __forceinline__ void dec_finish_window_body(const DecImage &im, uint32_t first, uint32_t end, uint32_t symbols)
+{
+    const uint8_t *__restrict__ c = im.c;
+    const uint32_t *__restrict__ serr = im.err;
+    uint32_t *__restrict__ status = im.status;
+    const uint32_t n = im.n, ns = im.ns, lat_w = im.lat_w, lat_h = im.lat_h, lat_c = im.lat_c, wss = im.wss;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const uint32_t valid = im.valid ? min(*im.valid, im.slot_cap) : im.slot_cap;
+    const size_t fixed = SICN_CODEC_HEADER_BYTES + 256 + 4 * (size_t)ns;
+    __shared__ uint32_t r_err, r_tab;
+    if (tid == 0) { r_err = 0; r_tab = 0; }
+    __syncthreads();
+    if (valid < fixed) {   // nothing of this slot was read: bit 8 + bit 2, and bit 5 for the streams that all refused it
+        if (tid == 0) {
+            status[0] = 0x104u | (end > first ? 32u : 0u);
+            status[1] = symbols;
+        }
+        return;
+    }
+    auto rd32 = [&](size_t o) { return c[o] | ((uint32_t)c[o + 1] << 8) | ((uint32_t)c[o + 2] << 16) | ((uint32_t)c[o + 3] << 24); };
+    uint32_t err = 0;
+    if (tid < 64) {   // wave 0: the checks of k_dec_parse
+        const uint32_t expect[10] = {0x4C434953u, 1u | ((uint32_t)SICN_CODEC_RANSW << 16), 0, 0, lat_w, lat_h, lat_c, n, ns, wss};
+        if (lane < 10 && lane != 2 && lane != 3 && rd32(4 * lane) != expect[lane]) err = 4;
+        uint32_t fsum = c[SICN_CODEC_HEADER_BYTES + 4 * lane] + ((uint32_t)c[SICN_CODEC_HEADER_BYTES + 4 * lane + 1] << 8) +
+                        c[SICN_CODEC_HEADER_BYTES + 4 * lane + 2] + ((uint32_t)c[SICN_CODEC_HEADER_BYTES + 4 * lane + 3] << 8);
+#pragma unroll
+        for (int d = 32; d > 0; d >>= 1) fsum += __shfl_xor((int)fsum, d);
+        if (n && fsum != 4096) err |= 8;
+    }
+    const uint32_t pb = rd32(40);
+    const bool pb_bad = (size_t)pb > (size_t)valid - fixed;
+    if (tid == 0 && pb_bad) err |= 16;
+    const uint32_t bound = pb_bad ? 0u : pb;
+    const uint32_t cap = wstream_cap(wss);
+    uint32_t tab = 0;
+    for (uint32_t i = tid; i < ns; i += 256) {
+        uint32_t v = rd32(SICN_CODEC_HEADER_BYTES + 256 + 4 * (size_t)i);
+        if (v > cap) { err |= 32; v = 0; }
+        tab += v;
+        if (i >= first && i < end && serr[i]) err |= 32;
+    }
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) {
+        err |= (uint32_t)__shfl_xor((int)err, d);
+        tab += (uint32_t)__shfl_xor((int)tab, d);
+    }
+    if (lane == 0) {
+        if (err) atomicOr(&r_err, err);
+        if (tab) atomicAdd(&r_tab, tab);
+    }
+    __syncthreads();
+    if (tid == 0) {
+        uint32_t e = r_err;
+        if (r_tab != bound) e |= 64;           // the length table does not add up to the payload
+        status[0] = e;
+        status[1] = symbols;
+    }
+}
+
 // ---- the bookkeeping stages of the scan form (mode 2, mode 3 above SELF_SCAN_MAX streams, mode 4) -------------------------------
 // Uniform kernels (sicn_codec.hip, sicn_codec_ctx.inc) resolve an image's pointers from strides, the ragged context coder
 // (k_ragged_ctx.hip) from its row; the stages themselves are these.

@@ -194,6 +194,16 @@ extern "C" int sicn_ragged_coder_create(const uint32_t *lat_w, const uint32_t *l
     return SICN_OK;
 }
 
+// what the window decoder (k_ragged_window.hip) builds on: the coder's rows, on the host and on the device
+void sicn::ragged_coder_view(const sicn_ragged_coder *coder, RaggedCoderView *v)
+{
+    v->n_images = coder->n_images;
+    v->rows_host = coder->plan.rows.data();
+    v->d_rows = coder->d_rows;
+    v->row_bytes = sizeof(CoderRow);
+    v->ws_bytes = coder->plan.ws_bytes;
+}
+
 extern "C" size_t sicn_ragged_coder_workspace_bytes(const sicn_ragged_coder *coder) { return coder ? (size_t)coder->plan.ws_bytes : 0; }
 
 extern "C" int sicn_ragged_coder_encode_async(const sicn_ragged_coder *coder, const uint8_t *latents, uint8_t *containers,

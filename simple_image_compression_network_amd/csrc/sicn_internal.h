@@ -29,6 +29,8 @@ inline LayerGeom geom_of(const sicn_layer_desc &d)
 
 }  // namespace sicn
 
+struct sicn_ragged_coder;   // k_ragged_codec.hip
+
 // One layer's device-resident parameters, in every layout a kernel family wants.
 struct sicn_weights {
     int cin, cout, transposed;
@@ -109,6 +111,16 @@ size_t any_bytes(int cin, int cout);
 void pack_any(const int8_t *w_okc, int cin, int cout, int8_t *dst);
 hipError_t launch_any(const LayerGeom &g, const sicn_weights &w, const uint8_t *in, uint8_t *out, int n_images, hipStream_t stream,
                       bool relu = true);
+
+// k_ragged_codec.hip: a ragged coder as the window decoder (k_ragged_window.hip) sees it — [n_images] CoderRow (k_codec_body.hpp)
+// on the host and on the device, both owned by the coder
+struct RaggedCoderView {
+    int n_images;
+    const void *rows_host, *d_rows;
+    size_t row_bytes;
+    uint64_t ws_bytes;
+};
+void ragged_coder_view(const sicn_ragged_coder *coder, RaggedCoderView *v);
 
 size_t l0_bytes(int cout);
 void pack_l0(const int8_t *w_okc, int cout, int8_t *dst);

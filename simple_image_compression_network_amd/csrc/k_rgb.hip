@@ -193,25 +193,37 @@ hipError_t launch_l0(const LayerGeom &g, const sicn_weights &w, const uint8_t *i
 }
 
 // =============================================================================================
-// Layer 7.  Per input position (y,x) the 4 output phases x 3 channels are 12 dot products over the
-// 3x3 input neighbourhood: row (4*phase + c) of a 16-row virtual weight matrix W' holds
-// W[c][2dy-py][2dx-px][:] at neighbourhood tap (dy,dx) (zero where that tap does not belong to the
-// phase).  v_mfma_i32_16x16x64_i8: A = W' (16 rows x 64 K bytes), B = 16 positions, 18 K steps
-// (9 taps x two 64-channel halves).  Output tile: lane (position l&15, phase l>>4) holds the 3
-// channel bytes of out[2y+py][2x+px].
-//   * W' (18 KB) is held in REGISTERS (72 VGPRs) for the whole vertical strip a workgroup walks.
-//   * The strip is walked in steps of 4 input rows (wave w = row w, 32 positions).  The input
-//     lives in a ROLLING LDS window: position P = r*36 + tx (r = row counted from the top of the
-//     strip, 34 of the 36 columns used) sits at ring slot P mod 368.  One step needs rows
-//     4t+2..4t+7 and, while it computes, the 4 rows of the next step (exactly 9 pieces of 16
-//     positions per region) are fetched by LDS-DMA into the slots the previous step freed: every
-//     input row is fetched once per strip (fetch = 34/32 of the input) and the load latency is
-//     hidden behind a whole step.  One barrier per step.
+// Layer 7 as tap products.  Input row i contributes to the output rows 2i-2 .. 2i+2 only (ky = 2i + 2 - oy), so a
+// workgroup multiplies every input row ONCE and adds the products up across the rows afterwards (everything mod 256,
+// bias and activation last).  Along x the layer stays a gather: for input row i and position x
+//     T(i, x)[ky][px][c] = sum over dx, ch of in[i][x - 1 + dx][ch] * W[c][ky][2 dx - px][ch]
+// is one column of a 30-row x 384-K matrix product (v_mfma_i32_16x16x64_i8: A = W'', 2 M tiles x 6 K steps, B = 16
+// positions at three column shifts dx), and
+//     out[2y    ][2x + px][c] = act(bias[c] + T(y - 1, x)[0] + T(y, x)[2] + T(y + 1, x)[4])
+//     out[2y + 1][2x + px][c] = act(bias[c] +                  T(y, x)[1] + T(y + 1, x)[3]).
+// A 16-position fragment is read from LDS 3 times per step (6 ds_read_b128, 12 MFMAs), not 9 times (18 and 18), and
+// no MFMA row is spent on a (tap, phase) pair that is zero.
+//   * W'' (12 KB) is held in REGISTERS (48 VGPRs) for the whole vertical strip a workgroup walks.  Row 4g + r of M
+//     tile 0 / 1 (lane group g = lane >> 4 = 2 py + px holds rows 4g .. 4g+3 of a D tile):
+//         tile 0, r < 3: (ky = 2 - py, px, c = r)          the lane's OWN output phase of row y = i
+//         tile 1, r < 3: (ky = py ? 3 : 0, px, c = r)      py = 0: for row i + 1 (phase 0), py = 1: for row i - 1 (phase 1)
+//         r = 3        : ky = 4 for row i - 1 (phase 0): c = 0 (tile 0) and 1 (tile 1) in the py = 0 groups, c = 2 (tile 0) in py = 1
+//   * The strip is walked in steps of 4 input rows through the ROLLING LDS window: position P = r*36 + tx (r = row
+//     counted from the top of the strip, 34 of the 36 columns used) sits at ring slot P mod 368.  While a step
+//     computes, the 4 rows of the next step (exactly 9 pieces of 16 positions per region) are fetched by LDS-DMA:
+//     every input row is fetched once per strip and the load latency is hidden behind a whole step.
+//   * In step s wave w multiplies input row 4s + 1 + w (the four rows that landed last), writes the 18 product bytes
+//     per position that belong to the rows above and below to a 3.5 KB LDS exchange area (packed, 3 bytes a dword),
+//     and after ONE extra barrier adds what its neighbours wrote for its own row.  Waves 0 - 2 then hold the output
+//     rows of y = 4s + 1 + w; wave 3's row 4s + 4 lacks the row below it until the next step, so wave 3 keeps its
+//     partial sums in registers and finishes row 4s (from the step before) instead: a step stores the rows 4s .. 4s+3
+//     as before.  Wave 3's bytes for the row below it cross the step in a slot that alternates with the step's parity.
+//     A chunk starts with one step that stores nothing: it multiplies the rows 4 s_begin - 1 and 4 s_begin.
 //   * Two LDS regions (K-group parity kg&1), each [slot][4 chunks x 16 B] with chunk
 //     c2 = 2*half + (kg>>1) stored at c2 ^ ((P>>2)&3): a 16-lane ds_read_b128 group covers 16
 //     distinct positions at ONE c2, i.e. 16 distinct 16-byte slots of a 256-byte LDS row.  Ring
 //     wrap and step advance are multiples of 16 positions, so the XOR term is a lane constant.
-//     Which channels a K byte stands for is free (W' is packed to match): region R holds the
+//     Which channels a K byte stands for is free (W'' is packed to match): region R holds the
 //     32-channel groups 2R, 2R+1 whole, so every LDS-DMA lane pair fetches one contiguous 32-byte
 //     group entry (region-interleaved halves made each instruction use half of every line it touched).
 //   * RGB output is transposed through a 384-byte per-wave LDS staging tile and stored as dwords
@@ -227,7 +239,13 @@ constexpr int L7_WGS = 3;                                // workgroups per CU th
 constexpr int L7_RING_POS = L7_RING_PIECES * 16;
 constexpr int L7_REGION = L7_RING_PIECES * 1024;
 constexpr int L7_STAGE = 2 * 192;                        // 2 output rows x 64 pixels x 3 B per wave
+constexpr int L7_X1 = 2 * 256;                           // exchange, per wave: [position tile 2][lane 64] dwords = the rows r < 3 of M tile 1
+constexpr int L7_X2 = 2 * 128;                           // exchange, per wave: [position tile 2][px 2][16 positions] dwords = the ky = 4 bytes
+constexpr int L7_XCH = 5 * L7_X1 + 4 * L7_X2;            // wave 3's L7_X1 record twice (step parity)
+constexpr int L7_LDS = 2 * L7_REGION + 4 * L7_STAGE + 1024 + L7_XCH;
+constexpr int L7_KSTEPS = 6, L7_MTILES = 2;              // W'': [M tile][K step = 2 dx + half][row 16][64 B]
 static_assert(L7_ROWS * L7_PITCH % 16 == 0 && L7_RING_POS >= (4 * L7_AHEAD + 6) * L7_PITCH, "ring geometry");
+static_assert(L7_WGS * L7_LDS <= 160 * 1024 && L7_XCH <= 4096, "three workgroups per CU");
 
 // LDS-DMA pieces `first + 4i` (i < n) of a run of window rows: piece j < npieces covers region
 // j / per_region, positions (j % per_region)*16 .. +15 of the run; row 0 of the run is input row iy0
@@ -269,6 +287,8 @@ __device__ __forceinline__ void l7_body(const uint8_t *__restrict__ in, uint8_t 
     uint8_t *patch = smem;
     uint8_t *stage = smem + 2 * L7_REGION;
     uint8_t *scratch = stage + 4 * L7_STAGE;   // 1 KiB sink of the padding loads
+    uint8_t *xch1 = scratch + 1024;            // 5 records of L7_X1
+    uint8_t *xch2 = xch1 + 5 * L7_X1;          // 4 records of L7_X2
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -283,9 +303,9 @@ __device__ __forceinline__ void l7_body(const uint8_t *__restrict__ in, uint8_t 
 
     // lane roles in v_mfma_i32_16x16x64_i8: A row / B column = lane & 15, K bytes 16*(lane>>4)..+15
     const int m = lane & 15, kg = lane >> 4;
-    v4i wf[18];
+    v4i wf[L7_MTILES * L7_KSTEPS];
 #pragma unroll
-    for (int s = 0; s < 18; s++) wf[s] = *(const v4i *)(w_l7 + (s * 16 + m) * 64 + kg * 16);
+    for (int s = 0; s < L7_MTILES * L7_KSTEPS; s++) wf[s] = *(const v4i *)(w_l7 + (s * 16 + m) * 64 + kg * 16);
     const int b0 = bias[0], b1 = bias[1], b2 = bias[2];
 
     const int in_img_bytes = IH * IW * CIN;
@@ -295,8 +315,8 @@ __device__ __forceinline__ void l7_body(const uint8_t *__restrict__ in, uint8_t 
     uint8_t *my_stage = stage + w * L7_STAGE;
     const bool fast_rows = ((OW * 3) & 3) == 0 && X0 + TILE_X <= IW;
 
-    // window row r <-> input row 4*s_begin - 3 + r; rows 0,1 are never read (they only make the
-    // prologue a whole number of pieces)
+    // window row r <-> input row 4*s_begin - 3 + r; rows 0,1 are never fetched (they only make the
+    // prologue a whole number of pieces and read as zeros)
     const int iy_top = 4 * s_begin - 3;
     const int iy_max = min(IH, 4 * s_end + 1);   // last row this chunk reads
     const TensorMap tm = tensor_map(in_layout, CIN, IW, IH);
@@ -313,48 +333,93 @@ __device__ __forceinline__ void l7_body(const uint8_t *__restrict__ in, uint8_t 
         pnext = pnext >= L7_RING_PIECES ? pnext - L7_RING_PIECES : pnext;
     }
 
-    // per-lane fragment addressing: P = (4t + 2 + w + dy)*36 + 16c + m + dx
-    auto frag_a = [&](int tap) { return (uint32_t)((2 + w + tap / 3) * L7_PITCH + m + tap % 3); };
+    // per-lane fragment addressing: step t multiplies window row 4t + 4 + w, P = (4t + 4 + w)*36 + 16c + m + dx
+    auto frag_a = [&](int dx) { return (uint32_t)((4 + w) * L7_PITCH + m + dx); };
     auto frag_s = [&](uint32_t a) { return (uint32_t)((kg & 1) * L7_REGION) + ((((uint32_t)(kg >> 1)) ^ ((a >> 2) & 3u)) << 4); };
-    uint32_t fa[9], fs[9];
+    uint32_t fa[3], fs[3];
 #pragma unroll
-    for (int tap = 0; tap < 9; tap++) {
-        fa[tap] = frag_a(tap);
-        fs[tap] = frag_s(fa[tap]);
+    for (int dx = 0; dx < 3; dx++) {
+        fa[dx] = frag_a(dx);
+        fs[dx] = frag_s(fa[dx]);
     }
+    // exchange: who multiplied the rows above and below this wave's output row
+    const int w_below = (w + 1) & 3;
+    const uint32_t x1_lane = (uint32_t)lane * 4u, x2_lane = (uint32_t)(px * 16 + m) * 4u;
+    int saved[2][3] = {{0, 0, 0}, {0, 0, 0}};   // wave 3: row 4s + 4 without the row below it
     wait_vmcnt<5 * (L7_AHEAD - 1)>();
     block_barrier();
 
-    int base = 0;                          // (144 t) mod ring: ring slot of window row 4t, column 0
-    for (int s = s_begin; s < s_end; s++) {
-        const int Y = 4 * s;               // first input row of this step
-        // always issued (rows past the chunk are zero fill): the counted waits below rely on it
-        l7_load_rows<5>(patch, scratch, in_img, in_img_bytes, w, lane, L7_STEP_PIECES, ynext, 0, iy_max, pnext, X0, IW, tm);
-        ynext += L7_ROWS;
+    // the first pass (s = s_begin - 1) stores nothing and requests nothing: its rows 4 s_begin - 1 and 4 s_begin came with the prologue
+    int base = L7_RING_POS - L7_ROWS * L7_PITCH;   // (144 t) mod ring: ring slot of window row 4t, column 0
+    for (int s = s_begin - 1; s < s_end; s++) {
+        const bool live = s >= s_begin;    // wave-uniform
+        const int par = (s - s_begin) & 1;
+        const int Y = 4 * s;               // first output row pair of this step
+        // always issued in a live step (rows past the chunk are zero fill): the counted waits below rely on it
+        if (live) {
+            l7_load_rows<5>(patch, scratch, in_img, in_img_bytes, w, lane, L7_STEP_PIECES, ynext, 0, iy_max, pnext, X0, IW, tm);
+            ynext += L7_ROWS;
+        }
 
-        v4i acc[2];
-        acc[0] = acc[1] = v4i{b0, b1, b2, 0};  // C row 4*kg + r = phase kg, channel r
+        v4i acc[2][L7_MTILES];
 #pragma unroll
-        for (int tap = 0; tap < 9; tap++) {
+        for (int c = 0; c < 2; c++) {
+            acc[c][0] = v4i{b0, b1, b2, 0};    // C row 4*kg + r of M tile 0 = this lane's own phase, channel r
+            acc[c][1] = v4i{0, 0, 0, 0};
 #pragma unroll
-            for (int c = 0; c < 2; c++) {
-                uint32_t slot = (uint32_t)base + fa[tap] + 16u * c;
+            for (int dx = 0; dx < 3; dx++) {
+                uint32_t slot = (uint32_t)base + fa[dx] + 16u * c;
                 slot = min(slot, slot - (uint32_t)L7_RING_POS);   // one wrap at most
-                const uint32_t addr = slot * 64u + fs[tap];
+                const uint32_t addr = slot * 64u + fs[dx];
                 const v4i p0 = *(const v4i *)(patch + addr);
                 const v4i p1 = *(const v4i *)(patch + (addr ^ 32u));   // channels 64..127: c2 ^ 2
-                acc[c] = __builtin_amdgcn_mfma_i32_16x16x64_i8(wf[tap * 2 + 0], p0, acc[c], 0, 0, 0);
-                acc[c] = __builtin_amdgcn_mfma_i32_16x16x64_i8(wf[tap * 2 + 1], p1, acc[c], 0, 0, 0);
+#pragma unroll
+                for (int t = 0; t < L7_MTILES; t++) {
+                    acc[c][t] = __builtin_amdgcn_mfma_i32_16x16x64_i8(wf[t * L7_KSTEPS + dx * 2 + 0], p0, acc[c][t], 0, 0, 0);
+                    acc[c][t] = __builtin_amdgcn_mfma_i32_16x16x64_i8(wf[t * L7_KSTEPS + dx * 2 + 1], p1, acc[c][t], 0, 0, 0);
+                }
             }
         }
-        asm volatile("" :: "v"(acc[0]), "v"(acc[1]));
+        // ---- products for the neighbouring rows -> exchange --------------------------------------
+        {
+            uint8_t *x1 = xch1 + (w == 3 ? 3 + par : w) * L7_X1, *x2 = xch2 + w * L7_X2;
+#pragma unroll
+            for (int c = 0; c < 2; c++) {
+                const uint32_t lo = __builtin_amdgcn_perm((uint32_t)acc[c][1][1], (uint32_t)acc[c][1][0], 0x0c0c0400u);
+                *(uint32_t *)(x1 + c * 256 + x1_lane) = __builtin_amdgcn_perm((uint32_t)acc[c][1][2], lo, 0x0c040100u);
+                // ky = 4: bytes 0, 1 from the py = 0 lane (c = 0, 1), bytes 2, 3 from the py = 1 lane (c = 2, zero)
+                *(uint16_t *)(x2 + c * 128 + x2_lane + 2 * py) =
+                    (uint16_t)__builtin_amdgcn_perm((uint32_t)acc[c][1][3], (uint32_t)acc[c][0][3], 0x0c0c0400u);
+            }
+        }
+        block_barrier();   // the four rows' products are in the exchange
+        // ---- sums across the rows (low bytes count, the rest is dropped by the pack) --------------
+        int fin[2][3];
+        {
+            // py = 0: ky = 0 of the row above and ky = 4 of the row below; py = 1: ky = 3 of the row below
+            const int w_above1 = w == 0 ? 3 + (par ^ 1) : w - 1, w_below1 = w_below == 3 ? 3 + par : w_below;
+            const uint8_t *x1 = xch1 + (py ? w_below1 : w_above1) * L7_X1, *x2 = xch2 + w_below * L7_X2;
+#pragma unroll
+            for (int c = 0; c < 2; c++) {
+                const uint32_t r1 = *(const uint32_t *)(x1 + c * 256 + x1_lane);
+                const uint32_t r2 = *(const uint32_t *)(x2 + c * 128 + x2_lane);
+                const uint32_t above = py ? 0u : r1, below = py ? r1 : r2;
+#pragma unroll
+                for (int k = 0; k < 3; k++) {
+                    const int cur = acc[c][0][k] + (int)(above >> (8 * k));
+                    const int mine = w == 3 ? saved[c][k] : cur;
+                    saved[c][k] = cur;
+                    fin[c][k] = mine + (int)(below >> (8 * k));
+                }
+            }
+        }
         // ---- epilogue ----------------------------------------------------------------------
-        const int gy = Y + w;
+        const int gy = Y + w_below;        // wave 3 finishes the row it kept from the step before
         if (fast_rows) {
             // stage [2 rows = py][64 pixels = 2*(16c+m)+px][3] and write the rows as dwords
 #pragma unroll
             for (int c = 0; c < 2; c++) {
-                const uint32_t v = pack4_relu7(acc[c][0], acc[c][1], acc[c][2], 0);
+                const uint32_t v = pack4_relu7(fin[c][0], fin[c][1], fin[c][2], 0);
                 uint8_t *d = my_stage + py * 192 + (2 * (16 * c + m) + px) * 3;
                 d[0] = (uint8_t)v;
                 d[1] = (uint8_t)(v >> 8);
@@ -366,7 +431,7 @@ __device__ __forceinline__ void l7_body(const uint8_t *__restrict__ in, uint8_t 
             for (int k = 0; k < 2; k++) {
                 const int idx = k * 64 + lane;                   // dword index in the 2 x 48 tile
                 const int row = idx >= 48 ? 1 : 0, col = idx - 48 * row;
-                const bool ok = idx < 96 && gy < IH;
+                const bool ok = live && idx < 96 && gy < IH;
                 const uint32_t v = *(const uint32_t *)(my_stage + (idx < 96 ? idx : 0) * 4);
                 const uint32_t off = ok ? (uint32_t)(((2 * gy + row) * OW + 2 * X0) * 3 + col * 4) : OOB;
                 __builtin_amdgcn_raw_buffer_store_b32(v, ro, off, 0, 0);
@@ -377,8 +442,8 @@ __device__ __forceinline__ void l7_body(const uint8_t *__restrict__ in, uint8_t 
 #pragma unroll
             for (int c = 0; c < 2; c++) {
                 const int gx = X0 + 16 * c + m;
-                if (gy < IH && gx < IW) {
-                    const uint32_t v = pack4_relu7(acc[c][0], acc[c][1], acc[c][2], 0);
+                if (live && gy < IH && gx < IW) {
+                    const uint32_t v = pack4_relu7(fin[c][0], fin[c][1], fin[c][2], 0);
                     uint8_t *dst = out_img + ((size_t)(2 * gy + py) * OW + 2 * gx + px) * 3;
                     dst[0] = (uint8_t)v;
                     dst[1] = (uint8_t)(v >> 8);
@@ -387,11 +452,13 @@ __device__ __forceinline__ void l7_body(const uint8_t *__restrict__ in, uint8_t 
             }
             wait_vmcnt<0>();
         }
-        block_barrier();   // next rows landed for every wave, this step's rows are free
+        block_barrier();   // next rows landed for every wave, this step's rows and the exchange are free
         base += L7_ROWS * L7_PITCH;
         base = base >= L7_RING_POS ? base - L7_RING_POS : base;
-        pnext += L7_STEP_PIECES;
-        pnext = pnext >= L7_RING_PIECES ? pnext - L7_RING_PIECES : pnext;
+        if (live) {
+            pnext += L7_STEP_PIECES;
+            pnext = pnext >= L7_RING_PIECES ? pnext - L7_RING_PIECES : pnext;
+        }
     }
     wait_vmcnt<0>();   // the zero-fill tail of the prefetch must land before the LDS is released
 }
@@ -402,26 +469,33 @@ __global__ __launch_bounds__(256, L7_WGS) void k_l7(const uint8_t *__restrict__ 
     l7_body(in, out, w_l7, bias, IW, IH, OW, OH, steps_y, y_chunks, tiles_x, n_images, in_layout, n_xcd);
 }
 
-size_t l7_bytes(int cin) { return (size_t)18 * 16 * 64 * (cin / 128); }
+size_t l7_bytes(int cin) { return (size_t)L7_MTILES * L7_KSTEPS * 16 * 64 * (cin / 128); }
 
 void pack_l7(const int8_t *w_okc, int cin, int8_t *dst)
 {
-    // w_okc: [3][25*cin]; dst: [tap 9][half 2][row 16][64 B], row = 4*phase + c
-    for (int tap = 0; tap < 9; tap++)
-        for (int half = 0; half < 2; half++)
-            for (int row = 0; row < 16; row++) {
-                const int ph = row >> 2, c = row & 3, py = ph >> 1, px = ph & 1;
-                const int dy = tap / 3, dx = tap % 3, ky = 2 * dy - py, kx = 2 * dx - px;
-                int8_t *t = dst + (((size_t)tap * 2 + half) * 16 + row) * 64;
-                // K byte b of step `half` is read by lane group kg = b>>4 from LDS region kg&1, chunk
-                // 2*half + (kg>>1): channel 64*(kg&1) + 32*half + 16*(kg>>1) + (b&15)   (see l7_load_rows)
-                for (int b = 0; b < 64; b++) {
-                    const int kg = b >> 4, ch = 64 * (kg & 1) + 32 * half + 16 * (kg >> 1) + (b & 15);
-                    t[b] = (c < 3 && ky >= 0 && ky < 5 && kx >= 0 && kx < 5)
-                               ? w_okc[(size_t)c * 25 * cin + (ky * 5 + kx) * cin + ch]
-                               : 0;
+    // w_okc: [3][25*cin]; dst: [M tile 2][K step 2 dx + half][row 16][64 B]; row = 4*(2 py + px) + r (see the head of this section)
+    for (int tile = 0; tile < L7_MTILES; tile++)
+        for (int dx = 0; dx < 3; dx++)
+            for (int half = 0; half < 2; half++)
+                for (int row = 0; row < 16; row++) {
+                    const int g = row >> 2, r = row & 3, py = g >> 1, px = g & 1;
+                    int ky, c;
+                    if (r < 3) {
+                        ky = tile == 0 ? 2 - py : (py ? 3 : 0);
+                        c = r;
+                    } else {
+                        ky = 4;
+                        c = py ? (tile == 0 ? 2 : -1) : tile;
+                    }
+                    const int kx = 2 * dx - px;
+                    int8_t *t = dst + ((((size_t)tile * 3 + dx) * 2 + half) * 16 + row) * 64;
+                    // K byte b of step `half` is read by lane group kg = b>>4 from LDS region kg&1, chunk
+                    // 2*half + (kg>>1): channel 64*(kg&1) + 32*half + 16*(kg>>1) + (b&15)   (see l7_load_rows)
+                    for (int b = 0; b < 64; b++) {
+                        const int kg = b >> 4, ch = 64 * (kg & 1) + 32 * half + 16 * (kg >> 1) + (b & 15);
+                        t[b] = (c >= 0 && kx >= 0 && kx < 5) ? w_okc[(size_t)c * 25 * cin + (ky * 5 + kx) * cin + ch] : 0;
+                    }
                 }
-            }
 }
 
 hipError_t launch_l7(const LayerGeom &g, const sicn_weights &w, const uint8_t *in, uint8_t *out,
@@ -432,11 +506,11 @@ hipError_t launch_l7(const LayerGeom &g, const sicn_weights &w, const uint8_t *i
     if ((size_t)g.OH * g.OW * 3 >= (size_t)OOB) return hipErrorInvalidValue;   // buffer-descriptor stores
     // about two workgroups per CU in all (three would fit) — measured
     // r02 (tools/strip_sweep.py): 1080p x 1 best at 16 - 24 chunks of 30 strips, x 4 at 4 - 6 of 120, 4K x 8 at 1 of 480;
-    // every extra chunk re-fetches six halo rows and re-loads the 18 KB of weights
+    // every extra chunk re-fetches six halo rows, re-loads the 12 KB of weights and multiplies the two rows above it once more
     // (r03, re-measured on one 1080p image, 30 strips: 13 / 15 / 17 / 19 / 21 / 25 chunks -> 23 / 22 / 19 / 24 / 23 / 21 us: the best
     // cut is the one that stays just under TWO workgroups per CU, 510 of 512; the 640 of round 2 was the middle of a flat region)
     const L7Plan p = plan_l7(g.IW, g.IH, n_images, o.strip_chunks, chip);
-    const size_t lds = 2 * L7_REGION + 4 * L7_STAGE + 1024;
+    const size_t lds = L7_LDS;
     const dim3 grid(p.grid_x);
     hipError_t e = hipFuncSetAttribute((const void *)k_l7, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;

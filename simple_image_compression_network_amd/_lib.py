@@ -276,6 +276,20 @@ def lib() -> ctypes.CDLL:
     return _lib
 
 
+class Handle:
+    """Base of every class that owns one library object in `self._h`: when the Python object goes, the object is given to the
+    library function the class names in `_free`."""
+    _free = ""
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None) and _lib is not None:
+                getattr(_lib, self._free)(self._h)
+                self._h = None
+        except Exception:       # interpreter shutdown: module globals may already be gone
+            pass
+
+
 def check(code: int, what: str) -> None:
     if code != 0:
         raise SicnError(code, what)

@@ -63,8 +63,9 @@ def _check_tensor(t, shape, what):
         raise ValueError(f"{what}: shape {tuple(t.shape)} != {tuple(shape)}")
 
 
-class DeviceWeights:
+class DeviceWeights(_lib.Handle):
     """One layer's weights + bias uploaded through `sicn_weights_from_finn_tiles`."""
+    _free = "sicn_weights_free"
 
     def __init__(self, desc: LayerDesc, weights: FixedPointWeights, bias):
         L = _lib.lib()
@@ -84,19 +85,12 @@ class DeviceWeights:
     def handle(self) -> ctypes.c_void_p:
         return self._h
 
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None) and _lib._lib is not None:
-                _lib._lib.sicn_weights_free(self._h)
-                self._h = None
-        except Exception:       # interpreter shutdown: module globals may already be gone
-            pass
 
-
-class GDN:
+class GDN(_lib.Handle):
     """Fixed-point GDN (inverse=False) / IGDN (inverse=True) activation, include/sicn_gdn.h.  EXTENSION BEYOND THE
     REFERENCE (it has no GDN, activations.hpp:127-224); replaces a layer's sign-bit ReLU (conv_nonsquare_top.cpp:273-275).
     beta: uint32 [C] in [1, 65535]; gamma: uint8 [C][C] in [0, 127]; shift in [1, 24]."""
+    _free = "sicn_gdn_free"
 
     def __init__(self, beta, gamma, inverse: bool = False, shift: int = 12):
         beta = np.ascontiguousarray(beta, dtype=np.uint32)
@@ -122,14 +116,6 @@ class GDN:
         _lib.check(_lib.lib().sicn_gdn_apply(self._h, ctypes.c_void_p(lanes.data_ptr()), lanes.numel() // self.channels,
                                              _stream_ptr(stream)), "sicn_gdn_apply")
         return lanes
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None) and _lib._lib is not None:
-                _lib._lib.sicn_gdn_free(self._h)
-                self._h = None
-        except Exception:       # interpreter shutdown
-            pass
 
 
 def _as_device(desc, weights, bias) -> DeviceWeights:
@@ -207,10 +193,11 @@ class _Param:
 PARAM = _Param()
 
 
-class EightLayersNet:
+class EightLayersNet(_lib.Handle):
     """`eight_layers_net` (conv_nonsquare_top.cpp:295-357) for one image size: descriptors, device
     weights, the chain handle and its ping-pong workspace.  `forward` enqueues the 8 layers on the
     current stream and returns (reconstruction, latent)."""
+    _free = "sicn_net_free"
 
     def __init__(self, width: int = 768, height: int = 512, params=None, device=None,
                  descs: Optional[Sequence[LayerDesc]] = None, shared_weights: Optional[Sequence[DeviceWeights]] = None,
@@ -240,14 +227,6 @@ class EightLayersNet:
             _lib.check(L.sicn_net_create_opt(cdescs, handles, n, _opt_ptr(options), ctypes.byref(self._h)), "sicn_net_create_opt")
         self._ws = None
         self._ws_bytes = {}
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None) and _lib._lib is not None:
-                _lib._lib.sicn_net_free(self._h)
-                self._h = None
-        except Exception:       # interpreter shutdown
-            pass
 
     def workspace(self, n_images: int):
         import torch
@@ -343,69 +322,12 @@ class EightLayersNet:
         return list(ms), list(cnt)
 
 
-class RaggedCrop:
-    """Every image of a ragged tensor cut to its top-left corner, ONE launch for the batch (sicn_ragged_crop_*, include/sicn_ragged.h).
-    src_shapes / dst_shapes: [(h, w)] per image, dst no larger than src; both tensors are flat uint8 CUDA tensors, the images'
-    [h][w][channels] arrays back to back.  What the chain rule rounds up is cut back with it: h_s(z) to the latent's shape, a
-    reconstruction to the image's size."""
-
-    def __init__(self, src_shapes, dst_shapes, channels: int, device=None):
-        import torch
-        L = _lib.lib()
-        self.src_shapes = [(int(h), int(w)) for h, w in src_shapes]
-        self.dst_shapes = [(int(h), int(w)) for h, w in dst_shapes]
-        self.channels = int(channels)
-        n = len(self.src_shapes)
-        if len(self.dst_shapes) != n:
-            raise ValueError("dst_shapes: one (h, w) per source shape")
-        i32 = ctypes.c_int32 * max(n, 1)
-        sw, sh = i32(*[w for _, w in self.src_shapes]), i32(*[h for h, _ in self.src_shapes])
-        dw, dh = i32(*[w for _, w in self.dst_shapes]), i32(*[h for h, _ in self.dst_shapes])
-        self.device = torch.device(device if device is not None else "cuda")
-        self._h = ctypes.c_void_p()
-        with torch.cuda.device(self.device):
-            _lib.check(L.sicn_ragged_crop_create(sw, sh, dw, dh, self.channels, n, ctypes.byref(self._h)), "sicn_ragged_crop_create")
-        self._src_off, self._dst_off = [], []
-        q = (ctypes.c_int64 * 4)()
-        for i in range(n):
-            _lib.check(L.sicn_ragged_crop_layout(sw, sh, dw, dh, self.channels, n, i, q), "sicn_ragged_crop_layout")
-            self._src_off.append(int(q[0]))
-            self._dst_off.append(int(q[1]))
-        self.src_bytes, self.dst_bytes = int(q[2]), int(q[3])
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None) and _lib._lib is not None:
-                _lib._lib.sicn_ragged_crop_free(self._h)
-                self._h = None
-        except Exception:       # interpreter shutdown
-            pass
-
-    def views(self, packed, which: str = "dst"):
-        """Per-image [h][w][channels] views of a destination (which="dst") or source (which="src") tensor (no copy)."""
-        shapes, offs, nbytes = ((self.dst_shapes, self._dst_off, self.dst_bytes) if which == "dst" else
-                                (self.src_shapes, self._src_off, self.src_bytes))
-        _check_tensor(packed, (nbytes,), which)
-        c = self.channels
-        return [packed[o:o + h * w * c].view(h, w, c) for o, (h, w) in zip(offs, shapes)]
-
-    def run(self, src, dst=None, stream=None):
-        """src (ragged, source shapes) -> dst (ragged, destination shapes; allocated when None).  Enqueue only."""
-        import torch
-        _check_tensor(src, (self.src_bytes,), "src")
-        if dst is None:
-            dst = torch.empty(self.dst_bytes, dtype=torch.uint8, device=src.device)
-        _check_tensor(dst, (self.dst_bytes,), "dst")
-        _lib.check(_lib.lib().sicn_ragged_crop_run(self._h, ctypes.c_void_p(src.data_ptr()), ctypes.c_void_p(dst.data_ptr()),
-                                                   _stream_ptr(stream)), "sicn_ragged_crop_run")
-        return dst
-
-
-class RaggedCut:
+class RaggedCut(_lib.Handle):
     """A rectangle out of every image of a ragged tensor, ONE launch for the batch (sicn_ragged_cut_*, include/sicn_ragged_window.h).
     src_shapes: [(h, w)] per image; rects: [(x0, y0, w, h)] per image, inside its source; both tensors are flat uint8 CUDA tensors, the
-    images' [h][w][channels] arrays back to back — or, for the source, at `src_offsets` (bytes, one per image).  RaggedCrop is the
-    case x0 = y0 = 0."""
+    images' [h][w][channels] arrays back to back — or, for the source, at `src_offsets` (bytes, one per image).  RaggedCrop (below) is
+    the case x0 = y0 = 0."""
+    _free = "sicn_ragged_cut_free"
 
     def __init__(self, src_shapes, rects, channels: int, src_offsets=None, device=None):
         import torch
@@ -438,14 +360,6 @@ class RaggedCut:
         with torch.cuda.device(self.device):
             _lib.check(L.sicn_ragged_cut_create(sw, sh, crects, self.channels, offs, n, ctypes.byref(self._h)), "sicn_ragged_cut_create")
 
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None) and _lib._lib is not None:
-                _lib._lib.sicn_ragged_cut_free(self._h)
-                self._h = None
-        except Exception:       # interpreter shutdown
-            pass
-
     def views(self, dst):
         """Per-image [h][w][channels] views of a destination tensor (no copy)."""
         _check_tensor(dst, (self.dst_bytes,), "dst")
@@ -463,6 +377,39 @@ class RaggedCut:
         _lib.check(_lib.lib().sicn_ragged_cut_run(self._h, ctypes.c_void_p(src.data_ptr()), ctypes.c_void_p(dst.data_ptr()),
                                                   _stream_ptr(stream)), "sicn_ragged_cut_run")
         return dst
+
+
+class RaggedCrop(RaggedCut):
+    """Every image of a ragged tensor cut to its top-left corner, ONE launch for the batch: RaggedCut with the rectangles
+    (0, 0, w, h) and both tensors back to back (sicn_ragged_crop_* of include/sicn_ragged_hyper.h are that cut too).
+    src_shapes / dst_shapes: [(h, w)] per image, dst no larger than src.  What the chain rule rounds up is cut back with it: h_s(z)
+    to the latent's shape, a reconstruction to the image's size."""
+
+    def __init__(self, src_shapes, dst_shapes, channels: int, device=None):
+        src_shapes, dst_shapes = list(src_shapes), list(dst_shapes)
+        if len(dst_shapes) != len(src_shapes):
+            raise ValueError("dst_shapes: one (h, w) per source shape")
+        super().__init__(src_shapes, [(0, 0, w, h) for h, w in dst_shapes], channels, device=device)
+
+    def views(self, packed, which: str = "dst"):
+        """Per-image [h][w][channels] views of a destination (which="dst") or source (which="src") tensor (no copy)."""
+        if which == "dst":
+            return super().views(packed)
+        _check_tensor(packed, (self.src_bytes,), which)
+        c = self.channels
+        return [packed[o:o + h * w * c].view(h, w, c) for o, (h, w) in zip(self._src_off, self.src_shapes)]
+
+    def run(self, src, dst=None, stream=None):
+        """src (ragged, source shapes, exactly src_bytes long) -> dst (ragged, destination shapes; allocated when None).  Enqueue only."""
+        _check_tensor(src, (self.src_bytes,), "src")
+        return super().run(src, dst, stream)
+
+
+def _raise_on_status(status, what):
+    """Raises for a batch's decoder verdicts (one word per image) unless all are 0: SICN_EBADMSG (-74) where nothing but the
+    checksum of a whole latent (bit 7) failed, SICN_EINVAL (-22) otherwise.  A window decode never sets bit 7."""
+    if any(status):
+        raise _lib.SicnError(-22 if any(v & ~128 for v in status) else -74, f"{what} status {status}")
 
 
 def roi_plan(size, rect, n_up_layers: int = 4):
@@ -530,7 +477,7 @@ class RaggedRoi:
         return self.pixel_cut.views(roi)
 
 
-class RaggedNet:
+class RaggedNet(_lib.Handle):
     """A layer chain over images of DIFFERENT sizes, one kernel launch per layer for the whole batch (include/sicn_ragged.h); by
     default the 8-layer chain.  `sizes`: [(width, height)] per image at the chain's input.  A ragged tensor is a flat uint8 CUDA
     tensor: the images' [H][W][C] arrays back to back; `layer` -1 names the input, l the output of layer l.  Same bytes as
@@ -538,6 +485,7 @@ class RaggedNet:
     `descs`: any chain the ragged kernels serve instead of the eight layers (its spatial fields are ignored; `params` or
     `shared_weights` must match it, as in `EightLayersNet(descs=...)`).  `gdn`: a list of `GDN | None`, one per layer — the
     activation in place of that layer's ReLU (sicn_ragged_net_create_gdn); one more launch per such layer, for the whole batch."""
+    _free = "sicn_ragged_net_free"
 
     def __init__(self, sizes, params=None, device=None, n_ch: int = 128, m_ch: int = 192,
                  shared_weights: Optional[Sequence[DeviceWeights]] = None, descs: Optional[Sequence[LayerDesc]] = None,
@@ -591,14 +539,6 @@ class RaggedNet:
         self._crop = None           # cropped()'s RaggedCrop, made on first use
         self._rois = {}             # decompress_archive(rois=)'s RaggedRoi objects by coder and rectangles
         self._last_roi = None
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None) and _lib._lib is not None:
-                _lib._lib.sicn_ragged_net_free(self._h)
-                self._h = None
-        except Exception:       # interpreter shutdown
-            pass
 
     def shapes(self, layer: int):
         """[(H, W, C)] of every image at boundary `layer`."""
@@ -689,15 +629,34 @@ class RaggedNet:
         return codec.RaggedLatentCoder([(h, w) for h, w, _ in self.shapes(3)], self.shapes(3)[0][2], self.sizes,
                                        stream_symbols=stream_symbols, device=self.device)
 
+    def _coder_for(self, stream_symbols):
+        """(key, coder): the latent coder for these stream lengths — one number, "auto", or one length per image — made on first
+        use and shared by compress, compress_archive and decompress_archive: creating one costs device allocations, table uploads
+        and a synchronisation.  Lengths per image are served by a coder that already has them, whatever it was asked for."""
+        if isinstance(stream_symbols, (int, str)):
+            key = stream_symbols
+        else:
+            stream_symbols = [int(v) for v in stream_symbols]
+            key = next((k for k, c in self._coders.items() if c.stream_symbols == stream_symbols), None)
+            if key is None:
+                key = stream_symbols[0] if len(set(stream_symbols)) == 1 else tuple(stream_symbols)
+        if key not in self._coders:
+            self._coders[key] = self.latent_coder(stream_symbols)
+        return key, self._coders[key]
+
+    def _archive_for(self, key):
+        """The one-section archive object over the coder of `key` (`_coder_for`), made on first use."""
+        from . import codec
+        if key not in self._archives:
+            self._archives[key] = codec.RaggedArchive([self._coders[key]], tag=0, device=self.device)
+        return self._archives[key]
+
     def compress(self, packed_in, stream_symbols=16384, stream=None):
         """Ragged input -> one rANS-W container (`bytes`) per image: layers 0-3, then the ragged encoder, enqueued back to back;
         the only host synchronisation is the read-back of the containers at the end.  stream_symbols: 16384, the format's default,
         gives the bytes of `EightLayersNet(w, h)` + `codec.encode_latent` on every image alone; "auto" or a shorter power of two
         (codec.RaggedLatentCoder) shortens the serial chain of small latents at 260 bytes per extra stream."""
-        key = stream_symbols if isinstance(stream_symbols, (int, str)) else tuple(stream_symbols)
-        if key not in self._coders:
-            self._coders[key] = self.latent_coder(stream_symbols)
-        coder = self._coders[key]
+        _, coder = self._coder_for(stream_symbols)
         latent, _ = self.run_layers(0, 3, packed_in, stream=stream)
         coder.encode(latent, stream=stream)
         return coder.containers()
@@ -720,14 +679,8 @@ class RaggedNet:
         """`compress` with the batch's containers as ONE byte string (codec.RaggedArchive, tag 0): layers 0-3, the ragged encoder and
         the two launches that pack the archive on the device, enqueued back to back; exactly the archive's bytes travel to the host.
         `codec.split_archive` of the result gives `compress`'s containers."""
-        from . import codec
-        key = stream_symbols if isinstance(stream_symbols, (int, str)) else tuple(stream_symbols)
-        if key not in self._coders:
-            self._coders[key] = self.latent_coder(stream_symbols)
-        coder = self._coders[key]
-        if key not in self._archives:
-            self._archives[key] = codec.RaggedArchive([coder], tag=0, device=self.device)
-        archive = self._archives[key]
+        key, coder = self._coder_for(stream_symbols)
+        archive = self._archive_for(key)
         latent, _ = self.run_layers(0, 3, packed_in, stream=stream)
         coder.encode(latent, stream=stream)
         archive.pack(stream=stream)
@@ -775,17 +728,8 @@ class RaggedNet:
             raise ValueError("not an archive of one rANS-W section")
         if [info["latent_shapes"][i][0] for i in chosen] != self.shapes(3) or [info["image_sizes"][i] for i in chosen] != self.sizes:
             raise ValueError("the archive's image sizes or latent shapes are not this net's")
-        # one coder and one archive object per set of stream lengths, shared with compress_archive: creating them costs device
-        # allocations, table uploads and a synchronisation
-        lengths = [int(h.stream_symbols) for h in heads]
-        key = next((k for k, c in self._coders.items() if c.stream_symbols == lengths), None)
-        if key is None:
-            key = lengths[0] if len(set(lengths)) == 1 else tuple(lengths)
-            self._coders[key] = self.latent_coder(lengths)
-        coder = self._coders[key]
-        if key not in self._archives:
-            self._archives[key] = codec.RaggedArchive([coder], tag=0, device=self.device)
-        archive = self._archives[key]
+        key, coder = self._coder_for([int(h.stream_symbols) for h in heads])
+        archive = self._archive_for(key)
         if rois is not None:
             if (key, rois) not in self._rois:
                 self._rois[(key, rois)] = RaggedRoi(self, rois, coder=coder)
@@ -793,18 +737,15 @@ class RaggedNet:
             valid, = archive.unpack(b, stream=stream, images=sel)
             out = roi.decode(valid=valid, stream=stream, out=out)
             archive.check()
-            status = roi.status[:, 0].cpu().tolist()
-            if any(status):
-                raise _lib.SicnError(-22, f"rANS-W window decode status {status}")
+            _raise_on_status(roi.status[:, 0].cpu().tolist(), "rANS-W window decode")
             return out
         valid, = archive.unpack(b, stream=stream, images=sel)
         latent = torch.empty(self.nbytes(3), dtype=torch.uint8, device=self.device)
         coder.decode(latent, valid=valid, stream=stream)
         out, _ = self.run_layers(4, len(self.descs) - 1, latent, out=out, stream=stream)
         archive.check()
-        status = coder.dec_status[:, 0].cpu().tolist()      # the decoder's verdicts alone: the shared coder's encoder status is another call's
-        if any(status):
-            raise _lib.SicnError(-22 if any(v & ~128 for v in status) else -74, f"rANS-W decode status {status}")
+        # the decoder's verdicts alone: the shared coder's encoder status is another call's
+        _raise_on_status(coder.dec_status[:, 0].cpu().tolist(), "rANS-W decode")
         return out
 
 

@@ -206,7 +206,7 @@ class LatentCoder:
             raise _lib.SicnError(-22 if any(v & ~128 for v in d) else -74, f"rANS-W decode status {d}")
 
 
-class RaggedLatentCoder:
+class RaggedLatentCoder(_lib.Handle):
     """The ragged rANS-W pair (include/sicn_ragged_codec.h): n latents of n DIFFERENT shapes -> n containers with three launches for
     the whole batch, and back with two.  `shapes`: [(lat_h, lat_w)] per image, `lat_c` channels in all of them; `image_sizes`:
     [(width, height)], header fields only.  Latents travel as a ragged tensor — a flat CUDA uint8 tensor, the images' [h][w][c]
@@ -214,6 +214,7 @@ class RaggedLatentCoder:
     stream_symbols: None or "auto" = `auto_stream_symbols` of EACH image's own latent, one value for all, or one per image.
     Container i is byte-identical to `LatentCoder(1, h_i, w_i, lat_c, stream_symbols=...)`'s and decodes with `decode_latent`.
     Same conventions as LatentCoder: enqueue only; verdicts and sizes stay on the device until `check()` / `sizes()` fetch them."""
+    _free = "sicn_ragged_coder_free"
 
     def __init__(self, shapes, lat_c: int, image_sizes=None, stream_symbols=None, device=None):
         import torch
@@ -250,14 +251,6 @@ class RaggedLatentCoder:
         self.ws = torch.empty(max(int(L.sicn_ragged_coder_workspace_bytes(self._h)), 256), dtype=torch.uint8, device=self.device)
         self.enc_status = torch.zeros((n, 2), dtype=torch.int32, device=self.device)   # sicn_codec_status {error, bytes}
         self.dec_status = torch.zeros((n, 2), dtype=torch.int32, device=self.device)
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None) and _lib._lib is not None:
-                _lib._lib.sicn_ragged_coder_free(self._h)
-                self._h = None
-        except Exception:       # interpreter shutdown
-            pass
 
     @classmethod
     def for_containers(cls, containers, device=None):
@@ -338,12 +331,13 @@ class RaggedLatentCoder:
         return [host[int(im.slot_offset):int(im.slot_offset) + size].tobytes() for im, (_, size) in zip(self.images, status)]
 
 
-class RaggedWindowDecoder:
+class RaggedWindowDecoder(_lib.Handle):
     """A window of latent ROWS of every image decoded from its streams alone (include/sicn_ragged_window.h): two launches for the
     batch.  Made by `RaggedLatentCoder.window(rows)`; shapes, stream lengths, slot buffer and workspace are the coder's, so whatever
     fills the coder's slots (`encode`, `RaggedArchive.unpack`) feeds this decoder.  The result is the BAND tensor: per image the
     symbols of the streams that hold the rows, image i at `images[i].band_offset`, row r0 `images[i].lead` bytes further.
     `.status`: device int32 [n][2], the window decoder's verdicts (bit 7, the checksum of the whole latent, is never set)."""
+    _free = "sicn_ragged_window_free"
 
     def __init__(self, coder, rows):
         import torch
@@ -367,14 +361,6 @@ class RaggedWindowDecoder:
         with torch.cuda.device(coder.device):
             _lib.check(L.sicn_ragged_window_create(coder._h, self._r0, self._rh, ctypes.byref(self._h)), "sicn_ragged_window_create")
         self.status = torch.zeros((n, 2), dtype=torch.int32, device=coder.device)
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None) and _lib._lib is not None:
-                _lib._lib.sicn_ragged_window_free(self._h)
-                self._h = None
-        except Exception:       # interpreter shutdown
-            pass
 
     def views(self, band):
         """Per-image [rh][lat_w][lat_c] views of the rows asked for, inside a band tensor (no copy)."""
@@ -456,13 +442,14 @@ class ContextCoder:
     check = LatentCoder.check
 
 
-class RaggedContextCoder:
+class RaggedContextCoder(_lib.Handle):
     """The ragged rANS-WC pair (include/sicn_ragged_ctx.h): n latents of n DIFFERENT shapes, each with its scale map -> n mode-4
     containers with six launches for the whole batch, and back with eight.  `shapes`: [(lat_h, lat_w)] per image, `lat_c` channels
     (a multiple of 4) in all of them; `image_sizes`: [(width, height)], header fields only.  Latents and scales travel as two ragged
     tensors of one layout — flat CUDA uint8 tensors, the images' [h][w][c] arrays back to back — containers in one flat slot buffer,
     image i's slot at `images[i].slot_offset`.  Container i is byte-identical to `ContextCoder(1, h_i, w_i, lat_c)`'s and decodes
     with it.  Same conventions as RaggedLatentCoder: enqueue only; verdicts and sizes stay on the device until `check()` / `sizes()`."""
+    _free = "sicn_ragged_ctx_coder_free"
 
     def __init__(self, shapes, lat_c: int, image_sizes=None, device=None):
         import torch
@@ -489,14 +476,6 @@ class RaggedContextCoder:
         self.ws = torch.empty(max(int(L.sicn_ragged_ctx_coder_workspace_bytes(self._h)), 256), dtype=torch.uint8, device=self.device)
         self.enc_status = torch.zeros((n, 2), dtype=torch.int32, device=self.device)   # sicn_codec_status {error, bytes}
         self.dec_status = torch.zeros((n, 2), dtype=torch.int32, device=self.device)
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None) and _lib._lib is not None:
-                _lib._lib.sicn_ragged_ctx_coder_free(self._h)
-                self._h = None
-        except Exception:       # interpreter shutdown
-            pass
 
     @classmethod
     def for_containers(cls, containers, device=None):
@@ -651,13 +630,14 @@ def subset_archive(b, images):
     return out.raw
 
 
-class RaggedArchive:
+class RaggedArchive(_lib.Handle):
     """The containers of a ragged batch as ONE byte string (include/sicn_ragged_archive.h): packed on the device from the slot buffers
     and encoder status arrays of one to four ragged coder objects of one batch as they lie — two launches, whatever the number of
     images — and unpacked into those coders' own slot buffers with the `valid` arrays their `decode(..., valid=...)` takes, with two.
     `coders`: RaggedLatentCoder / RaggedContextCoder objects (anything with `images[i].slot_offset / .slot_bytes`, `shapes`,
     `slot_buffer` and `enc_status`), one section each, in the archive's section order.  `tag`: stored by pack, compared by unpack.
     Same conventions as the coders: pack / unpack enqueue only; `bytes()` and `check()` synchronise."""
+    _free = "sicn_ragged_archive_free"
 
     def __init__(self, coders, tag: int = 0, device=None):
         import torch
@@ -685,14 +665,6 @@ class RaggedArchive:
         self.valid = [torch.zeros((n, 2), dtype=torch.int32, device=self.device) for _ in range(k)]   # unpack()'s {error, bytes} per section
         self._in = None             # the device copy of unpack()'s archive: alive until the next unpack
         self._index = None          # ... and of its selection (unpack(images=...))
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None) and _lib._lib is not None:
-                _lib._lib.sicn_ragged_archive_free(self._h)
-                self._h = None
-        except Exception:       # interpreter shutdown
-            pass
 
     def _ptrs(self, tensors):
         return (ctypes.c_void_p * self.n_sections)(*[t.data_ptr() for t in tensors])

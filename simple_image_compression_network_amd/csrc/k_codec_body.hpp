@@ -11,6 +11,7 @@
 
 #include "../../include/sicn.h"
 #include "../../include/sicn_codec.h"
+#include "k_ragged_common.hpp"
 
 namespace {
 
@@ -107,6 +108,14 @@ struct CoderRow {
     uint32_t lat_w, lat_h, lat_c, img_w, img_h;
     uint32_t first_stream, first_row, n_rows;   // ragged: the image's first work items in the flat grids; n_rows: its statistics rows
 };
+// a row of a table in memory (the ragged kernels), every field wave-uniform
+__device__ __forceinline__ CoderRow load_row(const CoderRow *__restrict__ rows, uint32_t img)
+{
+    const CoderRow *r = rows + img;
+    return CoderRow{uni(r->lat_off), uni(r->slot_off), uni(r->ws_off), uni(r->n), uni(r->ns), uni(r->wss), uni(r->slot_cap),
+                    uni(r->lat_w), uni(r->lat_h), uni(r->lat_c), uni(r->img_w), uni(r->img_h), uni(r->first_stream),
+                    uni(r->first_row), uni(r->n_rows)};
+}
 // A uniform batch (sicn_codec.hip: blockIdx.y = image, every image of one shape) is image 0's row and three byte strides.  Passed by
 // value, so it lives in kernel-argument SGPRs.  `scan`: the form above SELF_SCAN_MAX streams (no statistics rows; k_scan in front).
 struct UniformBatch {

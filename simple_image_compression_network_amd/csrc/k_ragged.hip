@@ -10,13 +10,15 @@
 // Both loads are wave-uniform (they depend on blockIdx.x only) and stay in scalar registers.
 //
 // A layer with a GDN / IGDN (sicn_ragged_net_create_gdn) runs the same kernel with ACT_FLOOR_RAW and then the activation of k_gdn.hip in
-// place over the whole boundary tensor: [bytes / OFM_CH][OFM_CH], no table needed.  The ragged crop at the end of this file follows the
-// same pattern as k_any_ragged with a work item of CROP_ROWS destination rows of one image.
+// place over the whole boundary tensor: [bytes / OFM_CH][OFM_CH], no table needed.  The ragged crop at the end of this file is the cut
+// of k_ragged_window.hip at the corner of every image: the rectangles (0, 0, dst_w, dst_h), the images back to back, the same handle.
 #include <new>
 #include <vector>
 
 #include "../../include/sicn_ragged_hyper.h"
+#include "../../include/sicn_ragged_window.h"
 #include "k_any_body.hpp"
+#include "k_ragged_common.hpp"
 #include "sicn_gdn_internal.h"
 #include "sicn_weights_io.h"
 
@@ -68,8 +70,6 @@ struct RaggedPlan {
     std::vector<RaggedBoundary> bounds;     // [n_layers + 1]
     std::vector<RaggedLayerPlan> layers;    // [n_layers]
 };
-
-constexpr int64_t RAGGED_MAX_ITEMS = 0x7fffffffLL;   // a layer has fewer work items than this (grid.x)
 
 static int ragged_plan(const sicn_layer_desc *descs, int n_layers, const int32_t *widths, const int32_t *heights, int n_images,
                        RaggedPlan *plan)
@@ -137,88 +137,6 @@ static hipError_t launch_ragged_as(const uint8_t *in, uint8_t *out, const int8_t
     hipLaunchKernelGGL((k_any_ragged<DECONV, NT>), dim3(items, (unsigned)((cout + 63) / 64), 1), dim3(256), lds, stream, in, out, wimg, bias,
                        rows, tile_image, cin, cout, floor2);
     return hipGetLastError();
-}
-
-// ---- ragged crop: dst image i = the top-left [dst_h][dst_w][C] of src image i -----------------------------------------------------------
-// Grid: x = work items over all images, a work item = CROP_ROWS destination rows of one image (the image's last item: the rest).
-//   item_image[item] : the image of an item
-//   rows[image]      : { source / destination row bytes, destination rows, first item, vec, 64-bit offsets in src and dst }
-// As in k_any_ragged both loads depend on blockIdx.x only.  `vec` (per image, host-made): both row lengths and both offsets are
-// multiples of 16; `ptr16` (per launch): so are both base pointers.  Then a row is copied as uint4, otherwise byte by byte.
-constexpr int CROP_ROWS = SICN_RAGGED_CROP_ROWS;
-
-struct CropRow {
-    uint32_t src_row, dst_row, dst_h, first_item, vec, pad;
-    int64_t src_off, dst_off;
-};
-
-__global__ __launch_bounds__(256) void k_ragged_crop(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, const CropRow *__restrict__ rows,
-                                                     const uint32_t *__restrict__ item_image, int ptr16)
-{
-    const uint32_t item = blockIdx.x;
-    const int img = __builtin_amdgcn_readfirstlane((int)item_image[item]);
-    const CropRow *row = rows + img;
-    const uint32_t src_row = (uint32_t)__builtin_amdgcn_readfirstlane((int)row->src_row);
-    const uint32_t dst_row = (uint32_t)__builtin_amdgcn_readfirstlane((int)row->dst_row);
-    const uint32_t dst_h = (uint32_t)__builtin_amdgcn_readfirstlane((int)row->dst_h);
-    const uint32_t y0 = (item - (uint32_t)__builtin_amdgcn_readfirstlane((int)row->first_item)) * (uint32_t)CROP_ROWS;
-    const int vec = __builtin_amdgcn_readfirstlane((int)row->vec) & ptr16;
-    const uint64_t src_off = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)row->src_off) |
-                             (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(row->src_off >> 32)) << 32;
-    const uint64_t dst_off = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)row->dst_off) |
-                             (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(row->dst_off >> 32)) << 32;
-    if (y0 >= dst_h) return;                                  // cannot happen with the host's tables
-    const uint32_t n_rows = dst_h - y0 < (uint32_t)CROP_ROWS ? dst_h - y0 : (uint32_t)CROP_ROWS;
-    // one image's tensor is < 2^31 bytes (host check), so every index below fits 32 bits
-    const uint8_t *s = src + src_off + (size_t)y0 * src_row;
-    uint8_t *d = dst + dst_off + (size_t)y0 * dst_row;
-    if (vec) {
-        const uint32_t q_row = dst_row / 16, total = n_rows * q_row;
-        for (uint32_t i = threadIdx.x; i < total; i += 256) {
-            const uint32_t r = i / q_row, q = i - r * q_row;
-            reinterpret_cast<uint4 *>(d + (size_t)r * dst_row)[q] = reinterpret_cast<const uint4 *>(s + (size_t)r * src_row)[q];
-        }
-    } else {
-        const uint32_t total = n_rows * dst_row;
-        for (uint32_t i = threadIdx.x; i < total; i += 256) {
-            const uint32_t r = i / dst_row, b = i - r * dst_row;
-            d[(size_t)r * dst_row + b] = s[(size_t)r * src_row + b];
-        }
-    }
-}
-
-struct CropPlan {
-    std::vector<CropRow> rows;              // [n_images]
-    std::vector<int64_t> first_item;        // [n_images + 1]
-    int64_t src_bytes = 0, dst_bytes = 0;
-};
-
-static int crop_plan(const int32_t *src_w, const int32_t *src_h, const int32_t *dst_w, const int32_t *dst_h, int channels, int n_images,
-                     CropPlan *plan)
-{
-    if (!src_w || !src_h || !dst_w || !dst_h || n_images < 1 || channels < 1) return SICN_EINVAL;
-    for (int i = 0; i < n_images; i++) {
-        if (dst_w[i] < 1 || dst_h[i] < 1 || src_w[i] > (1 << 20) || src_h[i] > (1 << 20)) return SICN_EINVAL;
-        if (dst_w[i] > src_w[i] || dst_h[i] > src_h[i]) return SICN_EINVAL;
-        if ((double)src_h[i] * src_w[i] * channels >= (double)OOB) return SICN_EINVAL;   // before the 64-bit product can overflow
-    }
-    try {
-        plan->rows.resize((size_t)n_images);
-        plan->first_item.assign((size_t)n_images + 1, 0);
-        int64_t so = 0, dof = 0;
-        for (int i = 0; i < n_images; i++) {
-            const int64_t srow = (int64_t)src_w[i] * channels, drow = (int64_t)dst_w[i] * channels;
-            const uint32_t vec = ((srow | drow | so | dof) & 15) == 0;
-            plan->rows[(size_t)i] = CropRow{(uint32_t)srow, (uint32_t)drow, (uint32_t)dst_h[i], (uint32_t)plan->first_item[(size_t)i], vec, 0u, so, dof};
-            plan->first_item[(size_t)i + 1] = plan->first_item[(size_t)i] + (dst_h[i] + CROP_ROWS - 1) / CROP_ROWS;
-            if (plan->first_item[(size_t)i + 1] >= RAGGED_MAX_ITEMS) return SICN_EINVAL;
-            so += srow * src_h[i];
-            dof += drow * dst_h[i];
-        }
-        plan->src_bytes = so;
-        plan->dst_bytes = dof;
-    } catch (const std::bad_alloc &) { return SICN_ENOMEM; }
-    return SICN_OK;
 }
 
 }  // namespace sicn
@@ -391,34 +309,31 @@ extern "C" int sicn_ragged_net_forward(const sicn_ragged_net *net, int first, in
     return SICN_OK;
 }
 
-// ---- ragged crop --------------------------------------------------------------------------------------------------------------------
-struct sicn_ragged_crop {
-    int n_images = 0;
-    unsigned items = 0;
-    CropRow *d_rows = nullptr;              // [n_images]
-    uint32_t *d_item_image = nullptr;       // [items]
-};
+// ---- ragged crop: dst image i = the top-left [dst_h][dst_w][C] of src image i --------------------------------------------------------
+// The cut (k_ragged_window.hip) of the rectangles (0, 0, dst_w, dst_h) without source offsets; a crop handle IS a cut handle.
+static sicn_ragged_cut *as_cut(sicn_ragged_crop *crop) { return reinterpret_cast<sicn_ragged_cut *>(crop); }
+static const sicn_ragged_cut *as_cut(const sicn_ragged_crop *crop) { return reinterpret_cast<const sicn_ragged_cut *>(crop); }
+static sicn_ragged_crop *as_crop(sicn_ragged_cut *cut) { return reinterpret_cast<sicn_ragged_crop *>(cut); }
+
+// the arguments are checked before dst_w and dst_h are read; what an image may be is the cut's to say
+static int corner_rects(const int32_t *src_w, const int32_t *src_h, const int32_t *dst_w, const int32_t *dst_h, int channels, int n_images,
+                        std::vector<sicn_ragged_rect> *rects)
+{
+    if (!src_w || !src_h || !dst_w || !dst_h || n_images < 1 || channels < 1) return SICN_EINVAL;
+    try {
+        rects->resize((size_t)n_images);
+    } catch (const std::bad_alloc &) { return SICN_ENOMEM; }
+    for (int i = 0; i < n_images; i++) (*rects)[(size_t)i] = sicn_ragged_rect{0, 0, dst_w[i], dst_h[i]};
+    return SICN_OK;
+}
 
 extern "C" int sicn_ragged_crop_layout(const int32_t *src_w, const int32_t *src_h, const int32_t *dst_w, const int32_t *dst_h, int channels,
                                        int n_images, int image, int64_t out[4])
 {
     if (!out) return SICN_EINVAL;
-    CropPlan p;
-    if (int rc = crop_plan(src_w, src_h, dst_w, dst_h, channels, n_images, &p)) return rc;
-    if (image < 0 || image >= n_images) return SICN_EINVAL;
-    out[0] = p.rows[(size_t)image].src_off;
-    out[1] = p.rows[(size_t)image].dst_off;
-    out[2] = p.src_bytes;
-    out[3] = p.dst_bytes;
-    return SICN_OK;
-}
-
-extern "C" void sicn_ragged_crop_free(sicn_ragged_crop *crop)
-{
-    if (!crop) return;
-    if (crop->d_rows) (void)hipFree(crop->d_rows);
-    if (crop->d_item_image) (void)hipFree(crop->d_item_image);
-    delete crop;
+    std::vector<sicn_ragged_rect> rects;
+    if (int rc = corner_rects(src_w, src_h, dst_w, dst_h, channels, n_images, &rects)) return rc;
+    return ragged_cut_layout(src_w, src_h, rects.data(), channels, nullptr, n_images, image, out);
 }
 
 extern "C" int sicn_ragged_crop_create(const int32_t *src_w, const int32_t *src_h, const int32_t *dst_w, const int32_t *dst_h, int channels,
@@ -426,35 +341,17 @@ extern "C" int sicn_ragged_crop_create(const int32_t *src_w, const int32_t *src_
 {
     if (!out) return SICN_EINVAL;
     *out = nullptr;
-    CropPlan p;
-    if (int rc = crop_plan(src_w, src_h, dst_w, dst_h, channels, n_images, &p)) return rc;
-    if (int rc = chip_geom(nullptr)) return rc;      // no device, or not a gfx950 one
-    sicn_ragged_crop *crop = new (std::nothrow) sicn_ragged_crop();
-    if (!crop) return SICN_ENOMEM;
-    int rc = SICN_OK;
-    try {
-        crop->n_images = n_images;
-        crop->items = (unsigned)p.first_item[(size_t)n_images];
-        std::vector<uint32_t> map;
-        map.reserve((size_t)crop->items);
-        for (int i = 0; i < n_images; i++) map.insert(map.end(), (size_t)(p.first_item[(size_t)i + 1] - p.first_item[(size_t)i]), (uint32_t)i);
-        if (!upload(p.rows.data(), p.rows.size() * sizeof(CropRow), &crop->d_rows) ||
-            !upload(map.data(), map.size() * sizeof(uint32_t), &crop->d_item_image))
-            rc = SICN_ENOMEM;
-    } catch (const std::bad_alloc &) { rc = SICN_ENOMEM; }
-    if (rc) {
-        sicn_ragged_crop_free(crop);
-        return rc;
-    }
-    *out = crop;
-    return SICN_OK;
+    std::vector<sicn_ragged_rect> rects;
+    if (int rc = corner_rects(src_w, src_h, dst_w, dst_h, channels, n_images, &rects)) return rc;
+    sicn_ragged_cut *cut = nullptr;
+    const int rc = ragged_cut_create(src_w, src_h, rects.data(), channels, nullptr, n_images, &cut);
+    *out = as_crop(cut);
+    return rc;
 }
+
+extern "C" void sicn_ragged_crop_free(sicn_ragged_crop *crop) { sicn_ragged_cut_free(as_cut(crop)); }
 
 extern "C" int sicn_ragged_crop_run(const sicn_ragged_crop *crop, const uint8_t *src, uint8_t *dst, void *hip_stream)
 {
-    if (!crop || !src || !dst) return SICN_EINVAL;
-    if (int rc = chip_geom(nullptr)) return rc;
-    const int ptr16 = ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0;
-    hipLaunchKernelGGL(k_ragged_crop, dim3(crop->items), dim3(256), 0, (hipStream_t)hip_stream, src, dst, crop->d_rows, crop->d_item_image, ptr16);
-    return hipGetLastError() == hipSuccess ? SICN_OK : SICN_ENODEV;
+    return ragged_cut_run(as_cut(crop), src, dst, hip_stream);
 }

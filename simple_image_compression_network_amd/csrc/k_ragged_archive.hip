@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "archive_host.hpp"
+#include "k_ragged_common.hpp"
 #include "sicn_internal.h"
 #include "sicn_weights_io.h"
 
@@ -37,8 +38,6 @@ struct ArchRow {
 };
 struct Ptrs4 { uint8_t *p[MAX_SECTIONS]; };        // one pointer per section, by value in the kernel arguments
 
-__device__ __forceinline__ uint32_t uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
-__device__ __forceinline__ uint64_t uni(uint64_t v) { return (uint64_t)uni((uint32_t)v) | (uint64_t)uni((uint32_t)(v >> 32)) << 32; }
 // a select chain, not an indexed load: kernel arguments indexed at run time would go through scratch
 __device__ __forceinline__ uint8_t *pick(const Ptrs4 &a, uint32_t s) { return s == 0 ? a.p[0] : s == 1 ? a.p[1] : s == 2 ? a.p[2] : a.p[3]; }
 

@@ -20,18 +20,6 @@
 
 namespace {
 
-__device__ __forceinline__ uint32_t uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
-__device__ __forceinline__ uint64_t uni(uint64_t v) { return (uint64_t)uni((uint32_t)v) | (uint64_t)uni((uint32_t)(v >> 32)) << 32; }
-
-// the image's row, every field wave-uniform
-__device__ __forceinline__ CoderRow load_row(const CoderRow *__restrict__ rows, uint32_t img)
-{
-    const CoderRow *r = rows + img;
-    return CoderRow{uni(r->lat_off), uni(r->slot_off), uni(r->ws_off), uni(r->n), uni(r->ns), uni(r->wss), uni(r->slot_cap),
-                          uni(r->lat_w), uni(r->lat_h), uni(r->lat_c), uni(r->img_w), uni(r->img_h), uni(r->first_stream),
-                          uni(r->first_row), uni(r->n_rows)};
-}
-
 __global__ __launch_bounds__(256) void k_ragged_stats(const uint8_t *__restrict__ latents, uint8_t *__restrict__ workspace,
                                                       const CoderRow *__restrict__ rows, const uint32_t *__restrict__ row_image)
 {

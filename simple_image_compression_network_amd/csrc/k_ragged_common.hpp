@@ -1,0 +1,19 @@
+// What the ragged translation units (k_ragged*.hip) share: the limit of a flat grid and the wave-uniform load.  The host part is
+// plain C++, so that window_host.hpp can include this file in a program without HIP.
+#pragma once
+#ifdef __HIPCC__
+#include <hip/hip_runtime.h>
+#endif
+#include <stdint.h>
+
+namespace sicn {
+constexpr int64_t RAGGED_MAX_ITEMS = 0x7fffffffLL;   // a launch has fewer work items than this (grid.x)
+}
+
+#ifdef __HIPCC__
+namespace {
+// a value that depends on blockIdx only, moved to scalar registers
+__device__ __forceinline__ uint32_t uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+__device__ __forceinline__ uint64_t uni(uint64_t v) { return (uint64_t)uni((uint32_t)v) | (uint64_t)uni((uint32_t)(v >> 32)) << 32; }
+}  // namespace
+#endif

@@ -34,9 +34,6 @@ struct CtxRow {
     uint32_t first_enc, first_dec[2], first_stream;
 };
 
-__device__ __forceinline__ uint32_t uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
-__device__ __forceinline__ uint64_t uni(uint64_t v) { return (uint64_t)uni((uint32_t)v) | (uint64_t)uni((uint32_t)(v >> 32)) << 32; }
-
 // the image's row, every field wave-uniform
 __device__ __forceinline__ CtxRow load_row(const CtxRow *__restrict__ rows, uint32_t img)
 {
@@ -167,8 +164,6 @@ __global__ __launch_bounds__(64) void k_ragged_ctx_finish(uint32_t *__restrict__
 }
 
 // ---- the layout: pure host --------------------------------------------------------------------------------------------------
-constexpr uint64_t RAGGED_MAX_ITEMS = 0x7fffffffull;   // fewer work items of a kind than this in all (grid.x)
-
 struct Plan {
     std::vector<CtxRow> rows;
     uint64_t lat_bytes = 0, slot_bytes = 0, ws_bytes = 0, streams = 0, chunks = 0, enc_groups = 0, dec_groups[2] = {0, 0};
@@ -206,7 +201,7 @@ int plan_ctx(const uint32_t *lat_w, const uint32_t *lat_h, uint32_t lat_c, const
         p->chunks += r.n_chunks;
         p->enc_groups += (ns + CTX_WPB - 1) / CTX_WPB;
         for (int s = 0; s < 2; s++) p->dec_groups[s] += (r.g.nst[s] + CTX_WPB_DEC - 1) / CTX_WPB_DEC;
-        if (p->streams >= RAGGED_MAX_ITEMS || p->chunks >= RAGGED_MAX_ITEMS) return SICN_EINVAL;
+        if (p->streams >= (uint64_t)sicn::RAGGED_MAX_ITEMS || p->chunks >= (uint64_t)sicn::RAGGED_MAX_ITEMS) return SICN_EINVAL;
         if (images) images[i] = sicn_ragged_ctx_image{r.lat_off, r.slot_off, r.ws_off, slot, n, r.g.nst[0], r.g.nst[1]};
         if (keep_rows) p->rows.push_back(r);
     }

@@ -11,8 +11,12 @@
 // in the band.  Its per-stream words (verdict, checksum sums) are indexed by st too, which is why the workspace is the full coder's.
 // k_ragged_dec_finish_window: one workgroup per image, dec_finish_window_body.
 //
-// Cut.  The pattern of k_ragged_crop (k_ragged.hip): a work item of CUT_ROWS destination rows, the image through two wave-uniform
-// loads.  The row's src_off leads to the rectangle's first byte (window_host.hpp), so a rectangle at any offset costs what a corner does.
+// Cut.  The one rectangle copy of the ragged family; the crop of sicn_ragged_hyper.h (k_ragged.hip) is this cut at the corner.  The
+// pattern of k_any_ragged: a work item of CUT_ROWS destination rows (the image's last item: the rest), the image through two
+// wave-uniform loads,
+//   item_image[item] : the image of an item
+//   rows[image]      : CutRow { source / destination row bytes, destination rows, first item, vec, 64-bit offsets in src and dst }
+// The row's src_off leads to the rectangle's first byte (window_host.hpp), so a rectangle at any offset costs what a corner does.
 #include <new>
 #include <vector>
 
@@ -23,18 +27,6 @@
 #include "window_host.hpp"
 
 namespace {
-
-__device__ __forceinline__ uint32_t uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
-__device__ __forceinline__ uint64_t uni(uint64_t v) { return (uint64_t)uni((uint32_t)v) | (uint64_t)uni((uint32_t)(v >> 32)) << 32; }
-
-// the image's row, every field wave-uniform
-__device__ __forceinline__ CoderRow load_row(const CoderRow *__restrict__ rows, uint32_t img)
-{
-    const CoderRow *r = rows + img;
-    return CoderRow{uni(r->lat_off), uni(r->slot_off), uni(r->ws_off), uni(r->n), uni(r->ns), uni(r->wss), uni(r->slot_cap),
-                    uni(r->lat_w), uni(r->lat_h), uni(r->lat_c), uni(r->img_w), uni(r->img_h), uni(r->first_stream),
-                    uni(r->first_row), uni(r->n_rows)};
-}
 
 struct WinRow {
     uint64_t lat_bias;                  // band_offset - first_stream * wss, modulo 2^64: added to the band tensor's address
@@ -224,54 +216,64 @@ struct sicn_ragged_cut {
     uint32_t *d_item_image = nullptr;       // [items]
 };
 
-extern "C" int sicn_ragged_cut_layout(const int32_t *src_w, const int32_t *src_h, const sicn_ragged_rect *rects, int channels,
-                                      const uint64_t *src_offset_or_null, int n_images, int image, int64_t out[4])
+namespace {
+
+struct CutTables {
+    std::vector<CutRow> rows;               // [n_images]
+    std::vector<int64_t> first_item;        // [n_images + 1]
+    std::vector<int64_t> image_off;         // [n_images]
+    int64_t totals[2] = {0, 0};
+};
+
+// cut_plan's first check in front of the arrays it fills, so that nothing is sized by an n_images it would refuse
+int cut_tables(const int32_t *src_w, const int32_t *src_h, const sicn_ragged_rect *rects, int channels, const uint64_t *src_offset_or_null,
+               int n_images, CutTables *t)
+{
+    if (!src_w || !src_h || !rects || n_images < 1 || channels < 1) return SICN_EINVAL;
+    try {
+        t->rows.resize((size_t)n_images);
+        t->first_item.resize((size_t)n_images + 1);
+        t->image_off.resize((size_t)n_images);
+    } catch (const std::bad_alloc &) { return SICN_ENOMEM; }
+    return sicn_window::cut_plan(src_w, src_h, rects, channels, src_offset_or_null, n_images, t->rows.data(), t->first_item.data(),
+                                 t->image_off.data(), t->totals);
+}
+
+}  // namespace
+
+int sicn::ragged_cut_layout(const int32_t *src_w, const int32_t *src_h, const sicn_ragged_rect *rects, int channels,
+                            const uint64_t *src_offset_or_null, int n_images, int image, int64_t out[4])
 {
     if (!out) return SICN_EINVAL;
-    int64_t totals[2];
-    if (int rc = sicn_window::cut_plan(src_w, src_h, rects, channels, src_offset_or_null, n_images, nullptr, nullptr, nullptr, totals)) return rc;
+    CutTables t;
+    if (int rc = cut_tables(src_w, src_h, rects, channels, src_offset_or_null, n_images, &t)) return rc;
     if (image < 0 || image >= n_images) return SICN_EINVAL;
-    try {
-        std::vector<CutRow> rows((size_t)n_images);
-        std::vector<int64_t> image_off((size_t)n_images);
-        (void)sicn_window::cut_plan(src_w, src_h, rects, channels, src_offset_or_null, n_images, rows.data(), nullptr, image_off.data(), totals);
-        out[0] = image_off[(size_t)image];
-        out[1] = rows[(size_t)image].dst_off;
-        out[2] = totals[0];
-        out[3] = totals[1];
-    } catch (const std::bad_alloc &) { return SICN_ENOMEM; }
+    out[0] = t.image_off[(size_t)image];
+    out[1] = t.rows[(size_t)image].dst_off;
+    out[2] = t.totals[0];
+    out[3] = t.totals[1];
     return SICN_OK;
 }
 
-extern "C" void sicn_ragged_cut_free(sicn_ragged_cut *cut)
-{
-    if (!cut) return;
-    if (cut->d_rows) (void)hipFree(cut->d_rows);
-    if (cut->d_item_image) (void)hipFree(cut->d_item_image);
-    delete cut;
-}
-
-extern "C" int sicn_ragged_cut_create(const int32_t *src_w, const int32_t *src_h, const sicn_ragged_rect *rects, int channels,
-                                      const uint64_t *src_offset_or_null, int n_images, sicn_ragged_cut **out)
+int sicn::ragged_cut_create(const int32_t *src_w, const int32_t *src_h, const sicn_ragged_rect *rects, int channels,
+                            const uint64_t *src_offset_or_null, int n_images, sicn_ragged_cut **out)
 {
     if (!out) return SICN_EINVAL;
     *out = nullptr;
-    if (int rc = sicn_window::cut_plan(src_w, src_h, rects, channels, src_offset_or_null, n_images, nullptr, nullptr, nullptr, nullptr)) return rc;
-    if (int rc = sicn::chip_geom(nullptr)) return rc;      // no device, or not a gfx950 one
+    CutTables t;
+    if (int rc = cut_tables(src_w, src_h, rects, channels, src_offset_or_null, n_images, &t)) return rc;
+    if (int rc = chip_geom(nullptr)) return rc;      // no device, or not a gfx950 one
     sicn_ragged_cut *cut = new (std::nothrow) sicn_ragged_cut();
     if (!cut) return SICN_ENOMEM;
     int rc = SICN_OK;
     try {
-        std::vector<CutRow> rows((size_t)n_images);
-        std::vector<int64_t> first_item((size_t)n_images + 1);
-        (void)sicn_window::cut_plan(src_w, src_h, rects, channels, src_offset_or_null, n_images, rows.data(), first_item.data(), nullptr, nullptr);
         cut->n_images = n_images;
-        cut->items = (unsigned)first_item[(size_t)n_images];
+        cut->items = (unsigned)t.first_item[(size_t)n_images];
         std::vector<uint32_t> map;
         map.reserve((size_t)cut->items);
-        for (int i = 0; i < n_images; i++) map.insert(map.end(), (size_t)(first_item[(size_t)i + 1] - first_item[(size_t)i]), (uint32_t)i);
-        if (!sicn::upload(rows.data(), rows.size() * sizeof(CutRow), &cut->d_rows) ||
-            !sicn::upload(map.data(), map.size() * sizeof(uint32_t), &cut->d_item_image))
+        for (int i = 0; i < n_images; i++) map.insert(map.end(), (size_t)(t.first_item[(size_t)i + 1] - t.first_item[(size_t)i]), (uint32_t)i);
+        if (!upload(t.rows.data(), t.rows.size() * sizeof(CutRow), &cut->d_rows) ||
+            !upload(map.data(), map.size() * sizeof(uint32_t), &cut->d_item_image))
             rc = SICN_ENOMEM;
     } catch (const std::bad_alloc &) { rc = SICN_ENOMEM; }
     if (rc) {
@@ -282,11 +284,36 @@ extern "C" int sicn_ragged_cut_create(const int32_t *src_w, const int32_t *src_h
     return SICN_OK;
 }
 
-extern "C" int sicn_ragged_cut_run(const sicn_ragged_cut *cut, const uint8_t *src, uint8_t *dst, void *hip_stream)
+int sicn::ragged_cut_run(const sicn_ragged_cut *cut, const uint8_t *src, uint8_t *dst, void *hip_stream)
 {
     if (!cut || !src || !dst) return SICN_EINVAL;
-    if (int rc = sicn::chip_geom(nullptr)) return rc;
+    if (int rc = chip_geom(nullptr)) return rc;
     const int ptr16 = ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0;
     hipLaunchKernelGGL(k_ragged_cut, dim3(cut->items), dim3(256), 0, (hipStream_t)hip_stream, src, dst, cut->d_rows, cut->d_item_image, ptr16);
     return hipGetLastError() == hipSuccess ? SICN_OK : SICN_ENODEV;
+}
+
+extern "C" int sicn_ragged_cut_layout(const int32_t *src_w, const int32_t *src_h, const sicn_ragged_rect *rects, int channels,
+                                      const uint64_t *src_offset_or_null, int n_images, int image, int64_t out[4])
+{
+    return sicn::ragged_cut_layout(src_w, src_h, rects, channels, src_offset_or_null, n_images, image, out);
+}
+
+extern "C" int sicn_ragged_cut_create(const int32_t *src_w, const int32_t *src_h, const sicn_ragged_rect *rects, int channels,
+                                      const uint64_t *src_offset_or_null, int n_images, sicn_ragged_cut **out)
+{
+    return sicn::ragged_cut_create(src_w, src_h, rects, channels, src_offset_or_null, n_images, out);
+}
+
+extern "C" void sicn_ragged_cut_free(sicn_ragged_cut *cut)
+{
+    if (!cut) return;
+    if (cut->d_rows) (void)hipFree(cut->d_rows);
+    if (cut->d_item_image) (void)hipFree(cut->d_item_image);
+    delete cut;
+}
+
+extern "C" int sicn_ragged_cut_run(const sicn_ragged_cut *cut, const uint8_t *src, uint8_t *dst, void *hip_stream)
+{
+    return sicn::ragged_cut_run(cut, src, dst, hip_stream);
 }

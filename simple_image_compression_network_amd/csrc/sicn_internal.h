@@ -30,6 +30,8 @@ inline LayerGeom geom_of(const sicn_layer_desc &d)
 }  // namespace sicn
 
 struct sicn_ragged_coder;   // k_ragged_codec.hip
+struct sicn_ragged_cut;     // k_ragged_window.hip
+struct sicn_ragged_rect;    // include/sicn_ragged_window.h
 
 // One layer's device-resident parameters, in every layout a kernel family wants.
 struct sicn_weights {
@@ -121,6 +123,14 @@ struct RaggedCoderView {
     uint64_t ws_bytes;
 };
 void ragged_coder_view(const sicn_ragged_coder *coder, RaggedCoderView *v);
+
+// k_ragged_window.hip: the one rectangle copy of the ragged family, behind sicn_ragged_cut_* (sicn_ragged_window.h) as they stand and
+// behind sicn_ragged_crop_* (sicn_ragged_hyper.h, k_ragged.hip) as the cut at the corner.  Arguments and codes: sicn_ragged_cut_*
+int ragged_cut_layout(const int32_t *src_w, const int32_t *src_h, const sicn_ragged_rect *rects, int channels,
+                      const uint64_t *src_offset_or_null, int n_images, int image, int64_t out[4]);
+int ragged_cut_create(const int32_t *src_w, const int32_t *src_h, const sicn_ragged_rect *rects, int channels,
+                      const uint64_t *src_offset_or_null, int n_images, sicn_ragged_cut **out);
+int ragged_cut_run(const sicn_ragged_cut *cut, const uint8_t *src, uint8_t *dst, void *hip_stream);
 
 size_t l0_bytes(int cout);
 void pack_l0(const int8_t *w_okc, int cout, int8_t *dst);

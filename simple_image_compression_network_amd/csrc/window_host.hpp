@@ -7,13 +7,13 @@
 
 #include "../../include/sicn.h"
 #include "../../include/sicn_ragged_window.h"
+#include "k_ragged_common.hpp"
 
 namespace sicn_window {
 
 constexpr int MAX_UP_LAYERS = 12;
 constexpr uint32_t SELF_SCAN_MAX = 2048;             // streams per image of the ragged coder (k_codec_body.hpp)
 constexpr int64_t MAX_IMAGE_BYTES = 0x80000000ll;    // one image's tensor stays below this (sicn_ragged_crop_layout)
-constexpr int64_t MAX_ITEMS = 0x7fffffffll;          // work items of one launch (grid.x)
 constexpr int CUT_ROWS = SICN_RAGGED_CROP_ROWS;
 
 constexpr uint64_t a16(uint64_t v) { return (v + 15) & ~(uint64_t)15; }
@@ -135,7 +135,7 @@ inline int cut_plan(const int32_t *src_w, const int32_t *src_h, const sicn_ragge
         if (first_item_or_null) first_item_or_null[i] = item;
         if (image_off_or_null) image_off_or_null[i] = so;
         item += (q.h + CUT_ROWS - 1) / CUT_ROWS;
-        if (item >= MAX_ITEMS) return SICN_EINVAL;
+        if (item >= sicn::RAGGED_MAX_ITEMS) return SICN_EINVAL;
         so += srow * src_h[i];
         if (so > reach) reach = so;
         dof += drow * q.h;

@@ -114,6 +114,69 @@ def test_crop_limits_are_einval_without_a_device():
     L.sicn_ragged_crop_free(None)
 
 
+def _cut_layout_at_the_corner(src, dst, channels, image, n_images=None):
+    """sicn_ragged_cut_layout of the rectangles (0, 0, dst_w, dst_h) without source offsets; src, dst: [(h, w)] per image."""
+    m = max(len(src), 1)
+    i32 = ctypes.c_int32 * m
+    sw, sh = i32(*[w for _, w in src]), i32(*[h for h, _ in src])
+    rects = (_lib.RaggedRect * m)(*[_lib.RaggedRect(0, 0, w, h) for h, w in dst])
+    out = (ctypes.c_int64 * 4)()
+    rc = _lib.lib().sicn_ragged_cut_layout(sw, sh, rects, channels, None, len(src) if n_images is None else n_images, image, out)
+    return rc, list(out)
+
+
+def test_crop_layout_is_the_cut_layout_at_the_corner():
+    """Destination heights of one row, exactly one work item and two; source rows of 16 c and of 5 c bytes (a multiple of 16 or
+    not, for c = 1 and 3); one image and three."""
+    r = _lib.RAGGED_CROP_ROWS
+    assert r == 8
+    for c in (1, 3, 192):
+        for sw, dw in ((16, 16), (32, 16), (5, 5), (7, 5)):
+            for dh in (1, r, r + 1):
+                one = ([(dh + 2, sw)], [(dh, dw)])
+                three = ([(dh, sw), (dh + 2, sw + 1), (r + 3, sw)], [(dh, dw), (dh, dw), (r + 1, dw)])
+                for src, dst in (one, three):
+                    total_src, total_dst = (sum(h * w * c for h, w in s) for s in (src, dst))
+                    for i in range(len(src)):
+                        crop, cut = _crop_layout(src, dst, c, i), _cut_layout_at_the_corner(src, dst, c, i)
+                        assert crop == cut and crop[0] == 0, (c, src, dst, i)
+                        assert crop[1][2:] == [total_src, total_dst]
+                        assert crop[1][:2] == [sum(h * w * c for h, w in src[:i]), sum(h * w * c for h, w in dst[:i])]
+    # what either refuses, both refuse
+    for src, dst, c, i, n in [([(4, 4)], [(4, 5)], 3, 0, None), ([(4, 4)], [(5, 4)], 3, 0, None), ([(4, 4)], [(4, 0)], 3, 0, None),
+                              ([(4, 4)], [(4, 4)], 0, 0, None), ([(4, 4)], [(4, 4)], 3, 0, 0), ([(4, 4)], [(4, 4)], 3, 1, None)]:
+        assert _crop_layout(src, dst, c, i, n)[0] == _cut_layout_at_the_corner(src, dst, c, i, n)[0] == EINVAL
+
+
+def test_every_refusal_of_crop_layout_is_einval():
+    """One case per check of the crop's plan, each with a valid neighbour image in front where the plan looks at every image."""
+    ok = [(4, 4)]
+    big = (1 << 20) + 1
+    assert _crop_layout(ok + [(8, 6)], ok + [(8, 5)], 3, 1)[0] == 0
+    assert _crop_layout(ok + [(8, 6)], ok + [(8, 7)], 3, 0)[0] == EINVAL            # dst wider than src
+    assert _crop_layout(ok + [(8, 6)], ok + [(9, 6)], 3, 0)[0] == EINVAL            # dst taller than src
+    assert _crop_layout(ok + [(8, 6)], ok + [(8, 0)], 3, 0)[0] == EINVAL            # dst_w = 0
+    assert _crop_layout(ok + [(8, 6)], ok + [(0, 6)], 3, 0)[0] == EINVAL            # dst_h = 0
+    assert _crop_layout(ok + [(1, 1 << 20)], ok + [(1, 1)], 1, 0)[0] == 0
+    assert _crop_layout(ok + [(1, big)], ok + [(1, 1)], 1, 0)[0] == EINVAL          # a side above 2^20
+    assert _crop_layout(ok + [(big, 1)], ok + [(1, 1)], 1, 0)[0] == EINVAL
+    assert _crop_layout(ok + [(1 << 15, 1 << 16)], ok + [(1, 1)], 1, 0)[0] == EINVAL            # an image of 2^31 bytes
+    assert _crop_layout(ok + [((1 << 15) - 1, 1 << 16)], ok + [(1, 1)], 1, 0)[0] == 0
+    assert _crop_layout(ok, ok, 0, 0)[0] == EINVAL                                  # channels = 0
+    assert _crop_layout(ok, ok, 3, 0, n_images=0)[0] == EINVAL                      # n_images = 0
+    assert _crop_layout(ok, ok, 3, 1)[0] == EINVAL and _crop_layout(ok, ok, 3, -1)[0] == EINVAL   # image index out of range
+    L = _lib.lib()
+    one, out = (ctypes.c_int32 * 1)(4), (ctypes.c_int64 * 4)()
+    assert L.sicn_ragged_crop_layout(one, one, one, one, 3, 1, 0, out) == 0
+    for null in range(4):                                                           # NULL arrays
+        arrays = [None if k == null else one for k in range(4)]
+        assert L.sicn_ragged_crop_layout(*arrays, 3, 1, 0, out) == EINVAL
+    assert L.sicn_ragged_crop_layout(one, one, one, one, 3, 1, 0, None) == EINVAL
+    handle = ctypes.c_void_p(1)
+    assert L.sicn_ragged_crop_create(one, one, None, one, 3, 1, ctypes.byref(handle)) == EINVAL and not handle.value
+    assert L.sicn_ragged_crop_create(one, one, one, one, 3, 1, None) == EINVAL
+
+
 def test_net_create_gdn_with_a_null_array_rejects_what_net_create_rejects():
     L = _lib.lib()
     descs = eight_layer_descs(768, 512)

@@ -225,6 +225,53 @@ def test_ragged_net_cropped_gives_the_images_sizes(api, param):
         assert tuple(v.shape) == (h, w, 3) and torch.equal(v, full[:h, :w])
 
 
+# (src (h, w), dst (h, w)): one byte; 9 rows = two work items, the second one row; 17 rows cut to 9, rows of 16 c and 8 c bytes
+CORNER = [((1, 1), (1, 1)), ((9, 5), (9, 4)), ((17, 16), (9, 8))]
+
+
+def _corner_case(api, shapes, c, seed, misalign=0):
+    """RaggedCrop, RaggedCut at x0 = y0 = 0 and the C entry points of the crop: one result, the slices of every image."""
+    L = api._lib.lib()
+    src_shapes, dst_shapes = [s for s, _ in shapes], [d for _, d in shapes]
+    rng = np.random.default_rng([182, seed])
+    srcs = [rng.integers(0, 256, (h, w, c), dtype=np.uint8) for h, w in src_shapes]
+    flat = np.concatenate([np.zeros(misalign, np.uint8)] + [a.reshape(-1) for a in srcs])
+    src = _dev(flat)[misalign:]
+    assert src.data_ptr() % 16 == misalign
+    crop = api.RaggedCrop(src_shapes, dst_shapes, c)
+    cut = api.RaggedCut(src_shapes, [(0, 0, w, h) for h, w in dst_shapes], c)
+    assert (crop.src_bytes, crop.dst_bytes) == (cut.src_bytes, cut.dst_bytes) == (src.numel(), sum(h * w * c for h, w in dst_shapes))
+    a, b = crop.run(src), cut.run(src)
+    n = len(shapes)
+    i32 = ctypes.c_int32 * n
+    handle = ctypes.c_void_p()
+    api._lib.check(L.sicn_ragged_crop_create(i32(*[w for _, w in src_shapes]), i32(*[h for h, _ in src_shapes]),
+                                             i32(*[w for _, w in dst_shapes]), i32(*[h for h, _ in dst_shapes]), c, n, ctypes.byref(handle)),
+                   "sicn_ragged_crop_create")
+    d = torch.full((crop.dst_bytes,), 0xA5, dtype=torch.uint8, device="cuda")
+    rc = L.sicn_ragged_crop_run(handle, ctypes.c_void_p(src.data_ptr()), ctypes.c_void_p(d.data_ptr()),
+                                ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+    torch.cuda.synchronize()
+    L.sicn_ragged_crop_free(handle)
+    assert rc == 0
+    assert torch.equal(a, b) and torch.equal(a, d)
+    for i, (x, v, (h, w)) in enumerate(zip(srcs, crop.views(a), dst_shapes)):
+        assert torch.equal(v.cpu(), torch.from_numpy(x)[:h, :w]), f"image {i}: {x.shape} -> {(h, w, c)}"
+    return src, a
+
+
+def test_crop_is_the_cut_at_the_corner(api):
+    """The three images as one batch at 3 channels — every row byte by byte: 24-byte rows in the third image, no offset a multiple
+    of 16 — and at 16 channels — every row as 16-byte vectors: offsets 0, 16 and 736.  (One batch has one channel count, so the
+    byte path and the vector path of the same three shapes are two batches.)  Then the crop that cuts nothing, a plain copy, and
+    the vector batch from a source one byte past a 16-byte boundary, which the kernel must copy byte by byte."""
+    _corner_case(api, CORNER, 3, 0)
+    _corner_case(api, CORNER, 16, 1)
+    src, dst = _corner_case(api, [((8, 16), (8, 16))], 1, 2)
+    assert torch.equal(src, dst)
+    _corner_case(api, CORNER, 16, 3, misalign=1)
+
+
 # ---- 4 - 6. the whole codec -----------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def coded(api, hyperprior):

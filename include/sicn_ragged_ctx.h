@@ -16,7 +16,7 @@
  * workspace_offset, laid out as the uniform coder's; the workspace must be 16-byte aligned.  Offsets are 64-bit: the tensors, the
  * slot buffer and the workspace may exceed 4 GiB.
  *
- * Kernels.  The stages of the uniform coder (csrc/k_ctx_body.hpp and the two step loops beside it) on FLAT grids over the work
+ * Kernels.  The stages of the uniform coder (csrc/k_ctx_body.hpp: functions of one image) on FLAT grids over the work
  * items of all images — chunks of dwords for the statistics, groups of streams for the coders, single streams for the compaction,
  * whole images for tables, parse, scan and verdict — each workgroup finding its image through tables the coder object uploads once.
  * An image has as many streams as its shape gives (no per-image limit, as in the uniform coder).

@@ -1,15 +1,11 @@
 // Container mode 4, "rANS-WC": the device code of the context coder, shared by the uniform batch kernels (sicn_codec_ctx.inc:
 // blockIdx.y = image, every image of one shape, pointers advancing by uniform strides) and the ragged ones (k_ragged_ctx.hip: flat
 // grids over the work items of n images of n shapes, each image found through a table).  Every stage is a __device__ function of ONE
-// image's pointers, its CtxGeom and the index of the work item INSIDE the image (a chunk of dwords, a group of streams).
-// The pointers pass through `at`, which names the three address spaces a stage touches — at.lat(p): the latent / scale tensors,
-// at.ws(p): the workspace, at.slot(p): the slot buffer — and turns a pointer into THIS image's.  The uniform kernels hand in image
-// 0's pointers and CtxStrided (+ blockIdx.y * stride, applied where a pointer is first used: their instructions are those of the
-// kernels that held this text before it moved here, profiles/ragged_ctx_resource_usage.txt); the ragged kernels resolve their image
-// before the call and hand in CtxResolved.  The format: oracle/sicn_hyper_oracle.c.
+// image (CtxImage: its geometry, latent, scale map, container slot and workspace block, already resolved to pointers) and of the index
+// of the work item INSIDE the image (a chunk of dwords, a group of streams).  Both kinds of kernel name an image by one CtxRow and
+// turn it into that context with ctx_image(); they differ only in where the row comes from (CtxBatch: computed; ragged: loaded) —
+// the shape k_codec_body.hpp gives mode 3.  The format: oracle/sicn_hyper_oracle.c.
 #pragma once
-#include <type_traits>
-
 #include "k_codec_body.hpp"
 
 namespace {
@@ -94,23 +90,89 @@ __host__ __device__ inline size_t ctx_carve(CtxWorkspace &w, void *base, uint32_
     off += (size_t)ns * scratch_per_stream;
     return off;
 }
-// `at` of a stage whose pointers are already this image's (k_ragged_ctx.hip)
-struct CtxResolved {
-    template <typename T> __device__ __forceinline__ T *lat(T *p) const { return p; }
-    template <typename T> __device__ __forceinline__ T *ws(T *p) const { return p; }
-    template <typename T> __device__ __forceinline__ T *slot(T *p) const { return p; }
-};
 inline size_t ctx_ws_bytes(uint32_t ns) { CtxWorkspace w; return align_up(ctx_carve(w, nullptr, ns, WCAP) + 64, 256); }
 // workgroups of the class-histogram stage that share one image of n symbols
 inline uint32_t ctx_hist_blocks(uint32_t n) { const uint32_t b = (n / 4 + 255u) / 256u; return b < 256u ? b : 256u; }
 
-// class histograms (+ range check of the scale map); one thread per dword of 4 channels.  Workgroup `bx` of the `nb` that share the image.
-template <class At>
-__device__ __forceinline__ void ctx_hist_body(const At &at, const uint8_t *lat_, const uint8_t *scale_, const CtxGeom &g, uint32_t *chist_,
-                                              uint32_t *meta_, uint32_t bx, uint32_t nb)
+// ---- one image as the kernels name it -------------------------------------------------------------------------------------
+// Geometry and 64-bit byte offsets into the latent / scale tensors, the slot buffer and the workspace; the workspace block of an image
+// is what ctx_carve() gives for its stream count.  The ragged coder keeps a table of these (k_ragged_ctx.hip).
+struct CtxRow {
+    uint64_t lat_off, slot_off, ws_off;
+    CtxGeom g;
+    uint32_t slot_cap;                 // min(slot bytes, 2^32 - 1): nothing of a slot is read beyond it
+    uint32_t img_w, img_h;
+    uint32_t first_chunk, n_chunks;    // ragged: the image's first work items in the flat grids; n_chunks: its statistics workgroups
+    uint32_t first_enc, first_dec[2], first_stream;
+};
+inline uint32_t ctx_slot_cap(uint64_t slot_bytes) { return (uint32_t)(slot_bytes < 0xFFFFFFFFull ? slot_bytes : 0xFFFFFFFFull); }
+// host: the fields of a row that follow from the image's shape (slot_cap: that of the smallest slot the ragged layout gives, a caller
+// with slots of its own overwrites it), and the shape limits of both families of entry points
+inline int ctx_row_shape(CtxRow &r, uint32_t lat_w, uint32_t lat_h, uint32_t lat_c, uint32_t img_w, uint32_t img_h)
 {
-    const uint8_t *lat = at.lat(lat_), *scale = at.lat(scale_);
-    uint32_t *chist = at.ws(chist_), *meta = at.ws(meta_);
+    const uint64_t positions = (uint64_t)lat_w * lat_h;
+    if (positions == 0 || lat_c == 0 || (lat_c & 3)) return SICN_EINVAL;
+    if (positions > MAX_RANS_SYMBOLS || positions * lat_c > MAX_RANS_SYMBOLS) return SICN_EINVAL;   // (the products cannot wrap)
+    r.g = ctx_geom(lat_w, lat_h, lat_c);
+    r.slot_cap = ctx_slot_cap(align_up(sicn_codec_ctx_max_bytes(lat_w, lat_h, lat_c), 16));
+    r.img_w = img_w; r.img_h = img_h;
+    r.n_chunks = ctx_hist_blocks((uint32_t)(positions * lat_c));
+    return SICN_OK;
+}
+// a row of a table in memory (the ragged kernels), every field wave-uniform
+__device__ __forceinline__ CtxRow load_row(const CtxRow *__restrict__ rows, uint32_t img)
+{
+    const CtxRow *r = rows + img;
+    return CtxRow{uni(r->lat_off), uni(r->slot_off), uni(r->ws_off),
+                  CtxGeom{uni(r->g.W), uni(r->g.H), uni(r->g.C), {uni(r->g.nsym[0]), uni(r->g.nsym[1])}, {uni(r->g.nst[0]), uni(r->g.nst[1])}},
+                  uni(r->slot_cap), uni(r->img_w), uni(r->img_h), uni(r->first_chunk), uni(r->n_chunks), uni(r->first_enc),
+                  {uni(r->first_dec[0]), uni(r->first_dec[1])}, uni(r->first_stream)};
+}
+// A uniform batch (sicn_codec_ctx.inc: blockIdx.y = image, every image of one shape) is image 0's row (offsets 0: the kernels get the
+// base pointers) and three byte strides.  Passed by value, so it lives in kernel-argument SGPRs.
+struct CtxBatch {
+    CtxRow row0;
+    uint64_t s_lat, s_slot, s_ws;
+};
+__device__ __forceinline__ CtxRow batch_row(const CtxBatch &b)
+{
+    CtxRow r = b.row0;
+    r.lat_off += blockIdx.y * b.s_lat; r.slot_off += blockIdx.y * b.s_slot; r.ws_off += blockIdx.y * b.s_ws;
+    return r;
+}
+
+// ---- one image as the stages see it ---------------------------------------------------------------------------------------
+// One type for both directions: the encoder reads `lat` and writes `slot`, the decoder the reverse, so both are writable here.
+struct CtxImage {
+    CtxGeom g;
+    uint8_t *lat;                  // [H][W][C] symbols
+    const uint8_t *scale;          // [H][W][C] the hyper-synthesis scale map
+    uint8_t *slot;                 // container slot: header, class tables, length table, payload
+    uint32_t slot_cap;
+    uint32_t img_w, img_h;
+    CtxWorkspace w;
+};
+__device__ __forceinline__ CtxImage ctx_image(const CtxRow &r, const uint8_t *latents, const uint8_t *scales, const uint8_t *containers,
+                                              uint8_t *workspace)
+{
+    CtxImage im;
+    im.g = r.g;
+    im.lat = const_cast<uint8_t *>(latents) + r.lat_off;
+    im.scale = scales + r.lat_off;
+    im.slot = const_cast<uint8_t *>(containers) + r.slot_off;
+    im.slot_cap = r.slot_cap;
+    im.img_w = r.img_w; im.img_h = r.img_h;
+    ctx_carve(im.w, workspace + r.ws_off, r.g.nst[0] + r.g.nst[1], WCAP);
+    return im;
+}
+
+// ---- stages ---------------------------------------------------------------------------------------------------------------
+// class histograms (+ range check of the scale map); one thread per dword of 4 channels.  Workgroup `bx` of the `nb` that share the image.
+__device__ __forceinline__ void ctx_hist_body(const CtxImage &im, uint32_t bx, uint32_t nb)
+{
+    const CtxGeom &g = im.g;
+    const uint8_t *lat = im.lat, *scale = im.scale;
+    uint32_t *chist = im.w.chist, *meta = im.w.meta;
     __shared__ uint32_t h[NCLS * 128];
     for (int i = threadIdx.x; i < NCLS * 128; i += 256) h[i] = 0;
     __syncthreads();
@@ -132,18 +194,16 @@ __device__ __forceinline__ void ctx_hist_body(const At &at, const uint8_t *lat_,
 
 // 16 waves, one per class: histogram -> 12-bit table (the walk of k_enc_header), container bytes, and the encoder's /
 // decoder's lookup images.  Wave 0 also writes the header.
-// encoder: table_in_ == nullptr, tables come from chist and go to out_; decoder: tables are READ from the container
-template <class At>
-__device__ __forceinline__ void ctx_tables_body(const At &at, const uint32_t *chist_, const unsigned long long *sums_, uint32_t *meta_,
-                                                uint32_t *tfc_, uint32_t *trcp_, uint8_t *tst_, uint8_t *out_, const CtxGeom &g,
-                                                uint32_t img_w, uint32_t img_h, const uint8_t *table_in_)
+// encoder (!dec): the tables come from the class histograms and go to the container; decoder: they are READ from the container
+__device__ __forceinline__ void ctx_tables_body(const CtxImage &im, bool dec)
 {
+    const CtxGeom &g = im.g;
     const int lane = threadIdx.x & 63, cls = threadIdx.x >> 6;
-    uint32_t *meta = at.ws(meta_), *tfc = at.ws(tfc_) + cls * 128, *trcp = at.ws(trcp_) + cls * 128;
-    uint8_t *tst = at.ws(tst_) + cls * 4096;
+    uint32_t *meta = im.w.meta, *tfc = im.w.tfc + cls * 128, *trcp = im.w.trcp + cls * 128;
+    uint8_t *tst = im.w.tst + cls * 4096;
     uint32_t f[2], err = 0;
-    if (table_in_) {
-        const uint8_t *t = at.slot(table_in_) + cls * 256 + 4 * lane;
+    if (dec) {
+        const uint8_t *t = im.slot + SICN_CODEC_HEADER_BYTES + cls * 256 + 4 * lane;
         const bool readable = (meta[0] & 0x100u) == 0;
         f[0] = readable ? (t[0] | ((uint32_t)t[1] << 8)) : 0u;
         f[1] = readable ? (t[2] | ((uint32_t)t[3] << 8)) : 0u;
@@ -152,7 +212,7 @@ __device__ __forceinline__ void ctx_tables_body(const At &at, const uint32_t *ch
         for (int d = 32; d > 0; d >>= 1) sum += __shfl_xor(sum, d);
         if (sum != 0 && sum != 4096) { err = 8; f[0] = f[1] = 0; }
     } else {
-        const uint32_t *hist = at.ws(chist_) + cls * 128;
+        const uint32_t *hist = im.w.chist + cls * 128;
         const uint32_t h0 = hist[2 * lane], h1 = hist[2 * lane + 1];
         uint32_t n = h0 + h1;
 #pragma unroll
@@ -182,7 +242,7 @@ __device__ __forceinline__ void ctx_tables_body(const At &at, const uint32_t *ch
             diff -= step;
         }
         if (diff != 0) { err = 2; f[0] = f[1] = 0; }
-        uint8_t *ft = at.slot(out_) + SICN_CODEC_HEADER_BYTES + cls * 256 + 4 * lane;
+        uint8_t *ft = im.slot + SICN_CODEC_HEADER_BYTES + cls * 256 + 4 * lane;
         ft[0] = (uint8_t)f[0]; ft[1] = (uint8_t)(f[0] >> 8); ft[2] = (uint8_t)f[1]; ft[3] = (uint8_t)(f[1] >> 8);
     }
     // exclusive prefix sums -> freq | cum << 16, reciprocals, bucket table
@@ -197,7 +257,7 @@ __device__ __forceinline__ void ctx_tables_body(const At &at, const uint32_t *ch
     tfc[2 * lane + 1] = f[1] | (c1 << 16);
     trcp[2 * lane] = ransw_rcp(f[0]);
     trcp[2 * lane + 1] = ransw_rcp(f[1]);
-    if (table_in_) {   // decoder only: slot -> symbol, 4096 slots per class.  Lane l fills slots 64 l .. 64 l + 63: a binary search for the
+    if (dec) {   // decoder only: slot -> symbol, 4096 slots per class.  Lane l fills slots 64 l .. 64 l + 63: a binary search for the
         // first one, then a walk along the cumulative table (filling "my symbol's range" instead left one lane with most of a
         // peaked table: 38 us per image set)
         __shared__ uint16_t cum[NCLS][130];
@@ -234,14 +294,14 @@ __device__ __forceinline__ void ctx_tables_body(const At &at, const uint32_t *ch
 #pragma unroll
     for (int d = 32; d > 0; d >>= 1) err |= (uint32_t)__shfl_xor((int)err, d);
     if (lane == 0 && err) atomicOr(&meta[0], err);
-    if (!table_in_ && threadIdx.x < 12) {   // header (dword 10 = payload bytes comes from the scan)
-        const unsigned long long *sums = at.ws(sums_);
+    if (!dec && threadIdx.x < 12) {   // header (dword 10 = payload bytes comes from the scan)
+        const unsigned long long *sums = im.w.sums;
         const uint32_t n = g.W * g.H * g.C;
         const uint32_t a = (uint32_t)((1 + sums[0]) % ADLER_MOD), b = (uint32_t)((n % ADLER_MOD + sums[1]) % ADLER_MOD);
-        const uint32_t words[12] = {0x4C434953u, 1u | (4u << 16), img_w, img_h, g.W, g.H, g.C, n, g.nst[0] + g.nst[1], WSS, 0u, (b << 16) | a};
+        const uint32_t words[12] = {0x4C434953u, 1u | (4u << 16), im.img_w, im.img_h, g.W, g.H, g.C, n, g.nst[0] + g.nst[1], WSS, 0u, (b << 16) | a};
         if (threadIdx.x != 10) {
             const uint32_t v = words[threadIdx.x];
-            uint8_t *p = at.slot(out_) + 4 * threadIdx.x;
+            uint8_t *p = im.slot + 4 * threadIdx.x;
             p[0] = (uint8_t)v; p[1] = (uint8_t)(v >> 8); p[2] = (uint8_t)(v >> 16); p[3] = (uint8_t)(v >> 24);
         }
     }
@@ -256,34 +316,15 @@ __device__ __forceinline__ uint32_t ctx_enc_verdict(const uint32_t *meta, const 
     return err;
 }
 
-// Round 4: FOUR streams (waves) per workgroup share one copy of the class tables.  A one-wave workgroup carried 16 + 8 KB of LDS
-// (12 + 8 in the decoder): six / eight waves per CU — 1.5 / 2 per SIMD — for step loops that are chains of dependent LDS
-// round trips.  Shared, the tables cost 4 / 3 KB per wave and twelve waves fit.  A ring is private to its wave and a wave's LDS
-// operations execute in order, so the flush / fill points (data-dependent, different in every wave) need no block barrier — only
-// the compiler has to keep the order (wave_lds_sync).
-constexpr uint32_t CTX_WPB = 4;
-// what k_ctx_encode_steps.inc / k_ctx_decode_steps.inc check of the names their including kernel must have declared
-template <class Name, class Want> constexpr bool ctx_names = std::is_same_v<std::remove_cv_t<std::remove_reference_t<Name>>, Want>;
-__device__ __forceinline__ void wave_lds_sync()
+// header of a mode-4 container against the caller's shape (the tables are checked by the tables stage), by one wave.  `valid`: a
+// sicn_codec_status array whose .bytes bound the slots (entry `img` is this image's), or nullptr = slot_cap.  Clears the image's
+// statistics block: the first stage of a decode.
+__device__ __forceinline__ void ctx_parse_body(const CtxImage &im, const uint32_t *valid_, uint32_t img)
 {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// one set per launch (anchors first): CTX_WPB_DEC streams of the set per workgroup.  The symbol of a slot comes from ONE table read
-// (16 classes x 4096 slots = 64 KB of LDS, shared by the workgroup's eight waves; round 3 read the first symbol of a 16-slot
-// bucket and walked the cumulative table from there — up to a dozen dependent LDS round trips per step on a flat class, with
-// six waves per CU to hide them behind).  The step loops themselves: k_ctx_encode_steps.inc, k_ctx_decode_steps.inc.
-constexpr uint32_t CTX_WPB_DEC = 8;
-
-// header of a mode-4 container `c` against the caller's shape (the tables are checked by the tables stage), by one wave.
-// `valid`: bytes of the slot that may be read.  Clears the image's statistics block: the first stage of a decode.
-template <class At>
-__device__ __forceinline__ void ctx_parse_body(const At &at, const uint8_t *containers_, uint32_t valid, uint32_t *meta_, const CtxGeom &g)
-{
-    const uint8_t *c = at.slot(containers_);
-    uint32_t *meta = at.ws(meta_);
+    const CtxGeom &g = im.g;
+    const uint8_t *c = im.slot;
+    uint32_t *meta = im.w.meta;
+    const uint32_t valid = valid_ ? min(valid_[2 * (size_t)img + 1], im.slot_cap) : im.slot_cap;   // sicn_codec_status.bytes
     const int lane = threadIdx.x;
     const uint32_t ns = g.nst[0] + g.nst[1], n = g.W * g.H * g.C;
     const size_t fixed = SICN_CODEC_HEADER_BYTES + CTX_TABLE_BYTES + 4 * (size_t)ns;
@@ -306,6 +347,186 @@ __device__ __forceinline__ void ctx_parse_body(const At &at, const uint8_t *cont
         meta[2] = rd32(44);
         meta[3] = 0;
     }
+}
+
+// Round 4: FOUR streams (waves) per workgroup share one copy of the class tables.  A one-wave workgroup carried 16 + 8 KB of LDS
+// (12 + 8 in the decoder): six / eight waves per CU — 1.5 / 2 per SIMD — for step loops that are chains of dependent LDS
+// round trips.  Shared, the tables cost 4 / 3 KB per wave and twelve waves fit.  A ring is private to its wave and a wave's LDS
+// operations execute in order, so the flush / fill points (data-dependent, different in every wave) need no block barrier — only
+// the compiler has to keep the order (wave_lds_sync).
+constexpr uint32_t CTX_WPB = 4;
+__device__ __forceinline__ void wave_lds_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// encoder: group `grp` of CTX_WPB streams of the image, anchors and non-anchors numbered through
+__device__ __forceinline__ void ctx_encode_body(const CtxImage &im, uint32_t grp)
+{
+    const CtxGeom &g = im.g;
+    const uint8_t *lat = im.lat, *scale = im.scale;
+    const uint32_t *tfc = im.w.tfc, *trcp = im.w.trcp;
+    uint8_t *scratch = im.w.scratch;
+    uint32_t *lens = im.w.lens;
+    __shared__ uint32_t fc[NCLS * 128], rcp[NCLS * 128];
+    __shared__ __attribute__((aligned(16))) uint16_t words_all[CTX_WPB][RING_WORDS];   // one ring per wave, see ransw_encode_body
+    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6, st = grp * CTX_WPB + wv;
+    for (uint32_t i = threadIdx.x; i < NCLS * 128; i += 64 * CTX_WPB) { fc[i] = tfc[i]; rcp[i] = trcp[i]; }
+    __syncthreads();
+    if (st >= g.nst[0] + g.nst[1]) return;   // (no block barrier below this line)
+    uint16_t *words = words_all[wv];
+    const int set = st >= g.nst[0];
+    const uint32_t q0 = set ? st - g.nst[0] : st;
+    const uint32_t begin = q0 * WSS, cnt = min(WSS, g.nsym[set] - begin), blocks = (cnt + 255) / 256;
+    uint16_t *dst = (uint16_t *)(scratch + (size_t)st * WCAP);
+    uint32_t pos = WCAP / 2, top = WCAP / 2, x = RANSW_L;
+    const unsigned long long below = (1ull << lane) - 1;
+    auto load = [&](uint32_t q, uint32_t &sym4, uint32_t &cls4) {   // C % 4 == 0: a lane's 4 symbols are 4 channels of one pixel
+        const uint32_t j = q * 256 + lane * 4;
+        sym4 = cls4 = 0;
+        if (j >= cnt) return;
+        const uint32_t e = begin + j, px = e / g.C, ch = e - px * g.C;
+        uint32_t y, xx;
+        ctx_pixel(set, px, g.W, y, xx);
+        const uint32_t off = (y * g.W + xx) * g.C + ch;
+        sym4 = *reinterpret_cast<const uint32_t *>(lat + off);
+        cls4 = ctx_class4(set, lat, scale, g.W, g.H, g.C, y, xx, off);
+    };
+    uint32_t nsym = 0, ncls = 0;
+    if (blocks) load(blocks - 1, nsym, ncls);
+    for (uint32_t q = blocks; q-- > 0;) {
+        const uint32_t sym4 = nsym, cls4 = ncls;
+        if (q) load(q - 1, nsym, ncls);
+#pragma unroll
+        for (int k = 3; k >= 0; k--) {
+            const bool active0 = q * 256 + lane * 4 + k < cnt;
+            const uint32_t idx = ((cls4 >> (8 * k)) & 15u) * 128 + ((sym4 >> (8 * k)) & 127u);
+            const uint32_t t = fc[idx], c = t >> 16;
+            uint32_t f = t & 0xFFFFu;
+            const bool active = active0 && f != 0;      // f == 0 only for input the statistics stage rejected
+            f = active ? f : 1u;
+            const bool emit = active && (unsigned long long)x >= ((unsigned long long)f << 20);
+            const unsigned long long mask = __ballot(emit);
+            pos -= (uint32_t)__popcll(mask);
+            if (emit) {
+                words[(pos + (uint32_t)__popcll(mask & below)) & (RING_WORDS - 1)] = (uint16_t)x;
+                x >>= 16;
+            }
+            if (active) {
+                uint32_t r;
+                const uint32_t qq = ransw_div(x, f, rcp[idx], r);
+                x = (qq << PROB_BITS) + r + c;
+            }
+        }
+        if (top - pos > RING_WORDS - 4 * 64 - 128) {
+            wave_lds_sync();
+            ring_flush(words, dst, pos, top, lane);
+            wave_lds_sync();
+            top = pos;
+        }
+    }
+    pos -= 128;
+    words[(pos + 2 * lane) & (RING_WORDS - 1)] = (uint16_t)x;
+    words[(pos + 2 * lane + 1) & (RING_WORDS - 1)] = (uint16_t)(x >> 16);
+    wave_lds_sync();
+    ring_flush(words, dst, pos, top, lane);
+    if (lane == 0) lens[st] = (WCAP / 2 - pos) * 2;
+}
+
+// decoder, one set per launch (anchors first): group `grp` of CTX_WPB_DEC streams of set SET of the image.  The symbol of a slot
+// comes from ONE table read (16 classes x 4096 slots = 64 KB of LDS, shared by the workgroup's eight waves; round 3 read the first
+// symbol of a 16-slot bucket and walked the cumulative table from there — up to a dozen dependent LDS round trips per step on a
+// flat class, with six waves per CU to hide them behind).  SET is a template parameter so that the geometry's per-set fields are
+// picked at compile time: indexed by a kernel argument, the row went to scratch memory (profiles/ragged_ctx_resource_usage.txt).
+constexpr uint32_t CTX_WPB_DEC = 8;
+template <int SET>
+__device__ __forceinline__ void ctx_decode_body(const CtxImage &im, uint32_t grp)
+{
+    constexpr int set = SET;
+    const CtxGeom &g = im.g;
+    const uint8_t *payload = im.slot + SICN_CODEC_HEADER_BYTES + CTX_TABLE_BYTES + 4 * (size_t)(g.nst[0] + g.nst[1]);
+    const uint8_t *scale = im.scale, *tst = im.w.tst;
+    const uint32_t *offsets = im.w.offsets, *tfc = im.w.tfc;
+    uint8_t *lat = im.lat;
+    uint32_t *meta = im.w.meta;
+    __shared__ uint32_t fc[NCLS * 128];
+    __shared__ __attribute__((aligned(16))) uint8_t stb[NCLS * 4096];
+    __shared__ __attribute__((aligned(16))) uint16_t words_all[CTX_WPB_DEC][RING_WORDS];   // one ring per wave, see ransw_decode_body
+    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6, sidx = grp * CTX_WPB_DEC + wv, st = sidx + (set ? g.nst[0] : 0);
+    {
+        const uint4 *b = reinterpret_cast<const uint4 *>(tst);   // the workspace block is 16-byte aligned (ctx_carve)
+        for (uint32_t i = threadIdx.x; i < NCLS * 128; i += 64 * CTX_WPB_DEC) fc[i] = tfc[i];
+        for (uint32_t i = threadIdx.x; i < NCLS * 256; i += 64 * CTX_WPB_DEC) reinterpret_cast<uint4 *>(stb)[i] = b[i];
+    }
+    __syncthreads();
+    if (sidx >= g.nst[set]) return;   // (no block barrier below this line)
+    uint16_t *words = words_all[wv];
+    const uint32_t begin = sidx * WSS, cnt = min(WSS, g.nsym[set] - begin), blocks = (cnt + 255) / 256;
+    const uint32_t off = offsets[st], len = offsets[st + 1] - off, payload_bytes = meta[1];
+    if (len < 256 || (len & 1) || (off & 1) || len > WCAP || (unsigned long long)off + len > payload_bytes) {
+        if (lane == 0) atomicOr(&meta[3], 1u);
+        return;
+    }
+    const uint32_t nwords = len / 2;
+    const uint16_t *src = (const uint16_t *)(payload + off);
+    uint32_t loaded = ring_fill(words, src, 0, min(nwords, RING_WORDS), lane);
+    wave_lds_sync();
+    uint32_t x = words[2 * lane] | ((uint32_t)words[2 * lane + 1] << 16), wpos = 128;
+    const unsigned long long below = (1ull << lane) - 1;
+    bool bad = false;
+    // the classes of a block come from global memory (the scale map and, for the non-anchors, the four anchor neighbours the
+    // previous launch decoded): requested ONE BLOCK AHEAD.  Round 3 fetched them at the top of the block they were needed in —
+    // with ~6 streams per CU in flight (a set of a 4K latent has 190 streams) that latency, 64 times per stream, was half of
+    // the kernel.
+    auto locate = [&](uint32_t q, uint32_t &o, uint32_t &cls4) -> bool {
+        const uint32_t j = q * 256 + lane * 4;
+        o = cls4 = 0;
+        if (j >= cnt) return false;      // cnt is a multiple of 4
+        const uint32_t e = begin + j, px = e / g.C, ch = e - px * g.C;
+        uint32_t y, xx;
+        ctx_pixel(set, px, g.W, y, xx);
+        o = (y * g.W + xx) * g.C + ch;
+        cls4 = ctx_class4(set, lat, scale, g.W, g.H, g.C, y, xx, o);
+        return true;
+    };
+    uint32_t o_next = 0, cls_next = 0;
+    bool mine_next = blocks ? locate(0, o_next, cls_next) : false;
+    for (uint32_t q = 0; q < blocks; q++) {
+        if (loaded < nwords && loaded - min(wpos, loaded) < 4 * 64) {
+            wave_lds_sync();
+            loaded = ring_fill(words, src, loaded, min(nwords, wpos + RING_WORDS), lane);
+            wave_lds_sync();
+        }
+        const bool mine = mine_next;
+        const uint32_t cls4 = cls_next, o = o_next;
+        mine_next = q + 1 < blocks ? locate(q + 1, o_next, cls_next) : false;
+        uint32_t out4 = 0;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            if (mine) {
+                const uint32_t base = ((cls4 >> (8 * k)) & 15u) * 128, v = x & 4095u;
+                const uint32_t sy = stb[(base << 5) + v] & 127u;   // (a slot no symbol covers holds anything: caught by the range test)
+                const uint32_t t = fc[base + sy], f = t & 0xFFFFu;
+                bad |= f == 0 || v < (t >> 16) || v >= (t >> 16) + f;   // a class without a table, or a hole in it
+                out4 |= sy << (8 * k);
+                x = f * (x >> PROB_BITS) + v - (t >> 16);
+            }
+            const bool need = mine && x < RANSW_L;
+            const unsigned long long mask = __ballot(need);
+            if (need) {
+                const uint32_t idx = wpos + (uint32_t)__popcll(mask & below);
+                if (idx < loaded)
+                    x = (x << 16) | words[idx & (RING_WORDS - 1)];
+                else
+                    bad = true;
+            }
+            wpos += (uint32_t)__popcll(mask);
+        }
+        if (mine) *reinterpret_cast<uint32_t *>(lat + o) = out4;
+    }
+    if (bad || x != RANSW_L || wpos != nwords) atomicOr(&meta[3], 1u);
 }
 
 }  // namespace

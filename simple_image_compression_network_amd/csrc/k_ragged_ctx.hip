@@ -1,6 +1,6 @@
 // Ragged context coder (include/sicn_ragged_ctx.h): the rANS-WC stages of k_ctx_body.hpp over n latents of n different shapes, six
-// launches per encode and eight per decode for the whole batch.  The stages are the uniform coder's (sicn_codec_ctx.inc); what is
-// new is how a workgroup finds its image.
+// launches per encode and eight per decode for the whole batch.  The stages, CtxRow and ctx_image() are the uniform coder's
+// (sicn_codec_ctx.inc); what differs is where a workgroup's row comes from: loaded from a table here, computed from blockIdx.y there.
 //
 // Grids: flat over work items.
 //   statistics          chunks of an image's dwords, ctx_hist_blocks(n_i) per image (the uniform coder's rule); one workgroup takes the
@@ -13,8 +13,8 @@
 //   chunk_image[], enc_image[], dec_image[2][], stream_image[] : the image a work item belongs to — ONE load resolves item -> image
 //   rows[image]                                                : CtxRow, the image's geometry, its first work items and its 64-bit
 //                                                                byte offsets in the latent / scale tensors, the slot buffer and the workspace
-// Both loads are wave-uniform (they depend on blockIdx.x only) and stay in scalar registers.  The workspace block of an image is
-// what ctx_carve() gives for its stream count, the same function the uniform coder calls on the host.
+// Both loads are wave-uniform (they depend on blockIdx.x only) and stay in scalar registers.  Every kernel below: load the row of
+// its image (load_row), resolve it (ctx_image), call the stage with the index inside the image.
 #include <new>
 #include <vector>
 
@@ -25,37 +25,11 @@
 
 namespace {
 
-struct CtxRow {
-    uint64_t lat_off, slot_off, ws_off;
-    CtxGeom g;
-    uint32_t slot_cap;                 // min(slot bytes, 2^32 - 1), as the uniform parse stage bounds a slot
-    uint32_t img_w, img_h;
-    uint32_t first_chunk, n_chunks;    // the image's first work items in the flat grids
-    uint32_t first_enc, first_dec[2], first_stream;
-};
-
-// the image's row, every field wave-uniform
-__device__ __forceinline__ CtxRow load_row(const CtxRow *__restrict__ rows, uint32_t img)
-{
-    const CtxRow *r = rows + img;
-    return CtxRow{uni(r->lat_off), uni(r->slot_off), uni(r->ws_off),
-                  CtxGeom{uni(r->g.W), uni(r->g.H), uni(r->g.C), {uni(r->g.nsym[0]), uni(r->g.nsym[1])}, {uni(r->g.nst[0]), uni(r->g.nst[1])}},
-                  uni(r->slot_cap), uni(r->img_w), uni(r->img_h), uni(r->first_chunk), uni(r->n_chunks), uni(r->first_enc),
-                  {uni(r->first_dec[0]), uni(r->first_dec[1])}, uni(r->first_stream)};
-}
-__device__ __forceinline__ CtxWorkspace row_workspace(const CtxRow &r, uint8_t *workspace)
-{
-    CtxWorkspace w;
-    ctx_carve(w, workspace + r.ws_off, r.g.nst[0] + r.g.nst[1], WCAP);
-    return w;
-}
-
 // encoder, first on the stream: the statistics block and the class histograms of every image, which the next stage adds to
 __global__ __launch_bounds__(256) void k_ragged_ctx_clear(uint8_t *__restrict__ workspace, const CtxRow *__restrict__ rows)
 {
-    const CtxRow r = load_row(rows, blockIdx.x);
-    const CtxWorkspace w = row_workspace(r, workspace);
-    for (uint32_t i = threadIdx.x; i < STATS_WORDS + 16 + NCLS * 128; i += 256) w.hist[i] = 0;   // hist .. meta, then chist: contiguous
+    const CtxImage im = ctx_image(load_row(rows, blockIdx.x), nullptr, nullptr, nullptr, workspace);
+    for (uint32_t i = threadIdx.x; i < STATS_WORDS + 16 + NCLS * 128; i += 256) im.w.hist[i] = 0;   // hist .. meta, then chist: contiguous
 }
 
 // CLASSES: the encoder's statistics (byte histogram, checksum sums, class histograms); else the decoder's (checksum sums of what it decoded)
@@ -65,30 +39,24 @@ __global__ __launch_bounds__(256) void k_ragged_ctx_stats(const uint8_t *__restr
                                                           const uint32_t *__restrict__ chunk_image)
 {
     const CtxRow r = load_row(rows, uni(chunk_image[blockIdx.x]));
-    const CtxWorkspace w = row_workspace(r, workspace);
+    const CtxImage im = ctx_image(r, latents, scales, nullptr, workspace);
     const uint32_t local = blockIdx.x - r.first_chunk;
-    stats_body(latents + r.lat_off, r.g.W * r.g.H * r.g.C, w.hist, w.sums, nullptr, local, r.n_chunks);
-    if constexpr (CLASSES) ctx_hist_body(CtxResolved{}, latents + r.lat_off, scales + r.lat_off, r.g, w.chist, w.meta, local, r.n_chunks);
+    stats_body(im.lat, r.g.W * r.g.H * r.g.C, im.w.hist, im.w.sums, nullptr, local, r.n_chunks);
+    if constexpr (CLASSES) ctx_hist_body(im, local, r.n_chunks);
 }
 
+// valid: a sicn_codec_status array or nullptr
 __global__ __launch_bounds__(64) void k_ragged_ctx_parse(const uint8_t *__restrict__ containers, const uint32_t *__restrict__ valid,
                                                          uint8_t *__restrict__ workspace, const CtxRow *__restrict__ rows)
 {
-    const CtxRow r = load_row(rows, blockIdx.x);
-    const CtxWorkspace w = row_workspace(r, workspace);
-    const uint32_t bytes = valid ? min(valid[2 * (size_t)blockIdx.x + 1], r.slot_cap) : r.slot_cap;   // sicn_codec_status.bytes
-    ctx_parse_body(CtxResolved{}, containers + r.slot_off, bytes, w.meta, r.g);
+    ctx_parse_body(ctx_image(load_row(rows, blockIdx.x), nullptr, nullptr, containers, workspace), valid, blockIdx.x);
 }
 
 // dec: the tables are read from the containers (and checked); else made from the class histograms and written to them, with the header
 __global__ __launch_bounds__(1024) void k_ragged_ctx_tables(uint8_t *__restrict__ containers, uint8_t *__restrict__ workspace,
                                                             const CtxRow *__restrict__ rows, int dec)
 {
-    const CtxRow r = load_row(rows, blockIdx.x);
-    const CtxWorkspace w = row_workspace(r, workspace);
-    uint8_t *c = containers + r.slot_off;
-    ctx_tables_body(CtxResolved{}, w.chist, w.sums, w.meta, w.tfc, w.trcp, w.tst, c, r.g, r.img_w, r.img_h,
-                    dec ? c + SICN_CODEC_HEADER_BYTES : (const uint8_t *)nullptr);
+    ctx_tables_body(ctx_image(load_row(rows, blockIdx.x), nullptr, nullptr, containers, workspace), dec);
 }
 
 __global__ __launch_bounds__(64 * CTX_WPB) void k_ragged_ctx_encode(const uint8_t *__restrict__ latents, const uint8_t *__restrict__ scales,
@@ -96,14 +64,7 @@ __global__ __launch_bounds__(64 * CTX_WPB) void k_ragged_ctx_encode(const uint8_
                                                                     const uint32_t *__restrict__ enc_image)
 {
     const CtxRow r = load_row(rows, uni(enc_image[blockIdx.x]));
-    const CtxWorkspace w = row_workspace(r, workspace);
-    const CtxGeom &g = r.g;
-    const uint8_t *lat = latents + r.lat_off, *scale = scales + r.lat_off;
-    uint8_t *scratch = w.scratch;
-    uint32_t *lens = w.lens;
-    const uint32_t *tfc = w.tfc, *trcp = w.trcp;
-    const uint32_t grp = blockIdx.x - r.first_enc;
-#include "k_ctx_encode_steps.inc"
+    ctx_encode_body(ctx_image(r, latents, scales, nullptr, workspace), blockIdx.x - r.first_enc);
 }
 
 // One workgroup per image.  Encoder: stream lengths -> offsets, the container's length table and payload-bytes field, and the image's
@@ -111,16 +72,16 @@ __global__ __launch_bounds__(64 * CTX_WPB) void k_ragged_ctx_encode(const uint8_
 __global__ __launch_bounds__(1024) void k_ragged_ctx_scan(uint8_t *__restrict__ containers, uint32_t *__restrict__ status,
                                                           uint8_t *__restrict__ workspace, const CtxRow *__restrict__ rows, int dec)
 {
-    const CtxRow r = load_row(rows, blockIdx.x);
-    const CtxWorkspace w = row_workspace(r, workspace);
-    const uint32_t ns = r.g.nst[0] + r.g.nst[1];
-    uint8_t *c = containers + r.slot_off, *table = c + SICN_CODEC_HEADER_BYTES + CTX_TABLE_BYTES;
+    const CtxImage im = ctx_image(load_row(rows, blockIdx.x), nullptr, nullptr, containers, workspace);
+    const CtxWorkspace &w = im.w;
+    const uint32_t ns = im.g.nst[0] + im.g.nst[1];
+    uint8_t *table = im.slot + SICN_CODEC_HEADER_BYTES + CTX_TABLE_BYTES;
     if (dec) {
         scan_body(nullptr, table, ns, w.offsets, nullptr, nullptr, WCAP, w.meta + 3, nullptr, 0u, (w.meta[0] & 0x100u) != 0);
         return;
     }
     if (threadIdx.x == 0) status[2 * (size_t)blockIdx.x] = ctx_enc_verdict(w.meta, w.hist);
-    scan_body(w.lens, nullptr, ns, w.offsets, table, c + 40, 0xFFFFFFFFu, nullptr, status + 2 * (size_t)blockIdx.x + 1,
+    scan_body(w.lens, nullptr, ns, w.offsets, table, im.slot + 40, 0xFFFFFFFFu, nullptr, status + 2 * (size_t)blockIdx.x + 1,
               (uint32_t)(SICN_CODEC_HEADER_BYTES + CTX_TABLE_BYTES) + 4 * ns, false);
 }
 
@@ -128,39 +89,28 @@ __global__ __launch_bounds__(256) void k_ragged_ctx_compact(uint8_t *__restrict_
                                                             const CtxRow *__restrict__ rows, const uint32_t *__restrict__ stream_image)
 {
     const CtxRow r = load_row(rows, uni(stream_image[blockIdx.x]));
-    const CtxWorkspace w = row_workspace(r, workspace);
+    const CtxImage im = ctx_image(r, nullptr, nullptr, containers, workspace);
     const uint32_t ns = r.g.nst[0] + r.g.nst[1];
-    compact_body(w.scratch, w.lens, w.offsets, containers + r.slot_off + SICN_CODEC_HEADER_BYTES + CTX_TABLE_BYTES + 4 * (size_t)ns, WCAP,
+    compact_body(im.w.scratch, im.w.lens, im.w.offsets, im.slot + SICN_CODEC_HEADER_BYTES + CTX_TABLE_BYTES + 4 * (size_t)ns, WCAP,
                  blockIdx.x - r.first_stream);
 }
 
-// one set per launch (anchors first): dec_image is the table of that set.  SET is a template parameter so that the row's per-set
-// fields are picked at compile time (indexed by a kernel argument, the row went to scratch memory)
+// one set per launch (anchors first): dec_image is the table of that set
 template <int SET>
 __global__ __launch_bounds__(64 * CTX_WPB_DEC) void k_ragged_ctx_decode(const uint8_t *__restrict__ containers, const uint8_t *__restrict__ scales,
                                                                         uint8_t *__restrict__ latents, uint8_t *__restrict__ workspace,
                                                                         const CtxRow *__restrict__ rows, const uint32_t *__restrict__ dec_image)
 {
-    constexpr int set = SET;
     const CtxRow r = load_row(rows, uni(dec_image[blockIdx.x]));
-    const CtxWorkspace w = row_workspace(r, workspace);
-    const CtxGeom &g = r.g;
-    const uint8_t *payload = containers + r.slot_off + SICN_CODEC_HEADER_BYTES + CTX_TABLE_BYTES + 4 * (size_t)(g.nst[0] + g.nst[1]);
-    const uint8_t *scale = scales + r.lat_off, *tst = w.tst;
-    const uint32_t *offsets = w.offsets, *tfc = w.tfc;
-    uint8_t *lat = latents + r.lat_off;
-    uint32_t *meta = w.meta;
-    const uint32_t grp = blockIdx.x - r.first_dec[set];
-#include "k_ctx_decode_steps.inc"
+    ctx_decode_body<SET>(ctx_image(r, latents, scales, containers, workspace), blockIdx.x - r.first_dec[SET]);
 }
 
 __global__ __launch_bounds__(64) void k_ragged_ctx_finish(uint32_t *__restrict__ status, uint8_t *__restrict__ workspace,
                                                           const CtxRow *__restrict__ rows)
 {
     if (threadIdx.x) return;
-    const CtxRow r = load_row(rows, blockIdx.x);
-    const CtxWorkspace w = row_workspace(r, workspace);
-    dec_finish_body(w.meta, w.sums, w.offsets, status + 2 * (size_t)blockIdx.x, r.g.W * r.g.H * r.g.C, r.g.nst[0] + r.g.nst[1]);
+    const CtxImage im = ctx_image(load_row(rows, blockIdx.x), nullptr, nullptr, nullptr, workspace);
+    dec_finish_body(im.w.meta, im.w.sums, im.w.offsets, status + 2 * (size_t)blockIdx.x, im.g.W * im.g.H * im.g.C, im.g.nst[0] + im.g.nst[1]);
 }
 
 // ---- the layout: pure host --------------------------------------------------------------------------------------------------
@@ -173,23 +123,17 @@ struct Plan {
 int plan_ctx(const uint32_t *lat_w, const uint32_t *lat_h, uint32_t lat_c, const uint32_t *img_w, const uint32_t *img_h, int n_images,
              bool keep_rows, sicn_ragged_ctx_image *images, Plan *p)
 {
-    if (!lat_w || !lat_h || n_images < 1 || lat_c < 1 || (lat_c & 3)) return SICN_EINVAL;
+    if (!lat_w || !lat_h || n_images < 1) return SICN_EINVAL;
     if (keep_rows) p->rows.reserve((size_t)n_images);
     for (int i = 0; i < n_images; i++) {
-        if (lat_w[i] < 1 || lat_h[i] < 1) return SICN_EINVAL;
-        const uint64_t positions = (uint64_t)lat_w[i] * lat_h[i];
-        if (positions > MAX_RANS_SYMBOLS || positions * lat_c > MAX_RANS_SYMBOLS) return SICN_EINVAL;   // (the products cannot wrap)
         CtxRow r{};
-        r.g = ctx_geom(lat_w[i], lat_h[i], lat_c);
-        const uint32_t n = (uint32_t)(positions * lat_c), ns = r.g.nst[0] + r.g.nst[1];
-        const uint64_t slot = align_up(sicn_codec_ctx_max_bytes(lat_w[i], lat_h[i], lat_c), 16);
+        if (int rc = ctx_row_shape(r, lat_w[i], lat_h[i], lat_c, img_w ? img_w[i] : 0, img_h ? img_h[i] : 0)) return rc;
+        const uint32_t n = r.g.W * r.g.H * r.g.C, ns = r.g.nst[0] + r.g.nst[1];
+        const uint64_t slot = align_up(sicn_codec_ctx_max_bytes(lat_w[i], lat_h[i], lat_c), 16);   // (r.slot_cap is this, saturated)
         r.lat_off = p->lat_bytes;
         r.slot_off = p->slot_bytes;
         r.ws_off = p->ws_bytes;
-        r.slot_cap = (uint32_t)(slot < 0xFFFFFFFFull ? slot : 0xFFFFFFFFull);
-        r.img_w = img_w ? img_w[i] : 0; r.img_h = img_h ? img_h[i] : 0;
         r.first_chunk = (uint32_t)p->chunks;
-        r.n_chunks = ctx_hist_blocks(n);
         r.first_enc = (uint32_t)p->enc_groups;
         r.first_dec[0] = (uint32_t)p->dec_groups[0];
         r.first_dec[1] = (uint32_t)p->dec_groups[1];

@@ -43,9 +43,9 @@ namespace {
 static inline unsigned stats_blocks(uint32_t n) { return std::min((n / 16 + 255u) / 256u + 1u, 128u); }
 
 // ---- kernels ----------------------------------------------------------------------------------
-// Batches: blockIdx.y = image.  The rANS-W kernels name their image by a UniformBatch (k_codec_body.hpp); k_scan, k_compact,
-// k_clear_stats, the header / parse / finish kernels of the scan form, mode 2 and the context coder take pointers into the latent
-// tensor / the per-image workspace / the container slots that advance by the given byte strides.
+// Batches: blockIdx.y = image.  The rANS-W kernels name their image by a UniformBatch (k_codec_body.hpp), the context coder's by a
+// CtxBatch (k_ctx_body.hpp); k_scan, k_compact, k_clear_stats, the header / parse / finish kernels of the scan form and mode 2 take
+// pointers into the latent tensor / the per-image workspace / the container slots that advance by the given byte strides.
 template <typename T>
 __device__ __forceinline__ T *img_ptr(T *p, size_t stride)
 {

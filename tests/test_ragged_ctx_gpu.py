@@ -314,6 +314,84 @@ def test_argument_checks_return_without_launching(codec):
     call.close()
 
 
+# ---- both forms build their image from the same row: n equal shapes through the ragged coder and through the uniform entry points ----
+SHARED = {"3x(37,37,192)": (3, (37, 37, 192)),     # 9 + 9 streams per image
+          "3x(1,1,4)": (3, (1, 1, 4)),             # no non-anchor set: the uniform decoder launches one set only
+          "2x(1,8193,4)": (2, (1, 8193, 4))}       # two anchor streams per image, the second of 4 symbols
+HEADER_BYTES, TABLE_BYTES = 48, 16 * 256           # include/sicn_codec.h; csrc/k_ctx_body.hpp
+
+
+@pytest.mark.parametrize("name", SHARED)
+def test_ragged_and_uniform_forms_on_the_same_buffers(codec, name):
+    """One latent tensor, one scale tensor, one slot buffer (slot stride = the ragged layout's) and one workspace serve a ragged
+    coder of n equal shapes and sicn_codec_ctx_*_batch_async: equal containers and status words, each decoder on the other's
+    containers in place, and the same verdict on an image whose valid bytes end inside its fixed part."""
+    n, (h, w, c) = SHARED[name]
+    rng = np.random.default_rng([n, h, w, c])
+    ys, ss = zip(*[ce.CTX_CONTENTS[k]((h, w, c), rng) for k in ("uniform-uniform", "tie-up", "checkerboard")[:n]])
+    call = _Call([(h, w)] * n, c)
+    im, n_sym = call.images, h * w * c
+    slot, ws1 = int(im[0].slot_bytes), call.ws_bytes // n
+    assert [(int(x.latent_offset), int(x.slot_offset), int(x.workspace_offset), int(x.slot_bytes)) for x in im] == \
+           [(i * n_sym, i * slot, i * ws1, slot) for i in range(n)]                  # a uniform batch with these three strides
+    assert ws1 * n == int(call.L.sicn_codec_ctx_workspace_bytes(w, h, c, n))
+    call.inner("lat").copy_(_pack(ys))
+    call.inner("scale").copy_(_pack(ss))
+    status = {k: torch.full((n, 2), -1, dtype=torch.int32, device="cuda") for k in ("enc_r", "enc_u", "dec_r", "dec_u")}
+    sp = {k: ctypes.c_void_p(v.data_ptr()) for k, v in status.items()}
+
+    def enc_u():
+        return call.L.sicn_codec_ctx_encode_batch_async(call.ptr("lat"), call.ptr("scale"), n, w, h, c, 16 * w, 16 * h, call.ptr("slots"), slot,
+                                                        sp["enc_u"], call.ptr("ws"), call.ws_bytes, call.stream)
+
+    def dec_u(valid):
+        return call.L.sicn_codec_ctx_decode_batch_async(call.ptr("slots"), slot, valid, call.ptr("scale"), n, w, h, c, call.ptr("back"),
+                                                        sp["dec_u"], call.ptr("ws"), call.ws_bytes, call.stream)
+
+    def decoded():
+        torch.cuda.synchronize()
+        return call.inner("back").cpu().numpy().reshape(n, n_sym)
+
+    want = call.inner("lat").cpu().numpy().reshape(n, n_sym)
+    ok = [[0, n_sym]] * n
+    # the ragged encoder's containers, through the uniform decoder in place
+    assert call.encode(status=sp["enc_r"]) == 0
+    call.guards_intact()
+    by_ragged = call.inner("slots").cpu().numpy().copy()
+    call.inner("back").fill_(0xEE)
+    assert dec_u(sp["enc_r"]) == 0
+    assert np.array_equal(decoded(), want) and status["dec_u"].cpu().tolist() == ok
+    # the uniform encoder's, on the same (refilled) slot buffer, through the ragged decoder in place
+    call.inner("slots").fill_(PATTERN)
+    assert enc_u() == 0
+    call.guards_intact()
+    assert np.array_equal(call.inner("slots").cpu().numpy(), by_ragged), "the two encoders' slot buffers differ"
+    enc = status["enc_r"].cpu().tolist()
+    assert enc == status["enc_u"].cpu().tolist() and [e for e, _ in enc] == [0] * n
+    call.inner("back").fill_(0xEE)
+    assert call.decode(valid=sp["enc_u"], status=sp["dec_r"]) == 0
+    assert np.array_equal(decoded(), want) and status["dec_r"].cpu().tolist() == ok
+    # image 1's valid bytes end one byte short of its fixed part (header, class tables, length table)
+    fixed = HEADER_BYTES + TABLE_BYTES + 4 * (int(im[1].anchor_streams) + int(im[1].nonanchor_streams))
+    assert fixed <= enc[1][1]
+    valid = status["enc_u"].clone()
+    valid[1, 1] = fixed - 1
+    words = {}
+    for key, run in (("dec_u", lambda: dec_u(ctypes.c_void_p(valid.data_ptr()))),
+                     ("dec_r", lambda: call.decode(valid=ctypes.c_void_p(valid.data_ptr()), status=sp["dec_r"]))):
+        status[key].fill_(-1)
+        call.inner("back").fill_(0xEE)
+        assert run() == 0
+        got = decoded()
+        words[key] = status[key].cpu().tolist()
+        for i in range(n):
+            if i != 1:
+                assert np.array_equal(got[i], want[i]) and words[key][i] == [0, n_sym], f"{key}: image {i}"
+    assert words["dec_u"] == words["dec_r"] and words["dec_u"][1][0] != 0
+    call.guards_intact()
+    call.close()
+
+
 def test_encode_and_decode_captured_in_one_graph(codec):
     """Encode + decode captured once and replayed on fresh latents give the bytes of the eager calls."""
     shapes, lat_c = BATCHES[192], 192

@@ -32,8 +32,9 @@
  *
  * One rectangle per image per call (a selection of an archive ascends strictly): two details of one photograph are two calls.
  *
- * Out of scope: the hyperprior configuration (sicn_ragged_ctx.h, mode 4).  Its y stream is context-coded against a scale map that
- * itself comes through h_s, and its windows need their own halo arithmetic.
+ * The hyperprior configuration (sicn_ragged_ctx.h, mode 4) has its own window decoder, sicn_ragged_ctx_window.h: its y stream is
+ * context-coded against a scale map that itself comes through h_s, and its windows need the halo arithmetic that header states.
+ * The cut and sicn_ragged_roi_plan here serve both.
  *
  * Limits (SICN_EINVAL): those of sicn_ragged_codec_layout and sicn_ragged_crop_layout, a window with rh < 1 or r0 + rh > lat_h, a
  * rectangle that is empty or reaches outside its source.  SICN_ENODEV off gfx950 (creation and the asynchronous calls).

@@ -242,6 +242,22 @@ RAGGED_WINDOW_ABI = {
     "sicn_ragged_cut_run": (_i, [_vp, _vp, _vp, _vp]),
 }
 
+
+class RaggedCtxWindowImage(ctypes.Structure):
+    """ctypes image of `sicn_ragged_ctx_window_image` (include/sicn_ragged_ctx_window.h)."""
+    _fields_ = [("band_offset", ctypes.c_uint64)] + [(n, ctypes.c_uint32) for n in ("band_bytes", "band_row0", "band_rows")] + \
+               [("first_stream", ctypes.c_uint32 * 2), ("end_stream", ctypes.c_uint32 * 2), ("symbols", ctypes.c_uint32)]
+
+
+# include/sicn_ragged_ctx_window.h (library 0.13: a window of latent rows of each image from its rANS-WC streams — 7 enqueued operations)
+RAGGED_CTX_WINDOW_ABI = {
+    "sicn_ragged_ctx_window_layout": (_i, [_u32p, _u32p, _u32, _u32p, _u32p, _i, ctypes.POINTER(RaggedCtxWindowImage), _u64p]),
+    "sicn_ragged_ctx_window_create": (_i, [_vp, _u32p, _u32p, ctypes.POINTER(_vp)]),
+    "sicn_ragged_ctx_window_free": (None, [_vp]),
+    "sicn_ragged_ctx_window_workspace_bytes": (_sz, [_vp]),
+    "sicn_ragged_ctx_window_decode_async": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+}
+
 _lib = None
 
 
@@ -268,7 +284,7 @@ def lib() -> ctypes.CDLL:
             pass
         L = ctypes.CDLL(str(LIB_PATH))
         for name, (res, args) in {**ABI, **CODEC_ABI, **CONVLAYER_ABI, **GDN_ABI, **RAGGED_ABI, **RAGGED_HYPER_ABI, **RAGGED_CODEC_ABI, **RAGGED_CTX_ABI, **RAGGED_ARCHIVE_ABI,
-                                  **RAGGED_ARCHIVE_SELECT_ABI, **RAGGED_WINDOW_ABI}.items():
+                                  **RAGGED_ARCHIVE_SELECT_ABI, **RAGGED_WINDOW_ABI, **RAGGED_CTX_WINDOW_ABI}.items():
             fn = getattr(L, name)          # AttributeError if the ABI is incomplete
             fn.restype = res
             fn.argtypes = args

@@ -429,6 +429,22 @@ def roi_plan(size, rect, n_up_layers: int = 4):
     return {k: int(getattr(out, k)) for k, _ in _lib.RaggedRoiPlan._fields_}
 
 
+def _roi_chain(net, plans, rects, bands, first_rows):
+    """What follows a window decoder in an ROI decode, shared by RaggedRoi and hyperprior.RaggedHyperpriorRoi: (the latent cut, the
+    window net, the pixel cut).  bands: per image (the latent rows its band holds, the band's byte offset in the band tensor);
+    first_rows: the band row at which the plan's row r0 lies.  The window net runs layers 4 .. on `net`'s weights, descs and GDN
+    objects over the sizes (16 cw, 16 rh)."""
+    lat = net.shapes(3)
+    latent_cut = RaggedCut([(rows, w) for (rows, _), (_, w, _) in zip(bands, lat)],
+                           [(p["c0"], y0, p["cw"], p["rh"]) for p, y0 in zip(plans, first_rows)], lat[0][2],
+                           src_offsets=[off for _, off in bands], device=net.device)
+    window_net = RaggedNet([(16 * p["cw"], 16 * p["rh"]) for p in plans], device=net.device, shared_weights=net.weights,
+                           descs=net.descs, gdn=net.gdn)
+    pixel_cut = RaggedCut([(16 * p["rh"], 16 * p["cw"]) for p in plans], [(p["x"], p["y"], r[2], r[3]) for p, r in zip(plans, rects)],
+                          net.shapes(len(net.descs) - 1)[0][2], device=net.device)
+    return latent_cut, window_net, pixel_cut
+
+
 class RaggedRoi:
     """One pixel rectangle of every image of a RaggedNet's batch, decoded from the images' rANS-W containers without the rest of the
     image (include/sicn_ragged_window.h): 2 + 1 + 4 + 1 launches whatever the number of images — the window decoder over the streams
@@ -449,16 +465,11 @@ class RaggedRoi:
         lat = net.shapes(3)
         if [(h, w) for h, w, _ in lat] != self.coder.shapes or lat[0][2] != self.coder.lat_c:
             raise ValueError("the coder's latent shapes are not the net's")
-        c = lat[0][2]
         self.window = self.coder.window([(p["r0"], p["rh"]) for p in self.plans])
-        self.latent_cut = RaggedCut([(p["rh"], w) for p, (_, w, _) in zip(self.plans, lat)],
-                                    [(p["c0"], 0, p["cw"], p["rh"]) for p in self.plans], c,
-                                    src_offsets=[int(im.band_offset) + int(im.lead) for im in self.window.images[:n]], device=net.device)
-        self.window_net = RaggedNet([(16 * p["cw"], 16 * p["rh"]) for p in self.plans], device=net.device, shared_weights=net.weights,
-                                    descs=net.descs, gdn=net.gdn)
-        self.pixel_cut = RaggedCut([(16 * p["rh"], 16 * p["cw"]) for p in self.plans],
-                                   [(p["x"], p["y"], r[2], r[3]) for p, r in zip(self.plans, self.rects)],
-                                   net.shapes(len(net.descs) - 1)[0][2], device=net.device)
+        # a band begins inside a stream: rows from r0 on, `lead` bytes in
+        self.latent_cut, self.window_net, self.pixel_cut = _roi_chain(
+            net, self.plans, self.rects, [(p["rh"], int(im.band_offset) + int(im.lead)) for p, im in zip(self.plans, self.window.images)],
+            [0] * n)
         self.status = self.window.status
 
     def decode(self, slots=None, valid=None, stream=None, out=None):

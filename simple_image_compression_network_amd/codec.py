@@ -10,7 +10,8 @@ from . import _lib
 
 RAW8, PACKED7, RANS, RANSW, RANSWC = 0, 1, 2, 3, 4
 __all__ = ["RAW8", "PACKED7", "RANS", "RANSW", "RANSWC", "encode_latent", "decode_latent", "parse_header", "encode_latents",
-           "decode_latents", "LatentCoder", "RaggedLatentCoder", "RaggedWindowDecoder", "ContextCoder", "RaggedContextCoder", "auto_stream_symbols", "WSTREAM_SYMBOLS",
+           "decode_latents", "LatentCoder", "RaggedLatentCoder", "RaggedWindowDecoder", "ContextCoder", "RaggedContextCoder", "RaggedContextWindowDecoder",
+           "auto_stream_symbols", "WSTREAM_SYMBOLS",
            "RaggedArchive", "split_archive", "archive_info", "subset_archive"]
 
 
@@ -530,6 +531,10 @@ class RaggedContextCoder(_lib.Handle):
 
     sizes = LatentCoder.sizes
 
+    def window(self, rows):
+        """A RaggedContextWindowDecoder over this coder's slots: `rows` = [(r0, rh)] per image, the latent rows [r0, r0 + rh) to decode."""
+        return RaggedContextWindowDecoder(self, rows)
+
     def check(self):
         """Raises SicnError if the last encode / decode reported an error (synchronises); the exception's `.image` is the first
         image that failed."""
@@ -553,6 +558,74 @@ class RaggedContextCoder(_lib.Handle):
             raise err
         host = self.slot_buffer.cpu().numpy()
         return [host[int(im.slot_offset):int(im.slot_offset) + size].tobytes() for im, (_, size) in zip(self.images, status)]
+
+
+class RaggedContextWindowDecoder(_lib.Handle):
+    """A window of latent ROWS of every image decoded from its rANS-WC streams alone (include/sicn_ragged_ctx_window.h): seven
+    enqueued operations for the batch.  Made by `RaggedContextCoder.window(rows)`; shapes, slot buffer and workspace are the coder's,
+    so whatever fills the coder's slots (`encode`, `RaggedArchive.unpack`) feeds this decoder.  The result is the BAND tensor: per
+    image the whole latent rows [band_row0, band_row0 + band_rows) at `images[i].band_offset` — the symbols of the selected streams,
+    zero where a position belongs to a stream outside the selection; the rows asked for are complete.
+    `.status`: device int32 [n][2], the window decoder's verdicts (bit 7, the checksum of the whole latent, is never set)."""
+    _free = "sicn_ragged_ctx_window_free"
+
+    def __init__(self, coder, rows):
+        import torch
+        L = _lib.lib()
+        self.coder = coder              # keeps the coder (and its device tables) alive
+        n = len(coder.shapes)
+        self.rows = [(int(r0), int(rh)) for r0, rh in rows]
+        if len(self.rows) != n:
+            raise ValueError("rows: one (r0, rh) per image of the coder")
+        if any(r0 < 0 or rh < 1 or r0 + rh > h for (r0, rh), (h, _) in zip(self.rows, coder.shapes)):
+            raise ValueError("a window of latent rows must be non-empty and lie inside its latent")
+        u32 = ctypes.c_uint32 * max(n, 1)
+        self._r0, self._rh = u32(*[r for r, _ in self.rows]), u32(*[h for _, h in self.rows])
+        self.images = (_lib.RaggedCtxWindowImage * max(n, 1))()
+        totals = (ctypes.c_uint64 * 2)()
+        _lib.check(L.sicn_ragged_ctx_window_layout(coder._lat_w, coder._lat_h, coder.lat_c, self._r0, self._rh, n, self.images, totals),
+                   "sicn_ragged_ctx_window_layout")
+        self.band_bytes = int(totals[0])
+        self.selected_streams = sum(int(im.end_stream[s]) - int(im.first_stream[s]) for im in self.images[:n] for s in (0, 1))
+        self._h = ctypes.c_void_p()
+        with torch.cuda.device(coder.device):
+            _lib.check(L.sicn_ragged_ctx_window_create(coder._h, self._r0, self._rh, ctypes.byref(self._h)), "sicn_ragged_ctx_window_create")
+        self.status = torch.zeros((n, 2), dtype=torch.int32, device=coder.device)
+
+    def views(self, band):
+        """Per-image [rh][lat_w][lat_c] views of the rows asked for, inside a band tensor (no copy)."""
+        out = []
+        for im, (r0, rh), (_, w) in zip(self.images, self.rows, self.coder.shapes):
+            row = w * self.coder.lat_c
+            at = int(im.band_offset) + (r0 - int(im.band_row0)) * row
+            out.append(band[at:at + rh * row].view(rh, w, self.coder.lat_c))
+        return out
+
+    def decode(self, band, scales, slots=None, valid=None, stream=None):
+        """slots (default: the coder's own) and the FULL scale maps (ragged, the coder's latent layout) -> band, self.status.
+        `valid` as in RaggedLatentCoder.decode.  Enqueue only."""
+        c = self.coder
+        slots = c.slot_buffer if slots is None else slots
+        c._flat(band, self.band_bytes, "band")
+        c._flat(scales, c.latent_bytes, "scales")
+        c._flat(slots, c.slot_bytes, "slots")
+        own = slots is c.slot_buffer
+        vptr = None if (valid is False or (valid is None and not own)) else ctypes.c_void_p((c.enc_status if valid is None else valid).data_ptr())
+        _lib.check(_lib.lib().sicn_ragged_ctx_window_decode_async(
+            self._h, ctypes.c_void_p(slots.data_ptr()), vptr, ctypes.c_void_p(scales.data_ptr()), ctypes.c_void_p(band.data_ptr()),
+            ctypes.c_void_p(self.status.data_ptr()), ctypes.c_void_p(c.ws.data_ptr()), c.ws.numel(), _stream_ptr(stream)),
+            "sicn_ragged_ctx_window_decode_async")
+        return band
+
+    def check(self):
+        """Synchronises and raises if a window reported an error; the exception's `.image` is the first image that failed."""
+        import torch
+        torch.cuda.synchronize(self.coder.device)
+        d = self.status[:, 0].cpu().tolist()
+        if any(d):
+            err = _lib.SicnError(-22, f"rANS-WC window decode status {d}")
+            err.image = next(i for i, v in enumerate(d) if v)
+            raise err
 
 
 def _parse_archive(b):

@@ -435,14 +435,16 @@ __device__ __forceinline__ void ctx_encode_body(const CtxImage &im, uint32_t grp
     if (lane == 0) lens[st] = (WCAP / 2 - pos) * 2;
 }
 
-// decoder, one set per launch (anchors first): group `grp` of CTX_WPB_DEC streams of set SET of the image.  The symbol of a slot
+// decoder, one set per launch (anchors first): the CTX_WPB_DEC streams from `first` on, below `end`, of set SET of the image, in
+// the set's own numbering (the full decoders: a group of the set, first = grp * CTX_WPB_DEC, end = nst[SET]; the window decoder: a
+// group of its selection — no wave decodes or writes a stream outside [first, end)).  The symbol of a slot
 // comes from ONE table read (16 classes x 4096 slots = 64 KB of LDS, shared by the workgroup's eight waves; round 3 read the first
 // symbol of a 16-slot bucket and walked the cumulative table from there — up to a dozen dependent LDS round trips per step on a
 // flat class, with six waves per CU to hide them behind).  SET is a template parameter so that the geometry's per-set fields are
 // picked at compile time: indexed by a kernel argument, the row went to scratch memory (profiles/ragged_ctx_resource_usage.txt).
 constexpr uint32_t CTX_WPB_DEC = 8;
 template <int SET>
-__device__ __forceinline__ void ctx_decode_body(const CtxImage &im, uint32_t grp)
+__device__ __forceinline__ void ctx_decode_body(const CtxImage &im, uint32_t first, uint32_t end)
 {
     constexpr int set = SET;
     const CtxGeom &g = im.g;
@@ -454,14 +456,14 @@ __device__ __forceinline__ void ctx_decode_body(const CtxImage &im, uint32_t grp
     __shared__ uint32_t fc[NCLS * 128];
     __shared__ __attribute__((aligned(16))) uint8_t stb[NCLS * 4096];
     __shared__ __attribute__((aligned(16))) uint16_t words_all[CTX_WPB_DEC][RING_WORDS];   // one ring per wave, see ransw_decode_body
-    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6, sidx = grp * CTX_WPB_DEC + wv, st = sidx + (set ? g.nst[0] : 0);
+    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6, sidx = first + wv, st = sidx + (set ? g.nst[0] : 0);
     {
         const uint4 *b = reinterpret_cast<const uint4 *>(tst);   // the workspace block is 16-byte aligned (ctx_carve)
         for (uint32_t i = threadIdx.x; i < NCLS * 128; i += 64 * CTX_WPB_DEC) fc[i] = tfc[i];
         for (uint32_t i = threadIdx.x; i < NCLS * 256; i += 64 * CTX_WPB_DEC) reinterpret_cast<uint4 *>(stb)[i] = b[i];
     }
     __syncthreads();
-    if (sidx >= g.nst[set]) return;   // (no block barrier below this line)
+    if (sidx >= end) return;   // (no block barrier below this line)
     uint16_t *words = words_all[wv];
     const uint32_t begin = sidx * WSS, cnt = min(WSS, g.nsym[set] - begin), blocks = (cnt + 255) / 256;
     const uint32_t off = offsets[st], len = offsets[st + 1] - off, payload_bytes = meta[1];

@@ -1,6 +1,7 @@
 // Ragged context coder (include/sicn_ragged_ctx.h): the rANS-WC stages of k_ctx_body.hpp over n latents of n different shapes, six
 // launches per encode and eight per decode for the whole batch.  The stages, CtxRow and ctx_image() are the uniform coder's
 // (sicn_codec_ctx.inc); what differs is where a workgroup's row comes from: loaded from a table here, computed from blockIdx.y there.
+// Behind them the window decoder (include/sicn_ragged_ctx_window.h): the decode stage over a SELECTION of every image's streams.
 //
 // Grids: flat over work items.
 //   statistics          chunks of an image's dwords, ctx_hist_blocks(n_i) per image (the uniform coder's rule); one workgroup takes the
@@ -19,6 +20,8 @@
 #include <vector>
 
 #include "../../include/sicn_ragged_ctx.h"
+#include "../../include/sicn_ragged_ctx_window.h"
+#include "ctx_window_host.hpp"
 #include "k_ctx_body.hpp"
 #include "sicn_internal.h"
 #include "sicn_weights_io.h"
@@ -102,7 +105,48 @@ __global__ __launch_bounds__(64 * CTX_WPB_DEC) void k_ragged_ctx_decode(const ui
                                                                         const CtxRow *__restrict__ rows, const uint32_t *__restrict__ dec_image)
 {
     const CtxRow r = load_row(rows, uni(dec_image[blockIdx.x]));
-    ctx_decode_body<SET>(ctx_image(r, latents, scales, containers, workspace), blockIdx.x - r.first_dec[SET]);
+    ctx_decode_body<SET>(ctx_image(r, latents, scales, containers, workspace), (blockIdx.x - r.first_dec[SET]) * CTX_WPB_DEC, r.g.nst[SET]);
+}
+
+// ---- the window decoder (include/sicn_ragged_ctx_window.h) ------------------------------------------------------------------------
+// One set per launch, a flat grid over groups of CTX_WPB_DEC SELECTED streams of that set, rounded up per image.  Two wave-uniform
+// loads resolve an item: win_image[item] -> image, then the coder's CtxRow and the window's CtxWinRow.  The decode stage runs with
+// the stream's REAL index — offsets, geometry and the edge tests of the class rule are the image's own — on a latent pointer
+// biased so that latent row band_row0 is the band's first: the symbols land in the band.  The scale map stays the image's full one.
+struct CtxWinRow {
+    uint64_t lat_bias;                  // band_offset - band_row0 * W * C, modulo 2^64: added to the band tensor's address
+    uint32_t first[2], end[2];          // the selected streams per set, in the set's own numbering
+    uint32_t first_item[2];             // the image's first work item in the flat grid of each set
+    uint32_t symbols;                   // what the selected streams hold
+    uint32_t pad;
+};
+
+template <int SET>
+__global__ __launch_bounds__(64 * CTX_WPB_DEC) void k_ragged_ctx_decode_window(const uint8_t *__restrict__ containers,
+                                                                               const uint8_t *__restrict__ scales, uint8_t *__restrict__ band,
+                                                                               uint8_t *__restrict__ workspace, const CtxRow *__restrict__ rows,
+                                                                               const CtxWinRow *__restrict__ wrows,
+                                                                               const uint32_t *__restrict__ win_image)
+{
+    const uint32_t img = uni(win_image[blockIdx.x]);
+    const CtxRow r = load_row(rows, img);
+    const CtxWinRow *w = wrows + img;
+    CtxImage im = ctx_image(r, nullptr, scales, containers, workspace);
+    im.lat = reinterpret_cast<uint8_t *>(reinterpret_cast<uintptr_t>(band) + uni(w->lat_bias));
+    ctx_decode_body<SET>(im, uni(w->first[SET]) + (blockIdx.x - uni(w->first_item[SET])) * CTX_WPB_DEC, uni(w->end[SET]));
+}
+
+// one workgroup per image: the verdict of the container's fixed part and of the selected streams; bit 7 is never set
+__global__ __launch_bounds__(64) void k_ragged_ctx_finish_window(uint32_t *__restrict__ status, uint8_t *__restrict__ workspace,
+                                                                 const CtxRow *__restrict__ rows, const CtxWinRow *__restrict__ wrows)
+{
+    if (threadIdx.x) return;
+    const CtxImage im = ctx_image(load_row(rows, blockIdx.x), nullptr, nullptr, nullptr, workspace);
+    uint32_t err = im.w.meta[0];
+    if (im.w.meta[3]) err |= 32;                                              // a selected stream, or an entry of the length table
+    if (im.w.offsets[im.g.nst[0] + im.g.nst[1]] != im.w.meta[1]) err |= 64;   // the length table does not add up to the payload
+    status[2 * (size_t)blockIdx.x] = err;
+    status[2 * (size_t)blockIdx.x + 1] = wrows[blockIdx.x].symbols;
 }
 
 __global__ __launch_bounds__(64) void k_ragged_ctx_finish(uint32_t *__restrict__ status, uint8_t *__restrict__ workspace,
@@ -285,5 +329,118 @@ extern "C" int sicn_ragged_ctx_decode_async(const sicn_ragged_ctx_coder *coder, 
     hipLaunchKernelGGL(k_ragged_ctx_stats<false>, dim3((unsigned)p.chunks), dim3(256), 0, stream, latents, scales, ws, coder->d_rows,
                        coder->d_chunk_image);
     hipLaunchKernelGGL(k_ragged_ctx_finish, dim3(n), dim3(64), 0, stream, (uint32_t *)status_dev, ws, coder->d_rows);
+    return hipGetLastError() == hipSuccess ? SICN_OK : SICN_ENODEV;
+}
+
+// ---- the window decoder ----------------------------------------------------------------------------------------------------------
+extern "C" int sicn_ragged_ctx_window_layout(const uint32_t *lat_w, const uint32_t *lat_h, uint32_t lat_c, const uint32_t *r0, const uint32_t *rh,
+                                             int n_images, sicn_ragged_ctx_window_image *images_or_null, uint64_t totals[2])
+{
+    uint64_t coder[3] = {0, 0, 0}, band = 0;
+    if (int rc = sicn_ragged_ctx_layout(lat_w, lat_h, lat_c, n_images, nullptr, coder)) return rc;
+    if (int rc = sicn_ctx_window::window_layout(lat_w, lat_h, lat_c, r0, rh, n_images, images_or_null, &band, nullptr)) return rc;
+    if (totals) {
+        totals[0] = band;
+        totals[1] = coder[2];
+    }
+    return SICN_OK;
+}
+
+struct sicn_ragged_ctx_window {
+    int n_images = 0;
+    uint64_t band_bytes = 0, ws_bytes = 0, groups[2] = {0, 0};
+    const CtxRow *d_rows = nullptr;                  // the coder's
+    CtxWinRow *d_wrows = nullptr;                    // [n_images]
+    uint32_t *d_win_image[2] = {nullptr, nullptr};   // [groups[set]]
+};
+
+extern "C" void sicn_ragged_ctx_window_free(sicn_ragged_ctx_window *win)
+{
+    if (!win) return;
+    for (void *p : {(void *)win->d_wrows, (void *)win->d_win_image[0], (void *)win->d_win_image[1]})
+        if (p) (void)hipFree(p);
+    delete win;
+}
+
+extern "C" int sicn_ragged_ctx_window_create(const sicn_ragged_ctx_coder *coder, const uint32_t *r0, const uint32_t *rh,
+                                             sicn_ragged_ctx_window **out)
+{
+    if (!out) return SICN_EINVAL;
+    *out = nullptr;
+    if (!coder || !r0 || !rh || coder->n_images < 1) return SICN_EINVAL;
+    sicn_ragged_ctx_window *win = new (std::nothrow) sicn_ragged_ctx_window();
+    if (!win) return SICN_ENOMEM;
+    int rc = SICN_OK;
+    try {
+        const int n = coder->n_images;
+        std::vector<CtxWinRow> wrows((size_t)n);
+        std::vector<uint32_t> win_image[2];
+        uint64_t at = 0;
+        for (int i = 0; !rc && i < n; i++) {
+            const CtxRow &r = coder->plan.rows[(size_t)i];
+            sicn_ragged_ctx_window_image im;
+            rc = sicn_ctx_window::plan_of(r.g.W, r.g.H, r.g.C, r0[i], rh[i], at, &im);
+            if (rc) break;
+            CtxWinRow w{};
+            w.lat_bias = at - (uint64_t)im.band_row0 * r.g.W * r.g.C;
+            w.symbols = im.symbols;
+            for (int s = 0; s < 2; s++) {
+                w.first[s] = im.first_stream[s];
+                w.end[s] = im.end_stream[s];
+                w.first_item[s] = (uint32_t)win_image[s].size();       // <= the coder's groups, which fit a grid
+                win_image[s].insert(win_image[s].end(), (size_t)((im.end_stream[s] - im.first_stream[s] + CTX_WPB_DEC - 1) / CTX_WPB_DEC), (uint32_t)i);
+            }
+            wrows[(size_t)i] = w;
+            at += sicn_ctx_window::a16(im.band_bytes);
+        }
+        if (!rc) rc = sicn::chip_geom(nullptr);       // no device, or not a gfx950 one
+        if (!rc) {
+            win->n_images = n;
+            win->band_bytes = at;
+            win->ws_bytes = coder->plan.ws_bytes;
+            win->d_rows = coder->d_rows;
+            for (int s = 0; s < 2; s++) win->groups[s] = win_image[s].size();
+            auto up = [](const std::vector<uint32_t> &v, uint32_t **dev) { return v.empty() || sicn::upload(v.data(), v.size() * sizeof(uint32_t), dev); };
+            if (!sicn::upload(wrows.data(), wrows.size() * sizeof(CtxWinRow), &win->d_wrows) || !up(win_image[0], &win->d_win_image[0]) ||
+                !up(win_image[1], &win->d_win_image[1]))
+                rc = SICN_ENOMEM;
+        }
+    } catch (const std::bad_alloc &) { rc = SICN_ENOMEM; }
+    if (rc) {
+        sicn_ragged_ctx_window_free(win);
+        return rc;
+    }
+    *out = win;
+    return SICN_OK;
+}
+
+extern "C" size_t sicn_ragged_ctx_window_workspace_bytes(const sicn_ragged_ctx_window *win) { return win ? (size_t)win->ws_bytes : 0; }
+
+extern "C" int sicn_ragged_ctx_window_decode_async(const sicn_ragged_ctx_window *win, const uint8_t *containers,
+                                                   const sicn_codec_status *valid_dev_or_null, const uint8_t *scales, uint8_t *band,
+                                                   sicn_codec_status *status_dev, void *workspace, size_t workspace_bytes, void *hip_stream)
+{
+    if (!win || !containers || !scales || !band || !status_dev) return SICN_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(band) | reinterpret_cast<uintptr_t>(scales)) & 3) return SICN_EINVAL;   // dword gathers
+    if (reinterpret_cast<uintptr_t>(containers) & 1) return SICN_EINVAL;   // the streams are read as 16-bit words (slot offsets are even)
+    if (!workspace || workspace_bytes < win->ws_bytes) return SICN_ENOSPC;
+    if (reinterpret_cast<uintptr_t>(workspace) & 15) return SICN_EINVAL;
+    if (int rc = sicn::chip_geom(nullptr)) return rc;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    uint8_t *ws = (uint8_t *)workspace;
+    uint8_t *slots = const_cast<uint8_t *>(containers);   // the tables and scan kernels write containers in the encoder only
+    const unsigned n = (unsigned)win->n_images;
+    // the full decoder's reason: a non-anchor's class reads its neighbours' bytes whatever they hold.  First, so that a failure here
+    // leaves nothing enqueued.
+    if (hipMemsetAsync(band, 0, (size_t)win->band_bytes, stream) != hipSuccess) return SICN_ENODEV;
+    hipLaunchKernelGGL(k_ragged_ctx_parse, dim3(n), dim3(64), 0, stream, containers, (const uint32_t *)valid_dev_or_null, ws, win->d_rows);
+    hipLaunchKernelGGL(k_ragged_ctx_tables, dim3(n), dim3(1024), 0, stream, slots, ws, win->d_rows, 1);
+    hipLaunchKernelGGL(k_ragged_ctx_scan, dim3(n), dim3(1024), 0, stream, slots, (uint32_t *)nullptr, ws, win->d_rows, 1);
+    hipLaunchKernelGGL(k_ragged_ctx_decode_window<0>, dim3((unsigned)win->groups[0]), dim3(64 * CTX_WPB_DEC), 0, stream, containers, scales, band,
+                       ws, win->d_rows, win->d_wrows, win->d_win_image[0]);
+    if (win->groups[1])   // (a window of rows without non-anchors, e.g. of 1 x 1 latents)
+        hipLaunchKernelGGL(k_ragged_ctx_decode_window<1>, dim3((unsigned)win->groups[1]), dim3(64 * CTX_WPB_DEC), 0, stream, containers, scales,
+                           band, ws, win->d_rows, win->d_wrows, win->d_win_image[1]);
+    hipLaunchKernelGGL(k_ragged_ctx_finish_window, dim3(n), dim3(64), 0, stream, (uint32_t *)status_dev, ws, win->d_rows, win->d_wrows);
     return hipGetLastError() == hipSuccess ? SICN_OK : SICN_ENODEV;
 }

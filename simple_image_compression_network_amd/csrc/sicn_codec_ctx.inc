@@ -39,7 +39,8 @@ template <int SET>
 __global__ __launch_bounds__(64 * CTX_WPB_DEC) void k_ctx_decode(const uint8_t *__restrict__ containers, const uint8_t *__restrict__ scales,
                                                                  uint8_t *__restrict__ latents, uint8_t *__restrict__ workspace, CtxBatch b)
 {
-    ctx_decode_body<SET>(ctx_image(batch_row(b), latents, scales, containers, workspace), blockIdx.x);
+    const CtxImage im = ctx_image(batch_row(b), latents, scales, containers, workspace);
+    ctx_decode_body<SET>(im, blockIdx.x * CTX_WPB_DEC, im.g.nst[SET]);
 }
 
 // valid: a sicn_codec_status array or nullptr

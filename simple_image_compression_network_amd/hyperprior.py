@@ -30,7 +30,7 @@ import numpy as np
 from . import api, codec
 from .config import LayerDesc
 
-__all__ = ["HyperpriorCodec", "RaggedHyperpriorCodec", "random_gdn_params", "random_layer_params", "hyper_descs", "hyper_parameters"]
+__all__ = ["HyperpriorCodec", "RaggedHyperpriorCodec", "RaggedHyperpriorRoi", "random_gdn_params", "random_layer_params", "hyper_descs", "hyper_parameters"]
 
 
 def random_gdn_params(rng, channels: int):
@@ -214,6 +214,8 @@ class RaggedHyperpriorCodec:
         self.archive_tag = int(api._lib.lib().sicn_gdn_spec_version()) if self.use_gdn else 0
         self._archive = None        # codec.RaggedArchive over (z_coder, y_coder), made on first use
         self._unpacked = False      # the last decode read an archive: check() reports its verdict first
+        self._rois = {}             # decode(rois=)'s RaggedHyperpriorRoi objects by rectangles, made on first use
+        self._last_roi = None       # ... the one the last decode used: check() reads its y verdicts
 
     def _scale_map(self, z):
         self.h_s.run_layers(0, 1, z, out=self.s_full)
@@ -221,6 +223,7 @@ class RaggedHyperpriorCodec:
 
     def encode(self, packed_x):
         """packed_x: the ragged input (main.pack) -> one z and one y container per image.  Enqueue only, on the current stream."""
+        self._last_roi = None                   # check() reads the y coder's own verdicts again
         self.main.run_layers(0, 3, packed_x, out=self.y)
         self.h_a.run_layers(0, 1, self.y, out=self.z)
         self.z_coder.encode(self.z)
@@ -269,43 +272,67 @@ class RaggedHyperpriorCodec:
         return cls([info["image_sizes"][i] for i in sel], seed=seed, device=device, use_gdn=info["tag"] != 0 if use_gdn is None else use_gdn,
                    main_params=main_params, z_stream_symbols=[int(h.stream_symbols) for h in heads])
 
-    def decode(self, out=None, z_containers=None, y_containers=None, archive=None, images=None):
-        """Containers (default: the last encode's; else lists of `bytes`, one per image; or `archive`, what `archive()` returned) ->
-        the reconstructions, a ragged tensor of main's boundary 7 (`main.cropped(out)` cuts them to the images' sizes).  An archive is
-        unpacked on the device into the coders' own slots; one whose tag is not this codec's (another GDN specification version, or
-        the other `use_gdn`) is refused as a whole: `check()` raises with bit 5.  Enqueue only.
-        `images` (with `archive` only): the archive may hold more images than this codec; a strictly ascending sequence of
-        len(self.sizes) indices into it names the ones to decode (ValueError otherwise, before any launch)."""
-        keep = []
+    def _decode_scales(self, z_containers=None, y_containers=None, archive=None, images=None):
+        """The front half of every decode, in full: unpack (with an archive), the z coder, h_s and its crop -> self.s.  Returns the y
+        section's `valid` array (an archive) or None.  ValueError before any launch for arguments that do not go together."""
         if images is not None and archive is None:
             raise ValueError("images= selects from an archive")
         self._unpacked = archive is not None
+        self._external = keep = []
+        y_valid = None
         if archive is not None:
             if z_containers is not None or y_containers is not None:
                 raise ValueError("either an archive or lists of containers")
             z_valid, y_valid = self._ragged_archive().unpack(archive, images=images)
             self.z_coder.decode(self.z_hat, valid=z_valid)
-            self._scale_map(self.z_hat)
-            self.y_coder.decode(self.y_hat, self.s, valid=y_valid)
-            self._external = keep
-            out, _ = self.main.run_layers(4, 7, self.y_hat, out=out)
-            return out
-        if z_containers is None:
+        elif z_containers is None:
             self.z_coder.decode(self.z_hat)
         else:
             buf, status = self._upload(z_containers, self.z_coder, "z_containers")
             keep += [buf, status]
             self.z_coder.decode(self.z_hat, slots=buf, valid=status)
         self._scale_map(self.z_hat)
-        if y_containers is None:
+        return y_valid
+
+    def roi(self, rects):
+        """A RaggedHyperpriorRoi over this codec: one pixel rectangle (x0, y0, w, h), or None, per image."""
+        return RaggedHyperpriorRoi(self, rects)
+
+    def decode(self, out=None, z_containers=None, y_containers=None, archive=None, images=None, rois=None):
+        """Containers (default: the last encode's; else lists of `bytes`, one per image; or `archive`, what `archive()` returned) ->
+        the reconstructions, a ragged tensor of main's boundary 7 (`main.cropped(out)` cuts them to the images' sizes).  An archive is
+        unpacked on the device into the coders' own slots; one whose tag is not this codec's (another GDN specification version, or
+        the other `use_gdn`) is refused as a whole: `check()` raises with bit 5.  Enqueue only.
+        `images` (with `archive` only): the archive may hold more images than this codec; a strictly ascending sequence of
+        len(self.sizes) indices into it names the ones to decode (ValueError otherwise, before any launch).
+        `rois`: one (x0, y0, w, h) per image, or None for that image whole — `roi(rois).decode(...)` in one call: only the y streams,
+        latent columns and pixels the rectangles need are decoded, and the result is the ROI pixels as a ragged [h][w][3] tensor
+        (`roi_views` gives them per image), the bytes of the full decode cut to the rectangles.  A wrong length or a rectangle outside
+        its image is a ValueError before any launch."""
+        if rois is not None:
+            key = tuple(None if r is None else tuple(int(v) for v in r) for r in rois)
+            if key not in self._rois:
+                self._rois[key] = RaggedHyperpriorRoi(self, key)
+            self._last_roi = self._rois[key]
+            return self._last_roi.decode(archive=archive, images=images, z_containers=z_containers, y_containers=y_containers, out=out)
+        self._last_roi = None
+        y_valid = self._decode_scales(z_containers, y_containers, archive, images)
+        if archive is not None:
+            self.y_coder.decode(self.y_hat, self.s, valid=y_valid)
+        elif y_containers is None:
             self.y_coder.decode(self.y_hat, self.s)
         else:
             buf, status = self._upload(y_containers, self.y_coder, "y_containers")
-            keep += [buf, status]
+            self._external += [buf, status]
             self.y_coder.decode(self.y_hat, self.s, slots=buf, valid=status)
-        self._external = keep
         out, _ = self.main.run_layers(4, 7, self.y_hat, out=out)
         return out
+
+    def roi_views(self, roi_pixels):
+        """Per-image [h][w][3] views of what the last `decode(rois=...)` returned."""
+        if self._last_roi is None:
+            raise ValueError("decode(rois=...) has not run")
+        return self._last_roi.views(roi_pixels)
 
     def containers(self):
         """[(z container, y container)] of the last encode as `bytes` (synchronises; raises if the encode reported an error)."""
@@ -318,7 +345,7 @@ class RaggedHyperpriorCodec:
             self._archive.check()
         self.z_coder.check()
         try:
-            self.y_coder.check()
+            (self._last_roi.window if self._last_roi is not None else self.y_coder).check()
         except api._lib.SicnError as e:
             err = api._lib.SicnError(e.code, f"image {e.image} {self.sizes[e.image]}: {e}")
             err.image = e.image
@@ -326,3 +353,63 @@ class RaggedHyperpriorCodec:
 
     def bytes_per_image(self):
         return [a + b for a, b in zip(self.z_coder.sizes(), self.y_coder.sizes())]
+
+
+class RaggedHyperpriorRoi:
+    """One pixel rectangle of every image of a RaggedHyperpriorCodec's batch, decoded without the rest of the image's y streams,
+    latent columns and pixels (include/sicn_ragged_ctx_window.h).  The chain of `decode`:
+
+        z coder, h_s and its crop   in FULL: z has 1/16 of y's positions and h_s ends at latent resolution, while layers 4-7 make
+                                    256 pixels per latent position; a windowed h_s is out of scope
+        codec.RaggedContextWindowDecoder   the y streams of both checkerboard sets that hold the latent rows, with the halo the
+                                    class rule asks for -> the band tensor (seven enqueued operations)
+        api.RaggedCut               the latent columns out of every band
+        api.RaggedNet 4 .. 7        a net made for the windows' sizes (16 cw, 16 rh) on `codec.main`'s weights, descs and GDN objects
+        api.RaggedCut               the rectangle out of every reconstruction -> the ROI pixels, a ragged [h][w][3] tensor
+
+    Same bytes as `codec.decode` + `main.cropped`, sliced.  rects: one (x0, y0, w, h) per image, or None for that image whole;
+    ValueError before anything is made for a wrong length or a rectangle outside its image.  Also `codec.roi(rects)` and, in one
+    call, `codec.decode(..., rois=rects)`."""
+
+    def __init__(self, codec_, rects):
+        n = len(codec_.sizes)
+        if len(rects) != n:
+            raise ValueError(f"rects: one per image, {n}")
+        self.codec = codec_
+        net = codec_.main
+        self.rects = [(0, 0, w, h) if r is None else tuple(int(v) for v in r) for r, (w, h) in zip(rects, codec_.sizes)]
+        self.plans = [api.roi_plan(size, r) for size, r in zip(codec_.sizes, self.rects)]     # ValueError before anything is made
+        self.window = codec_.y_coder.window([(p["r0"], p["rh"]) for p in self.plans])
+        self.latent_cut, self.window_net, self.pixel_cut = api._roi_chain(
+            net, self.plans, self.rects, [(int(im.band_rows), int(im.band_offset)) for im in self.window.images[:n]],
+            [p["r0"] - int(im.band_row0) for p, im in zip(self.plans, self.window.images)])
+        self.status = self.window.status
+
+    def decode(self, archive=None, images=None, z_containers=None, y_containers=None, out=None):
+        """Containers as in `RaggedHyperpriorCodec.decode` (default: the last encode's) -> the ROI pixels, a ragged [h][w][3]
+        tensor.  Enqueue only; `check()` raises for what the archive, the z coder or the window decoder reported."""
+        import torch
+        c = self.codec
+        c._last_roi = self
+        y_valid = c._decode_scales(z_containers, y_containers, archive, images)
+        self.band = torch.empty(self.window.band_bytes, dtype=torch.uint8, device=c.device)
+        if archive is not None:
+            self.window.decode(self.band, c.s, valid=y_valid)
+        elif y_containers is None:
+            self.window.decode(self.band, c.s)
+        else:
+            buf, status = c._upload(y_containers, c.y_coder, "y_containers")
+            c._external += [buf, status]
+            self.window.decode(self.band, c.s, slots=buf, valid=status)
+        self.latent = self.latent_cut.run(self.band)
+        recon, _ = self.window_net.run_layers(4, len(c.main.descs) - 1, self.latent)
+        return self.pixel_cut.run(recon, out)
+
+    def views(self, roi):
+        """Per-image [h][w][3] views of what `decode` returned."""
+        return self.pixel_cut.views(roi)
+
+    def check(self):
+        """The codec's `check()` in its order — archive, z, then y with the image named — with this object's window as the y decoder."""
+        self.codec._last_roi = self
+        self.codec.check()

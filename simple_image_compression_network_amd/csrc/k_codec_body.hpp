@@ -94,8 +94,8 @@ struct DecImage {
     uint32_t n, ns, wss, lat_w, lat_h, lat_c;
     uint32_t *err;                 // self form: [ns] per-stream verdicts; else one word of error flags (atomics)
     unsigned long long *sums;      // self form: [2 ns] per-stream checksum sums; else [2] (atomics)
-    const uint32_t *offsets;       // [ns + 1] from k_scan (not in the self form)
-    const uint32_t *meta;          // k_dec_parse's verdict (not in the self form)
+    const uint32_t *offsets;       // [ns + 1] from ransw_scan_body (not in the self form)
+    const uint32_t *meta;          // dec_parse_body's verdict (not in the self form)
     uint32_t *status;              // sicn_codec_status {error, bytes} of this image
 };
 
@@ -117,7 +117,7 @@ __device__ __forceinline__ CoderRow load_row(const CoderRow *__restrict__ rows, 
                     uni(r->first_row), uni(r->n_rows)};
 }
 // A uniform batch (sicn_codec.hip: blockIdx.y = image, every image of one shape) is image 0's row and three byte strides.  Passed by
-// value, so it lives in kernel-argument SGPRs.  `scan`: the form above SELF_SCAN_MAX streams (no statistics rows; k_scan in front).
+// value, so it lives in kernel-argument SGPRs.  `scan`: the form above SELF_SCAN_MAX streams (no statistics rows; a scan kernel in front).
 struct UniformBatch {
     CoderRow row0;
     uint64_t s_lat, s_slot, s_ws;
@@ -130,7 +130,7 @@ __device__ __forceinline__ CoderRow batch_row(const UniformBatch &b)
     return r;
 }
 
-// scan: the table comes from k_enc_header's `freq`, not from statistics rows
+// scan: the table comes from enc_header_body's `freq`, not from statistics rows
 __device__ __forceinline__ EncImage enc_image(const CoderRow &r, const uint8_t *latents, uint8_t *containers, uint32_t *status,
                                               uint8_t *workspace, uint32_t img, bool scan = false)
 {
@@ -150,7 +150,7 @@ __device__ __forceinline__ EncImage enc_image(const CoderRow &r, const uint8_t *
     return im;
 }
 
-// valid: a sicn_codec_status array whose .bytes bound the slots, or nullptr.  scan: k_dec_parse and k_scan ran in front, the
+// valid: a sicn_codec_status array whose .bytes bound the slots, or nullptr.  scan: dec_parse_body and ransw_scan_body ran in front, the
 // streams report through the statistics block (meta[3], sums) instead of per-stream words
 __device__ __forceinline__ DecImage dec_image(const CoderRow &r, const uint8_t *containers, const uint32_t *valid, uint8_t *latents,
                                               uint32_t *status, uint8_t *workspace, uint32_t img, bool scan = false)
@@ -557,7 +557,7 @@ __device__ __forceinline__ void ransw_decode_body(const DecImage &im, uint32_t s
     if (self) {
         const size_t fixed = SICN_CODEC_HEADER_BYTES + 256 + 4 * (size_t)ns;
         const uint32_t valid = im.valid ? min(*im.valid, im.slot_cap) : im.slot_cap;
-        if ((size_t)payload_bytes > (size_t)valid - fixed) payload_bytes = 0;   // what k_dec_parse's meta[1] says
+        if ((size_t)payload_bytes > (size_t)valid - fixed) payload_bytes = 0;   // what dec_parse_body's meta[1] says
     }
     const uint32_t *__restrict__ offsets = im.offsets;
     uint8_t *__restrict__ lat = im.lat;
@@ -597,7 +597,7 @@ __device__ __forceinline__ void ransw_decode_body(const DecImage &im, uint32_t s
     }
     const uint32_t begin = st * wss, cnt = min(wss, n - begin), blocks = (cnt + 255) / 256;
     uint32_t off, len;
-    if (self) {   // exclusive prefix sum of the length table up to this stream, entries above the cap counting as 0 (as in k_scan)
+    if (self) {   // exclusive prefix sum of the length table up to this stream, entries above the cap counting as 0 (as in scan_body)
         const uint8_t *table = freq_bytes + 256;
         const uint32_t cap = wstream_cap(wss);
         auto entry = [&](uint32_t i) {
@@ -709,7 +709,7 @@ __device__ __forceinline__ void ransw_decode_body(const DecImage &im, uint32_t s
 
 // The same without a scan kernel in front (asynchronous encoder, up to SELF_SCAN_MAX streams per image): every workgroup sums
 // the lengths of the streams before its own, copies its stream and writes its entry of the container's length table; the last
-// one also writes the header's payload-bytes field and the status' byte count (what k_scan did besides the offsets).
+// one also writes the header's payload-bytes field and the status' byte count (what ransw_scan_body does besides the offsets).
 // `cap` = wstream_cap(im.wss), `fixed_bytes` = the container's bytes in front of the payload.
 __device__ __forceinline__ void compact_self_body(const EncImage &im, uint32_t st, uint32_t cap, uint32_t fixed_bytes)
 {
@@ -749,7 +749,7 @@ __device__ __forceinline__ void compact_self_body(const EncImage &im, uint32_t s
 
 // The asynchronous decoder's ONLY other stage when the streams were decoded in self mode (ransw_decode_body, self != 0): header,
 // frequency table, payload size and length table validated here, AFTER the streams ran (they bound themselves), per-stream
-// verdicts and checksum sums folded -> status {error, n_symbols}; the same error bits as k_dec_parse + k_scan + k_dec_finish.
+// verdicts and checksum sums folded -> status {error, n_symbols}; the same error bits as dec_parse_body + ransw_scan_body + dec_finish_body.
 __device__ __forceinline__ void dec_finish_self_body(const DecImage &im)
 {
     const uint8_t *__restrict__ c = im.c;
@@ -773,7 +773,7 @@ __device__ __forceinline__ void dec_finish_self_body(const DecImage &im)
     }
     auto rd32 = [&](size_t o) { return c[o] | ((uint32_t)c[o + 1] << 8) | ((uint32_t)c[o + 2] << 16) | ((uint32_t)c[o + 3] << 24); };
     uint32_t err = 0;
-    if (tid < 64) {   // wave 0: the checks of k_dec_parse
+    if (tid < 64) {   // wave 0: the checks of dec_parse_body
         const uint32_t expect[10] = {0x4C434953u, 1u | ((uint32_t)SICN_CODEC_RANSW << 16), 0, 0, lat_w, lat_h, lat_c, n, ns, wss};
         if (lane < 10 && lane != 2 && lane != 3 && rd32(4 * lane) != expect[lane]) err = 4;
         uint32_t fsum = c[SICN_CODEC_HEADER_BYTES + 4 * lane] + ((uint32_t)c[SICN_CODEC_HEADER_BYTES + 4 * lane + 1] << 8) +
@@ -786,7 +786,7 @@ __device__ __forceinline__ void dec_finish_self_body(const DecImage &im)
     const bool pb_bad = (size_t)pb > (size_t)valid - fixed;
     if (tid == 0 && pb_bad) err |= 16;
     const uint32_t bound = pb_bad ? 0u : pb;
-    // length table: entries above the cap are an error and count as 0 (k_scan); the per-stream verdicts; the checksum sums
+    // length table: entries above the cap are an error and count as 0 (scan_body); the per-stream verdicts; the checksum sums
     const uint32_t cap = wstream_cap(wss);
     uint32_t tab = 0;
     unsigned long long s1 = 0, s2 = 0;
@@ -847,7 +847,7 @@ __device__ __forceinline__ void dec_finish_window_body(const DecImage &im, uint3
     }
     auto rd32 = [&](size_t o) { return c[o] | ((uint32_t)c[o + 1] << 8) | ((uint32_t)c[o + 2] << 16) | ((uint32_t)c[o + 3] << 24); };
     uint32_t err = 0;
-    if (tid < 64) {   // wave 0: the checks of k_dec_parse
+    if (tid < 64) {   // wave 0: the checks of dec_parse_body
         const uint32_t expect[10] = {0x4C434953u, 1u | ((uint32_t)SICN_CODEC_RANSW << 16), 0, 0, lat_w, lat_h, lat_c, n, ns, wss};
         if (lane < 10 && lane != 2 && lane != 3 && rd32(4 * lane) != expect[lane]) err = 4;
         uint32_t fsum = c[SICN_CODEC_HEADER_BYTES + 4 * lane] + ((uint32_t)c[SICN_CODEC_HEADER_BYTES + 4 * lane + 1] << 8) +
@@ -886,9 +886,9 @@ __device__ __forceinline__ void dec_finish_window_body(const DecImage &im, uint3
     }
 }
 
-// ---- the bookkeeping stages of the scan form (mode 2, mode 3 above SELF_SCAN_MAX streams, mode 4) -------------------------------
-// Uniform kernels (sicn_codec.hip, sicn_codec_ctx.inc) resolve an image's pointers from strides, the ragged context coder
-// (k_ragged_ctx.hip) from its row; the stages themselves are these.
+// ---- the bookkeeping of the scan form (mode 2, mode 3 above SELF_SCAN_MAX streams, mode 4) --------------------------------------
+// First the steps on plain pointers, which mode 2 (one image on the host's schedule) launches as they are; then mode 3's stages of
+// one ScanImage.  Mode 4's stages of a CtxImage (k_ctx_body.hpp) are made of the same steps.
 
 // Exclusive prefix sum of `in[0..n)` into out[0..n], out[n] = total.  One workgroup of 1024 lanes:
 // wavefront-level scan with __shfl_up, wave totals combined through LDS, carry across chunks.
@@ -985,6 +985,109 @@ __device__ __forceinline__ void dec_finish_body(const uint32_t *__restrict__ met
     if (!err && ((b << 16) | a) != meta[2]) err |= 128;   // checksum (SICN_EBADMSG)
     status[0] = err;
     status[1] = n;
+}
+
+// ---- mode 3, scan form: one image as its bookkeeping stages see it (the stream stages see it as EncImage / DecImage) -----------
+struct ScanImage {
+    CoderRow r;
+    Workspace w;                   // the image's block, carved
+    uint8_t *slot;                 // container slot; the decoder only reads it
+    const uint32_t *valid;         // decoder: valid bytes of this slot, or nullptr = r.slot_cap
+    uint32_t *status;              // sicn_codec_status {error, bytes} of this image
+};
+// valid: a sicn_codec_status array whose .bytes bound the slots, or nullptr
+__device__ __forceinline__ ScanImage scan_image(const CoderRow &r, const uint8_t *containers, const uint32_t *valid, uint32_t *status,
+                                                uint8_t *workspace, uint32_t img)
+{
+    ScanImage im;
+    im.r = r;
+    carve(im.w, workspace + r.ws_off, r.ns, wstream_cap(r.wss));
+    im.slot = const_cast<uint8_t *>(containers) + r.slot_off;
+    im.valid = valid ? valid + 2 * (size_t)img + 1 : nullptr;   // sicn_codec_status.bytes
+    im.status = status + 2 * (size_t)img;
+    return im;
+}
+
+// Encoder, one wave, after the statistics: histogram -> 12-bit frequencies (normalize_wave), then the container header and
+// frequency table.  status[0] = error flags (bit 0: symbol >= 128, bit 1: normalisation failed).
+__device__ __forceinline__ void enc_header_body(const ScanImage &im)
+{
+    const CoderRow &r = im.r;
+    const uint32_t *hist = im.w.hist;
+    const int lane = threadIdx.x;
+    uint32_t err = 0;
+    const uint32_t hh[2] = {hist[2 * lane], hist[2 * lane + 1]};
+    if (hist[128 + lane] | hist[192 + lane]) err = 1;
+    uint32_t f[2];
+    err |= normalize_wave(hh, r.n, f, lane);
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) err |= (uint32_t)__shfl_xor((int)err, d);
+    if (err) f[0] = f[1] = 0;   // the encode stage skips zero-frequency symbols: it stays memory-safe
+    im.w.freq[2 * lane] = (uint16_t)f[0];
+    im.w.freq[2 * lane + 1] = (uint16_t)f[1];
+    write_header_wave(im.slot, f, im.w.sums[0], im.w.sums[1], r.n, r.ns, r.lat_w, r.lat_h, r.lat_c, r.img_w, r.img_h, r.wss, lane);
+    if (lane == 0) im.status[0] = err;
+}
+
+// One workgroup of 1024.  Encoder, after the streams: their lengths -> offsets, the container's length table and payload-bytes field,
+// status.bytes.  Decoder: the container's length table -> offsets; a slot the parse stage rejected as too short (meta[0] & 0x100) is
+// not read: its table counts as empty, and with meta[1] = 0 every stream of it fails its bound off + len <= payload bytes.
+__device__ __forceinline__ void ransw_scan_body(const ScanImage &im, bool dec)
+{
+    uint8_t *table = im.slot + SICN_CODEC_HEADER_BYTES + 256;
+    if (dec)
+        scan_body(nullptr, table, im.r.ns, im.w.offsets, nullptr, nullptr, wstream_cap(im.r.wss), im.w.meta + 3, nullptr, 0u,
+                  (im.w.meta[0] & 0x100u) != 0);
+    else
+        scan_body(im.w.lens, nullptr, im.r.ns, im.w.offsets, table, im.slot + 40, 0xFFFFFFFFu, nullptr, im.status + 1,
+                  (uint32_t)(SICN_CODEC_HEADER_BYTES + 256) + 4 * im.r.ns, false);
+}
+__device__ __forceinline__ void enc_compact_body(const ScanImage &im, uint32_t st)
+{
+    compact_body(im.w.scratch, im.w.lens, im.w.offsets, im.slot + SICN_CODEC_HEADER_BYTES + 256 + 4 * (size_t)im.r.ns,
+                 wstream_cap(im.r.wss), st);
+}
+
+// Decoder front end, one wave: every header field against the shape the caller expects, the frequency table, and the sizes
+// against the bytes the caller vouches for.  meta[0] = error bits, meta[1] = payload bytes the streams may use.
+__device__ __forceinline__ void dec_parse_body(const ScanImage &im)
+{
+    const CoderRow &r = im.r;
+    const uint8_t *c = im.slot;
+    uint32_t *meta = im.w.meta;
+    const int lane = threadIdx.x;
+    const uint32_t valid = im.valid ? min(*im.valid, r.slot_cap) : r.slot_cap;
+    const size_t fixed = SICN_CODEC_HEADER_BYTES + 256 + 4 * (size_t)r.ns;
+    clear_stats_in_parse(meta, lane);
+    if (valid < fixed) {   // nothing of this slot may be read
+        if (lane == 0) { meta[0] = 0x104u; meta[1] = 0; meta[2] = 0; meta[3] = 0; }
+        return;
+    }
+    auto rd32 = [&](int o) { return c[o] | ((uint32_t)c[o + 1] << 8) | ((uint32_t)c[o + 2] << 16) | ((uint32_t)c[o + 3] << 24); };
+    const uint32_t expect[10] = {0x4C434953u, 1u | ((uint32_t)SICN_CODEC_RANSW << 16), 0, 0, r.lat_w, r.lat_h, r.lat_c, r.n, r.ns, r.wss};
+    uint32_t err = 0;
+    if (lane < 10 && lane != 2 && lane != 3 && rd32(4 * lane) != expect[lane]) err = 4;
+    uint32_t fsum = c[SICN_CODEC_HEADER_BYTES + 4 * lane] + ((uint32_t)c[SICN_CODEC_HEADER_BYTES + 4 * lane + 1] << 8) +
+                    c[SICN_CODEC_HEADER_BYTES + 4 * lane + 2] + ((uint32_t)c[SICN_CODEC_HEADER_BYTES + 4 * lane + 3] << 8);
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) fsum += __shfl_xor((int)fsum, d);
+    if (r.n && fsum != 4096) err |= 8;
+    const uint32_t pb = rd32(40);
+    if ((size_t)pb > (size_t)valid - fixed) err |= 16;
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) err |= (uint32_t)__shfl_xor((int)err, d);
+    if (lane == 0) {
+        meta[0] = err;
+        meta[1] = (err & 16) ? 0u : pb;
+        meta[2] = rd32(44);
+        meta[3] = 0;
+    }
+}
+
+// Decoder back end of one image, ONE lane
+__device__ __forceinline__ void dec_finish_body(const ScanImage &im)
+{
+    dec_finish_body(im.w.meta, im.w.sums, im.w.offsets, im.status, im.r.n, im.r.ns);
 }
 
 }  // namespace

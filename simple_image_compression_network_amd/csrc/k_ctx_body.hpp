@@ -62,7 +62,7 @@ __device__ __forceinline__ uint32_t ctx_class4(int set, const uint8_t *lat, cons
 }
 
 struct CtxWorkspace {        // per image, carved out of the caller's workspace
-    uint32_t *hist;          // [256] + sums (64 B) + freq (256 B, unused) + meta (64 B): the block k_clear_stats zeroes
+    uint32_t *hist;          // [256] + sums (64 B) + freq (256 B, unused) + meta (64 B): the statistics block, cleared before a coding
     unsigned long long *sums;
     uint32_t *meta;          // [0] error flags, [1] payload bytes the streams may use, [2] header adler32, [3] stream errors
     uint32_t *chist;         // [16][128] class histograms
@@ -90,6 +90,8 @@ __host__ __device__ inline size_t ctx_carve(CtxWorkspace &w, void *base, uint32_
     off += (size_t)ns * scratch_per_stream;
     return off;
 }
+// host: what ctx_carve says about a block without a block: the byte offset of the class histograms (carved from address 0), the size
+inline size_t ctx_chist_offset() { CtxWorkspace w; ctx_carve(w, nullptr, 0, 0); return reinterpret_cast<uintptr_t>(w.chist); }
 inline size_t ctx_ws_bytes(uint32_t ns) { CtxWorkspace w; return align_up(ctx_carve(w, nullptr, ns, WCAP) + 64, 256); }
 // workgroups of the class-histogram stage that share one image of n symbols
 inline uint32_t ctx_hist_blocks(uint32_t n) { const uint32_t b = (n / 4 + 255u) / 256u; return b < 256u ? b : 256u; }
@@ -192,7 +194,7 @@ __device__ __forceinline__ void ctx_hist_body(const CtxImage &im, uint32_t bx, u
     if (bad) atomicOr(&meta[0], 1u);
 }
 
-// 16 waves, one per class: histogram -> 12-bit table (the walk of k_enc_header), container bytes, and the encoder's /
+// 16 waves, one per class: histogram -> 12-bit table (the walk of normalize_wave), container bytes, and the encoder's /
 // decoder's lookup images.  Wave 0 also writes the header.
 // encoder (!dec): the tables come from the class histograms and go to the container; decoder: they are READ from the container
 __device__ __forceinline__ void ctx_tables_body(const CtxImage &im, bool dec)
@@ -529,6 +531,49 @@ __device__ __forceinline__ void ctx_decode_body(const CtxImage &im, uint32_t fir
         if (mine) *reinterpret_cast<uint32_t *>(lat + o) = out4;
     }
     if (bad || x != RANSW_L || wpos != nwords) atomicOr(&meta[3], 1u);
+}
+
+// ---- the bookkeeping stages: the steps of k_codec_body.hpp on one CtxImage.  `status`: the batch's sicn_codec_status array --------
+// encoder, first on the stream, 256 lanes: the statistics block and the class histograms behind it (contiguous), which the next stage adds to
+__device__ __forceinline__ void ctx_clear_body(const CtxImage &im)
+{
+    for (uint32_t i = threadIdx.x; i < STATS_WORDS + 16 + NCLS * 128; i += 256) im.w.hist[i] = 0;
+}
+
+// One workgroup of 1024.  Encoder: stream lengths -> offsets, the container's length table and payload-bytes field, status[img].bytes.
+// Decoder: the container's length table -> offsets (entries above a stream's cap are an error; a slot the parse stage found too short is not read).
+__device__ __forceinline__ void ctx_scan_body(const CtxImage &im, uint32_t *status, uint32_t img, bool dec)
+{
+    const CtxWorkspace &w = im.w;
+    const uint32_t ns = im.g.nst[0] + im.g.nst[1];
+    uint8_t *table = im.slot + SICN_CODEC_HEADER_BYTES + CTX_TABLE_BYTES;
+    if (dec)
+        scan_body(nullptr, table, ns, w.offsets, nullptr, nullptr, WCAP, w.meta + 3, nullptr, 0u, (w.meta[0] & 0x100u) != 0);
+    else
+        scan_body(w.lens, nullptr, ns, w.offsets, table, im.slot + 40, 0xFFFFFFFFu, nullptr, status + 2 * (size_t)img + 1,
+                  (uint32_t)(SICN_CODEC_HEADER_BYTES + CTX_TABLE_BYTES) + 4 * ns, false);
+}
+
+// stream `st` of the image, anchors and non-anchors numbered through, by one workgroup of 256
+__device__ __forceinline__ void ctx_compact_body(const CtxImage &im, uint32_t st)
+{
+    const uint32_t ns = im.g.nst[0] + im.g.nst[1];
+    compact_body(im.w.scratch, im.w.lens, im.w.offsets, im.slot + SICN_CODEC_HEADER_BYTES + CTX_TABLE_BYTES + 4 * (size_t)ns, WCAP, st);
+}
+
+// decoder back end, ONE lane: the verdict of the whole image -> status[img] = {error, n_symbols}
+__device__ __forceinline__ void ctx_finish_body(const CtxImage &im, uint32_t *status, uint32_t img)
+{
+    dec_finish_body(im.w.meta, im.w.sums, im.w.offsets, status + 2 * (size_t)img, im.g.W * im.g.H * im.g.C, im.g.nst[0] + im.g.nst[1]);
+}
+// the same for a window of the image's streams holding `symbols`: the container's fixed part and the selected streams; bit 7 is never set
+__device__ __forceinline__ void ctx_finish_window_body(const CtxImage &im, uint32_t *status, uint32_t img, uint32_t symbols)
+{
+    uint32_t err = im.w.meta[0];
+    if (im.w.meta[3]) err |= 32;                                              // a selected stream, or an entry of the length table
+    if (im.w.offsets[im.g.nst[0] + im.g.nst[1]] != im.w.meta[1]) err |= 64;   // the length table does not add up to the payload
+    status[2 * (size_t)img] = err;
+    status[2 * (size_t)img + 1] = symbols;
 }
 
 }  // namespace

@@ -31,8 +31,7 @@ namespace {
 // encoder, first on the stream: the statistics block and the class histograms of every image, which the next stage adds to
 __global__ __launch_bounds__(256) void k_ragged_ctx_clear(uint8_t *__restrict__ workspace, const CtxRow *__restrict__ rows)
 {
-    const CtxImage im = ctx_image(load_row(rows, blockIdx.x), nullptr, nullptr, nullptr, workspace);
-    for (uint32_t i = threadIdx.x; i < STATS_WORDS + 16 + NCLS * 128; i += 256) im.w.hist[i] = 0;   // hist .. meta, then chist: contiguous
+    ctx_clear_body(ctx_image(load_row(rows, blockIdx.x), nullptr, nullptr, nullptr, workspace));
 }
 
 // CLASSES: the encoder's statistics (byte histogram, checksum sums, class histograms); else the decoder's (checksum sums of what it decoded)
@@ -70,32 +69,21 @@ __global__ __launch_bounds__(64 * CTX_WPB) void k_ragged_ctx_encode(const uint8_
     ctx_encode_body(ctx_image(r, latents, scales, nullptr, workspace), blockIdx.x - r.first_enc);
 }
 
-// One workgroup per image.  Encoder: stream lengths -> offsets, the container's length table and payload-bytes field, and the image's
-// status {error, container bytes}.  Decoder: the container's length table -> offsets (entries above a stream's cap are an error).
+// One workgroup per image: the scan stage, in the encoder behind the image's verdict on its statistics and tables (status.error)
 __global__ __launch_bounds__(1024) void k_ragged_ctx_scan(uint8_t *__restrict__ containers, uint32_t *__restrict__ status,
                                                           uint8_t *__restrict__ workspace, const CtxRow *__restrict__ rows, int dec)
 {
     const CtxImage im = ctx_image(load_row(rows, blockIdx.x), nullptr, nullptr, containers, workspace);
-    const CtxWorkspace &w = im.w;
-    const uint32_t ns = im.g.nst[0] + im.g.nst[1];
-    uint8_t *table = im.slot + SICN_CODEC_HEADER_BYTES + CTX_TABLE_BYTES;
-    if (dec) {
-        scan_body(nullptr, table, ns, w.offsets, nullptr, nullptr, WCAP, w.meta + 3, nullptr, 0u, (w.meta[0] & 0x100u) != 0);
-        return;
-    }
-    if (threadIdx.x == 0) status[2 * (size_t)blockIdx.x] = ctx_enc_verdict(w.meta, w.hist);
-    scan_body(w.lens, nullptr, ns, w.offsets, table, im.slot + 40, 0xFFFFFFFFu, nullptr, status + 2 * (size_t)blockIdx.x + 1,
-              (uint32_t)(SICN_CODEC_HEADER_BYTES + CTX_TABLE_BYTES) + 4 * ns, false);
+    if (dec) return ctx_scan_body(im, nullptr, blockIdx.x, true);
+    if (threadIdx.x == 0) status[2 * (size_t)blockIdx.x] = ctx_enc_verdict(im.w.meta, im.w.hist);
+    ctx_scan_body(im, status, blockIdx.x, false);
 }
 
 __global__ __launch_bounds__(256) void k_ragged_ctx_compact(uint8_t *__restrict__ containers, uint8_t *__restrict__ workspace,
                                                             const CtxRow *__restrict__ rows, const uint32_t *__restrict__ stream_image)
 {
     const CtxRow r = load_row(rows, uni(stream_image[blockIdx.x]));
-    const CtxImage im = ctx_image(r, nullptr, nullptr, containers, workspace);
-    const uint32_t ns = r.g.nst[0] + r.g.nst[1];
-    compact_body(im.w.scratch, im.w.lens, im.w.offsets, im.slot + SICN_CODEC_HEADER_BYTES + CTX_TABLE_BYTES + 4 * (size_t)ns, WCAP,
-                 blockIdx.x - r.first_stream);
+    ctx_compact_body(ctx_image(r, nullptr, nullptr, containers, workspace), blockIdx.x - r.first_stream);
 }
 
 // one set per launch (anchors first): dec_image is the table of that set
@@ -141,20 +129,15 @@ __global__ __launch_bounds__(64) void k_ragged_ctx_finish_window(uint32_t *__res
                                                                  const CtxRow *__restrict__ rows, const CtxWinRow *__restrict__ wrows)
 {
     if (threadIdx.x) return;
-    const CtxImage im = ctx_image(load_row(rows, blockIdx.x), nullptr, nullptr, nullptr, workspace);
-    uint32_t err = im.w.meta[0];
-    if (im.w.meta[3]) err |= 32;                                              // a selected stream, or an entry of the length table
-    if (im.w.offsets[im.g.nst[0] + im.g.nst[1]] != im.w.meta[1]) err |= 64;   // the length table does not add up to the payload
-    status[2 * (size_t)blockIdx.x] = err;
-    status[2 * (size_t)blockIdx.x + 1] = wrows[blockIdx.x].symbols;
+    ctx_finish_window_body(ctx_image(load_row(rows, blockIdx.x), nullptr, nullptr, nullptr, workspace), status, blockIdx.x,
+                           wrows[blockIdx.x].symbols);
 }
 
 __global__ __launch_bounds__(64) void k_ragged_ctx_finish(uint32_t *__restrict__ status, uint8_t *__restrict__ workspace,
                                                           const CtxRow *__restrict__ rows)
 {
     if (threadIdx.x) return;
-    const CtxImage im = ctx_image(load_row(rows, blockIdx.x), nullptr, nullptr, nullptr, workspace);
-    dec_finish_body(im.w.meta, im.w.sums, im.w.offsets, status + 2 * (size_t)blockIdx.x, im.g.W * im.g.H * im.g.C, im.g.nst[0] + im.g.nst[1]);
+    ctx_finish_body(ctx_image(load_row(rows, blockIdx.x), nullptr, nullptr, nullptr, workspace), status, blockIdx.x);
 }
 
 // ---- the layout: pure host --------------------------------------------------------------------------------------------------

@@ -5,20 +5,21 @@
 // Two rANS forms.  Mode 3 ("rANS-W") is the wavefront form: a stream of up to 16384 symbols is coded by ONE WAVE, its 64 lanes holding
 // 64 interleaved rANS states that share one stream of 16-bit words (stages in k_codec_body.hpp).  Mode 2 is the first, lane-serial
 // form, kept for compatibility: streams of 1024 symbols, ONE LANE per stream, every lane writing its stream backwards into a
-// fixed-capacity scratch slot; k_scan (wavefront-level prefix scan) turns the sizes into offsets and k_compact copies the streams.
+// fixed-capacity scratch slot; k_rans_scan (wavefront-level prefix scan) turns the sizes into offsets and k_rans_compact copies the streams.
 //
-// Which entry point runs which launches (mode 3 has ONE host path per direction, the asynchronous pair):
+// Which entry point runs which launches (mode 3 has ONE host path per direction, the asynchronous pair; both of its forms hand every
+// kernel the same base pointers and one UniformBatch):
 //   sicn_codec_encode_batch_async[_sl]   up to SELF_SCAN_MAX streams per image, "self" form: k_stats (rows) -> k_ransw_encode (table,
-//                                        header and status made by the waves) -> k_compact_self;  above, or with no stream, "scan"
-//                                        form: k_clear_stats -> k_stats (atomics) -> k_enc_header -> k_ransw_encode -> k_scan -> k_compact
-//   sicn_codec_decode_batch_async[_sl]   self form: k_ransw_decode<BIGTAB> -> k_dec_finish_self;  scan form: k_dec_parse -> k_scan ->
+//                                        header and status made by the waves) -> k_compact_self;  above, or with no stream, "scan" form:
+//                                        k_clear_stats -> k_stats (atomics) -> k_enc_header -> k_ransw_encode -> k_ransw_scan -> k_enc_compact
+//   sicn_codec_decode_batch_async[_sl]   self form: k_ransw_decode<BIGTAB> -> k_dec_finish_self;  scan form: k_dec_parse -> k_ransw_scan ->
 //                                        k_ransw_decode<false> -> k_dec_finish
 //   sicn_codec_encode_batch, sicn_codec_encode(mode 3)   ransw_encode_sync: the asynchronous encoder + one read-back of the status
 //   sicn_codec_decode_batch, sicn_codec_decode(mode 3)   one header read-back (shape, stream length), then ransw_decode_sync: the
 //                                        asynchronous decoder + one read-back of the status
 //   sicn_codec_encode / _decode, modes 0 - 2   on the host's schedule: k_stats (atomics), host normalize(), k_pack7 / k_unpack7 or
-//                                        k_rans_encode -> k_scan -> k_compact / k_scan -> k_rans_decode, k_stats again for the checksum
-//   mode 4 (sicn_codec_ctx.inc)          its own kernels + k_clear_stats, k_stats (atomics), k_scan, k_compact, k_dec_finish
+//                                        k_rans_encode -> k_rans_scan -> k_rans_compact / k_rans_scan -> k_rans_decode, k_stats again
+//   mode 4 (sicn_codec_ctx.inc)          its own kernels (k_ctx_*) + k_clear_stats and k_stats (atomics) on the statistics block
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -44,18 +45,8 @@ static inline unsigned stats_blocks(uint32_t n) { return std::min((n / 16 + 255u
 
 // ---- kernels ----------------------------------------------------------------------------------
 // Batches: blockIdx.y = image.  The rANS-W kernels name their image by a UniformBatch (k_codec_body.hpp), the context coder's by a
-// CtxBatch (k_ctx_body.hpp); k_scan, k_compact, k_clear_stats, the header / parse / finish kernels of the scan form and mode 2 take
-// pointers into the latent tensor / the per-image workspace / the container slots that advance by the given byte strides.
-template <typename T>
-__device__ __forceinline__ T *img_ptr(T *p, size_t stride)
-{
-    return (T *)((uint8_t *)p + (size_t)blockIdx.y * stride);
-}
-template <typename T>
-__device__ __forceinline__ const T *img_ptr(const T *p, size_t stride)
-{
-    return (const T *)((const uint8_t *)p + (size_t)blockIdx.y * stride);
-}
+// CtxBatch (k_ctx_body.hpp): batch_row() makes the image's row, enc_image() / dec_image() / scan_image() / ctx_image() resolve it to
+// pointers, a stage gets the image and blockIdx.x.  Only mode 2, one image on the host's schedule, hands its kernels plain pointers.
 
 // A uniform batch on the host: image 0's row (its offsets are 0: the kernels get the base pointers) and the strides.
 // scan = the form without statistics rows (n_rows = 0).  stats_batch: all k_stats needs outside the rANS-W coder (atomic mode on
@@ -132,26 +123,30 @@ __global__ __launch_bounds__(256) void k_rans_encode(const uint8_t *__restrict__
     lens[st] = CAP - pos;
 }
 
-// Exclusive prefix sum of a length table, one workgroup of 1024 per image: scan_body (k_codec_body.hpp)
-__global__ __launch_bounds__(1024) void k_scan(const uint32_t *__restrict__ in_, const uint8_t *__restrict__ in_bytes_,
-                                               uint32_t n, uint32_t *__restrict__ out_, uint8_t *__restrict__ table_out_,
-                                               uint8_t *__restrict__ total_out_, size_t s_ws, size_t s_slot, uint32_t cap,
-                                               uint32_t *__restrict__ err_, uint32_t *__restrict__ status_bytes_ = nullptr,
-                                               uint32_t fixed_bytes = 0, const uint32_t *__restrict__ skip_meta_ = nullptr)
+// Mode 2.  Exclusive prefix sum of a length table by one workgroup of 1024, the arguments as scan_body (k_codec_body.hpp) names them:
+// the encoder scans `in` and writes the container's table and payload field, the decoder scans the container's `in_bytes` and has `err`
+__global__ __launch_bounds__(1024) void k_rans_scan(const uint32_t *__restrict__ in, const uint8_t *__restrict__ in_bytes, uint32_t n,
+                                                    uint32_t *__restrict__ out, uint8_t *__restrict__ table_out,
+                                                    uint8_t *__restrict__ total_out, uint32_t cap, uint32_t *__restrict__ err)
 {
-    // async decode: a slot the parse stage found shorter than its own fixed part (meta[0] & 0x100) is never read
-    const bool skip = skip_meta_ && (img_ptr(skip_meta_, s_ws)[0] & 0x100u);
-    scan_body(in_ ? img_ptr(in_, s_ws) : nullptr, in_bytes_ ? img_ptr(in_bytes_, s_slot) : nullptr, n, img_ptr(out_, s_ws),
-              table_out_ ? img_ptr(table_out_, s_slot) : nullptr, total_out_ ? img_ptr(total_out_, s_slot) : nullptr, cap,
-              err_ ? img_ptr(err_, s_ws) : nullptr, status_bytes_ ? status_bytes_ + 2 * blockIdx.y + 1 : nullptr, fixed_bytes, skip);
+    scan_body(in, in_bytes, n, out, table_out, total_out, cap, err, nullptr, 0u, false);
+}
+// one workgroup per stream: scratch tail -> payload
+__global__ __launch_bounds__(256) void k_rans_compact(const uint8_t *__restrict__ scratch, const uint32_t *__restrict__ lens,
+                                                      const uint32_t *__restrict__ offsets, uint8_t *__restrict__ payload)
+{
+    compact_body(scratch, lens, offsets, payload, CAP, blockIdx.x);
 }
 
-// one workgroup per stream: scratch tail -> payload
-__global__ __launch_bounds__(256) void k_compact(const uint8_t *__restrict__ scratch_, const uint32_t *__restrict__ lens_,
-                                                 const uint32_t *__restrict__ offsets_, uint8_t *__restrict__ payload_, uint32_t cap,
-                                                 size_t s_ws, size_t s_slot)
+// Mode 3, scan form: the scan of both directions (status: the encoder's; the decoder passes nullptr) and the encoder's compaction
+__global__ __launch_bounds__(1024) void k_ransw_scan(const uint8_t *__restrict__ containers, uint32_t *__restrict__ status,
+                                                     uint8_t *__restrict__ workspace, UniformBatch b, int dec)
 {
-    compact_body(img_ptr(scratch_, s_ws), img_ptr(lens_, s_ws), img_ptr(offsets_, s_ws), img_ptr(payload_, s_slot), cap, blockIdx.x);
+    ransw_scan_body(scan_image(batch_row(b), containers, nullptr, status, workspace, blockIdx.y), dec);
+}
+__global__ __launch_bounds__(256) void k_enc_compact(uint8_t *__restrict__ containers, uint8_t *__restrict__ workspace, UniformBatch b)
+{
+    enc_compact_body(scan_image(batch_row(b), containers, nullptr, nullptr, workspace, blockIdx.y), blockIdx.x);
 }
 
 // The same without a scan kernel in front (asynchronous encoder, up to SELF_SCAN_MAX streams per image): compact_self_body
@@ -223,86 +218,32 @@ __global__ __launch_bounds__(256) void k_unpack7(const uint8_t *__restrict__ in,
 
 
 // ---- asynchronous batch path: everything the host did between two synchronisations, on the device -----------
-// blockIdx.y = image everywhere; per-image workspace stride s_ws, container slot stride s_slot.
+// The other kernels of mode 3's scan form, one workgroup per image (blockIdx.y); the stages are in k_codec_body.hpp.
 
-__global__ __launch_bounds__(64) void k_clear_stats(uint32_t *__restrict__ hist_, size_t s_ws)
+// the statistics block at the head of an image's workspace block: the same in mode 3's layout and mode 4's, which passes a stats_batch()
+__global__ __launch_bounds__(64) void k_clear_stats(uint8_t *__restrict__ workspace, UniformBatch b)
 {
-    uint32_t *h = img_ptr(hist_, s_ws);
+    uint32_t *h = (uint32_t *)(workspace + batch_row(b).ws_off);
     for (uint32_t i = threadIdx.x; i < STATS_WORDS + 16; i += 64) h[i] = 0;
 }
-// Histogram -> 12-bit frequencies exactly as `normalize` / sicl_or_normalize do it (same floor, same "largest first,
-// lowest index on ties" correction walk), by one wave: lane l owns symbols 2l, 2l+1.  Then the container header and
-// frequency table.  status[0] = error flags (bit 0: symbol >= 128, bit 1: normalisation failed).
-__global__ __launch_bounds__(256) void k_enc_header(const uint32_t *__restrict__ hist_, const unsigned long long *__restrict__ sums_,
-                                                   uint16_t *__restrict__ freq_, uint8_t *__restrict__ out_, uint32_t *__restrict__ status_,
-                                                   uint32_t n, uint32_t ns, uint32_t lat_w, uint32_t lat_h, uint32_t lat_c,
-                                                   uint32_t img_w, uint32_t img_h, size_t s_ws, size_t s_slot, uint32_t wss)
+
+__global__ __launch_bounds__(64) void k_enc_header(uint8_t *__restrict__ containers, uint32_t *__restrict__ status,
+                                                   uint8_t *__restrict__ workspace, UniformBatch b)
 {
-    const uint32_t *hist = img_ptr(hist_, s_ws);
-    const unsigned long long *sums = img_ptr(sums_, s_ws);
-    uint16_t *freq = img_ptr(freq_, s_ws);
-    uint8_t *out = img_ptr(out_, s_slot);
-    uint32_t *status = status_ + 2 * blockIdx.y;
-    const int lane = threadIdx.x;
-    uint32_t err = 0;
-    const uint32_t hh[2] = {hist[2 * lane], hist[2 * lane + 1]};
-    if (hist[128 + lane] | hist[192 + lane]) err = 1;
-    uint32_t f[2];
-    err |= normalize_wave(hh, n, f, lane);
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) err |= (uint32_t)__shfl_xor((int)err, d);
-    if (err) f[0] = f[1] = 0;   // the encode kernel skips zero-frequency symbols: it stays memory-safe
-    freq[2 * lane] = (uint16_t)f[0];
-    freq[2 * lane + 1] = (uint16_t)f[1];
-    write_header_wave(out, f, sums[0], sums[1], n, ns, lat_w, lat_h, lat_c, img_w, img_h, wss, lane);
-    if (lane == 0) status[0] = err;
+    enc_header_body(scan_image(batch_row(b), containers, nullptr, status, workspace, blockIdx.y));
 }
 
-// Decoder front end: every header field against the shape the caller expects, the frequency table, and the sizes
-// against the bytes the caller vouches for.  meta[0] |= error bits, meta[1] = payload bytes the streams may use.
-__global__ __launch_bounds__(64) void k_dec_parse(const uint8_t *__restrict__ containers_, const uint32_t *__restrict__ valid_bytes_,
-                                                  uint32_t valid_stride, uint32_t *__restrict__ meta_, uint32_t n, uint32_t ns,
-                                                  uint32_t lat_w, uint32_t lat_h, uint32_t lat_c, size_t s_slot, size_t s_ws, uint32_t wss)
+__global__ __launch_bounds__(64) void k_dec_parse(const uint8_t *__restrict__ containers, const uint32_t *__restrict__ valid,
+                                                  uint8_t *__restrict__ workspace, UniformBatch b)
 {
-    const uint8_t *c = img_ptr(containers_, s_slot);
-    uint32_t *meta = img_ptr(meta_, s_ws);
-    const int lane = threadIdx.x;
-    const uint32_t valid = valid_bytes_ ? min(valid_bytes_[(size_t)blockIdx.y * valid_stride], (uint32_t)min(s_slot, (size_t)0xFFFFFFFFu))
-                                        : (uint32_t)min(s_slot, (size_t)0xFFFFFFFFu);
-    const size_t fixed = SICN_CODEC_HEADER_BYTES + 256 + 4 * (size_t)ns;
-    uint32_t err = 0;
-    clear_stats_in_parse(meta, lane);
-    if (valid < fixed) {   // nothing of this slot may be read
-        if (lane == 0) { meta[0] = 0x104u; meta[1] = 0; meta[2] = 0; meta[3] = 0; }
-        return;
-    }
-    auto rd32 = [&](int o) { return c[o] | ((uint32_t)c[o + 1] << 8) | ((uint32_t)c[o + 2] << 16) | ((uint32_t)c[o + 3] << 24); };
-    const uint32_t expect[10] = {0x4C434953u, 1u | ((uint32_t)SICN_CODEC_RANSW << 16), 0, 0, lat_w, lat_h, lat_c, n, ns, wss};
-    if (lane < 10 && lane != 2 && lane != 3 && rd32(4 * lane) != expect[lane]) err = 4;
-    uint32_t fsum = c[SICN_CODEC_HEADER_BYTES + 4 * lane] + ((uint32_t)c[SICN_CODEC_HEADER_BYTES + 4 * lane + 1] << 8) +
-                    c[SICN_CODEC_HEADER_BYTES + 4 * lane + 2] + ((uint32_t)c[SICN_CODEC_HEADER_BYTES + 4 * lane + 3] << 8);
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) fsum += __shfl_xor((int)fsum, d);
-    if (n && fsum != 4096) err |= 8;
-    const uint32_t pb = rd32(40);
-    if ((size_t)pb > (size_t)valid - fixed) err |= 16;
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) err |= (uint32_t)__shfl_xor((int)err, d);
-    if (lane == 0) {
-        meta[0] = err;
-        meta[1] = (err & 16) ? 0u : pb;
-        meta[2] = rd32(44);
-        meta[3] = 0;
-    }
+    dec_parse_body(scan_image(batch_row(b), containers, valid, nullptr, workspace, blockIdx.y));
 }
 
 // Decoder back end: stream-level errors, table total, checksum -> status {error, n_symbols}.
-__global__ __launch_bounds__(64) void k_dec_finish(const uint32_t *__restrict__ meta_, const unsigned long long *__restrict__ sums_,
-                                                   const uint32_t *__restrict__ offsets_, uint32_t *__restrict__ status_, uint32_t n,
-                                                   uint32_t ns, size_t s_ws)
+__global__ __launch_bounds__(64) void k_dec_finish(uint32_t *__restrict__ status, uint8_t *__restrict__ workspace, UniformBatch b)
 {
     if (threadIdx.x) return;
-    dec_finish_body(img_ptr(meta_, s_ws), img_ptr(sums_, s_ws), img_ptr(offsets_, s_ws), status_ + 2 * blockIdx.y, n, ns);
+    dec_finish_body(scan_image(batch_row(b), nullptr, nullptr, status, workspace, blockIdx.y));
 }
 
 // The asynchronous decoder's ONLY other kernel when the streams were decoded in self mode: dec_finish_self_body
@@ -605,9 +546,8 @@ extern "C" int sicn_codec_encode(int mode, const uint8_t *latent, uint32_t lat_w
         uint8_t *table = out + SICN_CODEC_HEADER_BYTES + 256;
         uint8_t *payload = table + 4 * (size_t)ns;
         if (ns) hipLaunchKernelGGL(k_rans_encode, dim3((ns + 255) / 256), dim3(256), 0, stream, latent, n, ns, w.freq, w.scratch, w.lens);
-        hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, stream, w.lens, (const uint8_t *)nullptr, ns, w.offsets, table, out + 40, (size_t)0, (size_t)0,
-                           0xFFFFFFFFu, (uint32_t *)nullptr);
-        if (ns) hipLaunchKernelGGL(k_compact, dim3(ns), dim3(256), 0, stream, w.scratch, w.lens, w.offsets, payload, CAP, (size_t)0, (size_t)0);
+        hipLaunchKernelGGL(k_rans_scan, dim3(1), dim3(1024), 0, stream, w.lens, nullptr, ns, w.offsets, table, out + 40, 0xFFFFFFFFu, nullptr);
+        if (ns) hipLaunchKernelGGL(k_rans_compact, dim3(ns), dim3(256), 0, stream, w.scratch, w.lens, w.offsets, payload);
         uint32_t payload_bytes = 0;
         HIP_TRY(hipMemcpyAsync(&payload_bytes, w.offsets + ns, 4, hipMemcpyDeviceToHost, stream));
         HIP_TRY(hipStreamSynchronize(stream));
@@ -666,8 +606,7 @@ extern "C" int sicn_codec_decode(const uint8_t *container, size_t bytes, uint8_t
             for (int s = 0; s < 128; s++) sum += get16(fb + 2 * s);
             if (sum != 4096) return SICN_EINVAL;
         }
-        hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, stream, (const uint32_t *)nullptr, table, ns, w.offsets,
-                           (uint8_t *)nullptr, (uint8_t *)nullptr, (size_t)0, (size_t)0, CAP, err);
+        hipLaunchKernelGGL(k_rans_scan, dim3(1), dim3(1024), 0, stream, nullptr, table, ns, w.offsets, nullptr, nullptr, CAP, err);
         uint32_t total = 0;
         HIP_TRY(hipMemcpyAsync(&total, w.offsets + ns, 4, hipMemcpyDeviceToHost, stream));
         HIP_TRY(hipStreamSynchronize(stream));
@@ -704,7 +643,7 @@ extern "C" int sicn_codec_encode_batch_async_sl(const uint8_t *latents, uint32_t
     const unsigned long long n64 = (unsigned long long)lat_w * lat_h * lat_c;
     if (!wstream_fits(n64, wss) || (n64 && !latents) || n_images > 65535) return SICN_EINVAL;
     if (n_images == 0) return SICN_OK;
-    const uint32_t n = (uint32_t)n64, ns = (n + wss - 1) / wss, wcap = wstream_cap(wss);
+    const uint32_t n = (uint32_t)n64, ns = (n + wss - 1) / wss;
     if (slot_bytes < sicn_codec_max_bytes_sl(n, wss) || (slot_bytes & 1)) return SICN_ENOSPC;
     const size_t ws1 = align_up(sicn_codec_workspace_bytes_sl(n, wss), 256);
     if (!workspace || workspace_bytes < ws1 * n_images) return SICN_ENOSPC;
@@ -722,20 +661,12 @@ extern "C" int sicn_codec_encode_batch_async_sl(const uint8_t *latents, uint32_t
         hipLaunchKernelGGL(k_compact_self, dim3(ns, n_images), dim3(256), 0, stream, out, status, ws, b);
         return hipGetLastError() == hipSuccess ? SICN_OK : SICN_ENODEV;
     }
-    Workspace w;
-    carve(w, workspace, ns, wcap);
-    uint8_t *table = out + SICN_CODEC_HEADER_BYTES + 256, *payload = table + 4 * (size_t)ns;
-    const uint32_t fixed = (uint32_t)(SICN_CODEC_HEADER_BYTES + 256 + 4 * (size_t)ns);
-    hipLaunchKernelGGL(k_clear_stats, dim3(1, n_images), dim3(64), 0, stream, w.hist, ws1);
+    hipLaunchKernelGGL(k_clear_stats, dim3(1, n_images), dim3(64), 0, stream, ws, b);
     if (n) hipLaunchKernelGGL(k_stats, dim3(stats_blocks(n), n_images), dim3(256), 0, stream, latents, ws, b);
-    hipLaunchKernelGGL(k_enc_header, dim3(1, n_images), dim3(64), 0, stream, w.hist, w.sums, w.freq, out, status, n, ns, lat_w,
-                       lat_h, lat_c, img_w, img_h, ws1, slot_bytes, wss);
+    hipLaunchKernelGGL(k_enc_header, dim3(1, n_images), dim3(64), 0, stream, out, status, ws, b);
     if (ns) hipLaunchKernelGGL(k_ransw_encode, dim3(ns, n_images), dim3(64), 0, stream, latents, out, status, ws, b);
-    hipLaunchKernelGGL(k_scan, dim3(1, n_images), dim3(1024), 0, stream, w.lens, (const uint8_t *)nullptr, ns, w.offsets, table,
-                       out + 40, ws1, slot_bytes, 0xFFFFFFFFu, (uint32_t *)nullptr, status, fixed);
-    if (ns)
-        hipLaunchKernelGGL(k_compact, dim3(ns, n_images), dim3(256), 0, stream, w.scratch, w.lens, w.offsets, payload, wcap, ws1,
-                           slot_bytes);
+    hipLaunchKernelGGL(k_ransw_scan, dim3(1, n_images), dim3(1024), 0, stream, out, status, ws, b, 0);
+    if (ns) hipLaunchKernelGGL(k_enc_compact, dim3(ns, n_images), dim3(256), 0, stream, out, ws, b);
     return hipGetLastError() == hipSuccess ? SICN_OK : SICN_ENODEV;
 }
 
@@ -782,18 +713,10 @@ extern "C" int sicn_codec_decode_batch_async_sl(const uint8_t *containers, size_
         hipLaunchKernelGGL(k_dec_finish_self, dim3(1, n_images), dim3(256), 0, stream, containers, valid, (uint32_t *)status_dev, ws, b);
         return hipGetLastError() == hipSuccess ? SICN_OK : SICN_ENODEV;
     }
-    Workspace w;
-    carve(w, workspace, ns, 0);
-    hipLaunchKernelGGL(k_dec_parse, dim3(1, n_images), dim3(64), 0, stream, containers,
-                       valid_dev_or_null ? &valid_dev_or_null->bytes : (const uint32_t *)nullptr, 2u, w.meta, n, ns, lat_w, lat_h,
-                       lat_c, slot_bytes, ws1, wss);
-    // a slot the parse stage rejected as too short is never read: its table counts as empty (ns_eff = 0 via meta[1] = 0 and
-    // the per-stream bound off + len <= payload bytes, so every stream of it flags an error and returns)
-    hipLaunchKernelGGL(k_scan, dim3(1, n_images), dim3(1024), 0, stream, (const uint32_t *)nullptr,
-                       containers + SICN_CODEC_HEADER_BYTES + 256, ns, w.offsets, (uint8_t *)nullptr, (uint8_t *)nullptr, ws1, slot_bytes,
-                       wstream_cap(wss), w.meta + 3, (uint32_t *)nullptr, 0u, (const uint32_t *)w.meta);
+    hipLaunchKernelGGL(k_dec_parse, dim3(1, n_images), dim3(64), 0, stream, containers, valid, ws, b);
+    hipLaunchKernelGGL(k_ransw_scan, dim3(1, n_images), dim3(1024), 0, stream, containers, (uint32_t *)nullptr, ws, b, 1);
     hipLaunchKernelGGL(k_ransw_decode<false>, dim3(ns, n_images), dim3(64), 0, stream, containers, valid, latents, ws, b);
-    hipLaunchKernelGGL(k_dec_finish, dim3(1, n_images), dim3(64), 0, stream, w.meta, w.sums, w.offsets, (uint32_t *)status_dev, n, ns, ws1);
+    hipLaunchKernelGGL(k_dec_finish, dim3(1, n_images), dim3(64), 0, stream, (uint32_t *)status_dev, ws, b);
     return hipGetLastError() == hipSuccess ? SICN_OK : SICN_ENODEV;
 }
 

@@ -2,7 +2,7 @@
 // class of a symbol given by the hyper-synthesis scale map and, for the non-anchor half of a checkerboard, by its already
 // coded anchor neighbours (specification: oracle/sicn_hyper_oracle.c; SURVEY.md §8f row 4; parity UNPINNED — the reference
 // has no coder, no hyperprior and no context model).  Textually included at the end of sicn_codec.hip (same translation
-// unit: it re-uses k_stats, k_scan, k_compact, k_clear_stats, the exact reciprocal divide and the status conventions).
+// unit: it re-uses k_clear_stats and k_stats on the statistics block, the exact reciprocal divide and the status conventions).
 //
 // Everything is asynchronous (device-side statistics / tables / validation, device status words), like the mode-3 pair.
 namespace {
@@ -50,6 +50,24 @@ __global__ __launch_bounds__(64) void k_ctx_parse(const uint8_t *__restrict__ co
     ctx_parse_body(ctx_image(batch_row(b), nullptr, nullptr, containers, workspace), valid, blockIdx.y);
 }
 
+// status: the encoder's (the decoder passes nullptr)
+__global__ __launch_bounds__(1024) void k_ctx_scan(uint8_t *__restrict__ containers, uint32_t *__restrict__ status,
+                                                   uint8_t *__restrict__ workspace, CtxBatch b, int dec)
+{
+    ctx_scan_body(ctx_image(batch_row(b), nullptr, nullptr, containers, workspace), status, blockIdx.y, dec);
+}
+
+__global__ __launch_bounds__(256) void k_ctx_compact(uint8_t *__restrict__ containers, uint8_t *__restrict__ workspace, CtxBatch b)
+{
+    ctx_compact_body(ctx_image(batch_row(b), nullptr, nullptr, containers, workspace), blockIdx.x);
+}
+
+__global__ __launch_bounds__(64) void k_ctx_finish(uint32_t *__restrict__ status, uint8_t *__restrict__ workspace, CtxBatch b)
+{
+    if (threadIdx.x) return;
+    ctx_finish_body(ctx_image(batch_row(b), nullptr, nullptr, nullptr, workspace), status, blockIdx.y);
+}
+
 }  // namespace
 
 extern "C" size_t sicn_codec_ctx_max_bytes(uint32_t lat_w, uint32_t lat_h, uint32_t lat_c)
@@ -95,21 +113,16 @@ extern "C" int sicn_codec_ctx_encode_batch_async(const uint8_t *latents, const u
     if (!workspace || workspace_bytes < ws1 * n_images) return SICN_ENOSPC;
     hipStream_t stream = (hipStream_t)hip_stream;
     uint8_t *ws = (uint8_t *)workspace;
-    CtxWorkspace w;   // image 0's block, for the shared bookkeeping kernels
-    ctx_carve(w, workspace, ns, WCAP);
     uint32_t *status = (uint32_t *)status_dev;
-    uint8_t *table = out + SICN_CODEC_HEADER_BYTES + CTX_TABLE_BYTES, *payload = table + 4 * (size_t)ns;
-    const uint32_t fixed = (uint32_t)(SICN_CODEC_HEADER_BYTES + CTX_TABLE_BYTES + 4 * (size_t)ns);
-    hipLaunchKernelGGL(k_clear_stats, dim3(1, n_images), dim3(64), 0, stream, w.hist, ws1);
-    HIP_TRY(hipMemset2DAsync(w.chist, ws1, 0, NCLS * 128 * 4, n_images, stream));
+    hipLaunchKernelGGL(k_clear_stats, dim3(1, n_images), dim3(64), 0, stream, ws, stats_batch(n, n, ws1));
+    HIP_TRY(hipMemset2DAsync(ws + ctx_chist_offset(), ws1, 0, NCLS * 128 * 4, n_images, stream));
     hipLaunchKernelGGL(k_stats, dim3(stats_blocks(n), n_images), dim3(256), 0, stream, latents, ws, stats_batch(n, n, ws1));
     hipLaunchKernelGGL(k_ctx_hist, dim3(b.row0.n_chunks, n_images), dim3(256), 0, stream, latents, scales, ws, b);
     hipLaunchKernelGGL(k_ctx_tables, dim3(1, n_images), dim3(1024), 0, stream, out, ws, b, 0);
     hipLaunchKernelGGL(k_ctx_enc_status, dim3(1, n_images), dim3(64), 0, stream, status, ws, b);
     hipLaunchKernelGGL(k_ctx_encode, dim3((ns + CTX_WPB - 1) / CTX_WPB, n_images), dim3(64 * CTX_WPB), 0, stream, latents, scales, ws, b);
-    hipLaunchKernelGGL(k_scan, dim3(1, n_images), dim3(1024), 0, stream, w.lens, (const uint8_t *)nullptr, ns, w.offsets, table,
-                       out + 40, ws1, slot_bytes, 0xFFFFFFFFu, (uint32_t *)nullptr, status, fixed);
-    hipLaunchKernelGGL(k_compact, dim3(ns, n_images), dim3(256), 0, stream, w.scratch, w.lens, w.offsets, payload, WCAP, ws1, slot_bytes);
+    hipLaunchKernelGGL(k_ctx_scan, dim3(1, n_images), dim3(1024), 0, stream, out, status, ws, b, 0);
+    hipLaunchKernelGGL(k_ctx_compact, dim3(ns, n_images), dim3(256), 0, stream, out, ws, b);
     return hipGetLastError() == hipSuccess ? SICN_OK : SICN_ENODEV;
 }
 
@@ -124,20 +137,15 @@ extern "C" int sicn_codec_ctx_decode_batch_async(const uint8_t *containers, size
     if (n_images == 0) return SICN_OK;
     if (((uintptr_t)latents | (uintptr_t)scales) & 3) return SICN_EINVAL;
     const CtxGeom &g = b.row0.g;
-    const uint32_t n = (uint32_t)b.s_lat, ns = g.nst[0] + g.nst[1];
+    const uint32_t n = (uint32_t)b.s_lat;
     const size_t ws1 = b.s_ws;
     if (!workspace || workspace_bytes < ws1 * n_images) return SICN_ENOSPC;
     hipStream_t stream = (hipStream_t)hip_stream;
     uint8_t *ws = (uint8_t *)workspace;
-    uint8_t *slots = const_cast<uint8_t *>(containers);   // the tables kernel writes containers in the encoder only
-    CtxWorkspace w;   // image 0's block, for the shared bookkeeping kernels
-    ctx_carve(w, workspace, ns, WCAP);
-    const uint8_t *table = containers + SICN_CODEC_HEADER_BYTES + CTX_TABLE_BYTES;
+    uint8_t *slots = const_cast<uint8_t *>(containers);   // the tables and scan kernels write containers in the encoder only
     hipLaunchKernelGGL(k_ctx_parse, dim3(1, n_images), dim3(64), 0, stream, containers, (const uint32_t *)valid_dev_or_null, ws, b);
     hipLaunchKernelGGL(k_ctx_tables, dim3(1, n_images), dim3(1024), 0, stream, slots, ws, b, 1);
-    hipLaunchKernelGGL(k_scan, dim3(1, n_images), dim3(1024), 0, stream, (const uint32_t *)nullptr, table, ns, w.offsets,
-                       (uint8_t *)nullptr, (uint8_t *)nullptr, ws1, slot_bytes, WCAP, w.meta + 3, (uint32_t *)nullptr, 0u,
-                       (const uint32_t *)w.meta);
+    hipLaunchKernelGGL(k_ctx_scan, dim3(1, n_images), dim3(1024), 0, stream, slots, (uint32_t *)nullptr, ws, b, 1);
     // a non-anchor's class reads its neighbours' bytes whatever they hold: start from zeros so that a rejected container
     // cannot make the result depend on what the buffer held before
     HIP_TRY(hipMemsetAsync(latents, 0, (size_t)n * n_images, stream));
@@ -147,6 +155,6 @@ extern "C" int sicn_codec_ctx_decode_batch_async(const uint8_t *containers, size
         hipLaunchKernelGGL(k_ctx_decode<1>, dim3((g.nst[1] + CTX_WPB_DEC - 1) / CTX_WPB_DEC, n_images), dim3(64 * CTX_WPB_DEC), 0, stream,
                            containers, scales, latents, ws, b);
     hipLaunchKernelGGL(k_stats, dim3(stats_blocks(n), n_images), dim3(256), 0, stream, latents, ws, stats_batch(n, n, ws1));
-    hipLaunchKernelGGL(k_dec_finish, dim3(1, n_images), dim3(64), 0, stream, w.meta, w.sums, w.offsets, (uint32_t *)status_dev, n, ns, ws1);
+    hipLaunchKernelGGL(k_ctx_finish, dim3(1, n_images), dim3(64), 0, stream, (uint32_t *)status_dev, ws, b);
     return hipGetLastError() == hipSuccess ? SICN_OK : SICN_ENODEV;
 }

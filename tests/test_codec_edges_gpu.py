@@ -159,13 +159,13 @@ def _hostile_cases(good, size):
       * k_ctx_tables reads the 4096 table bytes (inside the fixed part, skipped when parse said 0x100); a row whose sum is neither
         0 nor 4096 is replaced by zeros, so every cumulative value is <= 4096.  Its slot-table walk indexes cum[cls][sy + 1] with
         sy <= 127 because cum[cls][128] = 0xFFFF stops it; its stores go to workspace addresses that depend on class and lane only.
-      * k_scan reads the 8 bytes of the length table (inside the fixed part, skipped on 0x100), counts an entry above 33024 as 0, so the
+      * k_ctx_scan reads the 8 bytes of the length table (inside the fixed part, skipped on 0x100), counts an entry above 33024 as 0, so the
         32-bit sums cannot wrap, and writes offsets[0..2].
       * k_ctx_decode refuses a stream unless 256 <= len <= 33024, len and off even and off + len <= payload bytes (a 64-bit sum):
         every payload read is below fixed + payload <= valid.  The ring is indexed modulo 4096, the slot table with class * 4096 + 12
         bits, the frequency table with class * 128 + 7 bits; classes are masked to 4 bits.  Latent loads and stores use addresses
         made of the CALLER's W, H, C only — no header field, no decoded value.
-      * k_stats and k_dec_finish read the latent and the workspace."""
+      * k_stats and k_ctx_finish read the latent and the workspace."""
     head, tables, lens = ce.ctx_container_fields(good[:size].tobytes())
     pb = int(lens.sum())
     assert lens.size == 2 and pb == size - HOSTILE_FIXED

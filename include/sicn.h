@@ -202,6 +202,19 @@ size_t sicn_net_workspace_bytes(const sicn_net *net, int n_images);
 int sicn_net_forward(const sicn_net *net, int first_layer, int last_layer, const uint8_t *in,
                      uint8_t *out, int tap_layer, uint8_t *tap_out, int n_images, void *workspace,
                      size_t workspace_bytes, void *hip_stream);
+/* Live channels.  A net looks at its weights when it is made: an output channel of layer i that layer i + 1 multiplies by zero in
+ * every tap is not computed where layer i runs on the wide persistent kernels (128 -> 128, no sicn_gdn, not the call's last or
+ * tapped layer): those kernels then run 3 or 5 of their 8 accumulator columns of 16 channels, on weight images whose channels the
+ * net has permuted (it owns these copies; the caller's handles never change).  Bytes of intermediate tensors that no layer reads
+ * may be left as the workspace held them.  Results are the same bytes for any weights and any workspace content; dense
+ * weights run exactly what they ran before.  The per-layer entry points always compute every channel.
+ * Memory: a sicn_weights handle keeps its decoded weights and bias on the host as well (25 * IFM_CH * OFM_CH + OFM_CH bytes), for
+ * nets made of it later; a net whose weights allow skipping owns up to three permuted copies of a layer's handle (device images and
+ * host copy each: about 1.2 MB + 0.4 MB for a 128 -> 128 layer), made by sicn_net_create* and freed by sicn_net_free.
+ * sicn_debug_net_columns: what a call over [first_layer, last_layer] would do — per layer of the net the columns it computes
+ * (8 = all) and the output channels the call's next layer reads. */
+int sicn_debug_net_columns(const sicn_net *net, int first_layer, int last_layer, int tap_layer, int n_images, int32_t *columns,
+                           int32_t *live_outputs);
 /* eight_layers_net(in, out, numReps): the whole chain; latent_or_null receives layer 3's output. */
 int sicn_eight_layers_net(const sicn_net *net, const uint8_t *in, uint8_t *out,
                           uint8_t *latent_or_null, int n_images, void *workspace,

@@ -60,6 +60,7 @@ ABI = {
     "sicn_debug_plan": (_i, [_descp, _i, ctypes.POINTER(COptions), _i, ctypes.POINTER(ctypes.c_int32)]),
     "sicn_debug_xcd_item": (ctypes.c_longlong, [ctypes.c_longlong, ctypes.c_longlong, _i]),
     "sicn_debug_chip": (_i, [ctypes.POINTER(ctypes.c_int32)]),
+    "sicn_debug_net_columns": (_i, [_vp, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
 }
 
 

@@ -1,6 +1,7 @@
 // libsicn.so — C ABI (include/sicn.h): descriptor validation, weight ingestion from the
 // reference's FixedPointWeights tile format, kernel dispatch, layer chains with caller-provided
 // workspace, per-layer hipEvent timing.  Host code only; kernels live in k_*.hip.
+#include <array>
 #include <atomic>
 #include <cmath>
 #include <cstdio>
@@ -13,6 +14,7 @@
 
 #include "sicn_gdn_internal.h"
 #include "sicn_internal.h"
+#include "sicn_live.h"
 #include "sicn_weights_io.h"
 
 using namespace sicn;
@@ -196,6 +198,7 @@ struct LaunchArgs {
     const ChipGeom &chip;
     const sicn_gdn *gdn;       // the layer's activation, nullptr = the reference's ReLU
     unsigned long long *deal;
+    int columns;               // accumulator columns the wide family computes (sicn_live.h); 8: all
 };
 
 struct Family {
@@ -272,7 +275,8 @@ bool mfma_images(const int8_t *k, sicn_weights &w)
 }
 hipError_t mfma_launch(const LaunchArgs &a, bool *)
 {
-    return launch_mfma16(a.g, a.w, a.in, a.out, a.n_images, a.stream, a.in_layout, a.out_layout, a.o, a.chip, a.gdn == nullptr, a.deal);
+    return launch_mfma16(a.g, a.w, a.in, a.out, a.n_images, a.stream, a.in_layout, a.out_layout, a.o, a.chip, a.gdn == nullptr, a.deal,
+                         a.columns);
 }
 void mfma_plan(const LayerGeom &g, int n_images, const sicn_options &o, const ChipGeom &chip, int32_t out[12])
 {
@@ -347,6 +351,40 @@ extern "C" void sicn_weights_free(sicn_weights *w)
     delete w;
 }
 
+// a handle from decoded weights ([cout][25 cin]) and cout bias bytes: what sicn_weights_from_finn_tiles makes of its tiles, and what a
+// net makes of the permuted copies of its live-channel plan (sicn_live.h).  The handle keeps the host copies and never changes.
+static int weights_from_okc(int cin, int cout, int transposed, std::vector<int8_t> w_okc, const int8_t *bias, sicn_weights **out)
+{
+    sicn_weights *w = new (std::nothrow) sicn_weights();
+    if (!w) return SICN_ENOMEM;
+    w->cin = cin;
+    w->cout = cout;
+    w->transposed = transposed;
+    bool ok = upload(w_okc.data(), w_okc.size(), &w->d_w_okc);
+    // d_w_okc and the bias always (force_generic, and a layer whose family cannot store the lane before the ReLU, run on them);
+    // besides them the images of the family the shape runs on
+    try {
+        // bias, padded to a multiple of 16 bytes so kernels may read it with 16-byte loads
+        std::vector<int8_t> b(((size_t)cout + 15) / 16 * 16 + 16, 0);
+        for (int i = 0; i < cout; i++) b[i] = bias[i];
+        ok = ok && upload(b.data(), b.size(), &w->d_bias);
+        sicn_layer_desc d{};
+        d.IFM_CH = cin;
+        d.OFM_CH = cout;
+        d.transposed = transposed;
+        const Family &f = pick_family(d, sicn_options{});
+        if (ok && f.upload_images) ok = f.upload_images(w_okc.data(), *w);
+        w->h_bias.assign(bias, bias + cout);
+        w->h_w_okc = std::move(w_okc);
+    } catch (const std::bad_alloc &) { ok = false; }
+    if (!ok) {
+        sicn_weights_free(w);
+        return SICN_ENOMEM;
+    }
+    *out = w;
+    return SICN_OK;
+}
+
 extern "C" int sicn_weights_from_finn_tiles(const sicn_layer_desc *d, const void *m_weights, int word_bytes,
                                             const int8_t *bias, sicn_weights **out)
 {
@@ -363,31 +401,7 @@ extern "C" int sicn_weights_from_finn_tiles(const sicn_layer_desc *d, const void
         w_okc.resize((size_t)cout * kk);
     } catch (const std::bad_alloc &) { return SICN_ENOMEM; }
     decode_finn_tiles(m_weights, word_bytes, 4, d->SIMD, d->PE, d->W_TILES, kk, cout, w_okc.data());
-
-    sicn_weights *w = new (std::nothrow) sicn_weights();
-    if (!w) return SICN_ENOMEM;
-    *w = sicn_weights{};
-    w->cin = cin;
-    w->cout = cout;
-    w->transposed = d->transposed;
-    bool ok = upload(w_okc.data(), w_okc.size(), &w->d_w_okc);
-    {   // bias, padded to a multiple of 16 bytes so kernels may read it with 16-byte loads
-        std::vector<int8_t> b(((size_t)cout + 15) / 16 * 16 + 16, 0);
-        for (int i = 0; i < cout; i++) b[i] = bias[i];
-        ok = ok && upload(b.data(), b.size(), &w->d_bias);
-    }
-    // d_w_okc and the bias always (force_generic, and a layer whose family cannot store the lane before the ReLU, run on them);
-    // besides them the images of the family the shape runs on
-    try {
-        const Family &f = pick_family(*d, sicn_options{});
-        if (ok && f.upload_images) ok = f.upload_images(w_okc.data(), *w);
-    } catch (const std::bad_alloc &) { ok = false; }
-    if (!ok) {
-        sicn_weights_free(w);
-        return SICN_ENOMEM;
-    }
-    *out = w;
-    return SICN_OK;
+    return weights_from_okc(cin, cout, d->transposed, std::move(w_okc), bias, out);
 }
 
 // ---- single layers ------------------------------------------------------------------------------
@@ -409,7 +423,7 @@ static int link_layout(const sicn_layer_desc &p, const sicn_layer_desc &c, const
 // words in the workspace of a chain (launch_mfma16), or nullptr.
 static int run_layer(const sicn_layer_desc *d, const sicn_weights *w, const uint8_t *in, uint8_t *out,
                      int n_images, hipStream_t stream, int want_transposed, const sicn_options &o, int in_layout = 0,
-                     int out_layout = 0, const sicn_gdn *gdn = nullptr, unsigned long long *deal = nullptr)
+                     int out_layout = 0, const sicn_gdn *gdn = nullptr, unsigned long long *deal = nullptr, int columns = 8)
 {
     int rc = sicn_validate_desc(d);
     if (rc) return rc;
@@ -423,7 +437,7 @@ static int run_layer(const sicn_layer_desc *d, const sicn_weights *w, const uint
     ChipGeom chip;
     if ((rc = chip_geom(&chip)) != SICN_OK) return rc;   // no device, or not a gfx950 one
     bool act_done = false;
-    const LaunchArgs args{g, *w, in, out, n_images, stream, in_layout, out_layout, o, chip, gdn, deal};
+    const LaunchArgs args{g, *w, in, out, n_images, stream, in_layout, out_layout, o, chip, gdn, deal, columns};
     hipError_t e = layer_family(*d, o, gdn != nullptr).launch(args, &act_done);
     if (act_done) gdn = nullptr;
     if (e == hipSuccess && gdn) e = launch_gdn(*gdn, out, out_layout, d->OFM_ROW, d->OFM_COL, n_images, stream);
@@ -465,6 +479,11 @@ struct sicn_net {
     std::vector<const sicn_weights *> weights;
     std::vector<const sicn_gdn *> gdn;         // per layer, nullptr = the reference's ReLU
     sicn_options opt;                          // fixed at creation
+    // the live-channel plan (sicn_live.h): per layer what the next layer reads of it, and the handles of the permuted copies of its
+    // weights — derived[l][2 in + out], in / out = 1: the input channels arrive / the output channels leave in the order of the
+    // producing layer's plan ([0] stays nullptr: weights[l] itself).  Made at creation, owned by the net, never changed.
+    std::vector<live::Layer> live;
+    std::vector<std::array<sicn_weights *, 4>> derived;
     // profiling: the only state a launch changes.  One flat ring of event pairs; a forward call reserves the
     // slots of its layers with one atomic fetch_add, so calls on several streams / threads never share a slot.
     static constexpr int EV_RING = 8192;
@@ -488,6 +507,45 @@ extern "C" int sicn_net_create_opt(const sicn_layer_desc *descs, sicn_weights *c
                                    const sicn_options *opt, sicn_net **out)
 {
     return sicn_net_create_gdn(descs, weights, nullptr, n_layers, opt, out);
+}
+
+// The live-channel tables of a new net and the permuted copies of the weights they call for.  Layer l may skip accumulator columns
+// (live[l].nj < 8) when it is a 128 -> 128 layer without a GDN whose consumer has enough all-zero input channels; whether it does
+// is decided per call (sicn_net_forward).  May throw std::bad_alloc.
+static int make_live_plan(sicn_net *net)
+{
+    const size_t n = net->descs.size();
+    net->live.assign(n, live::Layer{});
+    net->derived.assign(n, std::array<sicn_weights *, 4>{});
+    for (size_t l = 0; l < n; l++) {
+        live::Layer &L = net->live[l];
+        const sicn_weights &w = *net->weights[l];
+        L.cin = w.cin;
+        L.cout = w.cout;
+        L.gdn = net->gdn[l] != nullptr;
+        if (!w.h_w_okc.empty()) L.in_mask = live::live_inputs(w.h_w_okc.data(), w.cin, w.cout);
+    }
+    live::make_tables(net->live, net->opt.force_generic != 0);
+    for (size_t l = 0; l < n; l++) {
+        const sicn_weights &w = *net->weights[l];
+        for (int v = 1; v < 4; v++) {
+            const bool in_p = (v & 2) != 0, out_p = (v & 1) != 0;
+            if ((in_p && !(l > 0 && net->live[l - 1].nj < live::COLS)) || (out_p && net->live[l].nj >= live::COLS)) continue;
+            std::vector<int8_t> okc = w.h_w_okc, bias = w.h_bias;
+            if (in_p) {
+                std::vector<int8_t> t(okc.size());
+                live::permute_inputs(okc.data(), w.cout, net->live[l - 1].p, t.data());
+                okc.swap(t);
+            }
+            if (out_p) {
+                std::vector<int8_t> t(okc.size());
+                live::permute_outputs(okc.data(), w.h_bias.data(), w.cin, net->live[l].p, t.data(), bias.data());
+                okc.swap(t);
+            }
+            if (int rc = weights_from_okc(w.cin, w.cout, w.transposed, std::move(okc), bias.data(), &net->derived[l][(size_t)v])) return rc;
+        }
+    }
+    return SICN_OK;
 }
 
 extern "C" int sicn_net_create_gdn(const sicn_layer_desc *descs, sicn_weights *const *weights, const sicn_gdn *const *gdn,
@@ -517,8 +575,12 @@ extern "C" int sicn_net_create_gdn(const sicn_layer_desc *descs, sicn_weights *c
         net->gdn.assign((size_t)n_layers, nullptr);
         if (gdn) net->gdn.assign(gdn, gdn + n_layers);
         net->opt = o;
+        if (int rc = make_live_plan(net)) {
+            sicn_net_free(net);
+            return rc;
+        }
     } catch (const std::exception &) {
-        delete net;
+        sicn_net_free(net);
         return SICN_ENOMEM;
     }
     *out = net;
@@ -528,6 +590,8 @@ extern "C" int sicn_net_create_gdn(const sicn_layer_desc *descs, sicn_weights *c
 extern "C" void sicn_net_free(sicn_net *net)
 {
     if (!net) return;
+    for (auto &v : net->derived)
+        for (sicn_weights *w : v) sicn_weights_free(w);
     for (hipEvent_t e : net->ev_begin) (void)hipEventDestroy(e);
     for (hipEvent_t e : net->ev_end) (void)hipEventDestroy(e);
     delete net;
@@ -550,6 +614,34 @@ extern "C" size_t sicn_net_workspace_bytes(const sicn_net *net, int n_images)
     return 2 * pingpong_slot_bytes(net, n_images) + deal_bytes(net);
 }
 
+// the accumulator columns layer l computes in a call over [first, last]: fewer than all where the net's tables allow it (make_live_plan)
+// and this call runs the layer on the wide family, in the middle of the chain, untapped
+static int call_columns(const sicn_net *net, int l, int first, int last, int tap_layer, int n_images, const ChipGeom &chip)
+{
+    if (net->live[(size_t)l].nj >= live::COLS) return live::COLS;
+    const Family &f = layer_family(net->descs[(size_t)l], net->opt, false);
+    const bool wide = (f.kind == KK_MFMA_CONV || f.kind == KK_MFMA_DECONV) &&
+                      plan_mfma(geom_of(net->descs[(size_t)l]), n_images, net->opt, chip).family == 2;
+    return live::columns(net->live, l, first, last, tap_layer, wide);
+}
+
+// what a call would do, for tests: per layer of the net the columns computed (8 outside [first, last]) and the output channels that
+// the call's next layer reads
+extern "C" int sicn_debug_net_columns(const sicn_net *net, int first, int last, int tap_layer, int n_images, int32_t *columns,
+                                      int32_t *live_outputs)
+{
+    if (!net || !columns || !live_outputs || n_images <= 0) return SICN_EINVAL;
+    const int n_layers = (int)net->descs.size();
+    if (first < 0 || last >= n_layers || first > last) return SICN_EINVAL;
+    ChipGeom chip;
+    if (int rc = chip_geom(&chip)) return rc;
+    for (int l = 0; l < n_layers; l++) {
+        columns[l] = call_columns(net, l, first, last, tap_layer, n_images, chip);
+        live_outputs[l] = live::live_outputs(net->live, l, first, last, tap_layer);
+    }
+    return SICN_OK;
+}
+
 extern "C" int sicn_net_forward(const sicn_net *net, int first, int last, const uint8_t *in, uint8_t *out,
                                 int tap_layer, uint8_t *tap_out, int n_images, void *workspace,
                                 size_t workspace_bytes, void *hip_stream)
@@ -564,9 +656,9 @@ extern "C" int sicn_net_forward(const sicn_net *net, int first, int last, const 
     hipStream_t stream = (hipStream_t)hip_stream;
     uint8_t *pp[2] = {(uint8_t *)workspace, (uint8_t *)workspace + slot};
     unsigned long long *deal_base = nullptr;   // the tile-deal words of this call's layers, zeroed below (a smaller / absent workspace: static deal)
+    ChipGeom chip;
+    if (int rc = chip_geom(&chip)) return rc;
     {
-        ChipGeom chip;
-        if (int rc = chip_geom(&chip)) return rc;
         // does a layer of this call deal tiles dynamically?  (small inputs never do: no zeroing launch in front of them)
         bool any_deal = false;
         for (int l = first; l <= last && !any_deal; l++) {
@@ -588,7 +680,14 @@ extern "C" int sicn_net_forward(const sicn_net *net, int first, int last, const 
         const int at = net->ev_next.fetch_add(need, std::memory_order_relaxed);
         if (at + need <= sicn_net::EV_RING) slot0 = at;   // ring full: this call is not timed
     }
+    int cols_before = live::COLS;   // the columns the previous layer of this call computed: fewer than all = its channels are permuted
     for (int l = first; l <= last; l++) {
+        // the live-channel plan of this call: a layer on the wide family computes only the columns the next layer reads (sicn_live.h)
+        const int cols = call_columns(net, l, first, last, tap_layer, n_images, chip);
+        const int variant = 2 * (cols_before < live::COLS) + (cols < live::COLS);
+        const sicn_weights *wl = variant ? net->derived[l][(size_t)variant] : net->weights[l];
+        if (!wl) return SICN_EINVAL;
+        cols_before = cols;
         // a tapped layer (the latent) is written straight into the caller's buffer and the next layer reads it there: no copy
         // (round 3 copied it device-to-device behind the layer: 4.8 us per forward pass on small inputs, 15 us on 8 x 4K)
         uint8_t *dst = (l == last) ? out : (l == tap_layer ? tap_out : pp[(l - first) & 1]);
@@ -601,8 +700,8 @@ extern "C" int sicn_net_forward(const sicn_net *net, int first, int last, const 
             net->ev_layer[ev].store(-1, std::memory_order_relaxed);   // becomes l once both events are recorded
             if (hipEventRecord(net->ev_begin[ev], stream) != hipSuccess) return SICN_ENODEV;
         }
-        int rc = run_layer(&net->descs[l], net->weights[l], cur, dst, n_images, stream, -1, net->opt, cur_layout, out_layout,
-                           net->gdn[l], deal_base ? deal_base + (size_t)l * DEAL_WORDS : nullptr);
+        int rc = run_layer(&net->descs[l], wl, cur, dst, n_images, stream, -1, net->opt, cur_layout, out_layout,
+                           net->gdn[l], deal_base ? deal_base + (size_t)l * DEAL_WORDS : nullptr, cols);
         if (rc) return rc;
         if (ev >= 0) {
             if (hipEventRecord(net->ev_end[ev], stream) != hipSuccess) return SICN_ENODEV;

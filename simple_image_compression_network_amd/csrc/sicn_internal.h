@@ -4,6 +4,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <vector>
+
 #include "../../include/sicn.h"
 #include "sicn_plan.h"
 
@@ -45,6 +47,8 @@ struct sicn_weights {
     int8_t *d_w_l0g;       // layer 0, 128 channels: the A-operand image of the kernel that applies a GDN before its store (k_l0g.hip)
     int8_t *d_w_l7;
     int8_t *d_w_any;       // the channel-generic MFMA kernels' weight image (k_mfma16c.hip: pack_any), or nullptr when they do not serve the shape
+    // what d_w_okc and d_bias were uploaded from: a net's live-channel plan (sicn_live.h) reads them and derives permuted images
+    std::vector<int8_t> h_w_okc, h_bias;
 };
 
 namespace sicn {
@@ -83,14 +87,18 @@ hipError_t launch_crop_nhwc(const uint8_t *src, uint8_t *dst, int n, int hs, int
 // deal: DEAL_WORDS zeroed words for the wide persistent kernels' tile deal (k_mfma16x.hip: DealX), or nullptr (static deal)
 hipError_t launch_mfma16(const LayerGeom &g, const sicn_weights &w, const uint8_t *in, uint8_t *out,
                          int n_images, hipStream_t stream, int in_layout, int out_layout, const sicn_options &o, const ChipGeom &chip,
-                         bool relu = true, unsigned long long *deal = nullptr);
+                         bool relu = true, unsigned long long *deal = nullptr, int columns = 8);
 // k_mfma16x.hip: the wide persistent form — one workgroup of 4 waves per CU walks through 16 x 32-position tiles, 128 x 128 outputs
 // per wave (accumulators in AGPRs, one wave per SIMD); grid_cap > 0 limits the number of workgroups (tests)
 bool wide_supported(const LayerGeom &g);
 size_t mfma16x_deconv_stream_bytes(int cin, int cout);   // 0 where the wide deconv does not exist
 void pack_mfma16x_deconv_stream(const int8_t *w_okc, int cin, int cout, int8_t *dst);
 hipError_t launch_wide(const LayerGeom &g, const sicn_weights &w, const uint8_t *in, uint8_t *out, int n_images, hipStream_t stream,
-                       int in_layout, int out_layout, bool relu, int grid_cap, const ChipGeom &chip, unsigned long long *deal = nullptr);
+                       int in_layout, int out_layout, bool relu, int grid_cap, const ChipGeom &chip, unsigned long long *deal = nullptr,
+                       int columns = 8);
+// k_mfma16x_live.hip: the same kernels with the first `columns` (3 | 5) of the 8 accumulator columns only, for weights permuted by the
+// net's live-channel plan (sicn_live.h); nullptr for a width that is not built
+const void *wide_live_kernel(int transposed, bool nt_store, int columns);
 // k_mfma16p.hip: the software-pipelined conv / deconv kernels (tile_x = 16 | 32)
 bool pipelined_supported(const LayerGeom &g, int tile_x);
 hipError_t launch_pipelined(const LayerGeom &g, const sicn_weights &w, const uint8_t *in, uint8_t *out, int n_images,

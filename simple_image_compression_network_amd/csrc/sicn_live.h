@@ -1,0 +1,136 @@
+// The live-channel plan of a layer chain (host C++ only: no HIP, no device; tests/cpp/live_plan_check.cpp compiles it alone).
+//
+// A layer's output channel that its only consumer multiplies by zero in every tap need not be computed.  The wide persistent
+// kernels (k_mfma16x.hip, k_mfma16x_live.hip) hold a 16 x 32-position tile as 8 accumulator COLUMNS of 16 channels; column
+// j = 4 J + d holds the physical channel positions 64 J + 16 g + 4 d + r (g, r = 0 .. 3).  A layer that computes only NJ columns
+// writes logical channel c at the physical position p(c):
+//   * the live channels, in ascending order, go to the positions of columns 0 .. NJ - 1, in ascending order;
+//   * the dead channels, in ascending order, go to the positions that remain (some may land in a computed column: harmless).
+// The layer's own weight rows and bias are packed in that order, the consumer's K index is permuted by the same p: both are copies
+// of w_okc ([cout][25 cin], k = tap cin + c) with rows or columns moved, which then go through the ordinary packers.  The bytes at
+// positions nobody computes are undefined; they meet zero weights, and integer arithmetic makes that exact.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#include <vector>
+
+namespace sicn {
+namespace live {
+
+constexpr int CH = 128;                      // channels of the wide family (128 -> 128)
+constexpr int COLS = 8;                      // accumulator columns of 16 channels
+constexpr int WIDTHS[] = {3, 5, 8};          // the column counts kernels are built for (8: k_mfma16x.hip, today's kernels)
+
+constexpr int column_of(int pos) { return 4 * (pos >> 6) + ((pos >> 2) & 3); }
+
+// mask[c] = 1 where input channel c of w_okc [cout][25 cin] has a non-zero weight in any tap of any output row
+inline std::vector<uint8_t> live_inputs(const int8_t *w_okc, int cin, int cout)
+{
+    std::vector<uint8_t> m((size_t)cin, 0);
+    const size_t kk = (size_t)25 * cin;
+    for (int o = 0; o < cout; o++)
+        for (int t = 0; t < 25; t++) {
+            const int8_t *src = w_okc + (size_t)o * kk + (size_t)t * cin;
+            for (int c = 0; c < cin; c++) m[(size_t)c] |= (uint8_t)(src[c] != 0);
+        }
+    return m;
+}
+
+inline int count_live(const std::vector<uint8_t> &m)
+{
+    int n = 0;
+    for (uint8_t v : m) n += v != 0;
+    return n;
+}
+
+// live channels -> whole columns -> the next width that is built
+inline int built_width(int n_live)
+{
+    const int cols = (n_live + 15) / 16;
+    for (int w : WIDTHS)
+        if (cols <= w) return w;
+    return COLS;
+}
+
+// p[c] = physical position of logical channel c for a layer that computes columns 0 .. nj - 1 (mask: CH entries)
+inline std::vector<int> permutation(const std::vector<uint8_t> &mask, int nj)
+{
+    std::vector<int> head, tail, p((size_t)CH, -1);
+    for (int pos = 0; pos < CH; pos++) (column_of(pos) < nj ? head : tail).push_back(pos);
+    head.insert(head.end(), tail.begin(), tail.end());   // computed positions first, each part ascending
+    size_t at = 0;
+    for (int pass = 0; pass < 2; pass++)
+        for (int c = 0; c < CH; c++)
+            if ((mask[(size_t)c] != 0) == (pass == 0)) p[(size_t)c] = head[at++];
+    return p;
+}
+
+// the producer's side: row p[c] of dst = row c of w_okc, bias likewise (cout = CH rows of 25 cin)
+inline void permute_outputs(const int8_t *w_okc, const int8_t *bias, int cin, const std::vector<int> &p, int8_t *w_dst, int8_t *b_dst)
+{
+    const size_t kk = (size_t)25 * cin;
+    for (int c = 0; c < CH; c++) {
+        const int8_t *src = w_okc + (size_t)c * kk;
+        int8_t *dst = w_dst + (size_t)p[(size_t)c] * kk;
+        for (size_t k = 0; k < kk; k++) dst[k] = src[k];
+        b_dst[p[(size_t)c]] = bias[c];
+    }
+}
+
+// the consumer's side: dst[o][tap CH + p[c]] = w_okc[o][tap CH + c] (cin = CH)
+inline void permute_inputs(const int8_t *w_okc, int cout, const std::vector<int> &p, int8_t *w_dst)
+{
+    const size_t kk = (size_t)25 * CH;
+    for (int o = 0; o < cout; o++)
+        for (int t = 0; t < 25; t++) {
+            const int8_t *src = w_okc + (size_t)o * kk + (size_t)t * CH;
+            int8_t *dst = w_dst + (size_t)o * kk + (size_t)t * CH;
+            for (int c = 0; c < CH; c++) dst[p[(size_t)c]] = src[c];
+        }
+}
+
+// ---- the plan ---------------------------------------------------------------------------------------------------------------
+// What is known of layer i when the net is made (Layer), and what one call makes of it (columns).
+struct Layer {
+    int cin = 0, cout = 0;
+    bool gdn = false;             // carries a sicn_gdn: the activation mixes channels, every channel is needed
+    std::vector<uint8_t> in_mask; // live_inputs of its own weights
+    // made by make_tables():
+    int live_out = 0;             // output channels the chain needs from it (cout: all)
+    int nj = COLS;                // built width for them; COLS where the layer can never skip a column
+    std::vector<int> p;           // nj < COLS: where it writes its channels
+};
+
+// creation: layer i + 1 is layer i's only consumer.  force_generic: no layer runs on the wide family.
+inline void make_tables(std::vector<Layer> &L, bool force_generic)
+{
+    const size_t n = L.size();
+    for (size_t i = 0; i < n; i++) {
+        Layer &l = L[i];
+        l.live_out = l.cout;
+        l.nj = COLS;
+        l.p.clear();
+        if (i + 1 < n && !l.gdn && (int)L[i + 1].in_mask.size() == l.cout) l.live_out = count_live(L[i + 1].in_mask);
+        const bool wide_shape = l.cin == CH && l.cout == CH;
+        if (wide_shape && !l.gdn && !force_generic && i + 1 < n) l.nj = built_width(l.live_out);
+        if (l.nj < COLS) l.p = permutation(L[i + 1].in_mask, l.nj);
+    }
+}
+
+// one call: the output channels of layer i that somebody reads (the last layer's and the tapped layer's leave the chain)
+inline int live_outputs(const std::vector<Layer> &L, int i, int first, int last, int tap_layer)
+{
+    if (i < first || i >= last || i == tap_layer) return L[(size_t)i].cout;
+    return L[(size_t)i].live_out;
+}
+
+// one call: the columns layer i computes.  wide: the layer is planned onto the wide family for this call (plan_mfma family 2).
+inline int columns(const std::vector<Layer> &L, int i, int first, int last, int tap_layer, bool wide)
+{
+    if (i < first || i >= last || i == tap_layer || !wide) return COLS;
+    return L[(size_t)i].nj;
+}
+
+}  // namespace live
+}  // namespace sicn

@@ -208,13 +208,18 @@ int sicn_net_forward(const sicn_net *net, int first_layer, int last_layer, const
  * net has permuted (it owns these copies; the caller's handles never change).  Bytes of intermediate tensors that no layer reads
  * may be left as the workspace held them.  Results are the same bytes for any weights and any workspace content; dense
  * weights run exactly what they ran before.  The per-layer entry points always compute every channel.
+ * The last layer of the net (deconv 128 -> 3) reads only the first 64-channel half of its input where the layer in front of it ran
+ * at most 4 columns in that call and hands its output over in an internal layout: its live channels all sit in that half.
  * Memory: a sicn_weights handle keeps its decoded weights and bias on the host as well (25 * IFM_CH * OFM_CH + OFM_CH bytes), for
- * nets made of it later; a net whose weights allow skipping owns up to three permuted copies of a layer's handle (device images and
+ * nets made of it later, and a handle of the 128 -> 3 deconv keeps two device images (12 KB for both halves, 6 KB for the first); a net whose weights allow skipping owns up to three permuted copies of a layer's handle (device images and
  * host copy each: about 1.2 MB + 0.4 MB for a 128 -> 128 layer), made by sicn_net_create* and freed by sicn_net_free.
  * sicn_debug_net_columns: what a call over [first_layer, last_layer] would do — per layer of the net the columns it computes
- * (8 = all) and the output channels the call's next layer reads. */
+ * (8 = all) and the output channels the call's next layer reads.
+ * sicn_debug_net_input_halves: per layer of the net the 64-channel halves of its input that the same call would read: 1 or 2 for a
+ * layer on "l7_rgb", 2 for every other layer (and outside [first_layer, last_layer]). */
 int sicn_debug_net_columns(const sicn_net *net, int first_layer, int last_layer, int tap_layer, int n_images, int32_t *columns,
                            int32_t *live_outputs);
+int sicn_debug_net_input_halves(const sicn_net *net, int first_layer, int last_layer, int tap_layer, int n_images, int32_t *halves);
 /* eight_layers_net(in, out, numReps): the whole chain; latent_or_null receives layer 3's output. */
 int sicn_eight_layers_net(const sicn_net *net, const uint8_t *in, uint8_t *out,
                           uint8_t *latent_or_null, int n_images, void *workspace,

@@ -61,6 +61,7 @@ ABI = {
     "sicn_debug_xcd_item": (ctypes.c_longlong, [ctypes.c_longlong, ctypes.c_longlong, _i]),
     "sicn_debug_chip": (_i, [ctypes.POINTER(ctypes.c_int32)]),
     "sicn_debug_net_columns": (_i, [_vp, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
+    "sicn_debug_net_input_halves": (_i, [_vp, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_int32)]),
 }
 
 

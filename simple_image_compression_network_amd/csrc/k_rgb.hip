@@ -229,6 +229,8 @@ hipError_t launch_l0(const LayerGeom &g, const sicn_weights &w, const uint8_t *i
 //   * RGB output is transposed through a 384-byte per-wave LDS staging tile and stored as dwords
 //     through a buffer descriptor (masked lanes = out of range), so a step always issues exactly
 //     two stores and the wait for the prefetched rows is a counted vmcnt that leaves them in flight.
+//   * k_l7<KH>: KH = 2 is all of the above.  k_l7<1> keeps region 0 only (L7Form below): half the requests, fragment reads and
+//     MFMAs, for an input whose channels 64 .. 127 nobody wrote and no weight reads (launch_l7, halves = 1).
 // =============================================================================================
 constexpr int L7_AUX = 0;                                // cache policy of the input stream (2 = nt)
 constexpr int L7_PITCH = 36;                             // positions per window row (34 used)
@@ -242,28 +244,49 @@ constexpr int L7_STAGE = 2 * 192;                        // 2 output rows x 64 p
 constexpr int L7_X1 = 2 * 256;                           // exchange, per wave: [position tile 2][lane 64] dwords = the rows r < 3 of M tile 1
 constexpr int L7_X2 = 2 * 128;                           // exchange, per wave: [position tile 2][px 2][16 positions] dwords = the ky = 4 bytes
 constexpr int L7_XCH = 5 * L7_X1 + 4 * L7_X2;            // wave 3's L7_X1 record twice (step parity)
-constexpr int L7_LDS = 2 * L7_REGION + 4 * L7_STAGE + 1024 + L7_XCH;
-constexpr int L7_KSTEPS = 6, L7_MTILES = 2;              // W'': [M tile][K step = 2 dx + half][row 16][64 B]
+constexpr int L7_MTILES = 2;
+// Everything that follows from the number KH of live regions (64-channel halves of the input that are read at all).  KH = 2 is the
+// kernel as described above.  KH = 1: the producing layer left its channels in the first half only (a wide layer of at most 4
+// accumulator columns, sicn_live.h: column_of(pos) < 4 <=> pos < 64) and stored nothing into the planes of the groups 2, 3, whose
+// weights are all zero: the ring is region 0 alone, a step requests 9 pieces, reads 3 fragments per position tile and runs 6 MFMAs.
+template <int KH>
+struct L7Form {
+    static_assert(KH == 1 || KH == 2, "one or two 64-channel halves");
+    static constexpr int LDS = KH * L7_REGION + 4 * L7_STAGE + 1024 + L7_XCH;
+    static constexpr int KSTEPS = 3 * KH;                                   // W'': [M tile][K step = KH dx + half][row 16][64 B]
+    static constexpr int PRO_N = (KH * 2 * L7_STEP_PIECES + 3) / 4;         // LDS-DMA instructions per wave: prologue (9 | 5)
+    static constexpr int STEP_N = (KH * L7_STEP_PIECES + 3) / 4;            // and per step (5 | 3); the counted waits follow from it
+    // the launch bound.  For KH = 1 it decides nothing: the kernel takes 92 VGPRs and 29 696 B of LDS, so five workgroups fit a CU
+    // whatever is written here, and 3, 4 and 5 compile to the same instructions (profiles/l7_live_half_resource_usage.txt);
+    // how many are resident is plan_l7's cut, just under two per CU
+    static constexpr int WGS = L7_WGS;
+};
 static_assert(L7_ROWS * L7_PITCH % 16 == 0 && L7_RING_POS >= (4 * L7_AHEAD + 6) * L7_PITCH, "ring geometry");
-static_assert(L7_WGS * L7_LDS <= 160 * 1024 && L7_XCH <= 4096, "three workgroups per CU");
+static_assert(L7Form<2>::WGS * L7Form<2>::LDS <= 160 * 1024 && L7Form<1>::WGS * L7Form<1>::LDS <= 160 * 1024 && L7_XCH <= 4096,
+              "workgroups per CU");
+static_assert(L7Form<2>::LDS == 53248 && L7Form<2>::PRO_N == 9 && L7Form<2>::STEP_N == 5, "KH = 2 is the kernel it was");
 
 // LDS-DMA pieces `first + 4i` (i < n) of a run of window rows: piece j < npieces covers region
 // j / per_region, positions (j % per_region)*16 .. +15 of the run; row 0 of the run is input row iy0
 // and lands at ring piece slot pslot0.  Only rows iy_min <= iy < iy_max (inside the image) are
 // fetched, the rest is zero fill.  Every wave issues exactly N loads (the vmcnt bookkeeping of the
 // caller depends on it): a piece index past the run becomes an out-of-range load into `scratch`.
-template <int N>
+// KH = 1: only region 0 exists, and stored chunk s of position P holds chunk c2 = 2*((s&1) ^ ((P>>2)&1)) + (s>>1), the inverse of
+// what the readers of l7_body compute; lanes s and s^2 of a position fetch the two halves of one contiguous 32-byte group entry.
+template <int N, int KH>
 __device__ __forceinline__ void l7_load_rows(uint8_t *patch, uint8_t *scratch, const uint8_t *in_img, int in_img_bytes, int w,
                                              int lane, int per_region, int iy0, int iy_min, int iy_max, int pslot0, int X0,
                                              int IW, const TensorMap &tm)
 {
     __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)in_img, 0, in_img_bytes, 0x00020000);
-    const int c2 = (lane & 3) ^ ((lane >> 4) & 3);   // stored chunk (lane&3) of position P holds c2 ^ ((P>>2)&3)
+    // KH = 2: stored chunk (lane&3) of position P holds c2 ^ ((P>>2)&3); a piece starts at a multiple of 16 positions, so
+    // (P>>2)&3 = (lane>>4)&3
+    const int c2 = KH == 2 ? (lane & 3) ^ ((lane >> 4) & 3) : 2 * ((lane & 1) ^ ((lane >> 4) & 1)) + ((lane >> 1) & 1);
 #pragma unroll
     for (int i = 0; i < N; i++) {
         const int j = w + 4 * i;
-        const bool real = j < 2 * per_region;   // wave-uniform
-        const int region = j >= per_region ? 1 : 0, kk = j - region * per_region;
+        const bool real = j < KH * per_region;   // wave-uniform
+        const int region = (KH == 2 && j >= per_region) ? 1 : 0, kk = j - region * per_region;
         const int q = kk * 16 + (lane >> 2);
         const int row = q / L7_PITCH, tx = q - row * L7_PITCH;
         const int iy = iy0 + row, ix = X0 - 1 + tx;
@@ -278,6 +301,7 @@ __device__ __forceinline__ void l7_load_rows(uint8_t *patch, uint8_t *scratch, c
     }
 }
 
+template <int KH>
 __device__ __forceinline__ void l7_body(const uint8_t *__restrict__ in, uint8_t *__restrict__ out, const int8_t *__restrict__ w_l7,
                                         const int8_t *__restrict__ bias, int IW, int IH, int OW, int OH, int steps_y, int y_chunks,
                                         int tiles_x, int n_images, int in_layout, int n_xcd)
@@ -285,7 +309,8 @@ __device__ __forceinline__ void l7_body(const uint8_t *__restrict__ in, uint8_t 
     constexpr int CIN = 128;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     uint8_t *patch = smem;
-    uint8_t *stage = smem + 2 * L7_REGION;
+    using F = L7Form<KH>;
+    uint8_t *stage = smem + KH * L7_REGION;
     uint8_t *scratch = stage + 4 * L7_STAGE;   // 1 KiB sink of the padding loads
     uint8_t *xch1 = scratch + 1024;            // 5 records of L7_X1
     uint8_t *xch2 = xch1 + 5 * L7_X1;          // 4 records of L7_X2
@@ -303,9 +328,9 @@ __device__ __forceinline__ void l7_body(const uint8_t *__restrict__ in, uint8_t 
 
     // lane roles in v_mfma_i32_16x16x64_i8: A row / B column = lane & 15, K bytes 16*(lane>>4)..+15
     const int m = lane & 15, kg = lane >> 4;
-    v4i wf[L7_MTILES * L7_KSTEPS];
+    v4i wf[L7_MTILES * F::KSTEPS];
 #pragma unroll
-    for (int s = 0; s < L7_MTILES * L7_KSTEPS; s++) wf[s] = *(const v4i *)(w_l7 + (s * 16 + m) * 64 + kg * 16);
+    for (int s = 0; s < L7_MTILES * F::KSTEPS; s++) wf[s] = *(const v4i *)(w_l7 + (s * 16 + m) * 64 + kg * 16);
     const int b0 = bias[0], b1 = bias[1], b2 = bias[2];
 
     const int in_img_bytes = IH * IW * CIN;
@@ -320,14 +345,14 @@ __device__ __forceinline__ void l7_body(const uint8_t *__restrict__ in, uint8_t 
     const int iy_top = 4 * s_begin - 3;
     const int iy_max = min(IH, 4 * s_end + 1);   // last row this chunk reads
     const TensorMap tm = tensor_map(in_layout, CIN, IW, IH);
-    l7_load_rows<9>(patch, scratch, in_img, in_img_bytes, w, lane, 2 * L7_STEP_PIECES, iy_top, max(iy_top + 2, 0), iy_max, 0, X0,
+    l7_load_rows<F::PRO_N, KH>(patch, scratch, in_img, in_img_bytes, w, lane, 2 * L7_STEP_PIECES, iy_top, max(iy_top + 2, 0), iy_max, 0, X0,
                     IW, tm);
     // block k = window rows 4k+4 .. 4k+7 = the rows step k adds; blocks 1 .. AHEAD-1 start now
     int pnext = 2 * L7_STEP_PIECES;        // ring piece slot of the next block to be requested
     int ynext = iy_top + 8;                // its first input row
 #pragma unroll
     for (int k = 1; k < L7_AHEAD; k++) {
-        l7_load_rows<5>(patch, scratch, in_img, in_img_bytes, w, lane, L7_STEP_PIECES, ynext, 0, iy_max, pnext, X0, IW, tm);
+        l7_load_rows<F::STEP_N, KH>(patch, scratch, in_img, in_img_bytes, w, lane, L7_STEP_PIECES, ynext, 0, iy_max, pnext, X0, IW, tm);
         ynext += L7_ROWS;
         pnext += L7_STEP_PIECES;
         pnext = pnext >= L7_RING_PIECES ? pnext - L7_RING_PIECES : pnext;
@@ -335,7 +360,18 @@ __device__ __forceinline__ void l7_body(const uint8_t *__restrict__ in, uint8_t 
 
     // per-lane fragment addressing: step t multiplies window row 4t + 4 + w, P = (4t + 4 + w)*36 + 16c + m + dx
     auto frag_a = [&](int dx) { return (uint32_t)((4 + w) * L7_PITCH + m + dx); };
-    auto frag_s = [&](uint32_t a) { return (uint32_t)((kg & 1) * L7_REGION) + ((((uint32_t)(kg >> 1)) ^ ((a >> 2) & 3u)) << 4); };
+    // KH = 1: one K step of 64 bytes is the region's 64 channels, lane group kg reads chunk c2 = kg (channels 16 kg .. 16 kg + 15:
+    // K byte b is channel b).  ds_read_b128 is served in lane groups that pair the m-complementary halves of kg = 2h and 2h + 1
+    // (lanes 0-3, 12-15 with 20-27, ...): 16 distinct positions, but two chunks.  So the chunk is stored at
+    // 2*(c2&1) + ((c2>>1) ^ ((P>>2)&1)) (not at c2 ^ ((P>>2)&3), which puts the two kg of a pair on the same banks): of the four
+    // positions of a lane group that share P&3 (one 64-byte quarter of a 256-byte LDS row), (P>>2)&3 runs through x, x+1, x+2, x+3
+    // with kg parity e, o, o, e or o, e, e, o; the two lanes of equal parity differ in (P>>2)&1 and the parities take different slot
+    // pairs, so the 16 lanes hit 16 distinct 16-byte slots whatever the alignment of the fragment.  Like the KH = 2 term it is a lane
+    // constant (ring wrap and step advance are multiples of 16 positions).
+    auto frag_s = [&](uint32_t a) {
+        return KH == 2 ? (uint32_t)((kg & 1) * L7_REGION) + ((((uint32_t)(kg >> 1)) ^ ((a >> 2) & 3u)) << 4)
+                       : (2u * (uint32_t)(kg & 1) + (((uint32_t)(kg >> 1)) ^ ((a >> 2) & 1u))) << 4;
+    };
     uint32_t fa[3], fs[3];
 #pragma unroll
     for (int dx = 0; dx < 3; dx++) {
@@ -346,7 +382,7 @@ __device__ __forceinline__ void l7_body(const uint8_t *__restrict__ in, uint8_t 
     const int w_below = (w + 1) & 3;
     const uint32_t x1_lane = (uint32_t)lane * 4u, x2_lane = (uint32_t)(px * 16 + m) * 4u;
     int saved[2][3] = {{0, 0, 0}, {0, 0, 0}};   // wave 3: row 4s + 4 without the row below it
-    wait_vmcnt<5 * (L7_AHEAD - 1)>();
+    wait_vmcnt<F::STEP_N * (L7_AHEAD - 1)>();
     block_barrier();
 
     // the first pass (s = s_begin - 1) stores nothing and requests nothing: its rows 4 s_begin - 1 and 4 s_begin came with the prologue
@@ -357,7 +393,7 @@ __device__ __forceinline__ void l7_body(const uint8_t *__restrict__ in, uint8_t 
         const int Y = 4 * s;               // first output row pair of this step
         // always issued in a live step (rows past the chunk are zero fill): the counted waits below rely on it
         if (live) {
-            l7_load_rows<5>(patch, scratch, in_img, in_img_bytes, w, lane, L7_STEP_PIECES, ynext, 0, iy_max, pnext, X0, IW, tm);
+            l7_load_rows<F::STEP_N, KH>(patch, scratch, in_img, in_img_bytes, w, lane, L7_STEP_PIECES, ynext, 0, iy_max, pnext, X0, IW, tm);
             ynext += L7_ROWS;
         }
 
@@ -372,11 +408,17 @@ __device__ __forceinline__ void l7_body(const uint8_t *__restrict__ in, uint8_t 
                 slot = min(slot, slot - (uint32_t)L7_RING_POS);   // one wrap at most
                 const uint32_t addr = slot * 64u + fs[dx];
                 const v4i p0 = *(const v4i *)(patch + addr);
-                const v4i p1 = *(const v4i *)(patch + (addr ^ 32u));   // channels 64..127: c2 ^ 2
+                if constexpr (KH == 2) {
+                    const v4i p1 = *(const v4i *)(patch + (addr ^ 32u));   // the other 32-channel group of each region: c2 ^ 2
 #pragma unroll
-                for (int t = 0; t < L7_MTILES; t++) {
-                    acc[c][t] = __builtin_amdgcn_mfma_i32_16x16x64_i8(wf[t * L7_KSTEPS + dx * 2 + 0], p0, acc[c][t], 0, 0, 0);
-                    acc[c][t] = __builtin_amdgcn_mfma_i32_16x16x64_i8(wf[t * L7_KSTEPS + dx * 2 + 1], p1, acc[c][t], 0, 0, 0);
+                    for (int t = 0; t < L7_MTILES; t++) {
+                        acc[c][t] = __builtin_amdgcn_mfma_i32_16x16x64_i8(wf[t * F::KSTEPS + dx * 2 + 0], p0, acc[c][t], 0, 0, 0);
+                        acc[c][t] = __builtin_amdgcn_mfma_i32_16x16x64_i8(wf[t * F::KSTEPS + dx * 2 + 1], p1, acc[c][t], 0, 0, 0);
+                    }
+                } else {
+#pragma unroll
+                    for (int t = 0; t < L7_MTILES; t++)
+                        acc[c][t] = __builtin_amdgcn_mfma_i32_16x16x64_i8(wf[t * F::KSTEPS + dx], p0, acc[c][t], 0, 0, 0);
                 }
             }
         }
@@ -436,8 +478,8 @@ __device__ __forceinline__ void l7_body(const uint8_t *__restrict__ in, uint8_t 
                 const uint32_t off = ok ? (uint32_t)(((2 * gy + row) * OW + 2 * X0) * 3 + col * 4) : OOB;
                 __builtin_amdgcn_raw_buffer_store_b32(v, ro, off, 0, 0);
             }
-            // leave in flight: this step's 2 stores and the AHEAD-1 younger row blocks (5 loads + 2 stores each)
-            wait_vmcnt<2 + 7 * (L7_AHEAD - 1)>();
+            // leave in flight: this step's 2 stores and the AHEAD-1 younger row blocks (STEP_N loads + 2 stores each)
+            wait_vmcnt<2 + (F::STEP_N + 2) * (L7_AHEAD - 1)>();
         } else {
 #pragma unroll
             for (int c = 0; c < 2; c++) {
@@ -462,14 +504,16 @@ __device__ __forceinline__ void l7_body(const uint8_t *__restrict__ in, uint8_t 
     }
     wait_vmcnt<0>();   // the zero-fill tail of the prefetch must land before the LDS is released
 }
-__global__ __launch_bounds__(256, L7_WGS) void k_l7(const uint8_t *__restrict__ in, uint8_t *__restrict__ out, const int8_t *__restrict__ w_l7,
+template <int KH>
+__global__ __launch_bounds__(256, L7Form<KH>::WGS) void k_l7(const uint8_t *__restrict__ in, uint8_t *__restrict__ out, const int8_t *__restrict__ w_l7,
                                                     const int8_t *__restrict__ bias, int IW, int IH, int OW, int OH, int steps_y, int y_chunks,
                                                     int tiles_x, int n_images, int in_layout, int n_xcd)
 {
-    l7_body(in, out, w_l7, bias, IW, IH, OW, OH, steps_y, y_chunks, tiles_x, n_images, in_layout, n_xcd);
+    l7_body<KH>(in, out, w_l7, bias, IW, IH, OW, OH, steps_y, y_chunks, tiles_x, n_images, in_layout, n_xcd);
 }
 
-size_t l7_bytes(int cin) { return (size_t)L7_MTILES * L7_KSTEPS * 16 * 64 * (cin / 128); }
+size_t l7_bytes(int cin) { return (size_t)L7_MTILES * L7Form<2>::KSTEPS * 16 * 64 * (cin / 128); }
+size_t l7_half_bytes() { return (size_t)L7_MTILES * L7Form<1>::KSTEPS * 16 * 64; }
 
 void pack_l7(const int8_t *w_okc, int cin, int8_t *dst)
 {
@@ -498,10 +542,49 @@ void pack_l7(const int8_t *w_okc, int cin, int8_t *dst)
                 }
 }
 
+void pack_l7_half(const int8_t *w_okc, int8_t *dst)
+{
+    // w_okc: [3][25*128]; dst: [M tile 2][dx 3][row 16][64 B]; the rows are those of pack_l7 (row = 4*(2 py + px) + r), one K step per dx
+    for (int tile = 0; tile < L7_MTILES; tile++)
+        for (int dx = 0; dx < 3; dx++)
+            for (int row = 0; row < 16; row++) {
+                const int g = row >> 2, r = row & 3, py = g >> 1, px = g & 1;
+                int ky, c;
+                if (r < 3) {
+                    ky = tile == 0 ? 2 - py : (py ? 3 : 0);
+                    c = r;
+                } else {
+                    ky = 4;
+                    c = py ? (tile == 0 ? 2 : -1) : tile;
+                }
+                const int kx = 2 * dx - px;
+                int8_t *t = dst + (((size_t)tile * 3 + dx) * 16 + row) * 64;
+                // K byte b is read by lane group kg = b>>4 from LDS region 0, chunk kg = bytes 16*(kg&1) .. of the 32-channel group
+                // kg>>1: channel b (see l7_load_rows); the channels 64 .. 127 have no K byte, their weights are zero by the plan
+                for (int b = 0; b < 64; b++)
+                    t[b] = (c >= 0 && kx >= 0 && kx < 5) ? w_okc[(size_t)c * 25 * 128 + (ky * 5 + kx) * 128 + b] : 0;
+            }
+}
+
+template <int KH>
+static hipError_t launch_l7_form(const LayerGeom &g, const int8_t *w_img, const sicn_weights &w, const uint8_t *in, uint8_t *out, int n_images,
+                                 hipStream_t stream, int in_layout, const L7Plan &p, const ChipGeom &chip)
+{
+    const size_t lds = L7Form<KH>::LDS;
+    hipError_t e = hipFuncSetAttribute((const void *)k_l7<KH>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_l7<KH>, dim3(p.grid_x), dim3(256), lds, stream, in, out, w_img, w.d_bias, g.IW, g.IH, g.OW, g.OH, p.steps_y, p.y_chunks,
+                       p.tiles_x, n_images, in_layout, chip.n_xcd);
+    return hipGetLastError();
+}
+
+// halves = 1: the channels 64 .. 127 of the input are neither read nor multiplied (the caller knows that their weights are zero and
+// that the layout keeps every 32-channel group in a plane of its own)
 hipError_t launch_l7(const LayerGeom &g, const sicn_weights &w, const uint8_t *in, uint8_t *out,
-                     int n_images, hipStream_t stream, int in_layout, const sicn_options &o, const ChipGeom &chip)
+                     int n_images, hipStream_t stream, int in_layout, const sicn_options &o, const ChipGeom &chip, int halves)
 {
     if (g.CIN != 128 || g.COUT != 3) return hipErrorInvalidValue;
+    if (halves == 1 && (in_layout == LAYOUT_NHWC || !w.d_w_l7_half)) return hipErrorInvalidValue;
     if ((size_t)g.IH * g.IW * g.CIN >= (size_t)OOB) return hipErrorInvalidValue;
     if ((size_t)g.OH * g.OW * 3 >= (size_t)OOB) return hipErrorInvalidValue;   // buffer-descriptor stores
     // about two workgroups per CU in all (three would fit) — measured
@@ -510,13 +593,8 @@ hipError_t launch_l7(const LayerGeom &g, const sicn_weights &w, const uint8_t *i
     // (r03, re-measured on one 1080p image, 30 strips: 13 / 15 / 17 / 19 / 21 / 25 chunks -> 23 / 22 / 19 / 24 / 23 / 21 us: the best
     // cut is the one that stays just under TWO workgroups per CU, 510 of 512; the 640 of round 2 was the middle of a flat region)
     const L7Plan p = plan_l7(g.IW, g.IH, n_images, o.strip_chunks, chip);
-    const size_t lds = L7_LDS;
-    const dim3 grid(p.grid_x);
-    hipError_t e = hipFuncSetAttribute((const void *)k_l7, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_l7, grid, dim3(256), lds, stream, in, out, w.d_w_l7, w.d_bias, g.IW, g.IH, g.OW, g.OH, p.steps_y, p.y_chunks,
-                       p.tiles_x, n_images, in_layout, chip.n_xcd);
-    return hipGetLastError();
+    return halves == 1 ? launch_l7_form<1>(g, w.d_w_l7_half, w, in, out, n_images, stream, in_layout, p, chip)
+                       : launch_l7_form<2>(g, w.d_w_l7, w, in, out, n_images, stream, in_layout, p, chip);
 }
 
 }  // namespace sicn

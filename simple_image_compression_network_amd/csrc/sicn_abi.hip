@@ -199,6 +199,7 @@ struct LaunchArgs {
     const sicn_gdn *gdn;       // the layer's activation, nullptr = the reference's ReLU
     unsigned long long *deal;
     int columns;               // accumulator columns the wide family computes (sicn_live.h); 8: all
+    int columns_in;            // the same of the layer that wrote `in` in this call; 8: all, or nothing is known of it
 };
 
 struct Family {
@@ -251,11 +252,18 @@ void l0_plan(const LayerGeom &g, int n_images, const sicn_options &o, const Chip
 bool l7_shape(int cin, int cout, int) { return cin == 128 && cout == 3; }
 bool l7_images(const int8_t *k, sicn_weights &w)
 {
-    return upload_image(l7_bytes(w.cin), &w.d_w_l7, [&](int8_t *s) { pack_l7(k, w.cin, s); });
+    return upload_image(l7_bytes(w.cin), &w.d_w_l7, [&](int8_t *s) { pack_l7(k, w.cin, s); }) &&
+           upload_image(l7_half_bytes(), &w.d_w_l7_half, [&](int8_t *s) { pack_l7_half(k, s); });   // the form that reads one channel half
 }
+// Layer 7 reads only the first 64-channel half of its input where the layer in front of it, in this call, computed at most 4
+// accumulator columns: column_of(pos) < 4 <=> pos < 64 (sicn_live.h), so every live channel sits in the 32-channel groups 0 and 1,
+// the weights of the groups 2 and 3 are zero in the permuted image this layer got, and (a layer with a GDN computes all 8) no
+// activation has mixed the channels.  The GROUP and PHASE layouts keep a group in a plane of its own: the two planes that are skipped
+// are whole; NHWC would leave half of every line unread for nothing.
+bool l7_reads_one_half(int columns_in, int in_layout) { return columns_in <= 4 && in_layout != 0; }
 hipError_t l7_launch(const LaunchArgs &a, bool *)
 {
-    return launch_l7(a.g, a.w, a.in, a.out, a.n_images, a.stream, a.in_layout, a.o, a.chip);
+    return launch_l7(a.g, a.w, a.in, a.out, a.n_images, a.stream, a.in_layout, a.o, a.chip, l7_reads_one_half(a.columns_in, a.in_layout) ? 1 : 2);
 }
 void l7_plan(const LayerGeom &g, int n_images, const sicn_options &o, const ChipGeom &chip, int32_t out[12])
 {
@@ -347,6 +355,7 @@ extern "C" void sicn_weights_free(sicn_weights *w)
     if (w->d_w_l0) (void)hipFree(w->d_w_l0);
     if (w->d_w_l0g) (void)hipFree(w->d_w_l0g);
     if (w->d_w_l7) (void)hipFree(w->d_w_l7);
+    if (w->d_w_l7_half) (void)hipFree(w->d_w_l7_half);
     if (w->d_w_any) (void)hipFree(w->d_w_any);
     delete w;
 }
@@ -423,7 +432,8 @@ static int link_layout(const sicn_layer_desc &p, const sicn_layer_desc &c, const
 // words in the workspace of a chain (launch_mfma16), or nullptr.
 static int run_layer(const sicn_layer_desc *d, const sicn_weights *w, const uint8_t *in, uint8_t *out,
                      int n_images, hipStream_t stream, int want_transposed, const sicn_options &o, int in_layout = 0,
-                     int out_layout = 0, const sicn_gdn *gdn = nullptr, unsigned long long *deal = nullptr, int columns = 8)
+                     int out_layout = 0, const sicn_gdn *gdn = nullptr, unsigned long long *deal = nullptr, int columns = 8,
+                     int columns_in = 8)
 {
     int rc = sicn_validate_desc(d);
     if (rc) return rc;
@@ -437,7 +447,7 @@ static int run_layer(const sicn_layer_desc *d, const sicn_weights *w, const uint
     ChipGeom chip;
     if ((rc = chip_geom(&chip)) != SICN_OK) return rc;   // no device, or not a gfx950 one
     bool act_done = false;
-    const LaunchArgs args{g, *w, in, out, n_images, stream, in_layout, out_layout, o, chip, gdn, deal, columns};
+    const LaunchArgs args{g, *w, in, out, n_images, stream, in_layout, out_layout, o, chip, gdn, deal, columns, columns_in};
     hipError_t e = layer_family(*d, o, gdn != nullptr).launch(args, &act_done);
     if (act_done) gdn = nullptr;
     if (e == hipSuccess && gdn) e = launch_gdn(*gdn, out, out_layout, d->OFM_ROW, d->OFM_COL, n_images, stream);
@@ -642,6 +652,27 @@ extern "C" int sicn_debug_net_columns(const sicn_net *net, int first, int last, 
     return SICN_OK;
 }
 
+// what a call would do, for tests: per layer of the net the 64-channel halves of its input that it reads (the walk of sicn_net_forward)
+extern "C" int sicn_debug_net_input_halves(const sicn_net *net, int first, int last, int tap_layer, int n_images, int32_t *halves)
+{
+    if (!net || !halves || n_images <= 0) return SICN_EINVAL;
+    const int n_layers = (int)net->descs.size();
+    if (first < 0 || last >= n_layers || first > last) return SICN_EINVAL;
+    ChipGeom chip;
+    if (int rc = chip_geom(&chip)) return rc;
+    for (int l = 0; l < n_layers; l++) halves[l] = 2;
+    int cols_before = live::COLS, cur_layout = 0;
+    for (int l = first; l <= last; l++) {
+        const bool l7 = layer_family(net->descs[l], net->opt, net->gdn[l] != nullptr).kind == KK_L7_RGB;
+        if (l7 && l7_reads_one_half(cols_before, cur_layout)) halves[l] = 1;
+        cols_before = call_columns(net, l, first, last, tap_layer, n_images, chip);
+        cur_layout = (l < last && l != tap_layer)
+                         ? link_layout(net->descs[l], net->descs[l + 1], net->opt, net->gdn[l] != nullptr, net->gdn[l + 1] != nullptr)
+                         : 0;
+    }
+    return SICN_OK;
+}
+
 extern "C" int sicn_net_forward(const sicn_net *net, int first, int last, const uint8_t *in, uint8_t *out,
                                 int tap_layer, uint8_t *tap_out, int n_images, void *workspace,
                                 size_t workspace_bytes, void *hip_stream)
@@ -687,6 +718,7 @@ extern "C" int sicn_net_forward(const sicn_net *net, int first, int last, const 
         const int variant = 2 * (cols_before < live::COLS) + (cols < live::COLS);
         const sicn_weights *wl = variant ? net->derived[l][(size_t)variant] : net->weights[l];
         if (!wl) return SICN_EINVAL;
+        const int cols_in = cols_before;
         cols_before = cols;
         // a tapped layer (the latent) is written straight into the caller's buffer and the next layer reads it there: no copy
         // (round 3 copied it device-to-device behind the layer: 4.8 us per forward pass on small inputs, 15 us on 8 x 4K)
@@ -701,7 +733,7 @@ extern "C" int sicn_net_forward(const sicn_net *net, int first, int last, const 
             if (hipEventRecord(net->ev_begin[ev], stream) != hipSuccess) return SICN_ENODEV;
         }
         int rc = run_layer(&net->descs[l], wl, cur, dst, n_images, stream, -1, net->opt, cur_layout, out_layout,
-                           net->gdn[l], deal_base ? deal_base + (size_t)l * DEAL_WORDS : nullptr, cols);
+                           net->gdn[l], deal_base ? deal_base + (size_t)l * DEAL_WORDS : nullptr, cols, cols_in);
         if (rc) return rc;
         if (ev >= 0) {
             if (hipEventRecord(net->ev_end[ev], stream) != hipSuccess) return SICN_ENODEV;

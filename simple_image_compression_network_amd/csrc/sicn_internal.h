@@ -46,6 +46,7 @@ struct sicn_weights {
     int8_t *d_w_l0;
     int8_t *d_w_l0g;       // layer 0, 128 channels: the A-operand image of the kernel that applies a GDN before its store (k_l0g.hip)
     int8_t *d_w_l7;
+    int8_t *d_w_l7_half;   // layer 7: the 6 KB image of the kernel form that reads the channels 0 .. 63 only (k_rgb.hip: pack_l7_half)
     int8_t *d_w_any;       // the channel-generic MFMA kernels' weight image (k_mfma16c.hip: pack_any), or nullptr when they do not serve the shape
     // what d_w_okc and d_bias were uploaded from: a net's live-channel plan (sicn_live.h) reads them and derives permuted images
     std::vector<int8_t> h_w_okc, h_bias;
@@ -107,7 +108,7 @@ hipError_t launch_pipelined(const LayerGeom &g, const sicn_weights &w, const uin
 hipError_t launch_l0(const LayerGeom &g, const sicn_weights &w, const uint8_t *in, uint8_t *out,
                      int n_images, hipStream_t stream, int out_layout, const sicn_options &o, const ChipGeom &chip, bool relu = true);
 hipError_t launch_l7(const LayerGeom &g, const sicn_weights &w, const uint8_t *in, uint8_t *out,
-                     int n_images, hipStream_t stream, int in_layout, const sicn_options &o, const ChipGeom &chip);
+                     int n_images, hipStream_t stream, int in_layout, const sicn_options &o, const ChipGeom &chip, int halves = 2);
 
 // Host-side weight packers (pure CPU, unit-testable without a GPU).
 // w_okc: [cout][25*cin].  Returns bytes written into `dst` (size from *_bytes()).
@@ -146,5 +147,7 @@ size_t l0g_bytes();
 void pack_l0g(const int8_t *w_okc, int8_t *dst);   // cout = 128
 size_t l7_bytes(int cin);
 void pack_l7(const int8_t *w_okc, int cin, int8_t *dst);
+size_t l7_half_bytes();
+void pack_l7_half(const int8_t *w_okc, int8_t *dst);   // cin = 128
 
 }  // namespace sicn

@@ -26,6 +26,9 @@ ap.add_argument("--gdn", type=int, default=0, help="additionally: layer 0 + GDN 
 ap.add_argument("--deal", type=int, default=0, help="additionally: one-layer nets of conv / deconv 128 -> 128 on few wide persistent workgroups that walk >= 16 "
                 "tiles each, so that the dynamic part of the tile deal (k_mfma16x.hip DealX: tickets, stealing across XCDs) is what runs; three "
                 "calls + a graph replay each")
+ap.add_argument("--live", type=int, default=0, help="additionally: two-layer nets, conv / deconv 128 -> 128 in front of a consumer with 112 .. 0 dead input channels, so "
+                "that the producer runs the live-column kernels (k_mfma16x_live.hip: 3 / 5 / 8 accumulator columns) and a deconv 128 -> 3 behind 3 "
+                "columns reads one channel half; 1 .. 6 x 1 .. 6 ragged tiles, 8 / 16 / all workgroups, against the C oracle")
 args = ap.parse_args()
 rng = np.random.default_rng(args.seed)
 
@@ -228,4 +231,49 @@ for case in range(args.deal):
         print(f"deal {case}: ok ({'deconv' if tr else 'conv'} {w}x{h} n={n}, {grid} workgroups, {chip[1]} ticket counters)", flush=True)
 if args.deal:
     print(f"{args.deal - dbad}/{args.deal} dynamic-deal cases bit-exact")
-sys.exit(1 if (bad or cbad or gbad or dbad) else 0)
+# the live-column kernels and the one-half layer 7: a producer that skips the accumulator columns its consumer does not read
+lbad = 0
+if args.live:
+    import live_geometry_cases as lg  # noqa: E402  (next to this file)
+    _lib.check(_lib.lib().sicn_debug_chip(chip), "sicn_debug_chip")
+LIVE_COLUMNS = {112: 3, 96: 3, 80: 3, 79: 5, 48: 5, 47: 8, 0: 8}     # dead channels -> columns: 1 .. 3 run as 3, 4 and 5 as 5, 6 .. 8 as 8
+for case in range(args.live):
+    tr = int(rng.integers(2))
+    kinds = ("deconv", "rgb" if rng.random() < 0.67 else "deconv") if tr else ("conv", "conv")
+    tx, ty, n = int(rng.integers(1, 7)), int(rng.integers(1, 7)), int(rng.integers(1, 4))
+    mw, mh = 32 * (tx - 1) + int(rng.integers(1, 33)), 16 * (ty - 1) + int(rng.integers(1, 17))      # ragged at both edges
+    w, h = (mw, mh) if tr else (2 * mw - int(rng.integers(2)), 2 * mh - int(rng.integers(2)))
+    grid = int(rng.choice([8, 16, 0]))
+    grid = grid and max(grid // chip[1] * chip[1], chip[1])
+    n_dead = int(rng.choice(list(LIVE_COLUMNS)))
+    descs = lg.chain_descs(kinds, w, h)
+    assert lg.tiles(descs[0]) == (tx, ty)
+    wts = []
+    for l, d in enumerate(descs):
+        Wt = rng.integers(-8, 8, (d.OFM_CH, 5, 5, 128)).astype(np.int8)
+        if l:
+            Wt[:, :, :, rng.permutation(128)[:n_dead]] = 0
+        wts.append((Wt, rng.integers(-128, 128, d.OFM_CH).astype(np.int8)))
+    env = {"wave_tile": 128, "persistent_grid": grid}
+    net = api.EightLayersNet(descs=descs, params=[(api.FixedPointWeights(d.SIMD, 4, d.PE, d.W_TILES, lg.words(k, Wt)), bt)
+                                                  for k, d, (Wt, bt) in zip(kinds, descs, wts)], options=env)
+    cols, live = (ctypes.c_int32 * 2)(), (ctypes.c_int32 * 2)()
+    _lib.check(_lib.lib().sicn_debug_net_columns(net._h, 0, 1, -1, n, cols, live), "sicn_debug_net_columns")
+    assert (cols[0], cols[1], live[0]) == (LIVE_COLUMNS[n_dead], 8, 128 - n_dead), (list(cols), list(live), n_dead)
+    x = rng.integers(0, 256, (n,) + descs[0].in_shape, dtype=np.uint8)
+    ws = net.workspace(n)
+    ws.copy_(torch.from_numpy(rng.integers(0, 256, ws.numel(), dtype=np.uint8)))       # positions nobody computes hold garbage
+    out, _ = net.run_layers(0, 1, torch.from_numpy(x).cuda())
+    torch.cuda.synchronize()
+    ref = x
+    for k, d, wb in zip(kinds, descs, wts):
+        ref = lg.oracle_layer(k, d, wb, ref)
+    what = f"{kinds[0]} {w}x{h} ({tx} x {ty} tiles) n={n} -> {kinds[1]}, grid {grid}, {n_dead} dead = {cols[0]} columns"
+    if not np.array_equal(out.cpu().numpy(), ref):
+        lbad += 1
+        print(f"LIVE MISMATCH {case}: {what}", flush=True)
+    elif case % 10 == 0:
+        print(f"live {case}: ok ({what})", flush=True)
+if args.live:
+    print(f"{args.live - lbad}/{args.live} live-column cases bit-exact")
+sys.exit(1 if (bad or cbad or gbad or dbad or lbad) else 0)

@@ -4,12 +4,16 @@ chain must be what it was: held to the oracle (c_oracle.run_net, direct form) an
 per-layer entry points, which compute and read every channel.
 wave_tile = 128 and persistent_grid = 8 put the wide family, and with it the 3-column layer 6, on tiny images
 (tests/test_live_columns_gpu.py).  Two sizes, 3 images each:
-  132 x 68: layer 7 sees 66 x 34 = three strips of 32 columns, the last one partial (2 columns: the slow epilogue path), and
-            9 steps of 4 rows, the last one partial (2 rows);
-  128 x 72: layer 7 sees 64 x 36 = two whole strips (the fast-row epilogue) and 9 whole steps.
+  132 x 68: layer 7 sees 72 x 40 (132 -> 66 -> 33 -> 17 -> 9 -> 18 -> 36 -> 72, 68 -> 34 -> 17 -> 9 -> 5 -> 10 -> 20 -> 40) = three
+            strips of 32 columns, the last one partial (8 columns: the slow epilogue path), and 10 whole steps of 4 rows;
+  128 x 72: layer 7 sees 64 x 40 = two whole strips (the fast-row epilogue) and 10 whole steps.
+An 8-layer net doubles a latent three times before layer 7, so the height layer 7 sees is always a multiple of 8: a partial last step
+and a strip of 2 columns (66 x 34 behind a deconv on 33 x 17), with the one-chunk run of 9 steps, are in
+tests/test_live_geometry_gpu.py.
 The ring of the kernel holds 368 positions: the prologue fills 8 rows of 36, every step adds 144, so the SECOND step of any chunk
-already wraps.  strip_chunks = 2 cuts the 9 steps into 5 + 4, strip_chunks = 3 into 3 + 3 + 3: every chunk wraps, and every chunk
-but the first starts with the pass that stores nothing."""
+already wraps.  The default cut on these sizes is one step per chunk (plan_l7: two workgroups per CU are more chunks than there are
+steps), which never gets that far; strip_chunks = 2 cuts the 10 steps into 5 + 5, strip_chunks = 3 into 4 + 4 + 2: every chunk wraps,
+and every chunk but the first starts with the pass that stores nothing."""
 import ctypes
 from pathlib import Path
 
@@ -66,6 +70,7 @@ def _param_net():
 WEIGHTS = {
     "param": _param_net,
     "random_dead112": lambda: _random_net(112, 112),
+    "random_dead80": lambda: _random_net(80, 80),       # 48 live: layer 7 is given, and reads, all 48 bytes that 3 columns leave
     "random_dead48": lambda: _random_net(48, 48),
     "dense": lambda: _random_net(5, 0),
 }
@@ -126,7 +131,7 @@ def _check_forward(net, name, size, what):
 
 
 @pytest.mark.parametrize("size", list(SIZES))
-@pytest.mark.parametrize("name", ["param", "random_dead112"])
+@pytest.mark.parametrize("name", ["param", "random_dead112", "random_dead80"])
 def test_one_half_is_the_oracle_and_the_layers_one_by_one(api, name, size):
     net, params = _build(api, name, size)
     assert _halves(net) == [2] * 7 + [1]
@@ -142,7 +147,7 @@ def test_one_half_is_the_oracle_and_the_layers_one_by_one(api, name, size):
 
 @pytest.mark.parametrize("chunks", [2, 3])
 def test_param_in_forced_chunks(api, chunks):
-    """9 steps as 5 + 4 or 3 + 3 + 3 (the module's docstring): the pass that stores nothing and the ring wrap in every chunk"""
+    """10 steps as 5 + 5 or 4 + 4 + 2 (the module's docstring): the pass that stores nothing and the ring wrap in every chunk"""
     net, _ = _build(api, "param", "132x68", strip_chunks=chunks)
     assert _halves(net) == [2] * 7 + [1]
     _check_forward(net, "param", "132x68", f"param, {chunks} chunks")

@@ -112,6 +112,7 @@ CASES = {
     "random_dead48": (lambda: _random_net(48, 48), (5, 5, 5, 5)),
     "random_dead47": (lambda: _random_net(47, 47), (8, 8, 8, 8)),       # 81 live = 6 columns: the next width that is built
     "random_dead112": (lambda: _random_net(112, 112), (3, 3, 3, 3)),    # 1 live column, rounded up to 3
+    "random_dead80": (lambda: _random_net(80, 80), (3, 3, 3, 3)),       # 48 live: every position that 3 columns compute is read
     "dense": (lambda: _random_net(5, 0), (8, 8, 8, 8)),
 }
 

@@ -139,9 +139,14 @@ int sicn_codec_decode_batch_async_sl(const uint8_t *containers, size_t slot_byte
  * shape (values < 128; the hyper-synthesis output).  Every symbol is coded with one of 16 static tables carried in the
  * container; its class is `scale >> 3` for the anchor half of a checkerboard ((x + y) even) and
  * `min(15, ((scale >> 3) + (max of the 4 anchor neighbours >> 3) + 1) >> 1)` for the other half, which is therefore decoded
- * in a second pass.  Both passes are rANS-W streams (64 interleaved states per wave).  Asynchronous only: same status
- * conventions as the pair above; lat_c must be a multiple of 4, latents / scales 4-byte aligned, n images back to back
- * ([n][lat_h][lat_w][lat_c]). */
+ * in a second pass.  Both passes are rANS-W streams (64 interleaved states per wave) of S symbols, S = header dword 9, a power
+ * of two in 1024 .. 16384: each checkerboard set is cut on its own, nst[set] = ceil(nsym[set] / S) streams, anchors first.  The
+ * class rule and the 16 tables do not depend on S.  The entry points below write and expect S = 16384; the _sl entry points of
+ * sicn_ctx_stream_length.h take S as a parameter (library 0.14).  A decoder is told the length it expects; a container whose dword 9
+ * disagrees is an error (bit 2).  Asynchronous only: same status conventions as the pair above; lat_c must be a multiple of 4,
+ * latents / scales 4-byte aligned, n images back to back ([n][lat_h][lat_w][lat_c]).
+ * Limits (SICN_EINVAL): lat_w * lat_h * lat_c <= 0x7F000000, and 32-bit stream offsets as in mode 3:
+ * (nst[0] + nst[1]) * (2 S + 256) < 2^32 — implied by the first limit at S = 16384, the tighter one at S = 1024. */
 size_t sicn_codec_ctx_max_bytes(uint32_t lat_w, uint32_t lat_h, uint32_t lat_c);
 size_t sicn_codec_ctx_workspace_bytes(uint32_t lat_w, uint32_t lat_h, uint32_t lat_c, uint32_t n_images);
 int sicn_codec_ctx_encode_batch_async(const uint8_t *latents, const uint8_t *scales, uint32_t n_images, uint32_t lat_w,

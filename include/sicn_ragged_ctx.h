@@ -6,7 +6,8 @@
  *
  * Bytes.  Container i is byte-identical to what sicn_codec_ctx_encode_batch_async writes for image i alone, and to the oracle's
  * (oracle/sicn_hyper_oracle.c); a container written here decodes with sicn_codec_ctx_decode_batch_async and the other way round.
- * The container format is unchanged and there is no new mode.
+ * The container format is unchanged and there is no new mode.  Streams are 16384 symbols long here; sicn_ctx_stream_length.h
+ * (library 0.14) makes a coder with a length per image, which these encode / decode calls then write and expect.
  *
  * Data model.  Latents and scales: two ragged tensors of ONE layout, the images' [lat_h][lat_w][lat_c] uint8 arrays back to back,
  * no padding (values < 128), image i at latent_offset = sum over j < i of n_symbols(j).  lat_c is common to the batch and a multiple

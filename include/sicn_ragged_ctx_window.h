@@ -2,24 +2,26 @@
  * sicn_ragged_ctx_window.h — random access INSIDE an image of the hyperprior configuration: a window of latent rows of each image of
  * a ragged batch decoded from its rANS-WC streams (container mode 4, sicn_ragged_ctx.h) without the other streams of the image
  * (library 0.13, sicn_version() >= 13).  Nothing in the container format or in the archive changes: a mode-4 container is two sets
- * of independent streams of 16384 symbols, anchors ((x + y) even) then non-anchors; inside a set the pixels lie in raster order over
+ * of independent streams of S symbols (header dword 9, the image's stream length: 16384 unless the encoder chose less, library
+ * 0.14), anchors ((x + y) even) then non-anchors; inside a set the pixels lie in raster order over
  * ROW PAIRS — pair p holds the set's pixels of rows 2 p and 2 p + 1, R = lat_w * lat_c symbols of either set — so a band of latent
  * rows is a contiguous range of streams in each set.  The only coupling between streams is the class rule: the class of a non-anchor
  * symbol reads its four anchor neighbours, and one symbol decoded with a wrong class corrupts its lane's rANS state for the rest of
  * its stream.  So EVERY symbol of a selected non-anchor stream needs all its anchor neighbours decoded, not only the symbols of the
  * rows asked for: that is the halo below.
  *
- * Plan, for one image W = lat_w, H = lat_h, C = lat_c (C % 4 == 0), nsym[2] / nst[2] the symbols / streams of the two sets, WSS =
- * 16384, rows wanted [r0, r1 = r0 + rh):
- *   non-anchor streams   lo = (r0 >> 1) R, hi = min(nsym[1], ((r1 + 1) >> 1) R).  hi > lo: [N0, N1) = [lo / WSS, ceil(hi / WSS)),
- *                        which touch the row pairs [P0, P1) = [N0 WSS / R, ceil(min(nsym[1], N1 WSS) / R)).  Else none.
+ * Plan, for one image W = lat_w, H = lat_h, C = lat_c (C % 4 == 0), nsym[2] / nst[2] the symbols / streams of the two sets, S its
+ * stream length, rows wanted [r0, r1 = r0 + rh):
+ *   non-anchor streams   lo = (r0 >> 1) R, hi = min(nsym[1], ((r1 + 1) >> 1) R).  hi > lo: [N0, N1) = [lo / S, ceil(hi / S)),
+ *                        which touch the row pairs [P0, P1) = [N0 S / R, ceil(min(nsym[1], N1 S) / R)).  Else none.
  *   anchor rows          the wanted rows and every neighbour of every non-anchor the selected streams hold:
  *                        [A0, A1) = [max(0, min(r0, 2 P0 - 1)), min(H, max(r1, 2 P1 + 1))); without non-anchor streams [r0, r1).
- *   anchor streams       [M0, M1) = [(A0 >> 1) R / WSS, ceil(min(nsym[0], ((A1 + 1) >> 1) R) / WSS)), touching the pairs [Q0, Q1)
+ *   anchor streams       [M0, M1) = [(A0 >> 1) R / S, ceil(min(nsym[0], ((A1 + 1) >> 1) R) / S)), touching the pairs [Q0, Q1)
  *                        by the formula of P.
  *   band                 whole latent rows [band_row0, band_row0 + band_rows) = [2 min(P0, Q0), min(H, 2 max(P1, Q1))) at full
  *                        width (without non-anchor streams: Q alone), band_bytes = band_rows W C.
- * Whole row pairs always; a tighter plan (half pairs for an odd r0) is not made.
+ * Whole row pairs always; a tighter plan (half pairs for an odd r0) is not made.  Streams shorter than a row pair (S < R) select
+ * rows more finely: the band of a window can only shrink as S does.
  *
  * Band.  Image i's band lies at band_offset (64-bit, a multiple of 16) of the band tensor, the images back to back; wanted row r0
  * begins (r0 - band_row0) W C bytes into it.  After a decode the band holds, at every position of its rows, the symbol of the

@@ -260,6 +260,18 @@ RAGGED_CTX_WINDOW_ABI = {
     "sicn_ragged_ctx_window_decode_async": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
+# library 0.14: the stream length of the rANS-WC coder (mode 4) as an encoder parameter — the last argument of the uniform calls, one
+# value per image (or NULL = 16384) after lat_c in the ragged ones
+CTX_SL_ABI = {
+    "sicn_codec_ctx_max_bytes_sl": (_sz, [_u32, _u32, _u32, _u32]),
+    "sicn_codec_ctx_workspace_bytes_sl": (_sz, [_u32, _u32, _u32, _u32, _u32]),
+    "sicn_codec_ctx_encode_batch_async_sl": (_i, [_vp, _vp, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _sz, _vp, _vp, _sz, _vp, _u32]),
+    "sicn_codec_ctx_decode_batch_async_sl": (_i, [_vp, _sz, _vp, _vp, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _sz, _vp, _u32]),
+    "sicn_ragged_ctx_layout_sl": (_i, [_u32p, _u32p, _u32, _u32p, _i, ctypes.POINTER(RaggedCtxImage), _u64p]),
+    "sicn_ragged_ctx_coder_create_sl": (_i, [_u32p, _u32p, _u32, _u32p, _u32p, _u32p, _i, ctypes.POINTER(_vp)]),
+    "sicn_ragged_ctx_window_layout_sl": (_i, [_u32p, _u32p, _u32, _u32p, _u32p, _u32p, _i, ctypes.POINTER(RaggedCtxWindowImage), _u64p]),
+}
+
 _lib = None
 
 
@@ -286,7 +298,7 @@ def lib() -> ctypes.CDLL:
             pass
         L = ctypes.CDLL(str(LIB_PATH))
         for name, (res, args) in {**ABI, **CODEC_ABI, **CONVLAYER_ABI, **GDN_ABI, **RAGGED_ABI, **RAGGED_HYPER_ABI, **RAGGED_CODEC_ABI, **RAGGED_CTX_ABI, **RAGGED_ARCHIVE_ABI,
-                                  **RAGGED_ARCHIVE_SELECT_ABI, **RAGGED_WINDOW_ABI, **RAGGED_CTX_WINDOW_ABI}.items():
+                                  **RAGGED_ARCHIVE_SELECT_ABI, **RAGGED_WINDOW_ABI, **RAGGED_CTX_WINDOW_ABI, **CTX_SL_ABI}.items():
             fn = getattr(L, name)          # AttributeError if the ABI is incomplete
             fn.restype = res
             fn.argtypes = args

@@ -5,6 +5,7 @@ mirrors a reference interface and parity is "unpinned" (own specification: oracl
 from __future__ import annotations
 
 import ctypes
+import numbers
 
 from . import _lib
 
@@ -393,21 +394,41 @@ class RaggedWindowDecoder(_lib.Handle):
             raise _lib.SicnError(-22, f"rANS-W window decode status {d}")
 
 
+def _ctx_stream_symbols(stream_symbols, n):
+    """The rANS-WC stream lengths of n images from None (16384), one int, or one per image; ValueError for a length that is not
+    admissible, before anything is made."""
+    if stream_symbols is None:
+        v = [WSTREAM_SYMBOLS] * n
+    elif isinstance(stream_symbols, numbers.Integral) and not isinstance(stream_symbols, bool):   # (a numpy integer from a parsed header too)
+        v = [int(stream_symbols)] * n
+    else:
+        v = [WSTREAM_SYMBOLS if x is None else int(x) for x in stream_symbols]
+        if len(v) != n:
+            raise ValueError("stream_symbols: one value, or one per shape")
+    if any(x not in (1024, 2048, 4096, 8192, 16384) for x in v):
+        raise ValueError("stream_symbols must be a power of two in 1024 .. 16384")
+    return v
+
+
 class ContextCoder:
     """Container mode 4 ("rANS-WC",sicn_codec_ctx_*_async): the conditional coder of the hyperprior configuration — 16
     class tables, class from the hyper-synthesis scale map and, for the non-anchor half of a checkerboard, from the
-    already decoded anchor neighbours.  Same conventions as LatentCoder (enqueue only; verdicts / sizes on the device)."""
+    already decoded anchor neighbours.  Same conventions as LatentCoder (enqueue only; verdicts / sizes on the device).
+    stream_symbols: the stream length the encoder writes and the decoder expects (header dword 9), a power of two in 1024 .. 16384;
+    None = 16384 (`auto_stream_symbols` is NOT applied to this coder)."""
 
     def __init__(self, n_images: int, lat_h: int, lat_w: int, lat_c: int, image_width: int = 0, image_height: int = 0,
-                 device="cuda"):
+                 device="cuda", stream_symbols=None):
         import torch
         L = _lib.lib()
         self.shape = (int(n_images), int(lat_h), int(lat_w), int(lat_c))
         self.image_wh = (int(image_width), int(image_height))
-        self.slot = (int(L.sicn_codec_ctx_max_bytes(lat_w, lat_h, lat_c)) + 255) // 256 * 256
+        self.stream_symbols = _ctx_stream_symbols(stream_symbols, 1)[0]
+        self.slot = (int(L.sicn_codec_ctx_max_bytes_sl(lat_w, lat_h, lat_c, self.stream_symbols)) + 255) // 256 * 256
         dev = torch.device(device)
         self.slots = torch.empty((n_images, self.slot), dtype=torch.uint8, device=dev)
-        self.ws = torch.empty(max(L.sicn_codec_ctx_workspace_bytes(lat_w, lat_h, lat_c, n_images), 256), dtype=torch.uint8, device=dev)
+        self.ws = torch.empty(max(L.sicn_codec_ctx_workspace_bytes_sl(lat_w, lat_h, lat_c, n_images, self.stream_symbols), 256),
+                              dtype=torch.uint8, device=dev)
         self.enc_status = torch.zeros((n_images, 2), dtype=torch.int32, device=dev)
         self.dec_status = torch.zeros((n_images, 2), dtype=torch.int32, device=dev)
 
@@ -420,10 +441,11 @@ class ContextCoder:
         self._check(latents, "latents")
         self._check(scales, "scales")
         n, h, w, c = self.shape
-        _lib.check(_lib.lib().sicn_codec_ctx_encode_batch_async(
+        _lib.check(_lib.lib().sicn_codec_ctx_encode_batch_async_sl(
             ctypes.c_void_p(latents.data_ptr()), ctypes.c_void_p(scales.data_ptr()), n, w, h, c, self.image_wh[0], self.image_wh[1],
             ctypes.c_void_p(self.slots.data_ptr()), self.slot, ctypes.c_void_p(self.enc_status.data_ptr()),
-            ctypes.c_void_p(self.ws.data_ptr()), self.ws.numel(), _stream_ptr(stream)), "sicn_codec_ctx_encode_batch_async")
+            ctypes.c_void_p(self.ws.data_ptr()), self.ws.numel(), _stream_ptr(stream), self.stream_symbols),
+            "sicn_codec_ctx_encode_batch_async_sl")
         return self.slots
 
     def decode(self, out_latents, scales, slots=None, valid=None, stream=None):
@@ -433,10 +455,11 @@ class ContextCoder:
         slots = self.slots if slots is None else slots
         own = slots is self.slots     # external containers: trust the slot unless their status array came along (see LatentCoder.decode)
         vptr = None if (valid is False or (valid is None and not own)) else ctypes.c_void_p((self.enc_status if valid is None else valid).data_ptr())
-        _lib.check(_lib.lib().sicn_codec_ctx_decode_batch_async(
+        _lib.check(_lib.lib().sicn_codec_ctx_decode_batch_async_sl(
             ctypes.c_void_p(slots.data_ptr()), self.slot, vptr, ctypes.c_void_p(scales.data_ptr()), n, w, h, c,
             ctypes.c_void_p(out_latents.data_ptr()), ctypes.c_void_p(self.dec_status.data_ptr()),
-            ctypes.c_void_p(self.ws.data_ptr()), self.ws.numel(), _stream_ptr(stream)), "sicn_codec_ctx_decode_batch_async")
+            ctypes.c_void_p(self.ws.data_ptr()), self.ws.numel(), _stream_ptr(stream), self.stream_symbols),
+            "sicn_codec_ctx_decode_batch_async_sl")
         return out_latents
 
     sizes = LatentCoder.sizes
@@ -449,10 +472,12 @@ class RaggedContextCoder(_lib.Handle):
     (a multiple of 4) in all of them; `image_sizes`: [(width, height)], header fields only.  Latents and scales travel as two ragged
     tensors of one layout — flat CUDA uint8 tensors, the images' [h][w][c] arrays back to back — containers in one flat slot buffer,
     image i's slot at `images[i].slot_offset`.  Container i is byte-identical to `ContextCoder(1, h_i, w_i, lat_c)`'s and decodes
-    with it.  Same conventions as RaggedLatentCoder: enqueue only; verdicts and sizes stay on the device until `check()` / `sizes()`."""
+    with it.  Same conventions as RaggedLatentCoder: enqueue only; verdicts and sizes stay on the device until `check()` / `sizes()`.
+    stream_symbols: None (16384), one length for all images, or one per image — `ContextCoder`'s parameter; the lengths live in the
+    coder, so `decode` and `window` expect them."""
     _free = "sicn_ragged_ctx_coder_free"
 
-    def __init__(self, shapes, lat_c: int, image_sizes=None, device=None):
+    def __init__(self, shapes, lat_c: int, image_sizes=None, stream_symbols=None, device=None):
         import torch
         L = _lib.lib()
         self.shapes = [(int(h), int(w)) for h, w in shapes]
@@ -461,18 +486,21 @@ class RaggedContextCoder(_lib.Handle):
         self.image_sizes = [(int(w), int(h)) for w, h in image_sizes] if image_sizes is not None else [(0, 0)] * n
         if len(self.image_sizes) != n:
             raise ValueError("image_sizes: one (width, height) per shape")
+        self.stream_symbols = _ctx_stream_symbols(stream_symbols, n)
         u32 = ctypes.c_uint32 * max(n, 1)
         self._lat_w, self._lat_h = u32(*[w for _, w in self.shapes]), u32(*[h for h, _ in self.shapes])
         self._img_w, self._img_h = u32(*[w for w, _ in self.image_sizes]), u32(*[h for _, h in self.image_sizes])
+        self._wss = u32(*self.stream_symbols)
         self.images = (_lib.RaggedCtxImage * max(n, 1))()            # where image i lies: offsets, slot capacity, streams of the two sets
         totals = (ctypes.c_uint64 * 3)()
-        _lib.check(L.sicn_ragged_ctx_layout(self._lat_w, self._lat_h, self.lat_c, n, self.images, totals), "sicn_ragged_ctx_layout")
+        _lib.check(L.sicn_ragged_ctx_layout_sl(self._lat_w, self._lat_h, self.lat_c, self._wss, n, self.images, totals),
+                   "sicn_ragged_ctx_layout_sl")
         self.latent_bytes, self.slot_bytes = int(totals[0]), int(totals[1])
         self.device = torch.device(device if device is not None else "cuda")
         self._h = ctypes.c_void_p()
         with torch.cuda.device(self.device):
-            _lib.check(L.sicn_ragged_ctx_coder_create(self._lat_w, self._lat_h, self.lat_c, self._img_w, self._img_h, n,
-                                                      ctypes.byref(self._h)), "sicn_ragged_ctx_coder_create")
+            _lib.check(L.sicn_ragged_ctx_coder_create_sl(self._lat_w, self._lat_h, self.lat_c, self._wss, self._img_w, self._img_h, n,
+                                                         ctypes.byref(self._h)), "sicn_ragged_ctx_coder_create_sl")
         self.slot_buffer = torch.empty(self.slot_bytes, dtype=torch.uint8, device=self.device)
         self.ws = torch.empty(max(int(L.sicn_ragged_ctx_coder_workspace_bytes(self._h)), 256), dtype=torch.uint8, device=self.device)
         self.enc_status = torch.zeros((n, 2), dtype=torch.int32, device=self.device)   # sicn_codec_status {error, bytes}
@@ -480,8 +508,8 @@ class RaggedContextCoder(_lib.Handle):
 
     @classmethod
     def for_containers(cls, containers, device=None):
-        """A coder for rANS-WC containers that came from somewhere else (a list of `bytes`): shapes and image sizes are READ from
-        the 48-byte headers, the containers are copied into the coder's slots and their lengths into its encoder status, so that
+        """A coder for rANS-WC containers that came from somewhere else (a list of `bytes`): shapes, image sizes and stream lengths
+        are READ from the 48-byte headers, the containers are copied into the coder's slots and their lengths into its encoder status, so that
         `decode(out, scales)` reads exactly them."""
         import torch
         infos = [parse_header(bytes(c[:48])) for c in containers]
@@ -490,7 +518,7 @@ class RaggedContextCoder(_lib.Handle):
         if any(int(i.mode) != RANSWC for i in infos) or len({int(i.lat_c) for i in infos}) != 1:
             raise ValueError("containers must all be rANS-WC and of one channel count")
         coder = cls([(int(i.lat_h), int(i.lat_w)) for i in infos], int(infos[0].lat_c),
-                    [(int(i.image_width), int(i.image_height)) for i in infos], device=device)
+                    [(int(i.image_width), int(i.image_height)) for i in infos], [int(i.stream_symbols) for i in infos], device=device)
         host = torch.zeros(coder.slot_bytes, dtype=torch.uint8)
         for c, im in zip(containers, coder.images):
             if len(c) > int(im.slot_bytes):
@@ -583,8 +611,8 @@ class RaggedContextWindowDecoder(_lib.Handle):
         self._r0, self._rh = u32(*[r for r, _ in self.rows]), u32(*[h for _, h in self.rows])
         self.images = (_lib.RaggedCtxWindowImage * max(n, 1))()
         totals = (ctypes.c_uint64 * 2)()
-        _lib.check(L.sicn_ragged_ctx_window_layout(coder._lat_w, coder._lat_h, coder.lat_c, self._r0, self._rh, n, self.images, totals),
-                   "sicn_ragged_ctx_window_layout")
+        _lib.check(L.sicn_ragged_ctx_window_layout_sl(coder._lat_w, coder._lat_h, coder.lat_c, coder._wss, self._r0, self._rh, n, self.images,
+                                                      totals), "sicn_ragged_ctx_window_layout_sl")
         self.band_bytes = int(totals[0])
         self.selected_streams = sum(int(im.end_stream[s]) - int(im.first_stream[s]) for im in self.images[:n] for s in (0, 1))
         self._h = ctypes.c_void_p()

@@ -8,23 +8,30 @@
 #pragma once
 #include "k_codec_body.hpp"
 
+// include/sicn_ctx_stream_length.h (declared here so that the uniform coder's translation unit does not see the ragged ABI)
+extern "C" size_t sicn_codec_ctx_max_bytes_sl(uint32_t lat_w, uint32_t lat_h, uint32_t lat_c, uint32_t stream_symbols);
+
 namespace {
 
 constexpr int NCLS = 16;
 constexpr uint32_t CTX_TABLE_BYTES = NCLS * 256;   // in the container: 16 x 128 x u16
 
+// S: the stream length, header dword 9 (wstream_ok: a power of two, 1024 .. 16384).  Each set is cut into streams of S symbols; a
+// stream's scratch slot and the bound of its length entry are wstream_cap(S) bytes.  It belongs to the image: the uniform entry
+// points give every image of a batch one S, the ragged coder keeps one per row.
 struct CtxGeom {
-    uint32_t W, H, C, nsym[2], nst[2];
+    uint32_t W, H, C, nsym[2], nst[2], S;
 };
-__host__ __device__ inline CtxGeom ctx_geom(uint32_t W, uint32_t H, uint32_t C)
+__host__ __device__ inline CtxGeom ctx_geom(uint32_t W, uint32_t H, uint32_t C, uint32_t S)
 {
     const uint32_t a = (W + 1) / 2, b = W / 2;
     CtxGeom g;
     g.W = W; g.H = H; g.C = C;
     g.nsym[0] = ((H / 2) * W + ((H & 1) ? a : 0)) * C;
     g.nsym[1] = ((H / 2) * W + ((H & 1) ? b : 0)) * C;
-    g.nst[0] = (g.nsym[0] + WSS - 1) / WSS;
-    g.nst[1] = (g.nsym[1] + WSS - 1) / WSS;
+    g.S = S;
+    g.nst[0] = (g.nsym[0] + S - 1) / S;
+    g.nst[1] = (g.nsym[1] + S - 1) / S;
     return g;
 }
 
@@ -92,7 +99,7 @@ __host__ __device__ inline size_t ctx_carve(CtxWorkspace &w, void *base, uint32_
 }
 // host: what ctx_carve says about a block without a block: the byte offset of the class histograms (carved from address 0), the size
 inline size_t ctx_chist_offset() { CtxWorkspace w; ctx_carve(w, nullptr, 0, 0); return reinterpret_cast<uintptr_t>(w.chist); }
-inline size_t ctx_ws_bytes(uint32_t ns) { CtxWorkspace w; return align_up(ctx_carve(w, nullptr, ns, WCAP) + 64, 256); }
+inline size_t ctx_ws_bytes(uint32_t ns, uint32_t S) { CtxWorkspace w; return align_up(ctx_carve(w, nullptr, ns, wstream_cap(S)) + 64, 256); }
 // workgroups of the class-histogram stage that share one image of n symbols
 inline uint32_t ctx_hist_blocks(uint32_t n) { const uint32_t b = (n / 4 + 255u) / 256u; return b < 256u ? b : 256u; }
 
@@ -109,14 +116,17 @@ struct CtxRow {
 };
 inline uint32_t ctx_slot_cap(uint64_t slot_bytes) { return (uint32_t)(slot_bytes < 0xFFFFFFFFull ? slot_bytes : 0xFFFFFFFFull); }
 // host: the fields of a row that follow from the image's shape (slot_cap: that of the smallest slot the ragged layout gives, a caller
-// with slots of its own overwrites it), and the shape limits of both families of entry points
-inline int ctx_row_shape(CtxRow &r, uint32_t lat_w, uint32_t lat_h, uint32_t lat_c, uint32_t img_w, uint32_t img_h)
+// with slots of its own overwrites it), and the shape limits of both families of entry points.  32-bit stream offsets: the scratch
+// slots of all streams, wstream_cap(S) bytes each, must stay below 2^32 (mode 3's rule, sicn_codec.hip wstream_fits) — at 16384
+// MAX_RANS_SYMBOLS implies it, at 1024 it is the tighter limit (about 1.9 G symbols).
+inline int ctx_row_shape(CtxRow &r, uint32_t lat_w, uint32_t lat_h, uint32_t lat_c, uint32_t img_w, uint32_t img_h, uint32_t S)
 {
     const uint64_t positions = (uint64_t)lat_w * lat_h;
-    if (positions == 0 || lat_c == 0 || (lat_c & 3)) return SICN_EINVAL;
+    if (positions == 0 || lat_c == 0 || (lat_c & 3) || !wstream_ok(S)) return SICN_EINVAL;
     if (positions > MAX_RANS_SYMBOLS || positions * lat_c > MAX_RANS_SYMBOLS) return SICN_EINVAL;   // (the products cannot wrap)
-    r.g = ctx_geom(lat_w, lat_h, lat_c);
-    r.slot_cap = ctx_slot_cap(align_up(sicn_codec_ctx_max_bytes(lat_w, lat_h, lat_c), 16));
+    r.g = ctx_geom(lat_w, lat_h, lat_c, S);
+    if (((uint64_t)r.g.nst[0] + r.g.nst[1]) * wstream_cap(S) >= (1ull << 32)) return SICN_EINVAL;
+    r.slot_cap = ctx_slot_cap(align_up(sicn_codec_ctx_max_bytes_sl(lat_w, lat_h, lat_c, S), 16));
     r.img_w = img_w; r.img_h = img_h;
     r.n_chunks = ctx_hist_blocks((uint32_t)(positions * lat_c));
     return SICN_OK;
@@ -126,7 +136,7 @@ __device__ __forceinline__ CtxRow load_row(const CtxRow *__restrict__ rows, uint
 {
     const CtxRow *r = rows + img;
     return CtxRow{uni(r->lat_off), uni(r->slot_off), uni(r->ws_off),
-                  CtxGeom{uni(r->g.W), uni(r->g.H), uni(r->g.C), {uni(r->g.nsym[0]), uni(r->g.nsym[1])}, {uni(r->g.nst[0]), uni(r->g.nst[1])}},
+                  CtxGeom{uni(r->g.W), uni(r->g.H), uni(r->g.C), {uni(r->g.nsym[0]), uni(r->g.nsym[1])}, {uni(r->g.nst[0]), uni(r->g.nst[1])}, uni(r->g.S)},
                   uni(r->slot_cap), uni(r->img_w), uni(r->img_h), uni(r->first_chunk), uni(r->n_chunks), uni(r->first_enc),
                   {uni(r->first_dec[0]), uni(r->first_dec[1])}, uni(r->first_stream)};
 }
@@ -164,7 +174,7 @@ __device__ __forceinline__ CtxImage ctx_image(const CtxRow &r, const uint8_t *la
     im.slot = const_cast<uint8_t *>(containers) + r.slot_off;
     im.slot_cap = r.slot_cap;
     im.img_w = r.img_w; im.img_h = r.img_h;
-    ctx_carve(im.w, workspace + r.ws_off, r.g.nst[0] + r.g.nst[1], WCAP);
+    ctx_carve(im.w, workspace + r.ws_off, r.g.nst[0] + r.g.nst[1], wstream_cap(r.g.S));
     return im;
 }
 
@@ -300,7 +310,7 @@ __device__ __forceinline__ void ctx_tables_body(const CtxImage &im, bool dec)
         const unsigned long long *sums = im.w.sums;
         const uint32_t n = g.W * g.H * g.C;
         const uint32_t a = (uint32_t)((1 + sums[0]) % ADLER_MOD), b = (uint32_t)((n % ADLER_MOD + sums[1]) % ADLER_MOD);
-        const uint32_t words[12] = {0x4C434953u, 1u | (4u << 16), im.img_w, im.img_h, g.W, g.H, g.C, n, g.nst[0] + g.nst[1], WSS, 0u, (b << 16) | a};
+        const uint32_t words[12] = {0x4C434953u, 1u | (4u << 16), im.img_w, im.img_h, g.W, g.H, g.C, n, g.nst[0] + g.nst[1], g.S, 0u, (b << 16) | a};
         if (threadIdx.x != 10) {
             const uint32_t v = words[threadIdx.x];
             uint8_t *p = im.slot + 4 * threadIdx.x;
@@ -336,7 +346,7 @@ __device__ __forceinline__ void ctx_parse_body(const CtxImage &im, const uint32_
         return;
     }
     auto rd32 = [&](int o) { return c[o] | ((uint32_t)c[o + 1] << 8) | ((uint32_t)c[o + 2] << 16) | ((uint32_t)c[o + 3] << 24); };
-    const uint32_t expect[10] = {0x4C434953u, 1u | (4u << 16), 0, 0, g.W, g.H, g.C, n, ns, WSS};
+    const uint32_t expect[10] = {0x4C434953u, 1u | (4u << 16), 0, 0, g.W, g.H, g.C, n, ns, g.S};
     uint32_t err = 0;
     if (lane < 10 && lane != 2 && lane != 3 && rd32(4 * lane) != expect[lane]) err = 4;
     const uint32_t pb = rd32(40);
@@ -381,9 +391,9 @@ __device__ __forceinline__ void ctx_encode_body(const CtxImage &im, uint32_t grp
     uint16_t *words = words_all[wv];
     const int set = st >= g.nst[0];
     const uint32_t q0 = set ? st - g.nst[0] : st;
-    const uint32_t begin = q0 * WSS, cnt = min(WSS, g.nsym[set] - begin), blocks = (cnt + 255) / 256;
-    uint16_t *dst = (uint16_t *)(scratch + (size_t)st * WCAP);
-    uint32_t pos = WCAP / 2, top = WCAP / 2, x = RANSW_L;
+    const uint32_t begin = q0 * g.S, cnt = min(g.S, g.nsym[set] - begin), blocks = (cnt + 255) / 256, cap = wstream_cap(g.S);
+    uint16_t *dst = (uint16_t *)(scratch + (size_t)st * cap);
+    uint32_t pos = cap / 2, top = cap / 2, x = RANSW_L;
     const unsigned long long below = (1ull << lane) - 1;
     auto load = [&](uint32_t q, uint32_t &sym4, uint32_t &cls4) {   // C % 4 == 0: a lane's 4 symbols are 4 channels of one pixel
         const uint32_t j = q * 256 + lane * 4;
@@ -434,12 +444,15 @@ __device__ __forceinline__ void ctx_encode_body(const CtxImage &im, uint32_t grp
     words[(pos + 2 * lane + 1) & (RING_WORDS - 1)] = (uint16_t)(x >> 16);
     wave_lds_sync();
     ring_flush(words, dst, pos, top, lane);
-    if (lane == 0) lens[st] = (WCAP / 2 - pos) * 2;
+    if (lane == 0) lens[st] = (cap / 2 - pos) * 2;
 }
 
 // decoder, one set per launch (anchors first): the CTX_WPB_DEC streams from `first` on, below `end`, of set SET of the image, in
 // the set's own numbering (the full decoders: a group of the set, first = grp * CTX_WPB_DEC, end = nst[SET]; the window decoder: a
-// group of its selection — no wave decodes or writes a stream outside [first, end)).  The symbol of a slot
+// group of its selection — no wave decodes or writes a stream outside [first, end)).  One group per table load at every stream
+// length.  A stream of S <= 2048 symbols (at most 4352 bytes) fits the 8 KB ring whole: one fill, and the refill
+// test of the block loop never fires.
+// LDS: 8 + 64 KB of tables + 8 rings of 8 KB = 136 KB of the CU's 160: one workgroup of 8 waves per CU, at every S.  The symbol of a slot
 // comes from ONE table read (16 classes x 4096 slots = 64 KB of LDS, shared by the workgroup's eight waves; round 3 read the first
 // symbol of a 16-slot bucket and walked the cumulative table from there — up to a dozen dependent LDS round trips per step on a
 // flat class, with six waves per CU to hide them behind).  SET is a template parameter so that the geometry's per-set fields are
@@ -467,9 +480,9 @@ __device__ __forceinline__ void ctx_decode_body(const CtxImage &im, uint32_t fir
     __syncthreads();
     if (sidx >= end) return;   // (no block barrier below this line)
     uint16_t *words = words_all[wv];
-    const uint32_t begin = sidx * WSS, cnt = min(WSS, g.nsym[set] - begin), blocks = (cnt + 255) / 256;
+    const uint32_t begin = sidx * g.S, cnt = min(g.S, g.nsym[set] - begin), blocks = (cnt + 255) / 256;
     const uint32_t off = offsets[st], len = offsets[st + 1] - off, payload_bytes = meta[1];
-    if (len < 256 || (len & 1) || (off & 1) || len > WCAP || (unsigned long long)off + len > payload_bytes) {
+    if (len < 256 || (len & 1) || (off & 1) || len > wstream_cap(g.S) || (unsigned long long)off + len > payload_bytes) {
         if (lane == 0) atomicOr(&meta[3], 1u);
         return;
     }
@@ -548,7 +561,7 @@ __device__ __forceinline__ void ctx_scan_body(const CtxImage &im, uint32_t *stat
     const uint32_t ns = im.g.nst[0] + im.g.nst[1];
     uint8_t *table = im.slot + SICN_CODEC_HEADER_BYTES + CTX_TABLE_BYTES;
     if (dec)
-        scan_body(nullptr, table, ns, w.offsets, nullptr, nullptr, WCAP, w.meta + 3, nullptr, 0u, (w.meta[0] & 0x100u) != 0);
+        scan_body(nullptr, table, ns, w.offsets, nullptr, nullptr, wstream_cap(im.g.S), w.meta + 3, nullptr, 0u, (w.meta[0] & 0x100u) != 0);
     else
         scan_body(w.lens, nullptr, ns, w.offsets, table, im.slot + 40, 0xFFFFFFFFu, nullptr, status + 2 * (size_t)img + 1,
                   (uint32_t)(SICN_CODEC_HEADER_BYTES + CTX_TABLE_BYTES) + 4 * ns, false);
@@ -558,7 +571,7 @@ __device__ __forceinline__ void ctx_scan_body(const CtxImage &im, uint32_t *stat
 __device__ __forceinline__ void ctx_compact_body(const CtxImage &im, uint32_t st)
 {
     const uint32_t ns = im.g.nst[0] + im.g.nst[1];
-    compact_body(im.w.scratch, im.w.lens, im.w.offsets, im.slot + SICN_CODEC_HEADER_BYTES + CTX_TABLE_BYTES + 4 * (size_t)ns, WCAP, st);
+    compact_body(im.w.scratch, im.w.lens, im.w.offsets, im.slot + SICN_CODEC_HEADER_BYTES + CTX_TABLE_BYTES + 4 * (size_t)ns, wstream_cap(im.g.S), st);
 }
 
 // decoder back end, ONE lane: the verdict of the whole image -> status[img] = {error, n_symbols}

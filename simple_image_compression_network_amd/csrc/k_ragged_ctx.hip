@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../../include/sicn_ragged_ctx.h"
+#include "../../include/sicn_ctx_stream_length.h"
 #include "../../include/sicn_ragged_ctx_window.h"
 #include "ctx_window_host.hpp"
 #include "k_ctx_body.hpp"
@@ -146,17 +147,18 @@ struct Plan {
     uint64_t lat_bytes = 0, slot_bytes = 0, ws_bytes = 0, streams = 0, chunks = 0, enc_groups = 0, dec_groups[2] = {0, 0};
 };
 
-// keep_rows = false: totals only (nothing is allocated)
-int plan_ctx(const uint32_t *lat_w, const uint32_t *lat_h, uint32_t lat_c, const uint32_t *img_w, const uint32_t *img_h, int n_images,
-             bool keep_rows, sicn_ragged_ctx_image *images, Plan *p)
+// keep_rows = false: totals only (nothing is allocated).  wss_or_null: the stream length of every image, NULL = 16384
+int plan_ctx(const uint32_t *lat_w, const uint32_t *lat_h, uint32_t lat_c, const uint32_t *wss_or_null, const uint32_t *img_w,
+             const uint32_t *img_h, int n_images, bool keep_rows, sicn_ragged_ctx_image *images, Plan *p)
 {
     if (!lat_w || !lat_h || n_images < 1) return SICN_EINVAL;
     if (keep_rows) p->rows.reserve((size_t)n_images);
     for (int i = 0; i < n_images; i++) {
         CtxRow r{};
-        if (int rc = ctx_row_shape(r, lat_w[i], lat_h[i], lat_c, img_w ? img_w[i] : 0, img_h ? img_h[i] : 0)) return rc;
+        const uint32_t wss = wss_or_null ? wss_or_null[i] : WSS;
+        if (int rc = ctx_row_shape(r, lat_w[i], lat_h[i], lat_c, img_w ? img_w[i] : 0, img_h ? img_h[i] : 0, wss)) return rc;
         const uint32_t n = r.g.W * r.g.H * r.g.C, ns = r.g.nst[0] + r.g.nst[1];
-        const uint64_t slot = align_up(sicn_codec_ctx_max_bytes(lat_w[i], lat_h[i], lat_c), 16);   // (r.slot_cap is this, saturated)
+        const uint64_t slot = align_up(sicn_codec_ctx_max_bytes_sl(lat_w[i], lat_h[i], lat_c, wss), 16);   // (r.slot_cap is this, saturated)
         r.lat_off = p->lat_bytes;
         r.slot_off = p->slot_bytes;
         r.ws_off = p->ws_bytes;
@@ -167,7 +169,7 @@ int plan_ctx(const uint32_t *lat_w, const uint32_t *lat_h, uint32_t lat_c, const
         r.first_stream = (uint32_t)p->streams;
         p->lat_bytes += n;
         p->slot_bytes += slot;
-        p->ws_bytes += ctx_ws_bytes(ns);
+        p->ws_bytes += ctx_ws_bytes(ns, wss);
         p->streams += ns;
         p->chunks += r.n_chunks;
         p->enc_groups += (ns + CTX_WPB - 1) / CTX_WPB;
@@ -191,17 +193,23 @@ struct sicn_ragged_ctx_coder {
     uint32_t *d_stream_image = nullptr;       // [streams]
 };
 
-extern "C" int sicn_ragged_ctx_layout(const uint32_t *lat_w, const uint32_t *lat_h, uint32_t lat_c, int n_images,
-                                      sicn_ragged_ctx_image *images_or_null, uint64_t totals[3])
+extern "C" int sicn_ragged_ctx_layout_sl(const uint32_t *lat_w, const uint32_t *lat_h, uint32_t lat_c, const uint32_t *stream_symbols_or_null,
+                                         int n_images, sicn_ragged_ctx_image *images_or_null, uint64_t totals[3])
 {
     Plan p;
-    if (int rc = plan_ctx(lat_w, lat_h, lat_c, nullptr, nullptr, n_images, false, images_or_null, &p)) return rc;
+    if (int rc = plan_ctx(lat_w, lat_h, lat_c, stream_symbols_or_null, nullptr, nullptr, n_images, false, images_or_null, &p)) return rc;
     if (totals) {
         totals[0] = p.lat_bytes;
         totals[1] = p.slot_bytes;
         totals[2] = p.ws_bytes;
     }
     return SICN_OK;
+}
+
+extern "C" int sicn_ragged_ctx_layout(const uint32_t *lat_w, const uint32_t *lat_h, uint32_t lat_c, int n_images,
+                                      sicn_ragged_ctx_image *images_or_null, uint64_t totals[3])
+{
+    return sicn_ragged_ctx_layout_sl(lat_w, lat_h, lat_c, nullptr, n_images, images_or_null, totals);
 }
 
 extern "C" void sicn_ragged_ctx_coder_free(sicn_ragged_ctx_coder *coder)
@@ -213,8 +221,9 @@ extern "C" void sicn_ragged_ctx_coder_free(sicn_ragged_ctx_coder *coder)
     delete coder;
 }
 
-extern "C" int sicn_ragged_ctx_coder_create(const uint32_t *lat_w, const uint32_t *lat_h, uint32_t lat_c, const uint32_t *image_w_or_null,
-                                            const uint32_t *image_h_or_null, int n_images, sicn_ragged_ctx_coder **out)
+extern "C" int sicn_ragged_ctx_coder_create_sl(const uint32_t *lat_w, const uint32_t *lat_h, uint32_t lat_c,
+                                               const uint32_t *stream_symbols_or_null, const uint32_t *image_w_or_null,
+                                               const uint32_t *image_h_or_null, int n_images, sicn_ragged_ctx_coder **out)
 {
     if (!out) return SICN_EINVAL;
     *out = nullptr;
@@ -222,7 +231,7 @@ extern "C" int sicn_ragged_ctx_coder_create(const uint32_t *lat_w, const uint32_
     if (!coder) return SICN_ENOMEM;
     int rc = SICN_OK;
     try {
-        rc = plan_ctx(lat_w, lat_h, lat_c, image_w_or_null, image_h_or_null, n_images, true, nullptr, &coder->plan);
+        rc = plan_ctx(lat_w, lat_h, lat_c, stream_symbols_or_null, image_w_or_null, image_h_or_null, n_images, true, nullptr, &coder->plan);
         if (!rc) rc = sicn::chip_geom(nullptr);       // no device, or not a gfx950 one
         if (!rc) {
             coder->n_images = n_images;
@@ -253,6 +262,12 @@ extern "C" int sicn_ragged_ctx_coder_create(const uint32_t *lat_w, const uint32_
     }
     *out = coder;
     return SICN_OK;
+}
+
+extern "C" int sicn_ragged_ctx_coder_create(const uint32_t *lat_w, const uint32_t *lat_h, uint32_t lat_c, const uint32_t *image_w_or_null,
+                                            const uint32_t *image_h_or_null, int n_images, sicn_ragged_ctx_coder **out)
+{
+    return sicn_ragged_ctx_coder_create_sl(lat_w, lat_h, lat_c, nullptr, image_w_or_null, image_h_or_null, n_images, out);
 }
 
 extern "C" size_t sicn_ragged_ctx_coder_workspace_bytes(const sicn_ragged_ctx_coder *coder) { return coder ? (size_t)coder->plan.ws_bytes : 0; }
@@ -316,17 +331,25 @@ extern "C" int sicn_ragged_ctx_decode_async(const sicn_ragged_ctx_coder *coder, 
 }
 
 // ---- the window decoder ----------------------------------------------------------------------------------------------------------
-extern "C" int sicn_ragged_ctx_window_layout(const uint32_t *lat_w, const uint32_t *lat_h, uint32_t lat_c, const uint32_t *r0, const uint32_t *rh,
-                                             int n_images, sicn_ragged_ctx_window_image *images_or_null, uint64_t totals[2])
+extern "C" int sicn_ragged_ctx_window_layout_sl(const uint32_t *lat_w, const uint32_t *lat_h, uint32_t lat_c,
+                                                const uint32_t *stream_symbols_or_null, const uint32_t *r0, const uint32_t *rh, int n_images,
+                                                sicn_ragged_ctx_window_image *images_or_null, uint64_t totals[2])
 {
     uint64_t coder[3] = {0, 0, 0}, band = 0;
-    if (int rc = sicn_ragged_ctx_layout(lat_w, lat_h, lat_c, n_images, nullptr, coder)) return rc;
-    if (int rc = sicn_ctx_window::window_layout(lat_w, lat_h, lat_c, r0, rh, n_images, images_or_null, &band, nullptr)) return rc;
+    if (int rc = sicn_ragged_ctx_layout_sl(lat_w, lat_h, lat_c, stream_symbols_or_null, n_images, nullptr, coder)) return rc;
+    if (int rc = sicn_ctx_window::window_layout_sl(lat_w, lat_h, lat_c, stream_symbols_or_null, r0, rh, n_images, images_or_null, &band, nullptr))
+        return rc;
     if (totals) {
         totals[0] = band;
         totals[1] = coder[2];
     }
     return SICN_OK;
+}
+
+extern "C" int sicn_ragged_ctx_window_layout(const uint32_t *lat_w, const uint32_t *lat_h, uint32_t lat_c, const uint32_t *r0, const uint32_t *rh,
+                                             int n_images, sicn_ragged_ctx_window_image *images_or_null, uint64_t totals[2])
+{
+    return sicn_ragged_ctx_window_layout_sl(lat_w, lat_h, lat_c, nullptr, r0, rh, n_images, images_or_null, totals);
 }
 
 struct sicn_ragged_ctx_window {
@@ -362,7 +385,7 @@ extern "C" int sicn_ragged_ctx_window_create(const sicn_ragged_ctx_coder *coder,
         for (int i = 0; !rc && i < n; i++) {
             const CtxRow &r = coder->plan.rows[(size_t)i];
             sicn_ragged_ctx_window_image im;
-            rc = sicn_ctx_window::plan_of(r.g.W, r.g.H, r.g.C, r0[i], rh[i], at, &im);
+            rc = sicn_ctx_window::plan_of_sl(r.g.W, r.g.H, r.g.C, r.g.S, r0[i], rh[i], at, &im);
             if (rc) break;
             CtxWinRow w{};
             w.lat_bias = at - (uint64_t)im.band_row0 * r.g.W * r.g.C;

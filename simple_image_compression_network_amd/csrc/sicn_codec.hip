@@ -398,8 +398,8 @@ extern "C" int sicn_codec_parse_header(const uint8_t *h, size_t bytes, sicn_code
     info->adler32 = get32(h + 44);
     info->stream_symbols = get32(h + 36);
     if (info->mode > 4) return SICN_EINVAL;
-    if (info->mode == SICN_CODEC_RANSW ? !wstream_ok(info->stream_symbols)
-                                       : info->stream_symbols != stream_symbols(info->mode == 4 ? 3 : (int)info->mode))
+    if (info->mode == SICN_CODEC_RANSW || info->mode == 4 ? !wstream_ok(info->stream_symbols)
+                                                          : info->stream_symbols != stream_symbols((int)info->mode))
         return SICN_EINVAL;
     if ((unsigned long long)info->lat_w * info->lat_h * info->lat_c != info->n_symbols) return SICN_EINVAL;
     const uint32_t ss = info->stream_symbols;
@@ -407,7 +407,7 @@ extern "C" int sicn_codec_parse_header(const uint8_t *h, size_t bytes, sicn_code
         const uint32_t W = info->lat_w, H = info->lat_h, C = info->lat_c;
         const unsigned long long na = ((unsigned long long)(H / 2) * W + ((H & 1) ? (W + 1) / 2 : 0)) * C;
         const unsigned long long nn = ((unsigned long long)(H / 2) * W + ((H & 1) ? W / 2 : 0)) * C;
-        if (info->n_streams != (na + WSS - 1) / WSS + (nn + WSS - 1) / WSS) return SICN_EINVAL;
+        if (info->n_streams != (na + ss - 1) / ss + (nn + ss - 1) / ss) return SICN_EINVAL;
         return SICN_OK;
     }
     if (info->n_streams != (info->n_symbols + ss - 1) / ss) return SICN_EINVAL;

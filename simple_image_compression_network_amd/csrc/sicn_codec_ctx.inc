@@ -70,45 +70,59 @@ __global__ __launch_bounds__(64) void k_ctx_finish(uint32_t *__restrict__ status
 
 }  // namespace
 
-extern "C" size_t sicn_codec_ctx_max_bytes(uint32_t lat_w, uint32_t lat_h, uint32_t lat_c)
+// ---- host: one path per direction, the stream length S a parameter (header dword 9); the entry points without it are S = 16384 ----
+extern "C" size_t sicn_codec_ctx_max_bytes_sl(uint32_t lat_w, uint32_t lat_h, uint32_t lat_c, uint32_t stream_symbols)
 {
-    const CtxGeom g = ctx_geom(lat_w, lat_h, lat_c);
+    if (!wstream_ok(stream_symbols)) return 0;
+    const CtxGeom g = ctx_geom(lat_w, lat_h, lat_c, stream_symbols);
     const size_t n = (size_t)lat_w * lat_h * lat_c, ns = (size_t)g.nst[0] + g.nst[1];
     return SICN_CODEC_HEADER_BYTES + CTX_TABLE_BYTES + 4 * ns + 2 * n + 256 * ns;
 }
 
-extern "C" size_t sicn_codec_ctx_workspace_bytes(uint32_t lat_w, uint32_t lat_h, uint32_t lat_c, uint32_t n_images)
+extern "C" size_t sicn_codec_ctx_workspace_bytes_sl(uint32_t lat_w, uint32_t lat_h, uint32_t lat_c, uint32_t n_images, uint32_t stream_symbols)
 {
-    const CtxGeom g = ctx_geom(lat_w, lat_h, lat_c);
-    return (size_t)n_images * ctx_ws_bytes(g.nst[0] + g.nst[1]);
+    if (!wstream_ok(stream_symbols)) return 0;
+    const CtxGeom g = ctx_geom(lat_w, lat_h, lat_c, stream_symbols);
+    return (size_t)n_images * ctx_ws_bytes(g.nst[0] + g.nst[1], stream_symbols);
 }
 
-// n_images of one shape in slots of slot_bytes: image 0's row and the strides, or SICN_EINVAL for a shape outside the limits
+extern "C" size_t sicn_codec_ctx_max_bytes(uint32_t lat_w, uint32_t lat_h, uint32_t lat_c)
+{
+    return sicn_codec_ctx_max_bytes_sl(lat_w, lat_h, lat_c, WSS);
+}
+
+extern "C" size_t sicn_codec_ctx_workspace_bytes(uint32_t lat_w, uint32_t lat_h, uint32_t lat_c, uint32_t n_images)
+{
+    return sicn_codec_ctx_workspace_bytes_sl(lat_w, lat_h, lat_c, n_images, WSS);
+}
+
+// n_images of one shape and one stream length in slots of slot_bytes: image 0's row and the strides, or SICN_EINVAL for a shape or a
+// length outside the limits
 static int ctx_batch(CtxBatch &b, uint32_t lat_w, uint32_t lat_h, uint32_t lat_c, uint32_t img_w, uint32_t img_h, uint32_t n_images,
-                     size_t slot_bytes)
+                     size_t slot_bytes, uint32_t S)
 {
     b = CtxBatch{};
     if (n_images > 65535) return SICN_EINVAL;
-    if (int rc = ctx_row_shape(b.row0, lat_w, lat_h, lat_c, img_w, img_h)) return rc;
+    if (int rc = ctx_row_shape(b.row0, lat_w, lat_h, lat_c, img_w, img_h, S)) return rc;
     b.row0.slot_cap = ctx_slot_cap(slot_bytes);   // the caller's slots, not the layout's
     b.s_lat = (size_t)lat_w * lat_h * lat_c;
     b.s_slot = slot_bytes;
-    b.s_ws = ctx_ws_bytes(b.row0.g.nst[0] + b.row0.g.nst[1]);
+    b.s_ws = ctx_ws_bytes(b.row0.g.nst[0] + b.row0.g.nst[1], S);
     return SICN_OK;
 }
 
-extern "C" int sicn_codec_ctx_encode_batch_async(const uint8_t *latents, const uint8_t *scales, uint32_t n_images, uint32_t lat_w,
-                                                 uint32_t lat_h, uint32_t lat_c, uint32_t img_w, uint32_t img_h, uint8_t *out,
-                                                 size_t slot_bytes, sicn_codec_status *status_dev, void *workspace,
-                                                 size_t workspace_bytes, void *hip_stream)
+extern "C" int sicn_codec_ctx_encode_batch_async_sl(const uint8_t *latents, const uint8_t *scales, uint32_t n_images, uint32_t lat_w,
+                                                    uint32_t lat_h, uint32_t lat_c, uint32_t img_w, uint32_t img_h, uint8_t *out,
+                                                    size_t slot_bytes, sicn_codec_status *status_dev, void *workspace,
+                                                    size_t workspace_bytes, void *hip_stream, uint32_t stream_symbols)
 {
     if (!latents || !scales || !out || !status_dev) return SICN_EINVAL;
     CtxBatch b;
-    if (int rc = ctx_batch(b, lat_w, lat_h, lat_c, img_w, img_h, n_images, slot_bytes)) return rc;
+    if (int rc = ctx_batch(b, lat_w, lat_h, lat_c, img_w, img_h, n_images, slot_bytes, stream_symbols)) return rc;
     if (n_images == 0) return SICN_OK;
     if (((uintptr_t)latents | (uintptr_t)scales) & 3) return SICN_EINVAL;   // dword gathers
     const uint32_t n = (uint32_t)b.s_lat, ns = b.row0.g.nst[0] + b.row0.g.nst[1];
-    if (slot_bytes < sicn_codec_ctx_max_bytes(lat_w, lat_h, lat_c) || (slot_bytes & 1)) return SICN_ENOSPC;
+    if (slot_bytes < sicn_codec_ctx_max_bytes_sl(lat_w, lat_h, lat_c, stream_symbols) || (slot_bytes & 1)) return SICN_ENOSPC;
     const size_t ws1 = b.s_ws;
     if (!workspace || workspace_bytes < ws1 * n_images) return SICN_ENOSPC;
     hipStream_t stream = (hipStream_t)hip_stream;
@@ -126,14 +140,14 @@ extern "C" int sicn_codec_ctx_encode_batch_async(const uint8_t *latents, const u
     return hipGetLastError() == hipSuccess ? SICN_OK : SICN_ENODEV;
 }
 
-extern "C" int sicn_codec_ctx_decode_batch_async(const uint8_t *containers, size_t slot_bytes, const sicn_codec_status *valid_dev_or_null,
-                                                 const uint8_t *scales, uint32_t n_images, uint32_t lat_w, uint32_t lat_h, uint32_t lat_c,
-                                                 uint8_t *latents, sicn_codec_status *status_dev, void *workspace, size_t workspace_bytes,
-                                                 void *hip_stream)
+extern "C" int sicn_codec_ctx_decode_batch_async_sl(const uint8_t *containers, size_t slot_bytes, const sicn_codec_status *valid_dev_or_null,
+                                                    const uint8_t *scales, uint32_t n_images, uint32_t lat_w, uint32_t lat_h, uint32_t lat_c,
+                                                    uint8_t *latents, sicn_codec_status *status_dev, void *workspace, size_t workspace_bytes,
+                                                    void *hip_stream, uint32_t stream_symbols)
 {
     if (!containers || !scales || !latents || !status_dev || (slot_bytes & 1)) return SICN_EINVAL;
     CtxBatch b;
-    if (int rc = ctx_batch(b, lat_w, lat_h, lat_c, 0, 0, n_images, slot_bytes)) return rc;
+    if (int rc = ctx_batch(b, lat_w, lat_h, lat_c, 0, 0, n_images, slot_bytes, stream_symbols)) return rc;
     if (n_images == 0) return SICN_OK;
     if (((uintptr_t)latents | (uintptr_t)scales) & 3) return SICN_EINVAL;
     const CtxGeom &g = b.row0.g;
@@ -157,4 +171,22 @@ extern "C" int sicn_codec_ctx_decode_batch_async(const uint8_t *containers, size
     hipLaunchKernelGGL(k_stats, dim3(stats_blocks(n), n_images), dim3(256), 0, stream, latents, ws, stats_batch(n, n, ws1));
     hipLaunchKernelGGL(k_ctx_finish, dim3(1, n_images), dim3(64), 0, stream, (uint32_t *)status_dev, ws, b);
     return hipGetLastError() == hipSuccess ? SICN_OK : SICN_ENODEV;
+}
+
+extern "C" int sicn_codec_ctx_encode_batch_async(const uint8_t *latents, const uint8_t *scales, uint32_t n_images, uint32_t lat_w,
+                                                 uint32_t lat_h, uint32_t lat_c, uint32_t img_w, uint32_t img_h, uint8_t *out,
+                                                 size_t slot_bytes, sicn_codec_status *status_dev, void *workspace,
+                                                 size_t workspace_bytes, void *hip_stream)
+{
+    return sicn_codec_ctx_encode_batch_async_sl(latents, scales, n_images, lat_w, lat_h, lat_c, img_w, img_h, out, slot_bytes, status_dev,
+                                                workspace, workspace_bytes, hip_stream, WSS);
+}
+
+extern "C" int sicn_codec_ctx_decode_batch_async(const uint8_t *containers, size_t slot_bytes, const sicn_codec_status *valid_dev_or_null,
+                                                 const uint8_t *scales, uint32_t n_images, uint32_t lat_w, uint32_t lat_h, uint32_t lat_c,
+                                                 uint8_t *latents, sicn_codec_status *status_dev, void *workspace, size_t workspace_bytes,
+                                                 void *hip_stream)
+{
+    return sicn_codec_ctx_decode_batch_async_sl(containers, slot_bytes, valid_dev_or_null, scales, n_images, lat_w, lat_h, lat_c, latents,
+                                                status_dev, workspace, workspace_bytes, hip_stream, WSS);
 }

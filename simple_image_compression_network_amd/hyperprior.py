@@ -92,7 +92,7 @@ def hyper_parameters(width: int, height: int, seed: int = 0, use_gdn: bool = Tru
 
 class HyperpriorCodec:
     def __init__(self, width: int, height: int, n_images: int, seed: int = 0, device="cuda", use_gdn: bool = True,
-                 main_params=None, options=None, z_stream_symbols=None, verify_z: bool = False):
+                 main_params=None, options=None, z_stream_symbols=None, verify_z: bool = False, y_stream_symbols=None):
         import torch
         self.n, self.width, self.height = int(n_images), int(width), int(height)
         self.verify_z = bool(verify_z)
@@ -120,7 +120,8 @@ class HyperpriorCodec:
         # so a container set written by a batch of 8 decodes in a batch of 1; `z_stream_symbols` overrides it and is
         # then part of the format the decoder must be built with
         self.z_coder = codec.LatentCoder(n, zh, zw, zc, width, height, device=self.device, stream_symbols=z_stream_symbols or "auto")
-        self.y_coder = codec.ContextCoder(n, lat_h, lat_w, lat_c, width, height, device=self.device)
+        # the stream length of y (rANS-WC): None = 16384; like z's it is part of the format the decoder must be built with
+        self.y_coder = codec.ContextCoder(n, lat_h, lat_w, lat_c, width, height, device=self.device, stream_symbols=y_stream_symbols)
         for net in (self.main, self.h_a, self.h_s):
             net.workspace(n)
 
@@ -177,7 +178,8 @@ class RaggedHyperpriorCodec:
     only, so every image gets that codec's parameters.  Stage tensors (y, z, z_hat, s, y_hat) are ragged tensors; `main.views(3, y)`,
     `h_a.views(1, z)` give the per-image arrays.  Parity UNPINNED, as everything in this module."""
 
-    def __init__(self, sizes, seed: int = 0, device="cuda", use_gdn: bool = True, main_params=None, z_stream_symbols=None):
+    def __init__(self, sizes, seed: int = 0, device="cuda", use_gdn: bool = True, main_params=None, z_stream_symbols=None,
+                 y_stream_symbols=None):
         import torch
         self.sizes = [(int(w), int(h)) for w, h in sizes]
         if not self.sizes:
@@ -197,7 +199,9 @@ class RaggedHyperpriorCodec:
         # the stream length of z: codec.auto_stream_symbols of EACH image's own hyper-latent, HyperpriorCodec's rule
         self.z_coder = codec.RaggedLatentCoder([(h, w) for h, w, _ in hyp], hyp[0][2], self.sizes, stream_symbols=z_stream_symbols or "auto",
                                                device=self.device)
-        self.y_coder = codec.RaggedContextCoder([(h, w) for h, w, _ in lat], lat[0][2], self.sizes, device=self.device)
+        # the stream length of y: None = 16384 (auto_stream_symbols is not applied), one value, or one per image
+        self.y_coder = codec.RaggedContextCoder([(h, w) for h, w, _ in lat], lat[0][2], self.sizes, stream_symbols=y_stream_symbols,
+                                                device=self.device)
         u8 = dict(dtype=torch.uint8, device=self.device)
         self.y = torch.empty(self.main.nbytes(3), **u8)
         self.z = torch.empty(self.h_a.nbytes(1), **u8)
@@ -262,7 +266,7 @@ class RaggedHyperpriorCodec:
     @classmethod
     def from_archive(cls, b, seed: int = 0, device="cuda", use_gdn=None, main_params=None, images=None):
         """The codec for the images an archive names — all of them, or the selection `images` (strictly ascending indices into the
-        archive): sizes and the z stream lengths are READ from the z containers' headers, and `use_gdn` (unless given) from the tag —
+        archive): sizes and the z stream lengths are READ from the z containers' headers, the y stream lengths from the y containers', and `use_gdn` (unless given) from the tag —
         0 means an archive written without GDN.  `decode(archive=b, images=images)` then reads it."""
         info = codec.archive_info(b)
         sel = range(info["n_images"]) if images is None else codec._selection(images, n_archive=info["n_images"])
@@ -270,7 +274,8 @@ class RaggedHyperpriorCodec:
         if info["n_sections"] != 2 or any(h is None for h in heads):
             raise ValueError("not a hyperprior archive: need the sections z and y of every image")
         return cls([info["image_sizes"][i] for i in sel], seed=seed, device=device, use_gdn=info["tag"] != 0 if use_gdn is None else use_gdn,
-                   main_params=main_params, z_stream_symbols=[int(h.stream_symbols) for h in heads])
+                   main_params=main_params, z_stream_symbols=[int(h.stream_symbols) for h in heads],
+                   y_stream_symbols=[int(h[1].stream_symbols) if h[1] is not None else None for h in (info["headers"][i] for i in sel)])
 
     def _decode_scales(self, z_containers=None, y_containers=None, archive=None, images=None):
         """The front half of every decode, in full: unpack (with an archive), the z coder, h_s and its crop -> self.s.  Returns the y

@@ -15,6 +15,8 @@
  * form: a workgroup is one 16 x 16 tile of positions x 64 output channels of one image and finds that image through tables the net
  * uploads once, at creation.  A layer these kernels do not serve (sicn_kernel_for's width rules: IFM_CH % 32 == 0 and
  * OFM_CH % 16 == 0, both <= 1024, conv 3 -> N, deconv N -> 3) is SICN_EINVAL: the ragged net has no other kernel to fall back on.
+ * Since library 0.15 the two RGB shapes, conv 3 -> N and deconv N -> 3, run on packed-K kernels of their own in a net made here; same
+ * bytes (sicn_ragged_rgb.h, which also has the entry point that chooses the form and the one that names a layer's kernel).
  *
  * Activations (library 0.8, sicn_version() >= 8; declared in sicn_ragged_hyper.h).  sicn_ragged_net_create_gdn gives layer i the
  * GDN / IGDN of sicn_gdn.h in place of the reference ReLU: the layer kernel stores its pre-activation lanes and the activation
@@ -46,7 +48,8 @@ typedef struct sicn_ragged_net sicn_ragged_net;
  * out[] = { W, H, C, byte offset of the image, bytes of the whole tensor of that boundary, first work item of the image in layer l,
  *           tiles_x of the image in layer l, work items of layer l over all images }.
  * A work item is one 16 x 16 tile of the layer's M grid (conv: output pixels; deconv: input pixels, times 4 phases, the phase in
- * the low two bits); the last three fields are 0 for layer = -1. */
+ * the low two bits); the last three fields are 0 for layer = -1.  They describe the channel-generic cut; the cut a net with packed
+ * RGB ends launches is sicn_ragged_rgb_layout's (sicn_ragged_rgb.h). */
 int sicn_ragged_layout(const sicn_layer_desc *descs, int n_layers, const int32_t *widths, const int32_t *heights, int n_images,
                        int layer, int image, int64_t out[8]);
 

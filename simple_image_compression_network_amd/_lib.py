@@ -272,6 +272,14 @@ CTX_SL_ABI = {
     "sicn_ragged_ctx_window_layout_sl": (_i, [_u32p, _u32p, _u32, _u32p, _u32p, _u32p, _i, ctypes.POINTER(RaggedCtxWindowImage), _u64p]),
 }
 
+# include/sicn_ragged_rgb.h (library 0.15: a ragged net's RGB ends — conv 3 -> N, deconv N -> 3 — on packed-K kernels of their own)
+RAGGED_RGB_ABI = {
+    "sicn_ragged_net_create_rgb": (_i, [_descp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _i, _i32p, _i32p, _i, _i, ctypes.POINTER(_vp)]),
+    "sicn_ragged_net_kernel_for": (ctypes.c_char_p, [_vp, _i]),
+    "sicn_ragged_rgb_layout": (_i, [_descp, _i, _i32p, _i32p, _i, _i, _i, _i, _i64p]),
+}
+RAGGED_RGB_ENDS = {"generic": 0, "packed": 1}     # SICN_RAGGED_RGB_GENERIC / SICN_RAGGED_RGB_PACKED
+
 _lib = None
 
 
@@ -298,7 +306,7 @@ def lib() -> ctypes.CDLL:
             pass
         L = ctypes.CDLL(str(LIB_PATH))
         for name, (res, args) in {**ABI, **CODEC_ABI, **CONVLAYER_ABI, **GDN_ABI, **RAGGED_ABI, **RAGGED_HYPER_ABI, **RAGGED_CODEC_ABI, **RAGGED_CTX_ABI, **RAGGED_ARCHIVE_ABI,
-                                  **RAGGED_ARCHIVE_SELECT_ABI, **RAGGED_WINDOW_ABI, **RAGGED_CTX_WINDOW_ABI, **CTX_SL_ABI}.items():
+                                  **RAGGED_ARCHIVE_SELECT_ABI, **RAGGED_WINDOW_ABI, **RAGGED_CTX_WINDOW_ABI, **CTX_SL_ABI, **RAGGED_RGB_ABI}.items():
             fn = getattr(L, name)          # AttributeError if the ABI is incomplete
             fn.restype = res
             fn.argtypes = args

@@ -495,13 +495,18 @@ class RaggedNet(_lib.Handle):
     `EightLayersNet(w, h).forward` of every image alone.
     `descs`: any chain the ragged kernels serve instead of the eight layers (its spatial fields are ignored; `params` or
     `shared_weights` must match it, as in `EightLayersNet(descs=...)`).  `gdn`: a list of `GDN | None`, one per layer — the
-    activation in place of that layer's ReLU (sicn_ragged_net_create_gdn); one more launch per such layer, for the whole batch."""
+    activation in place of that layer's ReLU (sicn_ragged_net_create_gdn); one more launch per such layer, for the whole batch.
+    `rgb_ends`: "packed" (default) runs a conv 3 -> N and a deconv N -> 3 of the chain on the packed-K kernels of
+    include/sicn_ragged_rgb.h, "generic" on the channel-generic ones like every other layer; the bytes are the same."""
     _free = "sicn_ragged_net_free"
 
     def __init__(self, sizes, params=None, device=None, n_ch: int = 128, m_ch: int = 192,
                  shared_weights: Optional[Sequence[DeviceWeights]] = None, descs: Optional[Sequence[LayerDesc]] = None,
-                 gdn: Optional[Sequence[Optional["GDN"]]] = None):
+                 gdn: Optional[Sequence[Optional["GDN"]]] = None, rgb_ends: str = "packed"):
         import torch
+        if rgb_ends not in _lib.RAGGED_RGB_ENDS:
+            raise ValueError(f"rgb_ends: 'packed' or 'generic', not {rgb_ends!r}")
+        self.rgb_ends = rgb_ends
         L = _lib.lib()
         self.sizes = [(int(w), int(h)) for w, h in sizes]
         n_img = len(self.sizes)
@@ -524,14 +529,12 @@ class RaggedNet(_lib.Handle):
         self.gdn = list(gdn) if gdn is not None else None      # keeps the activations alive
         if self.gdn is not None and len(self.gdn) != n:
             raise ValueError("gdn must have one entry (or None) per layer")
+        ghandles = None
+        if self.gdn is not None:
+            ghandles = (ctypes.c_void_p * n)(*[(g.handle if g is not None else None) for g in self.gdn])
         with torch.cuda.device(self.device):
-            if self.gdn is not None:
-                ghandles = (ctypes.c_void_p * n)(*[(g.handle if g is not None else None) for g in self.gdn])
-                _lib.check(L.sicn_ragged_net_create_gdn(self._cdescs, handles, ghandles, n, self._widths, self._heights, n_img,
-                                                        ctypes.byref(self._h)), "sicn_ragged_net_create_gdn")
-            else:
-                _lib.check(L.sicn_ragged_net_create(self._cdescs, handles, n, self._widths, self._heights, n_img, ctypes.byref(self._h)),
-                           "sicn_ragged_net_create")
+            _lib.check(L.sicn_ragged_net_create_rgb(self._cdescs, handles, ghandles, n, self._widths, self._heights, n_img,
+                                                    _lib.RAGGED_RGB_ENDS[rgb_ends], ctypes.byref(self._h)), "sicn_ragged_net_create_rgb")
         # per boundary (-1 .. n - 1, index layer + 1): the images' shapes and byte offsets, as the library lays them out
         self._shapes, self._offsets, self._nbytes = [], [], []
         q = (ctypes.c_int64 * 8)()
@@ -557,6 +560,14 @@ class RaggedNet(_lib.Handle):
 
     def nbytes(self, layer: int) -> int:
         return self._nbytes[layer + 1]
+
+    def kernel_for(self, layer: int) -> str:
+        """The kernel `layer` runs on (sicn_ragged_net_kernel_for): "mfma_conv_any", "mfma_deconv_any", "mfma_conv_rgb_packed" or
+        "mfma_deconv_rgb_packed"."""
+        name = _lib.lib().sicn_ragged_net_kernel_for(self._h, int(layer))
+        if name is None:
+            raise ValueError("layer out of range")
+        return name.decode()
 
     def pack(self, images, layer: int = -1):
         """[H][W][C] uint8 tensors (any device), one per image -> the ragged tensor of boundary `layer` on the net's device."""

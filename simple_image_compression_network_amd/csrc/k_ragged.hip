@@ -9,6 +9,9 @@
 //                       and its 64-bit byte offsets in the layer's input and output tensors
 // Both loads are wave-uniform (they depend on blockIdx.x only) and stay in scalar registers.
 //
+// The RGB ends (conv 3 -> N, deconv N -> 3) of a SICN_RAGGED_RGB_PACKED net (include/sicn_ragged_rgb.h) run on the kernels of
+// k_ragged_rgb.hip with the same two tables; the deconv N -> 3 is then cut into one item per tile, all four phases (ragged_plan).
+//
 // A layer with a GDN / IGDN (sicn_ragged_net_create_gdn) runs the same kernel with ACT_FLOOR_RAW and then the activation of k_gdn.hip in
 // place over the whole boundary tensor: [bytes / OFM_CH][OFM_CH], no table needed.  The ragged crop at the end of this file is the cut
 // of k_ragged_window.hip at the corner of every image: the rectangles (0, 0, dst_w, dst_h), the images back to back, the same handle.
@@ -16,18 +19,15 @@
 #include <vector>
 
 #include "../../include/sicn_ragged_hyper.h"
+#include "../../include/sicn_ragged_rgb.h"
 #include "../../include/sicn_ragged_window.h"
 #include "k_any_body.hpp"
 #include "k_ragged_common.hpp"
+#include "ragged_rgb_host.hpp"
 #include "sicn_gdn_internal.h"
 #include "sicn_weights_io.h"
 
 namespace sicn {
-
-struct RaggedRow {
-    int32_t IW, IH, OW, OH, tiles_x, first_item;
-    int64_t in_off, out_off;
-};
 
 template <bool DECONV, int NT>
 __global__ __launch_bounds__(256) void k_any_ragged(const uint8_t *__restrict__ in, uint8_t *__restrict__ out, const int8_t *__restrict__ wimg,
@@ -63,6 +63,8 @@ struct RaggedBoundary {                     // one layer boundary: -1 (index 0) 
     std::vector<int64_t> off;               // [n_images + 1]: byte offsets, the last one = the tensor's bytes
 };
 struct RaggedLayerPlan {
+    bool packed = false;                    // an RGB end on the packed-K kernels (k_ragged_rgb.hip)
+    int per_tile = 1;                       // work items per 16 x 16 tile: the deconv's four phases, except in its packed form
     std::vector<int32_t> tiles_x;
     std::vector<int64_t> first_item;        // [n_images + 1]: the last one = the layer's work items
 };
@@ -72,8 +74,9 @@ struct RaggedPlan {
 };
 
 static int ragged_plan(const sicn_layer_desc *descs, int n_layers, const int32_t *widths, const int32_t *heights, int n_images,
-                       RaggedPlan *plan)
+                       int rgb_ends, RaggedPlan *plan)
 {
+    if (rgb_ends != SICN_RAGGED_RGB_GENERIC && rgb_ends != SICN_RAGGED_RGB_PACKED) return SICN_EINVAL;
     if (!descs || !widths || !heights || n_layers <= 0 || n_layers > 64 || n_images < 1) return SICN_EINVAL;
     for (int i = 0; i < n_images; i++)
         if (widths[i] < 1 || heights[i] < 1 || widths[i] > (1 << 20) || heights[i] > (1 << 20)) return SICN_EINVAL;
@@ -99,6 +102,8 @@ static int ragged_plan(const sicn_layer_desc *descs, int n_layers, const int32_t
             RaggedBoundary &bo = plan->bounds[(size_t)l + 1];
             RaggedLayerPlan &lp = plan->layers[(size_t)l];
             bo.C = d.OFM_CH;
+            lp.packed = rgb_ends == SICN_RAGGED_RGB_PACKED && ragged_rgb_packed_serves(d.IFM_CH, d.OFM_CH, d.transposed);
+            lp.per_tile = tr && !lp.packed ? 4 : 1;
             bo.W.resize((size_t)n_images);
             bo.H.resize((size_t)n_images);
             lp.tiles_x.resize((size_t)n_images);
@@ -113,7 +118,7 @@ static int ragged_plan(const sicn_layer_desc *descs, int n_layers, const int32_t
                 const int64_t mw = tr ? iw : ow, mh = tr ? ih : oh;
                 const int64_t tx = (mw + ANY_T - 1) / ANY_T, ty = (mh + ANY_T - 1) / ANY_T;
                 lp.tiles_x[(size_t)i] = (int32_t)tx;
-                lp.first_item[(size_t)i + 1] = lp.first_item[(size_t)i] + tx * ty * (tr ? 4 : 1);
+                lp.first_item[(size_t)i + 1] = lp.first_item[(size_t)i] + tx * ty * lp.per_tile;
                 if (lp.first_item[(size_t)i + 1] >= RAGGED_MAX_ITEMS) return SICN_EINVAL;
             }
         }
@@ -150,7 +155,8 @@ struct sicn_ragged_net {
     std::vector<const sicn_weights *> weights;
     std::vector<const sicn_gdn *> gdn;      // per layer: the activation in place of the ReLU, or nullptr
     std::vector<const int8_t *> wimg;       // per layer: the weights' own pack_any image, or one of `owned`
-    std::vector<int8_t *> owned;            // images packed here for weights whose family is another one (the reference's widths)
+    std::vector<int8_t *> owned;            // images packed here: for weights whose family is another one (the reference's widths), and
+                                            // the packed-K images of the RGB ends (ragged_rgb_host.hpp)
     RaggedRow *d_rows = nullptr;            // [n_layers][n_images]
     uint32_t *d_tile_image = nullptr;       // the layers' tile -> image maps back to back
     std::vector<size_t> map_at;             // per layer: its first entry in d_tile_image
@@ -162,7 +168,7 @@ extern "C" int sicn_ragged_layout(const sicn_layer_desc *descs, int n_layers, co
 {
     if (!out) return SICN_EINVAL;
     RaggedPlan p;
-    if (int rc = ragged_plan(descs, n_layers, widths, heights, n_images, &p)) return rc;
+    if (int rc = ragged_plan(descs, n_layers, widths, heights, n_images, SICN_RAGGED_RGB_GENERIC, &p)) return rc;
     if (layer < -1 || layer >= n_layers || image < 0 || image >= n_images) return SICN_EINVAL;
     const RaggedBoundary &b = p.bounds[(size_t)(layer + 1)];
     out[0] = b.W[(size_t)image];
@@ -198,12 +204,40 @@ extern "C" int sicn_ragged_net_create(const sicn_layer_desc *descs, sicn_weights
 extern "C" int sicn_ragged_net_create_gdn(const sicn_layer_desc *descs, sicn_weights *const *weights, const sicn_gdn *const *gdn, int n_layers,
                                           const int32_t *widths, const int32_t *heights, int n_images, sicn_ragged_net **out)
 {
+    return sicn_ragged_net_create_rgb(descs, weights, gdn, n_layers, widths, heights, n_images, SICN_RAGGED_RGB_PACKED, out);
+}
+
+extern "C" int sicn_ragged_rgb_layout(const sicn_layer_desc *descs, int n_layers, const int32_t *widths, const int32_t *heights, int n_images,
+                                      int rgb_ends, int layer, int image, int64_t out[3])
+{
+    if (!out) return SICN_EINVAL;
+    RaggedPlan p;
+    if (int rc = ragged_plan(descs, n_layers, widths, heights, n_images, rgb_ends, &p)) return rc;
+    if (layer < 0 || layer >= n_layers || image < 0 || image >= n_images) return SICN_EINVAL;
+    const RaggedLayerPlan &lp = p.layers[(size_t)layer];
+    out[0] = lp.first_item[(size_t)image];
+    out[1] = lp.tiles_x[(size_t)image];
+    out[2] = lp.first_item[(size_t)n_images];
+    return SICN_OK;
+}
+
+extern "C" const char *sicn_ragged_net_kernel_for(const sicn_ragged_net *net, int layer)
+{
+    if (!net || layer < 0 || layer >= net->n_layers) return nullptr;
+    const bool tr = net->descs[(size_t)layer].transposed == 1;
+    if (net->plan.layers[(size_t)layer].packed) return tr ? "mfma_deconv_rgb_packed" : "mfma_conv_rgb_packed";
+    return tr ? "mfma_deconv_any" : "mfma_conv_any";
+}
+
+extern "C" int sicn_ragged_net_create_rgb(const sicn_layer_desc *descs, sicn_weights *const *weights, const sicn_gdn *const *gdn, int n_layers,
+                                          const int32_t *widths, const int32_t *heights, int n_images, int rgb_ends, sicn_ragged_net **out)
+{
     if (!out) return SICN_EINVAL;
     *out = nullptr;
     if (!weights) return SICN_EINVAL;
     sicn_ragged_net *net = new (std::nothrow) sicn_ragged_net();
     if (!net) return SICN_ENOMEM;
-    int rc = ragged_plan(descs, n_layers, widths, heights, n_images, &net->plan);
+    int rc = ragged_plan(descs, n_layers, widths, heights, n_images, rgb_ends, &net->plan);
     for (int l = 0; !rc && l < n_layers; l++) {
         const sicn_weights *w = weights[l];
         if (!w || w->cin != descs[l].IFM_CH || w->cout != descs[l].OFM_CH || w->transposed != descs[l].transposed) rc = SICN_EINVAL;
@@ -224,7 +258,7 @@ extern "C" int sicn_ragged_net_create_gdn(const sicn_layer_desc *descs, sicn_wei
         for (int l = 0; l < n_layers; l++) {
             const RaggedBoundary &bi = net->plan.bounds[(size_t)l], &bo = net->plan.bounds[(size_t)l + 1];
             const RaggedLayerPlan &lp = net->plan.layers[(size_t)l];
-            const int per_tile = descs[l].transposed ? 4 : 1;
+            const int per_tile = lp.per_tile;
             net->map_at.push_back(map.size());
             for (int i = 0; i < n_images; i++) {
                 rows[(size_t)l * n_images + i] = RaggedRow{bi.W[(size_t)i], bi.H[(size_t)i], bo.W[(size_t)i], bo.H[(size_t)i], lp.tiles_x[(size_t)i],
@@ -241,16 +275,23 @@ extern "C" int sicn_ragged_net_create_gdn(const sicn_layer_desc *descs, sicn_wei
         // packs the images of the family the shape runs on); pack it here from the plain [cout][25 cin] copy every handle has
         for (int l = 0; !rc && l < n_layers; l++) {
             const sicn_weights *w = weights[l];
-            if (w->d_w_any) {
+            const bool packed = net->plan.layers[(size_t)l].packed;
+            if (!packed && w->d_w_any) {
                 net->wimg.push_back(w->d_w_any);
                 continue;
             }
-            std::vector<int8_t> okc((size_t)w->cout * 25 * w->cin), img(any_bytes(w->cin, w->cout));
+            const size_t img_bytes = !packed ? any_bytes(w->cin, w->cout) : w->transposed ? rgb_deconv_bytes(w->cin) : rgb_conv_bytes(w->cout);
+            std::vector<int8_t> okc((size_t)w->cout * 25 * w->cin), img(img_bytes);
             if (hipMemcpy(okc.data(), w->d_w_okc, okc.size(), hipMemcpyDeviceToHost) != hipSuccess) {
                 rc = SICN_ENODEV;
                 break;
             }
-            pack_any(okc.data(), w->cin, w->cout, img.data());
+            if (!packed)
+                pack_any(okc.data(), w->cin, w->cout, img.data());
+            else if (w->transposed)
+                pack_rgb_deconv(okc.data(), w->cin, img.data());
+            else
+                pack_rgb_conv(okc.data(), w->cout, img.data());
             int8_t *dev = nullptr;
             const bool ok = upload(img.data(), img.size(), &dev);
             if (dev) net->owned.push_back(dev);
@@ -292,7 +333,11 @@ extern "C" int sicn_ragged_net_forward(const sicn_ragged_net *net, int first, in
         const uint32_t floor2 = g ? ACT_FLOOR_RAW : ACT_FLOOR_RELU;
         const size_t out_bytes = (size_t)net->plan.bounds[(size_t)l + 1].off[(size_t)net->n_images];
         hipError_t e;
-        if (d.transposed)
+        if (net->plan.layers[(size_t)l].packed)
+            e = d.transposed ? launch_ragged_rgb_deconv(cur, dst, wimg, w->d_bias, rows, map, d.IFM_CH, items, floor2, stream)
+                             : launch_ragged_rgb_conv(cur, (size_t)net->plan.bounds[(size_t)l].off[(size_t)net->n_images], dst, wimg,
+                                                      w->d_bias, rows, map, d.OFM_CH, items, floor2, stream);
+        else if (d.transposed)
             e = d.OFM_CH == 3 ? launch_ragged_as<true, 1>(cur, dst, wimg, w->d_bias, rows, map, d.IFM_CH, d.OFM_CH, items, floor2, stream)
                               : launch_ragged_as<true, 4>(cur, dst, wimg, w->d_bias, rows, map, d.IFM_CH, d.OFM_CH, items, floor2, stream);
         else

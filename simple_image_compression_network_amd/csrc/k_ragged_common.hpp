@@ -8,6 +8,13 @@
 
 namespace sicn {
 constexpr int64_t RAGGED_MAX_ITEMS = 0x7fffffffLL;   // a launch has fewer work items than this (grid.x)
+
+// one image in one layer of a ragged net (k_ragged.hip builds the table, k_ragged.hip and k_ragged_rgb.hip read it): its sizes, its
+// first work item and its byte offsets in the layer's input and output tensors
+struct RaggedRow {
+    int32_t IW, IH, OW, OH, tiles_x, first_item;
+    int64_t in_off, out_off;
+};
 }
 
 #ifdef __HIPCC__

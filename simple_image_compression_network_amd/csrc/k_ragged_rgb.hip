@@ -1,0 +1,81 @@
+// Ragged nets, the RGB ends in their packed-K form (include/sicn_ragged_rgb.h): conv 3 -> N and deconv N -> 3 over n images of n
+// different sizes, one launch per layer.  The tile bodies are rgb_conv_tile() / rgb_deconv_tile() (k_rgb_ragged_body.hpp), functions
+// of one image; the kernels here only resolve item -> image from the tables of k_ragged.hip (tile_image, RaggedRow), with
+// wave-uniform loads pinned to scalar registers, as k_any_ragged does.
+//
+// Grid: x = the layer's work items over all images.  Conv: one 16 x 16 tile of output positions, the same cut and the same
+// first_item as the channel-generic form; y = 1 — the blocks of 64 output channels are a loop inside the workgroup (the kernel
+// strides them by gridDim.y), so the patch and its expansion are paid once per tile.  Deconv: one 16 x 16 tile of input positions
+// with all four phases: tile_image is indexed by the item itself and first_item is the per-tile cut's.
+#include "k_ragged_common.hpp"
+#include "k_rgb_ragged_body.hpp"
+
+namespace sicn {
+
+struct RaggedItem {
+    int IW, IH, OW, OH, ty, tx;
+    uint64_t in_off, out_off;
+};
+
+__device__ __forceinline__ RaggedItem ragged_item(const RaggedRow *__restrict__ rows, const uint32_t *__restrict__ tile_image)
+{
+    const int item = (int)blockIdx.x;
+    const RaggedRow *row = rows + uni(tile_image[item]);
+    RaggedItem r;
+    r.IW = (int)uni((uint32_t)row->IW);
+    r.IH = (int)uni((uint32_t)row->IH);
+    r.OW = (int)uni((uint32_t)row->OW);
+    r.OH = (int)uni((uint32_t)row->OH);
+    const int tiles_x = (int)uni((uint32_t)row->tiles_x);
+    const int local = item - (int)uni((uint32_t)row->first_item);
+    r.in_off = uni((uint64_t)row->in_off);
+    r.out_off = uni((uint64_t)row->out_off);
+    r.ty = local / tiles_x;
+    r.tx = local - r.ty * tiles_x;
+    return r;
+}
+
+__global__ __launch_bounds__(256) void k_rgb_conv_ragged(const uint8_t *__restrict__ in, uint64_t in_bytes, uint8_t *__restrict__ out,
+                                                         const int8_t *__restrict__ wimg, const int8_t *__restrict__ bias,
+                                                         const RaggedRow *__restrict__ rows, const uint32_t *__restrict__ tile_image, int O,
+                                                         uint32_t floor2)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t smem[RGBC_LDS];
+    const RaggedItem r = ragged_item(rows, tile_image);
+    rgb_conv_tile(in + r.in_off, in, in + in_bytes, out + r.out_off, wimg, bias, r.IW, r.IH, r.OW, r.OH, O, r.ty * ANY_T, r.tx * ANY_T,
+                  (int)blockIdx.y, (int)gridDim.y, floor2, smem);
+}
+
+__global__ __launch_bounds__(256) void k_rgb_deconv_ragged(const uint8_t *__restrict__ in, uint8_t *__restrict__ out,
+                                                           const int8_t *__restrict__ wimg, const int8_t *__restrict__ bias,
+                                                           const RaggedRow *__restrict__ rows, const uint32_t *__restrict__ tile_image, int C,
+                                                           uint32_t floor2)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t smem[RGBD_LDS];
+    const RaggedItem r = ragged_item(rows, tile_image);
+    rgb_deconv_tile(in + r.in_off, out + r.out_off, wimg, bias, r.IW, r.IH, C, r.OW, r.ty * ANY_T, r.tx * ANY_T, floor2, smem);
+}
+
+bool ragged_rgb_packed_serves(int cin, int cout, int transposed)
+{
+    if (!any_supported(cin, cout, transposed)) return false;
+    return transposed ? cout == 3 : cin == 3;
+}
+
+hipError_t launch_ragged_rgb_conv(const uint8_t *in, size_t in_bytes, uint8_t *out, const int8_t *wimg, const int8_t *bias,
+                                  const RaggedRow *rows, const uint32_t *tile_image, int cout, unsigned items, uint32_t floor2,
+                                  hipStream_t stream)
+{
+    hipLaunchKernelGGL(k_rgb_conv_ragged, dim3(items, 1, 1), dim3(256), 0, stream, in, (uint64_t)in_bytes, out, wimg, bias, rows, tile_image,
+                       cout, floor2);
+    return hipGetLastError();
+}
+
+hipError_t launch_ragged_rgb_deconv(const uint8_t *in, uint8_t *out, const int8_t *wimg, const int8_t *bias, const RaggedRow *rows,
+                                    const uint32_t *tile_image, int cin, unsigned items, uint32_t floor2, hipStream_t stream)
+{
+    hipLaunchKernelGGL(k_rgb_deconv_ragged, dim3(items, 1, 1), dim3(256), 0, stream, in, out, wimg, bias, rows, tile_image, cin, floor2);
+    return hipGetLastError();
+}
+
+}  // namespace sicn

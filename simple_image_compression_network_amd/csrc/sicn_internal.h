@@ -123,6 +123,16 @@ void pack_any(const int8_t *w_okc, int cin, int cout, int8_t *dst);
 hipError_t launch_any(const LayerGeom &g, const sicn_weights &w, const uint8_t *in, uint8_t *out, int n_images, hipStream_t stream,
                       bool relu = true);
 
+// k_ragged_rgb.hip: the packed-K kernels of a ragged net's RGB ends (include/sicn_ragged_rgb.h) — conv 3 -> N, deconv N -> 3; the
+// tables are k_ragged.hip's (RaggedRow: k_ragged_common.hpp), the weight images pack_rgb_conv / pack_rgb_deconv's (ragged_rgb_host.hpp)
+struct RaggedRow;
+bool ragged_rgb_packed_serves(int cin, int cout, int transposed);
+hipError_t launch_ragged_rgb_conv(const uint8_t *in, size_t in_bytes, uint8_t *out, const int8_t *wimg, const int8_t *bias,
+                                  const RaggedRow *rows, const uint32_t *tile_image, int cout, unsigned items, uint32_t floor2,
+                                  hipStream_t stream);
+hipError_t launch_ragged_rgb_deconv(const uint8_t *in, uint8_t *out, const int8_t *wimg, const int8_t *bias, const RaggedRow *rows,
+                                    const uint32_t *tile_image, int cin, unsigned items, uint32_t floor2, hipStream_t stream);
+
 // k_ragged_codec.hip: a ragged coder as the window decoder (k_ragged_window.hip) sees it — [n_images] CoderRow (k_codec_body.hpp)
 // on the host and on the device, both owned by the coder
 struct RaggedCoderView {

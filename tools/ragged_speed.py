@@ -2,7 +2,8 @@
 """Ragged batch against the ways the library could run a folder of differently sized images before it (profiles/ragged_batch_speed.txt).
 
 A seeded mix of 64 image sizes, W and H each drawn from {256, 384, 512, 640, 768}, PARAM weights, whole 8-layer net with the latent:
-  ragged   one RaggedNet call: 8 launches for the whole mix (the channel-generic MFMA kernels, csrc/k_ragged.hip)
+  ragged   one RaggedNet call: 8 launches for the whole mix (the channel-generic MFMA kernels, csrc/k_ragged.hip; --rgb-ends
+           packed | generic: the RGB ends on the packed-K kernels of csrc/k_ragged_rgb.hip or on the channel-generic ones)
   loop     (a) one EightLayersNet per distinct size, created before timing, called once per image (the tuned kernels)
   grouped  (b) the same with the images of equal size grouped into one batch per size
   ceiling  the same number of pixels as ONE equal-size batch of 64 on the tuned kernels: what this untuned form is held to
@@ -43,7 +44,8 @@ def per_layer_from_trace(path, calls_hint=None):
         return []
     key = {k.lower(): k for k in rows[0]}
     name, t0, t1 = key["kernel_name"], key["start_timestamp"], key["end_timestamp"]
-    rows = sorted((r for r in rows if "k_any_ragged" in r[name]), key=lambda r: int(r[t0]))
+    rows = sorted((r for r in rows if any(k in r[name] for k in ("k_any_ragged", "k_rgb_conv_ragged", "k_rgb_deconv_ragged"))),
+                  key=lambda r: int(r[t0]))
     rows = rows[len(rows) % 8:]                       # whole calls only
     out = []
     for l in range(8):
@@ -61,6 +63,7 @@ def main():
     ap.add_argument("--images", type=int, default=64)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--seconds", type=float, default=0.5)
+    ap.add_argument("--rgb-ends", choices=["packed", "generic"], default="packed", help="the form of the ragged net's RGB ends")
     ap.add_argument("--only", choices=["ragged", "loop", "grouped", "ceiling"])
     ap.add_argument("--calls", type=int, default=20)
     ap.add_argument("--kernel-trace", help="a rocprofv3 *_kernel_trace.csv of an `--only ragged` run: print the per-layer table")
@@ -81,7 +84,7 @@ def main():
     weights = [api.DeviceWeights(d, w, b) for d, (w, b) in zip(eight_layer_descs(16, 16), api.load_param_weights())]
 
     # ---- the variants: every buffer is allocated before timing
-    ragged = api.RaggedNet(sizes, shared_weights=weights)
+    ragged = api.RaggedNet(sizes, shared_weights=weights, rgb_ends=a.rgb_ends)
     r_in = ragged.pack(images)
     r_out = torch.empty(ragged.nbytes(7), dtype=torch.uint8, device="cuda")
     r_lat = torch.empty(ragged.nbytes(3), dtype=torch.uint8, device="cuda")
@@ -160,7 +163,8 @@ def main():
 
     lines = []
     counts = {s: len(idx) for s, idx in groups.items()}
-    lines.append(f"tools/ragged_speed.py --seed {a.seed} --images {a.images} --rounds {a.rounds} --seconds {a.seconds}")
+    lines.append(f"tools/ragged_speed.py --seed {a.seed} --images {a.images} --rounds {a.rounds} --seconds {a.seconds} --rgb-ends {a.rgb_ends}")
+    lines.append("ragged kernels per layer: " + " ".join(ragged.kernel_for(l) for l in range(8)))
     lines.append(f"device: {torch.cuda.get_device_name(0)}; {a.images} images, {len(distinct)} distinct sizes, {pixels / 1e6:.2f} Mpixel in all; PARAM weights")
     lines.append("sizes W x H (count): " + ", ".join(f"{w}x{h} ({counts[(w, h)]})" for w, h in distinct))
     lines.append(f"outputs of ragged, loop and grouped byte-equal (reconstruction and latent of all {a.images} images): {equal}; "
@@ -186,7 +190,8 @@ def main():
         for l, kern, us, n in per_layer_from_trace(a.kernel_trace):
             total += us
             items = _items(api, ragged, l)
-            lines.append(f"  layer {l}  {us:9.1f} us  {items:7d} work items x {(ragged.descs[l].OFM_CH + 63) // 64} channel blocks  {kern}  ({n} dispatches)")
+            blocks = 1 if "rgb_packed" in ragged.kernel_for(l) else (ragged.descs[l].OFM_CH + 63) // 64
+            lines.append(f"  layer {l}  {us:9.1f} us  {items:7d} work items x {blocks} channel blocks  {kern}  ({n} dispatches)")
         lines.append(f"  sum      {total:9.1f} us of {med['ragged'] * 1e3:.1f} us per call measured above")
     text = "\n".join(lines)
     print(text)
@@ -197,10 +202,10 @@ def main():
 
 def _items(api, net, layer):
     import ctypes
-    q = (ctypes.c_int64 * 8)()
-    api._lib.check(api._lib.lib().sicn_ragged_layout(net._cdescs, len(net.descs), net._widths, net._heights, len(net.sizes), layer, 0, q),
-                   "sicn_ragged_layout")
-    return int(q[7])
+    q = (ctypes.c_int64 * 3)()
+    api._lib.check(api._lib.lib().sicn_ragged_rgb_layout(net._cdescs, len(net.descs), net._widths, net._heights, len(net.sizes),
+                                                         api._lib.RAGGED_RGB_ENDS[net.rgb_ends], layer, 0, q), "sicn_ragged_rgb_layout")
+    return int(q[2])
 
 
 if __name__ == "__main__":

@@ -216,10 +216,18 @@ int sicn_net_forward(const sicn_net *net, int first_layer, int last_layer, const
  * sicn_debug_net_columns: what a call over [first_layer, last_layer] would do — per layer of the net the columns it computes
  * (8 = all) and the output channels the call's next layer reads.
  * sicn_debug_net_input_halves: per layer of the net the 64-channel halves of its input that the same call would read: 1 or 2 for a
- * layer on "l7_rgb", 2 for every other layer (and outside [first_layer, last_layer]). */
+ * layer on "l7_rgb", 2 for every other layer (and outside [first_layer, last_layer]).
+ * Since library 0.16 (sicn_version() >= 16) the first layer of the reference's net (conv 3 -> 128 on "l0_rgb", no sicn_gdn, not the
+ * call's last or tapped layer) neither computes nor stores the fourth 32-channel group of its output where the next layer reads at
+ * most 96 of its channels and takes them in the internal GROUP layout; the net owns the permuted copies this needs as above.
+ * sicn_debug_net_groups: per layer of the net the 32-channel groups the same call would compute and store (groups_out: 3 or 4 for
+ * that layer, 4 for every other one) and those the layer that wrote its input computed (groups_in; 4 for the call's first layer and
+ * outside [first_layer, last_layer]). */
 int sicn_debug_net_columns(const sicn_net *net, int first_layer, int last_layer, int tap_layer, int n_images, int32_t *columns,
                            int32_t *live_outputs);
 int sicn_debug_net_input_halves(const sicn_net *net, int first_layer, int last_layer, int tap_layer, int n_images, int32_t *halves);
+int sicn_debug_net_groups(const sicn_net *net, int first_layer, int last_layer, int tap_layer, int n_images, int32_t *groups_out,
+                          int32_t *groups_in);
 /* eight_layers_net(in, out, numReps): the whole chain; latent_or_null receives layer 3's output. */
 int sicn_eight_layers_net(const sicn_net *net, const uint8_t *in, uint8_t *out,
                           uint8_t *latent_or_null, int n_images, void *workspace,

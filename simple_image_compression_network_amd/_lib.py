@@ -62,6 +62,7 @@ ABI = {
     "sicn_debug_chip": (_i, [ctypes.POINTER(ctypes.c_int32)]),
     "sicn_debug_net_columns": (_i, [_vp, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
     "sicn_debug_net_input_halves": (_i, [_vp, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_int32)]),
+    "sicn_debug_net_groups": (_i, [_vp, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
 }
 
 

@@ -24,12 +24,17 @@ namespace sicn {
 // expands the next tile's pixels LDS -> LDS, runs its MFMAs and issues its 8 stores per wave
 // (lanes outside the image: out-of-range offset of a buffer descriptor), separated by a raw barrier.
 // The two workgroups of a CU cover each other's prologue.
-template <int NTJ>
+// NTJ = 32-channel groups of the output LAYOUT (COUT = 32 NTJ: the image stride, the weight image, the bias).  NG = groups that are
+// computed and stored: NG < NTJ leaves the planes NG .. NTJ - 1 of the GROUP layout as the tensor held them (their channels are dead by
+// the net's plan, sicn_live.h; launch_l0 hands such a kernel nothing but the GROUP layout).  The weight image is loaded whole, its rows
+// j >= NG are never read; accumulators, MFMAs and stores run over NG groups.  k_l0<4> = k_l0<4, 4> is the kernel it was.
+template <int NTJ, int NG = NTJ>
 __global__ __launch_bounds__(256, 2) void k_l0(const uint8_t *__restrict__ in, uint8_t *__restrict__ out,
                                                const int8_t *__restrict__ w_l0,
                                                const int8_t *__restrict__ bias, int IW, int IH, int OW,
                                                int OH, int tiles_y, int ty_per, int out_layout, uint32_t act_floor)
 {
+    static_assert(NG >= 1 && NG <= NTJ, "computed groups of the NTJ groups of the layout");
     constexpr int COUT = NTJ * 32;
     constexpr int TB = COUT * KSTEP;
     constexpr int WBYTES = 5 * TB;
@@ -75,9 +80,9 @@ __global__ __launch_bounds__(256, 2) void k_l0(const uint8_t *__restrict__ in, u
             __builtin_amdgcn_global_load_lds(GLB_PTR(w_l0 + piece * 1024 + lane * 16), LDS_PTR(wl + piece * 1024), 16, 0, 0);
         if (tid < COUT / 4) ((uint32_t *)bias_lds)[tid] = ((const uint32_t *)bias)[tid];
     }
-    uint32_t wrow[NTJ];
+    uint32_t wrow[NG];
 #pragma unroll
-    for (int j = 0; j < NTJ; j++) wrow[j] = (uint32_t)((j * 32 + m) * 32 + ((kh ^ ((m >> 3) & 1)) << 4));
+    for (int j = 0; j < NG; j++) wrow[j] = (uint32_t)((j * 32 + m) * 32 + ((kh ^ ((m >> 3) & 1)) << 4));
     // the builtin (not inline asm): hipcc then KNOWS no LDS-DMA is pending and puts no vmcnt(0) of
     // its own in front of the LDS accesses of the loop
     __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0)
@@ -97,9 +102,9 @@ __global__ __launch_bounds__(256, 2) void k_l0(const uint8_t *__restrict__ in, u
             l0_expand(rsrc, nxt, img_byte0, tid + 256, Y0 + L0_TY, X0, IW, IH);
         }
 
-        v16i acc[2][NTJ];
+        v16i acc[2][NG];
 #pragma unroll
-        for (int j = 0; j < NTJ; j++) {
+        for (int j = 0; j < NG; j++) {
             const v4i b4 = *(const v4i *)(bias_lds + j * 32 + 16 * kh);
 #pragma unroll
             for (int r = 0; r < 16; r++) {
@@ -110,9 +115,9 @@ __global__ __launch_bounds__(256, 2) void k_l0(const uint8_t *__restrict__ in, u
         }
 #pragma unroll
         for (int ky = 0; ky < 5; ky++) {
-            v4i wf[NTJ], pf[2];
+            v4i wf[NG], pf[2];
 #pragma unroll
-            for (int j = 0; j < NTJ; j++) wf[j] = *(const v4i *)(wl + ky * TB + wrow[j]);
+            for (int j = 0; j < NG; j++) wf[j] = *(const v4i *)(wl + ky * TB + wrow[j]);
 #pragma unroll
             for (int i = 0; i < 2; i++) {
                 const uint8_t *src = patch + (2 * (2 * w + i) + ky) * L0_PITCH + 8 * m + 16 * kh;
@@ -120,7 +125,7 @@ __global__ __launch_bounds__(256, 2) void k_l0(const uint8_t *__restrict__ in, u
                 pf[i] = v4i{(int)lo.x, (int)lo.y, (int)hi.x, (int)hi.y};
             }
 #pragma unroll
-            for (int j = 0; j < NTJ; j++)
+            for (int j = 0; j < NG; j++)
 #pragma unroll
                 for (int i = 0; i < 2; i++)
                     acc[i][j] = __builtin_amdgcn_mfma_i32_32x32x32_i8(wf[j], pf[i], acc[i][j], 0, 0, 0);
@@ -131,7 +136,7 @@ __global__ __launch_bounds__(256, 2) void k_l0(const uint8_t *__restrict__ in, u
             const int gy = Y0 + 2 * w + i, gx = X0 + m;
             const bool ok = gy < OH && gx < OW;
 #pragma unroll
-            for (int j = 0; j < NTJ; j++) {
+            for (int j = 0; j < NG; j++) {
                 const v16i a = acc[i][j];
                 v4i v;
                 v[0] = (int)pack4_relu7(a[0], a[1], a[2], a[3], act_floor & ACT_FLOOR_MASK);
@@ -171,25 +176,34 @@ void pack_l0(const int8_t *w_okc, int cout, int8_t *dst)
         }
 }
 
+template <int NG>
+static hipError_t launch_l0_groups(const LayerGeom &g, const sicn_weights &w, const uint8_t *in, uint8_t *out, int n_images, hipStream_t stream,
+                                   int out_layout, const L0Plan &p, bool relu)
+{
+    const dim3 grid((unsigned)p.tiles_x, (unsigned)p.y_chunks, (unsigned)n_images);
+    const size_t lds = 5 * 128 * KSTEP + 2 * L0_PATCH + 128 + L0_RAW_BYTES;
+    hipError_t e = hipFuncSetAttribute((const void *)k_l0<4, NG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    // the nt policy follows the bytes of the whole tensor, as the consumer fetches it, whatever the groups stored here
+    hipLaunchKernelGGL((k_l0<4, NG>), grid, dim3(256), lds, stream, in, out, w.d_w_l0, w.d_bias, g.IW, g.IH, g.OW, g.OH, p.tiles_y, p.ty_per,
+                       out_layout,
+                       (relu ? ACT_FLOOR_RELU : ACT_FLOOR_RAW) | (nt_store_wanted((size_t)g.OH * g.OW * g.COUT * n_images) ? ACT_NT_STORE : 0u));
+    return hipGetLastError();
+}
+
 hipError_t launch_l0(const LayerGeom &g, const sicn_weights &w, const uint8_t *in, uint8_t *out,
-                     int n_images, hipStream_t stream, int out_layout, const sicn_options &o, const ChipGeom &chip, bool relu)
+                     int n_images, hipStream_t stream, int out_layout, const sicn_options &o, const ChipGeom &chip, bool relu, int groups)
 {
     // runs of at most L0_CHUNK tiles (the LDS holds a run's pixels), evened out; small images: shorter runs, enough workgroups
     // (about four per CU, sicn_plan.h); the test hook (strip_chunks) can only shorten them
     const L0Plan p = plan_l0(g.OW, g.OH, n_images, false, o.strip_chunks, chip);
-    dim3 grid((unsigned)p.tiles_x, (unsigned)p.y_chunks, (unsigned)n_images);
     if ((size_t)g.IH * g.IW * 3 * (size_t)n_images + 4 >= (size_t)OOB) return hipErrorInvalidValue;
     if ((size_t)g.OH * g.OW * g.COUT >= (size_t)OOB) return hipErrorInvalidValue;   // buffer-descriptor stores
-    if (g.COUT == 128) {
-        const size_t lds = 5 * 128 * KSTEP + 2 * L0_PATCH + 128 + L0_RAW_BYTES;
-        hipError_t e = hipFuncSetAttribute((const void *)k_l0<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k_l0<4>, grid, dim3(256), lds, stream, in, out, w.d_w_l0, w.d_bias, g.IW, g.IH,
-                           g.OW, g.OH, p.tiles_y, p.ty_per, out_layout,
-                           (relu ? ACT_FLOOR_RELU : ACT_FLOOR_RAW) | (nt_store_wanted((size_t)g.OH * g.OW * g.COUT * n_images) ? ACT_NT_STORE : 0u));
-    } else
-        return hipErrorInvalidValue;
-    return hipGetLastError();
+    if (g.COUT != 128) return hipErrorInvalidValue;
+    // three groups: only where a group is a plane of its own (in NHWC the fourth group is a quarter of every line)
+    if (groups == 3 && out_layout == LAYOUT_GROUP) return launch_l0_groups<3>(g, w, in, out, n_images, stream, out_layout, p, relu);
+    if (groups != 4) return hipErrorInvalidValue;
+    return launch_l0_groups<4>(g, w, in, out, n_images, stream, out_layout, p, relu);
 }
 
 // =============================================================================================

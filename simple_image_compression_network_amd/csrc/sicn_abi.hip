@@ -134,7 +134,7 @@ extern "C" void sicn_options_init(sicn_options *opt)
 // 0.7: ragged latent coder (include/sicn_ragged_codec.h, k_ragged_codec.hip).  Still 0.7 (no symbol, struct or byte changed): the
 // synchronous rANS-W calls are the asynchronous pair with one image, so sicn_codec_workspace_bytes(SICN_CODEC_RANSW, n) also holds
 // that pair's status words (it grew by less than 1 KiB) and sicn_codec_decode needs sicn_codec_batch_workspace_bytes_sl(n, 1, length)
-extern "C" int sicn_version(void) { return 1000 * 0 + 15; }
+extern "C" int sicn_version(void) { return 1000 * 0 + 16; }
 extern "C" int sicn_gdn_spec_version(void) { return 2; }
 
 extern "C" int sicn_has_alt_kernels(void) { return 0; }   // kept for callers that probe it: the alternate kernel build is gone
@@ -200,6 +200,8 @@ struct LaunchArgs {
     unsigned long long *deal;
     int columns;               // accumulator columns the wide family computes (sicn_live.h); 8: all
     int columns_in;            // the same of the layer that wrote `in` in this call; 8: all, or nothing is known of it
+    int groups;                // 32-channel groups a non-wide producer of 128 channels computes and stores (sicn_live.h); 4: all
+    int groups_in;             // the same of the layer that wrote `in` in this call; 4: all, or nothing is known of it
 };
 
 struct Family {
@@ -240,7 +242,7 @@ hipError_t l0_launch(const LaunchArgs &a, bool *act_done)
         *act_done = true;
         return launch_l0_gdn(a.g, a.w, *a.gdn, a.in, a.out, a.n_images, a.stream, a.out_layout, a.o, a.chip);
     }
-    return launch_l0(a.g, a.w, a.in, a.out, a.n_images, a.stream, a.out_layout, a.o, a.chip, a.gdn == nullptr);
+    return launch_l0(a.g, a.w, a.in, a.out, a.n_images, a.stream, a.out_layout, a.o, a.chip, a.gdn == nullptr, a.groups);
 }
 void l0_plan(const LayerGeom &g, int n_images, const sicn_options &o, const ChipGeom &chip, int32_t out[12])
 {
@@ -433,7 +435,7 @@ static int link_layout(const sicn_layer_desc &p, const sicn_layer_desc &c, const
 static int run_layer(const sicn_layer_desc *d, const sicn_weights *w, const uint8_t *in, uint8_t *out,
                      int n_images, hipStream_t stream, int want_transposed, const sicn_options &o, int in_layout = 0,
                      int out_layout = 0, const sicn_gdn *gdn = nullptr, unsigned long long *deal = nullptr, int columns = 8,
-                     int columns_in = 8)
+                     int columns_in = 8, int groups = 4, int groups_in = 4)
 {
     int rc = sicn_validate_desc(d);
     if (rc) return rc;
@@ -447,7 +449,7 @@ static int run_layer(const sicn_layer_desc *d, const sicn_weights *w, const uint
     ChipGeom chip;
     if ((rc = chip_geom(&chip)) != SICN_OK) return rc;   // no device, or not a gfx950 one
     bool act_done = false;
-    const LaunchArgs args{g, *w, in, out, n_images, stream, in_layout, out_layout, o, chip, gdn, deal, columns, columns_in};
+    const LaunchArgs args{g, *w, in, out, n_images, stream, in_layout, out_layout, o, chip, gdn, deal, columns, columns_in, groups, groups_in};
     hipError_t e = layer_family(*d, o, gdn != nullptr).launch(args, &act_done);
     if (act_done) gdn = nullptr;
     if (e == hipSuccess && gdn) e = launch_gdn(*gdn, out, out_layout, d->OFM_ROW, d->OFM_COL, n_images, stream);
@@ -520,8 +522,9 @@ extern "C" int sicn_net_create_opt(const sicn_layer_desc *descs, sicn_weights *c
 }
 
 // The live-channel tables of a new net and the permuted copies of the weights they call for.  Layer l may skip accumulator columns
-// (live[l].nj < 8) when it is a 128 -> 128 layer without a GDN whose consumer has enough all-zero input channels; whether it does
-// is decided per call (sicn_net_forward).  May throw std::bad_alloc.
+// (live[l].nj < 8) when it is a 128 -> 128 layer without a GDN whose consumer has enough all-zero input channels, and a whole
+// 32-channel group (live[l].ng < 4) when it is a 3 -> 128 layer without a GDN whose consumer reads at most 96 channels; whether it
+// does is decided per call (sicn_net_forward).  May throw std::bad_alloc.
 static int make_live_plan(sicn_net *net)
 {
     const size_t n = net->descs.size();
@@ -540,7 +543,8 @@ static int make_live_plan(sicn_net *net)
         const sicn_weights &w = *net->weights[l];
         for (int v = 1; v < 4; v++) {
             const bool in_p = (v & 2) != 0, out_p = (v & 1) != 0;
-            if ((in_p && !(l > 0 && net->live[l - 1].nj < live::COLS)) || (out_p && net->live[l].nj >= live::COLS)) continue;
+            // a layer has a p where it may skip columns (a wide layer) or a group (layer 0's family): sicn_live.h
+            if ((in_p && !(l > 0 && !net->live[l - 1].p.empty())) || (out_p && net->live[l].p.empty())) continue;
             std::vector<int8_t> okc = w.h_w_okc, bias = w.h_bias;
             if (in_p) {
                 std::vector<int8_t> t(okc.size());
@@ -635,6 +639,22 @@ static int call_columns(const sicn_net *net, int l, int first, int last, int tap
     return live::columns(net->live, l, first, last, tap_layer, wide);
 }
 
+// the layout layer l of a call that ends at `last` writes: the last and the tapped layer leave the chain in NHWC
+static int call_out_layout(const sicn_net *net, int l, int last, int tap_layer)
+{
+    return (l < last && l != tap_layer)
+               ? link_layout(net->descs[(size_t)l], net->descs[(size_t)l + 1], net->opt, net->gdn[(size_t)l] != nullptr, net->gdn[(size_t)l + 1] != nullptr)
+               : 0;
+}
+
+// the 32-channel groups layer l computes and stores in a call over [first, last]: fewer than all where the net's tables allow it
+// (make_live_plan: a 3 -> 128 layer without a GDN, which then runs on l0_rgb) and the layer is in the middle of the chain, untapped, and
+// writes the GROUP layout, whose planes are whole groups
+static int call_groups(const sicn_net *net, int l, int first, int last, int tap_layer, int out_layout)
+{
+    return live::groups(net->live, l, first, last, tap_layer, out_layout == 1);
+}
+
 // what a call would do, for tests: per layer of the net the columns computed (8 outside [first, last]) and the output channels that
 // the call's next layer reads
 extern "C" int sicn_debug_net_columns(const sicn_net *net, int first, int last, int tap_layer, int n_images, int32_t *columns,
@@ -666,9 +686,24 @@ extern "C" int sicn_debug_net_input_halves(const sicn_net *net, int first, int l
         const bool l7 = layer_family(net->descs[l], net->opt, net->gdn[l] != nullptr).kind == KK_L7_RGB;
         if (l7 && l7_reads_one_half(cols_before, cur_layout)) halves[l] = 1;
         cols_before = call_columns(net, l, first, last, tap_layer, n_images, chip);
-        cur_layout = (l < last && l != tap_layer)
-                         ? link_layout(net->descs[l], net->descs[l + 1], net->opt, net->gdn[l] != nullptr, net->gdn[l + 1] != nullptr)
-                         : 0;
+        cur_layout = call_out_layout(net, l, last, tap_layer);
+    }
+    return SICN_OK;
+}
+
+// what a call would do, for tests: per layer of the net the 32-channel groups it computes and stores, and the groups the layer that
+// wrote its input computed (4 outside [first, last] and for the first layer of the call) — the walk of sicn_net_forward
+extern "C" int sicn_debug_net_groups(const sicn_net *net, int first, int last, int tap_layer, int n_images, int32_t *groups_out,
+                                     int32_t *groups_in)
+{
+    if (!net || !groups_out || !groups_in || n_images <= 0) return SICN_EINVAL;
+    const int n_layers = (int)net->descs.size();
+    if (first < 0 || last >= n_layers || first > last) return SICN_EINVAL;
+    for (int l = 0; l < n_layers; l++) groups_out[l] = groups_in[l] = live::GROUPS;
+    int groups_before = live::GROUPS;
+    for (int l = first; l <= last; l++) {
+        groups_in[l] = groups_before;
+        groups_before = groups_out[l] = call_groups(net, l, first, last, tap_layer, call_out_layout(net, l, last, tap_layer));
     }
     return SICN_OK;
 }
@@ -711,29 +746,31 @@ extern "C" int sicn_net_forward(const sicn_net *net, int first, int last, const 
         const int at = net->ev_next.fetch_add(need, std::memory_order_relaxed);
         if (at + need <= sicn_net::EV_RING) slot0 = at;   // ring full: this call is not timed
     }
-    int cols_before = live::COLS;   // the columns the previous layer of this call computed: fewer than all = its channels are permuted
+    // the columns and groups the previous layer of this call computed: fewer than all of either = it wrote its channels in the order of its p
+    int cols_before = live::COLS, groups_before = live::GROUPS;
     for (int l = first; l <= last; l++) {
-        // the live-channel plan of this call: a layer on the wide family computes only the columns the next layer reads (sicn_live.h)
+        // intermediates nobody outside sees travel in the grouped layout when both neighbours can
+        const int out_layout = call_out_layout(net, l, last, tap_layer);
+        // the live-channel plan of this call: a layer on the wide family computes only the columns the next layer reads, layer 0's
+        // family only the groups (sicn_live.h)
         const int cols = call_columns(net, l, first, last, tap_layer, n_images, chip);
-        const int variant = 2 * (cols_before < live::COLS) + (cols < live::COLS);
+        const int groups = call_groups(net, l, first, last, tap_layer, out_layout);
+        const int variant = live::variant(cols_before, groups_before, cols, groups);
         const sicn_weights *wl = variant ? net->derived[l][(size_t)variant] : net->weights[l];
         if (!wl) return SICN_EINVAL;
-        const int cols_in = cols_before;
+        const int cols_in = cols_before, groups_in = groups_before;
         cols_before = cols;
+        groups_before = groups;
         // a tapped layer (the latent) is written straight into the caller's buffer and the next layer reads it there: no copy
         // (round 3 copied it device-to-device behind the layer: 4.8 us per forward pass on small inputs, 15 us on 8 x 4K)
         uint8_t *dst = (l == last) ? out : (l == tap_layer ? tap_out : pp[(l - first) & 1]);
-        // intermediates nobody outside sees travel in the grouped layout when both neighbours can
-        const int out_layout = (l < last && l != tap_layer)
-                                   ? link_layout(net->descs[l], net->descs[l + 1], net->opt, net->gdn[l] != nullptr, net->gdn[l + 1] != nullptr)
-                                   : 0;
         const int ev = slot0 >= 0 ? slot0 + (l - first) : -1;
         if (ev >= 0) {
             net->ev_layer[ev].store(-1, std::memory_order_relaxed);   // becomes l once both events are recorded
             if (hipEventRecord(net->ev_begin[ev], stream) != hipSuccess) return SICN_ENODEV;
         }
         int rc = run_layer(&net->descs[l], wl, cur, dst, n_images, stream, -1, net->opt, cur_layout, out_layout,
-                           net->gdn[l], deal_base ? deal_base + (size_t)l * DEAL_WORDS : nullptr, cols, cols_in);
+                           net->gdn[l], deal_base ? deal_base + (size_t)l * DEAL_WORDS : nullptr, cols, cols_in, groups, groups_in);
         if (rc) return rc;
         if (ev >= 0) {
             if (hipEventRecord(net->ev_end[ev], stream) != hipSuccess) return SICN_ENODEV;

@@ -105,8 +105,11 @@ bool pipelined_supported(const LayerGeom &g, int tile_x);
 hipError_t launch_pipelined(const LayerGeom &g, const sicn_weights &w, const uint8_t *in, uint8_t *out, int n_images,
                             hipStream_t stream, int in_layout, int out_layout, bool relu, int tile_x, bool split_channels,
                             const ChipGeom &chip);
+// groups = 3: the kernel computes and stores the 32-channel groups 0 .. 2 only (out_layout GROUP: plane 3 stays what it held); the
+// caller knows that the weight rows 96 .. 127 of `w` belong to channels nobody reads (sicn_live.h)
 hipError_t launch_l0(const LayerGeom &g, const sicn_weights &w, const uint8_t *in, uint8_t *out,
-                     int n_images, hipStream_t stream, int out_layout, const sicn_options &o, const ChipGeom &chip, bool relu = true);
+                     int n_images, hipStream_t stream, int out_layout, const sicn_options &o, const ChipGeom &chip, bool relu = true,
+                     int groups = 4);
 hipError_t launch_l7(const LayerGeom &g, const sicn_weights &w, const uint8_t *in, uint8_t *out,
                      int n_images, hipStream_t stream, int in_layout, const sicn_options &o, const ChipGeom &chip, int halves = 2);
 

@@ -9,6 +9,11 @@
 // The layer's own weight rows and bias are packed in that order, the consumer's K index is permuted by the same p: both are copies
 // of w_okc ([cout][25 cin], k = tap cin + c) with rows or columns moved, which then go through the ordinary packers.  The bytes at
 // positions nobody computes are undefined; they meet zero weights, and integer arithmetic makes that exact.
+//
+// A layer that is not a 128 -> 128 layer but whose 128 output channels leave in the GROUP layout ([n][C / 32][H][W][32]: the layer-0
+// RGB family, cin = 3) has no columns to skip, but it can skip a whole 32-channel GROUP, which is a plane of the tensor: with at most
+// 96 live channels it computes and stores NG = 3 groups, and p puts the live channels, ascending, at the positions 0, 1, 2, ... and the
+// dead ones, ascending, behind them.  Plane 3 then holds dead channels only and stays what the workspace held.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -21,6 +26,8 @@ namespace live {
 constexpr int CH = 128;                      // channels of the wide family (128 -> 128)
 constexpr int COLS = 8;                      // accumulator columns of 16 channels
 constexpr int WIDTHS[] = {3, 5, 8};          // the column counts kernels are built for (8: k_mfma16x.hip, today's kernels)
+constexpr int GROUPS = 4;                    // 32-channel groups = planes of the GROUP layout
+constexpr int GROUP_CH = 32;
 
 constexpr int column_of(int pos) { return 4 * (pos >> 6) + ((pos >> 2) & 3); }
 
@@ -66,6 +73,20 @@ inline std::vector<int> permutation(const std::vector<uint8_t> &mask, int nj)
     return p;
 }
 
+// a non-wide producer's group count: 3 where the live channels fit three planes, otherwise all 4 (only these two are built)
+inline int built_groups(int n_live) { return n_live <= 3 * GROUP_CH ? 3 : GROUPS; }
+
+// p[c] for a layer that writes whole groups: live channels ascending to 0, 1, 2, ..., dead channels ascending to the rest
+inline std::vector<int> group_permutation(const std::vector<uint8_t> &mask)
+{
+    std::vector<int> p((size_t)CH, -1);
+    int at = 0;
+    for (int pass = 0; pass < 2; pass++)
+        for (int c = 0; c < CH; c++)
+            if ((mask[(size_t)c] != 0) == (pass == 0)) p[(size_t)c] = at++;
+    return p;
+}
+
 // the producer's side: row p[c] of dst = row c of w_okc, bias likewise (cout = CH rows of 25 cin)
 inline void permute_outputs(const int8_t *w_okc, const int8_t *bias, int cin, const std::vector<int> &p, int8_t *w_dst, int8_t *b_dst)
 {
@@ -99,7 +120,8 @@ struct Layer {
     // made by make_tables():
     int live_out = 0;             // output channels the chain needs from it (cout: all)
     int nj = COLS;                // built width for them; COLS where the layer can never skip a column
-    std::vector<int> p;           // nj < COLS: where it writes its channels
+    int ng = GROUPS;              // groups a non-wide producer of 128 channels computes; GROUPS where it can never skip one
+    std::vector<int> p;           // nj < COLS or ng < GROUPS: where it writes its channels (empty: in their own order)
 };
 
 // creation: layer i + 1 is layer i's only consumer.  force_generic: no layer runs on the wide family.
@@ -110,11 +132,15 @@ inline void make_tables(std::vector<Layer> &L, bool force_generic)
         Layer &l = L[i];
         l.live_out = l.cout;
         l.nj = COLS;
+        l.ng = GROUPS;
         l.p.clear();
         if (i + 1 < n && !l.gdn && (int)L[i + 1].in_mask.size() == l.cout) l.live_out = count_live(L[i + 1].in_mask);
         const bool wide_shape = l.cin == CH && l.cout == CH;
         if (wide_shape && !l.gdn && !force_generic && i + 1 < n) l.nj = built_width(l.live_out);
         if (l.nj < COLS) l.p = permutation(L[i + 1].in_mask, l.nj);
+        const bool rgb_shape = l.cin == 3 && l.cout == CH;   // the layer-0 RGB family: 128 channels out in the GROUP layout
+        if (rgb_shape && !l.gdn && !force_generic && i + 1 < n && (int)L[i + 1].in_mask.size() == l.cout) l.ng = built_groups(l.live_out);
+        if (l.ng < GROUPS) l.p = group_permutation(L[i + 1].in_mask);
     }
 }
 
@@ -130,6 +156,22 @@ inline int columns(const std::vector<Layer> &L, int i, int first, int last, int 
 {
     if (i < first || i >= last || i == tap_layer || !wide) return COLS;
     return L[(size_t)i].nj;
+}
+
+// one call: the groups layer i computes and stores.  group_layout: its output leaves in the GROUP layout in this call.
+inline int groups(const std::vector<Layer> &L, int i, int first, int last, int tap_layer, bool group_layout)
+{
+    if (i < first || i >= last || i == tap_layer || !group_layout) return GROUPS;
+    return L[(size_t)i].ng;
+}
+
+// one call: a layer that skipped columns or a group wrote its channels in the order of its p, and which copy of a layer's weights a
+// call takes follows from that on both sides: 2 (the layer in front of it in this call wrote permuted channels) + 1 (it does itself);
+// 0 is the caller's own handle
+inline bool wrote_permuted(int cols, int groups) { return cols < COLS || groups < GROUPS; }
+inline int variant(int cols_in, int groups_in, int cols, int groups)
+{
+    return 2 * (int)wrote_permuted(cols_in, groups_in) + (int)wrote_permuted(cols, groups);
 }
 
 }  // namespace live

@@ -281,6 +281,38 @@ RAGGED_RGB_ABI = {
 }
 RAGGED_RGB_ENDS = {"generic": 0, "packed": 1}     # SICN_RAGGED_RGB_GENERIC / SICN_RAGGED_RGB_PACKED
 
+
+class RaggedRoiSlot(ctypes.Structure):
+    """ctypes image of `sicn_ragged_roi_slot` (include/sicn_ragged_roi_move.h)."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("image", "w", "h")]
+
+
+class RaggedRoiPlaced(ctypes.Structure):
+    """ctypes image of `sicn_ragged_roi_placed` (include/sicn_ragged_roi_move.h)."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("x0", "y0", "c0", "r0", "cw", "rh", "x", "y")] + [("flags", ctypes.c_uint32)]
+
+
+class RaggedRoiMoveSlot(ctypes.Structure):
+    """ctypes image of `sicn_ragged_roi_move_slot` (include/sicn_ragged_roi_move.h)."""
+    _fields_ = [(n, ctypes.c_uint64) for n in ("band_offset", "latent_offset", "recon_offset", "roi_offset", "workspace_offset")] + \
+               [(n, ctypes.c_uint32) for n in ("cw_cap", "rh_cap", "max_streams", "first_item")]
+
+
+_i32 = ctypes.c_int32
+_slotp = ctypes.POINTER(RaggedRoiSlot)
+# include/sicn_ragged_roi_move.h (library 0.17: the ROI decode with rectangles read from device memory on every call — 4 + 1 launches)
+RAGGED_ROI_MOVE_ABI = {
+    "sicn_ragged_roi_move_capacity": (_i, [_i, _i32, _i32, _i32, _i32, _i32, _i32, _i32p]),
+    "sicn_ragged_roi_move_place": (_i, [_i, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, ctypes.POINTER(RaggedRoiPlaced)]),
+    "sicn_ragged_roi_move_layout": (_i, [_u32p, _u32p, _u32, _u32p, _u32p, _u32p, _i, _slotp, _i, ctypes.POINTER(RaggedRoiMoveSlot), _u64p]),
+    "sicn_ragged_roi_move_create": (_i, [_vp, _slotp, _i, ctypes.POINTER(_vp)]),
+    "sicn_ragged_roi_move_free": (None, [_vp]),
+    "sicn_ragged_roi_move_workspace_bytes": (_sz, [_vp]),
+    "sicn_ragged_roi_move_decode_async": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "sicn_ragged_roi_move_cut_async": (_i, [_vp, _vp, _vp, _vp]),
+}
+ROI_MOVE_CLAMPED = 1      # SICN_ROI_MOVE_CLAMPED: flag bit 0, the position was clamped into the image
+
 _lib = None
 
 
@@ -307,7 +339,7 @@ def lib() -> ctypes.CDLL:
             pass
         L = ctypes.CDLL(str(LIB_PATH))
         for name, (res, args) in {**ABI, **CODEC_ABI, **CONVLAYER_ABI, **GDN_ABI, **RAGGED_ABI, **RAGGED_HYPER_ABI, **RAGGED_CODEC_ABI, **RAGGED_CTX_ABI, **RAGGED_ARCHIVE_ABI,
-                                  **RAGGED_ARCHIVE_SELECT_ABI, **RAGGED_WINDOW_ABI, **RAGGED_CTX_WINDOW_ABI, **CTX_SL_ABI, **RAGGED_RGB_ABI}.items():
+                                  **RAGGED_ARCHIVE_SELECT_ABI, **RAGGED_WINDOW_ABI, **RAGGED_CTX_WINDOW_ABI, **CTX_SL_ABI, **RAGGED_RGB_ABI, **RAGGED_ROI_MOVE_ABI}.items():
             fn = getattr(L, name)          # AttributeError if the ABI is incomplete
             fn.restype = res
             fn.argtypes = args
@@ -323,10 +355,29 @@ class Handle:
     def __del__(self):
         try:
             if getattr(self, "_h", None) and _lib is not None:
-                getattr(_lib, self._free)(self._h)
+                # The free functions call hipFree, which must not land inside a stream capture: the garbage collector may run
+                # this for an object of an earlier reference cycle at any allocation, also between two launches that are being
+                # captured, and the captured graph then loses the order of its nodes.  Such an object waits for the next free
+                # outside a capture.
+                if _capturing():
+                    _deferred.append((self._free, self._h))
+                else:
+                    while _deferred:
+                        name, h = _deferred.pop()
+                        getattr(_lib, name)(h)
+                    getattr(_lib, self._free)(self._h)
                 self._h = None
         except Exception:       # interpreter shutdown: module globals may already be gone
             pass
+
+
+_deferred = []      # (free function, handle) of objects collected while a stream capture was under way
+
+
+def _capturing() -> bool:
+    import sys
+    torch = sys.modules.get("torch")
+    return bool(torch is not None and torch.cuda.is_initialized() and torch.cuda.is_current_stream_capturing())
 
 
 def check(code: int, what: str) -> None:

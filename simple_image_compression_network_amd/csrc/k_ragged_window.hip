@@ -288,8 +288,13 @@ int sicn::ragged_cut_run(const sicn_ragged_cut *cut, const uint8_t *src, uint8_t
 {
     if (!cut || !src || !dst) return SICN_EINVAL;
     if (int rc = chip_geom(nullptr)) return rc;
+    return ragged_cut_launch(cut->d_rows, cut->d_item_image, cut->items, src, dst, hip_stream);
+}
+
+int sicn::ragged_cut_launch(const void *d_rows, const uint32_t *d_item_image, unsigned items, const uint8_t *src, uint8_t *dst, void *hip_stream)
+{
     const int ptr16 = ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0;
-    hipLaunchKernelGGL(k_ragged_cut, dim3(cut->items), dim3(256), 0, (hipStream_t)hip_stream, src, dst, cut->d_rows, cut->d_item_image, ptr16);
+    hipLaunchKernelGGL(k_ragged_cut, dim3(items), dim3(256), 0, (hipStream_t)hip_stream, src, dst, (const CutRow *)d_rows, d_item_image, ptr16);
     return hipGetLastError() == hipSuccess ? SICN_OK : SICN_ENODEV;
 }
 

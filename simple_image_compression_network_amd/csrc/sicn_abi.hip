@@ -134,7 +134,7 @@ extern "C" void sicn_options_init(sicn_options *opt)
 // 0.7: ragged latent coder (include/sicn_ragged_codec.h, k_ragged_codec.hip).  Still 0.7 (no symbol, struct or byte changed): the
 // synchronous rANS-W calls are the asynchronous pair with one image, so sicn_codec_workspace_bytes(SICN_CODEC_RANSW, n) also holds
 // that pair's status words (it grew by less than 1 KiB) and sicn_codec_decode needs sicn_codec_batch_workspace_bytes_sl(n, 1, length)
-extern "C" int sicn_version(void) { return 1000 * 0 + 16; }
+extern "C" int sicn_version(void) { return 1000 * 0 + 17; }
 extern "C" int sicn_gdn_spec_version(void) { return 2; }
 
 extern "C" int sicn_has_alt_kernels(void) { return 0; }   // kept for callers that probe it: the alternate kernel build is gone

@@ -153,6 +153,9 @@ int ragged_cut_layout(const int32_t *src_w, const int32_t *src_h, const sicn_rag
 int ragged_cut_create(const int32_t *src_w, const int32_t *src_h, const sicn_ragged_rect *rects, int channels,
                       const uint64_t *src_offset_or_null, int n_images, sicn_ragged_cut **out);
 int ragged_cut_run(const sicn_ragged_cut *cut, const uint8_t *src, uint8_t *dst, void *hip_stream);
+// the same kernel over tables that are not a sicn_ragged_cut's own (k_ragged_roi_move.hip writes its rows on the stream): d_rows is
+// [images] sicn_window::CutRow, d_item_image [items], both in device memory.  Enqueue only; SICN_OK or SICN_ENODEV
+int ragged_cut_launch(const void *d_rows, const uint32_t *d_item_image, unsigned items, const uint8_t *src, uint8_t *dst, void *hip_stream);
 
 size_t l0_bytes(int cout);
 void pack_l0(const int8_t *w_okc, int cout, int8_t *dst);

@@ -313,6 +313,37 @@ RAGGED_ROI_MOVE_ABI = {
 }
 ROI_MOVE_CLAMPED = 1      # SICN_ROI_MOVE_CLAMPED: flag bit 0, the position was clamped into the image
 
+
+class RaggedCtxRoiPlaced(ctypes.Structure):
+    """ctypes image of `sicn_ragged_ctx_roi_placed` (include/sicn_ragged_ctx_roi_move.h)."""
+    _fields_ = [("px", RaggedRoiPlaced), ("first_stream", ctypes.c_uint32 * 2), ("end_stream", ctypes.c_uint32 * 2)] + \
+               [(n, ctypes.c_uint32) for n in ("band_row0", "band_rows", "symbols", "pad")] + \
+               [(n, ctypes.c_uint64) for n in ("lat_bias", "cut_offset")]
+
+
+class RaggedCtxRoiMoveSlot(ctypes.Structure):
+    """ctypes image of `sicn_ragged_ctx_roi_move_slot` (include/sicn_ragged_ctx_roi_move.h)."""
+    _fields_ = [(n, ctypes.c_uint64) for n in ("band_offset", "latent_offset", "recon_offset", "roi_offset", "meta_offset")] + \
+               [(n, ctypes.c_uint32) for n in ("cw_cap", "rh_cap", "band_rows_cap")] + \
+               [(n, ctypes.c_uint32 * 2) for n in ("max_streams", "first_item", "items")] + [("pad", ctypes.c_uint32)]
+
+
+_u64 = ctypes.c_uint64
+# include/sicn_ragged_ctx_roi_move.h (the moving ROI decode of the hyperprior configuration: prepare 3 launches per set of containers,
+# decode 6 enqueued operations + cut 1 per move; sicn_version() stays 17 — these symbols being present is the marker)
+RAGGED_CTX_ROI_MOVE_ABI = {
+    "sicn_ragged_ctx_roi_move_capacity": (_i, [_u32, _u32, _u32, _u32, _u32, _u32p]),
+    "sicn_ragged_ctx_roi_move_place": (_i, [_i32, _i32, _i32, _i32, _u32, _u32, _i32, _i32, _i32, _i32, _u64, ctypes.POINTER(RaggedCtxRoiPlaced)]),
+    "sicn_ragged_ctx_roi_move_layout": (_i, [_u32p, _u32p, _u32, _u32p, _u32p, _u32p, _i, _slotp, _i, ctypes.POINTER(RaggedCtxRoiMoveSlot), _u64p]),
+    "sicn_ragged_ctx_roi_move_create": (_i, [_vp, _slotp, _i, ctypes.POINTER(_vp)]),
+    "sicn_ragged_ctx_roi_move_free": (None, [_vp]),
+    "sicn_ragged_ctx_roi_move_workspace_bytes": (_sz, [_vp]),
+    "sicn_ragged_ctx_roi_move_prepare_async": (_i, [_vp, _vp, _vp, _vp, _sz, _vp]),
+    "sicn_ragged_ctx_roi_move_decode_async": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "sicn_ragged_ctx_roi_move_cut_async": (_i, [_vp, _vp, _vp, _vp]),
+}
+CTX_ROI_MOVE_STREAMS_PER_ITEM = 8      # SICN_CTX_ROI_MOVE_STREAMS_PER_ITEM
+
 _lib = None
 
 
@@ -339,7 +370,8 @@ def lib() -> ctypes.CDLL:
             pass
         L = ctypes.CDLL(str(LIB_PATH))
         for name, (res, args) in {**ABI, **CODEC_ABI, **CONVLAYER_ABI, **GDN_ABI, **RAGGED_ABI, **RAGGED_HYPER_ABI, **RAGGED_CODEC_ABI, **RAGGED_CTX_ABI, **RAGGED_ARCHIVE_ABI,
-                                  **RAGGED_ARCHIVE_SELECT_ABI, **RAGGED_WINDOW_ABI, **RAGGED_CTX_WINDOW_ABI, **CTX_SL_ABI, **RAGGED_RGB_ABI, **RAGGED_ROI_MOVE_ABI}.items():
+                                  **RAGGED_ARCHIVE_SELECT_ABI, **RAGGED_WINDOW_ABI, **RAGGED_CTX_WINDOW_ABI, **CTX_SL_ABI, **RAGGED_RGB_ABI, **RAGGED_ROI_MOVE_ABI,
+                                  **RAGGED_CTX_ROI_MOVE_ABI}.items():
             fn = getattr(L, name)          # AttributeError if the ABI is incomplete
             fn.restype = res
             fn.argtypes = args

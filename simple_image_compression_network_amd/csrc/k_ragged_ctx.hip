@@ -270,6 +270,15 @@ extern "C" int sicn_ragged_ctx_coder_create(const uint32_t *lat_w, const uint32_
     return sicn_ragged_ctx_coder_create_sl(lat_w, lat_h, lat_c, nullptr, image_w_or_null, image_h_or_null, n_images, out);
 }
 
+void sicn::ragged_ctx_coder_view(const sicn_ragged_ctx_coder *coder, RaggedCoderView *v)
+{
+    v->n_images = coder->n_images;
+    v->rows_host = coder->plan.rows.data();
+    v->d_rows = coder->d_rows;
+    v->row_bytes = sizeof(CtxRow);
+    v->ws_bytes = coder->plan.ws_bytes;
+}
+
 extern "C" size_t sicn_ragged_ctx_coder_workspace_bytes(const sicn_ragged_ctx_coder *coder) { return coder ? (size_t)coder->plan.ws_bytes : 0; }
 
 extern "C" int sicn_ragged_ctx_encode_async(const sicn_ragged_ctx_coder *coder, const uint8_t *latents, const uint8_t *scales,

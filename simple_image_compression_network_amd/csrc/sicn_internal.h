@@ -32,6 +32,7 @@ inline LayerGeom geom_of(const sicn_layer_desc &d)
 }  // namespace sicn
 
 struct sicn_ragged_coder;   // k_ragged_codec.hip
+struct sicn_ragged_ctx_coder;   // k_ragged_ctx.hip
 struct sicn_ragged_cut;     // k_ragged_window.hip
 struct sicn_ragged_rect;    // include/sicn_ragged_window.h
 
@@ -145,6 +146,9 @@ struct RaggedCoderView {
     uint64_t ws_bytes;
 };
 void ragged_coder_view(const sicn_ragged_coder *coder, RaggedCoderView *v);
+// k_ragged_ctx.hip: the same of a ragged ctx coder as the moving ROI decode (k_ragged_ctx_roi_move.hip) sees it — [n_images] CtxRow
+// (k_ctx_body.hpp); host only
+void ragged_ctx_coder_view(const sicn_ragged_ctx_coder *coder, RaggedCoderView *v);
 
 // k_ragged_window.hip: the one rectangle copy of the ragged family, behind sicn_ragged_cut_* (sicn_ragged_window.h) as they stand and
 // behind sicn_ragged_crop_* (sicn_ragged_hyper.h, k_ragged.hip) as the cut at the corner.  Arguments and codes: sicn_ragged_cut_*

@@ -30,7 +30,7 @@ import numpy as np
 from . import api, codec
 from .config import LayerDesc
 
-__all__ = ["HyperpriorCodec", "RaggedHyperpriorCodec", "RaggedHyperpriorRoi", "random_gdn_params", "random_layer_params", "hyper_descs", "hyper_parameters"]
+__all__ = ["HyperpriorCodec", "RaggedHyperpriorCodec", "RaggedHyperpriorRoi", "MovingHyperpriorRoi", "random_gdn_params", "random_layer_params", "hyper_descs", "hyper_parameters"]
 
 
 def random_gdn_params(rng, channels: int):
@@ -303,6 +303,11 @@ class RaggedHyperpriorCodec:
         """A RaggedHyperpriorRoi over this codec: one pixel rectangle (x0, y0, w, h), or None, per image."""
         return RaggedHyperpriorRoi(self, rects)
 
+    def moving_roi(self, slots):
+        """A MovingHyperpriorRoi over this codec: `slots` = (image, w, h) per slot, positions given per `decode` call, from device
+        memory."""
+        return MovingHyperpriorRoi(self, slots)
+
     def decode(self, out=None, z_containers=None, y_containers=None, archive=None, images=None, rois=None):
         """Containers (default: the last encode's; else lists of `bytes`, one per image; or `archive`, what `archive()` returned) ->
         the reconstructions, a ragged tensor of main's boundary 7 (`main.cropped(out)` cuts them to the images' sizes).  An archive is
@@ -418,3 +423,170 @@ class RaggedHyperpriorRoi:
         """The codec's `check()` in its order — archive, z, then y with the image named — with this object's window as the y decoder."""
         self.codec._last_roi = self
         self.codec.check()
+
+
+class MovingHyperpriorRoi(api._lib.Handle):
+    """Pixel rectangles of fixed SIZE whose POSITIONS are read from device memory on every call, decoded from a
+    RaggedHyperpriorCodec's containers (include/sicn_ragged_ctx_roi_move.h).  Made once for a list of slots; what does not depend on
+    a rectangle runs once per set of containers, in `prepare`:
+
+        unpack (an archive), the z coder, h_s and its crop   codec._decode_scales -> codec.s, the FULL scale maps
+        parse, tables, scan of the y containers' fixed part  three launches over the images the slots name
+
+    and `decode(xy)` then costs its own enqueued operations and nothing else — no allocation, no upload, no host synchronisation:
+
+        placement, band memset, anchor streams, non-anchor streams, verdicts, latent cut   six (five without non-anchor capacity)
+        api.RaggedNet 4 .. 7    a net made for the sizes (16 cw_cap, 16 rh_cap) on `codec.main`'s weights, descs and GDN objects
+        the pixel cut           one
+
+    fourteen with GDN, eleven without.  Same bytes as `codec.decode` + `main.cropped`, sliced.  slots: (image, w, h) per slot, `image`
+    an index into the codec's batch; several slots may name one image, in any order.  A position outside [0, image - size] is
+    clamped and bit 0 of the slot's `.flags` word says so.  `.status`: device int32 [n_slots][2], the verdicts per slot;
+    `.flags`: device int32 [n_slots].  The containers must stay the bytes `prepare` read until the last `decode` of them has run.
+    Also `codec.moving_roi(slots)`."""
+    _free = "sicn_ragged_ctx_roi_move_free"
+
+    def __init__(self, codec_, slots):
+        import ctypes
+
+        import torch
+        _lib = api._lib
+        L = _lib.lib()
+        self.codec = codec_
+        net, c = codec_.main, codec_.y_coder
+        self.slots = [tuple(int(v) for v in s) for s in slots]
+        n = len(self.slots)
+        if n < 1 or any(len(s) != 3 for s in self.slots):
+            raise ValueError("slots: at least one (image, w, h)")
+        for img, w, h in self.slots:
+            if not 0 <= img < len(net.sizes):
+                raise ValueError(f"slot image {img}: the net has {len(net.sizes)} images")
+            if w < 1 or h < 1 or w > net.sizes[img][0] or h > net.sizes[img][1]:
+                raise ValueError(f"a {w} x {h} rectangle is empty or larger than the {net.sizes[img][0]} x {net.sizes[img][1]} image")
+        self.device = codec_.device
+        self._cslots = (_lib.RaggedRoiSlot * n)(*[_lib.RaggedRoiSlot(*s) for s in self.slots])
+        self.layout = (_lib.RaggedCtxRoiMoveSlot * n)()
+        totals = (ctypes.c_uint64 * 7)()
+        _lib.check(L.sicn_ragged_ctx_roi_move_layout(c._lat_w, c._lat_h, c.lat_c, c._wss, c._img_w, c._img_h, len(c.shapes), self._cslots, n,
+                                                     self.layout, totals), "sicn_ragged_ctx_roi_move_layout")
+        self.band_bytes, self.latent_bytes, self.recon_bytes, self.roi_bytes, ws_bytes = (int(v) for v in totals[:5])
+        self.items = (int(totals[5]), int(totals[6]))
+        self._h = ctypes.c_void_p()
+        with torch.cuda.device(self.device):
+            _lib.check(L.sicn_ragged_ctx_roi_move_create(c._h, self._cslots, n, ctypes.byref(self._h)), "sicn_ragged_ctx_roi_move_create")
+        # the window net: layers 4 .. on the main net's weights, descs and GDN objects over the sizes (16 cw_cap, 16 rh_cap)
+        self.window_net = api.RaggedNet([(16 * int(s.cw_cap), 16 * int(s.rh_cap)) for s in self.layout], device=self.device,
+                                        shared_weights=net.weights, descs=net.descs, gdn=net.gdn)
+        last = len(net.descs) - 1
+        if self.window_net.nbytes(3) != self.latent_bytes or self.window_net.nbytes(last) != self.recon_bytes:
+            raise RuntimeError("the window net's tensors are not the layout's")
+        self.window_net.workspace()
+        u8 = dict(dtype=torch.uint8, device=self.device)
+        self.band = torch.empty(max(self.band_bytes, 16), **u8)
+        self.latent = torch.empty(self.latent_bytes, **u8)
+        self.recon = torch.empty(self.recon_bytes, **u8)
+        self.roi = torch.empty(self.roi_bytes, **u8)
+        self.ws = torch.empty(max(int(L.sicn_ragged_ctx_roi_move_workspace_bytes(self._h)), ws_bytes, 256), **u8)
+        self.status = torch.zeros((n, 2), dtype=torch.int32, device=self.device)
+        self.flags = torch.zeros(n, dtype=torch.int32, device=self.device)
+        self.xy = torch.zeros((n, 2), dtype=torch.int32, device=self.device)      # where a host sequence of positions is copied
+        self.uniform = len({(w, h) for _, w, h in self.slots}) == 1
+        self._containers = None     # (slot buffer, valid or None) of the last prepare: kept alive, read by every decode
+        self._unpacked = False      # the last prepare read an archive: check() reports its verdict first
+
+    def prepare(self, archive=None, images=None, z_containers=None, y_containers=None):
+        """Containers as in `RaggedHyperpriorCodec.decode` (default: the last encode's): everything of a decode that no rectangle
+        changes — unpack, the z coder, h_s and its crop (-> codec.s), and the y containers' fixed part.  Enqueue only, on the current
+        stream; once per set of containers, then any number of `decode`s."""
+        import ctypes
+        c = self.codec
+        y = c.y_coder
+        y_valid = c._decode_scales(z_containers, y_containers, archive, images)
+        self._unpacked = archive is not None
+        if archive is not None:
+            buf, valid = y.slot_buffer, y_valid
+        elif y_containers is None:
+            buf, valid = y.slot_buffer, y.enc_status
+        else:
+            buf, valid = c._upload(y_containers, y, "y_containers")
+        self._containers = (buf, valid)
+        api._lib.check(api._lib.lib().sicn_ragged_ctx_roi_move_prepare_async(
+            self._h, ctypes.c_void_p(buf.data_ptr()), None if valid is None else ctypes.c_void_p(valid.data_ptr()),
+            ctypes.c_void_p(self.ws.data_ptr()), self.ws.numel(), api._stream_ptr(None)), "sicn_ragged_ctx_roi_move_prepare_async")
+
+    def decode(self, xy, out=None, stream=None):
+        """xy: the positions (x0, y0) per slot — a contiguous CUDA int32 tensor [n_slots][2], read when the kernels run, or a host
+        sequence, which is copied into the object's own device tensor on the stream.  Returns the ROI pixels: `out` (a flat tensor
+        of roi_bytes; default the object's own), as [n_slots][h][w][3] where all slots have one size, flat otherwise (`views` gives
+        them per slot).  Enqueue only, nothing allocated.  RuntimeError if `prepare` has not run."""
+        import ctypes
+
+        import torch
+        if self._containers is None:
+            raise RuntimeError("prepare() has not run: there is no container whose fixed part a decode could read")
+        n = len(self.slots)
+        if isinstance(xy, torch.Tensor) and xy.is_cuda:
+            if not (xy.dtype == torch.int32 and xy.is_contiguous() and tuple(xy.shape) == (n, 2)):
+                raise TypeError(f"xy as a tensor: a contiguous CUDA int32 tensor of shape ({n}, 2)")
+        else:
+            host = np.asarray(xy)
+            if host.shape != (n, 2) or host.dtype.kind not in "iu" or host.min() < -2 ** 31 or host.max() >= 2 ** 31:
+                raise ValueError(f"xy: one int32 (x0, y0) per slot, {n}")
+            host = torch.from_numpy(host.astype(np.int32))
+            ts = stream if isinstance(stream, torch.cuda.Stream) else None
+            with torch.cuda.stream(ts):
+                self.xy.copy_(host)
+            xy = self.xy
+        out = self.roi if out is None else out
+        api._check_tensor(out, (self.roi_bytes,), "out")
+        L, sp, vp = api._lib.lib(), api._stream_ptr(stream), ctypes.c_void_p
+        api._lib.check(L.sicn_ragged_ctx_roi_move_decode_async(
+            self._h, vp(xy.data_ptr()), vp(self._containers[0].data_ptr()), vp(self.codec.s.data_ptr()), vp(self.band.data_ptr()),
+            vp(self.latent.data_ptr()), vp(self.status.data_ptr()), vp(self.flags.data_ptr()), vp(self.ws.data_ptr()), self.ws.numel(), sp),
+            "sicn_ragged_ctx_roi_move_decode_async")
+        self.window_net.run_layers(4, len(self.codec.main.descs) - 1, self.latent, out=self.recon, stream=stream)
+        api._lib.check(L.sicn_ragged_ctx_roi_move_cut_async(self._h, vp(self.recon.data_ptr()), vp(out.data_ptr()), sp),
+                       "sicn_ragged_ctx_roi_move_cut_async")
+        if self.uniform:
+            return out.view(n, self.slots[0][2], self.slots[0][1], 3)
+        return out
+
+    def views(self, roi):
+        """Per-slot [h][w][3] views of what `decode` returned."""
+        flat = roi.reshape(-1)
+        api._check_tensor(flat, (self.roi_bytes,), "roi")
+        return [flat[int(s.roi_offset):int(s.roi_offset) + h * w * 3].view(h, w, 3) for s, (_, w, h) in zip(self.layout, self.slots)]
+
+    def place(self, xy):
+        """Host arithmetic (sicn_ragged_ctx_roi_move_place): per slot the dict {x0, y0 after the clamp, c0, r0, cw, rh, x, y, flags,
+        first_stream, end_stream (per set), band_row0, band_rows, symbols, lat_bias, cut_offset}."""
+        import ctypes
+        _lib = api._lib
+        y, out = self.codec.y_coder, []
+        for (img, w, h), s, (x0, y0) in zip(self.slots, self.layout, xy):
+            (lh, lw), (iw, ih) = y.shapes[img], self.codec.sizes[img]
+            p = _lib.RaggedCtxRoiPlaced()
+            _lib.check(_lib.lib().sicn_ragged_ctx_roi_move_place(iw, ih, lw, lh, y.lat_c, int(y.stream_symbols[img]), w, h, int(x0), int(y0),
+                                                                 int(s.band_offset), ctypes.byref(p)), "sicn_ragged_ctx_roi_move_place")
+            d = {k: int(getattr(p.px, k)) for k, _ in _lib.RaggedRoiPlaced._fields_}
+            d.update(first_stream=tuple(p.first_stream), end_stream=tuple(p.end_stream), band_row0=int(p.band_row0),
+                     band_rows=int(p.band_rows), symbols=int(p.symbols), lat_bias=int(p.lat_bias), cut_offset=int(p.cut_offset))
+            out.append(d)
+        return out
+
+    def check(self):
+        """Synchronises and raises SicnError for what the last `prepare` and `decode` reported: the archive first (`.bits`), then
+        the z coder, then the slots' verdicts — the exception's `.slot` and `.image` name the first slot that failed."""
+        import torch
+        c = self.codec
+        if self._unpacked:
+            c._archive.check()
+        c.z_coder.check()
+        torch.cuda.synchronize(self.device)
+        d = self.status[:, 0].cpu().tolist()
+        if any(d):
+            k = next(i for i, v in enumerate(d) if v)
+            img = self.slots[k][0]
+            err = api._lib.SicnError(-22, f"slot {k}, image {img} {c.sizes[img]}: moving ROI decode status {d}")
+            err.slot, err.image = k, img
+            raise err

@@ -39,10 +39,14 @@
  * hands out.  The only state a launch touches in a handle is the optional profiling ring of a net,
  * whose slots are reserved with an atomic counter.
  *
- * Size limits of the specialised kernels (SICN_EINVAL beyond them): one image's input and output
- * < 2 GiB per layer (31-bit offsets inside an image: loads and stores go through buffer descriptors
- * whose range check is the padding / masking; 8K RGB images fit: 8192 x 4320 x 128 B / 4 = 1.1 GB at
- * layer 0's output), the RGB input tensor of a batch < 2 GiB, n_images <= 65535.
+ * Size limits (SICN_EINVAL beyond them, from every kernel family, the shape-agnostic one included): one
+ * image's input and output < 2 GiB per layer (31-bit offsets inside an image: loads and stores of the
+ * specialised kernels go through buffer descriptors whose range check is the padding / masking; 8K RGB
+ * images fit: 8192 x 4320 x 128 B / 4 = 1.1 GB at layer 0's output), the RGB input tensor of a batch
+ * + 4 bytes < 2 GiB on "l0_rgb", n_images <= 65535.  A batch as a whole may pass 4 GiB.  A chain makes
+ * no check ahead of its launches: sicn_net_forward returns the SICN_EINVAL of the first layer that
+ * refuses, after the layers in front of it were enqueued; `out` is then untouched, the workspace not.
+ * tests/test_large_tensors_gpu.py runs both sides of these limits.
  *
  * Naming trap inherited from the reference: IFM_ROW / OFM_ROW are WIDTHS (x, fast dimension),
  * IFM_COL / OFM_COL are HEIGHTS (conv_nonsquare_top.cpp:283-285).

@@ -50,6 +50,9 @@ hipError_t launch_generic(const LayerGeom &g, const sicn_weights &w, const uint8
                           int n_images, hipStream_t stream, bool relu)
 {
     const size_t total = (size_t)g.OH * g.OW * g.COUT;
+    // the kernel's own arithmetic is 64-bit; the limit is the ABI's (include/sicn.h), the same from every family, so that what a
+    // call accepts does not depend on the kernel that serves it
+    if ((size_t)g.IH * g.IW * g.CIN >= ((size_t)1 << 31) || total >= ((size_t)1 << 31)) return hipErrorInvalidValue;
     const size_t blocks = (total + 255) / 256;
     if (blocks > 0x7fffffffu) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_generic, dim3((unsigned)blocks, (unsigned)n_images), dim3(256), 0, stream, in, out,

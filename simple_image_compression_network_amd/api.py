@@ -488,7 +488,95 @@ class RaggedRoi:
         return self.pixel_cut.views(roi)
 
 
-class MovingRoi(_lib.Handle):
+class _MovingRoiChain(_lib.Handle):
+    """What MovingRoi and hyperprior.MovingHyperpriorRoi share: the slots, the library object and its layout, the window net, the
+    chain's tensors, the positions and everything of a decode that follows its coder's arguments.  A subclass names its entry
+    points in `_abi` (`<_abi>_layout`, `_create`, `_workspace_bytes`, `_decode_async`, `_cut_async`), the struct of its layout in
+    `_slot_type` and the number of its layout's totals in `_n_totals` (the first five are the tensors' bytes)."""
+    _abi, _slot_type, _n_totals = "", None, 0
+
+    def _check_slots(self, net, slots):
+        """-> self.slots, or ValueError before anything is made."""
+        self.slots = [tuple(int(v) for v in s) for s in slots]
+        if len(self.slots) < 1 or any(len(s) != 3 for s in self.slots):
+            raise ValueError("slots: at least one (image, w, h)")
+        for img, w, h in self.slots:
+            if not 0 <= img < len(net.sizes):
+                raise ValueError(f"slot image {img}: the net has {len(net.sizes)} images")
+            if w < 1 or h < 1 or w > net.sizes[img][0] or h > net.sizes[img][1]:
+                raise ValueError(f"a {w} x {h} rectangle is empty or larger than the {net.sizes[img][0]} x {net.sizes[img][1]} image")
+
+    def _make(self, net, c):
+        """The library object over the coder `c` of `net`'s latents, the window net and the tensors."""
+        import torch
+        L, n = _lib.lib(), len(self.slots)
+        self.device = net.device
+        self._cslots = (_lib.RaggedRoiSlot * n)(*[_lib.RaggedRoiSlot(*s) for s in self.slots])
+        self.layout = (self._slot_type * n)()
+        totals = (ctypes.c_uint64 * self._n_totals)()
+        _lib.check(getattr(L, self._abi + "_layout")(c._lat_w, c._lat_h, c.lat_c, c._wss, c._img_w, c._img_h, len(c.shapes), self._cslots, n,
+                                                     self.layout, totals), self._abi + "_layout")
+        self.band_bytes, self.latent_bytes, self.recon_bytes, self.roi_bytes, ws_bytes = (int(v) for v in totals[:5])
+        self.items = int(totals[5]) if self._n_totals == 6 else tuple(int(v) for v in totals[5:])
+        self._h = ctypes.c_void_p()
+        with torch.cuda.device(self.device):
+            _lib.check(getattr(L, self._abi + "_create")(c._h, self._cslots, n, ctypes.byref(self._h)), self._abi + "_create")
+        # the window net: layers 4 .. on `net`'s weights, descs and GDN objects over the sizes (16 cw_cap, 16 rh_cap)
+        self.window_net = RaggedNet([(16 * int(s.cw_cap), 16 * int(s.rh_cap)) for s in self.layout], device=self.device,
+                                    shared_weights=net.weights, descs=net.descs, gdn=net.gdn)
+        self._last = len(net.descs) - 1
+        if self.window_net.nbytes(3) != self.latent_bytes or self.window_net.nbytes(self._last) != self.recon_bytes:
+            raise RuntimeError("the window net's tensors are not the layout's")
+        self.window_net.workspace()
+        u8 = dict(dtype=torch.uint8, device=self.device)
+        self.band = torch.empty(max(self.band_bytes, 16), **u8)
+        self.latent = torch.empty(self.latent_bytes, **u8)
+        self.recon = torch.empty(self.recon_bytes, **u8)
+        self.roi = torch.empty(self.roi_bytes, **u8)
+        self.ws = torch.empty(max(int(getattr(L, self._abi + "_workspace_bytes")(self._h)), ws_bytes, 256), **u8)
+        self.status = torch.zeros((n, 2), dtype=torch.int32, device=self.device)
+        self.flags = torch.zeros(n, dtype=torch.int32, device=self.device)
+        self.xy = torch.zeros((n, 2), dtype=torch.int32, device=self.device)      # where a host sequence of positions is copied
+        self.uniform = len({(w, h) for _, w, h in self.slots}) == 1
+
+    def _positions(self, xy, stream):
+        """xy as `decode` takes it -> the device tensor the kernels read: xy itself, or the object's own after a copy on the stream."""
+        import torch
+        n = len(self.slots)
+        if isinstance(xy, torch.Tensor) and xy.is_cuda:
+            if not (xy.dtype == torch.int32 and xy.is_contiguous() and tuple(xy.shape) == (n, 2)):
+                raise TypeError(f"xy as a tensor: a contiguous CUDA int32 tensor of shape ({n}, 2)")
+            return xy
+        host = np.asarray(xy)
+        if host.shape != (n, 2) or host.dtype.kind not in "iu" or host.min() < -2 ** 31 or host.max() >= 2 ** 31:
+            raise ValueError(f"xy: one int32 (x0, y0) per slot, {n}")
+        with torch.cuda.stream(stream if isinstance(stream, torch.cuda.Stream) else None):
+            self.xy.copy_(torch.from_numpy(host.astype(np.int32)))
+        return self.xy
+
+    def _decode(self, xy, out, stream, *coder_args):
+        """The placed decode (`coder_args`: what `<_abi>_decode_async` takes between the positions and the band), the window net and
+        the pixel cut -> `out` or the object's own pixels."""
+        out = self.roi if out is None else out
+        _check_tensor(out, (self.roi_bytes,), "out")
+        L, sp, vp = _lib.lib(), _stream_ptr(stream), ctypes.c_void_p
+        _lib.check(getattr(L, self._abi + "_decode_async")(
+            self._h, vp(xy.data_ptr()), *coder_args, vp(self.band.data_ptr()), vp(self.latent.data_ptr()), vp(self.status.data_ptr()),
+            vp(self.flags.data_ptr()), vp(self.ws.data_ptr()), self.ws.numel(), sp), self._abi + "_decode_async")
+        self.window_net.run_layers(4, self._last, self.latent, out=self.recon, stream=stream)
+        _lib.check(getattr(L, self._abi + "_cut_async")(self._h, vp(self.recon.data_ptr()), vp(out.data_ptr()), sp), self._abi + "_cut_async")
+        if self.uniform:
+            return out.view(len(self.slots), self.slots[0][2], self.slots[0][1], 3)
+        return out
+
+    def views(self, roi):
+        """Per-slot [h][w][3] views of what `decode` returned."""
+        flat = roi.reshape(-1)
+        _check_tensor(flat, (self.roi_bytes,), "roi")
+        return [flat[int(s.roi_offset):int(s.roi_offset) + h * w * 3].view(h, w, 3) for s, (_, w, h) in zip(self.layout, self.slots)]
+
+
+class MovingRoi(_MovingRoiChain):
     """Pixel rectangles of fixed SIZE whose POSITIONS are read from device memory on every call (include/sicn_ragged_roi_move.h):
     made once for a list of slots, `decode(xy)` then costs its nine launches and nothing else — no allocation, no upload of tables,
     no host synchronisation — so a captured graph replays with new positions and a loader can draw them on the device.
@@ -497,96 +585,29 @@ class MovingRoi(_lib.Handle):
     `RaggedArchive.unpack(images=...)` into it, an archive serves any number of moves.  Same bytes as the full decode, sliced; a
     position outside [0, image - size] is clamped and bit 0 of the slot's `.flags` word says so.
     `.status`: device int32 [n_slots][2], the window decoder's verdicts per slot; `.flags`: device int32 [n_slots]."""
-    _free = "sicn_ragged_roi_move_free"
+    _free, _abi, _slot_type, _n_totals = "sicn_ragged_roi_move_free", "sicn_ragged_roi_move", _lib.RaggedRoiMoveSlot, 6
 
     def __init__(self, net, slots, coder=None, stream_symbols=16384):
-        import torch
-        L = _lib.lib()
         self.net = net
-        self.slots = [tuple(int(v) for v in s) for s in slots]
-        n = len(self.slots)
-        if n < 1 or any(len(s) != 3 for s in self.slots):
-            raise ValueError("slots: at least one (image, w, h)")
-        for img, w, h in self.slots:
-            if not 0 <= img < len(net.sizes):
-                raise ValueError(f"slot image {img}: the net has {len(net.sizes)} images")
-            if w < 1 or h < 1 or w > net.sizes[img][0] or h > net.sizes[img][1]:
-                raise ValueError(f"a {w} x {h} rectangle is empty or larger than the {net.sizes[img][0]} x {net.sizes[img][1]} image")
-        self.coder = coder if coder is not None else net.latent_coder(stream_symbols)
-        c = self.coder
+        self._check_slots(net, slots)
+        self.coder = c = coder if coder is not None else net.latent_coder(stream_symbols)
         lat = net.shapes(3)
         if [(h, w) for h, w, _ in lat] != c.shapes or lat[0][2] != c.lat_c or c.image_sizes != net.sizes:
             raise ValueError("the coder's latent shapes or image sizes are not the net's")
-        self.device = net.device
-        self._cslots = (_lib.RaggedRoiSlot * n)(*[_lib.RaggedRoiSlot(*s) for s in self.slots])
-        self.layout = (_lib.RaggedRoiMoveSlot * n)()
-        totals = (ctypes.c_uint64 * 6)()
-        _lib.check(L.sicn_ragged_roi_move_layout(c._lat_w, c._lat_h, c.lat_c, c._wss, c._img_w, c._img_h, len(c.shapes), self._cslots, n,
-                                                 self.layout, totals), "sicn_ragged_roi_move_layout")
-        self.band_bytes, self.latent_bytes, self.recon_bytes, self.roi_bytes, ws_bytes, self.items = (int(v) for v in totals)
-        self._h = ctypes.c_void_p()
-        with torch.cuda.device(self.device):
-            _lib.check(L.sicn_ragged_roi_move_create(c._h, self._cslots, n, ctypes.byref(self._h)), "sicn_ragged_roi_move_create")
-        # the window net: layers 4 .. on `net`'s weights, descs and GDN objects over the sizes (16 cw_cap, 16 rh_cap)
-        self.window_net = RaggedNet([(16 * int(s.cw_cap), 16 * int(s.rh_cap)) for s in self.layout], device=self.device,
-                                    shared_weights=net.weights, descs=net.descs, gdn=net.gdn)
-        last = len(net.descs) - 1
-        if self.window_net.nbytes(3) != self.latent_bytes or self.window_net.nbytes(last) != self.recon_bytes:
-            raise RuntimeError("the window net's tensors are not the layout's")
-        self.window_net.workspace()
-        u8 = dict(dtype=torch.uint8, device=self.device)
-        self.band = torch.empty(max(self.band_bytes, 16), **u8)
-        self.latent = torch.empty(self.latent_bytes, **u8)
-        self.recon = torch.empty(self.recon_bytes, **u8)
-        self.roi = torch.empty(self.roi_bytes, **u8)
-        self.ws = torch.empty(max(int(L.sicn_ragged_roi_move_workspace_bytes(self._h)), 256), **u8)
-        self.status = torch.zeros((n, 2), dtype=torch.int32, device=self.device)
-        self.flags = torch.zeros(n, dtype=torch.int32, device=self.device)
-        self.xy = torch.zeros((n, 2), dtype=torch.int32, device=self.device)      # where a host sequence of positions is copied
-        self.uniform = len({(w, h) for _, w, h in self.slots}) == 1
+        self._make(net, c)
 
     def decode(self, xy, slots=None, valid=None, stream=None, out=None):
         """xy: the positions (x0, y0) per slot — a CUDA int32 tensor [n_slots][2], read when the kernels run, or a host sequence,
         which is copied into the object's own device tensor on the stream.  slots, valid: as in RaggedLatentCoder.decode.  Returns
         the ROI pixels: `out` (a flat tensor of roi_bytes; default the object's own), as [n_slots][h][w][3] where all slots have one
         size, flat otherwise (`views` gives them per slot).  Enqueue only: nine launches, nothing allocated."""
-        import torch
-        c, n = self.coder, len(self.slots)
-        if isinstance(xy, torch.Tensor) and xy.is_cuda:
-            if not (xy.dtype == torch.int32 and xy.is_contiguous() and tuple(xy.shape) == (n, 2)):
-                raise TypeError(f"xy as a tensor: a contiguous CUDA int32 tensor of shape ({n}, 2)")
-        else:
-            host = np.asarray(xy)
-            if host.shape != (n, 2) or host.dtype.kind not in "iu" or host.min() < -2 ** 31 or host.max() >= 2 ** 31:
-                raise ValueError(f"xy: one int32 (x0, y0) per slot, {n}")
-            host = torch.from_numpy(host.astype(np.int32))
-            ts = stream if isinstance(stream, torch.cuda.Stream) else None
-            with torch.cuda.stream(ts):
-                self.xy.copy_(host)
-            xy = self.xy
+        c = self.coder
+        xy = self._positions(xy, stream)
         slots = c.slot_buffer if slots is None else slots
         c._flat(slots, c.slot_bytes, "slots")
         own = slots is c.slot_buffer
         vptr = None if (valid is False or (valid is None and not own)) else ctypes.c_void_p((c.enc_status if valid is None else valid).data_ptr())
-        out = self.roi if out is None else out
-        _check_tensor(out, (self.roi_bytes,), "out")
-        L, sp = _lib.lib(), _stream_ptr(stream)
-        _lib.check(L.sicn_ragged_roi_move_decode_async(
-            self._h, ctypes.c_void_p(xy.data_ptr()), ctypes.c_void_p(slots.data_ptr()), vptr, ctypes.c_void_p(self.band.data_ptr()),
-            ctypes.c_void_p(self.latent.data_ptr()), ctypes.c_void_p(self.status.data_ptr()), ctypes.c_void_p(self.flags.data_ptr()),
-            ctypes.c_void_p(self.ws.data_ptr()), self.ws.numel(), sp), "sicn_ragged_roi_move_decode_async")
-        self.window_net.run_layers(4, len(self.net.descs) - 1, self.latent, out=self.recon, stream=stream)
-        _lib.check(L.sicn_ragged_roi_move_cut_async(self._h, ctypes.c_void_p(self.recon.data_ptr()), ctypes.c_void_p(out.data_ptr()), sp),
-                   "sicn_ragged_roi_move_cut_async")
-        if self.uniform:
-            return out.view(n, self.slots[0][2], self.slots[0][1], 3)
-        return out
-
-    def views(self, roi):
-        """Per-slot [h][w][3] views of what `decode` returned."""
-        flat = roi.reshape(-1)
-        _check_tensor(flat, (self.roi_bytes,), "roi")
-        return [flat[int(s.roi_offset):int(s.roi_offset) + h * w * 3].view(h, w, 3) for s, (_, w, h) in zip(self.layout, self.slots)]
+        return self._decode(xy, out, stream, ctypes.c_void_p(slots.data_ptr()), vptr)
 
     def place(self, xy):
         """Host arithmetic (sicn_ragged_roi_move_place): per slot the dict {x0, y0 after the clamp, c0, r0, cw, rh, x, y, flags}."""

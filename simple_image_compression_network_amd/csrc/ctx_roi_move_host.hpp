@@ -2,8 +2,10 @@
 // mode-4 container, the placement of a position, the layout of the slots in the chain's tensors, and the rows the placement writes
 // for the decode kernels and the two cuts.  Plain C++ that also compiles without HIP (tests/cpp/ctx_roi_move_plan_check.cpp runs it
 // under the host sanitizers); under hipcc the placement is __host__ __device__, so that k_ctx_roi_place
-// (k_ragged_ctx_roi_move.hip) and the host entry points state ONE rule: the pixel axes are roi_move_host.hpp's place_axis, the
-// plan of the placed rows is ctx_window_host.hpp's plan_of_sl — called, not restated.
+// (k_ragged_ctx_roi_move.hip) and the host entry points state ONE rule.  What a slot is whatever its coder — the SlotGeom, the pixel
+// side of a placement, the latent cut, the shared part of the layout — is roi_move_host.hpp's; the plan of the placed rows is
+// ctx_window_host.hpp's plan_of_sl: called, not restated.  What stands here is rANS-WC's own: the capacities of both sets and of
+// the band, the streams a placement selects, the meta blocks and the decode items.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -15,11 +17,7 @@
 
 namespace sicn_ctx_roi_move {
 
-using sicn_roi_move::AxisPlace;
-using sicn_roi_move::place_axis;
-using sicn_window::CutRow;
-constexpr int UP = SICN_ROI_MOVE_UP_LAYERS;
-constexpr int CUT_ROWS = sicn_window::CUT_ROWS;
+using sicn_roi_move::PixelPlace, sicn_roi_move::SlotGeom, sicn_roi_move::UP, sicn_window::CutRow;
 constexpr uint32_t WPB_DEC = SICN_CTX_ROI_MOVE_STREAMS_PER_ITEM;   // k_ctx_body.hpp's CTX_WPB_DEC (asserted where both are seen)
 constexpr uint64_t META_BYTES = 64;                                // a slot's own block of the workspace
 
@@ -43,11 +41,9 @@ inline int capacity(uint32_t W, uint32_t H, uint32_t C, uint32_t S, uint32_t rh,
 
 // ---- the tables --------------------------------------------------------------------------------------------------------------
 // One row per slot, constant, uploaded once: what the placement and the kernels need of the slot and of its image.
-struct SlotRow {
-    uint64_t band_off, lat_off, recon_off, roi_off, meta_off;
-    uint32_t image, first_item[2], max_streams[2], band_rows_cap, lat_first_item, pix_first_item;
-    int32_t w, h, cw_cap, rh_cap, image_w, image_h, lat_w, lat_h;
-    uint32_t lat_c, S;
+struct SlotRow : SlotGeom {
+    uint64_t meta_off;
+    uint32_t first_item[2], max_streams[2], band_rows_cap, S;
 };
 // One row per slot, written by the placement: the streams of both sets the slot selects in this call and where they land (the
 // CtxWinRow of k_ragged_ctx.hip without the first items, which are constant here).
@@ -57,37 +53,25 @@ struct MoveRow {
     uint32_t symbols;                   // what the selected streams hold
     uint32_t flags;
 };
-struct Placement {
+struct Placement : PixelPlace {
     MoveRow win;
-    CutRow lat_cut, pix_cut;            // band -> window latent, reconstruction -> ROI pixels
-    AxisPlace ax, ay;
+    CutRow lat_cut;                     // band -> window latent
     uint32_t band_row0, band_rows;
 };
 
 // What a position means for a slot: every word the device tables get.  Nothing here can leave the slot's band, window latent,
 // reconstruction or pixels, whatever (x0, y0) is: ay.first lies in [0, lat_h - rh_cap], so the plan cannot refuse and its streams
 // and band rows are within the capacities, which are the maxima over exactly those rows.
-SICN_ROI_HD inline Placement place_slot(const SlotRow &s, int32_t x0, int32_t y0)
+SICN_HD inline Placement place_slot(const SlotRow &s, int32_t x0, int32_t y0)
 {
-    const AxisPlace ax = place_axis(x0, s.image_w, s.lat_w, s.w, s.cw_cap, UP), ay = place_axis(y0, s.image_h, s.lat_h, s.h, s.rh_cap, UP);
+    Placement p{sicn_roi_move::place_pixels(s, x0, y0), {}, {}, 0, 0};
     sicn_ragged_ctx_window_image im{};
-    (void)sicn_ctx_window::plan_of_sl((uint32_t)s.lat_w, (uint32_t)s.lat_h, s.lat_c, s.S, (uint32_t)ay.first, (uint32_t)s.rh_cap, s.band_off, &im);
+    (void)sicn_ctx_window::plan_of_sl((uint32_t)s.lat_w, (uint32_t)s.lat_h, s.lat_c, s.S, (uint32_t)p.ay.first, (uint32_t)s.rh_cap, s.band_off, &im);
     const uint64_t row = (uint64_t)s.lat_w * s.lat_c;
-    Placement p;
-    p.ax = ax; p.ay = ay;
     p.band_row0 = im.band_row0; p.band_rows = im.band_rows;
-    p.win.lat_bias = s.band_off - (uint64_t)im.band_row0 * row;
-    for (int k = 0; k < 2; k++) { p.win.first[k] = im.first_stream[k]; p.win.end[k] = im.end_stream[k]; }
-    p.win.symbols = im.symbols;
-    p.win.flags = (ax.moved | ay.moved) ? SICN_ROI_MOVE_CLAMPED : 0u;
-    const uint64_t drow = (uint64_t)s.cw_cap * s.lat_c;
-    const uint64_t at = s.band_off + ((uint64_t)ay.first - im.band_row0) * row + (uint64_t)ax.first * s.lat_c;
-    p.lat_cut = CutRow{(uint32_t)row, (uint32_t)drow, (uint32_t)s.rh_cap, s.lat_first_item, ((row | drow | at | s.lat_off) & 15) == 0 ? 1u : 0u,
-                       0u, (int64_t)at, (int64_t)s.lat_off};
-    const uint64_t prow = ((uint64_t)s.cw_cap << UP) * 3, qrow = (uint64_t)s.w * 3;
-    const uint64_t pat = s.recon_off + (uint64_t)ay.inside * prow + (uint64_t)ax.inside * 3;
-    p.pix_cut = CutRow{(uint32_t)prow, (uint32_t)qrow, (uint32_t)s.h, s.pix_first_item, ((prow | qrow | pat | s.roi_off) & 15) == 0 ? 1u : 0u,
-                       0u, (int64_t)pat, (int64_t)s.roi_off};
+    p.win = MoveRow{s.band_off - (uint64_t)im.band_row0 * row, {im.first_stream[0], im.first_stream[1]}, {im.end_stream[0], im.end_stream[1]},
+                    im.symbols, p.flags};
+    p.lat_cut = sicn_roi_move::lat_cut_of(s, p.ax, s.band_off + ((uint64_t)p.ay.first - im.band_row0) * row);
     return p;
 }
 
@@ -100,12 +84,9 @@ inline int slot_of(int32_t image_w, int32_t image_h, int32_t lat_w, int32_t lat_
     sicn_ragged_ctx_window_image im;
     if (int rc = sicn_ctx_window::plan_of_sl((uint32_t)lat_w, (uint32_t)lat_h, lat_c, S, 0, (uint32_t)cap[1], 0, &im)) return rc;
     if (band_offset >= ((uint64_t)1 << 62)) return SICN_EINVAL;
-    SlotRow s{};
-    s.band_off = band_offset;
-    s.w = w; s.h = h; s.cw_cap = cap[0]; s.rh_cap = cap[1];
-    s.image_w = image_w; s.image_h = image_h; s.lat_w = lat_w; s.lat_h = lat_h;
-    s.lat_c = lat_c; s.S = S;
-    *out = s;
+    *out = SlotRow{};
+    static_cast<SlotGeom &>(*out) = SlotGeom{band_offset, 0, 0, 0, 0, 0, 0, w, h, cap[0], cap[1], image_w, image_h, lat_w, lat_h, lat_c};
+    out->S = S;
     return SICN_OK;
 }
 
@@ -128,9 +109,8 @@ inline int place(int32_t image_w, int32_t image_h, int32_t lat_w, int32_t lat_h,
 }
 
 // ---- the layout ----------------------------------------------------------------------------------------------------------------
-struct Totals {
-    uint64_t band = 0, latent = 0, recon = 0, roi = 0, workspace = 0;
-    uint64_t items[2] = {0, 0}, lat_items = 0, pix_items = 0;
+struct Totals : sicn_roi_move::GeomTotals {
+    uint64_t items[2] = {0, 0};
 };
 
 // coder_ws_bytes: the full ctx coder's workspace for the same images (sicn_ragged_ctx_layout's totals[2]), which this header
@@ -144,44 +124,24 @@ inline int layout(const uint32_t *lat_w, const uint32_t *lat_h, uint32_t lat_c, 
     Totals t;
     t.workspace = coder_ws_bytes;
     for (int k = 0; k < n_slots; k++) {
-        const sicn_ragged_roi_slot &q = slots[k];
-        if (q.image < 0 || q.image >= n_images) return SICN_EINVAL;
-        const uint32_t lw = lat_w[q.image], lh = lat_h[q.image], iw = image_w[q.image], ih = image_h[q.image];
-        const uint32_t S = wss_or_null ? wss_or_null[q.image] : (uint32_t)sicn_ctx_window::WSS;
-        if (lw < 1 || lh < 1 || lw > (1u << 20) || lh > (1u << 20) || iw > 0x7fffffffu || ih > 0x7fffffffu) return SICN_EINVAL;
-        int32_t cap[2];
-        if (int rc = sicn_roi_move::capacity(UP, (int32_t)iw, (int32_t)ih, (int32_t)lw, (int32_t)lh, q.w, q.h, cap)) return rc;
-        uint32_t sc[3];
-        if (int rc = capacity(lw, lh, lat_c, S, (uint32_t)cap[1], sc)) return rc;
-        const uint64_t rw = (uint64_t)cap[0] << UP, rh = (uint64_t)cap[1] << UP;
-        if ((double)rw * (double)rh * 3.0 >= (double)sicn_window::MAX_IMAGE_BYTES) return SICN_EINVAL;
-        const uint64_t it[2] = {((uint64_t)sc[0] + WPB_DEC - 1) / WPB_DEC, ((uint64_t)sc[1] + WPB_DEC - 1) / WPB_DEC};
         SlotRow s{};
-        s.band_off = t.band; s.lat_off = t.latent; s.recon_off = t.recon; s.roi_off = t.roi; s.meta_off = t.workspace;
-        s.image = (uint32_t)q.image;
-        s.first_item[0] = (uint32_t)t.items[0]; s.first_item[1] = (uint32_t)t.items[1];
-        s.max_streams[0] = sc[0]; s.max_streams[1] = sc[1]; s.band_rows_cap = sc[2];
-        s.lat_first_item = (uint32_t)t.lat_items; s.pix_first_item = (uint32_t)t.pix_items;
-        s.w = q.w; s.h = q.h; s.cw_cap = cap[0]; s.rh_cap = cap[1];
-        s.image_w = (int32_t)iw; s.image_h = (int32_t)ih; s.lat_w = (int32_t)lw; s.lat_h = (int32_t)lh;
-        s.lat_c = lat_c; s.S = S;
+        if (int rc = sicn_roi_move::slot_geom(lat_w, lat_h, lat_c, image_w, image_h, n_images, slots[k], &t, &s)) return rc;
+        s.S = wss_or_null ? wss_or_null[s.image] : (uint32_t)sicn_ctx_window::WSS;
+        uint32_t sc[3];
+        if (int rc = capacity((uint32_t)s.lat_w, (uint32_t)s.lat_h, lat_c, s.S, (uint32_t)s.rh_cap, sc)) return rc;
+        const uint32_t it[2] = {(sc[0] + WPB_DEC - 1) / WPB_DEC, (sc[1] + WPB_DEC - 1) / WPB_DEC};
+        s.meta_off = t.workspace;
+        for (int set = 0; set < 2; set++) { s.first_item[set] = (uint32_t)t.items[set]; s.max_streams[set] = sc[set]; }
+        s.band_rows_cap = sc[2];
         if (rows_or_null) rows_or_null[k] = s;
         if (slots_out_or_null)
-            slots_out_or_null[k] = sicn_ragged_ctx_roi_move_slot{s.band_off, s.lat_off, s.recon_off, s.roi_off, s.meta_off, (uint32_t)cap[0],
-                                                                 (uint32_t)cap[1], sc[2], {sc[0], sc[1]}, {s.first_item[0], s.first_item[1]},
-                                                                 {(uint32_t)it[0], (uint32_t)it[1]}, 0u};
-        t.band += sicn_ctx_window::a16((uint64_t)sc[2] * lw * lat_c);
-        t.latent += (uint64_t)cap[1] * cap[0] * lat_c;
-        t.recon += rw * rh * 3;
-        t.roi += (uint64_t)q.h * q.w * 3;
-        t.workspace += META_BYTES;
+            slots_out_or_null[k] = sicn_ragged_ctx_roi_move_slot{s.band_off, s.lat_off, s.recon_off, s.roi_off, s.meta_off, (uint32_t)s.cw_cap,
+                                                                 (uint32_t)s.rh_cap, sc[2], {sc[0], sc[1]}, {s.first_item[0], s.first_item[1]},
+                                                                 {it[0], it[1]}, 0u};
         t.items[0] += it[0];
         t.items[1] += it[1];
-        t.lat_items += ((uint64_t)cap[1] + CUT_ROWS - 1) / CUT_ROWS;
-        t.pix_items += ((uint64_t)q.h + CUT_ROWS - 1) / CUT_ROWS;
-        if (t.items[0] >= (uint64_t)sicn::RAGGED_MAX_ITEMS || t.items[1] >= (uint64_t)sicn::RAGGED_MAX_ITEMS ||
-            t.lat_items >= (uint64_t)sicn::RAGGED_MAX_ITEMS || t.pix_items >= (uint64_t)sicn::RAGGED_MAX_ITEMS ||
-            t.workspace >= ((uint64_t)1 << 62) || t.band >= ((uint64_t)1 << 62))
+        if (sicn_roi_move::grow(&t, (uint64_t)sc[2] * s.lat_w * lat_c, META_BYTES) || t.items[0] >= (uint64_t)sicn::RAGGED_MAX_ITEMS ||
+            t.items[1] >= (uint64_t)sicn::RAGGED_MAX_ITEMS)
             return SICN_EINVAL;
     }
     if (totals) *totals = t;

@@ -1,27 +1,23 @@
 // The arithmetic of include/sicn_ragged_ctx_window.h on the host: which streams of the two checkerboard sets of a mode-4 container a
 // window of latent rows needs, and the band of whole latent rows they fill.  Plain C++ without HIP, so that it also compiles into a
 // stand-alone program (tests/cpp/ctx_window_plan_check.cpp runs it under the host sanitizers).  k_ragged_ctx.hip wraps it in the
-// extern "C" entry points.  Under hipcc the plan of one image is __host__ __device__: the moving ROI decode (ctx_roi_move_host.hpp,
-// k_ragged_ctx_roi_move.hip) evaluates it on the device from a position read there, by this one statement of the rule.
+// extern "C" entry points.  Under hipcc the plan of one image is __host__ __device__ (SICN_HD, k_ragged_common.hpp): the moving ROI
+// decode (ctx_roi_move_host.hpp, k_ragged_ctx_roi_move.hip) evaluates it on the device from a position read there, by this one
+// statement of the rule.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
 
 #include "../../include/sicn.h"
 #include "../../include/sicn_ragged_ctx_window.h"
-
-#ifdef __HIPCC__
-#define SICN_CTX_WIN_HD __host__ __device__
-#else
-#define SICN_CTX_WIN_HD
-#endif
+#include "window_host.hpp"
 
 namespace sicn_ctx_window {
 
 constexpr uint64_t WSS = 16384;                      // the default length of a mode-4 stream (SICN_CODEC_WSTREAM_SYMBOLS)
 constexpr uint64_t MAX_SYMBOLS = 0x7F000000ull;      // the coder's limit on one image (sicn_ragged_ctx_layout)
 
-constexpr uint64_t a16(uint64_t v) { return (v + 15) & ~(uint64_t)15; }
+using sicn_window::a16;
 constexpr uint64_t ceil_div(uint64_t a, uint64_t b) { return (a + b - 1) / b; }
 constexpr uint64_t min64(uint64_t a, uint64_t b) { return a < b ? a : b; }
 constexpr uint64_t max64(uint64_t a, uint64_t b) { return a > b ? a : b; }
@@ -30,8 +26,8 @@ constexpr bool length_ok(uint64_t S) { return S >= 1024 && S <= WSS && (S & (S -
 
 // The plan of one image: rows [r0, r0 + rh) of a [H][W][C] latent.  Every quantity is 64-bit: with W H C <= MAX_SYMBOLS no product
 // below can wrap.  S: the image's stream length.
-SICN_CTX_WIN_HD inline int plan_of_sl(uint32_t W, uint32_t H, uint32_t C, uint32_t S_, uint32_t r0_, uint32_t rh, uint64_t band_offset,
-                                      sicn_ragged_ctx_window_image *out)
+SICN_HD inline int plan_of_sl(uint32_t W, uint32_t H, uint32_t C, uint32_t S_, uint32_t r0_, uint32_t rh, uint64_t band_offset,
+                              sicn_ragged_ctx_window_image *out)
 {
     const uint64_t positions = (uint64_t)W * H, S = S_;
     if (positions == 0 || C == 0 || (C & 3) || !length_ok(S)) return SICN_EINVAL;

@@ -1,8 +1,12 @@
-// What the ragged translation units (k_ragged*.hip) share: the limit of a flat grid and the wave-uniform load.  The host part is
-// plain C++, so that window_host.hpp can include this file in a program without HIP.
+// What the ragged translation units (k_ragged*.hip) share: the limit of a flat grid, the wave-uniform load and the mark of the host
+// arithmetic that a kernel evaluates too.  The host part is plain C++, so that window_host.hpp can include this file in a program
+// without HIP.
 #pragma once
 #ifdef __HIPCC__
 #include <hip/hip_runtime.h>
+#define SICN_HD __host__ __device__
+#else
+#define SICN_HD
 #endif
 #include <stdint.h>
 

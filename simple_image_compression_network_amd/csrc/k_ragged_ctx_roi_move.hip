@@ -5,19 +5,18 @@
 // stages are k_ctx_body.hpp's, called unchanged.  The two cuts are k_ragged_window.hip's k_ragged_cut itself
 // (sicn::ragged_cut_launch) over rows this file writes.
 //
-// Tables.  Constant, uploaded at creation:
-//   srows[slot]        : SlotRow (ctx_roi_move_host.hpp), the slot's size, capacities, offsets and first work items, its image's geometry
+// Tables.  What no coder changes is k_roi_move_common.hpp's MoveTables, shared with k_ragged_roi_move.hip: srows[slot] (SlotRow of
+// ctx_roi_move_host.hpp: the shared SlotGeom, then the slot's meta block, its first decode items and max_streams per set, the band's
+// row capacity and its image's stream length), the two cuts' item -> slot maps, and the rows k_ctx_roi_place writes on the stream,
+// one thread per slot, from place_slot() — the function the host entry points call too: mrows[slot] (MoveRow, the streams
+// [first, end) of each set the slot selects now and where they land in its band), lat_rows[slot], pix_rows[slot], and the caller's
+// flags[slot].  This file's own:
 //   item_slot[set][]   : the slot of a work item of a set's decode grid (sum of ceil(max_streams[set] / CTX_WPB_DEC)) — ONE load
 //                        resolves item -> slot
-//   lat_item_slot[], pix_item_slot[] : the same for the two cuts' grids, which the capacities fix
 //   images[]           : the DISTINCT images the slots name, ascending: the grid of the three prepare kernels
 //   rows[image]        : the CODER's CtxRow table
-// Written by k_ctx_roi_place on the stream, one thread per slot, from place_slot() — the function the host entry points call too:
-//   mrows[slot]        : MoveRow, the streams [first, end) of each set the slot selects now and where they land in its band
-//   lat_rows[slot], pix_rows[slot] : the CutRows of the latent cut and of the pixel cut
-//   flags[slot]        : the caller's flag words
-//   the slot's meta block of the workspace <- its image's meta[0..3] as prepare left them: what this call's streams report
-//   lands there and nowhere else, and what the last call's reported is gone
+//   the slot's meta block of the workspace <- its image's meta[0..3] as prepare left them, written by k_ctx_roi_place: what this
+//   call's streams report lands there and nowhere else, and what the last call's reported is gone
 // Every kernel below has the shape of k_ragged_ctx.hip's: load the row of its image (load_row), resolve it (ctx_image), call the stage.
 #include <new>
 #include <vector>
@@ -26,8 +25,7 @@
 #include "../../include/sicn_ctx_stream_length.h"
 #include "ctx_roi_move_host.hpp"
 #include "k_ctx_body.hpp"
-#include "sicn_internal.h"
-#include "sicn_weights_io.h"
+#include "k_roi_move_common.hpp"
 
 namespace {
 
@@ -70,11 +68,8 @@ __global__ __launch_bounds__(64) void k_ctx_roi_place(const int32_t *__restrict_
     const uint32_t slot = blockIdx.x * 64u + threadIdx.x;
     if (slot >= n_slots) return;
     const SlotRow s = srows[slot];
-    const sicn_ctx_roi_move::Placement p = sicn_ctx_roi_move::place_slot(s, xy[2 * (size_t)slot], xy[2 * (size_t)slot + 1]);
-    mrows[slot] = p.win;
-    lat_rows[slot] = p.lat_cut;
-    pix_rows[slot] = p.pix_cut;
-    flags[slot] = p.win.flags;
+    sicn_roi_move::store_placement(slot, sicn_ctx_roi_move::place_slot(s, xy[2 * (size_t)slot], xy[2 * (size_t)slot + 1]), mrows, lat_rows,
+                                   pix_rows, flags);
     const CtxRow *r = rows + s.image;
     CtxWorkspace w;
     ctx_carve(w, workspace + r->ws_off, r->g.nst[0] + r->g.nst[1], wstream_cap(r->g.S));
@@ -160,18 +155,15 @@ struct sicn_ragged_ctx_roi_move {
     int n_slots = 0, n_distinct = 0;
     sicn_ctx_roi_move::Totals totals;
     const CtxRow *d_rows = nullptr;         // the coder's
-    SlotRow *d_srows = nullptr;             // [n_slots] constant
-    uint32_t *d_item_slot[2] = {nullptr, nullptr}, *d_lat_item_slot = nullptr, *d_pix_item_slot = nullptr, *d_images = nullptr;
-    MoveRow *d_mrows = nullptr;             // [n_slots] written by k_ctx_roi_place
-    CutRow *d_lat_rows = nullptr, *d_pix_rows = nullptr;
+    uint32_t *d_item_slot[2] = {nullptr, nullptr}, *d_images = nullptr;
+    sicn_roi_move::MoveTables<SlotRow, MoveRow> t;
 };
 
 extern "C" void sicn_ragged_ctx_roi_move_free(sicn_ragged_ctx_roi_move *mv)
 {
     if (!mv) return;
-    void *blocks[] = {mv->d_srows, mv->d_item_slot[0], mv->d_item_slot[1], mv->d_lat_item_slot, mv->d_pix_item_slot, mv->d_images,
-                      mv->d_mrows, mv->d_lat_rows, mv->d_pix_rows};
-    for (void *b : blocks)
+    mv->t.release();
+    for (void *b : {(void *)mv->d_item_slot[0], (void *)mv->d_item_slot[1], (void *)mv->d_images})
         if (b) (void)hipFree(b);
     delete mv;
 }
@@ -202,32 +194,17 @@ extern "C" int sicn_ragged_ctx_roi_move_create(const sicn_ragged_ctx_coder *code
         if (!rc) {
             mv->n_slots = n_slots;
             mv->d_rows = (const CtxRow *)v.d_rows;
-            std::vector<uint32_t> item_slot[2], lat_item_slot, pix_item_slot, images;
+            std::vector<uint32_t> groups[2], images;
             std::vector<char> named(n, 0);
-            for (int k = 0; k < n_slots; k++) {
-                const SlotRow &s = srows[(size_t)k];
-                for (int set = 0; set < 2; set++)
-                    item_slot[set].insert(item_slot[set].end(), (size_t)((s.max_streams[set] + CTX_WPB_DEC - 1) / CTX_WPB_DEC), (uint32_t)k);
-                lat_item_slot.insert(lat_item_slot.end(), (size_t)((s.rh_cap + sicn_ctx_roi_move::CUT_ROWS - 1) / sicn_ctx_roi_move::CUT_ROWS), (uint32_t)k);
-                pix_item_slot.insert(pix_item_slot.end(), (size_t)((s.h + sicn_ctx_roi_move::CUT_ROWS - 1) / sicn_ctx_roi_move::CUT_ROWS), (uint32_t)k);
+            for (const SlotRow &s : srows) {
+                for (int set = 0; set < 2; set++) groups[set].push_back((s.max_streams[set] + CTX_WPB_DEC - 1) / CTX_WPB_DEC);
                 named[s.image] = 1;
             }
             for (size_t i = 0; i < n; i++)
                 if (named[i]) images.push_back((uint32_t)i);
             mv->n_distinct = (int)images.size();
-            // the rows the placement writes start as the placement of (0, 0): a cut that runs before any decode stays in bounds
-            std::vector<MoveRow> mrows((size_t)n_slots);
-            std::vector<CutRow> lat_rows((size_t)n_slots), pix_rows((size_t)n_slots);
-            for (int k = 0; k < n_slots; k++) {
-                const sicn_ctx_roi_move::Placement p = sicn_ctx_roi_move::place_slot(srows[(size_t)k], 0, 0);
-                mrows[(size_t)k] = p.win; lat_rows[(size_t)k] = p.lat_cut; pix_rows[(size_t)k] = p.pix_cut;
-            }
-            auto up = [](const std::vector<uint32_t> &t, uint32_t **dev) { return t.empty() || sicn::upload(t.data(), t.size() * sizeof(uint32_t), dev); };
-            if (!sicn::upload(srows.data(), srows.size() * sizeof(SlotRow), &mv->d_srows) || !up(item_slot[0], &mv->d_item_slot[0]) ||
-                !up(item_slot[1], &mv->d_item_slot[1]) || !up(lat_item_slot, &mv->d_lat_item_slot) || !up(pix_item_slot, &mv->d_pix_item_slot) ||
-                !up(images, &mv->d_images) || !sicn::upload(mrows.data(), mrows.size() * sizeof(MoveRow), &mv->d_mrows) ||
-                !sicn::upload(lat_rows.data(), lat_rows.size() * sizeof(CutRow), &mv->d_lat_rows) ||
-                !sicn::upload(pix_rows.data(), pix_rows.size() * sizeof(CutRow), &mv->d_pix_rows))
+            if (!sicn_roi_move::upload_item_slots(groups[0], &mv->d_item_slot[0]) || !sicn_roi_move::upload_item_slots(groups[1], &mv->d_item_slot[1]) ||
+                !sicn::upload(images.data(), images.size() * sizeof(uint32_t), &mv->d_images) || !mv->t.build(srows))
                 rc = SICN_ENOMEM;
         }
     } catch (const std::bad_alloc &) { rc = SICN_ENOMEM; }
@@ -273,23 +250,22 @@ extern "C" int sicn_ragged_ctx_roi_move_decode_async(const sicn_ragged_ctx_roi_m
     hipStream_t stream = (hipStream_t)hip_stream;
     uint8_t *ws = (uint8_t *)workspace;
     const unsigned n_slots = (unsigned)mv->n_slots;
-    hipLaunchKernelGGL(k_ctx_roi_place, dim3((n_slots + 63) / 64), dim3(64), 0, stream, xy_dev, mv->d_srows, n_slots, mv->d_rows, ws, mv->d_mrows,
-                       mv->d_lat_rows, mv->d_pix_rows, flags_dev);
+    const auto &t = mv->t;
+    hipLaunchKernelGGL(k_ctx_roi_place, dim3((n_slots + 63) / 64), dim3(64), 0, stream, xy_dev, t.d_srows, n_slots, mv->d_rows, ws, t.d_mrows,
+                       t.d_lat_rows, t.d_pix_rows, flags_dev);
     // the full decoder's reason: a non-anchor's class reads its neighbours' bytes whatever they hold
     if (hipMemsetAsync(band, 0, (size_t)mv->totals.band, stream) != hipSuccess) return SICN_ENODEV;
     hipLaunchKernelGGL(k_ctx_roi_move_decode<0>, dim3((unsigned)mv->totals.items[0]), dim3(64 * CTX_WPB_DEC), 0, stream, containers, scales, band, ws,
-                       mv->d_rows, mv->d_srows, mv->d_mrows, mv->d_item_slot[0]);
+                       mv->d_rows, t.d_srows, t.d_mrows, mv->d_item_slot[0]);
     if (mv->totals.items[1])   // (slots on 1 x 1 latents have no non-anchor capacity)
         hipLaunchKernelGGL(k_ctx_roi_move_decode<1>, dim3((unsigned)mv->totals.items[1]), dim3(64 * CTX_WPB_DEC), 0, stream, containers, scales, band,
-                           ws, mv->d_rows, mv->d_srows, mv->d_mrows, mv->d_item_slot[1]);
-    hipLaunchKernelGGL(k_ctx_roi_move_finish, dim3(n_slots), dim3(64), 0, stream, (uint32_t *)status_dev, ws, mv->d_rows, mv->d_srows, mv->d_mrows);
+                           ws, mv->d_rows, t.d_srows, t.d_mrows, mv->d_item_slot[1]);
+    hipLaunchKernelGGL(k_ctx_roi_move_finish, dim3(n_slots), dim3(64), 0, stream, (uint32_t *)status_dev, ws, mv->d_rows, t.d_srows, t.d_mrows);
     if (hipGetLastError() != hipSuccess) return SICN_ENODEV;
-    return sicn::ragged_cut_launch(mv->d_lat_rows, mv->d_lat_item_slot, (unsigned)mv->totals.lat_items, band, window_latent, hip_stream);
+    return t.cut(false, band, window_latent, hip_stream);
 }
 
 extern "C" int sicn_ragged_ctx_roi_move_cut_async(const sicn_ragged_ctx_roi_move *mv, const uint8_t *recon, uint8_t *roi_out, void *hip_stream)
 {
-    if (!mv || !recon || !roi_out) return SICN_EINVAL;
-    if (int rc = sicn::chip_geom(nullptr)) return rc;
-    return sicn::ragged_cut_launch(mv->d_pix_rows, mv->d_pix_item_slot, (unsigned)mv->totals.pix_items, recon, roi_out, hip_stream);
+    return mv ? mv->t.cut(true, recon, roi_out, hip_stream) : SICN_EINVAL;
 }

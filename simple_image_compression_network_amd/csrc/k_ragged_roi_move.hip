@@ -3,15 +3,13 @@
 // k_ragged_window.hip, k_ragged_codec.hip and sicn_codec.hip keep their code as it is.  The two cuts are k_ragged_window.hip's
 // k_ragged_cut itself (sicn::ragged_cut_launch) over rows this file writes.
 //
-// Tables.  Constant, uploaded at creation:
-//   srows[slot]      : SlotRow (roi_move_host.hpp), the slot's size, capacities, offsets and first work items, its image's geometry
+// Tables.  What no coder changes is k_roi_move_common.hpp's MoveTables, shared with k_ragged_ctx_roi_move.hip: srows[slot] (SlotRow
+// of roi_move_host.hpp: the shared SlotGeom, then the slot's workspace block, first decode item, max_streams and its image's stream
+// length and symbols), the two cuts' item -> slot maps, and the rows k_roi_place writes on the stream, one thread per slot, from
+// place_slot() — the function the host entry points call too: mrows[slot] (MoveRow, the streams [first_stream, end_stream) the slot
+// selects now and where they land in its band), lat_rows[slot], pix_rows[slot], and the caller's flags[slot].  This file's own:
 //   item_slot[item]  : the slot of a work item of the decode grid (sum of max_streams) — ONE load resolves item -> slot
-//   lat_item_slot[], pix_item_slot[] : the same for the two cuts' grids, which the capacities fix
 //   rows[image]      : the CODER's CoderRow table
-// Written by k_roi_place on the stream, one thread per slot, from place_slot() — the function the host entry points call too:
-//   mrows[slot]      : MoveRow, the streams [first_stream, end_stream) the slot selects now and where they land in its band
-//   lat_rows[slot], pix_rows[slot] : the CutRows of the latent cut and of the pixel cut
-//   flags[slot]      : the caller's flag words
 // k_roi_move_decode: slot -> image is one more wave-uniform load; a surplus item (its stream >= end_stream) returns before it reads
 // or writes anything else; otherwise ransw_decode_body runs unchanged on the slot's OWN workspace block with the stream's real
 // index, as in k_ragged_decode_window.  k_roi_move_finish: one workgroup per slot, dec_finish_window_body, one status pair per slot.
@@ -20,9 +18,7 @@
 
 #include "../../include/sicn_ragged_roi_move.h"
 #include "k_codec_body.hpp"
-#include "roi_move_host.hpp"
-#include "sicn_internal.h"
-#include "sicn_weights_io.h"
+#include "k_roi_move_common.hpp"
 
 namespace {
 
@@ -36,11 +32,8 @@ __global__ __launch_bounds__(64) void k_roi_place(const int32_t *__restrict__ xy
 {
     const uint32_t slot = blockIdx.x * 64u + threadIdx.x;
     if (slot >= n_slots) return;
-    const sicn_roi_move::Placement p = sicn_roi_move::place_slot(srows[slot], xy[2 * (size_t)slot], xy[2 * (size_t)slot + 1]);
-    mrows[slot] = p.win;
-    lat_rows[slot] = p.lat_cut;
-    pix_rows[slot] = p.pix_cut;
-    flags[slot] = p.win.flags;
+    sicn_roi_move::store_placement(slot, sicn_roi_move::place_slot(srows[slot], xy[2 * (size_t)slot], xy[2 * (size_t)slot + 1]), mrows, lat_rows,
+                                   pix_rows, flags);
 }
 
 // the slot's image as the stage bodies see it: the coder's row with the slot's own workspace block
@@ -138,18 +131,15 @@ struct sicn_ragged_roi_move {
     bool bigtab = false;                    // the decode form, chosen once from the capacity
     sicn_roi_move::Totals totals;
     const CoderRow *d_rows = nullptr;       // the coder's
-    SlotRow *d_srows = nullptr;             // [n_slots] constant
-    uint32_t *d_item_slot = nullptr, *d_lat_item_slot = nullptr, *d_pix_item_slot = nullptr;
-    MoveRow *d_mrows = nullptr;             // [n_slots] written by k_roi_place
-    CutRow *d_lat_rows = nullptr, *d_pix_rows = nullptr;
+    uint32_t *d_item_slot = nullptr;
+    sicn_roi_move::MoveTables<SlotRow, MoveRow> t;
 };
 
 extern "C" void sicn_ragged_roi_move_free(sicn_ragged_roi_move *mv)
 {
     if (!mv) return;
-    void *blocks[] = {mv->d_srows, mv->d_item_slot, mv->d_lat_item_slot, mv->d_pix_item_slot, mv->d_mrows, mv->d_lat_rows, mv->d_pix_rows};
-    for (void *b : blocks)
-        if (b) (void)hipFree(b);
+    mv->t.release();
+    if (mv->d_item_slot) (void)hipFree(mv->d_item_slot);
     delete mv;
 }
 
@@ -185,31 +175,9 @@ extern "C" int sicn_ragged_roi_move_create(const sicn_ragged_coder *coder, const
             mv->d_rows = (const CoderRow *)v.d_rows;
             // the latency form (one 16 KB table) while all waves of the CAPACITY fit the chip at five per CU, the full decoder's rule
             mv->bigtab = mv->totals.items <= 5ull * (unsigned)chip.n_cu;
-            std::vector<uint32_t> item_slot, lat_item_slot, pix_item_slot;
-            item_slot.reserve((size_t)mv->totals.items);
-            lat_item_slot.reserve((size_t)mv->totals.lat_items);
-            pix_item_slot.reserve((size_t)mv->totals.pix_items);
-            for (int k = 0; k < n_slots; k++) {
-                const SlotRow &s = srows[(size_t)k];
-                item_slot.insert(item_slot.end(), (size_t)s.max_streams, (uint32_t)k);
-                lat_item_slot.insert(lat_item_slot.end(), (size_t)((s.rh_cap + sicn_roi_move::CUT_ROWS - 1) / sicn_roi_move::CUT_ROWS), (uint32_t)k);
-                pix_item_slot.insert(pix_item_slot.end(), (size_t)((s.h + sicn_roi_move::CUT_ROWS - 1) / sicn_roi_move::CUT_ROWS), (uint32_t)k);
-            }
-            // the rows the placement writes start as the placement of (0, 0): a cut that runs before any decode stays in bounds
-            std::vector<MoveRow> mrows((size_t)n_slots);
-            std::vector<CutRow> lat_rows((size_t)n_slots), pix_rows((size_t)n_slots);
-            for (int k = 0; k < n_slots; k++) {
-                const sicn_roi_move::Placement p = sicn_roi_move::place_slot(srows[(size_t)k], 0, 0);
-                mrows[(size_t)k] = p.win; lat_rows[(size_t)k] = p.lat_cut; pix_rows[(size_t)k] = p.pix_cut;
-            }
-            if (!sicn::upload(srows.data(), srows.size() * sizeof(SlotRow), &mv->d_srows) ||
-                !sicn::upload(item_slot.data(), item_slot.size() * sizeof(uint32_t), &mv->d_item_slot) ||
-                !sicn::upload(lat_item_slot.data(), lat_item_slot.size() * sizeof(uint32_t), &mv->d_lat_item_slot) ||
-                !sicn::upload(pix_item_slot.data(), pix_item_slot.size() * sizeof(uint32_t), &mv->d_pix_item_slot) ||
-                !sicn::upload(mrows.data(), mrows.size() * sizeof(MoveRow), &mv->d_mrows) ||
-                !sicn::upload(lat_rows.data(), lat_rows.size() * sizeof(CutRow), &mv->d_lat_rows) ||
-                !sicn::upload(pix_rows.data(), pix_rows.size() * sizeof(CutRow), &mv->d_pix_rows))
-                rc = SICN_ENOMEM;
+            std::vector<uint32_t> streams;
+            for (const SlotRow &s : srows) streams.push_back(s.max_streams);
+            if (!sicn_roi_move::upload_item_slots(streams, &mv->d_item_slot) || !mv->t.build(srows)) rc = SICN_ENOMEM;
         }
     } catch (const std::bad_alloc &) { rc = SICN_ENOMEM; }
     if (rc) {
@@ -235,23 +203,22 @@ extern "C" int sicn_ragged_roi_move_decode_async(const sicn_ragged_roi_move *mv,
     uint8_t *ws = (uint8_t *)workspace;
     const uint32_t *valid = (const uint32_t *)valid_dev_or_null;
     const unsigned n_slots = (unsigned)mv->n_slots, items = (unsigned)mv->totals.items;
-    hipLaunchKernelGGL(k_roi_place, dim3((n_slots + 63) / 64), dim3(64), 0, stream, xy_dev, mv->d_srows, n_slots, mv->d_mrows, mv->d_lat_rows,
-                       mv->d_pix_rows, flags_dev);
+    const auto &t = mv->t;
+    hipLaunchKernelGGL(k_roi_place, dim3((n_slots + 63) / 64), dim3(64), 0, stream, xy_dev, t.d_srows, n_slots, t.d_mrows, t.d_lat_rows,
+                       t.d_pix_rows, flags_dev);
     if (mv->bigtab)
-        hipLaunchKernelGGL(k_roi_move_decode<true>, dim3(items), dim3(64), 0, stream, containers, valid, band, ws, mv->d_rows, mv->d_srows,
-                           mv->d_mrows, mv->d_item_slot);
+        hipLaunchKernelGGL(k_roi_move_decode<true>, dim3(items), dim3(64), 0, stream, containers, valid, band, ws, mv->d_rows, t.d_srows,
+                           t.d_mrows, mv->d_item_slot);
     else
-        hipLaunchKernelGGL(k_roi_move_decode<false>, dim3(items), dim3(64), 0, stream, containers, valid, band, ws, mv->d_rows, mv->d_srows,
-                           mv->d_mrows, mv->d_item_slot);
+        hipLaunchKernelGGL(k_roi_move_decode<false>, dim3(items), dim3(64), 0, stream, containers, valid, band, ws, mv->d_rows, t.d_srows,
+                           t.d_mrows, mv->d_item_slot);
     hipLaunchKernelGGL(k_roi_move_finish, dim3(n_slots), dim3(256), 0, stream, containers, valid, (uint32_t *)status_dev, ws, mv->d_rows,
-                       mv->d_srows, mv->d_mrows);
+                       t.d_srows, t.d_mrows);
     if (hipGetLastError() != hipSuccess) return SICN_ENODEV;
-    return sicn::ragged_cut_launch(mv->d_lat_rows, mv->d_lat_item_slot, (unsigned)mv->totals.lat_items, band, window_latent, hip_stream);
+    return t.cut(false, band, window_latent, hip_stream);
 }
 
 extern "C" int sicn_ragged_roi_move_cut_async(const sicn_ragged_roi_move *mv, const uint8_t *recon, uint8_t *roi_out, void *hip_stream)
 {
-    if (!mv || !recon || !roi_out) return SICN_EINVAL;
-    if (int rc = sicn::chip_geom(nullptr)) return rc;
-    return sicn::ragged_cut_launch(mv->d_pix_rows, mv->d_pix_item_slot, (unsigned)mv->totals.pix_items, recon, roi_out, hip_stream);
+    return mv ? mv->t.cut(true, recon, roi_out, hip_stream) : SICN_EINVAL;
 }

@@ -23,6 +23,7 @@ Weights: the main transform uses the PARAM tables (memdata_nonsquare.h); the hyp
 reference values and are seeded random (the reference's own weights are placeholders too)."""
 from __future__ import annotations
 
+import ctypes
 from typing import Optional
 
 import numpy as np
@@ -127,7 +128,6 @@ class HyperpriorCodec:
 
     def _scale_map(self, z):
         """h_s(z) cropped to the latent's shape (deconv doubles a size that conv rounded up)."""
-        import ctypes
         self.h_s.run_layers(0, 1, z, out=self.s_full)
         n, h, w, c = self.y.shape
         _, hs, ws, _ = self.s_full.shape
@@ -425,7 +425,7 @@ class RaggedHyperpriorRoi:
         self.codec.check()
 
 
-class MovingHyperpriorRoi(api._lib.Handle):
+class MovingHyperpriorRoi(api._MovingRoiChain):
     """Pixel rectangles of fixed SIZE whose POSITIONS are read from device memory on every call, decoded from a
     RaggedHyperpriorCodec's containers (include/sicn_ragged_ctx_roi_move.h).  Made once for a list of slots; what does not depend on
     a rectangle runs once per set of containers, in `prepare`:
@@ -444,53 +444,12 @@ class MovingHyperpriorRoi(api._lib.Handle):
     clamped and bit 0 of the slot's `.flags` word says so.  `.status`: device int32 [n_slots][2], the verdicts per slot;
     `.flags`: device int32 [n_slots].  The containers must stay the bytes `prepare` read until the last `decode` of them has run.
     Also `codec.moving_roi(slots)`."""
-    _free = "sicn_ragged_ctx_roi_move_free"
+    _free, _abi, _slot_type, _n_totals = "sicn_ragged_ctx_roi_move_free", "sicn_ragged_ctx_roi_move", api._lib.RaggedCtxRoiMoveSlot, 7
 
     def __init__(self, codec_, slots):
-        import ctypes
-
-        import torch
-        _lib = api._lib
-        L = _lib.lib()
         self.codec = codec_
-        net, c = codec_.main, codec_.y_coder
-        self.slots = [tuple(int(v) for v in s) for s in slots]
-        n = len(self.slots)
-        if n < 1 or any(len(s) != 3 for s in self.slots):
-            raise ValueError("slots: at least one (image, w, h)")
-        for img, w, h in self.slots:
-            if not 0 <= img < len(net.sizes):
-                raise ValueError(f"slot image {img}: the net has {len(net.sizes)} images")
-            if w < 1 or h < 1 or w > net.sizes[img][0] or h > net.sizes[img][1]:
-                raise ValueError(f"a {w} x {h} rectangle is empty or larger than the {net.sizes[img][0]} x {net.sizes[img][1]} image")
-        self.device = codec_.device
-        self._cslots = (_lib.RaggedRoiSlot * n)(*[_lib.RaggedRoiSlot(*s) for s in self.slots])
-        self.layout = (_lib.RaggedCtxRoiMoveSlot * n)()
-        totals = (ctypes.c_uint64 * 7)()
-        _lib.check(L.sicn_ragged_ctx_roi_move_layout(c._lat_w, c._lat_h, c.lat_c, c._wss, c._img_w, c._img_h, len(c.shapes), self._cslots, n,
-                                                     self.layout, totals), "sicn_ragged_ctx_roi_move_layout")
-        self.band_bytes, self.latent_bytes, self.recon_bytes, self.roi_bytes, ws_bytes = (int(v) for v in totals[:5])
-        self.items = (int(totals[5]), int(totals[6]))
-        self._h = ctypes.c_void_p()
-        with torch.cuda.device(self.device):
-            _lib.check(L.sicn_ragged_ctx_roi_move_create(c._h, self._cslots, n, ctypes.byref(self._h)), "sicn_ragged_ctx_roi_move_create")
-        # the window net: layers 4 .. on the main net's weights, descs and GDN objects over the sizes (16 cw_cap, 16 rh_cap)
-        self.window_net = api.RaggedNet([(16 * int(s.cw_cap), 16 * int(s.rh_cap)) for s in self.layout], device=self.device,
-                                        shared_weights=net.weights, descs=net.descs, gdn=net.gdn)
-        last = len(net.descs) - 1
-        if self.window_net.nbytes(3) != self.latent_bytes or self.window_net.nbytes(last) != self.recon_bytes:
-            raise RuntimeError("the window net's tensors are not the layout's")
-        self.window_net.workspace()
-        u8 = dict(dtype=torch.uint8, device=self.device)
-        self.band = torch.empty(max(self.band_bytes, 16), **u8)
-        self.latent = torch.empty(self.latent_bytes, **u8)
-        self.recon = torch.empty(self.recon_bytes, **u8)
-        self.roi = torch.empty(self.roi_bytes, **u8)
-        self.ws = torch.empty(max(int(L.sicn_ragged_ctx_roi_move_workspace_bytes(self._h)), ws_bytes, 256), **u8)
-        self.status = torch.zeros((n, 2), dtype=torch.int32, device=self.device)
-        self.flags = torch.zeros(n, dtype=torch.int32, device=self.device)
-        self.xy = torch.zeros((n, 2), dtype=torch.int32, device=self.device)      # where a host sequence of positions is copied
-        self.uniform = len({(w, h) for _, w, h in self.slots}) == 1
+        self._check_slots(codec_.main, slots)
+        self._make(codec_.main, codec_.y_coder)
         self._containers = None     # (slot buffer, valid or None) of the last prepare: kept alive, read by every decode
         self._unpacked = False      # the last prepare read an archive: check() reports its verdict first
 
@@ -498,7 +457,6 @@ class MovingHyperpriorRoi(api._lib.Handle):
         """Containers as in `RaggedHyperpriorCodec.decode` (default: the last encode's): everything of a decode that no rectangle
         changes — unpack, the z coder, h_s and its crop (-> codec.s), and the y containers' fixed part.  Enqueue only, on the current
         stream; once per set of containers, then any number of `decode`s."""
-        import ctypes
         c = self.codec
         y = c.y_coder
         y_valid = c._decode_scales(z_containers, y_containers, archive, images)
@@ -519,48 +477,14 @@ class MovingHyperpriorRoi(api._lib.Handle):
         sequence, which is copied into the object's own device tensor on the stream.  Returns the ROI pixels: `out` (a flat tensor
         of roi_bytes; default the object's own), as [n_slots][h][w][3] where all slots have one size, flat otherwise (`views` gives
         them per slot).  Enqueue only, nothing allocated.  RuntimeError if `prepare` has not run."""
-        import ctypes
-
-        import torch
         if self._containers is None:
             raise RuntimeError("prepare() has not run: there is no container whose fixed part a decode could read")
-        n = len(self.slots)
-        if isinstance(xy, torch.Tensor) and xy.is_cuda:
-            if not (xy.dtype == torch.int32 and xy.is_contiguous() and tuple(xy.shape) == (n, 2)):
-                raise TypeError(f"xy as a tensor: a contiguous CUDA int32 tensor of shape ({n}, 2)")
-        else:
-            host = np.asarray(xy)
-            if host.shape != (n, 2) or host.dtype.kind not in "iu" or host.min() < -2 ** 31 or host.max() >= 2 ** 31:
-                raise ValueError(f"xy: one int32 (x0, y0) per slot, {n}")
-            host = torch.from_numpy(host.astype(np.int32))
-            ts = stream if isinstance(stream, torch.cuda.Stream) else None
-            with torch.cuda.stream(ts):
-                self.xy.copy_(host)
-            xy = self.xy
-        out = self.roi if out is None else out
-        api._check_tensor(out, (self.roi_bytes,), "out")
-        L, sp, vp = api._lib.lib(), api._stream_ptr(stream), ctypes.c_void_p
-        api._lib.check(L.sicn_ragged_ctx_roi_move_decode_async(
-            self._h, vp(xy.data_ptr()), vp(self._containers[0].data_ptr()), vp(self.codec.s.data_ptr()), vp(self.band.data_ptr()),
-            vp(self.latent.data_ptr()), vp(self.status.data_ptr()), vp(self.flags.data_ptr()), vp(self.ws.data_ptr()), self.ws.numel(), sp),
-            "sicn_ragged_ctx_roi_move_decode_async")
-        self.window_net.run_layers(4, len(self.codec.main.descs) - 1, self.latent, out=self.recon, stream=stream)
-        api._lib.check(L.sicn_ragged_ctx_roi_move_cut_async(self._h, vp(self.recon.data_ptr()), vp(out.data_ptr()), sp),
-                       "sicn_ragged_ctx_roi_move_cut_async")
-        if self.uniform:
-            return out.view(n, self.slots[0][2], self.slots[0][1], 3)
-        return out
-
-    def views(self, roi):
-        """Per-slot [h][w][3] views of what `decode` returned."""
-        flat = roi.reshape(-1)
-        api._check_tensor(flat, (self.roi_bytes,), "roi")
-        return [flat[int(s.roi_offset):int(s.roi_offset) + h * w * 3].view(h, w, 3) for s, (_, w, h) in zip(self.layout, self.slots)]
+        return self._decode(self._positions(xy, stream), out, stream, ctypes.c_void_p(self._containers[0].data_ptr()),
+                            ctypes.c_void_p(self.codec.s.data_ptr()))
 
     def place(self, xy):
         """Host arithmetic (sicn_ragged_ctx_roi_move_place): per slot the dict {x0, y0 after the clamp, c0, r0, cw, rh, x, y, flags,
         first_stream, end_stream (per set), band_row0, band_rows, symbols, lat_bias, cut_offset}."""
-        import ctypes
         _lib = api._lib
         y, out = self.codec.y_coder, []
         for (img, w, h), s, (x0, y0) in zip(self.slots, self.layout, xy):

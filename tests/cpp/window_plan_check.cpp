@@ -64,8 +64,9 @@ void plans()
                 }
     // margins for every admissible layer count, and the largest sizes
     for (int l = 1; l <= sicn_window::MAX_UP_LAYERS; l++) {
-        int64_t lo, hi;
-        sicn_window::margins(l, &lo, &hi);
+        int64_t lo = 0, hi = 0;
+        for (int k = 0; k < l; k++) { lo = 2 * lo + 1; hi = 2 * hi + 2; }      // m' = 2 m + 1, n' = 2 n + 2 per deconv522 layer
+        EXPECT(lo == sicn_window::margin_lo(l) && hi == sicn_window::margin_hi(l));
         EXPECT(lo == ((int64_t)1 << l) - 1 && hi == 2 * (((int64_t)1 << l) - 1));
     }
     sicn_ragged_roi out;

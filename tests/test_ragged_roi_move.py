@@ -377,6 +377,21 @@ def test_an_object_collected_during_a_stream_capture_is_freed_after_it(monkeypat
     assert _lib._capturing.__call__() is False
 
 
+def test_python_class_refuses_bad_slots_before_anything_is_made():
+    """The seven cases of test_ragged_ctx_roi_move.py's test of the same name, against api.MovingRoi: the base class of the two
+    states these checks once, and a stub net that has nothing but its sizes shows that nothing else was asked of it."""
+    from simple_image_compression_network_amd import api
+
+    class Net:
+        sizes = [(112, 144), (100, 131)]
+
+    for slots, text in [([], "at least one"), ([(0, 20)], "at least one"), ([(2, 20, 20)], "the net has 2 images"),
+                        ([(-1, 20, 20)], "the net has 2 images"), ([(0, 113, 20)], "empty or larger"), ([(1, 20, 132)], "empty or larger"),
+                        ([(0, 20, 20), (0, 0, 20)], "empty or larger")]:
+        with pytest.raises(ValueError, match=text):
+            api.MovingRoi(Net(), slots)
+
+
 def test_roi_move_host_under_the_sanitizers(tmp_path):
     """tests/cpp/roi_move_plan_check.cpp — the pure-host header csrc/roi_move_host.hpp with its own main — built with the address and
     undefined-behaviour sanitizers and run as a child process: placement and layout into heap blocks of exactly their length, the

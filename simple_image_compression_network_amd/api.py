@@ -605,9 +605,8 @@ class MovingRoi(_MovingRoiChain):
         xy = self._positions(xy, stream)
         slots = c.slot_buffer if slots is None else slots
         c._flat(slots, c.slot_bytes, "slots")
-        own = slots is c.slot_buffer
-        vptr = None if (valid is False or (valid is None and not own)) else ctypes.c_void_p((c.enc_status if valid is None else valid).data_ptr())
-        return self._decode(xy, out, stream, ctypes.c_void_p(slots.data_ptr()), vptr)
+        from .codec import _valid_ptr
+        return self._decode(xy, out, stream, ctypes.c_void_p(slots.data_ptr()), _valid_ptr(c.enc_status, slots is c.slot_buffer, valid))
 
     def place(self, xy):
         """Host arithmetic (sicn_ragged_roi_move_place): per slot the dict {x0, y0 after the clamp, c0, r0, cw, rh, x, y, flags}."""

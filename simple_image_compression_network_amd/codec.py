@@ -38,6 +38,15 @@ def _stream_ptr(stream):
     return ctypes.c_void_p(getattr(stream, "cuda_stream", stream))
 
 
+def _valid_ptr(own_status, own: bool, valid):
+    """The `valid` argument of a decode as the library takes it.  None — the whole slot is trusted — for `valid=False` and, by
+    default, for slots that are not the object's own; by default the object's encoder status (`own_status`) for its own slots;
+    otherwise the status array the caller passed."""
+    if valid is False or (valid is None and not own):
+        return None
+    return ctypes.c_void_p((own_status if valid is None else valid).data_ptr())
+
+
 def encode_latent(latent, image_width: int, image_height: int, mode: int = RANSW, stream=None):
     """latent: CUDA uint8 tensor [H/16][W/16][C] (one image).  Returns a CUDA uint8 tensor holding the container."""
     import torch
@@ -186,8 +195,7 @@ class LatentCoder:
             raise TypeError(f"out_latents must be a contiguous CUDA uint8 tensor of shape {self.shape}")
         if not (slots.is_cuda and slots.dtype == torch.uint8 and slots.is_contiguous() and tuple(slots.shape) == (n, self.slot)):
             raise TypeError("slots must be a contiguous CUDA uint8 tensor [n][slot_bytes]")
-        own = slots is self.slots
-        vptr = None if (valid is False or (valid is None and not own)) else ctypes.c_void_p((self.enc_status if valid is None else valid).data_ptr())
+        vptr = _valid_ptr(self.enc_status, slots is self.slots, valid)
         _lib.check(_lib.lib().sicn_codec_decode_batch_async_sl(
             ctypes.c_void_p(slots.data_ptr()), self.slot, vptr, n, w, h, c, ctypes.c_void_p(out_latents.data_ptr()), h * w * c,
             ctypes.c_void_p(self.dec_status.data_ptr()), ctypes.c_void_p(self.ws.data_ptr()), self.ws.numel(), _stream_ptr(stream),
@@ -208,15 +216,14 @@ class LatentCoder:
             raise _lib.SicnError(-22 if any(v & ~128 for v in d) else -74, f"rANS-W decode status {d}")
 
 
-class RaggedLatentCoder(_lib.Handle):
-    """The ragged rANS-W pair (include/sicn_ragged_codec.h): n latents of n DIFFERENT shapes -> n containers with three launches for
-    the whole batch, and back with two.  `shapes`: [(lat_h, lat_w)] per image, `lat_c` channels in all of them; `image_sizes`:
-    [(width, height)], header fields only.  Latents travel as a ragged tensor — a flat CUDA uint8 tensor, the images' [h][w][c]
-    arrays back to back (api.RaggedNet's boundary 3) — containers in one flat slot buffer, image i's slot at `images[i].slot_offset`.
-    stream_symbols: None or "auto" = `auto_stream_symbols` of EACH image's own latent, one value for all, or one per image.
-    Container i is byte-identical to `LatentCoder(1, h_i, w_i, lat_c, stream_symbols=...)`'s and decodes with `decode_latent`.
-    Same conventions as LatentCoder: enqueue only; verdicts and sizes stay on the device until `check()` / `sizes()` fetch them."""
-    _free = "sicn_ragged_coder_free"
+class _RaggedCoder(_lib.Handle):
+    """What RaggedLatentCoder and RaggedContextCoder share: the arrays that describe the batch, layout and library object, the slot
+    buffer, the workspace and the two status tensors; `for_containers`, the per-image views and `containers`.  A subclass names its
+    entry points (`_layout`, `_create`, `_workspace_bytes`, `_free`), the struct of its layout (`_image_type`), its container mode
+    and display name (`_mode`, `_name`), whether its errors carry `.image`, and how it resolves `stream_symbols`; `encode` and
+    `decode` are the subclass's own."""
+    _layout = _create = _workspace_bytes = ""
+    _image_type, _mode, _name, _error_image = None, None, "", False
 
     def __init__(self, shapes, lat_c: int, image_sizes=None, stream_symbols=None, device=None):
         import torch
@@ -227,44 +234,36 @@ class RaggedLatentCoder(_lib.Handle):
         self.image_sizes = [(int(w), int(h)) for w, h in image_sizes] if image_sizes is not None else [(0, 0)] * n
         if len(self.image_sizes) != n:
             raise ValueError("image_sizes: one (width, height) per shape")
-        if stream_symbols in (None, "auto"):
-            self.stream_symbols = [auto_stream_symbols(h * w * self.lat_c) for h, w in self.shapes]
-        elif isinstance(stream_symbols, int):
-            self.stream_symbols = [stream_symbols] * n
-        else:
-            self.stream_symbols = [int(v) for v in stream_symbols]
-            if len(self.stream_symbols) != n:
-                raise ValueError("stream_symbols: one value, or one per shape")
+        self.stream_symbols = self._stream_symbols(stream_symbols)
         u32 = ctypes.c_uint32 * max(n, 1)
         self._lat_w, self._lat_h = u32(*[w for _, w in self.shapes]), u32(*[h for h, _ in self.shapes])
         self._wss = u32(*self.stream_symbols)
         self._img_w, self._img_h = u32(*[w for w, _ in self.image_sizes]), u32(*[h for _, h in self.image_sizes])
-        self.images = (_lib.RaggedCodecImage * max(n, 1))()          # where image i lies: offsets, slot capacity, stream cut
+        self.images = (self._image_type * max(n, 1))()               # where image i lies: offsets, slot capacity, its streams
         totals = (ctypes.c_uint64 * 3)()
-        _lib.check(L.sicn_ragged_codec_layout(self._lat_w, self._lat_h, self.lat_c, self._wss, n, self.images, totals),
-                   "sicn_ragged_codec_layout")
+        _lib.check(getattr(L, self._layout)(self._lat_w, self._lat_h, self.lat_c, self._wss, n, self.images, totals), self._layout)
         self.latent_bytes, self.slot_bytes = int(totals[0]), int(totals[1])
         self.device = torch.device(device if device is not None else "cuda")
         self._h = ctypes.c_void_p()
         with torch.cuda.device(self.device):
-            _lib.check(L.sicn_ragged_coder_create(self._lat_w, self._lat_h, self.lat_c, self._wss, self._img_w, self._img_h, n,
-                                                  ctypes.byref(self._h)), "sicn_ragged_coder_create")
+            _lib.check(getattr(L, self._create)(self._lat_w, self._lat_h, self.lat_c, self._wss, self._img_w, self._img_h, n,
+                                                ctypes.byref(self._h)), self._create)
         self.slot_buffer = torch.empty(self.slot_bytes, dtype=torch.uint8, device=self.device)
-        self.ws = torch.empty(max(int(L.sicn_ragged_coder_workspace_bytes(self._h)), 256), dtype=torch.uint8, device=self.device)
+        self.ws = torch.empty(max(int(getattr(L, self._workspace_bytes)(self._h)), 256), dtype=torch.uint8, device=self.device)
         self.enc_status = torch.zeros((n, 2), dtype=torch.int32, device=self.device)   # sicn_codec_status {error, bytes}
         self.dec_status = torch.zeros((n, 2), dtype=torch.int32, device=self.device)
 
     @classmethod
     def for_containers(cls, containers, device=None):
-        """A coder for rANS-W containers that came from somewhere else (a list of `bytes`): shapes, image sizes and stream lengths
-        are READ from the 48-byte headers, the containers are copied into the coder's slots and their lengths into its encoder
-        status, so that `decode(out)` reads exactly them."""
+        """A coder for containers of this coder's mode that came from somewhere else (a list of `bytes`): shapes, image sizes and
+        stream lengths are READ from the 48-byte headers, the containers are copied into the coder's slots and their lengths into
+        its encoder status, so that `decode` reads exactly them."""
         import torch
         infos = [parse_header(bytes(c[:48])) for c in containers]
         if not infos:
             raise ValueError("no containers")
-        if any(int(i.mode) != RANSW for i in infos) or len({int(i.lat_c) for i in infos}) != 1:
-            raise ValueError("containers must all be rANS-W and of one channel count")
+        if any(int(i.mode) != cls._mode for i in infos) or len({int(i.lat_c) for i in infos}) != 1:
+            raise ValueError(f"containers must all be {cls._name} and of one channel count")
         coder = cls([(int(i.lat_h), int(i.lat_w)) for i in infos], int(infos[0].lat_c),
                     [(int(i.image_width), int(i.image_height)) for i in infos], [int(i.stream_symbols) for i in infos], device=device)
         host = torch.zeros(coder.slot_bytes, dtype=torch.uint8)
@@ -291,6 +290,87 @@ class RaggedLatentCoder(_lib.Handle):
         if not (t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and tuple(t.shape) == (nbytes,)):
             raise TypeError(f"{what} must be a contiguous CUDA uint8 tensor of {nbytes} bytes")
 
+    def _error(self, code, what, status):
+        """The SicnError of a status column with a set word; with `_error_image`, `.image` is the first image that failed."""
+        err = _lib.SicnError(code, f"{self._name} {what} status {status}")
+        if self._error_image:
+            err.image = next(i for i, v in enumerate(status) if v)
+        return err
+
+    sizes = LatentCoder.sizes
+
+    def containers(self):
+        """The containers of the last encode as `bytes`, one per image (synchronises; raises if the encode reported an error)."""
+        import torch
+        torch.cuda.synchronize(self.device)
+        status = self.enc_status.cpu().tolist()
+        if any(e for e, _ in status):
+            raise self._error(-22, "encode", [e for e, _ in status])
+        host = self.slot_buffer.cpu().numpy()
+        return [host[int(im.slot_offset):int(im.slot_offset) + size].tobytes() for im, (_, size) in zip(self.images, status)]
+
+
+class _RaggedWindow(_lib.Handle):
+    """What the two window decoders share: the checks of `rows`, the arrays, layout and library object, `status` and `check`.  A
+    subclass names its entry points (`_layout`, `_create`, `_free`) and the struct of its layout (`_image_type`); `selected_streams`,
+    `views` and `decode` are its own, because the band layouts differ."""
+    _layout = _create = ""
+    _image_type = None
+
+    def __init__(self, coder, rows):
+        import torch
+        L = _lib.lib()
+        self.coder = coder              # keeps the coder (and its device tables) alive
+        n = len(coder.shapes)
+        self.rows = [(int(r0), int(rh)) for r0, rh in rows]
+        if len(self.rows) != n:
+            raise ValueError("rows: one (r0, rh) per image of the coder")
+        if any(r0 < 0 or rh < 1 or r0 + rh > h for (r0, rh), (h, _) in zip(self.rows, coder.shapes)):
+            raise ValueError("a window of latent rows must be non-empty and lie inside its latent")
+        u32 = ctypes.c_uint32 * max(n, 1)
+        self._r0, self._rh = u32(*[r for r, _ in self.rows]), u32(*[h for _, h in self.rows])
+        self.images = (self._image_type * max(n, 1))()
+        totals = (ctypes.c_uint64 * 2)()
+        _lib.check(getattr(L, self._layout)(coder._lat_w, coder._lat_h, coder.lat_c, coder._wss, self._r0, self._rh, n, self.images, totals),
+                   self._layout)
+        self.band_bytes = int(totals[0])
+        self._h = ctypes.c_void_p()
+        with torch.cuda.device(coder.device):
+            _lib.check(getattr(L, self._create)(coder._h, self._r0, self._rh, ctypes.byref(self._h)), self._create)
+        self.status = torch.zeros((n, 2), dtype=torch.int32, device=coder.device)
+
+    def check(self):
+        """Synchronises and raises if a window reported an error (an rANS-WC window's exception carries `.image`, the first image
+        that failed)."""
+        import torch
+        torch.cuda.synchronize(self.coder.device)
+        d = self.status[:, 0].cpu().tolist()
+        if any(d):
+            raise self.coder._error(-22, "window decode", d)
+
+
+class RaggedLatentCoder(_RaggedCoder):
+    """The ragged rANS-W pair (include/sicn_ragged_codec.h): n latents of n DIFFERENT shapes -> n containers with three launches for
+    the whole batch, and back with two.  `shapes`: [(lat_h, lat_w)] per image, `lat_c` channels in all of them; `image_sizes`:
+    [(width, height)], header fields only.  Latents travel as a ragged tensor — a flat CUDA uint8 tensor, the images' [h][w][c]
+    arrays back to back (api.RaggedNet's boundary 3) — containers in one flat slot buffer, image i's slot at `images[i].slot_offset`.
+    stream_symbols: None or "auto" = `auto_stream_symbols` of EACH image's own latent, one value for all, or one per image.
+    Container i is byte-identical to `LatentCoder(1, h_i, w_i, lat_c, stream_symbols=...)`'s and decodes with `decode_latent`.
+    Same conventions as LatentCoder: enqueue only; verdicts and sizes stay on the device until `check()` / `sizes()` fetch them."""
+    _free, _layout, _create = "sicn_ragged_coder_free", "sicn_ragged_codec_layout", "sicn_ragged_coder_create"
+    _workspace_bytes, _image_type, _mode, _name = "sicn_ragged_coder_workspace_bytes", _lib.RaggedCodecImage, RANSW, "rANS-W"
+
+    def _stream_symbols(self, stream_symbols):
+        n = len(self.shapes)
+        if stream_symbols in (None, "auto"):
+            return [auto_stream_symbols(h * w * self.lat_c) for h, w in self.shapes]
+        if isinstance(stream_symbols, int):
+            return [stream_symbols] * n
+        v = [int(x) for x in stream_symbols]
+        if len(v) != n:
+            raise ValueError("stream_symbols: one value, or one per shape")
+        return v
+
     def encode(self, latents, stream=None):
         """latents: ragged CUDA uint8 tensor -> self.slot_buffer (containers), self.enc_status.  Enqueue only."""
         self._flat(latents, self.latent_bytes, "latents")
@@ -307,62 +387,31 @@ class RaggedLatentCoder(_lib.Handle):
         slots = self.slot_buffer if slots is None else slots
         self._flat(out_latents, self.latent_bytes, "out_latents")
         self._flat(slots, self.slot_bytes, "slots")
-        own = slots is self.slot_buffer
-        vptr = None if (valid is False or (valid is None and not own)) else ctypes.c_void_p((self.enc_status if valid is None else valid).data_ptr())
         _lib.check(_lib.lib().sicn_ragged_coder_decode_async(
-            self._h, ctypes.c_void_p(slots.data_ptr()), vptr, ctypes.c_void_p(out_latents.data_ptr()),
-            ctypes.c_void_p(self.dec_status.data_ptr()), ctypes.c_void_p(self.ws.data_ptr()), self.ws.numel(), _stream_ptr(stream)),
-            "sicn_ragged_coder_decode_async")
+            self._h, ctypes.c_void_p(slots.data_ptr()), _valid_ptr(self.enc_status, slots is self.slot_buffer, valid),
+            ctypes.c_void_p(out_latents.data_ptr()), ctypes.c_void_p(self.dec_status.data_ptr()), ctypes.c_void_p(self.ws.data_ptr()),
+            self.ws.numel(), _stream_ptr(stream)), "sicn_ragged_coder_decode_async")
         return out_latents
 
-    sizes = LatentCoder.sizes
     check = LatentCoder.check
 
     def window(self, rows):
         """A RaggedWindowDecoder over this coder's slots: `rows` = [(r0, rh)] per image, the latent rows [r0, r0 + rh) to decode."""
         return RaggedWindowDecoder(self, rows)
 
-    def containers(self):
-        """The containers of the last encode as `bytes`, one per image (synchronises; raises if the encode reported an error)."""
-        import torch
-        torch.cuda.synchronize(self.device)
-        status = self.enc_status.cpu().tolist()
-        if any(e for e, _ in status):
-            raise _lib.SicnError(-22, f"rANS-W encode status {[e for e, _ in status]}")
-        host = self.slot_buffer.cpu().numpy()
-        return [host[int(im.slot_offset):int(im.slot_offset) + size].tobytes() for im, (_, size) in zip(self.images, status)]
 
-
-class RaggedWindowDecoder(_lib.Handle):
+class RaggedWindowDecoder(_RaggedWindow):
     """A window of latent ROWS of every image decoded from its streams alone (include/sicn_ragged_window.h): two launches for the
     batch.  Made by `RaggedLatentCoder.window(rows)`; shapes, stream lengths, slot buffer and workspace are the coder's, so whatever
     fills the coder's slots (`encode`, `RaggedArchive.unpack`) feeds this decoder.  The result is the BAND tensor: per image the
     symbols of the streams that hold the rows, image i at `images[i].band_offset`, row r0 `images[i].lead` bytes further.
     `.status`: device int32 [n][2], the window decoder's verdicts (bit 7, the checksum of the whole latent, is never set)."""
-    _free = "sicn_ragged_window_free"
+    _free, _layout, _create = "sicn_ragged_window_free", "sicn_ragged_window_layout", "sicn_ragged_window_create"
+    _image_type = _lib.RaggedWindowImage
 
     def __init__(self, coder, rows):
-        import torch
-        L = _lib.lib()
-        self.coder = coder              # keeps the coder (and its device tables) alive
-        n = len(coder.shapes)
-        self.rows = [(int(r0), int(rh)) for r0, rh in rows]
-        if len(self.rows) != n:
-            raise ValueError("rows: one (r0, rh) per image of the coder")
-        if any(r0 < 0 or rh < 1 or r0 + rh > h for (r0, rh), (h, _) in zip(self.rows, coder.shapes)):
-            raise ValueError("a window of latent rows must be non-empty and lie inside its latent")
-        u32 = ctypes.c_uint32 * max(n, 1)
-        self._r0, self._rh = u32(*[r for r, _ in self.rows]), u32(*[h for _, h in self.rows])
-        self.images = (_lib.RaggedWindowImage * max(n, 1))()
-        totals = (ctypes.c_uint64 * 2)()
-        _lib.check(L.sicn_ragged_window_layout(coder._lat_w, coder._lat_h, coder.lat_c, coder._wss, self._r0, self._rh, n, self.images,
-                                               totals), "sicn_ragged_window_layout")
-        self.band_bytes = int(totals[0])
-        self.selected_streams = sum(int(im.end_stream) - int(im.first_stream) for im in self.images[:n])
-        self._h = ctypes.c_void_p()
-        with torch.cuda.device(coder.device):
-            _lib.check(L.sicn_ragged_window_create(coder._h, self._r0, self._rh, ctypes.byref(self._h)), "sicn_ragged_window_create")
-        self.status = torch.zeros((n, 2), dtype=torch.int32, device=coder.device)
+        super().__init__(coder, rows)
+        self.selected_streams = sum(int(im.end_stream) - int(im.first_stream) for im in self.images[:len(self.rows)])
 
     def views(self, band):
         """Per-image [rh][lat_w][lat_c] views of the rows asked for, inside a band tensor (no copy)."""
@@ -378,20 +427,11 @@ class RaggedWindowDecoder(_lib.Handle):
         slots = c.slot_buffer if slots is None else slots
         c._flat(band, self.band_bytes, "band")
         c._flat(slots, c.slot_bytes, "slots")
-        own = slots is c.slot_buffer
-        vptr = None if (valid is False or (valid is None and not own)) else ctypes.c_void_p((c.enc_status if valid is None else valid).data_ptr())
         _lib.check(_lib.lib().sicn_ragged_window_decode_async(
-            self._h, ctypes.c_void_p(slots.data_ptr()), vptr, ctypes.c_void_p(band.data_ptr()), ctypes.c_void_p(self.status.data_ptr()),
-            ctypes.c_void_p(c.ws.data_ptr()), c.ws.numel(), _stream_ptr(stream)), "sicn_ragged_window_decode_async")
+            self._h, ctypes.c_void_p(slots.data_ptr()), _valid_ptr(c.enc_status, slots is c.slot_buffer, valid),
+            ctypes.c_void_p(band.data_ptr()), ctypes.c_void_p(self.status.data_ptr()), ctypes.c_void_p(c.ws.data_ptr()), c.ws.numel(),
+            _stream_ptr(stream)), "sicn_ragged_window_decode_async")
         return band
-
-    def check(self):
-        """Synchronises and raises if a window reported an error."""
-        import torch
-        torch.cuda.synchronize(self.coder.device)
-        d = self.status[:, 0].cpu().tolist()
-        if any(d):
-            raise _lib.SicnError(-22, f"rANS-W window decode status {d}")
 
 
 def _ctx_stream_symbols(stream_symbols, n):
@@ -453,8 +493,7 @@ class ContextCoder:
         self._check(scales, "scales")
         n, h, w, c = self.shape
         slots = self.slots if slots is None else slots
-        own = slots is self.slots     # external containers: trust the slot unless their status array came along (see LatentCoder.decode)
-        vptr = None if (valid is False or (valid is None and not own)) else ctypes.c_void_p((self.enc_status if valid is None else valid).data_ptr())
+        vptr = _valid_ptr(self.enc_status, slots is self.slots, valid)   # external containers: see LatentCoder.decode
         _lib.check(_lib.lib().sicn_codec_ctx_decode_batch_async_sl(
             ctypes.c_void_p(slots.data_ptr()), self.slot, vptr, ctypes.c_void_p(scales.data_ptr()), n, w, h, c,
             ctypes.c_void_p(out_latents.data_ptr()), ctypes.c_void_p(self.dec_status.data_ptr()),
@@ -466,7 +505,7 @@ class ContextCoder:
     check = LatentCoder.check
 
 
-class RaggedContextCoder(_lib.Handle):
+class RaggedContextCoder(_RaggedCoder):
     """The ragged rANS-WC pair (include/sicn_ragged_ctx.h): n latents of n DIFFERENT shapes, each with its scale map -> n mode-4
     containers with six launches for the whole batch, and back with eight.  `shapes`: [(lat_h, lat_w)] per image, `lat_c` channels
     (a multiple of 4) in all of them; `image_sizes`: [(width, height)], header fields only.  Latents and scales travel as two ragged
@@ -475,62 +514,12 @@ class RaggedContextCoder(_lib.Handle):
     with it.  Same conventions as RaggedLatentCoder: enqueue only; verdicts and sizes stay on the device until `check()` / `sizes()`.
     stream_symbols: None (16384), one length for all images, or one per image — `ContextCoder`'s parameter; the lengths live in the
     coder, so `decode` and `window` expect them."""
-    _free = "sicn_ragged_ctx_coder_free"
+    _free, _layout, _create = "sicn_ragged_ctx_coder_free", "sicn_ragged_ctx_layout_sl", "sicn_ragged_ctx_coder_create_sl"
+    _workspace_bytes, _image_type, _mode, _name = "sicn_ragged_ctx_coder_workspace_bytes", _lib.RaggedCtxImage, RANSWC, "rANS-WC"
+    _error_image = True
 
-    def __init__(self, shapes, lat_c: int, image_sizes=None, stream_symbols=None, device=None):
-        import torch
-        L = _lib.lib()
-        self.shapes = [(int(h), int(w)) for h, w in shapes]
-        self.lat_c = int(lat_c)
-        n = len(self.shapes)
-        self.image_sizes = [(int(w), int(h)) for w, h in image_sizes] if image_sizes is not None else [(0, 0)] * n
-        if len(self.image_sizes) != n:
-            raise ValueError("image_sizes: one (width, height) per shape")
-        self.stream_symbols = _ctx_stream_symbols(stream_symbols, n)
-        u32 = ctypes.c_uint32 * max(n, 1)
-        self._lat_w, self._lat_h = u32(*[w for _, w in self.shapes]), u32(*[h for h, _ in self.shapes])
-        self._img_w, self._img_h = u32(*[w for w, _ in self.image_sizes]), u32(*[h for _, h in self.image_sizes])
-        self._wss = u32(*self.stream_symbols)
-        self.images = (_lib.RaggedCtxImage * max(n, 1))()            # where image i lies: offsets, slot capacity, streams of the two sets
-        totals = (ctypes.c_uint64 * 3)()
-        _lib.check(L.sicn_ragged_ctx_layout_sl(self._lat_w, self._lat_h, self.lat_c, self._wss, n, self.images, totals),
-                   "sicn_ragged_ctx_layout_sl")
-        self.latent_bytes, self.slot_bytes = int(totals[0]), int(totals[1])
-        self.device = torch.device(device if device is not None else "cuda")
-        self._h = ctypes.c_void_p()
-        with torch.cuda.device(self.device):
-            _lib.check(L.sicn_ragged_ctx_coder_create_sl(self._lat_w, self._lat_h, self.lat_c, self._wss, self._img_w, self._img_h, n,
-                                                         ctypes.byref(self._h)), "sicn_ragged_ctx_coder_create_sl")
-        self.slot_buffer = torch.empty(self.slot_bytes, dtype=torch.uint8, device=self.device)
-        self.ws = torch.empty(max(int(L.sicn_ragged_ctx_coder_workspace_bytes(self._h)), 256), dtype=torch.uint8, device=self.device)
-        self.enc_status = torch.zeros((n, 2), dtype=torch.int32, device=self.device)   # sicn_codec_status {error, bytes}
-        self.dec_status = torch.zeros((n, 2), dtype=torch.int32, device=self.device)
-
-    @classmethod
-    def for_containers(cls, containers, device=None):
-        """A coder for rANS-WC containers that came from somewhere else (a list of `bytes`): shapes, image sizes and stream lengths
-        are READ from the 48-byte headers, the containers are copied into the coder's slots and their lengths into its encoder status, so that
-        `decode(out, scales)` reads exactly them."""
-        import torch
-        infos = [parse_header(bytes(c[:48])) for c in containers]
-        if not infos:
-            raise ValueError("no containers")
-        if any(int(i.mode) != RANSWC for i in infos) or len({int(i.lat_c) for i in infos}) != 1:
-            raise ValueError("containers must all be rANS-WC and of one channel count")
-        coder = cls([(int(i.lat_h), int(i.lat_w)) for i in infos], int(infos[0].lat_c),
-                    [(int(i.image_width), int(i.image_height)) for i in infos], [int(i.stream_symbols) for i in infos], device=device)
-        host = torch.zeros(coder.slot_bytes, dtype=torch.uint8)
-        for c, im in zip(containers, coder.images):
-            if len(c) > int(im.slot_bytes):
-                raise ValueError(f"a container of {len(c)} bytes is longer than the {int(im.slot_bytes)} its shape may take")
-            host[int(im.slot_offset):int(im.slot_offset) + len(c)] = torch.frombuffer(bytearray(c), dtype=torch.uint8)
-        coder.slot_buffer.copy_(host)
-        coder.enc_status.copy_(torch.tensor([[0, len(c)] for c in containers], dtype=torch.int32))
-        return coder
-
-    slots = RaggedLatentCoder.slots
-    views = RaggedLatentCoder.views
-    _flat = RaggedLatentCoder._flat
+    def _stream_symbols(self, stream_symbols):
+        return _ctx_stream_symbols(stream_symbols, len(self.shapes))
 
     def encode(self, latents, scales, stream=None):
         """latents, scales: ragged CUDA uint8 tensors -> self.slot_buffer (containers), self.enc_status.  Enqueue only."""
@@ -549,15 +538,11 @@ class RaggedContextCoder(_lib.Handle):
         self._flat(out_latents, self.latent_bytes, "out_latents")
         self._flat(scales, self.latent_bytes, "scales")
         self._flat(slots, self.slot_bytes, "slots")
-        own = slots is self.slot_buffer
-        vptr = None if (valid is False or (valid is None and not own)) else ctypes.c_void_p((self.enc_status if valid is None else valid).data_ptr())
         _lib.check(_lib.lib().sicn_ragged_ctx_decode_async(
-            self._h, ctypes.c_void_p(slots.data_ptr()), vptr, ctypes.c_void_p(scales.data_ptr()), ctypes.c_void_p(out_latents.data_ptr()),
-            ctypes.c_void_p(self.dec_status.data_ptr()), ctypes.c_void_p(self.ws.data_ptr()), self.ws.numel(), _stream_ptr(stream)),
-            "sicn_ragged_ctx_decode_async")
+            self._h, ctypes.c_void_p(slots.data_ptr()), _valid_ptr(self.enc_status, slots is self.slot_buffer, valid),
+            ctypes.c_void_p(scales.data_ptr()), ctypes.c_void_p(out_latents.data_ptr()), ctypes.c_void_p(self.dec_status.data_ptr()),
+            ctypes.c_void_p(self.ws.data_ptr()), self.ws.numel(), _stream_ptr(stream)), "sicn_ragged_ctx_decode_async")
         return out_latents
-
-    sizes = LatentCoder.sizes
 
     def window(self, rows):
         """A RaggedContextWindowDecoder over this coder's slots: `rows` = [(r0, rh)] per image, the latent rows [r0, r0 + rh) to decode."""
@@ -570,55 +555,22 @@ class RaggedContextCoder(_lib.Handle):
         d = self.dec_status[:, 0].cpu().tolist()
         for what, st in (("encode", e), ("decode", d)):
             if any(st):
-                code = -74 if what == "decode" and not any(v & ~128 for v in st) else -22
-                err = _lib.SicnError(code, f"rANS-WC {what} status {st}")
-                err.image = next(i for i, v in enumerate(st) if v)
-                raise err
-
-    def containers(self):
-        """The containers of the last encode as `bytes`, one per image (synchronises; raises if the encode reported an error)."""
-        import torch
-        torch.cuda.synchronize(self.device)
-        status = self.enc_status.cpu().tolist()
-        if any(e for e, _ in status):
-            err = _lib.SicnError(-22, f"rANS-WC encode status {[e for e, _ in status]}")
-            err.image = next(i for i, (e, _) in enumerate(status) if e)
-            raise err
-        host = self.slot_buffer.cpu().numpy()
-        return [host[int(im.slot_offset):int(im.slot_offset) + size].tobytes() for im, (_, size) in zip(self.images, status)]
+                raise self._error(-74 if what == "decode" and not any(v & ~128 for v in st) else -22, what, st)
 
 
-class RaggedContextWindowDecoder(_lib.Handle):
+class RaggedContextWindowDecoder(_RaggedWindow):
     """A window of latent ROWS of every image decoded from its rANS-WC streams alone (include/sicn_ragged_ctx_window.h): seven
     enqueued operations for the batch.  Made by `RaggedContextCoder.window(rows)`; shapes, slot buffer and workspace are the coder's,
     so whatever fills the coder's slots (`encode`, `RaggedArchive.unpack`) feeds this decoder.  The result is the BAND tensor: per
     image the whole latent rows [band_row0, band_row0 + band_rows) at `images[i].band_offset` — the symbols of the selected streams,
     zero where a position belongs to a stream outside the selection; the rows asked for are complete.
     `.status`: device int32 [n][2], the window decoder's verdicts (bit 7, the checksum of the whole latent, is never set)."""
-    _free = "sicn_ragged_ctx_window_free"
+    _free, _layout, _create = "sicn_ragged_ctx_window_free", "sicn_ragged_ctx_window_layout_sl", "sicn_ragged_ctx_window_create"
+    _image_type = _lib.RaggedCtxWindowImage
 
     def __init__(self, coder, rows):
-        import torch
-        L = _lib.lib()
-        self.coder = coder              # keeps the coder (and its device tables) alive
-        n = len(coder.shapes)
-        self.rows = [(int(r0), int(rh)) for r0, rh in rows]
-        if len(self.rows) != n:
-            raise ValueError("rows: one (r0, rh) per image of the coder")
-        if any(r0 < 0 or rh < 1 or r0 + rh > h for (r0, rh), (h, _) in zip(self.rows, coder.shapes)):
-            raise ValueError("a window of latent rows must be non-empty and lie inside its latent")
-        u32 = ctypes.c_uint32 * max(n, 1)
-        self._r0, self._rh = u32(*[r for r, _ in self.rows]), u32(*[h for _, h in self.rows])
-        self.images = (_lib.RaggedCtxWindowImage * max(n, 1))()
-        totals = (ctypes.c_uint64 * 2)()
-        _lib.check(L.sicn_ragged_ctx_window_layout_sl(coder._lat_w, coder._lat_h, coder.lat_c, coder._wss, self._r0, self._rh, n, self.images,
-                                                      totals), "sicn_ragged_ctx_window_layout_sl")
-        self.band_bytes = int(totals[0])
-        self.selected_streams = sum(int(im.end_stream[s]) - int(im.first_stream[s]) for im in self.images[:n] for s in (0, 1))
-        self._h = ctypes.c_void_p()
-        with torch.cuda.device(coder.device):
-            _lib.check(L.sicn_ragged_ctx_window_create(coder._h, self._r0, self._rh, ctypes.byref(self._h)), "sicn_ragged_ctx_window_create")
-        self.status = torch.zeros((n, 2), dtype=torch.int32, device=coder.device)
+        super().__init__(coder, rows)
+        self.selected_streams = sum(int(im.end_stream[s]) - int(im.first_stream[s]) for im in self.images[:len(self.rows)] for s in (0, 1))
 
     def views(self, band):
         """Per-image [rh][lat_w][lat_c] views of the rows asked for, inside a band tensor (no copy)."""
@@ -637,23 +589,11 @@ class RaggedContextWindowDecoder(_lib.Handle):
         c._flat(band, self.band_bytes, "band")
         c._flat(scales, c.latent_bytes, "scales")
         c._flat(slots, c.slot_bytes, "slots")
-        own = slots is c.slot_buffer
-        vptr = None if (valid is False or (valid is None and not own)) else ctypes.c_void_p((c.enc_status if valid is None else valid).data_ptr())
         _lib.check(_lib.lib().sicn_ragged_ctx_window_decode_async(
-            self._h, ctypes.c_void_p(slots.data_ptr()), vptr, ctypes.c_void_p(scales.data_ptr()), ctypes.c_void_p(band.data_ptr()),
-            ctypes.c_void_p(self.status.data_ptr()), ctypes.c_void_p(c.ws.data_ptr()), c.ws.numel(), _stream_ptr(stream)),
-            "sicn_ragged_ctx_window_decode_async")
+            self._h, ctypes.c_void_p(slots.data_ptr()), _valid_ptr(c.enc_status, slots is c.slot_buffer, valid),
+            ctypes.c_void_p(scales.data_ptr()), ctypes.c_void_p(band.data_ptr()), ctypes.c_void_p(self.status.data_ptr()),
+            ctypes.c_void_p(c.ws.data_ptr()), c.ws.numel(), _stream_ptr(stream)), "sicn_ragged_ctx_window_decode_async")
         return band
-
-    def check(self):
-        """Synchronises and raises if a window reported an error; the exception's `.image` is the first image that failed."""
-        import torch
-        torch.cuda.synchronize(self.coder.device)
-        d = self.status[:, 0].cpu().tolist()
-        if any(d):
-            err = _lib.SicnError(-22, f"rANS-WC window decode status {d}")
-            err.image = next(i for i, v in enumerate(d) if v)
-            raise err
 
 
 def _parse_archive(b):

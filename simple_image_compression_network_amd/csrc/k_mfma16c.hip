@@ -71,8 +71,10 @@ size_t any_bytes(int cin, int cout)
     return (size_t)((cout + 63) / 64) * 25 * ((cin + 63) / 64) * any_tiles_per_block(cout) * 1024;
 }
 
-// w_okc [cout][25 * cin] -> [block][tap ky * 5 + kx][chunk][tile][row 16][64 B], zero for channels past either count
-void pack_any(const int8_t *w_okc, int cin, int cout, int8_t *dst)
+// w_okc [cout][25 * cin] -> [block][tap ky * 5 + kx][chunk][tile][row 16][64 B], zero for channels past either count.
+// Placed on a 256-byte boundary: the time of these loops on the host was seen to move by a third with the address the linker gave the
+// function (profiles/ragged_owned_tables.txt, section 6), and a ragged net made per call runs them once per layer.
+__attribute__((aligned(256))) void pack_any(const int8_t *w_okc, int cin, int cout, int8_t *dst)
 {
     const int nblk = (cout + 63) / 64, nchunk = (cin + 63) / 64, nt = any_tiles_per_block(cout), kk = 25 * cin;
     for (int J = 0; J < nblk; J++)

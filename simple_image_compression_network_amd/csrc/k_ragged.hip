@@ -21,11 +21,11 @@
 #include "../../include/sicn_ragged_hyper.h"
 #include "../../include/sicn_ragged_rgb.h"
 #include "../../include/sicn_ragged_window.h"
+#include "device_table.hpp"
 #include "k_any_body.hpp"
 #include "k_ragged_common.hpp"
 #include "ragged_rgb_host.hpp"
 #include "sicn_gdn_internal.h"
-#include "sicn_weights_io.h"
 
 namespace sicn {
 
@@ -155,10 +155,10 @@ struct sicn_ragged_net {
     std::vector<const sicn_weights *> weights;
     std::vector<const sicn_gdn *> gdn;      // per layer: the activation in place of the ReLU, or nullptr
     std::vector<const int8_t *> wimg;       // per layer: the weights' own pack_any image, or one of `owned`
-    std::vector<int8_t *> owned;            // images packed here: for weights whose family is another one (the reference's widths), and
+    std::vector<DeviceTable<int8_t>> owned; // images packed here: for weights whose family is another one (the reference's widths), and
                                             // the packed-K images of the RGB ends (ragged_rgb_host.hpp)
-    RaggedRow *d_rows = nullptr;            // [n_layers][n_images]
-    uint32_t *d_tile_image = nullptr;       // the layers' tile -> image maps back to back
+    DeviceTable<RaggedRow> d_rows;          // [n_layers][n_images]
+    DeviceTable<uint32_t> d_tile_image;     // the layers' tile -> image maps back to back
     std::vector<size_t> map_at;             // per layer: its first entry in d_tile_image
     size_t slot = 0;                        // bytes of one ping-pong buffer
 };
@@ -186,14 +186,7 @@ extern "C" int sicn_ragged_layout(const sicn_layer_desc *descs, int n_layers, co
     return SICN_OK;
 }
 
-extern "C" void sicn_ragged_net_free(sicn_ragged_net *net)
-{
-    if (!net) return;
-    for (int8_t *p : net->owned) (void)hipFree(p);
-    if (net->d_rows) (void)hipFree(net->d_rows);
-    if (net->d_tile_image) (void)hipFree(net->d_tile_image);
-    delete net;
-}
+extern "C" void sicn_ragged_net_free(sicn_ragged_net *net) { delete net; }
 
 extern "C" int sicn_ragged_net_create(const sicn_layer_desc *descs, sicn_weights *const *weights, int n_layers, const int32_t *widths,
                                       const int32_t *heights, int n_images, sicn_ragged_net **out)
@@ -235,76 +228,63 @@ extern "C" int sicn_ragged_net_create_rgb(const sicn_layer_desc *descs, sicn_wei
     if (!out) return SICN_EINVAL;
     *out = nullptr;
     if (!weights) return SICN_EINVAL;
-    sicn_ragged_net *net = new (std::nothrow) sicn_ragged_net();
-    if (!net) return SICN_ENOMEM;
-    int rc = ragged_plan(descs, n_layers, widths, heights, n_images, rgb_ends, &net->plan);
-    for (int l = 0; !rc && l < n_layers; l++) {
-        const sicn_weights *w = weights[l];
-        if (!w || w->cin != descs[l].IFM_CH || w->cout != descs[l].OFM_CH || w->transposed != descs[l].transposed) rc = SICN_EINVAL;
-        if (gdn && gdn[l] && gdn[l]->channels != descs[l].OFM_CH) rc = SICN_EINVAL;
-    }
-    if (!rc) rc = chip_geom(nullptr);       // no device, or not a gfx950 one
-    if (!rc) try {
-        net->n_layers = n_layers;
-        net->n_images = n_images;
-        net->descs.assign(descs, descs + n_layers);
-        net->weights.assign(weights, weights + n_layers);
-        net->gdn.assign((size_t)n_layers, nullptr);
-        if (gdn) net->gdn.assign(gdn, gdn + n_layers);
+    return make_object(out, [&](sicn_ragged_net &net) {
+        if (int rc = ragged_plan(descs, n_layers, widths, heights, n_images, rgb_ends, &net.plan)) return rc;
+        for (int l = 0; l < n_layers; l++) {
+            const sicn_weights *w = weights[l];
+            if (!w || w->cin != descs[l].IFM_CH || w->cout != descs[l].OFM_CH || w->transposed != descs[l].transposed) return SICN_EINVAL;
+            if (gdn && gdn[l] && gdn[l]->channels != descs[l].OFM_CH) return SICN_EINVAL;
+        }
+        if (int rc = chip_geom(nullptr)) return rc;       // no device, or not a gfx950 one
+        net.n_layers = n_layers;
+        net.n_images = n_images;
+        net.descs.assign(descs, descs + n_layers);
+        net.weights.assign(weights, weights + n_layers);
+        net.gdn.assign((size_t)n_layers, nullptr);
+        if (gdn) net.gdn.assign(gdn, gdn + n_layers);
         // the tables: one row per (layer, image), one tile -> image entry per tile
         std::vector<RaggedRow> rows((size_t)n_layers * n_images);
-        std::vector<uint32_t> map;
+        ItemMap map;
         size_t mx = 0;
         for (int l = 0; l < n_layers; l++) {
-            const RaggedBoundary &bi = net->plan.bounds[(size_t)l], &bo = net->plan.bounds[(size_t)l + 1];
-            const RaggedLayerPlan &lp = net->plan.layers[(size_t)l];
+            const RaggedBoundary &bi = net.plan.bounds[(size_t)l], &bo = net.plan.bounds[(size_t)l + 1];
+            const RaggedLayerPlan &lp = net.plan.layers[(size_t)l];
             const int per_tile = lp.per_tile;
-            net->map_at.push_back(map.size());
+            net.map_at.push_back(map.size());
             for (int i = 0; i < n_images; i++) {
                 rows[(size_t)l * n_images + i] = RaggedRow{bi.W[(size_t)i], bi.H[(size_t)i], bo.W[(size_t)i], bo.H[(size_t)i], lp.tiles_x[(size_t)i],
                                                            (int32_t)lp.first_item[(size_t)i], bi.off[(size_t)i], bo.off[(size_t)i]};
-                map.insert(map.end(), (size_t)((lp.first_item[(size_t)i + 1] - lp.first_item[(size_t)i]) / per_tile), (uint32_t)i);
+                map.add((size_t)((lp.first_item[(size_t)i + 1] - lp.first_item[(size_t)i]) / per_tile), (uint32_t)i);
             }
             if (l + 1 < n_layers && (size_t)bo.off[(size_t)n_images] > mx) mx = (size_t)bo.off[(size_t)n_images];
         }
-        net->slot = (mx + 255) / 256 * 256;
-        if (!upload(rows.data(), rows.size() * sizeof(RaggedRow), &net->d_rows) ||
-            !upload(map.data(), map.size() * sizeof(uint32_t), &net->d_tile_image))
-            rc = SICN_ENOMEM;
+        net.slot = (mx + 255) / 256 * 256;
+        if (!net.d_rows.upload(rows) || !map.upload(net.d_tile_image)) return SICN_ENOMEM;
         // the weight image: weights of a width the specialised families serve were uploaded without one (sicn_weights_from_finn_tiles
         // packs the images of the family the shape runs on); pack it here from the plain [cout][25 cin] copy every handle has
-        for (int l = 0; !rc && l < n_layers; l++) {
+        for (int l = 0; l < n_layers; l++) {
             const sicn_weights *w = weights[l];
-            const bool packed = net->plan.layers[(size_t)l].packed;
+            const bool packed = net.plan.layers[(size_t)l].packed;
             if (!packed && w->d_w_any) {
-                net->wimg.push_back(w->d_w_any);
+                net.wimg.push_back(w->d_w_any);
                 continue;
             }
             const size_t img_bytes = !packed ? any_bytes(w->cin, w->cout) : w->transposed ? rgb_deconv_bytes(w->cin) : rgb_conv_bytes(w->cout);
             std::vector<int8_t> okc((size_t)w->cout * 25 * w->cin), img(img_bytes);
-            if (hipMemcpy(okc.data(), w->d_w_okc, okc.size(), hipMemcpyDeviceToHost) != hipSuccess) {
-                rc = SICN_ENODEV;
-                break;
-            }
+            if (hipMemcpy(okc.data(), w->d_w_okc, okc.size(), hipMemcpyDeviceToHost) != hipSuccess) return SICN_ENODEV;
             if (!packed)
                 pack_any(okc.data(), w->cin, w->cout, img.data());
             else if (w->transposed)
                 pack_rgb_deconv(okc.data(), w->cin, img.data());
             else
                 pack_rgb_conv(okc.data(), w->cout, img.data());
-            int8_t *dev = nullptr;
-            const bool ok = upload(img.data(), img.size(), &dev);
-            if (dev) net->owned.push_back(dev);
-            if (!ok) rc = SICN_ENOMEM;
-            net->wimg.push_back(dev);
+            DeviceTable<int8_t> dev;
+            if (!dev.upload(img)) return SICN_ENOMEM;
+            net.wimg.push_back(dev.get());
+            net.owned.push_back(std::move(dev));
         }
-    } catch (const std::bad_alloc &) { rc = SICN_ENOMEM; }
-    if (rc) {
-        sicn_ragged_net_free(net);
-        return rc;
-    }
-    *out = net;
-    return SICN_OK;
+        return SICN_OK;
+    });
 }
 
 extern "C" size_t sicn_ragged_net_workspace_bytes(const sicn_ragged_net *net) { return net ? 2 * net->slot : 0; }
@@ -325,8 +305,8 @@ extern "C" int sicn_ragged_net_forward(const sicn_ragged_net *net, int first, in
         uint8_t *dst = (l == last) ? out : (l == tap_layer ? tap_out : pp[(l - first) & 1]);
         const sicn_layer_desc &d = net->descs[(size_t)l];
         const sicn_weights *w = net->weights[(size_t)l];
-        const RaggedRow *rows = net->d_rows + (size_t)l * net->n_images;
-        const uint32_t *map = net->d_tile_image + net->map_at[(size_t)l];
+        const RaggedRow *rows = net->d_rows.get() + (size_t)l * net->n_images;
+        const uint32_t *map = net->d_tile_image.get() + net->map_at[(size_t)l];
         const unsigned items = (unsigned)net->plan.layers[(size_t)l].first_item[(size_t)net->n_images];
         const int8_t *wimg = net->wimg[(size_t)l];
         const sicn_gdn *g = net->gdn[(size_t)l];

@@ -16,13 +16,12 @@
 //   and only the container's last partial 16 bytes move bytewise.  Otherwise byte by byte.
 // k_archive_parse_select (include/sicn_ragged_archive_select.h): k_archive_parse for an object made for a SELECTION of the archive's
 //   images; then k_archive_copy<false> as it is, over the object's item grid.  Described at the kernel.
-#include <new>
 #include <vector>
 
 #include "archive_host.hpp"
+#include "device_table.hpp"
 #include "k_ragged_common.hpp"
 #include "sicn_internal.h"
-#include "sicn_weights_io.h"
 
 namespace {
 
@@ -376,8 +375,8 @@ __global__ __launch_bounds__(WG) void k_archive_copy(Ptrs4 slots, uint8_t *__res
 struct sicn_ragged_archive {
     uint32_t n_images = 0, k = 0, entries = 0, items = 0;
     uint64_t max_bytes = 0, ws_bytes = 0;
-    ArchRow *d_rows = nullptr;              // [entries]
-    uint32_t *d_item_entry = nullptr;       // [max(items, 1)]
+    sicn::DeviceTable<ArchRow> d_rows;              // [entries]
+    sicn::DeviceTable<uint32_t> d_item_entry;       // [max(items, 1)]
 };
 
 extern "C" int sicn_ragged_archive_layout(const uint32_t *sizes, uint32_t n_images, uint32_t n_sections, uint64_t *offsets_out_or_null,
@@ -394,13 +393,7 @@ extern "C" int sicn_ragged_archive_parse(const uint8_t *archive, size_t archive_
 
 extern "C" size_t sicn_ragged_archive_chunk_bytes(void) { return CHUNK_BYTES; }
 
-extern "C" void sicn_ragged_archive_free(sicn_ragged_archive *archive)
-{
-    if (!archive) return;
-    if (archive->d_rows) (void)hipFree(archive->d_rows);
-    if (archive->d_item_entry) (void)hipFree(archive->d_item_entry);
-    delete archive;
-}
+extern "C" void sicn_ragged_archive_free(sicn_ragged_archive *archive) { delete archive; }
 
 extern "C" int sicn_ragged_archive_create(int n_images, int n_sections, const uint64_t *const *slot_offset, const uint64_t *const *slot_bytes,
                                           sicn_ragged_archive **out)
@@ -410,45 +403,30 @@ extern "C" int sicn_ragged_archive_create(int n_images, int n_sections, const ui
     if (n_images < 1 || n_sections < 1 || !counts_ok((uint64_t)n_images, (uint64_t)n_sections) || !slot_offset || !slot_bytes) return SICN_EINVAL;
     for (int s = 0; s < n_sections; s++)
         if (!slot_offset[s] || !slot_bytes[s]) return SICN_EINVAL;
-    sicn_ragged_archive *ar = new (std::nothrow) sicn_ragged_archive();
-    if (!ar) return SICN_ENOMEM;
-    int rc = SICN_OK;
-    try {
-        ar->n_images = (uint32_t)n_images;
-        ar->k = (uint32_t)n_sections;
-        ar->entries = ar->n_images * ar->k;
-        std::vector<ArchRow> rows((size_t)ar->entries);
-        uint64_t items = 0, most = payload_offset(ar->entries);
-        for (uint32_t i = 0; i < ar->n_images && !rc; i++)
-            for (uint32_t s = 0; s < ar->k; s++) {
+    return sicn::make_object(out, [&](sicn_ragged_archive &ar) {
+        ar.n_images = (uint32_t)n_images;
+        ar.k = (uint32_t)n_sections;
+        ar.entries = ar.n_images * ar.k;
+        std::vector<ArchRow> rows((size_t)ar.entries);
+        uint64_t items = 0, most = payload_offset(ar.entries);
+        for (uint32_t i = 0; i < ar.n_images; i++)
+            for (uint32_t s = 0; s < ar.k; s++) {
                 const uint64_t off = slot_offset[s][i], cap = slot_bytes[s][i];
-                if ((off & 15) || cap > 0xFFFFFFFFull || off + cap < off) { rc = SICN_EINVAL; break; }
-                rows[(size_t)i * ar->k + s] = ArchRow{off, (uint32_t)cap, (uint32_t)items, s, 0};
+                if ((off & 15) || cap > 0xFFFFFFFFull || off + cap < off) return SICN_EINVAL;
+                rows[(size_t)i * ar.k + s] = ArchRow{off, (uint32_t)cap, (uint32_t)items, s, 0};
                 items += (cap + CHUNK_BYTES - 1) / CHUNK_BYTES;     // <= 2^24 * 2^18
                 most += a16(cap);
-                if (items >= 0x7fffffffull) { rc = SICN_EINVAL; break; }   // grid.x
+                if (items >= 0x7fffffffull) return SICN_EINVAL;    // grid.x
             }
-        if (!rc) rc = sicn::chip_geom(nullptr);       // no device, or not a gfx950 one
-        if (!rc) {
-            ar->items = (uint32_t)items;
-            ar->max_bytes = most;
-            ar->ws_bytes = a16(12ull * ar->entries);
-            std::vector<uint32_t> item_entry;
-            item_entry.reserve((size_t)items + 1);
-            for (uint32_t e = 0; e < ar->entries; e++)
-                item_entry.insert(item_entry.end(), ((size_t)rows[e].slot_bytes + CHUNK_BYTES - 1) / CHUNK_BYTES, e);
-            if (item_entry.empty()) item_entry.push_back(0);
-            if (!sicn::upload(rows.data(), rows.size() * sizeof(ArchRow), &ar->d_rows) ||
-                !sicn::upload(item_entry.data(), item_entry.size() * sizeof(uint32_t), &ar->d_item_entry))
-                rc = SICN_ENOMEM;
-        }
-    } catch (const std::bad_alloc &) { rc = SICN_ENOMEM; }
-    if (rc) {
-        sicn_ragged_archive_free(ar);
-        return rc;
-    }
-    *out = ar;
-    return SICN_OK;
+        if (int rc = sicn::chip_geom(nullptr)) return rc;       // no device, or not a gfx950 one
+        ar.items = (uint32_t)items;
+        ar.max_bytes = most;
+        ar.ws_bytes = a16(12ull * ar.entries);
+        sicn::ItemMap item_entry;
+        for (uint32_t e = 0; e < ar.entries; e++) item_entry.add(((size_t)rows[e].slot_bytes + CHUNK_BYTES - 1) / CHUNK_BYTES, e);
+        if (!item_entry.size()) item_entry.add(1, 0);
+        return ar.d_rows.upload(rows) && item_entry.upload(ar.d_item_entry) ? SICN_OK : SICN_ENOMEM;
+    });
 }
 
 extern "C" size_t sicn_ragged_archive_workspace_bytes(const sicn_ragged_archive *archive) { return archive ? (size_t)archive->ws_bytes : 0; }
@@ -490,10 +468,10 @@ extern "C" int sicn_ragged_archive_pack_async(const sicn_ragged_archive *archive
     hipStream_t stream = (hipStream_t)hip_stream;
     uint64_t *ws_off = (uint64_t *)workspace;
     uint32_t *ws_size = (uint32_t *)(ws_off + archive->entries);
-    hipLaunchKernelGGL(k_archive_index, dim3(1), dim3(WG), 0, stream, st, archive->d_rows, archive->n_images, archive->k, tag, out,
+    hipLaunchKernelGGL(k_archive_index, dim3(1), dim3(WG), 0, stream, st, archive->d_rows.get(), archive->n_images, archive->k, tag, out,
                        (uint64_t)out_capacity, status_dev, ws_off, ws_size);
-    hipLaunchKernelGGL(k_archive_copy<true>, dim3(archive->items ? archive->items : 1u), dim3(WG), 0, stream, slots, out, archive->d_rows,
-                       archive->d_item_entry, archive->items, ws_off, ws_size, status_dev, vecmask);
+    hipLaunchKernelGGL(k_archive_copy<true>, dim3(archive->items ? archive->items : 1u), dim3(WG), 0, stream, slots, out, archive->d_rows.get(),
+                       archive->d_item_entry.get(), archive->items, ws_off, ws_size, status_dev, vecmask);
     return hipGetLastError() == hipSuccess ? SICN_OK : SICN_ENODEV;
 }
 
@@ -509,10 +487,10 @@ extern "C" int sicn_ragged_archive_unpack_async(const sicn_ragged_archive *archi
     hipStream_t stream = (hipStream_t)hip_stream;
     uint64_t *ws_off = (uint64_t *)workspace;
     uint32_t *ws_size = (uint32_t *)(ws_off + archive->entries);
-    hipLaunchKernelGGL(k_archive_parse, dim3(1), dim3(WG), 0, stream, in, (uint64_t)in_bytes, expected_tag, archive->d_rows, archive->n_images,
+    hipLaunchKernelGGL(k_archive_parse, dim3(1), dim3(WG), 0, stream, in, (uint64_t)in_bytes, expected_tag, archive->d_rows.get(), archive->n_images,
                        archive->k, valid, status_dev, ws_off, ws_size);
     hipLaunchKernelGGL(k_archive_copy<false>, dim3(archive->items ? archive->items : 1u), dim3(WG), 0, stream, slots, const_cast<uint8_t *>(in),
-                       archive->d_rows, archive->d_item_entry, archive->items, ws_off, ws_size, status_dev, vecmask);
+                       archive->d_rows.get(), archive->d_item_entry.get(), archive->items, ws_off, ws_size, status_dev, vecmask);
     return hipGetLastError() == hipSuccess ? SICN_OK : SICN_ENODEV;
 }
 
@@ -530,10 +508,10 @@ extern "C" int sicn_ragged_archive_unpack_select_async(const sicn_ragged_archive
     hipStream_t stream = (hipStream_t)hip_stream;
     uint64_t *ws_off = (uint64_t *)workspace;
     uint32_t *ws_size = (uint32_t *)(ws_off + archive->entries);
-    hipLaunchKernelGGL(k_archive_parse_select, dim3(1), dim3(WG), 0, stream, in, (uint64_t)in_bytes, expected_tag, archive->d_rows,
+    hipLaunchKernelGGL(k_archive_parse_select, dim3(1), dim3(WG), 0, stream, in, (uint64_t)in_bytes, expected_tag, archive->d_rows.get(),
                        archive->n_images, archive->k, image_index_dev, valid, status_dev, ws_off, ws_size);
     hipLaunchKernelGGL(k_archive_copy<false>, dim3(archive->items ? archive->items : 1u), dim3(WG), 0, stream, slots, const_cast<uint8_t *>(in),
-                       archive->d_rows, archive->d_item_entry, archive->items, ws_off, ws_size, status_dev, vecmask);
+                       archive->d_rows.get(), archive->d_item_entry.get(), archive->items, ws_off, ws_size, status_dev, vecmask);
     return hipGetLastError() == hipSuccess ? SICN_OK : SICN_ENODEV;
 }
 

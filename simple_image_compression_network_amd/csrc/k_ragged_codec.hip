@@ -10,13 +10,12 @@
 //                                          work items and its 64-bit byte offsets in the latent tensor, the slot buffer and the workspace
 // Both loads are wave-uniform (they depend on blockIdx.x only) and stay in scalar registers.  The workspace block of an image is
 // what carve() gives for (ns_i, wstream_cap(wss_i)), the same function the uniform coder calls on the host.
-#include <new>
 #include <vector>
 
 #include "../../include/sicn_ragged_codec.h"
+#include "device_table.hpp"
 #include "k_codec_body.hpp"
 #include "sicn_internal.h"
-#include "sicn_weights_io.h"
 
 namespace {
 
@@ -119,9 +118,9 @@ int plan_coder(const uint32_t *lat_w, const uint32_t *lat_h, uint32_t lat_c, con
 struct sicn_ragged_coder {
     int n_images = 0;
     Plan plan;
-    CoderRow *d_rows = nullptr;       // [n_images]
-    uint32_t *d_stream_image = nullptr;     // [streams]
-    uint32_t *d_row_image = nullptr;        // [stat_rows]
+    sicn::DeviceTable<CoderRow> d_rows;             // [n_images]
+    sicn::DeviceTable<uint32_t> d_stream_image;     // [streams]
+    sicn::DeviceTable<uint32_t> d_row_image;        // [stat_rows]
 };
 
 extern "C" int sicn_ragged_codec_layout(const uint32_t *lat_w, const uint32_t *lat_h, uint32_t lat_c, const uint32_t *stream_symbols_or_null,
@@ -137,49 +136,26 @@ extern "C" int sicn_ragged_codec_layout(const uint32_t *lat_w, const uint32_t *l
     return SICN_OK;
 }
 
-extern "C" void sicn_ragged_coder_free(sicn_ragged_coder *coder)
-{
-    if (!coder) return;
-    if (coder->d_rows) (void)hipFree(coder->d_rows);
-    if (coder->d_stream_image) (void)hipFree(coder->d_stream_image);
-    if (coder->d_row_image) (void)hipFree(coder->d_row_image);
-    delete coder;
-}
+extern "C" void sicn_ragged_coder_free(sicn_ragged_coder *coder) { delete coder; }
 
 extern "C" int sicn_ragged_coder_create(const uint32_t *lat_w, const uint32_t *lat_h, uint32_t lat_c, const uint32_t *stream_symbols_or_null,
                                         const uint32_t *image_w_or_null, const uint32_t *image_h_or_null, int n_images,
                                         sicn_ragged_coder **out)
 {
-    if (!out) return SICN_EINVAL;
-    *out = nullptr;
-    sicn_ragged_coder *coder = new (std::nothrow) sicn_ragged_coder();
-    if (!coder) return SICN_ENOMEM;
-    int rc = SICN_OK;
-    try {
-        rc = plan_coder(lat_w, lat_h, lat_c, stream_symbols_or_null, image_w_or_null, image_h_or_null, n_images, true, nullptr, &coder->plan);
-        if (!rc) rc = sicn::chip_geom(nullptr);       // no device, or not a gfx950 one
-        if (!rc) {
-            coder->n_images = n_images;
-            std::vector<uint32_t> stream_image, row_image;
-            stream_image.reserve((size_t)coder->plan.streams);
-            row_image.reserve((size_t)coder->plan.stat_rows);
-            for (int i = 0; i < n_images; i++) {
-                const CoderRow &r = coder->plan.rows[(size_t)i];
-                stream_image.insert(stream_image.end(), (size_t)r.ns, (uint32_t)i);
-                row_image.insert(row_image.end(), (size_t)r.n_rows, (uint32_t)i);
-            }
-            if (!sicn::upload(coder->plan.rows.data(), coder->plan.rows.size() * sizeof(CoderRow), &coder->d_rows) ||
-                !sicn::upload(stream_image.data(), stream_image.size() * sizeof(uint32_t), &coder->d_stream_image) ||
-                !sicn::upload(row_image.data(), row_image.size() * sizeof(uint32_t), &coder->d_row_image))
-                rc = SICN_ENOMEM;
+    return sicn::make_object(out, [&](sicn_ragged_coder &coder) {
+        if (int rc = plan_coder(lat_w, lat_h, lat_c, stream_symbols_or_null, image_w_or_null, image_h_or_null, n_images, true, nullptr, &coder.plan))
+            return rc;
+        if (int rc = sicn::chip_geom(nullptr)) return rc;       // no device, or not a gfx950 one
+        coder.n_images = n_images;
+        sicn::ItemMap stream_image, row_image;
+        for (int i = 0; i < n_images; i++) {
+            const CoderRow &r = coder.plan.rows[(size_t)i];
+            stream_image.add(r.ns, (uint32_t)i);
+            row_image.add(r.n_rows, (uint32_t)i);
         }
-    } catch (const std::bad_alloc &) { rc = SICN_ENOMEM; }
-    if (rc) {
-        sicn_ragged_coder_free(coder);
-        return rc;
-    }
-    *out = coder;
-    return SICN_OK;
+        const bool ok = coder.d_rows.upload(coder.plan.rows) && stream_image.upload(coder.d_stream_image) && row_image.upload(coder.d_row_image);
+        return ok ? SICN_OK : SICN_ENOMEM;
+    });
 }
 
 // what the window decoder (k_ragged_window.hip) builds on: the coder's rows, on the host and on the device
@@ -187,7 +163,7 @@ void sicn::ragged_coder_view(const sicn_ragged_coder *coder, RaggedCoderView *v)
 {
     v->n_images = coder->n_images;
     v->rows_host = coder->plan.rows.data();
-    v->d_rows = coder->d_rows;
+    v->d_rows = coder->d_rows.get();
     v->row_bytes = sizeof(CoderRow);
     v->ws_bytes = coder->plan.ws_bytes;
 }
@@ -198,8 +174,7 @@ extern "C" int sicn_ragged_coder_encode_async(const sicn_ragged_coder *coder, co
                                               sicn_codec_status *status_dev, void *workspace, size_t workspace_bytes, void *hip_stream)
 {
     if (!coder || !latents || !containers || !status_dev) return SICN_EINVAL;
-    if (!workspace || workspace_bytes < coder->plan.ws_bytes) return SICN_ENOSPC;
-    if (reinterpret_cast<uintptr_t>(workspace) & 15) return SICN_EINVAL;
+    if (int rc = sicn::workspace_rc(workspace, workspace_bytes, coder->plan.ws_bytes)) return rc;
     if (int rc = sicn::chip_geom(nullptr)) return rc;
     hipStream_t stream = (hipStream_t)hip_stream;
     uint8_t *ws = (uint8_t *)workspace;
@@ -207,10 +182,11 @@ extern "C" int sicn_ragged_coder_encode_async(const sicn_ragged_coder *coder, co
     const unsigned streams = (unsigned)coder->plan.streams, stat_rows = (unsigned)coder->plan.stat_rows;
     // the uniform coder's three stages (sicn_codec_encode_batch_async_sl, self-scanning form): statistics in rows -> streams, every
     // wave making the frequency table itself and stream 0's wave of an image writing its header -> compaction with its own scan
-    hipLaunchKernelGGL(k_ragged_stats, dim3(stat_rows), dim3(256), 0, stream, latents, ws, coder->d_rows, coder->d_row_image);
-    hipLaunchKernelGGL(k_ragged_encode, dim3(streams), dim3(64), 0, stream, latents, containers, status, ws, coder->d_rows,
-                       coder->d_stream_image);
-    hipLaunchKernelGGL(k_ragged_compact, dim3(streams), dim3(256), 0, stream, containers, status, ws, coder->d_rows, coder->d_stream_image);
+    hipLaunchKernelGGL(k_ragged_stats, dim3(stat_rows), dim3(256), 0, stream, latents, ws, coder->d_rows.get(), coder->d_row_image.get());
+    hipLaunchKernelGGL(k_ragged_encode, dim3(streams), dim3(64), 0, stream, latents, containers, status, ws, coder->d_rows.get(),
+                       coder->d_stream_image.get());
+    hipLaunchKernelGGL(k_ragged_compact, dim3(streams), dim3(256), 0, stream, containers, status, ws, coder->d_rows.get(),
+                       coder->d_stream_image.get());
     return hipGetLastError() == hipSuccess ? SICN_OK : SICN_ENODEV;
 }
 
@@ -219,8 +195,7 @@ extern "C" int sicn_ragged_coder_decode_async(const sicn_ragged_coder *coder, co
                                               void *workspace, size_t workspace_bytes, void *hip_stream)
 {
     if (!coder || !containers || !latents || !status_dev) return SICN_EINVAL;
-    if (!workspace || workspace_bytes < coder->plan.ws_bytes) return SICN_ENOSPC;
-    if (reinterpret_cast<uintptr_t>(workspace) & 15) return SICN_EINVAL;
+    if (int rc = sicn::workspace_rc(workspace, workspace_bytes, coder->plan.ws_bytes)) return rc;
     sicn::ChipGeom chip;
     if (int rc = sicn::chip_geom(&chip)) return rc;
     hipStream_t stream = (hipStream_t)hip_stream;
@@ -229,12 +204,12 @@ extern "C" int sicn_ragged_coder_decode_async(const sicn_ragged_coder *coder, co
     const unsigned streams = (unsigned)coder->plan.streams;
     // the latency form (one 16 KB table) while all waves of the BATCH fit the chip at five per CU, as in the uniform decoder
     if (coder->plan.streams <= 5ull * (unsigned)chip.n_cu)
-        hipLaunchKernelGGL(k_ragged_decode<true>, dim3(streams), dim3(64), 0, stream, containers, valid, latents, ws, coder->d_rows,
-                           coder->d_stream_image);
+        hipLaunchKernelGGL(k_ragged_decode<true>, dim3(streams), dim3(64), 0, stream, containers, valid, latents, ws, coder->d_rows.get(),
+                           coder->d_stream_image.get());
     else
-        hipLaunchKernelGGL(k_ragged_decode<false>, dim3(streams), dim3(64), 0, stream, containers, valid, latents, ws, coder->d_rows,
-                           coder->d_stream_image);
+        hipLaunchKernelGGL(k_ragged_decode<false>, dim3(streams), dim3(64), 0, stream, containers, valid, latents, ws, coder->d_rows.get(),
+                           coder->d_stream_image.get());
     hipLaunchKernelGGL(k_ragged_dec_finish, dim3((unsigned)coder->n_images), dim3(256), 0, stream, containers, valid, (uint32_t *)status_dev,
-                       ws, coder->d_rows);
+                       ws, coder->d_rows.get());
     return hipGetLastError() == hipSuccess ? SICN_OK : SICN_ENODEV;
 }

@@ -16,16 +16,15 @@
 //                                                                byte offsets in the latent / scale tensors, the slot buffer and the workspace
 // Both loads are wave-uniform (they depend on blockIdx.x only) and stay in scalar registers.  Every kernel below: load the row of
 // its image (load_row), resolve it (ctx_image), call the stage with the index inside the image.
-#include <new>
 #include <vector>
 
 #include "../../include/sicn_ragged_ctx.h"
 #include "../../include/sicn_ctx_stream_length.h"
 #include "../../include/sicn_ragged_ctx_window.h"
 #include "ctx_window_host.hpp"
+#include "device_table.hpp"
 #include "k_ctx_body.hpp"
 #include "sicn_internal.h"
-#include "sicn_weights_io.h"
 
 namespace {
 
@@ -186,11 +185,11 @@ int plan_ctx(const uint32_t *lat_w, const uint32_t *lat_h, uint32_t lat_c, const
 struct sicn_ragged_ctx_coder {
     int n_images = 0;
     Plan plan;
-    CtxRow *d_rows = nullptr;                 // [n_images]
-    uint32_t *d_chunk_image = nullptr;        // [chunks]
-    uint32_t *d_enc_image = nullptr;          // [enc_groups]
-    uint32_t *d_dec_image[2] = {nullptr, nullptr};   // [dec_groups[set]]
-    uint32_t *d_stream_image = nullptr;       // [streams]
+    sicn::DeviceTable<CtxRow> d_rows;               // [n_images]
+    sicn::DeviceTable<uint32_t> d_chunk_image;      // [chunks]
+    sicn::DeviceTable<uint32_t> d_enc_image;        // [enc_groups]
+    sicn::DeviceTable<uint32_t> d_dec_image[2];     // [dec_groups[set]]
+    sicn::DeviceTable<uint32_t> d_stream_image;     // [streams]
 };
 
 extern "C" int sicn_ragged_ctx_layout_sl(const uint32_t *lat_w, const uint32_t *lat_h, uint32_t lat_c, const uint32_t *stream_symbols_or_null,
@@ -212,56 +211,31 @@ extern "C" int sicn_ragged_ctx_layout(const uint32_t *lat_w, const uint32_t *lat
     return sicn_ragged_ctx_layout_sl(lat_w, lat_h, lat_c, nullptr, n_images, images_or_null, totals);
 }
 
-extern "C" void sicn_ragged_ctx_coder_free(sicn_ragged_ctx_coder *coder)
-{
-    if (!coder) return;
-    for (void *p : {(void *)coder->d_rows, (void *)coder->d_chunk_image, (void *)coder->d_enc_image, (void *)coder->d_dec_image[0],
-                    (void *)coder->d_dec_image[1], (void *)coder->d_stream_image})
-        if (p) (void)hipFree(p);
-    delete coder;
-}
+extern "C" void sicn_ragged_ctx_coder_free(sicn_ragged_ctx_coder *coder) { delete coder; }
 
 extern "C" int sicn_ragged_ctx_coder_create_sl(const uint32_t *lat_w, const uint32_t *lat_h, uint32_t lat_c,
                                                const uint32_t *stream_symbols_or_null, const uint32_t *image_w_or_null,
                                                const uint32_t *image_h_or_null, int n_images, sicn_ragged_ctx_coder **out)
 {
-    if (!out) return SICN_EINVAL;
-    *out = nullptr;
-    sicn_ragged_ctx_coder *coder = new (std::nothrow) sicn_ragged_ctx_coder();
-    if (!coder) return SICN_ENOMEM;
-    int rc = SICN_OK;
-    try {
-        rc = plan_ctx(lat_w, lat_h, lat_c, stream_symbols_or_null, image_w_or_null, image_h_or_null, n_images, true, nullptr, &coder->plan);
-        if (!rc) rc = sicn::chip_geom(nullptr);       // no device, or not a gfx950 one
-        if (!rc) {
-            coder->n_images = n_images;
-            const Plan &p = coder->plan;
-            std::vector<uint32_t> chunk_image, enc_image, dec_image[2], stream_image;
-            chunk_image.reserve((size_t)p.chunks);
-            enc_image.reserve((size_t)p.enc_groups);
-            stream_image.reserve((size_t)p.streams);
-            for (int i = 0; i < n_images; i++) {
-                const CtxRow &r = p.rows[(size_t)i];
-                const uint32_t ns = r.g.nst[0] + r.g.nst[1];
-                chunk_image.insert(chunk_image.end(), (size_t)r.n_chunks, (uint32_t)i);
-                enc_image.insert(enc_image.end(), (size_t)((ns + CTX_WPB - 1) / CTX_WPB), (uint32_t)i);
-                for (int s = 0; s < 2; s++)
-                    dec_image[s].insert(dec_image[s].end(), (size_t)((r.g.nst[s] + CTX_WPB_DEC - 1) / CTX_WPB_DEC), (uint32_t)i);
-                stream_image.insert(stream_image.end(), (size_t)ns, (uint32_t)i);
-            }
-            auto up = [](const std::vector<uint32_t> &v, uint32_t **dev) { return v.empty() || sicn::upload(v.data(), v.size() * sizeof(uint32_t), dev); };
-            if (!sicn::upload(p.rows.data(), p.rows.size() * sizeof(CtxRow), &coder->d_rows) || !up(chunk_image, &coder->d_chunk_image) ||
-                !up(enc_image, &coder->d_enc_image) || !up(dec_image[0], &coder->d_dec_image[0]) ||
-                !up(dec_image[1], &coder->d_dec_image[1]) || !up(stream_image, &coder->d_stream_image))
-                rc = SICN_ENOMEM;
+    return sicn::make_object(out, [&](sicn_ragged_ctx_coder &coder) {
+        if (int rc = plan_ctx(lat_w, lat_h, lat_c, stream_symbols_or_null, image_w_or_null, image_h_or_null, n_images, true, nullptr, &coder.plan))
+            return rc;
+        if (int rc = sicn::chip_geom(nullptr)) return rc;       // no device, or not a gfx950 one
+        coder.n_images = n_images;
+        sicn::ItemMap chunk_image, enc_image, dec_image[2], stream_image;
+        for (int i = 0; i < n_images; i++) {
+            const CtxRow &r = coder.plan.rows[(size_t)i];
+            const uint32_t ns = r.g.nst[0] + r.g.nst[1];
+            chunk_image.add(r.n_chunks, (uint32_t)i);
+            enc_image.add((ns + CTX_WPB - 1) / CTX_WPB, (uint32_t)i);
+            for (int s = 0; s < 2; s++) dec_image[s].add((r.g.nst[s] + CTX_WPB_DEC - 1) / CTX_WPB_DEC, (uint32_t)i);
+            stream_image.add(ns, (uint32_t)i);
         }
-    } catch (const std::bad_alloc &) { rc = SICN_ENOMEM; }
-    if (rc) {
-        sicn_ragged_ctx_coder_free(coder);
-        return rc;
-    }
-    *out = coder;
-    return SICN_OK;
+        const bool ok = coder.d_rows.upload(coder.plan.rows) && chunk_image.upload(coder.d_chunk_image) && enc_image.upload(coder.d_enc_image) &&
+                        dec_image[0].upload(coder.d_dec_image[0]) && dec_image[1].upload(coder.d_dec_image[1]) &&
+                        stream_image.upload(coder.d_stream_image);
+        return ok ? SICN_OK : SICN_ENOMEM;
+    });
 }
 
 extern "C" int sicn_ragged_ctx_coder_create(const uint32_t *lat_w, const uint32_t *lat_h, uint32_t lat_c, const uint32_t *image_w_or_null,
@@ -274,7 +248,7 @@ void sicn::ragged_ctx_coder_view(const sicn_ragged_ctx_coder *coder, RaggedCoder
 {
     v->n_images = coder->n_images;
     v->rows_host = coder->plan.rows.data();
-    v->d_rows = coder->d_rows;
+    v->d_rows = coder->d_rows.get();
     v->row_bytes = sizeof(CtxRow);
     v->ws_bytes = coder->plan.ws_bytes;
 }
@@ -287,23 +261,22 @@ extern "C" int sicn_ragged_ctx_encode_async(const sicn_ragged_ctx_coder *coder, 
 {
     if (!coder || !latents || !scales || !containers || !status_dev) return SICN_EINVAL;
     if ((reinterpret_cast<uintptr_t>(latents) | reinterpret_cast<uintptr_t>(scales)) & 3) return SICN_EINVAL;   // dword gathers
-    if (!workspace || workspace_bytes < coder->plan.ws_bytes) return SICN_ENOSPC;
-    if (reinterpret_cast<uintptr_t>(workspace) & 15) return SICN_EINVAL;
+    if (int rc = sicn::workspace_rc(workspace, workspace_bytes, coder->plan.ws_bytes)) return rc;
     if (int rc = sicn::chip_geom(nullptr)) return rc;
     hipStream_t stream = (hipStream_t)hip_stream;
     uint8_t *ws = (uint8_t *)workspace;
     const Plan &p = coder->plan;
     const unsigned n = (unsigned)coder->n_images;
     // the uniform coder's stages (sicn_codec_ctx_encode_batch_async), its two statistics kernels as one and its verdict in the scan
-    hipLaunchKernelGGL(k_ragged_ctx_clear, dim3(n), dim3(256), 0, stream, ws, coder->d_rows);
-    hipLaunchKernelGGL(k_ragged_ctx_stats<true>, dim3((unsigned)p.chunks), dim3(256), 0, stream, latents, scales, ws, coder->d_rows,
-                       coder->d_chunk_image);
-    hipLaunchKernelGGL(k_ragged_ctx_tables, dim3(n), dim3(1024), 0, stream, containers, ws, coder->d_rows, 0);
-    hipLaunchKernelGGL(k_ragged_ctx_encode, dim3((unsigned)p.enc_groups), dim3(64 * CTX_WPB), 0, stream, latents, scales, ws, coder->d_rows,
-                       coder->d_enc_image);
-    hipLaunchKernelGGL(k_ragged_ctx_scan, dim3(n), dim3(1024), 0, stream, containers, (uint32_t *)status_dev, ws, coder->d_rows, 0);
-    hipLaunchKernelGGL(k_ragged_ctx_compact, dim3((unsigned)p.streams), dim3(256), 0, stream, containers, ws, coder->d_rows,
-                       coder->d_stream_image);
+    hipLaunchKernelGGL(k_ragged_ctx_clear, dim3(n), dim3(256), 0, stream, ws, coder->d_rows.get());
+    hipLaunchKernelGGL(k_ragged_ctx_stats<true>, dim3((unsigned)p.chunks), dim3(256), 0, stream, latents, scales, ws, coder->d_rows.get(),
+                       coder->d_chunk_image.get());
+    hipLaunchKernelGGL(k_ragged_ctx_tables, dim3(n), dim3(1024), 0, stream, containers, ws, coder->d_rows.get(), 0);
+    hipLaunchKernelGGL(k_ragged_ctx_encode, dim3((unsigned)p.enc_groups), dim3(64 * CTX_WPB), 0, stream, latents, scales, ws, coder->d_rows.get(),
+                       coder->d_enc_image.get());
+    hipLaunchKernelGGL(k_ragged_ctx_scan, dim3(n), dim3(1024), 0, stream, containers, (uint32_t *)status_dev, ws, coder->d_rows.get(), 0);
+    hipLaunchKernelGGL(k_ragged_ctx_compact, dim3((unsigned)p.streams), dim3(256), 0, stream, containers, ws, coder->d_rows.get(),
+                       coder->d_stream_image.get());
     return hipGetLastError() == hipSuccess ? SICN_OK : SICN_ENODEV;
 }
 
@@ -314,8 +287,7 @@ extern "C" int sicn_ragged_ctx_decode_async(const sicn_ragged_ctx_coder *coder, 
     if (!coder || !containers || !scales || !latents || !status_dev) return SICN_EINVAL;
     if ((reinterpret_cast<uintptr_t>(latents) | reinterpret_cast<uintptr_t>(scales)) & 3) return SICN_EINVAL;
     if (reinterpret_cast<uintptr_t>(containers) & 1) return SICN_EINVAL;   // the streams are read as 16-bit words (slot offsets are even)
-    if (!workspace || workspace_bytes < coder->plan.ws_bytes) return SICN_ENOSPC;
-    if (reinterpret_cast<uintptr_t>(workspace) & 15) return SICN_EINVAL;
+    if (int rc = sicn::workspace_rc(workspace, workspace_bytes, coder->plan.ws_bytes)) return rc;
     if (int rc = sicn::chip_geom(nullptr)) return rc;
     hipStream_t stream = (hipStream_t)hip_stream;
     uint8_t *ws = (uint8_t *)workspace;
@@ -325,17 +297,17 @@ extern "C" int sicn_ragged_ctx_decode_async(const sicn_ragged_ctx_coder *coder, 
     // a non-anchor's class reads its neighbours' bytes whatever they hold: start from zeros so that a rejected container
     // cannot make the result depend on what the buffer held before.  First, so that a failure here leaves nothing enqueued.
     if (hipMemsetAsync(latents, 0, (size_t)p.lat_bytes, stream) != hipSuccess) return SICN_ENODEV;
-    hipLaunchKernelGGL(k_ragged_ctx_parse, dim3(n), dim3(64), 0, stream, containers, (const uint32_t *)valid_dev_or_null, ws, coder->d_rows);
-    hipLaunchKernelGGL(k_ragged_ctx_tables, dim3(n), dim3(1024), 0, stream, slots, ws, coder->d_rows, 1);
-    hipLaunchKernelGGL(k_ragged_ctx_scan, dim3(n), dim3(1024), 0, stream, slots, (uint32_t *)nullptr, ws, coder->d_rows, 1);
+    hipLaunchKernelGGL(k_ragged_ctx_parse, dim3(n), dim3(64), 0, stream, containers, (const uint32_t *)valid_dev_or_null, ws, coder->d_rows.get());
+    hipLaunchKernelGGL(k_ragged_ctx_tables, dim3(n), dim3(1024), 0, stream, slots, ws, coder->d_rows.get(), 1);
+    hipLaunchKernelGGL(k_ragged_ctx_scan, dim3(n), dim3(1024), 0, stream, slots, (uint32_t *)nullptr, ws, coder->d_rows.get(), 1);
     hipLaunchKernelGGL(k_ragged_ctx_decode<0>, dim3((unsigned)p.dec_groups[0]), dim3(64 * CTX_WPB_DEC), 0, stream, containers, scales, latents, ws,
-                       coder->d_rows, coder->d_dec_image[0]);
+                       coder->d_rows.get(), coder->d_dec_image[0].get());
     if (p.dec_groups[1])   // (a batch of 1 x 1 latents has no non-anchors)
         hipLaunchKernelGGL(k_ragged_ctx_decode<1>, dim3((unsigned)p.dec_groups[1]), dim3(64 * CTX_WPB_DEC), 0, stream, containers, scales, latents, ws,
-                           coder->d_rows, coder->d_dec_image[1]);
-    hipLaunchKernelGGL(k_ragged_ctx_stats<false>, dim3((unsigned)p.chunks), dim3(256), 0, stream, latents, scales, ws, coder->d_rows,
-                       coder->d_chunk_image);
-    hipLaunchKernelGGL(k_ragged_ctx_finish, dim3(n), dim3(64), 0, stream, (uint32_t *)status_dev, ws, coder->d_rows);
+                           coder->d_rows.get(), coder->d_dec_image[1].get());
+    hipLaunchKernelGGL(k_ragged_ctx_stats<false>, dim3((unsigned)p.chunks), dim3(256), 0, stream, latents, scales, ws, coder->d_rows.get(),
+                       coder->d_chunk_image.get());
+    hipLaunchKernelGGL(k_ragged_ctx_finish, dim3(n), dim3(64), 0, stream, (uint32_t *)status_dev, ws, coder->d_rows.get());
     return hipGetLastError() == hipSuccess ? SICN_OK : SICN_ENODEV;
 }
 
@@ -365,17 +337,11 @@ struct sicn_ragged_ctx_window {
     int n_images = 0;
     uint64_t band_bytes = 0, ws_bytes = 0, groups[2] = {0, 0};
     const CtxRow *d_rows = nullptr;                  // the coder's
-    CtxWinRow *d_wrows = nullptr;                    // [n_images]
-    uint32_t *d_win_image[2] = {nullptr, nullptr};   // [groups[set]]
+    sicn::DeviceTable<CtxWinRow> d_wrows;            // [n_images]
+    sicn::DeviceTable<uint32_t> d_win_image[2];      // [groups[set]]
 };
 
-extern "C" void sicn_ragged_ctx_window_free(sicn_ragged_ctx_window *win)
-{
-    if (!win) return;
-    for (void *p : {(void *)win->d_wrows, (void *)win->d_win_image[0], (void *)win->d_win_image[1]})
-        if (p) (void)hipFree(p);
-    delete win;
-}
+extern "C" void sicn_ragged_ctx_window_free(sicn_ragged_ctx_window *win) { delete win; }
 
 extern "C" int sicn_ragged_ctx_window_create(const sicn_ragged_ctx_coder *coder, const uint32_t *r0, const uint32_t *rh,
                                              sicn_ragged_ctx_window **out)
@@ -383,50 +349,36 @@ extern "C" int sicn_ragged_ctx_window_create(const sicn_ragged_ctx_coder *coder,
     if (!out) return SICN_EINVAL;
     *out = nullptr;
     if (!coder || !r0 || !rh || coder->n_images < 1) return SICN_EINVAL;
-    sicn_ragged_ctx_window *win = new (std::nothrow) sicn_ragged_ctx_window();
-    if (!win) return SICN_ENOMEM;
-    int rc = SICN_OK;
-    try {
+    return sicn::make_object(out, [&](sicn_ragged_ctx_window &win) {
         const int n = coder->n_images;
         std::vector<CtxWinRow> wrows((size_t)n);
-        std::vector<uint32_t> win_image[2];
+        sicn::ItemMap win_image[2];
         uint64_t at = 0;
-        for (int i = 0; !rc && i < n; i++) {
+        for (int i = 0; i < n; i++) {
             const CtxRow &r = coder->plan.rows[(size_t)i];
             sicn_ragged_ctx_window_image im;
-            rc = sicn_ctx_window::plan_of_sl(r.g.W, r.g.H, r.g.C, r.g.S, r0[i], rh[i], at, &im);
-            if (rc) break;
+            if (int rc = sicn_ctx_window::plan_of_sl(r.g.W, r.g.H, r.g.C, r.g.S, r0[i], rh[i], at, &im)) return rc;
             CtxWinRow w{};
             w.lat_bias = at - (uint64_t)im.band_row0 * r.g.W * r.g.C;
             w.symbols = im.symbols;
             for (int s = 0; s < 2; s++) {
                 w.first[s] = im.first_stream[s];
                 w.end[s] = im.end_stream[s];
-                w.first_item[s] = (uint32_t)win_image[s].size();       // <= the coder's groups, which fit a grid
-                win_image[s].insert(win_image[s].end(), (size_t)((im.end_stream[s] - im.first_stream[s] + CTX_WPB_DEC - 1) / CTX_WPB_DEC), (uint32_t)i);
+                // <= the coder's groups, which fit a grid
+                w.first_item[s] = win_image[s].add((im.end_stream[s] - im.first_stream[s] + CTX_WPB_DEC - 1) / CTX_WPB_DEC, (uint32_t)i);
             }
             wrows[(size_t)i] = w;
             at += sicn_ctx_window::a16(im.band_bytes);
         }
-        if (!rc) rc = sicn::chip_geom(nullptr);       // no device, or not a gfx950 one
-        if (!rc) {
-            win->n_images = n;
-            win->band_bytes = at;
-            win->ws_bytes = coder->plan.ws_bytes;
-            win->d_rows = coder->d_rows;
-            for (int s = 0; s < 2; s++) win->groups[s] = win_image[s].size();
-            auto up = [](const std::vector<uint32_t> &v, uint32_t **dev) { return v.empty() || sicn::upload(v.data(), v.size() * sizeof(uint32_t), dev); };
-            if (!sicn::upload(wrows.data(), wrows.size() * sizeof(CtxWinRow), &win->d_wrows) || !up(win_image[0], &win->d_win_image[0]) ||
-                !up(win_image[1], &win->d_win_image[1]))
-                rc = SICN_ENOMEM;
-        }
-    } catch (const std::bad_alloc &) { rc = SICN_ENOMEM; }
-    if (rc) {
-        sicn_ragged_ctx_window_free(win);
-        return rc;
-    }
-    *out = win;
-    return SICN_OK;
+        if (int rc = sicn::chip_geom(nullptr)) return rc;       // no device, or not a gfx950 one
+        win.n_images = n;
+        win.band_bytes = at;
+        win.ws_bytes = coder->plan.ws_bytes;
+        win.d_rows = coder->d_rows.get();
+        for (int s = 0; s < 2; s++) win.groups[s] = win_image[s].size();
+        const bool ok = win.d_wrows.upload(wrows) && win_image[0].upload(win.d_win_image[0]) && win_image[1].upload(win.d_win_image[1]);
+        return ok ? SICN_OK : SICN_ENOMEM;
+    });
 }
 
 extern "C" size_t sicn_ragged_ctx_window_workspace_bytes(const sicn_ragged_ctx_window *win) { return win ? (size_t)win->ws_bytes : 0; }
@@ -438,8 +390,7 @@ extern "C" int sicn_ragged_ctx_window_decode_async(const sicn_ragged_ctx_window 
     if (!win || !containers || !scales || !band || !status_dev) return SICN_EINVAL;
     if ((reinterpret_cast<uintptr_t>(band) | reinterpret_cast<uintptr_t>(scales)) & 3) return SICN_EINVAL;   // dword gathers
     if (reinterpret_cast<uintptr_t>(containers) & 1) return SICN_EINVAL;   // the streams are read as 16-bit words (slot offsets are even)
-    if (!workspace || workspace_bytes < win->ws_bytes) return SICN_ENOSPC;
-    if (reinterpret_cast<uintptr_t>(workspace) & 15) return SICN_EINVAL;
+    if (int rc = sicn::workspace_rc(workspace, workspace_bytes, win->ws_bytes)) return rc;
     if (int rc = sicn::chip_geom(nullptr)) return rc;
     hipStream_t stream = (hipStream_t)hip_stream;
     uint8_t *ws = (uint8_t *)workspace;
@@ -452,10 +403,10 @@ extern "C" int sicn_ragged_ctx_window_decode_async(const sicn_ragged_ctx_window 
     hipLaunchKernelGGL(k_ragged_ctx_tables, dim3(n), dim3(1024), 0, stream, slots, ws, win->d_rows, 1);
     hipLaunchKernelGGL(k_ragged_ctx_scan, dim3(n), dim3(1024), 0, stream, slots, (uint32_t *)nullptr, ws, win->d_rows, 1);
     hipLaunchKernelGGL(k_ragged_ctx_decode_window<0>, dim3((unsigned)win->groups[0]), dim3(64 * CTX_WPB_DEC), 0, stream, containers, scales, band,
-                       ws, win->d_rows, win->d_wrows, win->d_win_image[0]);
+                       ws, win->d_rows, win->d_wrows.get(), win->d_win_image[0].get());
     if (win->groups[1])   // (a window of rows without non-anchors, e.g. of 1 x 1 latents)
         hipLaunchKernelGGL(k_ragged_ctx_decode_window<1>, dim3((unsigned)win->groups[1]), dim3(64 * CTX_WPB_DEC), 0, stream, containers, scales,
-                           band, ws, win->d_rows, win->d_wrows, win->d_win_image[1]);
-    hipLaunchKernelGGL(k_ragged_ctx_finish_window, dim3(n), dim3(64), 0, stream, (uint32_t *)status_dev, ws, win->d_rows, win->d_wrows);
+                           band, ws, win->d_rows, win->d_wrows.get(), win->d_win_image[1].get());
+    hipLaunchKernelGGL(k_ragged_ctx_finish_window, dim3(n), dim3(64), 0, stream, (uint32_t *)status_dev, ws, win->d_rows, win->d_wrows.get());
     return hipGetLastError() == hipSuccess ? SICN_OK : SICN_ENODEV;
 }

@@ -18,7 +18,6 @@
 //   the slot's meta block of the workspace <- its image's meta[0..3] as prepare left them, written by k_ctx_roi_place: what this
 //   call's streams report lands there and nowhere else, and what the last call's reported is gone
 // Every kernel below has the shape of k_ragged_ctx.hip's: load the row of its image (load_row), resolve it (ctx_image), call the stage.
-#include <new>
 #include <vector>
 
 #include "../../include/sicn_ragged_ctx_roi_move.h"
@@ -155,18 +154,11 @@ struct sicn_ragged_ctx_roi_move {
     int n_slots = 0, n_distinct = 0;
     sicn_ctx_roi_move::Totals totals;
     const CtxRow *d_rows = nullptr;         // the coder's
-    uint32_t *d_item_slot[2] = {nullptr, nullptr}, *d_images = nullptr;
+    sicn::DeviceTable<uint32_t> d_item_slot[2], d_images;
     sicn_roi_move::MoveTables<SlotRow, MoveRow> t;
 };
 
-extern "C" void sicn_ragged_ctx_roi_move_free(sicn_ragged_ctx_roi_move *mv)
-{
-    if (!mv) return;
-    mv->t.release();
-    for (void *b : {(void *)mv->d_item_slot[0], (void *)mv->d_item_slot[1], (void *)mv->d_images})
-        if (b) (void)hipFree(b);
-    delete mv;
-}
+extern "C" void sicn_ragged_ctx_roi_move_free(sicn_ragged_ctx_roi_move *mv) { delete mv; }
 
 extern "C" int sicn_ragged_ctx_roi_move_create(const sicn_ragged_ctx_coder *coder, const sicn_ragged_roi_slot *slots, int n_slots,
                                                sicn_ragged_ctx_roi_move **out)
@@ -178,42 +170,34 @@ extern "C" int sicn_ragged_ctx_roi_move_create(const sicn_ragged_ctx_coder *code
     sicn::ragged_ctx_coder_view(coder, &v);
     if (v.row_bytes != sizeof(CtxRow) || v.n_images < 1) return SICN_EINVAL;
     const CtxRow *rows = (const CtxRow *)v.rows_host;
-    sicn_ragged_ctx_roi_move *mv = new (std::nothrow) sicn_ragged_ctx_roi_move();
-    if (!mv) return SICN_ENOMEM;
-    int rc = SICN_OK;
-    try {
+    return sicn::make_object(out, [&](sicn_ragged_ctx_roi_move &mv) {
         const size_t n = (size_t)v.n_images;
         std::vector<uint32_t> lat_w(n), lat_h(n), wss(n), img_w(n), img_h(n);
         for (size_t i = 0; i < n; i++) {
             lat_w[i] = rows[i].g.W; lat_h[i] = rows[i].g.H; wss[i] = rows[i].g.S; img_w[i] = rows[i].img_w; img_h[i] = rows[i].img_h;
         }
         std::vector<SlotRow> srows((size_t)n_slots);
-        rc = sicn_ctx_roi_move::layout(lat_w.data(), lat_h.data(), rows[0].g.C, wss.data(), img_w.data(), img_h.data(), v.ws_bytes, v.n_images,
-                                       slots, n_slots, srows.data(), nullptr, &mv->totals);
-        if (!rc) rc = sicn::chip_geom(nullptr);       // no device, or not a gfx950 one
-        if (!rc) {
-            mv->n_slots = n_slots;
-            mv->d_rows = (const CtxRow *)v.d_rows;
-            std::vector<uint32_t> groups[2], images;
-            std::vector<char> named(n, 0);
-            for (const SlotRow &s : srows) {
-                for (int set = 0; set < 2; set++) groups[set].push_back((s.max_streams[set] + CTX_WPB_DEC - 1) / CTX_WPB_DEC);
-                named[s.image] = 1;
-            }
-            for (size_t i = 0; i < n; i++)
-                if (named[i]) images.push_back((uint32_t)i);
-            mv->n_distinct = (int)images.size();
-            if (!sicn_roi_move::upload_item_slots(groups[0], &mv->d_item_slot[0]) || !sicn_roi_move::upload_item_slots(groups[1], &mv->d_item_slot[1]) ||
-                !sicn::upload(images.data(), images.size() * sizeof(uint32_t), &mv->d_images) || !mv->t.build(srows))
-                rc = SICN_ENOMEM;
+        if (int rc = sicn_ctx_roi_move::layout(lat_w.data(), lat_h.data(), rows[0].g.C, wss.data(), img_w.data(), img_h.data(), v.ws_bytes,
+                                               v.n_images, slots, n_slots, srows.data(), nullptr, &mv.totals))
+            return rc;
+        if (int rc = sicn::chip_geom(nullptr)) return rc;       // no device, or not a gfx950 one
+        mv.n_slots = n_slots;
+        mv.d_rows = (const CtxRow *)v.d_rows;
+        sicn::ItemMap item_slot[2];
+        std::vector<uint32_t> images;
+        std::vector<char> named(n, 0);
+        for (size_t k = 0; k < srows.size(); k++) {
+            const SlotRow &s = srows[k];
+            for (int set = 0; set < 2; set++) item_slot[set].add((s.max_streams[set] + CTX_WPB_DEC - 1) / CTX_WPB_DEC, (uint32_t)k);
+            named[s.image] = 1;
         }
-    } catch (const std::bad_alloc &) { rc = SICN_ENOMEM; }
-    if (rc) {
-        sicn_ragged_ctx_roi_move_free(mv);
-        return rc;
-    }
-    *out = mv;
-    return SICN_OK;
+        for (size_t i = 0; i < n; i++)
+            if (named[i]) images.push_back((uint32_t)i);
+        mv.n_distinct = (int)images.size();
+        const bool ok = item_slot[0].upload(mv.d_item_slot[0]) && item_slot[1].upload(mv.d_item_slot[1]) && mv.d_images.upload(images) &&
+                        mv.t.build(srows);
+        return ok ? SICN_OK : SICN_ENOMEM;
+    });
 }
 
 extern "C" size_t sicn_ragged_ctx_roi_move_workspace_bytes(const sicn_ragged_ctx_roi_move *mv) { return mv ? (size_t)mv->totals.workspace : 0; }
@@ -224,15 +208,15 @@ extern "C" int sicn_ragged_ctx_roi_move_prepare_async(const sicn_ragged_ctx_roi_
 {
     if (!mv || !containers) return SICN_EINVAL;
     if (reinterpret_cast<uintptr_t>(containers) & 1) return SICN_EINVAL;   // the streams are read as 16-bit words (slot offsets are even)
-    if (!workspace || workspace_bytes < mv->totals.workspace) return SICN_ENOSPC;
-    if (reinterpret_cast<uintptr_t>(workspace) & 15) return SICN_EINVAL;
+    if (int rc = sicn::workspace_rc(workspace, workspace_bytes, mv->totals.workspace)) return rc;
     if (int rc = sicn::chip_geom(nullptr)) return rc;
     hipStream_t stream = (hipStream_t)hip_stream;
     uint8_t *ws = (uint8_t *)workspace;
     const unsigned n = (unsigned)mv->n_distinct;
-    hipLaunchKernelGGL(k_ctx_roi_parse, dim3(n), dim3(64), 0, stream, containers, (const uint32_t *)valid_dev_or_null, ws, mv->d_rows, mv->d_images);
-    hipLaunchKernelGGL(k_ctx_roi_tables, dim3(n), dim3(1024), 0, stream, containers, ws, mv->d_rows, mv->d_images);
-    hipLaunchKernelGGL(k_ctx_roi_scan, dim3(n), dim3(1024), 0, stream, containers, ws, mv->d_rows, mv->d_images);
+    hipLaunchKernelGGL(k_ctx_roi_parse, dim3(n), dim3(64), 0, stream, containers, (const uint32_t *)valid_dev_or_null, ws, mv->d_rows,
+                       mv->d_images.get());
+    hipLaunchKernelGGL(k_ctx_roi_tables, dim3(n), dim3(1024), 0, stream, containers, ws, mv->d_rows, mv->d_images.get());
+    hipLaunchKernelGGL(k_ctx_roi_scan, dim3(n), dim3(1024), 0, stream, containers, ws, mv->d_rows, mv->d_images.get());
     return hipGetLastError() == hipSuccess ? SICN_OK : SICN_ENODEV;
 }
 
@@ -244,23 +228,24 @@ extern "C" int sicn_ragged_ctx_roi_move_decode_async(const sicn_ragged_ctx_roi_m
     if (!mv || !xy_dev || !containers || !scales || !band || !window_latent || !status_dev || !flags_dev) return SICN_EINVAL;
     if ((reinterpret_cast<uintptr_t>(band) | reinterpret_cast<uintptr_t>(scales)) & 3) return SICN_EINVAL;   // dword gathers
     if (reinterpret_cast<uintptr_t>(containers) & 1) return SICN_EINVAL;
-    if (!workspace || workspace_bytes < mv->totals.workspace) return SICN_ENOSPC;
-    if ((reinterpret_cast<uintptr_t>(workspace) & 15) || (reinterpret_cast<uintptr_t>(xy_dev) & 3)) return SICN_EINVAL;
+    if (int rc = sicn::workspace_rc(workspace, workspace_bytes, mv->totals.workspace)) return rc;
+    if (reinterpret_cast<uintptr_t>(xy_dev) & 3) return SICN_EINVAL;
     if (int rc = sicn::chip_geom(nullptr)) return rc;
     hipStream_t stream = (hipStream_t)hip_stream;
     uint8_t *ws = (uint8_t *)workspace;
     const unsigned n_slots = (unsigned)mv->n_slots;
     const auto &t = mv->t;
-    hipLaunchKernelGGL(k_ctx_roi_place, dim3((n_slots + 63) / 64), dim3(64), 0, stream, xy_dev, t.d_srows, n_slots, mv->d_rows, ws, t.d_mrows,
-                       t.d_lat_rows, t.d_pix_rows, flags_dev);
+    hipLaunchKernelGGL(k_ctx_roi_place, dim3((n_slots + 63) / 64), dim3(64), 0, stream, xy_dev, t.d_srows.get(), n_slots, mv->d_rows, ws,
+                       t.d_mrows.mut(), t.d_lat_rows.mut(), t.d_pix_rows.mut(), flags_dev);
     // the full decoder's reason: a non-anchor's class reads its neighbours' bytes whatever they hold
     if (hipMemsetAsync(band, 0, (size_t)mv->totals.band, stream) != hipSuccess) return SICN_ENODEV;
     hipLaunchKernelGGL(k_ctx_roi_move_decode<0>, dim3((unsigned)mv->totals.items[0]), dim3(64 * CTX_WPB_DEC), 0, stream, containers, scales, band, ws,
-                       mv->d_rows, t.d_srows, t.d_mrows, mv->d_item_slot[0]);
+                       mv->d_rows, t.d_srows.get(), t.d_mrows.get(), mv->d_item_slot[0].get());
     if (mv->totals.items[1])   // (slots on 1 x 1 latents have no non-anchor capacity)
         hipLaunchKernelGGL(k_ctx_roi_move_decode<1>, dim3((unsigned)mv->totals.items[1]), dim3(64 * CTX_WPB_DEC), 0, stream, containers, scales, band,
-                           ws, mv->d_rows, t.d_srows, t.d_mrows, mv->d_item_slot[1]);
-    hipLaunchKernelGGL(k_ctx_roi_move_finish, dim3(n_slots), dim3(64), 0, stream, (uint32_t *)status_dev, ws, mv->d_rows, t.d_srows, t.d_mrows);
+                           ws, mv->d_rows, t.d_srows.get(), t.d_mrows.get(), mv->d_item_slot[1].get());
+    hipLaunchKernelGGL(k_ctx_roi_move_finish, dim3(n_slots), dim3(64), 0, stream, (uint32_t *)status_dev, ws, mv->d_rows, t.d_srows.get(),
+                       t.d_mrows.get());
     if (hipGetLastError() != hipSuccess) return SICN_ENODEV;
     return t.cut(false, band, window_latent, hip_stream);
 }

@@ -131,17 +131,11 @@ struct sicn_ragged_roi_move {
     bool bigtab = false;                    // the decode form, chosen once from the capacity
     sicn_roi_move::Totals totals;
     const CoderRow *d_rows = nullptr;       // the coder's
-    uint32_t *d_item_slot = nullptr;
+    sicn::DeviceTable<uint32_t> d_item_slot;
     sicn_roi_move::MoveTables<SlotRow, MoveRow> t;
 };
 
-extern "C" void sicn_ragged_roi_move_free(sicn_ragged_roi_move *mv)
-{
-    if (!mv) return;
-    mv->t.release();
-    if (mv->d_item_slot) (void)hipFree(mv->d_item_slot);
-    delete mv;
-}
+extern "C" void sicn_ragged_roi_move_free(sicn_ragged_roi_move *mv) { delete mv; }
 
 extern "C" int sicn_ragged_roi_move_create(const sicn_ragged_coder *coder, const sicn_ragged_roi_slot *slots, int n_slots,
                                            sicn_ragged_roi_move **out)
@@ -153,10 +147,7 @@ extern "C" int sicn_ragged_roi_move_create(const sicn_ragged_coder *coder, const
     sicn::ragged_coder_view(coder, &v);
     if (v.row_bytes != sizeof(CoderRow) || v.n_images < 1) return SICN_EINVAL;
     const CoderRow *rows = (const CoderRow *)v.rows_host;
-    sicn_ragged_roi_move *mv = new (std::nothrow) sicn_ragged_roi_move();
-    if (!mv) return SICN_ENOMEM;
-    int rc = SICN_OK;
-    try {
+    return sicn::make_object(out, [&](sicn_ragged_roi_move &mv) {
         const size_t n = (size_t)v.n_images;
         std::vector<uint32_t> lat_w(n), lat_h(n), wss(n), img_w(n), img_h(n);
         for (size_t i = 0; i < n; i++) {
@@ -164,28 +155,20 @@ extern "C" int sicn_ragged_roi_move_create(const sicn_ragged_coder *coder, const
         }
         std::vector<uint64_t> ws;
         std::vector<SlotRow> srows((size_t)n_slots);
-        rc = image_workspace_bytes(rows, v.n_images, v.ws_bytes, &ws);
-        if (!rc)
-            rc = sicn_roi_move::layout(lat_w.data(), lat_h.data(), rows[0].lat_c, wss.data(), img_w.data(), img_h.data(), ws.data(), v.n_images,
-                                       slots, n_slots, srows.data(), nullptr, &mv->totals);
+        if (int rc = image_workspace_bytes(rows, v.n_images, v.ws_bytes, &ws)) return rc;
+        if (int rc = sicn_roi_move::layout(lat_w.data(), lat_h.data(), rows[0].lat_c, wss.data(), img_w.data(), img_h.data(), ws.data(), v.n_images,
+                                           slots, n_slots, srows.data(), nullptr, &mv.totals))
+            return rc;
         sicn::ChipGeom chip;
-        if (!rc) rc = sicn::chip_geom(&chip);       // no device, or not a gfx950 one
-        if (!rc) {
-            mv->n_slots = n_slots;
-            mv->d_rows = (const CoderRow *)v.d_rows;
-            // the latency form (one 16 KB table) while all waves of the CAPACITY fit the chip at five per CU, the full decoder's rule
-            mv->bigtab = mv->totals.items <= 5ull * (unsigned)chip.n_cu;
-            std::vector<uint32_t> streams;
-            for (const SlotRow &s : srows) streams.push_back(s.max_streams);
-            if (!sicn_roi_move::upload_item_slots(streams, &mv->d_item_slot) || !mv->t.build(srows)) rc = SICN_ENOMEM;
-        }
-    } catch (const std::bad_alloc &) { rc = SICN_ENOMEM; }
-    if (rc) {
-        sicn_ragged_roi_move_free(mv);
-        return rc;
-    }
-    *out = mv;
-    return SICN_OK;
+        if (int rc = sicn::chip_geom(&chip)) return rc;       // no device, or not a gfx950 one
+        mv.n_slots = n_slots;
+        mv.d_rows = (const CoderRow *)v.d_rows;
+        // the latency form (one 16 KB table) while all waves of the CAPACITY fit the chip at five per CU, the full decoder's rule
+        mv.bigtab = mv.totals.items <= 5ull * (unsigned)chip.n_cu;
+        sicn::ItemMap item_slot;
+        for (size_t k = 0; k < srows.size(); k++) item_slot.add(srows[k].max_streams, (uint32_t)k);
+        return item_slot.upload(mv.d_item_slot) && mv.t.build(srows) ? SICN_OK : SICN_ENOMEM;
+    });
 }
 
 extern "C" size_t sicn_ragged_roi_move_workspace_bytes(const sicn_ragged_roi_move *mv) { return mv ? (size_t)mv->totals.workspace : 0; }
@@ -196,24 +179,24 @@ extern "C" int sicn_ragged_roi_move_decode_async(const sicn_ragged_roi_move *mv,
                                                  void *hip_stream)
 {
     if (!mv || !xy_dev || !containers || !band || !window_latent || !status_dev || !flags_dev) return SICN_EINVAL;
-    if (!workspace || workspace_bytes < mv->totals.workspace) return SICN_ENOSPC;
-    if ((reinterpret_cast<uintptr_t>(workspace) & 15) || (reinterpret_cast<uintptr_t>(xy_dev) & 3)) return SICN_EINVAL;
+    if (int rc = sicn::workspace_rc(workspace, workspace_bytes, mv->totals.workspace)) return rc;
+    if (reinterpret_cast<uintptr_t>(xy_dev) & 3) return SICN_EINVAL;
     if (int rc = sicn::chip_geom(nullptr)) return rc;
     hipStream_t stream = (hipStream_t)hip_stream;
     uint8_t *ws = (uint8_t *)workspace;
     const uint32_t *valid = (const uint32_t *)valid_dev_or_null;
     const unsigned n_slots = (unsigned)mv->n_slots, items = (unsigned)mv->totals.items;
     const auto &t = mv->t;
-    hipLaunchKernelGGL(k_roi_place, dim3((n_slots + 63) / 64), dim3(64), 0, stream, xy_dev, t.d_srows, n_slots, t.d_mrows, t.d_lat_rows,
-                       t.d_pix_rows, flags_dev);
+    hipLaunchKernelGGL(k_roi_place, dim3((n_slots + 63) / 64), dim3(64), 0, stream, xy_dev, t.d_srows.get(), n_slots, t.d_mrows.mut(),
+                       t.d_lat_rows.mut(), t.d_pix_rows.mut(), flags_dev);
     if (mv->bigtab)
-        hipLaunchKernelGGL(k_roi_move_decode<true>, dim3(items), dim3(64), 0, stream, containers, valid, band, ws, mv->d_rows, t.d_srows,
-                           t.d_mrows, mv->d_item_slot);
+        hipLaunchKernelGGL(k_roi_move_decode<true>, dim3(items), dim3(64), 0, stream, containers, valid, band, ws, mv->d_rows, t.d_srows.get(),
+                           t.d_mrows.get(), mv->d_item_slot.get());
     else
-        hipLaunchKernelGGL(k_roi_move_decode<false>, dim3(items), dim3(64), 0, stream, containers, valid, band, ws, mv->d_rows, t.d_srows,
-                           t.d_mrows, mv->d_item_slot);
+        hipLaunchKernelGGL(k_roi_move_decode<false>, dim3(items), dim3(64), 0, stream, containers, valid, band, ws, mv->d_rows, t.d_srows.get(),
+                           t.d_mrows.get(), mv->d_item_slot.get());
     hipLaunchKernelGGL(k_roi_move_finish, dim3(n_slots), dim3(256), 0, stream, containers, valid, (uint32_t *)status_dev, ws, mv->d_rows,
-                       t.d_srows, t.d_mrows);
+                       t.d_srows.get(), t.d_mrows.get());
     if (hipGetLastError() != hipSuccess) return SICN_ENODEV;
     return t.cut(false, band, window_latent, hip_stream);
 }

@@ -21,9 +21,9 @@
 #include <vector>
 
 #include "../../include/sicn_ragged_window.h"
+#include "device_table.hpp"
 #include "k_codec_body.hpp"
 #include "sicn_internal.h"
-#include "sicn_weights_io.h"
 #include "window_host.hpp"
 
 namespace {
@@ -124,17 +124,11 @@ struct sicn_ragged_window {
     int n_images = 0;
     uint64_t streams = 0, ws_bytes = 0;
     const CoderRow *d_rows = nullptr;       // the coder's
-    WinRow *d_wrows = nullptr;              // [n_images]
-    uint32_t *d_stream_image = nullptr;     // [streams]
+    sicn::DeviceTable<WinRow> d_wrows;              // [n_images]
+    sicn::DeviceTable<uint32_t> d_stream_image;     // [streams]
 };
 
-extern "C" void sicn_ragged_window_free(sicn_ragged_window *win)
-{
-    if (!win) return;
-    if (win->d_wrows) (void)hipFree(win->d_wrows);
-    if (win->d_stream_image) (void)hipFree(win->d_stream_image);
-    delete win;
-}
+extern "C" void sicn_ragged_window_free(sicn_ragged_window *win) { delete win; }
 
 extern "C" int sicn_ragged_window_create(const sicn_ragged_coder *coder, const uint32_t *r0, const uint32_t *rh, sicn_ragged_window **out)
 {
@@ -145,40 +139,26 @@ extern "C" int sicn_ragged_window_create(const sicn_ragged_coder *coder, const u
     sicn::ragged_coder_view(coder, &v);
     if (v.row_bytes != sizeof(CoderRow) || v.n_images < 1) return SICN_EINVAL;
     const CoderRow *rows = (const CoderRow *)v.rows_host;
-    sicn_ragged_window *win = new (std::nothrow) sicn_ragged_window();
-    if (!win) return SICN_ENOMEM;
-    int rc = SICN_OK;
-    try {
+    return sicn::make_object(out, [&](sicn_ragged_window &win) {
         std::vector<WinRow> wrows((size_t)v.n_images);
-        std::vector<uint32_t> stream_image;
-        uint64_t at = 0, item = 0;
-        for (int i = 0; !rc && i < v.n_images; i++) {
+        sicn::ItemMap stream_image;
+        uint64_t at = 0;
+        for (int i = 0; i < v.n_images; i++) {
             const CoderRow &r = rows[i];
             sicn_ragged_window_image im;
-            rc = sicn_window::band_of(r.lat_w, r.lat_h, r.lat_c, r.wss, r0[i], rh[i], at, &im);
-            if (rc) break;
-            wrows[(size_t)i] = WinRow{at - (uint64_t)im.first_stream * r.wss, im.first_stream, im.end_stream, (uint32_t)item, im.band_bytes};
-            stream_image.insert(stream_image.end(), (size_t)(im.end_stream - im.first_stream), (uint32_t)i);
+            if (int rc = sicn_window::band_of(r.lat_w, r.lat_h, r.lat_c, r.wss, r0[i], rh[i], at, &im)) return rc;
+            // the items are <= the coder's streams, which fit a grid
+            const uint32_t first_item = stream_image.add(im.end_stream - im.first_stream, (uint32_t)i);
+            wrows[(size_t)i] = WinRow{at - (uint64_t)im.first_stream * r.wss, im.first_stream, im.end_stream, first_item, im.band_bytes};
             at += sicn_window::a16(im.band_bytes);
-            item += im.end_stream - im.first_stream;       // <= the coder's streams, which fit a grid
         }
-        if (!rc) rc = sicn::chip_geom(nullptr);       // no device, or not a gfx950 one
-        if (!rc) {
-            win->n_images = v.n_images;
-            win->streams = item;
-            win->ws_bytes = v.ws_bytes;
-            win->d_rows = (const CoderRow *)v.d_rows;
-            if (!sicn::upload(wrows.data(), wrows.size() * sizeof(WinRow), &win->d_wrows) ||
-                !sicn::upload(stream_image.data(), stream_image.size() * sizeof(uint32_t), &win->d_stream_image))
-                rc = SICN_ENOMEM;
-        }
-    } catch (const std::bad_alloc &) { rc = SICN_ENOMEM; }
-    if (rc) {
-        sicn_ragged_window_free(win);
-        return rc;
-    }
-    *out = win;
-    return SICN_OK;
+        if (int rc = sicn::chip_geom(nullptr)) return rc;       // no device, or not a gfx950 one
+        win.n_images = v.n_images;
+        win.streams = stream_image.size();
+        win.ws_bytes = v.ws_bytes;
+        win.d_rows = (const CoderRow *)v.d_rows;
+        return win.d_wrows.upload(wrows) && stream_image.upload(win.d_stream_image) ? SICN_OK : SICN_ENOMEM;
+    });
 }
 
 extern "C" size_t sicn_ragged_window_workspace_bytes(const sicn_ragged_window *win) { return win ? (size_t)win->ws_bytes : 0; }
@@ -188,8 +168,7 @@ extern "C" int sicn_ragged_window_decode_async(const sicn_ragged_window *win, co
                                                void *workspace, size_t workspace_bytes, void *hip_stream)
 {
     if (!win || !containers || !band || !status_dev) return SICN_EINVAL;
-    if (!workspace || workspace_bytes < win->ws_bytes) return SICN_ENOSPC;
-    if (reinterpret_cast<uintptr_t>(workspace) & 15) return SICN_EINVAL;
+    if (int rc = sicn::workspace_rc(workspace, workspace_bytes, win->ws_bytes)) return rc;
     sicn::ChipGeom chip;
     if (int rc = sicn::chip_geom(&chip)) return rc;
     hipStream_t stream = (hipStream_t)hip_stream;
@@ -199,12 +178,12 @@ extern "C" int sicn_ragged_window_decode_async(const sicn_ragged_window *win, co
     // the latency form (one 16 KB table) while all waves of the SELECTION fit the chip at five per CU, the full decoder's rule
     if (win->streams <= 5ull * (unsigned)chip.n_cu)
         hipLaunchKernelGGL(k_ragged_decode_window<true>, dim3(streams), dim3(64), 0, stream, containers, valid, band, ws, win->d_rows,
-                           win->d_wrows, win->d_stream_image);
+                           win->d_wrows.get(), win->d_stream_image.get());
     else
         hipLaunchKernelGGL(k_ragged_decode_window<false>, dim3(streams), dim3(64), 0, stream, containers, valid, band, ws, win->d_rows,
-                           win->d_wrows, win->d_stream_image);
+                           win->d_wrows.get(), win->d_stream_image.get());
     hipLaunchKernelGGL(k_ragged_dec_finish_window, dim3((unsigned)win->n_images), dim3(256), 0, stream, containers, valid,
-                       (uint32_t *)status_dev, ws, win->d_rows, win->d_wrows);
+                       (uint32_t *)status_dev, ws, win->d_rows, win->d_wrows.get());
     return hipGetLastError() == hipSuccess ? SICN_OK : SICN_ENODEV;
 }
 
@@ -212,8 +191,8 @@ extern "C" int sicn_ragged_window_decode_async(const sicn_ragged_window *win, co
 struct sicn_ragged_cut {
     int n_images = 0;
     unsigned items = 0;
-    CutRow *d_rows = nullptr;               // [n_images]
-    uint32_t *d_item_image = nullptr;       // [items]
+    sicn::DeviceTable<CutRow> d_rows;               // [n_images]
+    sicn::DeviceTable<uint32_t> d_item_image;       // [items]
 };
 
 namespace {
@@ -263,32 +242,20 @@ int sicn::ragged_cut_create(const int32_t *src_w, const int32_t *src_h, const si
     CutTables t;
     if (int rc = cut_tables(src_w, src_h, rects, channels, src_offset_or_null, n_images, &t)) return rc;
     if (int rc = chip_geom(nullptr)) return rc;      // no device, or not a gfx950 one
-    sicn_ragged_cut *cut = new (std::nothrow) sicn_ragged_cut();
-    if (!cut) return SICN_ENOMEM;
-    int rc = SICN_OK;
-    try {
-        cut->n_images = n_images;
-        cut->items = (unsigned)t.first_item[(size_t)n_images];
-        std::vector<uint32_t> map;
-        map.reserve((size_t)cut->items);
-        for (int i = 0; i < n_images; i++) map.insert(map.end(), (size_t)(t.first_item[(size_t)i + 1] - t.first_item[(size_t)i]), (uint32_t)i);
-        if (!upload(t.rows.data(), t.rows.size() * sizeof(CutRow), &cut->d_rows) ||
-            !upload(map.data(), map.size() * sizeof(uint32_t), &cut->d_item_image))
-            rc = SICN_ENOMEM;
-    } catch (const std::bad_alloc &) { rc = SICN_ENOMEM; }
-    if (rc) {
-        sicn_ragged_cut_free(cut);
-        return rc;
-    }
-    *out = cut;
-    return SICN_OK;
+    return make_object(out, [&](sicn_ragged_cut &cut) {
+        cut.n_images = n_images;
+        cut.items = (unsigned)t.first_item[(size_t)n_images];
+        ItemMap map;
+        for (int i = 0; i < n_images; i++) map.add((size_t)(t.first_item[(size_t)i + 1] - t.first_item[(size_t)i]), (uint32_t)i);
+        return cut.d_rows.upload(t.rows) && map.upload(cut.d_item_image) ? SICN_OK : SICN_ENOMEM;
+    });
 }
 
 int sicn::ragged_cut_run(const sicn_ragged_cut *cut, const uint8_t *src, uint8_t *dst, void *hip_stream)
 {
     if (!cut || !src || !dst) return SICN_EINVAL;
     if (int rc = chip_geom(nullptr)) return rc;
-    return ragged_cut_launch(cut->d_rows, cut->d_item_image, cut->items, src, dst, hip_stream);
+    return ragged_cut_launch(cut->d_rows.get(), cut->d_item_image.get(), cut->items, src, dst, hip_stream);
 }
 
 int sicn::ragged_cut_launch(const void *d_rows, const uint32_t *d_item_image, unsigned items, const uint8_t *src, uint8_t *dst, void *hip_stream)
@@ -310,13 +277,7 @@ extern "C" int sicn_ragged_cut_create(const int32_t *src_w, const int32_t *src_h
     return sicn::ragged_cut_create(src_w, src_h, rects, channels, src_offset_or_null, n_images, out);
 }
 
-extern "C" void sicn_ragged_cut_free(sicn_ragged_cut *cut)
-{
-    if (!cut) return;
-    if (cut->d_rows) (void)hipFree(cut->d_rows);
-    if (cut->d_item_image) (void)hipFree(cut->d_item_image);
-    delete cut;
-}
+extern "C" void sicn_ragged_cut_free(sicn_ragged_cut *cut) { delete cut; }
 
 extern "C" int sicn_ragged_cut_run(const sicn_ragged_cut *cut, const uint8_t *src, uint8_t *dst, void *hip_stream)
 {

@@ -1,57 +1,44 @@
 // What the two moving ROI decodes hold in common on the device (k_ragged_roi_move.hip over rANS-W, k_ragged_ctx_roi_move.hip over
-// rANS-WC): the tables that do not depend on the coder, built, released and cut from in ONE place.  Slot and Move are the coder's
+// rANS-WC): the tables that do not depend on the coder, built, owned and cut from in ONE place.  Slot and Move are the coder's
 // SlotRow and MoveRow (roi_move_host.hpp, ctx_roi_move_host.hpp); nothing else here differs between the two.
 #pragma once
 #include <vector>
 
+#include "device_table.hpp"
 #include "roi_move_host.hpp"
 #include "sicn_internal.h"
-#include "sicn_weights_io.h"
 
 namespace sicn_roi_move {
 
-// counts[k] work items of slot k -> the grid's table on the device, the slot of every item: ONE load resolves item -> slot.
-// *items: the grid.  An empty grid has no table.
-inline bool upload_item_slots(const std::vector<uint32_t> &counts, uint32_t **dev, unsigned *items = nullptr)
-{
-    std::vector<uint32_t> map;
-    for (size_t k = 0; k < counts.size(); k++) map.insert(map.end(), (size_t)counts[k], (uint32_t)k);
-    if (items) *items = (unsigned)map.size();
-    return map.empty() || sicn::upload(map.data(), map.size() * sizeof(uint32_t), dev);
-}
-
 template <class Slot, class Move>
 struct MoveTables {
-    Slot *d_srows = nullptr;                                            // [n_slots] constant: it begins with the shared SlotGeom
-    uint32_t *d_lat_item_slot = nullptr, *d_pix_item_slot = nullptr;    // the two cuts' grids, which the capacities fix
+    sicn::DeviceTable<Slot> d_srows;                                    // [n_slots] constant: it begins with the shared SlotGeom
+    sicn::DeviceTable<uint32_t> d_lat_item_slot, d_pix_item_slot;       // the two cuts' grids, which the capacities fix
     unsigned lat_items = 0, pix_items = 0;
-    Move *d_mrows = nullptr;                                            // [n_slots] each, written by the coder's place kernel
-    CutRow *d_lat_rows = nullptr, *d_pix_rows = nullptr;
+    // [n_slots] each, written by the coder's place kernel on every decode: mutable, because a decode takes the object as const — it
+    // changes nothing on the host, and what the device holds is the last placement's by contract
+    mutable sicn::DeviceTable<Move> d_mrows;
+    mutable sicn::DeviceTable<CutRow> d_lat_rows, d_pix_rows;
 
     // The rows the placement writes start as the placement of (0, 0): a cut that runs before any decode stays in bounds.
     bool build(const std::vector<Slot> &srows)
     {
-        std::vector<uint32_t> lat_n, pix_n;
+        sicn::ItemMap lat_map, pix_map;
         std::vector<Move> mrows;
         std::vector<CutRow> lat_rows, pix_rows;
-        for (const Slot &s : srows) {
-            lat_n.push_back((uint32_t)((s.rh_cap + CUT_ROWS - 1) / CUT_ROWS));
-            pix_n.push_back((uint32_t)((s.h + CUT_ROWS - 1) / CUT_ROWS));
+        for (size_t k = 0; k < srows.size(); k++) {
+            const Slot &s = srows[k];
+            lat_map.add((uint32_t)((s.rh_cap + CUT_ROWS - 1) / CUT_ROWS), (uint32_t)k);
+            pix_map.add((uint32_t)((s.h + CUT_ROWS - 1) / CUT_ROWS), (uint32_t)k);
             const auto p = place_slot(s, 0, 0);
             mrows.push_back(p.win);
             lat_rows.push_back(p.lat_cut);
             pix_rows.push_back(p.pix_cut);
         }
-        return sicn::upload(srows.data(), srows.size() * sizeof(Slot), &d_srows) && upload_item_slots(lat_n, &d_lat_item_slot, &lat_items) &&
-               upload_item_slots(pix_n, &d_pix_item_slot, &pix_items) && sicn::upload(mrows.data(), mrows.size() * sizeof(Move), &d_mrows) &&
-               sicn::upload(lat_rows.data(), lat_rows.size() * sizeof(CutRow), &d_lat_rows) &&
-               sicn::upload(pix_rows.data(), pix_rows.size() * sizeof(CutRow), &d_pix_rows);
-    }
-
-    void release()
-    {
-        for (void *b : {(void *)d_srows, (void *)d_lat_item_slot, (void *)d_pix_item_slot, (void *)d_mrows, (void *)d_lat_rows, (void *)d_pix_rows})
-            if (b) (void)hipFree(b);
+        lat_items = (unsigned)lat_map.size();
+        pix_items = (unsigned)pix_map.size();
+        return d_srows.upload(srows) && lat_map.upload(d_lat_item_slot) && pix_map.upload(d_pix_item_slot) && d_mrows.upload(mrows) &&
+               d_lat_rows.upload(lat_rows) && d_pix_rows.upload(pix_rows);
     }
 
     // k_ragged_cut over the rows of the last placement: band -> window latent, or (pixels) reconstruction -> ROI pixels
@@ -59,8 +46,8 @@ struct MoveTables {
     {
         if (!src || !dst) return SICN_EINVAL;
         if (int rc = sicn::chip_geom(nullptr)) return rc;
-        return pixels ? sicn::ragged_cut_launch(d_pix_rows, d_pix_item_slot, pix_items, src, dst, hip_stream)
-                      : sicn::ragged_cut_launch(d_lat_rows, d_lat_item_slot, lat_items, src, dst, hip_stream);
+        return pixels ? sicn::ragged_cut_launch(d_pix_rows.get(), d_pix_item_slot.get(), pix_items, src, dst, hip_stream)
+                      : sicn::ragged_cut_launch(d_lat_rows.get(), d_lat_item_slot.get(), lat_items, src, dst, hip_stream);
     }
 };
 

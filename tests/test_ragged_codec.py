@@ -2,7 +2,10 @@
 sicn_ragged_codec_layout — where every latent, container slot and workspace block of a batch of different shapes lies and how every
 image is cut into streams — against plain Python arithmetic.  Nothing here touches a device."""
 import ctypes
+import os
 import re
+import shutil
+import subprocess
 from pathlib import Path
 
 import numpy as np
@@ -147,3 +150,25 @@ def test_coder_create_rejects_bad_arguments_without_a_device():
     dummy = ctypes.c_void_p(16)
     assert L.sicn_ragged_coder_encode_async(None, dummy, dummy, dummy, dummy, 1 << 20, None) == EINVAL
     assert L.sicn_ragged_coder_decode_async(None, dummy, None, dummy, dummy, dummy, 1 << 20, None) == EINVAL
+
+
+def test_device_tables_under_the_sanitizers(tmp_path):
+    """tests/cpp/device_table_check.cpp — csrc/device_table.hpp with host fakes of hipMalloc, hipFree and hipMemcpy and its own
+    main — built with the address and undefined-behaviour sanitizers and run as a child process: every allocation and every copy of
+    a create fails in its turn and leaves SICN_ENOMEM, a null handle and no live allocation; success and delete, an empty vector, a
+    moved-from table, a build that throws std::bad_alloc, the item map against the insert loop, the workspace check."""
+    gxx = shutil.which("g++") or shutil.which("c++")
+    if gxx is None:
+        pytest.skip("no host C++ compiler")
+    exe = tmp_path / "device_table_check"
+    flags = ["-std=c++17", "-g", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
+    r = subprocess.run([gxx, *flags, str(ROOT / "tests" / "cpp" / "device_table_check.cpp"), "-o", str(exe)], capture_output=True, text=True)
+    if r.returncode != 0 and re.search(r"cannot find -l(asan|ubsan)|libasan|libubsan|unrecognized.*-fsanitize", r.stderr):
+        pytest.skip(f"the compiler cannot link the sanitizer runtime here: {r.stderr.strip().splitlines()[-1]}")
+    assert r.returncode == 0, r.stderr
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+    r = subprocess.run([str(exe)], capture_output=True, text=True, env=env, timeout=120)
+    if r.returncode != 0 and "ASan runtime does not come first in initial library list" in r.stderr:
+        pytest.skip("a library preloaded into every process here comes before the sanitizer's runtime, which refuses to start behind it")
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert re.search(r"device_table_check ok: \d+ checks", r.stdout), r.stdout

@@ -475,3 +475,24 @@ def test_valid_shorter_than_the_fixed_part(mods, batch_a):
         lo = int(im.first_stream) * 1024
         assert np.array_equal(host[int(im.band_offset):int(im.band_offset) + int(im.band_bytes)],
                               b.latents[i].reshape(-1)[lo:lo + int(im.band_bytes)])
+
+
+def test_window_create_refuses_a_bad_second_image_and_leaves_no_handle(mods):
+    """sicn_ragged_window_create over a live coder of two images (latents 1 x 1 and 3 x 2, 4 channels): a row range the SECOND image
+    cannot hold is refused after the first image's entries were made — SICN_EINVAL and a null handle — and the same coder then
+    makes a window of sound rows."""
+    _lib, _, _ = mods
+    L = _lib.lib()
+    u32 = ctypes.c_uint32 * 2
+    coder, win = ctypes.c_void_p(), ctypes.c_void_p(1)
+    assert L.sicn_ragged_coder_create(u32(1, 3), u32(1, 2), 4, u32(1024, 1024), None, None, 2, ctypes.byref(coder)) == 0
+    try:
+        for r0, rh in [((0, 0), (1, 0)), ((0, 2), (1, 1)), ((0, 1), (1, 2))]:       # no rows; behind the latent; past its end
+            win.value = 1
+            assert L.sicn_ragged_window_create(coder, u32(*r0), u32(*rh), ctypes.byref(win)) == -22
+            assert not win.value
+        assert L.sicn_ragged_window_create(coder, u32(0, 1), u32(1, 1), ctypes.byref(win)) == 0 and win.value
+        assert L.sicn_ragged_window_workspace_bytes(win) == L.sicn_ragged_coder_workspace_bytes(coder)
+        L.sicn_ragged_window_free(win)
+    finally:
+        L.sicn_ragged_coder_free(coder)

@@ -504,3 +504,26 @@ def test_argument_checks_come_before_any_launch(mods, batches):
     assert call(*args, need, stream) == 0
     torch.cuda.synchronize()
     _guards_untouched(outer)
+
+
+def test_create_refuses_a_bad_second_slot_and_leaves_no_handle(mods):
+    """sicn_ragged_roi_move_create over a live coder of two images (16 x 16 and 48 x 32: latents 1 x 1 and 3 x 2, 4 channels): a
+    SECOND slot its image cannot hold is refused after the first slot was laid out — SICN_EINVAL and a null handle — and the same
+    coder then makes an object of sound slots."""
+    _lib, _, _ = mods
+    L = _lib.lib()
+    u32 = ctypes.c_uint32 * 2
+    coder, mv = ctypes.c_void_p(), ctypes.c_void_p(1)
+    assert L.sicn_ragged_coder_create(u32(1, 3), u32(1, 2), 4, u32(1024, 1024), u32(16, 48), u32(16, 32), 2, ctypes.byref(coder)) == 0
+    try:
+        for bad in [(1, 49, 20), (1, 20, 0), (2, 16, 16)]:                           # wider than its image; empty; no such image
+            mv.value = 1
+            slots = (_lib.RaggedRoiSlot * 2)(_lib.RaggedRoiSlot(0, 16, 16), _lib.RaggedRoiSlot(*bad))
+            assert L.sicn_ragged_roi_move_create(coder, slots, 2, ctypes.byref(mv)) == -22
+            assert not mv.value
+        slots = (_lib.RaggedRoiSlot * 2)(_lib.RaggedRoiSlot(0, 16, 16), _lib.RaggedRoiSlot(1, 20, 20))
+        assert L.sicn_ragged_roi_move_create(coder, slots, 2, ctypes.byref(mv)) == 0 and mv.value
+        assert L.sicn_ragged_roi_move_workspace_bytes(mv) == L.sicn_ragged_coder_workspace_bytes(coder)
+        L.sicn_ragged_roi_move_free(mv)
+    finally:
+        L.sicn_ragged_coder_free(coder)

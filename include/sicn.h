@@ -226,12 +226,17 @@ int sicn_net_forward(const sicn_net *net, int first_layer, int last_layer, const
  * most 96 of its channels and takes them in the internal GROUP layout; the net owns the permuted copies this needs as above.
  * sicn_debug_net_groups: per layer of the net the 32-channel groups the same call would compute and store (groups_out: 3 or 4 for
  * that layer, 4 for every other one) and those the layer that wrote its input computed (groups_in; 4 for the call's first layer and
- * outside [first_layer, last_layer]). */
+ * outside [first_layer, last_layer]).
+ * Behind such a layer a conv 128 -> 128 on the wide family walks K over the three groups that were stored (a tile of 80 K steps in
+ * place of 100; the symbol sicn_debug_net_walk_groups being present is the marker, sicn_version() stays 17).
+ * sicn_debug_net_walk_groups: per layer of the net the groups of its input that its K walk covers in the same call: 3 or 4 for such a
+ * conv, 4 for every other layer and outside [first_layer, last_layer]. */
 int sicn_debug_net_columns(const sicn_net *net, int first_layer, int last_layer, int tap_layer, int n_images, int32_t *columns,
                            int32_t *live_outputs);
 int sicn_debug_net_input_halves(const sicn_net *net, int first_layer, int last_layer, int tap_layer, int n_images, int32_t *halves);
 int sicn_debug_net_groups(const sicn_net *net, int first_layer, int last_layer, int tap_layer, int n_images, int32_t *groups_out,
                           int32_t *groups_in);
+int sicn_debug_net_walk_groups(const sicn_net *net, int first_layer, int last_layer, int tap_layer, int n_images, int32_t *walk_groups);
 /* eight_layers_net(in, out, numReps): the whole chain; latent_or_null receives layer 3's output. */
 int sicn_eight_layers_net(const sicn_net *net, const uint8_t *in, uint8_t *out,
                           uint8_t *latent_or_null, int n_images, void *workspace,

@@ -63,6 +63,7 @@ ABI = {
     "sicn_debug_net_columns": (_i, [_vp, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
     "sicn_debug_net_input_halves": (_i, [_vp, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_int32)]),
     "sicn_debug_net_groups": (_i, [_vp, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
+    "sicn_debug_net_walk_groups": (_i, [_vp, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_int32)]),
 }
 
 

@@ -1,5 +1,6 @@
 // Device-side helpers shared by the MFMA kernels (k_mfma16*.hip, k_rgb.hip, k_l0g.hip, k_gdn.hip).
 #pragma once
+#include "conv_walk.hpp"
 #include "sicn_internal.h"
 #include "sicn_plan.h"
 
@@ -135,20 +136,6 @@ __device__ __forceinline__ int xcd_logical_index(int n_items, int n_xcd)
     return (l / n_xcd < per && idx < n_items) ? idx : -1;
 }
 
-// ---- conv tap order: by parity plane (a,b) = (ky&1, kx&1), so that a plane's LDS buffer is
-// ---- free for the next channel group as soon as its taps are done (k_mfma.hip) -------------
-struct Tap { int ky, kx; };
-__host__ __device__ constexpr Tap conv_tap(int t)
-{
-    int n = 0;
-    for (int a = 0; a < 2; a++)
-        for (int b = 0; b < 2; b++)
-            for (int ky = a; ky < 5; ky += 2)
-                for (int kx = b; kx < 5; kx += 2) {
-                    if (n == t) return Tap{ky, kx};
-                    n++;
-                }
-    return Tap{-1, -1};
-}
+// (the conv tap order, conv_tap: conv_walk.hpp)
 
 }  // namespace sicn

@@ -57,13 +57,14 @@ bool mfma_supported(int cin, int cout, int transposed)
 
 hipError_t launch_mfma16(const LayerGeom &g, const sicn_weights &w, const uint8_t *in, uint8_t *out, int n_images,
                          hipStream_t stream, int in_layout, int out_layout, const sicn_options &o, const ChipGeom &chip, bool relu,
-                         unsigned long long *deal, int columns)
+                         unsigned long long *deal, int columns, int groups_in)
 {
     if ((size_t)g.IH * g.IW * g.CIN >= (size_t)OOB) return hipErrorInvalidValue;          // 31-bit patch offsets
     if ((size_t)g.OH * g.OW * g.COUT >= (size_t)OOB) return hipErrorInvalidValue;         // buffer-descriptor stores
     if (!mfma_supported(g.CIN, g.COUT, g.transposed)) return hipErrorInvalidValue;
     const MfmaPlan p = plan_mfma(g, n_images, o, chip);
-    if (p.family == 2) return launch_wide(g, w, in, out, n_images, stream, in_layout, out_layout, relu, o.persistent_grid, chip, deal, columns);
+    if (p.family == 2) return launch_wide(g, w, in, out, n_images, stream, in_layout, out_layout, relu, o.persistent_grid, chip, deal, columns,
+                                          groups_in);
     if (columns != 8) return hipErrorInvalidValue;   // only the wide family skips columns (sicn_live.h)
     // (round 2 sent the deconv 192 -> 128 on full grids back to a plain, unpipelined kernel: the pipelined one was 7 % slower there.
     // The reason was the v_mov copies hipcc made for its run-time buffer parity — right around the asm MFMAs, where
@@ -73,19 +74,8 @@ hipError_t launch_mfma16(const LayerGeom &g, const sicn_weights &w, const uint8_
 
 // ---- host-side weight packing: the tile sequence of the 32x32x32 form, rows in the 16x16 C/D
 // ---- order (LDS row j*16 + rho holds channel 64*(j>>2) + 16*(rho>>2) + 4*(j&3) + (rho&3)), no swizzle;
-// ---- PAD16 zero tiles behind the stream (k_common.hpp)
+// ---- PAD16 zero tiles behind the stream (k_common.hpp).  The tile packer and the conv's group-major order: conv_walk.hpp
 size_t mfma16_stream_bytes(int cin, int cout) { return (size_t)(25 * (cin / 32) + PAD16) * cout * KSTEP; }
-
-static void pack_tile16(const int8_t *w_okc, int cin, int cout, int tap, int q, int8_t *tile)
-{
-    const int kk = 25 * cin;
-    for (int row = 0; row < cout; row++) {
-        const int j = row >> 4, rho = row & 15;
-        const int ch = 64 * (j >> 2) + 16 * (rho >> 2) + 4 * (j & 3) + (rho & 3);
-        const int8_t *src = w_okc + (size_t)ch * kk + tap * cin + q * 32;
-        for (int b = 0; b < 32; b++) tile[row * 32 + b] = src[b];
-    }
-}
 
 void pack_mfma16_stream(const int8_t *w_okc, int cin, int cout, int transposed, int8_t *dst)
 {
@@ -93,11 +83,8 @@ void pack_mfma16_stream(const int8_t *w_okc, int cin, int cout, int transposed, 
     const size_t tb = (size_t)cout * KSTEP;
     size_t step = 0;
     if (!transposed) {
-        for (int q = 0; q < nq; q++)
-            for (int t = 0; t < 25; t++) {
-                const Tap tap = conv_tap(t);
-                pack_tile16(w_okc, cin, cout, tap.ky * 5 + tap.kx, q, dst + (step++) * tb);
-            }
+        pack_conv_stream16(w_okc, cin, cout, dst);
+        step = (size_t)25 * nq;
     } else {
         for (int ph = 0; ph < 4; ph++) {
             const int py = ph >> 1, px = ph & 1;

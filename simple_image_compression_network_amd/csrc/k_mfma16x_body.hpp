@@ -1,9 +1,10 @@
 // The wide persistent kernels of the 128 -> 128 layers as templates: the passes, the accumulator hand-over, the tile deal and the two
 // kernel bodies.  k_mfma16x.hip (which describes the form) instantiates them with all 8 accumulator columns, k_mfma16x_live.hip with
-// the NJ < 8 columns whose channels the next layer reads (sicn_live.h).
+// the NJ < 8 columns whose channels the next layer reads (sicn_live.h), k_mfma16x_g3.hip the conv whose K walk covers three channel groups.
 #pragma once
 #include <algorithm>
 
+#include "conv_walk.hpp"
 #include "k_common.hpp"
 
 namespace sicn {
@@ -14,13 +15,12 @@ constexpr int PIECES = (PIX * KSTEP + 1023) / 1024;                       // 20 
 constexpr int SLOTS = PIECES / 4;                                         // 5 per wave
 static_assert(PIECES % 4 == 0, "every wave issues the same number of pieces");
 constexpr int PLANE = PIECES * 1024;                                      // 20480
-constexpr int RING = 10, TB = 128 * KSTEP;                                // 10 slots x 4 KiB: one K step of 128 output channels
-constexpr int FLIGHT = 3;                                                 // passes whose requests may be in flight at a barrier
+constexpr int TB = 128 * KSTEP;                                           // a ring slot (RING of them, conv_walk.hpp): 4 KiB, one K step of 128 output channels
 constexpr int NSTORE = 16;                                                // output stores per wave and accumulator hand-over
 // ... of NJ columns: a store carries the 4 columns of one channel half, and a half without a column (NJ <= 4: channels 64 .. 127) is
 // not stored at all.  The counted waits behind a hand-over (EXTRA) go by this number: too high would let a request land uncounted.
 __host__ __device__ constexpr int nstore_x(int NJ) { return NJ > 4 ? NSTORE : NSTORE / 2; }
-constexpr int NPASS = 50;                                                 // passes (of two K steps) per tile
+constexpr int NPASS = 50;                                                 // passes (of two K steps) per deconv tile (the conv: conv_npass)
 
 typedef __attribute__((address_space(3))) uint8_t lds_u8;   // LDS pointers stay 32-bit (a generic pointer costs a null check per cast)
 
@@ -384,91 +384,8 @@ __device__ __forceinline__ int deal_take(const DealX &d, unsigned long long &m, 
 // =====================================================================================================================
 // conv2d<>
 // =====================================================================================================================
-// The DMA schedule: one 25-pass window = two channel groups (50 K steps); a tile is two windows.  Plane pl of the group the
-// window starts with is last READ (fragments are fetched one pass ahead of their MFMAs) in pass 3 / 6 / 9 / 11, of the window's
-// second group in pass 15 / 18 / 21 / 23; it is re-filled from the pass after that.  What a pass reads was requested at least
-// FLIGHT + 1 passes earlier.  KIND: which group a piece belongs to —
-//   CUR0: the window's first group (the tail of plane 2 and plane 3, requested in the window's first passes)
-//   CUR1: the window's second group
-//   NEXT0: the first group of the NEXT window (in a tile's second window: of the workgroup's next tile)
-enum { K_CUR0 = 0, K_CUR1 = 1, K_NEXT0 = 2 };
-struct Refresh {
-    int plane, slot, kind;
-};
-__host__ __device__ constexpr Refresh refresh_x(int P, int idx)   // the idx-th (0 / 1) piece of window pass P, plane < 0: none
-{
-    constexpr Refresh none{-1, 0, 0};
-    switch (P) {
-    case 0: return idx == 0 ? Refresh{2, 3, K_CUR0} : Refresh{3, 0, K_CUR0};
-    case 1: return idx == 0 ? Refresh{2, 4, K_CUR0} : Refresh{3, 1, K_CUR0};
-    case 2: return idx == 0 ? Refresh{3, 2, K_CUR0} : none;
-    case 3: return idx == 0 ? Refresh{3, 3, K_CUR0} : none;
-    case 4: return idx == 0 ? Refresh{3, 4, K_CUR0} : Refresh{0, 0, K_CUR1};
-    case 5: return idx == 0 ? Refresh{0, 1, K_CUR1} : none;
-    case 6: return idx == 0 ? Refresh{0, 2, K_CUR1} : Refresh{0, 3, K_CUR1};
-    case 7: return idx == 0 ? Refresh{0, 4, K_CUR1} : Refresh{1, 0, K_CUR1};
-    case 8: return idx == 0 ? Refresh{1, 1, K_CUR1} : none;
-    case 9: return idx == 0 ? Refresh{1, 2, K_CUR1} : none;
-    case 10: return idx == 0 ? Refresh{1, 3, K_CUR1} : Refresh{2, 0, K_CUR1};
-    case 11: return idx == 0 ? Refresh{1, 4, K_CUR1} : Refresh{2, 1, K_CUR1};
-    case 12: return idx == 0 ? Refresh{2, 2, K_CUR1} : Refresh{3, 0, K_CUR1};
-    case 13: return idx == 0 ? Refresh{2, 3, K_CUR1} : Refresh{3, 1, K_CUR1};
-    case 14: return idx == 0 ? Refresh{2, 4, K_CUR1} : Refresh{3, 2, K_CUR1};
-    case 15: return idx == 0 ? Refresh{3, 3, K_CUR1} : Refresh{3, 4, K_CUR1};
-    case 16: return idx == 0 ? Refresh{0, 0, K_NEXT0} : none;
-    case 17: return idx == 0 ? Refresh{0, 1, K_NEXT0} : none;
-    case 18: return idx == 0 ? Refresh{0, 2, K_NEXT0} : none;
-    case 19: return idx == 0 ? Refresh{0, 3, K_NEXT0} : Refresh{1, 0, K_NEXT0};
-    case 20: return idx == 0 ? Refresh{0, 4, K_NEXT0} : Refresh{1, 1, K_NEXT0};
-    case 21: return idx == 0 ? Refresh{1, 2, K_NEXT0} : none;
-    case 22: return idx == 0 ? Refresh{1, 3, K_NEXT0} : Refresh{2, 0, K_NEXT0};
-    case 23: return idx == 0 ? Refresh{1, 4, K_NEXT0} : Refresh{2, 1, K_NEXT0};
-    case 24: return idx == 0 ? Refresh{2, 2, K_NEXT0} : none;
-    }
-    return none;
-}
-__host__ __device__ constexpr int requests_x(int P)   // LDS-DMA instructions a wave issues in window pass P (any integer P)
-{
-    const int p = ((P % 25) + 25) % 25;
-    return 2 + (refresh_x(p, 0).plane >= 0) + (refresh_x(p, 1).plane >= 0);
-}
-__host__ __device__ constexpr int in_flight_x(int P)   // requests of the last FLIGHT passes
-{
-    int s = 0;
-    for (int i = 0; i < FLIGHT; i++) s += requests_x(P - i);
-    return s;
-}
-// the schedule against the walk, checked at compile time: a piece of plane pl, kind k, requested in pass P must be requested
-// after the plane's last read and FLIGHT + 1 passes before its first read
-__host__ __device__ constexpr bool schedule_ok()
-{
-    int count[3][4] = {};
-    for (int P = 0; P < 25; P++)
-        for (int i = 0; i < 2; i++) {
-            const Refresh r = refresh_x(P, i);
-            if (r.plane < 0) continue;
-            count[r.kind][r.plane] |= 1 << r.slot;
-            // steps (window-local) at which the OLD content of the plane is last used and the NEW content first used
-            const int first_tap[4] = {0, 9, 15, 21}, last_tap[4] = {8, 14, 20, 24};
-            int last_use_step = 0, first_use_step = 0;   // relative to this window's step 0
-            if (r.kind == K_CUR0) { last_use_step = last_tap[r.plane] - 25; first_use_step = first_tap[r.plane]; }
-            else if (r.kind == K_CUR1) { last_use_step = last_tap[r.plane]; first_use_step = 25 + first_tap[r.plane]; }
-            else { last_use_step = 25 + last_tap[r.plane]; first_use_step = 50 + first_tap[r.plane]; }
-            // MFMAs of step s run in pass floor(s / 2) and their fragments are read one pass earlier
-            auto fl = [](int s) { return s >= 0 ? s / 2 : -((-s + 1) / 2); };
-            const int last_read = fl(last_use_step) - 1, first_read = fl(first_use_step) - 1;
-            if (P <= last_read) return false;               // would overwrite fragments still to be read
-            if (P > first_read - 1 - FLIGHT) return false;   // would not be covered by the counted wait before its first read
-        }
-    // every plane's 5 slots exactly once per group: CUR0 carries plane 2 slots 3, 4 and plane 3; NEXT0 the rest
-    for (int pl = 0; pl < 4; pl++) {
-        if (count[K_CUR1][pl] != 31) return false;
-        if ((count[K_CUR0][pl] | count[K_NEXT0][pl]) != 31 || (count[K_CUR0][pl] & count[K_NEXT0][pl]) != 0) return false;
-    }
-    return true;
-}
-static_assert(schedule_ok(), "conv refresh schedule violates the read / landing windows");
-
+// The walk itself — tap order, stream steps, ring slots, the plane refresh schedule of a tile over NG = 4 or 3 channel groups and
+// its compile-time checks — is plain C++ in conv_walk.hpp, which the host-side replay (tests/cpp/conv_walk_check.cpp) reads too.
 __host__ __device__ constexpr uint32_t tap_off_x(int t)   // byte offset of tap t (plane-ordered walk) inside the planes
 {
     const Tap a = conv_tap(t);
@@ -504,17 +421,19 @@ __device__ __forceinline__ void set_poff_x(uint32_t (&poff)[4][SLOTS], const Ten
     }
 }
 
-// pass T (0 .. 49) of a conv tile: the window pass is T % 25, the window T / 25
-template <int T, int KIND, bool NT, int JV, int NJ>
+// pass T (0 .. conv_npass(NG) - 1) of a conv tile over NG channel groups (conv_walk.hpp)
+template <int T, int KIND, bool NT, int JV, int NJ, int NG>
 __device__ __forceinline__ void conv_pass_x(v4i (&acc)[8][8], const v4i (&pc)[8], const v4i (&wc)[8], v4i (&pn)[8], v4i (&wn)[8],
                                             const ConvXCtx &c, const uint32_t (&poff)[4][SLOTS], bool stores, const HandX &h,
                                             const BiasX &bias)
 {
-    constexpr int P = T % 25, WIN = T / 25;
+    static_assert(NG == 3 || NG == 4, "the walks that are scheduled");
+    constexpr int NP = conv_npass(NG);
+    static_assert(T >= 0 && T < NP, "a pass of the tile");
     // ---- fragments of the next pass (T + 1, wrapping into the next tile: same offsets, the ring does not care) --------------
-    constexpr int TN = (T + 1) % NPASS;
-    constexpr uint32_t offNA = tap_off_x((2 * TN) % 25), offNB = tap_off_x((2 * TN + 1) % 25);
-    constexpr int slotN = (2 * TN) % RING;                    // the upper K half reads slot slotN + 1 (lane_wt carries that)
+    constexpr uint32_t offNA = tap_off_x(conv_step_tap(conv_read_step(NG, T, 0))), offNB = tap_off_x(conv_step_tap(conv_read_step(NG, T, 1)));
+    constexpr int slotN = ring_slot(conv_read_step(NG, T, 0));   // the upper K half reads slot slotN + 1 (lane_wt carries that)
+    static_assert(ring_slot(conv_read_step(NG, T, 1)) == slotN + 1, "the two K halves of a pass sit in neighbouring slots");
     const uint32_t pixn = c.lane_pix + (c.hi ? offNB : offNA);
     const uint32_t wtn = c.lane_wt;
     auto rd = [&](auto r_tag) {
@@ -528,47 +447,51 @@ __device__ __forceinline__ void conv_pass_x(v4i (&acc)[8][8], const v4i (&pc)[8]
     auto dma = [&](auto idx_tag) {
         constexpr int idx = decltype(idx_tag)::value;   // 0, 1: weight tiles; 2, 3: plane pieces
         if constexpr (idx < 2) {
-            constexpr int step = (2 * T + RING + idx) % (2 * NPASS), slot = (2 * T + idx) % RING;   // slot of step s is s % RING
-            __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void *)c.wstream, 0, 2 * NPASS * TB, 0x00020000);
+            constexpr int step = conv_ring_step(NG, T, idx), slot = conv_ring_slot(T, idx);   // slot of step s is s % RING
+            static_assert(ring_slot(step) == slot, "the ring wraps with the tile");
+            // the stream ends where the tile does: three groups read the first 2 NP = 80 steps of the four-group stream, 75 real ones and
+            // 5 all-zero tiles (conv_walk.hpp)
+            __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void *)c.wstream, 0, 2 * NP * TB, 0x00020000);
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, c.ring_w + slot * TB, 16, c.lane_w16, (uint32_t)(step * TB), 0, 0);
         } else {
-            constexpr Refresh r = refresh_x(P, idx - 2);
+            constexpr Refresh r = conv_refresh(NG, T, idx - 2);
             if constexpr (r.plane >= 0) {
-                // group of the piece: window WIN holds groups 2 WIN, 2 WIN + 1; NEXT0 of the second window = group 0 (of the next tile)
-                constexpr int q = r.kind == K_CUR0 ? 2 * WIN : r.kind == K_CUR1 ? 2 * WIN + 1 : (2 * WIN + 2) % 4;
+                // group of the piece: the NEXT0 pieces of a tile's last window are group 0 of the next tile
+                constexpr int q = conv_piece_group(NG, T, r.kind);
                 __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)c.dma_img, 0, c.img_bytes, 0x00020000);
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, c.planes_w + r.plane * PLANE + r.slot * 4096, 16,
                                                          poff[r.plane][r.slot] + (uint32_t)q * c.grp, 0, 0, 0);
             }
         }
     };
-    constexpr int VM = in_flight_x(P);
+    constexpr int VM = conv_in_flight(NG, T);   // across the window seam and the tile seam alike
     pass_x<JV, NJ, KIND, VM, (T < FLIGHT ? nstore_x(NJ) : 0), NT>(acc, pc, wc, rd, dma, stores, h, bias);
 }
 
-template <int T, int END, bool NT, int JV, int NJ>
+template <int T, int END, bool NT, int JV, int NJ, int NG>
 __device__ __forceinline__ void conv_passes_x(v4i (&acc)[8][8], v4i (&pa)[8], v4i (&wa)[8], v4i (&pb)[8], v4i (&wb)[8], const ConvXCtx &c,
                                               const uint32_t (&poff)[4][SLOTS], bool stores, const HandX &h, const BiasX &bias)
 {
     if constexpr ((T & 1) == 0)
-        conv_pass_x<T, 0, NT, JV, NJ>(acc, pa, wa, pb, wb, c, poff, stores, h, bias);
+        conv_pass_x<T, 0, NT, JV, NJ, NG>(acc, pa, wa, pb, wb, c, poff, stores, h, bias);
     else
-        conv_pass_x<T, 0, NT, JV, NJ>(acc, pb, wb, pa, wa, c, poff, stores, h, bias);
-    if constexpr (T + 1 < END) conv_passes_x<T + 1, END, NT, JV, NJ>(acc, pa, wa, pb, wb, c, poff, stores, h, bias);
+        conv_pass_x<T, 0, NT, JV, NJ, NG>(acc, pb, wb, pa, wa, c, poff, stores, h, bias);
+    if constexpr (T + 1 < END) conv_passes_x<T + 1, END, NT, JV, NJ, NG>(acc, pa, wa, pb, wb, c, poff, stores, h, bias);
 }
 
 constexpr size_t CONV_LDS = 4 * PLANE + RING * TB;
-constexpr int SWITCH_T = 25 + 16;                 // from this pass of a tile on, every plane request belongs to the next tile
 
-// the kernel's body: k_conv_x (k_mfma16x.hip, NJ = 8) and k_conv_live (k_mfma16x_live.hip) are this and nothing else
+// the kernel's body: k_conv_x (k_mfma16x.hip, NJ = 8), k_conv_live (k_mfma16x_live.hip) and, with NG = 3, k_conv_g3 (k_mfma16x_g3.hip) are this
+// and nothing else
 #define SICN_WIDE_KERNEL_ARGS \
     const uint8_t *__restrict__ in, uint8_t *__restrict__ out, const int8_t *__restrict__ wstream, const int8_t *__restrict__ bias_g, int IW, \
     int IH, int OW, int OH, int tiles_x, int n_tiles, int n_images, int in_layout, int out_layout, uint32_t act_floor, int n_xcd, \
     unsigned long long *deal
 #define SICN_WIDE_KERNEL_PASS in, out, wstream, bias_g, IW, IH, OW, OH, tiles_x, n_tiles, n_images, in_layout, out_layout, act_floor, n_xcd, deal
-template <bool NT, int JV, int NJ>
+template <bool NT, int JV, int NJ, int NG>
 __device__ __forceinline__ void conv_x_body(SICN_WIDE_KERNEL_ARGS)
 {
+    constexpr int NP = conv_npass(NG), SWITCH_T = conv_switch_pass(NG);   // NG = 4: 50 and 41, NG = 3: 40 and 30
     static_assert(NJ >= 1 && NJ <= 8 && JV <= NJ, "columns j < JV in AGPRs, JV <= j < NJ in VGPRs");
     constexpr int CIN = 128, COUT = 128;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -616,7 +539,7 @@ __device__ __forceinline__ void conv_x_body(SICN_WIDE_KERNEL_ARGS)
 #pragma unroll
             for (int slot = 0; slot < (pl < 2 ? SLOTS : 3); slot++)
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, ctx.planes_w + pl * PLANE + slot * 4096, 16, poff[pl][slot], 0, 0, 0);
-        __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void *)wstream, 0, 2 * NPASS * TB, 0x00020000);
+        __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void *)wstream, 0, 2 * NP * TB, 0x00020000);
 #pragma unroll
         for (int s = 0; s < RING; s++) __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, ctx.ring_w + s * TB, 16, ctx.lane_w16, (uint32_t)(s * TB), 0, 0);
     }
@@ -652,7 +575,7 @@ __device__ __forceinline__ void conv_x_body(SICN_WIDE_KERNEL_ARGS)
                 asm volatile("" : "+v"(acc[i][j]));
         }
     asm volatile("s_nop 3" ::: "memory");   // v_accvgpr_write / v_mov -> asm MFMA reading it as SrcC
-    conv_pass_x<0, 0, NT, JV, NJ>(acc, pa, wa, pb, wb, ctx, poff, false, h, bias);
+    conv_pass_x<0, 0, NT, JV, NJ, NG>(acc, pa, wa, pb, wb, ctx, poff, false, h, bias);
     bool stores = false;   // a hand-over's stores may be in flight (not in the first tile)
     int tile_no = 0;         // tiles this workgroup has finished (DealX: the mailbox's sequence numbers)
     uint32_t deal_tk = DEAL_PENDING;
@@ -670,21 +593,21 @@ __device__ __forceinline__ void conv_x_body(SICN_WIDE_KERNEL_ARGS)
         // the next tile: tile 1 is the static deal's; from then on it was published in the mailbox while the previous tile ran (DealX)
         int next = item + stride;
         const bool dyn = dl.ws != 0, later = dyn && tile_no > 0;
-        conv_passes_x<1, 3, NT, JV, NJ>(acc, pa, wa, pb, wb, ctx, poff, stores, h, bias);
+        conv_passes_x<1, 3, NT, JV, NJ, NG>(acc, pa, wa, pb, wb, ctx, poff, stores, h, bias);
         if (later) deal_request(dl, deal_mail);
-        conv_passes_x<3, 7, NT, JV, NJ>(acc, pa, wa, pb, wb, ctx, poff, stores, h, bias);
+        conv_passes_x<3, 7, NT, JV, NJ, NG>(acc, pa, wa, pb, wb, ctx, poff, stores, h, bias);
         if (later) next = deal_take(dl, deal_mail, (uint32_t)tile_no + 1u);
         // a ticket is only taken for a tile this workgroup will get to: the one behind `next`
         const bool has_next = dyn ? (next >= 0 && (tile_no > 0 || next < item_end)) : next < item_end;
         const bool goes_on = dyn && has_next && w == 0 && !deal_done;
         if (goes_on) deal_ticket_issue(dl, dl.xcd, deal_tk, lane);
-        conv_passes_x<7, 13, NT, JV, NJ>(acc, pa, wa, pb, wb, ctx, poff, stores, h, bias);
+        conv_passes_x<7, 13, NT, JV, NJ, NG>(acc, pa, wa, pb, wb, ctx, poff, stores, h, bias);
         if (goes_on) {
             const int it2 = deal_resolve(dl, deal_tk, lane);
             deal_publish(dl, (uint32_t)tile_no + 2u, it2, lane);
             deal_done = it2 < 0;
         }
-        conv_passes_x<13, SWITCH_T, NT, JV, NJ>(acc, pa, wa, pb, wb, ctx, poff, stores, h, bias);
+        conv_passes_x<13, SWITCH_T, NT, JV, NJ, NG>(acc, pa, wa, pb, wb, ctx, poff, stores, h, bias);
         // every plane request for THIS tile has been issued: the rest of the tile fetches the next tile's first group
         const TileX tn = coord(has_next ? next : item);
         int lane_l;   // recomputed, not kept
@@ -694,11 +617,11 @@ __device__ __forceinline__ void conv_x_body(SICN_WIDE_KERNEL_ARGS)
         // where the finished tile goes
         h.ro = __builtin_amdgcn_make_buffer_rsrc((void *)(out + (size_t)tc.img * out_img_bytes), 0, out_img_bytes, 0x00020000);
         set_out_off_x(h.off, om, tc, w, lane_l, OW, OH, 1);
-        conv_passes_x<SWITCH_T, NPASS, NT, JV, NJ>(acc, pa, wa, pb, wb, ctx, poff, false, h, bias);
+        conv_passes_x<SWITCH_T, NP, NT, JV, NJ, NG>(acc, pa, wa, pb, wb, ctx, poff, false, h, bias);
         // pass 0 of the next tile with the hand-over of this one woven in (after the last tile: the same pass on zero-filled
         // planes, whose results nobody reads — one pass in 32 tiles, and the tile loop stays one body)
         asm volatile("s_nop 7" ::: "memory");   // the last MFMAs' results -> v_accvgpr_read (AGPR tiles) / the SDWA pack (VGPR tiles)
-        conv_pass_x<0, 2, NT, JV, NJ>(acc, pa, wa, pb, wb, ctx, poff, true, h, bias);
+        conv_pass_x<0, 2, NT, JV, NJ, NG>(acc, pa, wa, pb, wb, ctx, poff, true, h, bias);
         stores = true;
         if (!has_next) break;
         item = next;

@@ -16,7 +16,7 @@ namespace xw {
 template <bool NT, int NJ>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void k_conv_live(SICN_WIDE_KERNEL_ARGS)
 {
-    conv_x_body<NT, 0, NJ>(SICN_WIDE_KERNEL_PASS);
+    conv_x_body<NT, 0, NJ, 4>(SICN_WIDE_KERNEL_PASS);
 }
 template <bool NT, int NJ>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void k_deconv_live(SICN_WIDE_KERNEL_ARGS)

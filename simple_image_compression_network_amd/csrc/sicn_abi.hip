@@ -12,6 +12,7 @@
 #include <new>
 #include <vector>
 
+#include "conv_walk.hpp"
 #include "sicn_gdn_internal.h"
 #include "sicn_internal.h"
 #include "sicn_live.h"
@@ -286,7 +287,7 @@ bool mfma_images(const int8_t *k, sicn_weights &w)
 hipError_t mfma_launch(const LaunchArgs &a, bool *)
 {
     return launch_mfma16(a.g, a.w, a.in, a.out, a.n_images, a.stream, a.in_layout, a.out_layout, a.o, a.chip, a.gdn == nullptr, a.deal,
-                         a.columns);
+                         a.columns, a.groups_in);
 }
 void mfma_plan(const LayerGeom &g, int n_images, const sicn_options &o, const ChipGeom &chip, int32_t out[12])
 {
@@ -550,6 +551,11 @@ static int make_live_plan(sicn_net *net)
                 std::vector<int8_t> t(okc.size());
                 live::permute_inputs(okc.data(), w.cout, net->live[l - 1].p, t.data());
                 okc.swap(t);
+                // behind a producer that stores three groups the wide conv walks three (k_mfma16x.hip: wide_walk_groups) and takes the
+                // steps 75 .. 79 of this copy's stream for zero tiles: no weight on an input position in the fourth group
+                if (net->live[l - 1].ng < live::GROUPS && w.cin == live::CH &&
+                    !conv_inputs_zero_from(okc.data(), w.cin, w.cout, net->live[l - 1].ng * live::GROUP_CH))
+                    return SICN_EINVAL;
             }
             if (out_p) {
                 std::vector<int8_t> t(okc.size());
@@ -704,6 +710,28 @@ extern "C" int sicn_debug_net_groups(const sicn_net *net, int first, int last, i
     for (int l = first; l <= last; l++) {
         groups_in[l] = groups_before;
         groups_before = groups_out[l] = call_groups(net, l, first, last, tap_layer, call_out_layout(net, l, last, tap_layer));
+    }
+    return SICN_OK;
+}
+
+// what a call would do, for tests: per layer of the net the 32-channel groups of its input that its K walk covers — 3 for a conv on the
+// wide family behind a layer that stored three groups in this call (wide_walk_groups, the function launch_wide chooses its kernel by),
+// 4 for every other launch and outside [first, last]
+extern "C" int sicn_debug_net_walk_groups(const sicn_net *net, int first, int last, int tap_layer, int n_images, int32_t *walk_groups)
+{
+    if (!net || !walk_groups || n_images <= 0) return SICN_EINVAL;
+    const int n_layers = (int)net->descs.size();
+    if (first < 0 || last >= n_layers || first > last) return SICN_EINVAL;
+    ChipGeom chip;
+    if (int rc = chip_geom(&chip)) return rc;
+    for (int l = 0; l < n_layers; l++) walk_groups[l] = live::GROUPS;
+    int groups_before = live::GROUPS;
+    for (int l = first; l <= last; l++) {
+        const Family &f = layer_family(net->descs[l], net->opt, net->gdn[l] != nullptr);
+        const LayerGeom g = geom_of(net->descs[l]);
+        const bool wide = (f.kind == KK_MFMA_CONV || f.kind == KK_MFMA_DECONV) && plan_mfma(g, n_images, net->opt, chip).family == 2;
+        if (wide) walk_groups[l] = wide_walk_groups(g, groups_before);
+        groups_before = call_groups(net, l, first, last, tap_layer, call_out_layout(net, l, last, tap_layer));
     }
     return SICN_OK;
 }

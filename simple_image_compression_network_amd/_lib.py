@@ -282,6 +282,15 @@ RAGGED_RGB_ABI = {
 }
 RAGGED_RGB_ENDS = {"generic": 0, "packed": 1}     # SICN_RAGGED_RGB_GENERIC / SICN_RAGGED_RGB_PACKED
 
+# include/sicn_ragged_planar.h (planar RGB [3][h][w] at a ragged net's pixel boundaries, the output at sizes of the caller's choice;
+# sicn_version() stays 17 — these symbols being present is the marker)
+RAGGED_PLANAR_ABI = {
+    "sicn_ragged_net_create_planar": (_i, [_descp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _i, _i32p, _i32p, _i, _i, _i, _i, _i32p, _i32p,
+                                           ctypes.POINTER(_vp)]),
+    "sicn_ragged_planar_layout": (_i, [_descp, _i, _i32p, _i32p, _i, _i, _i32p, _i32p, _i, _i64p]),
+}
+RAGGED_PIXELS = {"interleaved": 0, "planar": 1}   # SICN_RAGGED_PIXELS_INTERLEAVED / SICN_RAGGED_PIXELS_PLANAR
+
 
 class RaggedRoiSlot(ctypes.Structure):
     """ctypes image of `sicn_ragged_roi_slot` (include/sicn_ragged_roi_move.h)."""
@@ -372,7 +381,7 @@ def lib() -> ctypes.CDLL:
         L = ctypes.CDLL(str(LIB_PATH))
         for name, (res, args) in {**ABI, **CODEC_ABI, **CONVLAYER_ABI, **GDN_ABI, **RAGGED_ABI, **RAGGED_HYPER_ABI, **RAGGED_CODEC_ABI, **RAGGED_CTX_ABI, **RAGGED_ARCHIVE_ABI,
                                   **RAGGED_ARCHIVE_SELECT_ABI, **RAGGED_WINDOW_ABI, **RAGGED_CTX_WINDOW_ABI, **CTX_SL_ABI, **RAGGED_RGB_ABI, **RAGGED_ROI_MOVE_ABI,
-                                  **RAGGED_CTX_ROI_MOVE_ABI}.items():
+                                  **RAGGED_CTX_ROI_MOVE_ABI, **RAGGED_PLANAR_ABI}.items():
             fn = getattr(L, name)          # AttributeError if the ABI is incomplete
             fn.restype = res
             fn.argtypes = args

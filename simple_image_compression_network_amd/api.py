@@ -429,6 +429,12 @@ def roi_plan(size, rect, n_up_layers: int = 4):
     return {k: int(getattr(out, k)) for k, _ in _lib.RaggedRoiPlan._fields_}
 
 
+def _refuse_planar(net, what):
+    """The ROI decodes cut their pixels from interleaved rows (k_ragged_cut): a net with planar pixels is refused before any launch."""
+    if getattr(net, "planar_in", False) or getattr(net, "planar_out", False):
+        raise ValueError(f"{what}: the ROI decodes have no planar form; make the net with rgb_layout='interleaved'")
+
+
 def _roi_chain(net, plans, rects, bands, first_rows):
     """What follows a window decoder in an ROI decode, shared by RaggedRoi and hyperprior.RaggedHyperpriorRoi: (the latent cut, the
     window net, the pixel cut).  bands: per image (the latent rows its band holds, the band's byte offset in the band tensor);
@@ -455,6 +461,7 @@ class RaggedRoi:
     one from net.latent_coder(stream_symbols))."""
 
     def __init__(self, net, rects, coder=None, stream_symbols=16384):
+        _refuse_planar(net, "RaggedRoi")
         n = len(net.sizes)
         if len(rects) != n:
             raise ValueError(f"rects: one per image, {n}")
@@ -497,6 +504,7 @@ class _MovingRoiChain(_lib.Handle):
 
     def _check_slots(self, net, slots):
         """-> self.slots, or ValueError before anything is made."""
+        _refuse_planar(net, type(self).__name__)
         self.slots = [tuple(int(v) for v in s) for s in slots]
         if len(self.slots) < 1 or any(len(s) != 3 for s in self.slots):
             raise ValueError("slots: at least one (image, w, h)")
@@ -629,16 +637,28 @@ class RaggedNet(_lib.Handle):
     `shared_weights` must match it, as in `EightLayersNet(descs=...)`).  `gdn`: a list of `GDN | None`, one per layer — the
     activation in place of that layer's ReLU (sicn_ragged_net_create_gdn); one more launch per such layer, for the whole batch.
     `rgb_ends`: "packed" (default) runs a conv 3 -> N and a deconv N -> 3 of the chain on the packed-K kernels of
-    include/sicn_ragged_rgb.h, "generic" on the channel-generic ones like every other layer; the bytes are the same."""
+    include/sicn_ragged_rgb.h, "generic" on the channel-generic ones like every other layer; the bytes are the same.
+    `rgb_layout`: "interleaved" (default) or "planar" (include/sicn_ragged_planar.h).  With "planar" the input is [3][h][w] per image
+    if the chain begins with a conv 3 -> N, and the output is [3][h][w] if it ends with a deconv N -> 3: `shapes`, `nbytes`, `pack`
+    and `views` of those boundaries follow, everything else is unchanged.  `out_sizes`: [(width, height)] of the planar output, each
+    within the chain-rule size — the top-left corner of every reconstruction is stored, nothing else.  None: the images' sizes where
+    the chain begins with a conv 3 -> N and every image fits its reconstruction (the eight layers: no `cropped` pass is needed),
+    the chain-rule sizes otherwise.  An end of the chain that is not such a layer stays as it is: on a chain with neither, "planar"
+    makes the interleaved net (`planar_in`, `planar_out` say which ends are planar)."""
     _free = "sicn_ragged_net_free"
 
     def __init__(self, sizes, params=None, device=None, n_ch: int = 128, m_ch: int = 192,
                  shared_weights: Optional[Sequence[DeviceWeights]] = None, descs: Optional[Sequence[LayerDesc]] = None,
-                 gdn: Optional[Sequence[Optional["GDN"]]] = None, rgb_ends: str = "packed"):
+                 gdn: Optional[Sequence[Optional["GDN"]]] = None, rgb_ends: str = "packed", rgb_layout: str = "interleaved",
+                 out_sizes=None):
         import torch
         if rgb_ends not in _lib.RAGGED_RGB_ENDS:
             raise ValueError(f"rgb_ends: 'packed' or 'generic', not {rgb_ends!r}")
-        self.rgb_ends = rgb_ends
+        if rgb_layout not in _lib.RAGGED_PIXELS:
+            raise ValueError(f"rgb_layout: 'interleaved' or 'planar', not {rgb_layout!r}")
+        if rgb_layout == "planar" and rgb_ends != "packed":
+            raise ValueError("rgb_layout='planar' needs rgb_ends='packed': the generic family has no planar form")
+        self.rgb_ends, self.rgb_layout = rgb_ends, rgb_layout
         L = _lib.lib()
         self.sizes = [(int(w), int(h)) for w, h in sizes]
         n_img = len(self.sizes)
@@ -653,6 +673,20 @@ class RaggedNet(_lib.Handle):
             with torch.cuda.device(self.device):
                 self.weights = [DeviceWeights(d, w, b) for d, (w, b) in zip(self.descs, params)]
         n = len(self.descs)
+        planar = rgb_layout == "planar" and n > 0
+        self.planar_in = planar and not self.descs[0].transposed and self.descs[0].IFM_CH == 3
+        self.planar_out = planar and bool(self.descs[-1].transposed) and self.descs[-1].OFM_CH == 3
+        if out_sizes is not None and not self.planar_out:
+            raise ValueError("out_sizes: only a planar output (rgb_layout='planar', a chain that ends with deconv N -> 3) has sizes of its own")
+        if out_sizes is None and self.planar_out and self.planar_in:
+            chain = self.sizes
+            for d in self.descs:
+                chain = [(2 * w, 2 * h) if d.transposed else (-(-w // 2), -(-h // 2)) for w, h in chain]
+            if all(w <= cw and h <= ch for (w, h), (cw, ch) in zip(self.sizes, chain)):
+                out_sizes = self.sizes
+        self.out_sizes = None if out_sizes is None else [(int(w), int(h)) for w, h in out_sizes]
+        if self.out_sizes is not None and len(self.out_sizes) != len(self.sizes):
+            raise ValueError(f"out_sizes: one (width, height) per image, {len(self.sizes)}")
         self._cdescs = (CLayerDesc * n)(*[d.to_c() for d in self.descs])
         self._widths = (ctypes.c_int32 * max(n_img, 1))(*[w for w, _ in self.sizes])
         self._heights = (ctypes.c_int32 * max(n_img, 1))(*[h for _, h in self.sizes])
@@ -664,9 +698,15 @@ class RaggedNet(_lib.Handle):
         ghandles = None
         if self.gdn is not None:
             ghandles = (ctypes.c_void_p * n)(*[(g.handle if g is not None else None) for g in self.gdn])
+        self._out_widths = self._out_heights = None
+        if self.out_sizes is not None:
+            self._out_widths = (ctypes.c_int32 * max(n_img, 1))(*[w for w, _ in self.out_sizes])
+            self._out_heights = (ctypes.c_int32 * max(n_img, 1))(*[h for _, h in self.out_sizes])
         with torch.cuda.device(self.device):
-            _lib.check(L.sicn_ragged_net_create_rgb(self._cdescs, handles, ghandles, n, self._widths, self._heights, n_img,
-                                                    _lib.RAGGED_RGB_ENDS[rgb_ends], ctypes.byref(self._h)), "sicn_ragged_net_create_rgb")
+            _lib.check(L.sicn_ragged_net_create_planar(self._cdescs, handles, ghandles, n, self._widths, self._heights, n_img,
+                                                       _lib.RAGGED_RGB_ENDS[rgb_ends], int(self.planar_in), int(self.planar_out),
+                                                       self._out_widths, self._out_heights, ctypes.byref(self._h)),
+                       "sicn_ragged_net_create_planar")
         # per boundary (-1 .. n - 1, index layer + 1): the images' shapes and byte offsets, as the library lays them out
         self._shapes, self._offsets, self._nbytes = [], [], []
         q = (ctypes.c_int64 * 8)()
@@ -679,6 +719,17 @@ class RaggedNet(_lib.Handle):
             self._shapes.append(shapes)
             self._offsets.append(offs)
             self._nbytes.append(int(q[4]))
+        # a planar boundary: (3, h, w) per image; the output at its own sizes and offsets (sicn_ragged_planar_layout)
+        if self.planar_in:
+            self._shapes[0] = [(c, h, w) for h, w, c in self._shapes[0]]
+        if self.planar_out:
+            shapes, offs = [], []
+            for i in range(n_img):
+                _lib.check(L.sicn_ragged_planar_layout(self._cdescs, n, self._widths, self._heights, n_img, 1, self._out_widths,
+                                                       self._out_heights, i, q), "sicn_ragged_planar_layout")
+                shapes.append((3, int(q[1]), int(q[0])))
+                offs.append(int(q[2]))
+            self._shapes[n], self._offsets[n], self._nbytes[n] = shapes, offs, int(q[3])
         self._ws = None
         self._coders = {}           # compress()'s RaggedLatentCoders by stream length, made on first use
         self._archives = {}         # compress_archive()'s RaggedArchives, one per coder
@@ -687,7 +738,7 @@ class RaggedNet(_lib.Handle):
         self._last_roi = None
 
     def shapes(self, layer: int):
-        """[(H, W, C)] of every image at boundary `layer`."""
+        """[(H, W, C)] of every image at boundary `layer`; [(3, H, W)] at a planar one."""
         return list(self._shapes[layer + 1])
 
     def nbytes(self, layer: int) -> int:
@@ -695,14 +746,15 @@ class RaggedNet(_lib.Handle):
 
     def kernel_for(self, layer: int) -> str:
         """The kernel `layer` runs on (sicn_ragged_net_kernel_for): "mfma_conv_any", "mfma_deconv_any", "mfma_conv_rgb_packed" or
-        "mfma_deconv_rgb_packed"."""
+        "mfma_deconv_rgb_packed"; "mfma_conv_rgb_planar" and "mfma_deconv_rgb_planar" at a planar boundary."""
         name = _lib.lib().sicn_ragged_net_kernel_for(self._h, int(layer))
         if name is None:
             raise ValueError("layer out of range")
         return name.decode()
 
     def pack(self, images, layer: int = -1):
-        """[H][W][C] uint8 tensors (any device), one per image -> the ragged tensor of boundary `layer` on the net's device."""
+        """[H][W][C] uint8 tensors (any device; [3][H][W] at a planar boundary), one per image -> the ragged tensor of boundary
+        `layer` on the net's device."""
         import torch
         shapes = self._shapes[layer + 1]
         if len(images) != len(shapes):
@@ -715,9 +767,10 @@ class RaggedNet(_lib.Handle):
         return packed
 
     def views(self, layer: int, packed):
-        """Per-image [H][W][C] views of a ragged tensor of boundary `layer` (no copy; each one is contiguous)."""
+        """Per-image [H][W][C] views of a ragged tensor of boundary `layer` ([3][H][W] at a planar one; no copy; each one is
+        contiguous)."""
         _check_tensor(packed, (self.nbytes(layer),), "packed")
-        return [packed[o:o + h * w * c].view(h, w, c) for o, (h, w, c) in zip(self._offsets[layer + 1], self._shapes[layer + 1])]
+        return [packed[o:o + a * b * c].view(a, b, c) for o, (a, b, c) in zip(self._offsets[layer + 1], self._shapes[layer + 1])]
 
     def workspace(self):
         import torch
@@ -758,15 +811,25 @@ class RaggedNet(_lib.Handle):
     def cropped(self, out, dst=None, stream=None):
         """The chain's last output (boundary n - 1, every size rounded up by the chain rule: 112 x 48 for a 100 x 36 image) cut to the
         images' own sizes: a ragged tensor laid out as boundary -1 with the output's channels.  One launch.  Needs a chain that
-        ends no smaller than it began (the eight layers do)."""
+        ends no smaller than it began (the eight layers do).  A planar output that already has the images' sizes is returned as it
+        is; one of other sizes is a ValueError (make the net with out_sizes=None)."""
         last = len(self.descs) - 1
+        if self.planar_out:
+            if [(w, h) for _, h, w in self.shapes(last)] != self.sizes:
+                raise ValueError("the planar output has sizes of its own (out_sizes), not the images': there is no planar crop")
+            if dst is not None:
+                raise ValueError("dst: the planar output already has the images' sizes and is returned as it is; nothing is copied")
+            _check_tensor(out, (self.nbytes(last),), "out")
+            return out
         if self._crop is None:
             self._crop = RaggedCrop([(h, w) for h, w, _ in self.shapes(last)], [(h, w) for w, h in self.sizes],
                                     self.shapes(last)[0][2], device=self.device)
         return self._crop.run(out, dst, stream=stream)
 
     def crop_views(self, cropped):
-        """Per-image [height][width][C] views of what `cropped` returned."""
+        """Per-image [height][width][C] views of what `cropped` returned ([3][height][width] of a planar output)."""
+        if self.planar_out:
+            return self.views(len(self.descs) - 1, cropped)
         if self._crop is None:
             raise ValueError("cropped() has not run")
         return self._crop.views(cropped)
@@ -778,11 +841,15 @@ class RaggedNet(_lib.Handle):
         return self._last_roi.views(roi_pixels)
 
     def moving_roi(self, slots, coder=None, stream_symbols=16384):
-        """A MovingRoi over this net: `slots` = (image, w, h) per slot, positions given per `decode` call, from device memory."""
+        """A MovingRoi over this net: `slots` = (image, w, h) per slot, positions given per `decode` call, from device memory.
+        ValueError for a net with planar pixels."""
         return MovingRoi(self, slots, coder=coder, stream_symbols=stream_symbols)
 
     def latent_coder(self, stream_symbols=None):
-        """A codec.RaggedLatentCoder for this net's latents (boundary 3) and image sizes: the whole batch in 3 + 2 launches."""
+        """A codec.RaggedLatentCoder for this net's latents (boundary 3) and image sizes: the whole batch in 3 + 2 launches.
+        ValueError where boundary 3 is a planar pixel boundary and no latent."""
+        if self.planar_out and len(self.descs) == 4:
+            raise ValueError("boundary 3 of this chain is its planar RGB output, not a latent")
         from . import codec
         return codec.RaggedLatentCoder([(h, w) for h, w, _ in self.shapes(3)], self.shapes(3)[0][2], self.sizes,
                                        stream_symbols=stream_symbols, device=self.device)
@@ -874,6 +941,7 @@ class RaggedNet(_lib.Handle):
         from . import codec
         info = codec.archive_info(b)
         if rois is not None:
+            _refuse_planar(self, "decompress_archive(rois=)")
             if len(rois) != len(self.sizes):
                 raise ValueError(f"rois: one rectangle (or None) per decoded image, {len(self.sizes)}")
             rois = tuple(None if r is None else tuple(int(v) for v in r) for r in rois)

@@ -15,15 +15,20 @@
 // A layer with a GDN / IGDN (sicn_ragged_net_create_gdn) runs the same kernel with ACT_FLOOR_RAW and then the activation of k_gdn.hip in
 // place over the whole boundary tensor: [bytes / OFM_CH][OFM_CH], no table needed.  The ragged crop at the end of this file is the cut
 // of k_ragged_window.hip at the corner of every image: the rectangles (0, 0, dst_w, dst_h), the images back to back, the same handle.
+//
+// A net with PLANAR pixels (include/sicn_ragged_planar.h) runs the planar siblings of the packed RGB kernels at the boundary that is
+// planar; a planar output has sizes of its own (planar_out_plan), which reach the kernel through the PlanarOut table.
 #include <new>
 #include <vector>
 
 #include "../../include/sicn_ragged_hyper.h"
+#include "../../include/sicn_ragged_planar.h"
 #include "../../include/sicn_ragged_rgb.h"
 #include "../../include/sicn_ragged_window.h"
 #include "device_table.hpp"
 #include "k_any_body.hpp"
 #include "k_ragged_common.hpp"
+#include "ragged_planar_host.hpp"
 #include "ragged_rgb_host.hpp"
 #include "sicn_gdn_internal.h"
 
@@ -130,6 +135,31 @@ static int ragged_plan(const sicn_layer_desc *descs, int n_layers, const int32_t
     return SICN_OK;
 }
 
+// The output boundary as a net with `pixels_out` lays it out: per image its size and byte offset, and the tensor's bytes.
+// INTERLEAVED: the chain-rule sizes, the plan's offsets; sizes of the caller's are refused.  PLANAR: ow x oh (both NULL: the
+// chain-rule sizes), each within [1, chain-rule size], three planes per image back to back; the last layer must be a deconv N -> 3.
+static int planar_out_plan(const RaggedPlan &plan, const sicn_layer_desc *descs, int n_layers, int n_images, int pixels_out,
+                           const int32_t *ow, const int32_t *oh, std::vector<PlanarOut> *cuts, int64_t *bytes)
+{
+    if (pixels_out != SICN_RAGGED_PIXELS_INTERLEAVED && pixels_out != SICN_RAGGED_PIXELS_PLANAR) return SICN_EINVAL;
+    if ((ow == nullptr) != (oh == nullptr)) return SICN_EINVAL;
+    const bool planar = pixels_out == SICN_RAGGED_PIXELS_PLANAR;
+    if (!planar && ow) return SICN_EINVAL;
+    const sicn_layer_desc &d = descs[n_layers - 1];
+    if (planar && !(d.transposed == 1 && d.OFM_CH == 3)) return SICN_EINVAL;
+    const RaggedBoundary &b = plan.bounds[(size_t)n_layers];
+    cuts->resize((size_t)n_images);
+    int64_t off = 0;
+    for (int i = 0; i < n_images; i++) {
+        const int32_t w = ow ? ow[i] : b.W[(size_t)i], h = oh ? oh[i] : b.H[(size_t)i];
+        if (w < 1 || h < 1 || w > b.W[(size_t)i] || h > b.H[(size_t)i]) return SICN_EINVAL;
+        (*cuts)[(size_t)i] = PlanarOut{w, h, off};
+        off += (int64_t)h * w * b.C;
+    }
+    *bytes = off;
+    return SICN_OK;
+}
+
 template <bool DECONV, int NT>
 static hipError_t launch_ragged_as(const uint8_t *in, uint8_t *out, const int8_t *wimg, const int8_t *bias, const RaggedRow *rows,
                                    const uint32_t *tile_image, int cin, int cout, unsigned items, uint32_t floor2, hipStream_t stream)
@@ -161,6 +191,9 @@ struct sicn_ragged_net {
     DeviceTable<uint32_t> d_tile_image;     // the layers' tile -> image maps back to back
     std::vector<size_t> map_at;             // per layer: its first entry in d_tile_image
     size_t slot = 0;                        // bytes of one ping-pong buffer
+    bool planar_in = false, planar_out = false;   // include/sicn_ragged_planar.h: the pixel layout of boundary -1 and of boundary n - 1
+    int64_t out_bytes = 0;                  // bytes of boundary n - 1 as this net lays it out
+    DeviceTable<PlanarOut> d_cuts;          // planar out: [n_images] the sizes and offsets of the output
 };
 
 extern "C" int sicn_ragged_layout(const sicn_layer_desc *descs, int n_layers, const int32_t *widths, const int32_t *heights, int n_images,
@@ -218,6 +251,8 @@ extern "C" const char *sicn_ragged_net_kernel_for(const sicn_ragged_net *net, in
 {
     if (!net || layer < 0 || layer >= net->n_layers) return nullptr;
     const bool tr = net->descs[(size_t)layer].transposed == 1;
+    if (layer == 0 && net->planar_in) return "mfma_conv_rgb_planar";
+    if (layer == net->n_layers - 1 && net->planar_out) return "mfma_deconv_rgb_planar";
     if (net->plan.layers[(size_t)layer].packed) return tr ? "mfma_deconv_rgb_packed" : "mfma_conv_rgb_packed";
     return tr ? "mfma_deconv_any" : "mfma_conv_any";
 }
@@ -225,11 +260,51 @@ extern "C" const char *sicn_ragged_net_kernel_for(const sicn_ragged_net *net, in
 extern "C" int sicn_ragged_net_create_rgb(const sicn_layer_desc *descs, sicn_weights *const *weights, const sicn_gdn *const *gdn, int n_layers,
                                           const int32_t *widths, const int32_t *heights, int n_images, int rgb_ends, sicn_ragged_net **out)
 {
+    return sicn_ragged_net_create_planar(descs, weights, gdn, n_layers, widths, heights, n_images, rgb_ends, SICN_RAGGED_PIXELS_INTERLEAVED,
+                                         SICN_RAGGED_PIXELS_INTERLEAVED, nullptr, nullptr, out);
+}
+
+extern "C" int sicn_ragged_planar_layout(const sicn_layer_desc *descs, int n_layers, const int32_t *widths, const int32_t *heights,
+                                         int n_images, int pixels_out, const int32_t *out_widths, const int32_t *out_heights, int image,
+                                         int64_t out[6])
+{
+    if (!out) return SICN_EINVAL;
+    RaggedPlan p;
+    if (int rc = ragged_plan(descs, n_layers, widths, heights, n_images, SICN_RAGGED_RGB_PACKED, &p)) return rc;
+    std::vector<PlanarOut> cuts;
+    int64_t bytes = 0;
+    try {
+        if (int rc = planar_out_plan(p, descs, n_layers, n_images, pixels_out, out_widths, out_heights, &cuts, &bytes)) return rc;
+    } catch (const std::bad_alloc &) { return SICN_ENOMEM; }
+    if (image < 0 || image >= n_images) return SICN_EINVAL;
+    out[0] = cuts[(size_t)image].w;
+    out[1] = cuts[(size_t)image].h;
+    out[2] = cuts[(size_t)image].off;
+    out[3] = bytes;
+    out[4] = p.bounds[0].off[(size_t)image];
+    out[5] = p.bounds[0].off[(size_t)n_images];
+    return SICN_OK;
+}
+
+extern "C" int sicn_ragged_net_create_planar(const sicn_layer_desc *descs, sicn_weights *const *weights, const sicn_gdn *const *gdn,
+                                             int n_layers, const int32_t *widths, const int32_t *heights, int n_images, int rgb_ends,
+                                             int pixels_in, int pixels_out, const int32_t *out_widths, const int32_t *out_heights,
+                                             sicn_ragged_net **out)
+{
     if (!out) return SICN_EINVAL;
     *out = nullptr;
     if (!weights) return SICN_EINVAL;
     return make_object(out, [&](sicn_ragged_net &net) {
         if (int rc = ragged_plan(descs, n_layers, widths, heights, n_images, rgb_ends, &net.plan)) return rc;
+        // the pixel layouts: a planar end is the packed-K kernel of that end with another loader or epilogue, nothing else
+        if (pixels_in != SICN_RAGGED_PIXELS_INTERLEAVED && pixels_in != SICN_RAGGED_PIXELS_PLANAR) return SICN_EINVAL;
+        net.planar_in = pixels_in == SICN_RAGGED_PIXELS_PLANAR;
+        std::vector<PlanarOut> cuts;
+        if (int rc = planar_out_plan(net.plan, descs, n_layers, n_images, pixels_out, out_widths, out_heights, &cuts, &net.out_bytes)) return rc;
+        net.planar_out = pixels_out == SICN_RAGGED_PIXELS_PLANAR;
+        if ((net.planar_in || net.planar_out) && rgb_ends != SICN_RAGGED_RGB_PACKED) return SICN_EINVAL;
+        if (net.planar_in && !(descs[0].transposed == 0 && descs[0].IFM_CH == 3)) return SICN_EINVAL;
+        if (net.planar_out && gdn && gdn[n_layers - 1]) return SICN_EINVAL;
         for (int l = 0; l < n_layers; l++) {
             const sicn_weights *w = weights[l];
             if (!w || w->cin != descs[l].IFM_CH || w->cout != descs[l].OFM_CH || w->transposed != descs[l].transposed) return SICN_EINVAL;
@@ -260,6 +335,7 @@ extern "C" int sicn_ragged_net_create_rgb(const sicn_layer_desc *descs, sicn_wei
         }
         net.slot = (mx + 255) / 256 * 256;
         if (!net.d_rows.upload(rows) || !map.upload(net.d_tile_image)) return SICN_ENOMEM;
+        if (net.planar_out && !net.d_cuts.upload(cuts)) return SICN_ENOMEM;
         // the weight image: weights of a width the specialised families serve were uploaded without one (sicn_weights_from_finn_tiles
         // packs the images of the family the shape runs on); pack it here from the plain [cout][25 cin] copy every handle has
         for (int l = 0; l < n_layers; l++) {
@@ -311,12 +387,17 @@ extern "C" int sicn_ragged_net_forward(const sicn_ragged_net *net, int first, in
         const int8_t *wimg = net->wimg[(size_t)l];
         const sicn_gdn *g = net->gdn[(size_t)l];
         const uint32_t floor2 = g ? ACT_FLOOR_RAW : ACT_FLOOR_RELU;
-        const size_t out_bytes = (size_t)net->plan.bounds[(size_t)l + 1].off[(size_t)net->n_images];
+        const bool planar_out = net->planar_out && l == net->n_layers - 1;
+        const size_t in_bytes = (size_t)net->plan.bounds[(size_t)l].off[(size_t)net->n_images];
+        const size_t out_bytes = planar_out ? (size_t)net->out_bytes : (size_t)net->plan.bounds[(size_t)l + 1].off[(size_t)net->n_images];
         hipError_t e;
-        if (net->plan.layers[(size_t)l].packed)
+        if (net->planar_in && l == 0)
+            e = launch_ragged_rgb_conv_planar(cur, in_bytes, dst, wimg, w->d_bias, rows, map, d.OFM_CH, items, floor2, stream);
+        else if (planar_out)
+            e = launch_ragged_rgb_deconv_planar(cur, dst, wimg, w->d_bias, rows, map, net->d_cuts.get(), d.IFM_CH, items, floor2, stream);
+        else if (net->plan.layers[(size_t)l].packed)
             e = d.transposed ? launch_ragged_rgb_deconv(cur, dst, wimg, w->d_bias, rows, map, d.IFM_CH, items, floor2, stream)
-                             : launch_ragged_rgb_conv(cur, (size_t)net->plan.bounds[(size_t)l].off[(size_t)net->n_images], dst, wimg,
-                                                      w->d_bias, rows, map, d.OFM_CH, items, floor2, stream);
+                             : launch_ragged_rgb_conv(cur, in_bytes, dst, wimg, w->d_bias, rows, map, d.OFM_CH, items, floor2, stream);
         else if (d.transposed)
             e = d.OFM_CH == 3 ? launch_ragged_as<true, 1>(cur, dst, wimg, w->d_bias, rows, map, d.IFM_CH, d.OFM_CH, items, floor2, stream)
                               : launch_ragged_as<true, 4>(cur, dst, wimg, w->d_bias, rows, map, d.IFM_CH, d.OFM_CH, items, floor2, stream);

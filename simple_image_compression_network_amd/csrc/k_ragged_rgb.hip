@@ -7,6 +7,9 @@
 // first_item as the channel-generic form; y = 1 — the blocks of 64 output channels are a loop inside the workgroup (the kernel
 // strides them by gridDim.y), so the patch and its expansion are paid once per tile.  Deconv: one 16 x 16 tile of input positions
 // with all four phases: tile_image is indexed by the item itself and first_item is the per-tile cut's.
+//
+// k_rgb_conv_ragged_planar and k_rgb_deconv_ragged_planar (include/sicn_ragged_planar.h) are the same two kernels at a planar
+// boundary: the same grids and tables, the conv with planar_quad as its loader, the deconv with the cut epilogue.
 #include "k_ragged_common.hpp"
 #include "k_rgb_ragged_body.hpp"
 
@@ -53,7 +56,33 @@ __global__ __launch_bounds__(256) void k_rgb_deconv_ragged(const uint8_t *__rest
 {
     __shared__ __attribute__((aligned(16))) uint8_t smem[RGBD_LDS];
     const RaggedItem r = ragged_item(rows, tile_image);
-    rgb_deconv_tile(in + r.in_off, out + r.out_off, wimg, bias, r.IW, r.IH, C, r.OW, r.ty * ANY_T, r.tx * ANY_T, floor2, smem);
+    rgb_deconv_tile<false>(in + r.in_off, out + r.out_off, wimg, bias, r.IW, r.IH, C, r.OW, r.OH, r.ty * ANY_T, r.tx * ANY_T, floor2, smem);
+}
+
+// The planar siblings (include/sicn_ragged_planar.h): `in` holds the images as [3][IH][IW] planes at the same offsets, `out` as
+// [3][h][w] planes cut to the sizes and placed at the offsets of `cuts` — a table of its own, RaggedRow keeps its layout.
+__global__ __launch_bounds__(256) void k_rgb_conv_ragged_planar(const uint8_t *__restrict__ in, uint64_t in_bytes, uint8_t *__restrict__ out,
+                                                                const int8_t *__restrict__ wimg, const int8_t *__restrict__ bias,
+                                                                const RaggedRow *__restrict__ rows, const uint32_t *__restrict__ tile_image,
+                                                                int O, uint32_t floor2)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t smem[RGBC_LDS];
+    const RaggedItem r = ragged_item(rows, tile_image);
+    rgb_conv_tile_planar(in + r.in_off, in, in + in_bytes, out + r.out_off, wimg, bias, r.IW, r.IH, r.OW, r.OH, O, r.ty * ANY_T,
+                         r.tx * ANY_T, (int)blockIdx.y, (int)gridDim.y, floor2, smem);
+}
+
+__global__ __launch_bounds__(256) void k_rgb_deconv_ragged_planar(const uint8_t *__restrict__ in, uint8_t *__restrict__ out,
+                                                                  const int8_t *__restrict__ wimg, const int8_t *__restrict__ bias,
+                                                                  const RaggedRow *__restrict__ rows, const uint32_t *__restrict__ tile_image,
+                                                                  const PlanarOut *__restrict__ cuts, int C, uint32_t floor2)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t smem[RGBD_LDS];
+    const RaggedItem r = ragged_item(rows, tile_image);
+    const PlanarOut *cut = cuts + uni(tile_image[(int)blockIdx.x]);
+    const int w = (int)uni((uint32_t)cut->w), h = (int)uni((uint32_t)cut->h);
+    rgb_deconv_tile<true>(in + r.in_off, out + uni((uint64_t)cut->off), wimg, bias, r.IW, r.IH, C, w, h, r.ty * ANY_T, r.tx * ANY_T, floor2,
+                          smem);
 }
 
 bool ragged_rgb_packed_serves(int cin, int cout, int transposed)
@@ -75,6 +104,24 @@ hipError_t launch_ragged_rgb_deconv(const uint8_t *in, uint8_t *out, const int8_
                                     const uint32_t *tile_image, int cin, unsigned items, uint32_t floor2, hipStream_t stream)
 {
     hipLaunchKernelGGL(k_rgb_deconv_ragged, dim3(items, 1, 1), dim3(256), 0, stream, in, out, wimg, bias, rows, tile_image, cin, floor2);
+    return hipGetLastError();
+}
+
+hipError_t launch_ragged_rgb_conv_planar(const uint8_t *in, size_t in_bytes, uint8_t *out, const int8_t *wimg, const int8_t *bias,
+                                         const RaggedRow *rows, const uint32_t *tile_image, int cout, unsigned items, uint32_t floor2,
+                                         hipStream_t stream)
+{
+    hipLaunchKernelGGL(k_rgb_conv_ragged_planar, dim3(items, 1, 1), dim3(256), 0, stream, in, (uint64_t)in_bytes, out, wimg, bias, rows,
+                       tile_image, cout, floor2);
+    return hipGetLastError();
+}
+
+hipError_t launch_ragged_rgb_deconv_planar(const uint8_t *in, uint8_t *out, const int8_t *wimg, const int8_t *bias, const RaggedRow *rows,
+                                           const uint32_t *tile_image, const PlanarOut *cuts, int cin, unsigned items, uint32_t floor2,
+                                           hipStream_t stream)
+{
+    hipLaunchKernelGGL(k_rgb_deconv_ragged_planar, dim3(items, 1, 1), dim3(256), 0, stream, in, out, wimg, bias, rows, tile_image, cuts, cin,
+                       floor2);
     return hipGetLastError();
 }
 

@@ -15,8 +15,13 @@
 // any_tile stages it; nine tap offsets; lane (col, g) of the C/D layout then holds the three channels of phase g at position col
 // and stores 3 bytes to output pixel (2 my + (g >> 1), 2 mx + (g & 1)).  Byte stores only: the neighbouring pixels belong to other
 // lanes, tiles and images.
+//
+// Both have a PLANAR sibling (include/sicn_ragged_planar.h; k_rgb_conv_ragged_planar and k_rgb_deconv_ragged_planar of
+// k_ragged_rgb.hip): the conv with another loader in front of the same rgb_conv_mma, the deconv with another epilogue
+// (rgb_deconv_tile<true>).
 #pragma once
 #include "k_any_body.hpp"
+#include "ragged_planar_host.hpp"
 #include "ragged_rgb_host.hpp"
 
 namespace sicn {
@@ -28,45 +33,14 @@ constexpr int RGBC_QUADS = RGBC_ROWS * (RGBC_PX / 4);
 constexpr int RGBC_LDS = RGBC_ROWS * RGBC_PITCH;     // 5760 bytes
 constexpr int RGBD_LDS = ANY_DECONV_EDGE * ANY_DECONV_EDGE * 64;   // 20736 bytes
 
-// im / om: the image's own [IH][IW][3] input and [OH][OW][O] output; [t0, t1): the whole input tensor; (y0, x0): the tile's origin in
-// output positions; blocks J0, J0 + Jstep, ... of 64 output channels; smem: RGBC_LDS bytes, 16-byte aligned
-__device__ __forceinline__ void rgb_conv_tile(const uint8_t *__restrict__ im, const uint8_t *t0, const uint8_t *t1, uint8_t *__restrict__ om,
-                                              const int8_t *__restrict__ wimg, const int8_t *__restrict__ bias, int IW, int IH, int OW,
-                                              int OH, int O, int y0, int x0, int J0, int Jstep, uint32_t floor2, uint8_t *smem)
+// Everything behind the patch, which every wave sees in smem (RGBC_LDS bytes of RGBX dwords): the B fragments, the three K steps, the
+// loop over the blocks J0, J0 + Jstep, ... of 64 output channels and the epilogue.  om: the image's own [OH][OW][O] output.
+__device__ __forceinline__ void rgb_conv_mma(uint8_t *__restrict__ om, const int8_t *__restrict__ wimg, const int8_t *__restrict__ bias,
+                                             int OW, int OH, int O, int y0, int x0, int J0, int Jstep, uint32_t floor2,
+                                             const uint8_t *smem)
 {
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int col = lane & 15, g = lane >> 4;
-
-    // ---- the patch: a quad = 4 pixels of one patch row = 12 bytes from byte phase sh of four aligned dwords
-    const uintptr_t lo = (uintptr_t)t0, hi = (uintptr_t)t1;
-#pragma unroll
-    for (int q0 = 0; q0 < RGBC_QUADS; q0 += 256) {
-        const int q = q0 + tid;
-        if (q >= RGBC_QUADS) break;
-        const int r = q / (RGBC_PX / 4), gq = q - r * (RGBC_PX / 4);
-        const int iy = 2 * y0 - 2 + r, ix = 2 * x0 - 2 + 4 * gq;
-        uint4 v = uint4{0u, 0u, 0u, 0u};
-        if (iy >= 0 && iy < IH && ix + 3 >= 0 && ix < IW) {
-            const uint8_t *p = im + ((int64_t)iy * IW + ix) * 3;                        // ix < 0: up to 6 bytes before the row
-            const uint32_t sh = (uint32_t)(uintptr_t)p & 3u;
-            const uint8_t *p0 = p - sh;
-            uint32_t d[4];
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                const uintptr_t A = (uintptr_t)(p0 + 4 * k);
-                d[k] = (A + 4 > lo && A < hi) ? *reinterpret_cast<const uint32_t *>(p0 + 4 * k) : 0u;
-            }
-            const uint32_t w0 = __builtin_amdgcn_alignbyte(d[1], d[0], sh);
-            const uint32_t w1 = __builtin_amdgcn_alignbyte(d[2], d[1], sh);
-            const uint32_t w2 = __builtin_amdgcn_alignbyte(d[3], d[2], sh);
-            v.x = (ix + 0 >= 0 && ix + 0 < IW) ? (w0 & 0xFFFFFFu) : 0u;
-            v.y = (ix + 1 >= 0 && ix + 1 < IW) ? (__builtin_amdgcn_alignbyte(w1, w0, 3) & 0xFFFFFFu) : 0u;
-            v.z = (ix + 2 >= 0 && ix + 2 < IW) ? (__builtin_amdgcn_alignbyte(w2, w1, 2) & 0xFFFFFFu) : 0u;
-            v.w = (ix + 3 >= 0 && ix + 3 < IW) ? (w2 >> 8) : 0u;
-        }
-        *reinterpret_cast<uint4 *>(smem + q * 16) = v;
-    }
-    __syncthreads();
 
     // ---- the B fragments of the wave's four rows, all three K steps: read once, used for every block of channels
     v4i bf[RGB_CONV_KSTEPS][4];
@@ -119,10 +93,76 @@ __device__ __forceinline__ void rgb_conv_tile(const uint8_t *__restrict__ im, co
     }
 }
 
+// im / om: the image's own [IH][IW][3] input and [OH][OW][O] output; [t0, t1): the whole input tensor; (y0, x0): the tile's origin in
+// output positions; blocks J0, J0 + Jstep, ... of 64 output channels; smem: RGBC_LDS bytes, 16-byte aligned
+__device__ __forceinline__ void rgb_conv_tile(const uint8_t *__restrict__ im, const uint8_t *t0, const uint8_t *t1, uint8_t *__restrict__ om,
+                                              const int8_t *__restrict__ wimg, const int8_t *__restrict__ bias, int IW, int IH, int OW,
+                                              int OH, int O, int y0, int x0, int J0, int Jstep, uint32_t floor2, uint8_t *smem)
+{
+    const int tid = threadIdx.x;
+
+    // ---- the patch: a quad = 4 pixels of one patch row = 12 bytes from byte phase sh of four aligned dwords
+    const uintptr_t lo = (uintptr_t)t0, hi = (uintptr_t)t1;
+#pragma unroll
+    for (int q0 = 0; q0 < RGBC_QUADS; q0 += 256) {
+        const int q = q0 + tid;
+        if (q >= RGBC_QUADS) break;
+        const int r = q / (RGBC_PX / 4), gq = q - r * (RGBC_PX / 4);
+        const int iy = 2 * y0 - 2 + r, ix = 2 * x0 - 2 + 4 * gq;
+        uint4 v = uint4{0u, 0u, 0u, 0u};
+        if (iy >= 0 && iy < IH && ix + 3 >= 0 && ix < IW) {
+            const uint8_t *p = im + ((int64_t)iy * IW + ix) * 3;                        // ix < 0: up to 6 bytes before the row
+            const uint32_t sh = (uint32_t)(uintptr_t)p & 3u;
+            const uint8_t *p0 = p - sh;
+            uint32_t d[4];
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const uintptr_t A = (uintptr_t)(p0 + 4 * k);
+                d[k] = (A + 4 > lo && A < hi) ? *reinterpret_cast<const uint32_t *>(p0 + 4 * k) : 0u;
+            }
+            const uint32_t w0 = __builtin_amdgcn_alignbyte(d[1], d[0], sh);
+            const uint32_t w1 = __builtin_amdgcn_alignbyte(d[2], d[1], sh);
+            const uint32_t w2 = __builtin_amdgcn_alignbyte(d[3], d[2], sh);
+            v.x = (ix + 0 >= 0 && ix + 0 < IW) ? (w0 & 0xFFFFFFu) : 0u;
+            v.y = (ix + 1 >= 0 && ix + 1 < IW) ? (__builtin_amdgcn_alignbyte(w1, w0, 3) & 0xFFFFFFu) : 0u;
+            v.z = (ix + 2 >= 0 && ix + 2 < IW) ? (__builtin_amdgcn_alignbyte(w2, w1, 2) & 0xFFFFFFu) : 0u;
+            v.w = (ix + 3 >= 0 && ix + 3 < IW) ? (w2 >> 8) : 0u;
+        }
+        *reinterpret_cast<uint4 *>(smem + q * 16) = v;
+    }
+    __syncthreads();
+    rgb_conv_mma(om, wimg, bias, OW, OH, O, y0, x0, J0, Jstep, floor2, smem);
+}
+
+// rgb_conv_tile over a PLANAR image: im = its three planes [3][IH][IW].  Only the loader differs (planar_quad, ragged_planar_host.hpp).
+__device__ __forceinline__ void rgb_conv_tile_planar(const uint8_t *__restrict__ im, const uint8_t *t0, const uint8_t *t1,
+                                                     uint8_t *__restrict__ om, const int8_t *__restrict__ wimg,
+                                                     const int8_t *__restrict__ bias, int IW, int IH, int OW, int OH, int O, int y0, int x0,
+                                                     int J0, int Jstep, uint32_t floor2, uint8_t *smem)
+{
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int q0 = 0; q0 < RGBC_QUADS; q0 += 256) {
+        const int q = q0 + tid;
+        if (q >= RGBC_QUADS) break;
+        const int r = q / (RGBC_PX / 4), gq = q - r * (RGBC_PX / 4);
+        const PlanarQuad v = planar_quad((uintptr_t)im, IW, IH, 2 * y0 - 2 + r, 2 * x0 - 2 + 4 * gq, (uintptr_t)t0, (uintptr_t)t1,
+                                         [](uintptr_t a) { return *reinterpret_cast<const uint32_t *>(a); });
+        *reinterpret_cast<uint4 *>(smem + q * 16) = uint4{v.px[0], v.px[1], v.px[2], v.px[3]};
+    }
+    __syncthreads();
+    rgb_conv_mma(om, wimg, bias, OW, OH, O, y0, x0, J0, Jstep, floor2, smem);
+}
+
 // im / om: the image's own [IH][IW][C] input and [2 IH][OW = 2 IW][3] output; (y0, x0): the tile's origin in input positions;
-// smem: RGBD_LDS bytes, 16-byte aligned
+// smem: RGBD_LDS bytes, 16-byte aligned.  OH is not read.
+// PLANAR: om = the image's planes [3][OH][OW] cut to 1 <= OW <= 2 IW, 1 <= OH <= 2 IH (include/sicn_ragged_planar.h).  Only the
+// epilogue differs: the lane stores one byte into each plane where its pixel lies inside the cut; the pixels outside are computed
+// and not stored.  Across the 16 lanes of a row group the bytes of a plane are 2 apart and the phase g & 1 fills the gaps: 32
+// consecutive bytes per plane.
+template <bool PLANAR>
 __device__ __forceinline__ void rgb_deconv_tile(const uint8_t *__restrict__ im, uint8_t *__restrict__ om, const int8_t *__restrict__ wimg,
-                                                const int8_t *__restrict__ bias, int IW, int IH, int C, int OW, int y0, int x0,
+                                                const int8_t *__restrict__ bias, int IW, int IH, int C, int OW, int OH, int y0, int x0,
                                                 uint32_t floor2, uint8_t *smem)
 {
     constexpr int EDGE = ANY_DECONV_EDGE;
@@ -184,12 +224,21 @@ __device__ __forceinline__ void rgb_deconv_tile(const uint8_t *__restrict__ im, 
 #pragma unroll
     for (int c = 0; c < 4; c++) {
         const int my = y0 + 4 * wv + c, mx = x0 + col;
-        if (my >= IH || mx >= IW) continue;
-        const uint32_t q = pack4_relu7(acc[c][0], acc[c][1], acc[c][2], acc[c][3], floor2);
-        uint8_t *op = om + ((size_t)(2 * my + (g >> 1)) * OW + (2 * mx + (g & 1))) * 3;
-        op[0] = (uint8_t)q;
-        op[1] = (uint8_t)(q >> 8);
-        op[2] = (uint8_t)(q >> 16);
+        if constexpr (PLANAR) {
+            const int oy = 2 * my + (g >> 1), ox = 2 * mx + (g & 1);
+            if (!planar_stored(oy, ox, OW, OH)) continue;
+            const uint32_t q = pack4_relu7(acc[c][0], acc[c][1], acc[c][2], acc[c][3], floor2);
+            om[planar_at(0, oy, ox, OW, OH)] = (uint8_t)q;
+            om[planar_at(1, oy, ox, OW, OH)] = (uint8_t)(q >> 8);
+            om[planar_at(2, oy, ox, OW, OH)] = (uint8_t)(q >> 16);
+        } else {
+            if (my >= IH || mx >= IW) continue;
+            const uint32_t q = pack4_relu7(acc[c][0], acc[c][1], acc[c][2], acc[c][3], floor2);
+            uint8_t *op = om + ((size_t)(2 * my + (g >> 1)) * OW + (2 * mx + (g & 1))) * 3;
+            op[0] = (uint8_t)q;
+            op[1] = (uint8_t)(q >> 8);
+            op[2] = (uint8_t)(q >> 16);
+        }
     }
 }
 

@@ -141,6 +141,15 @@ hipError_t launch_ragged_rgb_conv(const uint8_t *in, size_t in_bytes, uint8_t *o
                                   hipStream_t stream);
 hipError_t launch_ragged_rgb_deconv(const uint8_t *in, uint8_t *out, const int8_t *wimg, const int8_t *bias, const RaggedRow *rows,
                                     const uint32_t *tile_image, int cin, unsigned items, uint32_t floor2, hipStream_t stream);
+// their planar siblings (include/sicn_ragged_planar.h): `in` as [3][IH][IW] planes; `out` as [3][h][w] planes at the sizes and
+// offsets of `cuts` (PlanarOut: ragged_planar_host.hpp), one entry per image
+struct PlanarOut;
+hipError_t launch_ragged_rgb_conv_planar(const uint8_t *in, size_t in_bytes, uint8_t *out, const int8_t *wimg, const int8_t *bias,
+                                         const RaggedRow *rows, const uint32_t *tile_image, int cout, unsigned items, uint32_t floor2,
+                                         hipStream_t stream);
+hipError_t launch_ragged_rgb_deconv_planar(const uint8_t *in, uint8_t *out, const int8_t *wimg, const int8_t *bias, const RaggedRow *rows,
+                                           const uint32_t *tile_image, const PlanarOut *cuts, int cin, unsigned items, uint32_t floor2,
+                                           hipStream_t stream);
 
 // k_ragged_codec.hip: a ragged coder as the window decoder (k_ragged_window.hip) sees it — [n_images] CoderRow (k_codec_body.hpp)
 // on the host and on the device, both owned by the coder

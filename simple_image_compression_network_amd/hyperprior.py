@@ -176,10 +176,13 @@ class RaggedHyperpriorCodec:
 
     Image i's containers are `HyperpriorCodec(w_i, h_i, 1, seed)`'s, byte for byte: hyper_parameters draws depend on channel counts
     only, so every image gets that codec's parameters.  Stage tensors (y, z, z_hat, s, y_hat) are ragged tensors; `main.views(3, y)`,
-    `h_a.views(1, z)` give the per-image arrays.  Parity UNPINNED, as everything in this module."""
+    `h_a.views(1, z)` give the per-image arrays.  Parity UNPINNED, as everything in this module.
+    `rgb_layout`: handed to `main` (api.RaggedNet): with "planar", `encode` takes the planar ragged input and `decode` returns the
+    planar reconstructions at the images' sizes; containers and archives are the interleaved codec's bytes; `roi` and `moving_roi`
+    raise ValueError."""
 
     def __init__(self, sizes, seed: int = 0, device="cuda", use_gdn: bool = True, main_params=None, z_stream_symbols=None,
-                 y_stream_symbols=None):
+                 y_stream_symbols=None, rgb_layout: str = "interleaved"):
         import torch
         self.sizes = [(int(w), int(h)) for w, h in sizes]
         if not self.sizes:
@@ -189,7 +192,7 @@ class RaggedHyperpriorCodec:
         self.gdn_np = hp["gdn_np"]
         with torch.cuda.device(self.device):
             gdn = [None if g is None else api.GDN(g[0], g[1], inverse=g[2], shift=g[3]) for g in self.gdn_np]
-        self.main = api.RaggedNet(self.sizes, params=main_params, device=self.device, gdn=gdn if use_gdn else None)
+        self.main = api.RaggedNet(self.sizes, params=main_params, device=self.device, gdn=gdn if use_gdn else None, rgb_layout=rgb_layout)
         self.ha_np, self.hs_np = hp["ha_np"], hp["hs_np"]
         lat = self.main.shapes(3)                                           # [(h, w, 192)]
         self.h_a = api.RaggedNet([(w, h) for h, w, _ in lat], params=list(hp["pa"]), device=self.device, descs=hp["da"])
@@ -264,7 +267,7 @@ class RaggedHyperpriorCodec:
         return b
 
     @classmethod
-    def from_archive(cls, b, seed: int = 0, device="cuda", use_gdn=None, main_params=None, images=None):
+    def from_archive(cls, b, seed: int = 0, device="cuda", use_gdn=None, main_params=None, images=None, rgb_layout: str = "interleaved"):
         """The codec for the images an archive names — all of them, or the selection `images` (strictly ascending indices into the
         archive): sizes and the z stream lengths are READ from the z containers' headers, the y stream lengths from the y containers', and `use_gdn` (unless given) from the tag —
         0 means an archive written without GDN.  `decode(archive=b, images=images)` then reads it."""
@@ -275,7 +278,8 @@ class RaggedHyperpriorCodec:
             raise ValueError("not a hyperprior archive: need the sections z and y of every image")
         return cls([info["image_sizes"][i] for i in sel], seed=seed, device=device, use_gdn=info["tag"] != 0 if use_gdn is None else use_gdn,
                    main_params=main_params, z_stream_symbols=[int(h.stream_symbols) for h in heads],
-                   y_stream_symbols=[int(h[1].stream_symbols) if h[1] is not None else None for h in (info["headers"][i] for i in sel)])
+                   y_stream_symbols=[int(h[1].stream_symbols) if h[1] is not None else None for h in (info["headers"][i] for i in sel)],
+                   rgb_layout=rgb_layout)
 
     def _decode_scales(self, z_containers=None, y_containers=None, archive=None, images=None):
         """The front half of every decode, in full: unpack (with an archive), the z coder, h_s and its crop -> self.s.  Returns the y
@@ -310,7 +314,8 @@ class RaggedHyperpriorCodec:
 
     def decode(self, out=None, z_containers=None, y_containers=None, archive=None, images=None, rois=None):
         """Containers (default: the last encode's; else lists of `bytes`, one per image; or `archive`, what `archive()` returned) ->
-        the reconstructions, a ragged tensor of main's boundary 7 (`main.cropped(out)` cuts them to the images' sizes).  An archive is
+        the reconstructions, a ragged tensor of main's boundary 7 (`main.cropped(out)` cuts them to the images' sizes; a planar main
+        writes them at those sizes).  An archive is
         unpacked on the device into the coders' own slots; one whose tag is not this codec's (another GDN specification version, or
         the other `use_gdn`) is refused as a whole: `check()` raises with bit 5.  Enqueue only.
         `images` (with `archive` only): the archive may hold more images than this codec; a strictly ascending sequence of
@@ -382,6 +387,7 @@ class RaggedHyperpriorRoi:
     call, `codec.decode(..., rois=rects)`."""
 
     def __init__(self, codec_, rects):
+        api._refuse_planar(codec_.main, "RaggedHyperpriorRoi")
         n = len(codec_.sizes)
         if len(rects) != n:
             raise ValueError(f"rects: one per image, {n}")

@@ -3,7 +3,9 @@
 
 A seeded mix of 64 image sizes, W and H each drawn from {256, 384, 512, 640, 768}, PARAM weights, whole 8-layer net with the latent:
   ragged   one RaggedNet call: 8 launches for the whole mix (the channel-generic MFMA kernels, csrc/k_ragged.hip; --rgb-ends
-           packed | generic: the RGB ends on the packed-K kernels of csrc/k_ragged_rgb.hip or on the channel-generic ones)
+           packed | generic: the RGB ends on the packed-K kernels of csrc/k_ragged_rgb.hip or on the channel-generic ones;
+           --rgb-layout interleaved | planar: the pixels as [h][w][3] or, include/sicn_ragged_planar.h, as [3][h][w] planes with the
+           output written at the images' own sizes)
   loop     (a) one EightLayersNet per distinct size, created before timing, called once per image (the tuned kernels)
   grouped  (b) the same with the images of equal size grouped into one batch per size
   ceiling  the same number of pixels as ONE equal-size batch of 64 on the tuned kernels: what this untuned form is held to
@@ -44,7 +46,7 @@ def per_layer_from_trace(path, calls_hint=None):
         return []
     key = {k.lower(): k for k in rows[0]}
     name, t0, t1 = key["kernel_name"], key["start_timestamp"], key["end_timestamp"]
-    rows = sorted((r for r in rows if any(k in r[name] for k in ("k_any_ragged", "k_rgb_conv_ragged", "k_rgb_deconv_ragged"))),
+    rows = sorted((r for r in rows if any(k in r[name] for k in ("k_any_ragged", "k_rgb_conv_ragged", "k_rgb_deconv_ragged"))),      # also *_planar
                   key=lambda r: int(r[t0]))
     rows = rows[len(rows) % 8:]                       # whole calls only
     out = []
@@ -64,6 +66,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--seconds", type=float, default=0.5)
     ap.add_argument("--rgb-ends", choices=["packed", "generic"], default="packed", help="the form of the ragged net's RGB ends")
+    ap.add_argument("--rgb-layout", choices=["interleaved", "planar"], default="interleaved", help="the pixel layout of the ragged net's RGB boundaries")
     ap.add_argument("--only", choices=["ragged", "loop", "grouped", "ceiling"])
     ap.add_argument("--calls", type=int, default=20)
     ap.add_argument("--kernel-trace", help="a rocprofv3 *_kernel_trace.csv of an `--only ragged` run: print the per-layer table")
@@ -84,8 +87,9 @@ def main():
     weights = [api.DeviceWeights(d, w, b) for d, (w, b) in zip(eight_layer_descs(16, 16), api.load_param_weights())]
 
     # ---- the variants: every buffer is allocated before timing
-    ragged = api.RaggedNet(sizes, shared_weights=weights, rgb_ends=a.rgb_ends)
-    r_in = ragged.pack(images)
+    planar = a.rgb_layout == "planar"
+    ragged = api.RaggedNet(sizes, shared_weights=weights, rgb_ends=a.rgb_ends, rgb_layout=a.rgb_layout)
+    r_in = ragged.pack([x.permute(2, 0, 1) for x in images] if planar else images)
     r_out = torch.empty(ragged.nbytes(7), dtype=torch.uint8, device="cuda")
     r_lat = torch.empty(ragged.nbytes(3), dtype=torch.uint8, device="cuda")
 
@@ -134,11 +138,14 @@ def main():
         fn()
     torch.cuda.synchronize()
     r_outs, r_lats = ragged.views(7, r_out), ragged.views(3, r_lat)
+    if planar:          # [3][h][w] at the image's size: the corner of the chain-rule reconstruction, permuted (these sizes are their own corner)
+        r_outs = [v.permute(1, 2, 0) for v in r_outs]
     equal = True
     for i, s in enumerate(sizes):
         k = groups[s].index(i)
-        equal &= torch.equal(r_outs[i], l_out[i][0]) and torch.equal(r_lats[i], l_lat[i][0])
-        equal &= torch.equal(r_outs[i], g_out[s][k]) and torch.equal(r_lats[i], g_lat[s][k])
+        h, w = r_outs[i].shape[:2]
+        equal &= torch.equal(r_outs[i], l_out[i][0][:h, :w]) and torch.equal(r_lats[i], l_lat[i][0])
+        equal &= torch.equal(r_outs[i], g_out[s][k][:h, :w]) and torch.equal(r_lats[i], g_lat[s][k])
     nonzero = float((r_lat != 0).float().mean())
 
     def timed(fn, reps):
@@ -163,7 +170,8 @@ def main():
 
     lines = []
     counts = {s: len(idx) for s, idx in groups.items()}
-    lines.append(f"tools/ragged_speed.py --seed {a.seed} --images {a.images} --rounds {a.rounds} --seconds {a.seconds} --rgb-ends {a.rgb_ends}")
+    lines.append(f"tools/ragged_speed.py --seed {a.seed} --images {a.images} --rounds {a.rounds} --seconds {a.seconds} --rgb-ends {a.rgb_ends}"
+                 + (f" --rgb-layout {a.rgb_layout}" if planar else ""))
     lines.append("ragged kernels per layer: " + " ".join(ragged.kernel_for(l) for l in range(8)))
     lines.append(f"device: {torch.cuda.get_device_name(0)}; {a.images} images, {len(distinct)} distinct sizes, {pixels / 1e6:.2f} Mpixel in all; PARAM weights")
     lines.append("sizes W x H (count): " + ", ".join(f"{w}x{h} ({counts[(w, h)]})" for w, h in distinct))
@@ -190,7 +198,7 @@ def main():
         for l, kern, us, n in per_layer_from_trace(a.kernel_trace):
             total += us
             items = _items(api, ragged, l)
-            blocks = 1 if "rgb_packed" in ragged.kernel_for(l) else (ragged.descs[l].OFM_CH + 63) // 64
+            blocks = 1 if "_rgb_" in ragged.kernel_for(l) else (ragged.descs[l].OFM_CH + 63) // 64
             lines.append(f"  layer {l}  {us:9.1f} us  {items:7d} work items x {blocks} channel blocks  {kern}  ({n} dispatches)")
         lines.append(f"  sum      {total:9.1f} us of {med['ragged'] * 1e3:.1f} us per call measured above")
     text = "\n".join(lines)

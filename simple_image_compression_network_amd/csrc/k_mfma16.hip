@@ -57,14 +57,14 @@ bool mfma_supported(int cin, int cout, int transposed)
 
 hipError_t launch_mfma16(const LayerGeom &g, const sicn_weights &w, const uint8_t *in, uint8_t *out, int n_images,
                          hipStream_t stream, int in_layout, int out_layout, const sicn_options &o, const ChipGeom &chip, bool relu,
-                         unsigned long long *deal, int columns, int groups_in)
+                         unsigned long long *deal, int columns, int walk_groups)
 {
     if ((size_t)g.IH * g.IW * g.CIN >= (size_t)OOB) return hipErrorInvalidValue;          // 31-bit patch offsets
     if ((size_t)g.OH * g.OW * g.COUT >= (size_t)OOB) return hipErrorInvalidValue;         // buffer-descriptor stores
     if (!mfma_supported(g.CIN, g.COUT, g.transposed)) return hipErrorInvalidValue;
     const MfmaPlan p = plan_mfma(g, n_images, o, chip);
     if (p.family == 2) return launch_wide(g, w, in, out, n_images, stream, in_layout, out_layout, relu, o.persistent_grid, chip, deal, columns,
-                                          groups_in);
+                                          walk_groups);
     if (columns != 8) return hipErrorInvalidValue;   // only the wide family skips columns (sicn_live.h)
     // (round 2 sent the deconv 192 -> 128 on full grids back to a plain, unpipelined kernel: the pipelined one was 7 % slower there.
     // The reason was the v_mov copies hipcc made for its run-time buffer parity — right around the asm MFMAs, where

@@ -85,21 +85,16 @@ void pack_mfma16x_deconv_stream(const int8_t *w_okc, int cin, int cout, int8_t *
 // conv / deconv 128 -> 128 on 16 x 32 tiles by one persistent workgroup per CU
 bool wide_supported(const LayerGeom &g) { return g.CIN == 128 && g.COUT == 128; }
 
-// The one rule of the three-group walk: a conv whose input's producer computed and stored three groups in this call.  Only a net's plan
-// says groups_in == 3 (sicn_net_forward; the per-layer entry points and the ragged nets say 4), and then the layer runs on the
-// input-permuted copy of its weights (sicn_live.h: group_permutation puts every dead channel at a position >= 96), whose stream
-// steps 75 .. 99 — group 3 — are all-zero tiles: make_live_plan asserts it.  k_conv_g3 reads that same d_w_mfma16 through a descriptor
-// of 80 steps, the ring wrapping there: 75 real steps and the zero tiles 75 .. 79 (conv_walk.hpp).
-int wide_walk_groups(const LayerGeom &g, int groups_in) { return (!g.transposed && groups_in == 3) ? 3 : 4; }
-
+// walk_groups = 3: the three-group K walk, which only a net's call plan asks for (sicn_live.h: walk_groups)
 hipError_t launch_wide(const LayerGeom &g, const sicn_weights &w, const uint8_t *in, uint8_t *out, int n_images, hipStream_t stream,
                        int in_layout, int out_layout, bool relu, int grid_cap, const ChipGeom &chip, unsigned long long *deal, int columns,
-                       int groups_in)
+                       int walk_groups)
 {
     using namespace xw;
     if (!wide_supported(g)) return hipErrorInvalidValue;
     if (g.transposed && !w.d_w_mfma16x) return hipErrorInvalidValue;
-    if (wide_walk_groups(g, groups_in) == 3 && in_layout != LAYOUT_GROUP) return hipErrorInvalidValue;   // three groups are three planes of the GROUP layout
+    // the three-group walk is the conv's, and three groups are three planes of the GROUP layout
+    if (walk_groups == 3 && (g.transposed || in_layout != LAYOUT_GROUP)) return hipErrorInvalidValue;
     if ((size_t)g.IH * g.IW * g.CIN >= (size_t)OOB || (size_t)g.OH * g.OW * g.COUT >= (size_t)OOB) return hipErrorInvalidValue;
     const int MW = g.transposed ? g.IW : g.OW, MH = g.transposed ? g.IH : g.OH;
     const int tiles_x = (MW + TX - 1) / TX, tiles_y = (MH + TY - 1) / TY;
@@ -109,7 +104,7 @@ hipError_t launch_wide(const LayerGeom &g, const sicn_weights &w, const uint8_t 
     const bool nt = nt_store_wanted((size_t)g.OH * g.OW * g.COUT * n_images);
     const unsigned grid = wide_grid(total, grid_cap, chip);   // one resident per CU, a multiple of the XCD count (sicn_plan.h)
     // columns < 8: the weight image w is permuted so that the channels the next layer reads fill the first `columns` columns
-    const void *fn = wide_walk_groups(g, groups_in) == 3 ? wide_g3_kernel(nt, columns)
+    const void *fn = walk_groups == 3 ? wide_g3_kernel(nt, columns)
                      : columns != 8 ? wide_live_kernel(g.transposed, nt, columns)
                      : g.transposed ? (nt ? (const void *)&k_deconv_x<true, JV_DECONV> : (const void *)&k_deconv_x<false, JV_DECONV>)
                                     : (nt ? (const void *)&k_conv_x<true, JV_CONV> : (const void *)&k_conv_x<false, JV_CONV>);

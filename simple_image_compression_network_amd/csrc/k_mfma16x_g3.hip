@@ -4,7 +4,7 @@
 // wrote (conv_walk.hpp: the schedule, its compile-time check, and the argument for the zero steps).  The same accumulator columns as
 // the four-group kernels: 3 and 5 with the register map of k_mfma16x_live.hip (fragments in AGPRs, every column in VGPRs), 8 with
 // k_conv_x's (JV = 7: fragments in VGPRs) for a call that ends or is tapped at the layer.  The weight stream is the four-group one of
-// the input-permuted handle, read through a descriptor of 80 steps (k_mfma16x.hip: wide_walk_groups).
+// the input-permuted handle, read through a descriptor of 80 steps (sicn_live.h: walk_groups).
 #include "k_mfma16x_body.hpp"
 
 namespace sicn {

@@ -194,15 +194,11 @@ struct LaunchArgs {
     uint8_t *out;
     int n_images;
     hipStream_t stream;
-    int in_layout, out_layout;
     const sicn_options &o;
     const ChipGeom &chip;
     const sicn_gdn *gdn;       // the layer's activation, nullptr = the reference's ReLU
     unsigned long long *deal;
-    int columns;               // accumulator columns the wide family computes (sicn_live.h); 8: all
-    int columns_in;            // the same of the layer that wrote `in` in this call; 8: all, or nothing is known of it
-    int groups;                // 32-channel groups a non-wide producer of 128 channels computes and stores (sicn_live.h); 4: all
-    int groups_in;             // the same of the layer that wrote `in` in this call; 4: all, or nothing is known of it
+    const live::Step &step;    // the layouts, and what of its channels the layer computes and reads in this call (sicn_live.h)
 };
 
 struct Family {
@@ -218,7 +214,6 @@ struct Family {
     // *act_done = true: the kernel applied a.gdn itself
     hipError_t (*launch)(const LaunchArgs &a, bool *act_done);
     void (*plan)(const LayerGeom &g, int n_images, const sicn_options &o, const ChipGeom &chip, int32_t out[12]);   // out[3..11] of sicn_debug_plan
-    bool (*deals)(const LayerGeom &g, int n_images, const sicn_options &o, const ChipGeom &chip);   // wants zeroed tile-deal words
 };
 
 template <class Pack>
@@ -241,9 +236,9 @@ hipError_t l0_launch(const LaunchArgs &a, bool *act_done)
     // layer 0 + activation in one kernel: the pre-activation tensor never reaches HBM
     if (a.gdn && a.o.gdn_fuse != 1 && a.w.d_w_l0g && a.gdn->d_gamma_mfma) {
         *act_done = true;
-        return launch_l0_gdn(a.g, a.w, *a.gdn, a.in, a.out, a.n_images, a.stream, a.out_layout, a.o, a.chip);
+        return launch_l0_gdn(a.g, a.w, *a.gdn, a.in, a.out, a.n_images, a.stream, a.step.out_layout, a.o, a.chip);
     }
-    return launch_l0(a.g, a.w, a.in, a.out, a.n_images, a.stream, a.out_layout, a.o, a.chip, a.gdn == nullptr, a.groups);
+    return launch_l0(a.g, a.w, a.in, a.out, a.n_images, a.stream, a.step.out_layout, a.o, a.chip, a.gdn == nullptr, a.step.groups);
 }
 void l0_plan(const LayerGeom &g, int n_images, const sicn_options &o, const ChipGeom &chip, int32_t out[12])
 {
@@ -258,15 +253,9 @@ bool l7_images(const int8_t *k, sicn_weights &w)
     return upload_image(l7_bytes(w.cin), &w.d_w_l7, [&](int8_t *s) { pack_l7(k, w.cin, s); }) &&
            upload_image(l7_half_bytes(), &w.d_w_l7_half, [&](int8_t *s) { pack_l7_half(k, s); });   // the form that reads one channel half
 }
-// Layer 7 reads only the first 64-channel half of its input where the layer in front of it, in this call, computed at most 4
-// accumulator columns: column_of(pos) < 4 <=> pos < 64 (sicn_live.h), so every live channel sits in the 32-channel groups 0 and 1,
-// the weights of the groups 2 and 3 are zero in the permuted image this layer got, and (a layer with a GDN computes all 8) no
-// activation has mixed the channels.  The GROUP and PHASE layouts keep a group in a plane of its own: the two planes that are skipped
-// are whole; NHWC would leave half of every line unread for nothing.
-bool l7_reads_one_half(int columns_in, int in_layout) { return columns_in <= 4 && in_layout != 0; }
 hipError_t l7_launch(const LaunchArgs &a, bool *)
 {
-    return launch_l7(a.g, a.w, a.in, a.out, a.n_images, a.stream, a.in_layout, a.o, a.chip, l7_reads_one_half(a.columns_in, a.in_layout) ? 1 : 2);
+    return launch_l7(a.g, a.w, a.in, a.out, a.n_images, a.stream, a.step.in_layout, a.o, a.chip, a.step.halves);
 }
 void l7_plan(const LayerGeom &g, int n_images, const sicn_options &o, const ChipGeom &chip, int32_t out[12])
 {
@@ -286,8 +275,8 @@ bool mfma_images(const int8_t *k, sicn_weights &w)
 }
 hipError_t mfma_launch(const LaunchArgs &a, bool *)
 {
-    return launch_mfma16(a.g, a.w, a.in, a.out, a.n_images, a.stream, a.in_layout, a.out_layout, a.o, a.chip, a.gdn == nullptr, a.deal,
-                         a.columns, a.groups_in);
+    return launch_mfma16(a.g, a.w, a.in, a.out, a.n_images, a.stream, a.step.in_layout, a.step.out_layout, a.o, a.chip, a.gdn == nullptr,
+                         a.deal, a.step.cols, a.step.walk_groups);
 }
 void mfma_plan(const LayerGeom &g, int n_images, const sicn_options &o, const ChipGeom &chip, int32_t out[12])
 {
@@ -296,7 +285,6 @@ void mfma_plan(const LayerGeom &g, int n_images, const sicn_options &o, const Ch
     out[7] = (int)p.grid_x; out[8] = (int)p.grid_y; out[9] = (int)p.grid_z;
     out[10] = p.deal;
 }
-bool mfma_deals(const LayerGeom &g, int n_images, const sicn_options &o, const ChipGeom &chip) { return plan_mfma(g, n_images, o, chip).deal; }
 
 // every other width the matrix cores can take (k_mfma16c.hip), NHWC in and out
 bool any_images(const int8_t *k, sicn_weights &w)
@@ -315,15 +303,15 @@ bool every_shape(int, int, int) { return true; }
 hipError_t generic_launch(const LaunchArgs &a, bool *) { return launch_generic(a.g, a.w, a.in, a.out, a.n_images, a.stream, a.gdn == nullptr); }
 
 const Family FAMILIES[] = {
-    // kind, name, direction, shape | reads, writes, rgb_sink, pre_relu | images, launch, plan, deals
-    {KK_L0_RGB, "l0_rgb", 0, l0_shape, 0, GROUP, false, true, l0_images, l0_launch, l0_plan, nullptr},
-    {KK_L7_RGB, "l7_rgb", 1, l7_shape, GROUP | PHASE, 0, true, false, l7_images, l7_launch, l7_plan, nullptr},
-    {KK_MFMA_CONV, "mfma_conv", 0, mfma_supported, GROUP, GROUP, false, true, mfma_images, mfma_launch, mfma_plan, mfma_deals},
+    // kind, name, direction, shape | reads, writes, rgb_sink, pre_relu | images, launch, plan
+    {KK_L0_RGB, "l0_rgb", 0, l0_shape, 0, GROUP, false, true, l0_images, l0_launch, l0_plan},
+    {KK_L7_RGB, "l7_rgb", 1, l7_shape, GROUP | PHASE, 0, true, false, l7_images, l7_launch, l7_plan},
+    {KK_MFMA_CONV, "mfma_conv", 0, mfma_supported, GROUP, GROUP, false, true, mfma_images, mfma_launch, mfma_plan},
     // the deconv's outputs come one pixel parity at a time
-    {KK_MFMA_DECONV, "mfma_deconv", 1, mfma_supported, GROUP | PHASE, GROUP | PHASE, false, true, mfma_images, mfma_launch, mfma_plan, mfma_deals},
-    {KK_MFMA_CONV_ANY, "mfma_conv_any", 0, any_supported, 0, 0, false, true, any_images, any_launch, any_plan, nullptr},
-    {KK_MFMA_DECONV_ANY, "mfma_deconv_any", 1, any_supported, 0, 0, false, true, any_images, any_launch, any_plan, nullptr},
-    {KK_GENERIC, "generic", -1, every_shape, 0, 0, false, true, nullptr, generic_launch, nullptr, nullptr},
+    {KK_MFMA_DECONV, "mfma_deconv", 1, mfma_supported, GROUP | PHASE, GROUP | PHASE, false, true, mfma_images, mfma_launch, mfma_plan},
+    {KK_MFMA_CONV_ANY, "mfma_conv_any", 0, any_supported, 0, 0, false, true, any_images, any_launch, any_plan},
+    {KK_MFMA_DECONV_ANY, "mfma_deconv_any", 1, any_supported, 0, 0, false, true, any_images, any_launch, any_plan},
+    {KK_GENERIC, "generic", -1, every_shape, 0, 0, false, true, nullptr, generic_launch, nullptr},
 };
 const Family &GENERIC = FAMILIES[sizeof FAMILIES / sizeof *FAMILIES - 1];
 
@@ -419,10 +407,9 @@ extern "C" int sicn_weights_from_finn_tiles(const sicn_layer_desc *d, const void
 // ---- single layers ------------------------------------------------------------------------------
 // Layout of the tensor between layer `p` (producer) and layer `c` (consumer) of a chain: the best
 // one both kernels implement (k_common.hpp).  0 = NHWC, 1 = GROUP, 2 = PHASE.
-static int link_layout(const sicn_layer_desc &p, const sicn_layer_desc &c, const sicn_options &o, bool p_gdn, bool c_gdn)
+static int link_layout(const Family &fp, const Family &fc, const sicn_options &o)
 {
-    const Family &fc = layer_family(c, o, c_gdn);
-    const unsigned common = layer_family(p, o, p_gdn).writes & fc.reads;
+    const unsigned common = fp.writes & fc.reads;
     // experiments: no_phase_layout 1 = never, 2 = not towards the RGB layer
     const bool phase_ok = o.no_phase_layout == 0 || (o.no_phase_layout == 2 && !fc.rgb_sink);
     if ((common & PHASE) && phase_ok) return 2;
@@ -432,11 +419,10 @@ static int link_layout(const sicn_layer_desc &p, const sicn_layer_desc &c, const
 
 // gdn != nullptr: the layer stores its lanes BEFORE the sign-bit ReLU and the GDN / IGDN kernel then rewrites them in
 // place, in whatever layout the layer wrote (include/sicn_gdn.h; extension beyond the reference).  deal: the layer's tile-deal
-// words in the workspace of a chain (launch_mfma16), or nullptr.
-static int run_layer(const sicn_layer_desc *d, const sicn_weights *w, const uint8_t *in, uint8_t *out,
-                     int n_images, hipStream_t stream, int want_transposed, const sicn_options &o, int in_layout = 0,
-                     int out_layout = 0, const sicn_gdn *gdn = nullptr, unsigned long long *deal = nullptr, int columns = 8,
-                     int columns_in = 8, int groups = 4, int groups_in = 4)
+// words in the workspace of a chain (launch_mfma16), or nullptr.  step: what a net's call plan makes of the layer (sicn_live.h); a
+// layer run alone takes the default, everything whole and NHWC.
+static int run_layer(const sicn_layer_desc *d, const sicn_weights *w, const uint8_t *in, uint8_t *out, int n_images, hipStream_t stream,
+                     int want_transposed, const sicn_options &o, const sicn_gdn *gdn, const live::Step &step, unsigned long long *deal)
 {
     int rc = sicn_validate_desc(d);
     if (rc) return rc;
@@ -450,10 +436,10 @@ static int run_layer(const sicn_layer_desc *d, const sicn_weights *w, const uint
     ChipGeom chip;
     if ((rc = chip_geom(&chip)) != SICN_OK) return rc;   // no device, or not a gfx950 one
     bool act_done = false;
-    const LaunchArgs args{g, *w, in, out, n_images, stream, in_layout, out_layout, o, chip, gdn, deal, columns, columns_in, groups, groups_in};
+    const LaunchArgs args{g, *w, in, out, n_images, stream, o, chip, gdn, deal, step};
     hipError_t e = layer_family(*d, o, gdn != nullptr).launch(args, &act_done);
     if (act_done) gdn = nullptr;
-    if (e == hipSuccess && gdn) e = launch_gdn(*gdn, out, out_layout, d->OFM_ROW, d->OFM_COL, n_images, stream);
+    if (e == hipSuccess && gdn) e = launch_gdn(*gdn, out, step.out_layout, d->OFM_ROW, d->OFM_COL, n_images, stream);
     if (e == hipErrorInvalidValue) return SICN_EINVAL;
     return e == hipSuccess ? SICN_OK : SICN_ENODEV;
 }
@@ -461,7 +447,7 @@ static int run_layer(const sicn_layer_desc *d, const sicn_weights *w, const uint
 extern "C" int sicn_conv2d(const sicn_layer_desc *d, const sicn_weights *w, const uint8_t *in, uint8_t *out,
                            int n_images, void *hip_stream)
 {
-    return run_layer(d, w, in, out, n_images, (hipStream_t)hip_stream, 0, default_options());
+    return run_layer(d, w, in, out, n_images, (hipStream_t)hip_stream, 0, default_options(), nullptr, live::Step{}, nullptr);
 }
 
 extern "C" int sicn_conv2d_opt(const sicn_layer_desc *d, const sicn_weights *w, const uint8_t *in, uint8_t *out,
@@ -469,13 +455,13 @@ extern "C" int sicn_conv2d_opt(const sicn_layer_desc *d, const sicn_weights *w, 
 {
     sicn_options o;
     int rc = resolve_options(opt, &o);
-    return rc ? rc : run_layer(d, w, in, out, n_images, (hipStream_t)hip_stream, 0, o);
+    return rc ? rc : run_layer(d, w, in, out, n_images, (hipStream_t)hip_stream, 0, o, nullptr, live::Step{}, nullptr);
 }
 
 extern "C" int sicn_deconv522(const sicn_layer_desc *d, const sicn_weights *w, const uint8_t *in,
                               uint8_t *out, int n_images, void *hip_stream)
 {
-    return run_layer(d, w, in, out, n_images, (hipStream_t)hip_stream, 1, default_options());
+    return run_layer(d, w, in, out, n_images, (hipStream_t)hip_stream, 1, default_options(), nullptr, live::Step{}, nullptr);
 }
 
 extern "C" int sicn_deconv522_opt(const sicn_layer_desc *d, const sicn_weights *w, const uint8_t *in, uint8_t *out,
@@ -483,10 +469,12 @@ extern "C" int sicn_deconv522_opt(const sicn_layer_desc *d, const sicn_weights *
 {
     sicn_options o;
     int rc = resolve_options(opt, &o);
-    return rc ? rc : run_layer(d, w, in, out, n_images, (hipStream_t)hip_stream, 1, o);
+    return rc ? rc : run_layer(d, w, in, out, n_images, (hipStream_t)hip_stream, 1, o, nullptr, live::Step{}, nullptr);
 }
 
 // ---- layer chains ---------------------------------------------------------------------------------
+constexpr int MAX_LAYERS = 64;   // of a net (sicn_net_create_gdn): a call's facts and steps are arrays on the stack
+
 struct sicn_net {
     std::vector<sicn_layer_desc> descs;
     std::vector<const sicn_weights *> weights;
@@ -551,7 +539,7 @@ static int make_live_plan(sicn_net *net)
                 std::vector<int8_t> t(okc.size());
                 live::permute_inputs(okc.data(), w.cout, net->live[l - 1].p, t.data());
                 okc.swap(t);
-                // behind a producer that stores three groups the wide conv walks three (k_mfma16x.hip: wide_walk_groups) and takes the
+                // behind a producer that stores three groups the wide conv walks three (sicn_live.h: walk_groups) and takes the
                 // steps 75 .. 79 of this copy's stream for zero tiles: no weight on an input position in the fourth group
                 if (net->live[l - 1].ng < live::GROUPS && w.cin == live::CH &&
                     !conv_inputs_zero_from(okc.data(), w.cin, w.cout, net->live[l - 1].ng * live::GROUP_CH))
@@ -573,7 +561,7 @@ extern "C" int sicn_net_create_gdn(const sicn_layer_desc *descs, sicn_weights *c
 {
     if (!out) return SICN_EINVAL;
     *out = nullptr;
-    if (!descs || !weights || n_layers <= 0 || n_layers > 64) return SICN_EINVAL;
+    if (!descs || !weights || n_layers <= 0 || n_layers > MAX_LAYERS) return SICN_EINVAL;
     sicn_options o;
     if (int rc = resolve_options(opt, &o)) return rc;
     for (int i = 0; i < n_layers; i++) {
@@ -634,105 +622,87 @@ extern "C" size_t sicn_net_workspace_bytes(const sicn_net *net, int n_images)
     return 2 * pingpong_slot_bytes(net, n_images) + deal_bytes(net);
 }
 
-// the accumulator columns layer l computes in a call over [first, last]: fewer than all where the net's tables allow it (make_live_plan)
-// and this call runs the layer on the wide family, in the middle of the chain, untapped
-static int call_columns(const sicn_net *net, int l, int first, int last, int tap_layer, int n_images, const ChipGeom &chip)
+// What the host layer knows of every layer of the net for a call of n_images on this chip (sicn_live.h).  chip == nullptr: nothing that
+// depends on the chip is asked, no layer counts as wide or dealing.
+static void call_facts(const sicn_net *net, int n_images, const ChipGeom *chip, live::CallFacts *out)
 {
-    if (net->live[(size_t)l].nj >= live::COLS) return live::COLS;
-    const Family &f = layer_family(net->descs[(size_t)l], net->opt, false);
-    const bool wide = (f.kind == KK_MFMA_CONV || f.kind == KK_MFMA_DECONV) &&
-                      plan_mfma(geom_of(net->descs[(size_t)l]), n_images, net->opt, chip).family == 2;
-    return live::columns(net->live, l, first, last, tap_layer, wide);
+    const int n_layers = (int)net->descs.size();
+    const Family *fam[MAX_LAYERS];
+    for (int l = 0; l < n_layers; l++) fam[l] = &layer_family(net->descs[l], net->opt, net->gdn[l] != nullptr);
+    for (int l = 0; l < n_layers; l++) {
+        const LayerGeom g = geom_of(net->descs[l]);
+        live::CallFacts &f = out[l] = live::CallFacts{};
+        f.transposed = g.transposed != 0;
+        f.l7 = fam[l]->kind == KK_L7_RGB;
+        f.link_layout = l + 1 < n_layers ? link_layout(*fam[l], *fam[l + 1], net->opt) : 0;
+        // no family with pre_relu == false is an MFMA family (FAMILIES): pick_family and layer_family agree on every layer asked here
+        if (chip && (fam[l]->kind == KK_MFMA_CONV || fam[l]->kind == KK_MFMA_DECONV) && wide_supported(g)) {
+            const MfmaPlan p = plan_mfma(g, n_images, net->opt, *chip);   // only the 128 -> 128 shape has a family 2 and a deal
+            f.wide = p.family == 2;
+            f.deals = p.deal != 0;
+        }
+    }
 }
 
-// the layout layer l of a call that ends at `last` writes: the last and the tapped layer leave the chain in NHWC
-static int call_out_layout(const sicn_net *net, int l, int last, int tap_layer)
+// What a call would do, for tests: the plan sicn_net_forward executes, made the way it makes it.  need_chip = false: what is asked for
+// does not depend on the chip, and the call succeeds without one.
+static int debug_call_plan(const sicn_net *net, int first, int last, int tap_layer, int n_images, bool args_ok, bool need_chip, live::Step *steps)
 {
-    return (l < last && l != tap_layer)
-               ? link_layout(net->descs[(size_t)l], net->descs[(size_t)l + 1], net->opt, net->gdn[(size_t)l] != nullptr, net->gdn[(size_t)l + 1] != nullptr)
-               : 0;
+    if (!net || !args_ok || n_images <= 0) return SICN_EINVAL;
+    const int n_layers = (int)net->descs.size();
+    if (first < 0 || last >= n_layers || first > last) return SICN_EINVAL;
+    ChipGeom chip;
+    if (need_chip)
+        if (int rc = chip_geom(&chip)) return rc;
+    live::CallFacts facts[MAX_LAYERS];
+    call_facts(net, n_images, need_chip ? &chip : nullptr, facts);
+    live::plan_call(net->live, facts, n_layers, first, last, tap_layer, steps);
+    return SICN_OK;
 }
 
-// the 32-channel groups layer l computes and stores in a call over [first, last]: fewer than all where the net's tables allow it
-// (make_live_plan: a 3 -> 128 layer without a GDN, which then runs on l0_rgb) and the layer is in the middle of the chain, untapped, and
-// writes the GROUP layout, whose planes are whole groups
-static int call_groups(const sicn_net *net, int l, int first, int last, int tap_layer, int out_layout)
-{
-    return live::groups(net->live, l, first, last, tap_layer, out_layout == 1);
-}
-
-// what a call would do, for tests: per layer of the net the columns computed (8 outside [first, last]) and the output channels that
-// the call's next layer reads
+// per layer of the net the columns computed (8 outside [first, last]) and the output channels that the call's next layer reads
 extern "C" int sicn_debug_net_columns(const sicn_net *net, int first, int last, int tap_layer, int n_images, int32_t *columns,
                                       int32_t *live_outputs)
 {
-    if (!net || !columns || !live_outputs || n_images <= 0) return SICN_EINVAL;
-    const int n_layers = (int)net->descs.size();
-    if (first < 0 || last >= n_layers || first > last) return SICN_EINVAL;
-    ChipGeom chip;
-    if (int rc = chip_geom(&chip)) return rc;
-    for (int l = 0; l < n_layers; l++) {
-        columns[l] = call_columns(net, l, first, last, tap_layer, n_images, chip);
-        live_outputs[l] = live::live_outputs(net->live, l, first, last, tap_layer);
+    live::Step steps[MAX_LAYERS];
+    if (int rc = debug_call_plan(net, first, last, tap_layer, n_images, columns && live_outputs, true, steps)) return rc;
+    for (size_t l = 0; l < net->descs.size(); l++) {
+        columns[l] = steps[l].cols;
+        live_outputs[l] = steps[l].live_out;
     }
     return SICN_OK;
 }
 
-// what a call would do, for tests: per layer of the net the 64-channel halves of its input that it reads (the walk of sicn_net_forward)
+// per layer of the net the 64-channel halves of its input that it reads
 extern "C" int sicn_debug_net_input_halves(const sicn_net *net, int first, int last, int tap_layer, int n_images, int32_t *halves)
 {
-    if (!net || !halves || n_images <= 0) return SICN_EINVAL;
-    const int n_layers = (int)net->descs.size();
-    if (first < 0 || last >= n_layers || first > last) return SICN_EINVAL;
-    ChipGeom chip;
-    if (int rc = chip_geom(&chip)) return rc;
-    for (int l = 0; l < n_layers; l++) halves[l] = 2;
-    int cols_before = live::COLS, cur_layout = 0;
-    for (int l = first; l <= last; l++) {
-        const bool l7 = layer_family(net->descs[l], net->opt, net->gdn[l] != nullptr).kind == KK_L7_RGB;
-        if (l7 && l7_reads_one_half(cols_before, cur_layout)) halves[l] = 1;
-        cols_before = call_columns(net, l, first, last, tap_layer, n_images, chip);
-        cur_layout = call_out_layout(net, l, last, tap_layer);
-    }
+    live::Step steps[MAX_LAYERS];
+    if (int rc = debug_call_plan(net, first, last, tap_layer, n_images, halves != nullptr, true, steps)) return rc;
+    for (size_t l = 0; l < net->descs.size(); l++) halves[l] = steps[l].halves;
     return SICN_OK;
 }
 
-// what a call would do, for tests: per layer of the net the 32-channel groups it computes and stores, and the groups the layer that
-// wrote its input computed (4 outside [first, last] and for the first layer of the call) — the walk of sicn_net_forward
+// per layer of the net the 32-channel groups it computes and stores, and the groups the layer that wrote its input computed (4 outside
+// [first, last] and for the first layer of the call)
 extern "C" int sicn_debug_net_groups(const sicn_net *net, int first, int last, int tap_layer, int n_images, int32_t *groups_out,
                                      int32_t *groups_in)
 {
-    if (!net || !groups_out || !groups_in || n_images <= 0) return SICN_EINVAL;
-    const int n_layers = (int)net->descs.size();
-    if (first < 0 || last >= n_layers || first > last) return SICN_EINVAL;
-    for (int l = 0; l < n_layers; l++) groups_out[l] = groups_in[l] = live::GROUPS;
-    int groups_before = live::GROUPS;
-    for (int l = first; l <= last; l++) {
-        groups_in[l] = groups_before;
-        groups_before = groups_out[l] = call_groups(net, l, first, last, tap_layer, call_out_layout(net, l, last, tap_layer));
+    live::Step steps[MAX_LAYERS];
+    if (int rc = debug_call_plan(net, first, last, tap_layer, n_images, groups_out && groups_in, false, steps)) return rc;
+    for (size_t l = 0; l < net->descs.size(); l++) {
+        groups_out[l] = steps[l].groups;
+        groups_in[l] = steps[l].groups_in;
     }
     return SICN_OK;
 }
 
-// what a call would do, for tests: per layer of the net the 32-channel groups of its input that its K walk covers — 3 for a conv on the
-// wide family behind a layer that stored three groups in this call (wide_walk_groups, the function launch_wide chooses its kernel by),
-// 4 for every other launch and outside [first, last]
+// per layer of the net the 32-channel groups of its input that its K walk covers — 3 for a conv on the wide family behind a layer that
+// stored three groups in this call (live::walk_groups), 4 for every other launch and outside [first, last]
 extern "C" int sicn_debug_net_walk_groups(const sicn_net *net, int first, int last, int tap_layer, int n_images, int32_t *walk_groups)
 {
-    if (!net || !walk_groups || n_images <= 0) return SICN_EINVAL;
-    const int n_layers = (int)net->descs.size();
-    if (first < 0 || last >= n_layers || first > last) return SICN_EINVAL;
-    ChipGeom chip;
-    if (int rc = chip_geom(&chip)) return rc;
-    for (int l = 0; l < n_layers; l++) walk_groups[l] = live::GROUPS;
-    int groups_before = live::GROUPS;
-    for (int l = first; l <= last; l++) {
-        const Family &f = layer_family(net->descs[l], net->opt, net->gdn[l] != nullptr);
-        const LayerGeom g = geom_of(net->descs[l]);
-        const bool wide = (f.kind == KK_MFMA_CONV || f.kind == KK_MFMA_DECONV) && plan_mfma(g, n_images, net->opt, chip).family == 2;
-        if (wide) walk_groups[l] = wide_walk_groups(g, groups_before);
-        groups_before = call_groups(net, l, first, last, tap_layer, call_out_layout(net, l, last, tap_layer));
-    }
+    live::Step steps[MAX_LAYERS];
+    if (int rc = debug_call_plan(net, first, last, tap_layer, n_images, walk_groups != nullptr, true, steps)) return rc;
+    for (size_t l = 0; l < net->descs.size(); l++) walk_groups[l] = steps[l].walk_groups;
     return SICN_OK;
 }
 
@@ -752,13 +722,16 @@ extern "C" int sicn_net_forward(const sicn_net *net, int first, int last, const 
     unsigned long long *deal_base = nullptr;   // the tile-deal words of this call's layers, zeroed below (a smaller / absent workspace: static deal)
     ChipGeom chip;
     if (int rc = chip_geom(&chip)) return rc;
+    // the plan of this call (sicn_live.h): per layer the layouts, the columns and groups it computes (a layer on the wide family only the
+    // columns the next layer reads, layer 0's family only the groups), the copy of its weights, and what it reads of its input
+    live::CallFacts facts[MAX_LAYERS];
+    live::Step steps[MAX_LAYERS];
+    call_facts(net, n_images, &chip, facts);
+    live::plan_call(net->live, facts, n_layers, first, last, tap_layer, steps);
     {
         // does a layer of this call deal tiles dynamically?  (small inputs never do: no zeroing launch in front of them)
         bool any_deal = false;
-        for (int l = first; l <= last && !any_deal; l++) {
-            const Family &f = pick_family(net->descs[l], net->opt);
-            any_deal = f.deals && f.deals(geom_of(net->descs[l]), n_images, net->opt, chip);
-        }
+        for (int l = first; l <= last; l++) any_deal |= facts[l].deals;
         if (any_deal && workspace && workspace_bytes >= 2 * slot + deal_bytes(net) && !debug_env().no_deal) {
             deal_base = (unsigned long long *)((uint8_t *)workspace + 2 * slot);
             // zeroed once per forward pass, by a kernel; every layer of the call gets its own DEAL_WORDS
@@ -766,7 +739,6 @@ extern "C" int sicn_net_forward(const sicn_net *net, int first, int last, const 
         }
     }
     const uint8_t *cur = in;
-    int cur_layout = 0;  // the chain's input is always NHWC
     // profiling: reserve this call's event slots (one per layer) in one atomic step
     int slot0 = -1;
     if (net->profile.load(std::memory_order_acquire)) {
@@ -774,21 +746,10 @@ extern "C" int sicn_net_forward(const sicn_net *net, int first, int last, const 
         const int at = net->ev_next.fetch_add(need, std::memory_order_relaxed);
         if (at + need <= sicn_net::EV_RING) slot0 = at;   // ring full: this call is not timed
     }
-    // the columns and groups the previous layer of this call computed: fewer than all of either = it wrote its channels in the order of its p
-    int cols_before = live::COLS, groups_before = live::GROUPS;
     for (int l = first; l <= last; l++) {
-        // intermediates nobody outside sees travel in the grouped layout when both neighbours can
-        const int out_layout = call_out_layout(net, l, last, tap_layer);
-        // the live-channel plan of this call: a layer on the wide family computes only the columns the next layer reads, layer 0's
-        // family only the groups (sicn_live.h)
-        const int cols = call_columns(net, l, first, last, tap_layer, n_images, chip);
-        const int groups = call_groups(net, l, first, last, tap_layer, out_layout);
-        const int variant = live::variant(cols_before, groups_before, cols, groups);
-        const sicn_weights *wl = variant ? net->derived[l][(size_t)variant] : net->weights[l];
+        const live::Step &step = steps[l];
+        const sicn_weights *wl = step.variant ? net->derived[l][(size_t)step.variant] : net->weights[l];
         if (!wl) return SICN_EINVAL;
-        const int cols_in = cols_before, groups_in = groups_before;
-        cols_before = cols;
-        groups_before = groups;
         // a tapped layer (the latent) is written straight into the caller's buffer and the next layer reads it there: no copy
         // (round 3 copied it device-to-device behind the layer: 4.8 us per forward pass on small inputs, 15 us on 8 x 4K)
         uint8_t *dst = (l == last) ? out : (l == tap_layer ? tap_out : pp[(l - first) & 1]);
@@ -797,8 +758,8 @@ extern "C" int sicn_net_forward(const sicn_net *net, int first, int last, const 
             net->ev_layer[ev].store(-1, std::memory_order_relaxed);   // becomes l once both events are recorded
             if (hipEventRecord(net->ev_begin[ev], stream) != hipSuccess) return SICN_ENODEV;
         }
-        int rc = run_layer(&net->descs[l], wl, cur, dst, n_images, stream, -1, net->opt, cur_layout, out_layout,
-                           net->gdn[l], deal_base ? deal_base + (size_t)l * DEAL_WORDS : nullptr, cols, cols_in, groups, groups_in);
+        int rc = run_layer(&net->descs[l], wl, cur, dst, n_images, stream, -1, net->opt, net->gdn[l], step,
+                           deal_base ? deal_base + (size_t)l * DEAL_WORDS : nullptr);
         if (rc) return rc;
         if (ev >= 0) {
             if (hipEventRecord(net->ev_end[ev], stream) != hipSuccess) return SICN_ENODEV;
@@ -810,7 +771,6 @@ extern "C" int sicn_net_forward(const sicn_net *net, int first, int last, const 
                 return SICN_ENODEV;
         }
         cur = dst;
-        cur_layout = out_layout;
     }
     return SICN_OK;
 }
@@ -1009,7 +969,7 @@ extern "C" int sicn_conv2d_gdn(const sicn_layer_desc *d, const sicn_weights *w, 
 {
     sicn_options o;
     int rc = resolve_options(opt, &o);
-    return rc ? rc : run_layer(d, w, in, out, n_images, (hipStream_t)hip_stream, 0, o, 0, 0, gdn);
+    return rc ? rc : run_layer(d, w, in, out, n_images, (hipStream_t)hip_stream, 0, o, gdn, live::Step{}, nullptr);
 }
 
 extern "C" int sicn_deconv522_gdn(const sicn_layer_desc *d, const sicn_weights *w, const sicn_gdn *gdn, const uint8_t *in,
@@ -1017,5 +977,5 @@ extern "C" int sicn_deconv522_gdn(const sicn_layer_desc *d, const sicn_weights *
 {
     sicn_options o;
     int rc = resolve_options(opt, &o);
-    return rc ? rc : run_layer(d, w, in, out, n_images, (hipStream_t)hip_stream, 1, o, 0, 0, gdn);
+    return rc ? rc : run_layer(d, w, in, out, n_images, (hipStream_t)hip_stream, 1, o, gdn, live::Step{}, nullptr);
 }

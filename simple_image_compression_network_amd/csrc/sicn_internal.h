@@ -89,7 +89,7 @@ hipError_t launch_crop_nhwc(const uint8_t *src, uint8_t *dst, int n, int hs, int
 // deal: DEAL_WORDS zeroed words for the wide persistent kernels' tile deal (k_mfma16x.hip: DealX), or nullptr (static deal)
 hipError_t launch_mfma16(const LayerGeom &g, const sicn_weights &w, const uint8_t *in, uint8_t *out,
                          int n_images, hipStream_t stream, int in_layout, int out_layout, const sicn_options &o, const ChipGeom &chip,
-                         bool relu = true, unsigned long long *deal = nullptr, int columns = 8, int groups_in = 4);
+                         bool relu = true, unsigned long long *deal = nullptr, int columns = 8, int walk_groups = 4);
 // k_mfma16x.hip: the wide persistent form — one workgroup of 4 waves per CU walks through 16 x 32-position tiles, 128 x 128 outputs
 // per wave (accumulators in AGPRs, one wave per SIMD); grid_cap > 0 limits the number of workgroups (tests)
 bool wide_supported(const LayerGeom &g);
@@ -97,10 +97,7 @@ size_t mfma16x_deconv_stream_bytes(int cin, int cout);   // 0 where the wide dec
 void pack_mfma16x_deconv_stream(const int8_t *w_okc, int cin, int cout, int8_t *dst);
 hipError_t launch_wide(const LayerGeom &g, const sicn_weights &w, const uint8_t *in, uint8_t *out, int n_images, hipStream_t stream,
                        int in_layout, int out_layout, bool relu, int grid_cap, const ChipGeom &chip, unsigned long long *deal = nullptr,
-                       int columns = 8, int groups_in = 4);
-// the 32-channel groups of its input the K walk of a wide launch covers: 3 for a conv whose input's producer computed and stored
-// three groups in this call (groups_in: sicn_live.h — only a net's plan ever says 3), otherwise all 4
-int wide_walk_groups(const LayerGeom &g, int groups_in);
+                       int columns = 8, int walk_groups = 4);   // walk_groups: sicn_live.h — only a net's call plan ever says 3
 // k_mfma16x_live.hip: the same kernels with the first `columns` (3 | 5) of the 8 accumulator columns only, for weights permuted by the
 // net's live-channel plan (sicn_live.h); nullptr for a width that is not built
 const void *wide_live_kernel(int transposed, bool nt_store, int columns);

@@ -1,4 +1,4 @@
-// The live-channel plan of a layer chain (host C++ only: no HIP, no device; tests/cpp/live_plan_check.cpp compiles it alone).
+// The live-channel plan of a layer chain (host C++ only: no HIP, no device; tests/cpp/call_plan_check.cpp compiles it alone).
 //
 // A layer's output channel that its only consumer multiplies by zero in every tap need not be computed.  The wide persistent
 // kernels (k_mfma16x.hip, k_mfma16x_live.hip) hold a 16 x 32-position tile as 8 accumulator COLUMNS of 16 channels; column
@@ -112,7 +112,7 @@ inline void permute_inputs(const int8_t *w_okc, int cout, const std::vector<int>
 }
 
 // ---- the plan ---------------------------------------------------------------------------------------------------------------
-// What is known of layer i when the net is made (Layer), and what one call makes of it (columns).
+// What is known of layer i when the net is made (Layer), and what one call makes of it (plan_call).
 struct Layer {
     int cin = 0, cout = 0;
     bool gdn = false;             // carries a sicn_gdn: the activation mixes channels, every channel is needed
@@ -172,6 +172,69 @@ inline bool wrote_permuted(int cols, int groups) { return cols < COLS || groups 
 inline int variant(int cols_in, int groups_in, int cols, int groups)
 {
     return 2 * (int)wrote_permuted(cols_in, groups_in) + (int)wrote_permuted(cols, groups);
+}
+
+// Layer 7 reads only the first 64-channel half of its input where the layer in front of it, in this call, computed at most 4
+// accumulator columns: column_of(pos) < 4 <=> pos < 64, so every live channel sits in the 32-channel groups 0 and 1,
+// the weights of the groups 2 and 3 are zero in the permuted image this layer got, and (a layer with a GDN computes all 8) no
+// activation has mixed the channels.  The GROUP and PHASE layouts keep a group in a plane of its own: the two planes that are skipped
+// are whole; NHWC would leave half of every line unread for nothing.
+inline int input_halves(bool l7, int cols_in, int in_layout) { return (l7 && cols_in <= 4 && in_layout != 0) ? 1 : 2; }
+
+// The one rule of the three-group walk: a conv on the wide family whose input's producer computed and stored three groups in this call.
+// Only a net's plan says groups_in == 3 (the per-layer entry points and the ragged nets say 4), and then the layer runs on the
+// input-permuted copy of its weights (group_permutation puts every dead channel at a position >= 96), whose stream steps 75 .. 99 —
+// group 3 — are all-zero tiles: make_live_plan asserts it.  k_conv_g3 reads that same d_w_mfma16 through a descriptor of 80 steps, the
+// ring wrapping there: 75 real steps and the zero tiles 75 .. 79 (conv_walk.hpp).
+inline int walk_groups(bool wide, bool transposed, int groups_in) { return (wide && !transposed && groups_in == 3) ? 3 : GROUPS; }
+
+// ---- one call ---------------------------------------------------------------------------------------------------------------
+// What the host layer knows of a layer for one call's options, image count and chip (csrc/sicn_abi.hip: call_facts).
+struct CallFacts {
+    bool wide = false;        // planned onto the wide family (plan_mfma family 2)
+    bool transposed = false;
+    bool l7 = false;          // runs on the layer-7 RGB family
+    int link_layout = 0;      // the layout both this layer and the next one implement (0 for the net's last layer)
+    bool deals = false;       // wants zeroed tile-deal words
+};
+
+// What one call does with a layer.  The default is "everything whole, NHWC": a layer outside [first, last], and a layer run alone.
+struct Step {
+    int in_layout = 0, out_layout = 0;
+    int cols = COLS, cols_in = COLS;         // accumulator columns it computes / the layer that wrote its input computed
+    int groups = GROUPS, groups_in = GROUPS; // 32-channel groups it computes and stores / the layer that wrote its input did
+    int variant = 0;                         // the copy of its weights it takes
+    int halves = 2;                          // 64-channel halves of its input it reads (input_halves)
+    int walk_groups = GROUPS;                // groups of its input its K walk covers (walk_groups)
+    int live_out = 0;                        // output channels somebody reads (plan_call: live_outputs, for every layer of the net)
+};
+
+// The walk over a call's layers, the only one: out[0 .. n_layers - 1]; the chain's input is NHWC, the last and the tapped layer leave
+// in NHWC, intermediates nobody outside sees travel in the layout both neighbours implement.
+inline void plan_call(const std::vector<Layer> &L, const CallFacts *facts, int n_layers, int first, int last, int tap_layer, Step *out)
+{
+    for (int l = 0; l < n_layers; l++) {
+        out[l] = Step{};
+        out[l].live_out = live_outputs(L, l, first, last, tap_layer);
+    }
+    // the columns and groups the previous layer of this call computed: fewer than all of either = it wrote its channels in the order of its p
+    int cols_before = COLS, groups_before = GROUPS, cur_layout = 0;
+    for (int l = first; l <= last; l++) {
+        const CallFacts &f = facts[l];
+        Step &s = out[l];
+        s.in_layout = cur_layout;
+        s.out_layout = (l < last && l != tap_layer) ? f.link_layout : 0;
+        s.cols = columns(L, l, first, last, tap_layer, f.wide);
+        s.groups = groups(L, l, first, last, tap_layer, s.out_layout == 1);
+        s.cols_in = cols_before;
+        s.groups_in = groups_before;
+        s.variant = variant(s.cols_in, s.groups_in, s.cols, s.groups);
+        s.halves = input_halves(f.l7, s.cols_in, s.in_layout);
+        s.walk_groups = walk_groups(f.wide, f.transposed, s.groups_in);
+        cols_before = s.cols;
+        groups_before = s.groups;
+        cur_layout = s.out_layout;
+    }
 }
 
 }  // namespace live

@@ -74,7 +74,7 @@ def words(kind, w):
 
 
 def okc(w):
-    """[cout][25 cin] with k = tap cin + c, as a weights handle keeps it on the host and tests/cpp/live_plan_check.cpp reads it"""
+    """[cout][25 cin] with k = tap cin + c, as a weights handle keeps it on the host and tests/cpp/call_plan_check.cpp reads it"""
     return np.ascontiguousarray(w.reshape(w.shape[0], -1))
 
 

@@ -1,4 +1,4 @@
-"""The channel groups of layer 0 in the live-channel plan (csrc/sicn_live.h) without a GPU: tests/cpp/l0_groups_plan_check.cpp is the
+"""The channel groups of layer 0 in the live-channel plan (csrc/sicn_live.h) without a GPU: tests/cpp/call_plan_check.cpp is the
 plan header and nothing else, compiled here with -fsanitize=address,undefined and run on weight sets written to a temporary directory.
 A 3 -> 128 layer without a GDN whose consumer reads at most 96 of its channels computes and stores three of the four 32-channel
 groups: the live channels go, ascending, to the positions 0, 1, 2, ..., the dead ones behind them, and the consumer's K index moves
@@ -16,11 +16,12 @@ import pytest
 from oracle import sicn_ref
 
 ROOT = Path(__file__).resolve().parent.parent
-SRC = ROOT / "tests" / "cpp" / "l0_groups_plan_check.cpp"
+SRC = ROOT / "tests" / "cpp" / "call_plan_check.cpp"
 GOLDEN = ROOT / "tests" / "golden" / "param_weights.npz"
-# (cin, cout, gdn, planned onto the wide family, output in the GROUP layout) of the reference's eight layers on a large input
-NET = [(3, 128, 0, 0, 1), (128, 128, 0, 1, 1), (128, 128, 0, 1, 1), (128, 192, 0, 0, 0), (192, 128, 0, 0, 1), (128, 128, 0, 1, 1),
-       (128, 128, 0, 1, 1), (128, 3, 0, 0, 0)]
+# (cin, cout, gdn, planned onto the wide family, layout towards the next layer: 1 = GROUP, 2 = PHASE, transposed, on the layer-7 family)
+# of the reference's eight layers on a large input
+NET = [(3, 128, 0, 0, 1, 0, 0), (128, 128, 0, 1, 1, 0, 0), (128, 128, 0, 1, 1, 0, 0), (128, 192, 0, 0, 1, 0, 0), (192, 128, 0, 0, 2, 1, 0),
+       (128, 128, 0, 1, 2, 1, 0), (128, 128, 0, 1, 2, 1, 0), (128, 3, 0, 0, 0, 1, 1)]
 
 
 @pytest.fixture(scope="module")
@@ -28,7 +29,7 @@ def exe(tmp_path_factory):
     cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
     if cxx is None:
         pytest.fail("no host C++ compiler")
-    out = tmp_path_factory.mktemp("l0_groups_plan") / "l0_groups_plan_check"
+    out = tmp_path_factory.mktemp("l0_groups_plan") / "call_plan_check"
     r = subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
                         "-fno-sanitize-recover=all", str(SRC), "-o", str(out)], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
@@ -43,7 +44,7 @@ def _random(seed, n_dead, n=3):
     """layers 0 .. n - 1 with dense random weights, n_dead random input channels of layer 1 zero in every tap"""
     rng = np.random.default_rng(seed)
     net = []
-    for l, (cin, cout, _, _, _) in enumerate(NET[:n]):
+    for l, (cin, cout, *_) in enumerate(NET[:n]):
         w = rng.integers(-8, 8, (cout, 25, cin)).astype(np.int8)
         if l == 1 and n_dead:
             w[:, :, rng.permutation(128)[:n_dead]] = 0
@@ -65,7 +66,7 @@ def _run(exe, d, weights, first=0, last=None, tap=-1, meta=NET):
         f = line.split()
         if f[0] == "L":
             rows[int(f[1])] = {f[i]: int(f[i + 1]) for i in range(2, len(f), 2)}
-        elif f[0] == "P":
+        elif f[0] == "G":
             perm[int(f[1])] = [int(v) for v in f[2:]]
     return [rows[l] for l in range(n)], perm
 
@@ -97,8 +98,9 @@ def _check_images(d, weights, p):
 def test_param_tables(exe, tmp_path):
     weights = _param()
     rows, perm = _run(exe, tmp_path, weights, 0, 7, 3)
-    assert rows[0] == {"live": 80, "nj": 8, "ng": 3, "groups": 3, "groups_in": 4, "variant": 1}, rows[0]
-    assert rows[1] == {"live": 80, "nj": 5, "ng": 4, "groups": 4, "groups_in": 3, "variant": 3}, rows[1]
+    assert rows[0] == {"live": 80, "nj": 8, "ng": 3, "groups": 3, "groups_in": 4, "variant": 1, "halves": 2, "walk": 4}, rows[0]
+    assert rows[1] == {"live": 80, "nj": 5, "ng": 4, "groups": 4, "groups_in": 3, "variant": 3, "halves": 2, "walk": 3}, rows[1]
+    assert [r["walk"] for r in rows[2:]] == [4] * 6 and [r["halves"] for r in rows] == [2] * 7 + [1]
     assert [r["groups"] for r in rows[1:]] == [4] * 7 and [r["groups_in"] for r in rows[2:]] == [4] * 6
     assert [r["ng"] for r in rows[1:]] == [4] * 7
     assert [r["variant"] for r in rows] == [1, 3, 3, 2, 0, 1, 3, 2]      # layers 1 .. 7 as before the groups
@@ -113,7 +115,7 @@ def test_param_calls_that_end_or_tap_at_layer_1(exe, tmp_path):
     for last, tap in ((1, -1), (2, 1)):
         rows, _ = _run(exe, tmp_path, _param(3), 0, last, tap)
         assert (rows[0]["groups"], rows[0]["variant"]) == (3, 1)
-        assert (rows[1]["nj"], rows[1]["groups_in"], rows[1]["variant"]) == (8, 3, 2), rows[1]
+        assert (rows[1]["nj"], rows[1]["groups_in"], rows[1]["variant"], rows[1]["walk"]) == (8, 3, 2, 3), rows[1]
         if last == 2:
             assert (rows[2]["groups_in"], rows[2]["variant"]) == (4, 0), rows[2]
 
@@ -124,6 +126,7 @@ def test_random_dead_sets(exe, tmp_path, n_dead, groups):
     rows, perm = _run(exe, tmp_path, weights)
     assert (rows[0]["live"], rows[0]["ng"], rows[0]["groups"], rows[0]["nj"]) == (128 - n_dead, groups, groups, 8), rows[0]
     assert rows[1]["groups_in"] == groups and rows[0]["variant"] == int(groups == 3) and rows[1]["variant"] >> 1 == int(groups == 3)
+    assert [r["walk"] for r in rows] == [4, groups, 4]
     assert sorted(perm) == ([0] if groups == 3 else [])
     if groups == 3:
         assert _check_images(tmp_path, weights, perm[0]) == 128 - n_dead
@@ -151,3 +154,4 @@ def test_calls_that_keep_four_groups_and_the_standard_handles(exe, tmp_path):
     meta[0][4] = 0
     rows, _ = _run(exe, tmp_path, weights, meta=meta)
     assert (rows[0]["ng"], rows[0]["groups"], rows[0]["variant"], rows[1]["groups_in"]) == (3, 4, 0, 4), rows[0]
+    assert rows[1]["walk"] == 4

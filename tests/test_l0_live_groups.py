@@ -2,7 +2,7 @@
 tests/test_live_geometry.py).
 
 Coverage of positions.  Layer 0 with three groups computes the positions 0 .. 95; a wrong byte at a position whose channel layer 1
-multiplies by zero cannot fail anything.  tests/cpp/l0_groups_plan_check.cpp (the plan header alone, compiled with
+multiplies by zero cannot fail anything.  tests/cpp/call_plan_check.cpp (the plan header alone, compiled with
 -fsanitize=address,undefined) on the weight sets of the GPU file: with 32 dead channels the live ones fill ALL 96 computed positions,
 with 48 (random and PARAM) the positions 0 .. 79, and every one of those is read; the controls keep four groups and no permutation.
 
@@ -24,7 +24,7 @@ from oracle import c_oracle
 from simple_image_compression_network_amd.config import LayerDesc
 
 ROOT = Path(__file__).resolve().parent.parent
-SRC = ROOT / "tests" / "cpp" / "l0_groups_plan_check.cpp"
+SRC = ROOT / "tests" / "cpp" / "call_plan_check.cpp"
 
 
 @pytest.fixture(scope="module")
@@ -32,7 +32,7 @@ def exe(tmp_path_factory):
     cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
     if cxx is None:
         pytest.fail("no host C++ compiler")
-    out = tmp_path_factory.mktemp("l0_live_groups") / "l0_groups_plan_check"
+    out = tmp_path_factory.mktemp("l0_live_groups") / "call_plan_check"
     r = subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
                         "-fno-sanitize-recover=all", str(SRC), "-o", str(out)], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
@@ -45,12 +45,12 @@ def test_live_channels_fill_the_computed_positions_from_zero(exe, tmp_path, wset
         w, b = gc.weights(wset, l)
         gc.okc(w).tofile(tmp_path / f"l{l}.okc")
         b.tofile(tmp_path / f"l{l}.bias")
-    (tmp_path / "meta.txt").write_text("3 128 0 0 1\n128 128 0 1 1\n128 128 0 1 1\n")
+    (tmp_path / "meta.txt").write_text("3 128 0 0 1 0 0\n128 128 0 1 1 0 0\n128 128 0 1 1 0 0\n")
     r = subprocess.run([str(exe), str(tmp_path), "3", "0", "2", "-1"], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr     # a sanitizer report ends the program with an error
     lines = [ln.split() for ln in r.stdout.splitlines()]
     row0 = next(f for f in lines if f[:2] == ["L", "0"])
-    perm = [[int(v) for v in f[2:]] for f in lines if f[:2] == ["P", "0"]]
+    perm = [[int(v) for v in f[2:]] for f in lines if f[:2] == ["G", "0"]]
     n_live = 128 - gc.SETS[wset]
     alive = gc.live_channels(gc.weights(wset, 1)[0])
     assert len(alive) == n_live and int(row0[row0.index("live") + 1]) == n_live

@@ -1,9 +1,10 @@
 """Layer 0 with three of its four 32-channel groups (k_l0<4, 3>, csrc/k_rgb.hip) and layer 1 behind it, on the copies of its weights
 whose K index follows layer 0's permutation (csrc/sicn_live.h, csrc/sicn_abi.hip).  The nets are the first two and three layers of the
 reference's net (tests/l0_groups_cases.py): PARAM weights and random ones whose layer-1 input has 48 or 32 dead channels run three
-groups; 31 and 0 dead channels are the controls on four.  Layer 1 walks all four planes of its input whatever layer 0 stored: plane 3
-holds what the workspace held and meets zero weights, so the whole workspace is filled with seeded random bytes before every call and
-two different fills must give the same bytes.
+groups; 31 and 0 dead channels are the controls on four.  Behind three groups layer 1, on the wide family here, walks the three planes
+that were written (k_conv_g3, tests/test_l1_three_group_walk_gpu.py); plane 3 holds what the workspace held, and a kernel that read it
+would meet zero weights there, so the whole workspace is filled with seeded random bytes before every call and two different fills must
+give the same bytes.
 Geometries (input W x H of layer 0): 2 x 2 and 14 x 10 (less than a tile, less than a strip); 260 x 136 x 3 (layer 0 writes 130 x 68:
 five strips, the last 2 wide, 9 tiles high; layer 1 writes 65 x 34 = 3 x 3 ragged tiles, a workgroup walking tiles across image
 boundaries) and 400 x 180 x 3 (layer 1: 4 x 3 tiles, 4 - 5 per workgroup) on 8 / 16 / all workgroups; 260 x 136 x 3 on the smallest

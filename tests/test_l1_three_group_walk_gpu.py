@@ -10,8 +10,8 @@ walks 3 - 4 of them across image boundaries: the next-tile requests of the tile'
 one workgroup per XCD (the longest chain of tiles); 260 x 136 with the images sized from the chip (the dynamic deal: one call in a
 workspace without deal words, one captured graph replayed twice).  Three layers: layer 1 has 5 columns; two: it is the call's last and
 has 8; a tap at layer 1: 8 columns in the middle of a chain.
-Every case first asserts what ran — sicn_debug_net_walk_groups (computed by the function the launch chooses its kernel by),
-sicn_debug_net_groups, sicn_debug_net_columns, the families of sicn_debug_plan — then compares every byte with the C oracle's direct
+Every case first asserts what ran — sicn_debug_net_walk_groups, sicn_debug_net_groups and sicn_debug_net_columns (fields of the call plan that sicn_net_forward executes:
+live::plan_call, csrc/sicn_live.h), the families of sicn_debug_plan — then compares every byte with the C oracle's direct
 form, with the whole workspace filled with two different seeded garbage patterns."""
 import ctypes
 

@@ -1,7 +1,7 @@
 """What keeps tests/test_live_geometry_gpu.py from hiding a failure, checked where no GPU is needed.
 
 Coverage of positions.  A live kernel with NJ columns computes the positions of the columns 0 .. NJ - 1 (16 NJ of 128); a wrong byte at
-a position whose channel the consumer multiplies by zero cannot fail anything.  tests/cpp/live_plan_check.cpp (the plan header alone,
+a position whose channel the consumer multiplies by zero cannot fail anything.  tests/cpp/call_plan_check.cpp (the plan header alone,
 compiled with -fsanitize=address,undefined as tests/test_live_plan.py does) on the weight sets of the GPU file: with 80 dead channels the
 live ones fill ALL 48 positions of 3 columns, with 48 dead all 80 of 5 columns - and with 112 dead, the only 3-column case with random
 weights that the suite had, 16 of the 48.
@@ -25,7 +25,7 @@ import live_geometry_cases as lg
 from oracle import c_oracle
 
 ROOT = Path(__file__).resolve().parent.parent
-SRC = ROOT / "tests" / "cpp" / "live_plan_check.cpp"
+SRC = ROOT / "tests" / "cpp" / "call_plan_check.cpp"
 SEED = 20                                    # tests/test_live_geometry_gpu.py
 CHAINS = [("conv", "conv"), ("deconv", "rgb"), ("deconv", "deconv"), ("conv", "conv", "conv192"), ("deconv", "deconv", "rgb")]
 
@@ -35,7 +35,7 @@ def exe(tmp_path_factory):
     cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
     if cxx is None:
         pytest.fail("no host C++ compiler")
-    out = tmp_path_factory.mktemp("live_geometry") / "live_plan_check"
+    out = tmp_path_factory.mktemp("live_geometry") / "call_plan_check"
     r = subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
                         "-fno-sanitize-recover=all", str(SRC), "-o", str(out)], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
@@ -47,7 +47,8 @@ def _plan(exe, d, kinds, wts):
     for l, (w, b) in enumerate(wts):
         lg.okc(w).tofile(d / f"l{l}.okc")
         b.tofile(d / f"l{l}.bias")
-    (d / "meta.txt").write_text("".join(f"128 {lg.KINDS[k][0]} 0 {int(k in ('conv', 'deconv'))}\n" for k in kinds))
+    (d / "meta.txt").write_text("".join(f"128 {lg.KINDS[k][0]} 0 {int(k in ('conv', 'deconv'))} {2 if lg.KINDS[k][3] else 1} {lg.KINDS[k][3]} {int(k == 'rgb')}\n"
+                                          for k in kinds))
     r = subprocess.run([str(exe), str(d), str(len(kinds)), "0", str(len(kinds) - 1), "-1"], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr     # a sanitizer report ends the program with an error
     live, nj, perm = {}, {}, {}

@@ -1,4 +1,4 @@
-"""The live-channel plan (csrc/sicn_live.h) without a GPU: tests/cpp/live_plan_check.cpp is the plan header and nothing else, compiled
+"""The live-channel plan (csrc/sicn_live.h) without a GPU: tests/cpp/call_plan_check.cpp is the plan header and nothing else, compiled
 here with -fsanitize=address,undefined and run on weight sets written to a temporary directory.  What it says about a call is held to
 the reference's PARAM tables and to numpy statements of the same permutation.
 The device images themselves are not packed here.  The packers (pack_mfma16_stream, pack_mfma16x_deconv_stream, pack_l7, ...) live in
@@ -16,10 +16,12 @@ import pytest
 from oracle import sicn_ref
 
 ROOT = Path(__file__).resolve().parent.parent
-SRC = ROOT / "tests" / "cpp" / "live_plan_check.cpp"
+SRC = ROOT / "tests" / "cpp" / "call_plan_check.cpp"
 GOLDEN = ROOT / "tests" / "golden" / "param_weights.npz"
-# (cin, cout, gdn, planned onto the wide family) of the reference's eight layers on a large input
-NET = [(3, 128, 0, 0), (128, 128, 0, 1), (128, 128, 0, 1), (128, 192, 0, 0), (192, 128, 0, 0), (128, 128, 0, 1), (128, 128, 0, 1), (128, 3, 0, 0)]
+# (cin, cout, gdn, planned onto the wide family, layout towards the next layer: 1 = GROUP, 2 = PHASE, transposed, on the layer-7 family)
+# of the reference's eight layers on a large input
+NET = [(3, 128, 0, 0, 1, 0, 0), (128, 128, 0, 1, 1, 0, 0), (128, 128, 0, 1, 1, 0, 0), (128, 192, 0, 0, 1, 0, 0), (192, 128, 0, 0, 2, 1, 0),
+       (128, 128, 0, 1, 2, 1, 0), (128, 128, 0, 1, 2, 1, 0), (128, 3, 0, 0, 0, 1, 1)]
 
 
 @pytest.fixture(scope="module")
@@ -27,7 +29,7 @@ def exe(tmp_path_factory):
     cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
     if cxx is None:
         pytest.fail("no host C++ compiler")
-    out = tmp_path_factory.mktemp("live_plan") / "live_plan_check"
+    out = tmp_path_factory.mktemp("live_plan") / "call_plan_check"
     r = subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
                         "-fno-sanitize-recover=all", str(SRC), "-o", str(out)], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
@@ -42,7 +44,7 @@ def _param():
 def _random(seed, n_dead):
     rng = np.random.default_rng(seed)
     net = []
-    for cin, cout, _, _ in NET:
+    for cin, cout, *_ in NET:
         w = rng.integers(-8, 8, (cout, 25, cin)).astype(np.int8)
         if cin == 128 and n_dead:
             w[:, :, rng.permutation(128)[:n_dead]] = 0
@@ -50,22 +52,27 @@ def _random(seed, n_dead):
     return net
 
 
-def _run(exe, d, weights, first=0, last=7, tap=3, meta=NET):
+def _run_rows(exe, d, weights, first=0, last=7, tap=3, meta=NET):
+    """per layer the fields of its line as a dict, and the permutations of the layers that skip columns"""
     for l, (w, b) in enumerate(weights):
         w.tofile(d / f"l{l}.okc")
         b.tofile(d / f"l{l}.bias")
     (d / "meta.txt").write_text("".join(" ".join(map(str, m)) + "\n" for m in meta))
     r = subprocess.run([str(exe), str(d), str(len(weights)), str(first), str(last), str(tap)], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr     # a sanitizer report ends the program with an error
-    live, nj, perm = {}, {}, {}
+    rows, perm = {}, {}
     for line in r.stdout.splitlines():
         f = line.split()
         if f[0] == "L":
-            live[int(f[1])], nj[int(f[1])] = int(f[3]), int(f[5])
+            rows[int(f[1])] = {f[i]: int(f[i + 1]) for i in range(2, len(f), 2)}
         elif f[0] == "P":
             perm[int(f[1])] = [int(v) for v in f[2:]]
-    n = len(weights)
-    return [live[l] for l in range(n)], [nj[l] for l in range(n)], perm
+    return [rows[l] for l in range(len(weights))], perm
+
+
+def _run(exe, d, weights, first=0, last=7, tap=3, meta=NET):
+    rows, perm = _run_rows(exe, d, weights, first, last, tap, meta)
+    return [r["live"] for r in rows], [r["nj"] for r in rows], perm
 
 
 def _column(pos):
@@ -129,11 +136,39 @@ def test_gdn_and_other_families_keep_every_column(exe, tmp_path):
     assert nj[1] == 8 and live[1] == 128 and nj[5] == 8 and nj[2] == 5 and nj[6] == 3 and sorted(perm) == [2, 6], (live, nj)
 
 
+def test_halves_and_walk_of_the_param_tables(exe, tmp_path):
+    """layer 7 behind at most 4 columns in the GROUP or PHASE layout reads 1 half, otherwise 2; a wide conv behind three groups walks 3
+    groups, a deconv 4"""
+    rows, _ = _run_rows(exe, tmp_path, _param())
+    assert rows[6]["nj"] == 3 and [r["halves"] for r in rows] == [2] * 7 + [1], rows
+    assert rows[0]["groups"] == 3 and [r["walk"] for r in rows] == [4, 3] + [4] * 6, rows
+    for layout, halves in ((1, 1), (0, 2)):
+        meta = [list(m) for m in NET]
+        meta[6][4] = layout       # layer 6 hands layer 7 the GROUP layout / NHWC
+        rows, _ = _run_rows(exe, tmp_path, _param(), meta=meta)
+        assert rows[6]["nj"] == 3 and rows[7]["halves"] == halves, rows[7]
+    rows, _ = _run_rows(exe, tmp_path, _param(), 4, 7, -1)      # layer 5 runs 5 columns, layer 6 3: only layer 7 reads a half
+    assert [r["halves"] for r in rows] == [2] * 7 + [1] and [r["walk"] for r in rows] == [4] * 8, rows
+    rows, _ = _run_rows(exe, tmp_path, _param(), 0, 7, 6)       # a tap at layer 6: it computes all 8 columns and leaves in NHWC
+    assert rows[6]["nj"] == 8 and rows[7]["halves"] == 2, rows
+    meta = [list(m) for m in NET]
+    meta[1][5] = 1                # layer 1 as a deconv behind layer 0's three groups
+    rows, _ = _run_rows(exe, tmp_path, _param(), meta=meta)
+    assert (rows[0]["groups"], rows[1]["groups_in"], rows[1]["walk"]) == (3, 3, 4), rows[1]
+    meta = [list(m) for m in NET]
+    meta[1][3] = 0                # layer 1 not on the wide family
+    rows, _ = _run_rows(exe, tmp_path, _param(), meta=meta)
+    assert (rows[1]["groups_in"], rows[1]["walk"]) == (3, 4), rows[1]
+
+
 @pytest.mark.parametrize("n_dead, want", [(0, 8), (47, 8), (48, 5), (79, 5), (80, 3), (112, 3), (127, 3)])
 def test_random_weights(exe, tmp_path, n_dead, want):
     """dense weights skip nothing; 81 live channels are 6 columns, which run on the next width that is built: all 8"""
     weights = _random(n_dead, n_dead)
-    live, nj, perm = _run(exe, tmp_path, weights)
+    rows, perm = _run_rows(exe, tmp_path, weights)
+    live, nj = [r["live"] for r in rows], [r["nj"] for r in rows]
+    assert rows[7]["halves"] == (1 if want == 3 else 2) and [r["halves"] for r in rows[:7]] == [2] * 7, rows
+    assert rows[1]["walk"] == (3 if 128 - n_dead <= 96 else 4) and [r["walk"] for r in rows[2:]] == [4] * 6, rows
     assert [nj[l] for l in (1, 2, 5, 6)] == [want] * 4 and [nj[l] for l in (0, 3, 4, 7)] == [8] * 4, nj
     assert [live[l] for l in (0, 1, 2, 5, 6)] == [128 - n_dead] * 5
     assert sorted(perm) == ([1, 2, 5, 6] if want < 8 else [])

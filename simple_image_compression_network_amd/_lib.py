@@ -291,6 +291,17 @@ RAGGED_PLANAR_ABI = {
 }
 RAGGED_PIXELS = {"interleaved": 0, "planar": 1}   # SICN_RAGGED_PIXELS_INTERLEAVED / SICN_RAGGED_PIXELS_PLANAR
 
+# include/sicn_ragged_rect.h (the last layer of a ragged net stores a rectangle of every reconstruction, in either pixel layout, at
+# origins of the net's or from the caller's device memory; sicn_version() stays 17 — these symbols being present is the marker)
+RAGGED_RECT_ABI = {
+    "sicn_ragged_net_create_rect": (_i, [_descp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _i, _i32p, _i32p, _i, _i, _i, _i, _rectp,
+                                         ctypes.POINTER(_vp)]),
+    "sicn_ragged_rect_layout": (_i, [_descp, _i, _i32p, _i32p, _i, _rectp, _i, _i64p]),
+    "sicn_ragged_net_forward_at": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _vp, _sz, _vp, _vp]),
+    "sicn_ragged_roi_move_origins": (_vp, [_vp]),
+    "sicn_ragged_ctx_roi_move_origins": (_vp, [_vp]),
+}
+
 
 class RaggedRoiSlot(ctypes.Structure):
     """ctypes image of `sicn_ragged_roi_slot` (include/sicn_ragged_roi_move.h)."""
@@ -381,7 +392,7 @@ def lib() -> ctypes.CDLL:
         L = ctypes.CDLL(str(LIB_PATH))
         for name, (res, args) in {**ABI, **CODEC_ABI, **CONVLAYER_ABI, **GDN_ABI, **RAGGED_ABI, **RAGGED_HYPER_ABI, **RAGGED_CODEC_ABI, **RAGGED_CTX_ABI, **RAGGED_ARCHIVE_ABI,
                                   **RAGGED_ARCHIVE_SELECT_ABI, **RAGGED_WINDOW_ABI, **RAGGED_CTX_WINDOW_ABI, **CTX_SL_ABI, **RAGGED_RGB_ABI, **RAGGED_ROI_MOVE_ABI,
-                                  **RAGGED_CTX_ROI_MOVE_ABI, **RAGGED_PLANAR_ABI}.items():
+                                  **RAGGED_CTX_ROI_MOVE_ABI, **RAGGED_PLANAR_ABI, **RAGGED_RECT_ABI}.items():
             fn = getattr(L, name)          # AttributeError if the ABI is incomplete
             fn.restype = res
             fn.argtypes = args

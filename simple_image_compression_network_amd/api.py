@@ -435,15 +435,38 @@ def _refuse_planar(net, what):
         raise ValueError(f"{what}: the ROI decodes have no planar form; make the net with rgb_layout='interleaved'")
 
 
-def _roi_chain(net, plans, rects, bands, first_rows):
+def _roi_options(net, what, roi_layout, direct):
+    """The keywords `roi_layout` and `direct` of an ROI decode -> (layout, direct).  roi_layout None is today's chain: interleaved
+    pixels, and a net with planar pixels is refused.  "interleaved" or "planar" name the layout of the ROI pixels whatever the net's
+    own layout is — it plays no part in layers 4-7.  direct: layer 7 stores the rectangles itself (include/sicn_ragged_rect.h), no
+    reconstruction tensor and no cut launch; None means True for planar, which has no other form, and False for interleaved."""
+    if roi_layout is None:
+        _refuse_planar(net, what)
+        roi_layout = "interleaved"
+    elif roi_layout not in _lib.RAGGED_PIXELS:
+        raise ValueError(f"roi_layout: 'interleaved' or 'planar', not {roi_layout!r}")
+    if direct is None:
+        direct = roi_layout == "planar"
+    if roi_layout == "planar" and not direct:
+        raise ValueError("roi_layout='planar' has no form with a pixel cut: direct must be True (or None)")
+    return roi_layout, bool(direct)
+
+
+def _roi_chain(net, plans, rects, bands, first_rows, roi_layout="interleaved", direct=False):
     """What follows a window decoder in an ROI decode, shared by RaggedRoi and hyperprior.RaggedHyperpriorRoi: (the latent cut, the
     window net, the pixel cut).  bands: per image (the latent rows its band holds, the band's byte offset in the band tensor);
     first_rows: the band row at which the plan's row r0 lies.  The window net runs layers 4 .. on `net`'s weights, descs and GDN
-    objects over the sizes (16 cw, 16 rh)."""
+    objects over the sizes (16 cw, 16 rh).  direct: the window net is made with the rectangles (x, y, w, h) inside the windows'
+    reconstructions, its last layer writes the ROI pixels in `roi_layout` and there is no pixel cut (None)."""
     lat = net.shapes(3)
     latent_cut = RaggedCut([(rows, w) for (rows, _), (_, w, _) in zip(bands, lat)],
                            [(p["c0"], y0, p["cw"], p["rh"]) for p, y0 in zip(plans, first_rows)], lat[0][2],
                            src_offsets=[off for _, off in bands], device=net.device)
+    if direct:
+        window_net = RaggedNet([(16 * p["cw"], 16 * p["rh"]) for p in plans], device=net.device, shared_weights=net.weights,
+                               descs=net.descs, gdn=net.gdn, out_rects=[(p["x"], p["y"], r[2], r[3]) for p, r in zip(plans, rects)],
+                               out_layout=roi_layout)
+        return latent_cut, window_net, None
     window_net = RaggedNet([(16 * p["cw"], 16 * p["rh"]) for p in plans], device=net.device, shared_weights=net.weights,
                            descs=net.descs, gdn=net.gdn)
     pixel_cut = RaggedCut([(16 * p["rh"], 16 * p["cw"]) for p in plans], [(p["x"], p["y"], r[2], r[3]) for p, r in zip(plans, rects)],
@@ -458,10 +481,12 @@ class RaggedRoi:
     (16 cw, 16 rh) on `net`'s weights, the cut of the rectangle.  Same bytes as the full decode, sliced.
     rects: one (x0, y0, w, h) per image, or None for that image whole.  One rectangle per image: two details of one photograph are
     two objects (and, through an archive, two calls).  coder: the RaggedLatentCoder whose slots hold the containers (default: a new
-    one from net.latent_coder(stream_symbols))."""
+    one from net.latent_coder(stream_symbols)).
+    roi_layout, direct: see `_roi_options`.  With `direct`, layer 7 of the window net stores the rectangles itself — [h][w][3] or,
+    planar, [3][h][w] per image: seven launches, no reconstruction tensor; `pixel_cut` is None."""
 
-    def __init__(self, net, rects, coder=None, stream_symbols=16384):
-        _refuse_planar(net, "RaggedRoi")
+    def __init__(self, net, rects, coder=None, stream_symbols=16384, roi_layout=None, direct=None):
+        self.roi_layout, self.direct = _roi_options(net, "RaggedRoi", roi_layout, direct)
         n = len(net.sizes)
         if len(rects) != n:
             raise ValueError(f"rects: one per image, {n}")
@@ -476,22 +501,27 @@ class RaggedRoi:
         # a band begins inside a stream: rows from r0 on, `lead` bytes in
         self.latent_cut, self.window_net, self.pixel_cut = _roi_chain(
             net, self.plans, self.rects, [(p["rh"], int(im.band_offset) + int(im.lead)) for p, im in zip(self.plans, self.window.images)],
-            [0] * n)
+            [0] * n, self.roi_layout, self.direct)
         self.status = self.window.status
 
     def decode(self, slots=None, valid=None, stream=None, out=None):
-        """The coder's slots (or `slots`, `valid` as in RaggedLatentCoder.decode) -> the ROI pixels, a ragged [h][w][3] tensor.
-        Enqueue only: eight launches.  `self.status` holds the window decoder's verdicts."""
+        """The coder's slots (or `slots`, `valid` as in RaggedLatentCoder.decode) -> the ROI pixels, a ragged [h][w][3] tensor
+        ([3][h][w] per image with roi_layout="planar").  Enqueue only: eight launches, seven with `direct`.  `self.status` holds the
+        window decoder's verdicts."""
         import torch
         dev = self.net.device
         self.band = torch.empty(self.window.band_bytes, dtype=torch.uint8, device=dev)
         self.window.decode(self.band, slots=slots, valid=valid, stream=stream)
         self.latent = self.latent_cut.run(self.band, stream=stream)
+        if self.direct:
+            return self.window_net.run_layers(4, len(self.net.descs) - 1, self.latent, out=out, stream=stream)[0]
         recon, _ = self.window_net.run_layers(4, len(self.net.descs) - 1, self.latent, stream=stream)
         return self.pixel_cut.run(recon, out, stream=stream)
 
     def views(self, roi):
-        """Per-image [h][w][3] views of what `decode` returned."""
+        """Per-image [h][w][3] views of what `decode` returned ([3][h][w] with roi_layout="planar")."""
+        if self.direct:
+            return self.window_net.views(len(self.net.descs) - 1, roi)
         return self.pixel_cut.views(roi)
 
 
@@ -502,9 +532,9 @@ class _MovingRoiChain(_lib.Handle):
     `_slot_type` and the number of its layout's totals in `_n_totals` (the first five are the tensors' bytes)."""
     _abi, _slot_type, _n_totals = "", None, 0
 
-    def _check_slots(self, net, slots):
-        """-> self.slots, or ValueError before anything is made."""
-        _refuse_planar(net, type(self).__name__)
+    def _check_slots(self, net, slots, roi_layout=None, direct=None):
+        """-> self.slots, self.roi_layout, self.direct (`_roi_options`), or ValueError before anything is made."""
+        self.roi_layout, self.direct = _roi_options(net, type(self).__name__, roi_layout, direct)
         self.slots = [tuple(int(v) for v in s) for s in slots]
         if len(self.slots) < 1 or any(len(s) != 3 for s in self.slots):
             raise ValueError("slots: at least one (image, w, h)")
@@ -529,17 +559,24 @@ class _MovingRoiChain(_lib.Handle):
         self._h = ctypes.c_void_p()
         with torch.cuda.device(self.device):
             _lib.check(getattr(L, self._abi + "_create")(c._h, self._cslots, n, ctypes.byref(self._h)), self._abi + "_create")
-        # the window net: layers 4 .. on `net`'s weights, descs and GDN objects over the sizes (16 cw_cap, 16 rh_cap)
+        # the window net: layers 4 .. on `net`'s weights, descs and GDN objects over the sizes (16 cw_cap, 16 rh_cap); direct: with
+        # the rectangles (0, 0, w, h) of the slots, moved on every decode to the origins the place kernel leaves in the object
         self.window_net = RaggedNet([(16 * int(s.cw_cap), 16 * int(s.rh_cap)) for s in self.layout], device=self.device,
-                                    shared_weights=net.weights, descs=net.descs, gdn=net.gdn)
+                                    shared_weights=net.weights, descs=net.descs, gdn=net.gdn,
+                                    **(dict(out_rects=[(0, 0, w, h) for _, w, h in self.slots], out_layout=self.roi_layout)
+                                       if self.direct else {}))
         self._last = len(net.descs) - 1
-        if self.window_net.nbytes(3) != self.latent_bytes or self.window_net.nbytes(self._last) != self.recon_bytes:
+        if self.window_net.nbytes(3) != self.latent_bytes or self.window_net.nbytes(self._last) != (self.roi_bytes if self.direct
+                                                                                                   else self.recon_bytes):
             raise RuntimeError("the window net's tensors are not the layout's")
+        if self.direct and self.window_net._offsets[self._last + 1] != [int(s.roi_offset) for s in self.layout]:
+            raise RuntimeError("the window net's rectangles do not lie where the layout puts the ROI pixels")
+        self._origins = ctypes.c_void_p(getattr(L, self._abi + "_origins")(self._h)) if self.direct else None
         self.window_net.workspace()
         u8 = dict(dtype=torch.uint8, device=self.device)
         self.band = torch.empty(max(self.band_bytes, 16), **u8)
         self.latent = torch.empty(self.latent_bytes, **u8)
-        self.recon = torch.empty(self.recon_bytes, **u8)
+        self.recon = None if self.direct else torch.empty(self.recon_bytes, **u8)
         self.roi = torch.empty(self.roi_bytes, **u8)
         self.ws = torch.empty(max(int(getattr(L, self._abi + "_workspace_bytes")(self._h)), ws_bytes, 256), **u8)
         self.status = torch.zeros((n, 2), dtype=torch.int32, device=self.device)
@@ -571,17 +608,24 @@ class _MovingRoiChain(_lib.Handle):
         _lib.check(getattr(L, self._abi + "_decode_async")(
             self._h, vp(xy.data_ptr()), *coder_args, vp(self.band.data_ptr()), vp(self.latent.data_ptr()), vp(self.status.data_ptr()),
             vp(self.flags.data_ptr()), vp(self.ws.data_ptr()), self.ws.numel(), sp), self._abi + "_decode_async")
-        self.window_net.run_layers(4, self._last, self.latent, out=self.recon, stream=stream)
-        _lib.check(getattr(L, self._abi + "_cut_async")(self._h, vp(self.recon.data_ptr()), vp(out.data_ptr()), sp), self._abi + "_cut_async")
+        if self.direct:
+            # layer 7 stores the placed rectangles itself, at the origins the place kernel has just written on this stream
+            self.window_net.run_layers(4, self._last, self.latent, out=out, stream=stream, origins=self._origins)
+        else:
+            self.window_net.run_layers(4, self._last, self.latent, out=self.recon, stream=stream)
+            _lib.check(getattr(L, self._abi + "_cut_async")(self._h, vp(self.recon.data_ptr()), vp(out.data_ptr()), sp),
+                       self._abi + "_cut_async")
         if self.uniform:
-            return out.view(len(self.slots), self.slots[0][2], self.slots[0][1], 3)
+            _, w, h = self.slots[0]
+            return out.view(len(self.slots), *((3, h, w) if self.roi_layout == "planar" else (h, w, 3)))
         return out
 
     def views(self, roi):
-        """Per-slot [h][w][3] views of what `decode` returned."""
+        """Per-slot [h][w][3] views of what `decode` returned ([3][h][w] with roi_layout="planar")."""
         flat = roi.reshape(-1)
         _check_tensor(flat, (self.roi_bytes,), "roi")
-        return [flat[int(s.roi_offset):int(s.roi_offset) + h * w * 3].view(h, w, 3) for s, (_, w, h) in zip(self.layout, self.slots)]
+        return [flat[int(s.roi_offset):int(s.roi_offset) + h * w * 3].view(*((3, h, w) if self.roi_layout == "planar" else (h, w, 3)))
+                for s, (_, w, h) in zip(self.layout, self.slots)]
 
 
 class MovingRoi(_MovingRoiChain):
@@ -592,12 +636,14 @@ class MovingRoi(_MovingRoiChain):
     coder: the RaggedLatentCoder whose slots hold the containers (default: a new one from net.latent_coder(stream_symbols)); after
     `RaggedArchive.unpack(images=...)` into it, an archive serves any number of moves.  Same bytes as the full decode, sliced; a
     position outside [0, image - size] is clamped and bit 0 of the slot's `.flags` word says so.
-    `.status`: device int32 [n_slots][2], the window decoder's verdicts per slot; `.flags`: device int32 [n_slots]."""
+    `.status`: device int32 [n_slots][2], the window decoder's verdicts per slot; `.flags`: device int32 [n_slots].
+    roi_layout, direct: see `_roi_options`.  With `direct`, layer 7 of the window net stores the placed rectangles itself, at the
+    origins the placement leaves on the device — eight launches, `recon` is None and no pixel cut runs."""
     _free, _abi, _slot_type, _n_totals = "sicn_ragged_roi_move_free", "sicn_ragged_roi_move", _lib.RaggedRoiMoveSlot, 6
 
-    def __init__(self, net, slots, coder=None, stream_symbols=16384):
+    def __init__(self, net, slots, coder=None, stream_symbols=16384, roi_layout=None, direct=None):
         self.net = net
-        self._check_slots(net, slots)
+        self._check_slots(net, slots, roi_layout, direct)
         self.coder = c = coder if coder is not None else net.latent_coder(stream_symbols)
         lat = net.shapes(3)
         if [(h, w) for h, w, _ in lat] != c.shapes or lat[0][2] != c.lat_c or c.image_sizes != net.sizes:
@@ -644,13 +690,18 @@ class RaggedNet(_lib.Handle):
     within the chain-rule size — the top-left corner of every reconstruction is stored, nothing else.  None: the images' sizes where
     the chain begins with a conv 3 -> N and every image fits its reconstruction (the eight layers: no `cropped` pass is needed),
     the chain-rule sizes otherwise.  An end of the chain that is not such a layer stays as it is: on a chain with neither, "planar"
-    makes the interleaved net (`planar_in`, `planar_out` say which ends are planar)."""
+    makes the interleaved net (`planar_in`, `planar_out` say which ends are planar).
+    `out_rects`: [(x0, y0, w, h)] per image (include/sicn_ragged_rect.h), with either `rgb_layout`, exclusive with `out_sizes`: the
+    last layer — a deconv N -> 3 without an activation of its own — stores that rectangle of every reconstruction and nothing else,
+    [h][w][3] or [3][h][w] per image; `shapes`, `nbytes`, `views`, `pack` and `kernel_for` of the last boundary follow, and
+    `run_layers(origins=)` moves the rectangles.  `out_layout`: the layout of that output where it is not `rgb_layout`'s (a window
+    net writes planar rectangles while its own input end, which it never runs, stays as it is)."""
     _free = "sicn_ragged_net_free"
 
     def __init__(self, sizes, params=None, device=None, n_ch: int = 128, m_ch: int = 192,
                  shared_weights: Optional[Sequence[DeviceWeights]] = None, descs: Optional[Sequence[LayerDesc]] = None,
                  gdn: Optional[Sequence[Optional["GDN"]]] = None, rgb_ends: str = "packed", rgb_layout: str = "interleaved",
-                 out_sizes=None):
+                 out_sizes=None, out_rects=None, out_layout: Optional[str] = None):
         import torch
         if rgb_ends not in _lib.RAGGED_RGB_ENDS:
             raise ValueError(f"rgb_ends: 'packed' or 'generic', not {rgb_ends!r}")
@@ -678,12 +729,32 @@ class RaggedNet(_lib.Handle):
         self.planar_out = planar and bool(self.descs[-1].transposed) and self.descs[-1].OFM_CH == 3
         if out_sizes is not None and not self.planar_out:
             raise ValueError("out_sizes: only a planar output (rgb_layout='planar', a chain that ends with deconv N -> 3) has sizes of its own")
-        if out_sizes is None and self.planar_out and self.planar_in:
+        if out_sizes is None and out_rects is None and self.planar_out and self.planar_in:
             chain = self.sizes
             for d in self.descs:
                 chain = [(2 * w, 2 * h) if d.transposed else (-(-w // 2), -(-h // 2)) for w, h in chain]
             if all(w <= cw and h <= ch for (w, h), (cw, ch) in zip(self.sizes, chain)):
                 out_sizes = self.sizes
+        if out_rects is not None:
+            if out_sizes is not None:
+                raise ValueError("out_rects and out_sizes exclude each other: a rectangle has its own size")
+            if rgb_ends != "packed":
+                raise ValueError("out_rects needs rgb_ends='packed': the generic family has no rectangle form")
+            if out_layout is not None and out_layout not in _lib.RAGGED_PIXELS:
+                raise ValueError(f"out_layout: 'interleaved' or 'planar', not {out_layout!r}")
+            if not (n > 0 and self.descs[-1].transposed and self.descs[-1].OFM_CH == 3):
+                raise ValueError("out_rects: the chain must end with a deconv N -> 3")
+            if gdn is not None and len(gdn) == n and gdn[-1] is not None:
+                raise ValueError("out_rects: the last layer must not carry a GDN / IGDN")
+            self.out_rects = [tuple(int(v) for v in r) for r in out_rects]
+            if len(self.out_rects) != len(self.sizes) or any(len(r) != 4 for r in self.out_rects):
+                raise ValueError(f"out_rects: one (x0, y0, w, h) per image, {len(self.sizes)}")
+            if out_layout is not None:
+                self.planar_out = out_layout == "planar"
+        else:
+            if out_layout is not None:
+                raise ValueError("out_layout: only with out_rects")
+            self.out_rects = None
         self.out_sizes = None if out_sizes is None else [(int(w), int(h)) for w, h in out_sizes]
         if self.out_sizes is not None and len(self.out_sizes) != len(self.sizes):
             raise ValueError(f"out_sizes: one (width, height) per image, {len(self.sizes)}")
@@ -702,11 +773,22 @@ class RaggedNet(_lib.Handle):
         if self.out_sizes is not None:
             self._out_widths = (ctypes.c_int32 * max(n_img, 1))(*[w for w, _ in self.out_sizes])
             self._out_heights = (ctypes.c_int32 * max(n_img, 1))(*[h for _, h in self.out_sizes])
+        self._crects = None
+        if self.out_rects is not None:
+            self._crects = (_lib.RaggedRect * max(n_img, 1))(*[_lib.RaggedRect(*r) for r in self.out_rects])
+            rc = L.sicn_ragged_rect_layout(self._cdescs, n, self._widths, self._heights, n_img, self._crects, 0, (ctypes.c_int64 * 5)())
+            if rc == -22:
+                raise ValueError(f"out_rects {self.out_rects}: a rectangle is empty, has a negative corner or reaches beyond its reconstruction")
         with torch.cuda.device(self.device):
-            _lib.check(L.sicn_ragged_net_create_planar(self._cdescs, handles, ghandles, n, self._widths, self._heights, n_img,
-                                                       _lib.RAGGED_RGB_ENDS[rgb_ends], int(self.planar_in), int(self.planar_out),
-                                                       self._out_widths, self._out_heights, ctypes.byref(self._h)),
-                       "sicn_ragged_net_create_planar")
+            if self.out_rects is not None:
+                _lib.check(L.sicn_ragged_net_create_rect(self._cdescs, handles, ghandles, n, self._widths, self._heights, n_img,
+                                                         _lib.RAGGED_RGB_ENDS[rgb_ends], int(self.planar_in), int(self.planar_out),
+                                                         self._crects, ctypes.byref(self._h)), "sicn_ragged_net_create_rect")
+            else:
+                _lib.check(L.sicn_ragged_net_create_planar(self._cdescs, handles, ghandles, n, self._widths, self._heights, n_img,
+                                                           _lib.RAGGED_RGB_ENDS[rgb_ends], int(self.planar_in), int(self.planar_out),
+                                                           self._out_widths, self._out_heights, ctypes.byref(self._h)),
+                           "sicn_ragged_net_create_planar")
         # per boundary (-1 .. n - 1, index layer + 1): the images' shapes and byte offsets, as the library lays them out
         self._shapes, self._offsets, self._nbytes = [], [], []
         q = (ctypes.c_int64 * 8)()
@@ -722,7 +804,17 @@ class RaggedNet(_lib.Handle):
         # a planar boundary: (3, h, w) per image; the output at its own sizes and offsets (sicn_ragged_planar_layout)
         if self.planar_in:
             self._shapes[0] = [(c, h, w) for h, w, c in self._shapes[0]]
-        if self.planar_out:
+        if self.out_rects is not None:
+            shapes, offs, q5 = [], [], (ctypes.c_int64 * 5)()
+            self.live_tiles = []        # per image: the tiles of the last layer that meet the rectangle at the creation's origin
+            for i in range(n_img):
+                _lib.check(L.sicn_ragged_rect_layout(self._cdescs, n, self._widths, self._heights, n_img, self._crects, i, q5),
+                           "sicn_ragged_rect_layout")
+                shapes.append((3, int(q5[1]), int(q5[0])) if self.planar_out else (int(q5[1]), int(q5[0]), 3))
+                offs.append(int(q5[2]))
+                self.live_tiles.append(int(q5[4]))
+            self._shapes[n], self._offsets[n], self._nbytes[n] = shapes, offs, int(q5[3])
+        elif self.planar_out:
             shapes, offs = [], []
             for i in range(n_img):
                 _lib.check(L.sicn_ragged_planar_layout(self._cdescs, n, self._widths, self._heights, n_img, 1, self._out_widths,
@@ -746,7 +838,8 @@ class RaggedNet(_lib.Handle):
 
     def kernel_for(self, layer: int) -> str:
         """The kernel `layer` runs on (sicn_ragged_net_kernel_for): "mfma_conv_any", "mfma_deconv_any", "mfma_conv_rgb_packed" or
-        "mfma_deconv_rgb_packed"; "mfma_conv_rgb_planar" and "mfma_deconv_rgb_planar" at a planar boundary."""
+        "mfma_deconv_rgb_packed"; "mfma_conv_rgb_planar" and "mfma_deconv_rgb_planar" at a planar boundary;
+        "mfma_deconv_rgb_rect" and "mfma_deconv_rgb_planar_rect" for the last layer of a net with `out_rects`."""
         name = _lib.lib().sicn_ragged_net_kernel_for(self._h, int(layer))
         if name is None:
             raise ValueError("layer out of range")
@@ -779,11 +872,25 @@ class RaggedNet(_lib.Handle):
             self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         return self._ws
 
-    def run_layers(self, first: int, last: int, packed_in, tap_layer: int = -1, out=None, tap=None, stream=None):
-        """Layers [first, last] over the whole batch (sicn_ragged_net_forward); returns (out, tap or None), ragged tensors."""
+    def run_layers(self, first: int, last: int, packed_in, tap_layer: int = -1, out=None, tap=None, stream=None, origins=None):
+        """Layers [first, last] over the whole batch (sicn_ragged_net_forward_at); returns (out, tap or None), ragged tensors.
+        origins: on a net with `out_rects` and with `last` the last layer, a contiguous CUDA int32 tensor [n_images][2] of (x0, y0)
+        per image, read when the last layer runs, in place of the creation's origins.  Every value is admissible: the part of a
+        rectangle that lies outside its reconstruction is not written."""
         import torch
         if not 0 <= first <= last < len(self.descs):
             raise ValueError("layer range")
+        origins_ptr = ctypes.c_void_p(0)
+        if origins is not None:
+            if self.out_rects is None or last != len(self.descs) - 1:
+                raise ValueError("origins: only on a net made with out_rects, and only when the last layer runs")
+            if isinstance(origins, ctypes.c_void_p):        # the table a moving ROI object owns (sicn_ragged_roi_move_origins)
+                origins_ptr = origins
+            elif not (isinstance(origins, torch.Tensor) and origins.is_cuda and origins.dtype == torch.int32 and origins.is_contiguous()
+                      and tuple(origins.shape) == (len(self.sizes), 2)):
+                raise TypeError(f"origins: a contiguous CUDA int32 tensor of shape ({len(self.sizes)}, 2)")
+            else:
+                origins_ptr = ctypes.c_void_p(origins.data_ptr())
         _check_tensor(packed_in, (self.nbytes(first - 1),), "in")
         if out is None:
             out = torch.empty(self.nbytes(last), dtype=torch.uint8, device=packed_in.device)
@@ -797,10 +904,10 @@ class RaggedNet(_lib.Handle):
         else:
             tap = None
         ws = self.workspace()
-        _lib.check(_lib.lib().sicn_ragged_net_forward(self._h, first, last, ctypes.c_void_p(packed_in.data_ptr()),
-                                                      ctypes.c_void_p(out.data_ptr()), tap_layer, tap_ptr,
-                                                      ctypes.c_void_p(ws.data_ptr()), ws.numel(), _stream_ptr(stream)),
-                   "sicn_ragged_net_forward")
+        _lib.check(_lib.lib().sicn_ragged_net_forward_at(self._h, first, last, ctypes.c_void_p(packed_in.data_ptr()),
+                                                         ctypes.c_void_p(out.data_ptr()), tap_layer, tap_ptr,
+                                                         ctypes.c_void_p(ws.data_ptr()), ws.numel(), origins_ptr, _stream_ptr(stream)),
+                   "sicn_ragged_net_forward_at")
         return out, tap
 
     def forward(self, packed_in, out=None, latent=None, stream=None):
@@ -840,10 +947,10 @@ class RaggedNet(_lib.Handle):
             raise ValueError("decompress_archive(rois=...) has not run")
         return self._last_roi.views(roi_pixels)
 
-    def moving_roi(self, slots, coder=None, stream_symbols=16384):
+    def moving_roi(self, slots, coder=None, stream_symbols=16384, roi_layout=None, direct=None):
         """A MovingRoi over this net: `slots` = (image, w, h) per slot, positions given per `decode` call, from device memory.
-        ValueError for a net with planar pixels."""
-        return MovingRoi(self, slots, coder=coder, stream_symbols=stream_symbols)
+        ValueError for a net with planar pixels unless `roi_layout` names the layout of the ROI pixels."""
+        return MovingRoi(self, slots, coder=coder, stream_symbols=stream_symbols, roi_layout=roi_layout, direct=direct)
 
     def latent_coder(self, stream_symbols=None):
         """A codec.RaggedLatentCoder for this net's latents (boundary 3) and image sizes: the whole batch in 3 + 2 launches.
@@ -925,7 +1032,7 @@ class RaggedNet(_lib.Handle):
             raise ValueError("an image of the selection has no container to read its size from")
         return cls(sizes, **net_kwargs)
 
-    def decompress_archive(self, b, out=None, stream=None, images=None, rois=None):
+    def decompress_archive(self, b, out=None, stream=None, images=None, rois=None, roi_layout=None, direct=None):
         """An archive of this net's images (e.g. from `compress_archive`) -> the reconstructions as a ragged tensor of boundary 7:
         upload, the two launches that unpack it, the ragged decoder, layers 4-7.  Raises when the work has finished if the archive
         was refused or a container fails to decode.
@@ -936,12 +1043,14 @@ class RaggedNet(_lib.Handle):
         rectangles need are decoded (RaggedRoi: eight launches behind the unpack), and the result is the ROI pixels as a ragged
         [h][w][3] tensor (`roi_views` gives them per image), the bytes of the full decode sliced.  A wrong length or a rectangle
         outside its image is a ValueError before any launch.  One rectangle per image per call: two details of one photograph are
-        two calls.  The window cannot check the checksum of the whole latent; every other verdict raises as without `rois`."""
+        two calls.  The window cannot check the checksum of the whole latent; every other verdict raises as without `rois`.
+        `roi_layout`, `direct` (with `rois`): as in RaggedRoi — "planar" gives [3][h][w] per image, `direct` lets layer 7 store the
+        rectangles itself."""
         import torch
         from . import codec
         info = codec.archive_info(b)
         if rois is not None:
-            _refuse_planar(self, "decompress_archive(rois=)")
+            roi_layout, direct = _roi_options(self, "decompress_archive(rois=)", roi_layout, direct)
             if len(rois) != len(self.sizes):
                 raise ValueError(f"rois: one rectangle (or None) per decoded image, {len(self.sizes)}")
             rois = tuple(None if r is None else tuple(int(v) for v in r) for r in rois)
@@ -957,9 +1066,9 @@ class RaggedNet(_lib.Handle):
         key, coder = self._coder_for([int(h.stream_symbols) for h in heads])
         archive = self._archive_for(key)
         if rois is not None:
-            if (key, rois) not in self._rois:
-                self._rois[(key, rois)] = RaggedRoi(self, rois, coder=coder)
-            roi = self._last_roi = self._rois[(key, rois)]
+            if (key, rois, roi_layout, direct) not in self._rois:
+                self._rois[(key, rois, roi_layout, direct)] = RaggedRoi(self, rois, coder=coder, roi_layout=roi_layout, direct=direct)
+            roi = self._last_roi = self._rois[(key, rois, roi_layout, direct)]
             valid, = archive.unpack(b, stream=stream, images=sel)
             out = roi.decode(valid=valid, stream=stream, out=out)
             archive.check()

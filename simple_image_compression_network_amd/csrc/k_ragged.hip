@@ -18,17 +18,22 @@
 //
 // A net with PLANAR pixels (include/sicn_ragged_planar.h) runs the planar siblings of the packed RGB kernels at the boundary that is
 // planar; a planar output has sizes of its own (planar_out_plan), which reach the kernel through the PlanarOut table.
+//
+// A net with RECTANGLES (include/sicn_ragged_rect.h) runs the deconv N -> 3 with the rectangle epilogue in either layout: the sizes
+// and offsets through the same PlanarOut table, the origins through an int32 [n_images][2] table of the net's or the caller's.
 #include <new>
 #include <vector>
 
 #include "../../include/sicn_ragged_hyper.h"
 #include "../../include/sicn_ragged_planar.h"
+#include "../../include/sicn_ragged_rect.h"
 #include "../../include/sicn_ragged_rgb.h"
 #include "../../include/sicn_ragged_window.h"
 #include "device_table.hpp"
 #include "k_any_body.hpp"
 #include "k_ragged_common.hpp"
 #include "ragged_planar_host.hpp"
+#include "ragged_rect_host.hpp"
 #include "ragged_rgb_host.hpp"
 #include "sicn_gdn_internal.h"
 
@@ -160,6 +165,43 @@ static int planar_out_plan(const RaggedPlan &plan, const sicn_layer_desc *descs,
     return SICN_OK;
 }
 
+// The output boundary of a net with rectangles: per image the rectangle's size and the byte offset of its 3 h w bytes (the same in
+// both layouts), the origins (x0, y0) back to back, the tensor's bytes and, where asked for, the live tiles per image.  The last layer
+// must be a deconv N -> 3 on the packed kernels without an activation of its own; a rectangle lies inside its reconstruction.
+static int rect_out_plan(const RaggedPlan &plan, const sicn_layer_desc *descs, int n_layers, int n_images, int pixels_out,
+                         const sicn_ragged_rect *rects, std::vector<PlanarOut> *cuts, std::vector<int32_t> *origins, int64_t *bytes,
+                         std::vector<int64_t> *live)
+{
+    if (pixels_out != SICN_RAGGED_PIXELS_INTERLEAVED && pixels_out != SICN_RAGGED_PIXELS_PLANAR) return SICN_EINVAL;
+    const sicn_layer_desc &d = descs[n_layers - 1];
+    if (!(d.transposed == 1 && d.OFM_CH == 3) || !plan.layers[(size_t)n_layers - 1].packed) return SICN_EINVAL;
+    const RaggedBoundary &b = plan.bounds[(size_t)n_layers], &bi = plan.bounds[(size_t)n_layers - 1];
+    cuts->resize((size_t)n_images);
+    origins->resize(2 * (size_t)n_images);
+    if (live) live->assign((size_t)n_images, 0);
+    int64_t off = 0;
+    for (int i = 0; i < n_images; i++) {
+        const sicn_ragged_rect r = rects ? rects[i] : sicn_ragged_rect{0, 0, b.W[(size_t)i], b.H[(size_t)i]};
+        if (r.w < 1 || r.h < 1 || r.x0 < 0 || r.y0 < 0) return SICN_EINVAL;
+        if ((int64_t)r.x0 + r.w > b.W[(size_t)i] || (int64_t)r.y0 + r.h > b.H[(size_t)i]) return SICN_EINVAL;
+        (*cuts)[(size_t)i] = PlanarOut{r.w, r.h, off};
+        (*origins)[2 * (size_t)i] = r.x0;
+        (*origins)[2 * (size_t)i + 1] = r.y0;
+        off += (int64_t)r.h * r.w * 3;
+        if (live) {
+            // the test is a product of a row test and a column test: count the rows in the tile column that holds x0 (live in x
+            // by construction) and the columns in the tile row that holds y0
+            const int cx = r.x0 / RECT_TILE_OUT * ANY_T, cy = r.y0 / RECT_TILE_OUT * ANY_T;
+            int64_t ny = 0, nx = 0;
+            for (int ty = 0; ty < bi.H[(size_t)i]; ty += ANY_T) ny += rect_tile_live(ty, cx, r.x0, r.y0, r.w, r.h);
+            for (int tx = 0; tx < bi.W[(size_t)i]; tx += ANY_T) nx += rect_tile_live(cy, tx, r.x0, r.y0, r.w, r.h);
+            (*live)[(size_t)i] = ny * nx;
+        }
+    }
+    *bytes = off;
+    return SICN_OK;
+}
+
 template <bool DECONV, int NT>
 static hipError_t launch_ragged_as(const uint8_t *in, uint8_t *out, const int8_t *wimg, const int8_t *bias, const RaggedRow *rows,
                                    const uint32_t *tile_image, int cin, int cout, unsigned items, uint32_t floor2, hipStream_t stream)
@@ -193,7 +235,9 @@ struct sicn_ragged_net {
     size_t slot = 0;                        // bytes of one ping-pong buffer
     bool planar_in = false, planar_out = false;   // include/sicn_ragged_planar.h: the pixel layout of boundary -1 and of boundary n - 1
     int64_t out_bytes = 0;                  // bytes of boundary n - 1 as this net lays it out
-    DeviceTable<PlanarOut> d_cuts;          // planar out: [n_images] the sizes and offsets of the output
+    DeviceTable<PlanarOut> d_cuts;          // planar or rectangle out: [n_images] the sizes and offsets of the output
+    bool rect_out = false;                  // include/sicn_ragged_rect.h: the last layer stores a rectangle of every reconstruction
+    DeviceTable<int32_t> d_origins;         // rectangle out: [n_images][2] the creation's origins (x0, y0)
 };
 
 extern "C" int sicn_ragged_layout(const sicn_layer_desc *descs, int n_layers, const int32_t *widths, const int32_t *heights, int n_images,
@@ -252,6 +296,7 @@ extern "C" const char *sicn_ragged_net_kernel_for(const sicn_ragged_net *net, in
     if (!net || layer < 0 || layer >= net->n_layers) return nullptr;
     const bool tr = net->descs[(size_t)layer].transposed == 1;
     if (layer == 0 && net->planar_in) return "mfma_conv_rgb_planar";
+    if (layer == net->n_layers - 1 && net->rect_out) return net->planar_out ? "mfma_deconv_rgb_planar_rect" : "mfma_deconv_rgb_rect";
     if (layer == net->n_layers - 1 && net->planar_out) return "mfma_deconv_rgb_planar";
     if (net->plan.layers[(size_t)layer].packed) return tr ? "mfma_deconv_rgb_packed" : "mfma_conv_rgb_packed";
     return tr ? "mfma_deconv_any" : "mfma_conv_any";
@@ -286,10 +331,54 @@ extern "C" int sicn_ragged_planar_layout(const sicn_layer_desc *descs, int n_lay
     return SICN_OK;
 }
 
+// every creation ends here: out_widths / out_heights as sicn_ragged_net_create_planar takes them, or rects as
+// sicn_ragged_net_create_rect does (then without sizes)
+static int create_net(const sicn_layer_desc *descs, sicn_weights *const *weights, const sicn_gdn *const *gdn, int n_layers,
+                      const int32_t *widths, const int32_t *heights, int n_images, int rgb_ends, int pixels_in, int pixels_out,
+                      const int32_t *out_widths, const int32_t *out_heights, const sicn_ragged_rect *rects, sicn_ragged_net **out);
+
 extern "C" int sicn_ragged_net_create_planar(const sicn_layer_desc *descs, sicn_weights *const *weights, const sicn_gdn *const *gdn,
                                              int n_layers, const int32_t *widths, const int32_t *heights, int n_images, int rgb_ends,
                                              int pixels_in, int pixels_out, const int32_t *out_widths, const int32_t *out_heights,
                                              sicn_ragged_net **out)
+{
+    return create_net(descs, weights, gdn, n_layers, widths, heights, n_images, rgb_ends, pixels_in, pixels_out, out_widths, out_heights,
+                      nullptr, out);
+}
+
+extern "C" int sicn_ragged_net_create_rect(const sicn_layer_desc *descs, sicn_weights *const *weights, const sicn_gdn *const *gdn,
+                                           int n_layers, const int32_t *widths, const int32_t *heights, int n_images, int rgb_ends,
+                                           int pixels_in, int pixels_out, const sicn_ragged_rect *rects, sicn_ragged_net **out)
+{
+    return create_net(descs, weights, gdn, n_layers, widths, heights, n_images, rgb_ends, pixels_in, pixels_out, nullptr, nullptr, rects, out);
+}
+
+extern "C" int sicn_ragged_rect_layout(const sicn_layer_desc *descs, int n_layers, const int32_t *widths, const int32_t *heights,
+                                       int n_images, const sicn_ragged_rect *rects, int image, int64_t out[5])
+{
+    if (!out) return SICN_EINVAL;
+    RaggedPlan p;
+    if (int rc = ragged_plan(descs, n_layers, widths, heights, n_images, SICN_RAGGED_RGB_PACKED, &p)) return rc;
+    std::vector<PlanarOut> cuts;
+    std::vector<int32_t> origins;
+    std::vector<int64_t> live;
+    int64_t bytes = 0;
+    try {
+        if (int rc = rect_out_plan(p, descs, n_layers, n_images, SICN_RAGGED_PIXELS_INTERLEAVED, rects, &cuts, &origins, &bytes, &live))
+            return rc;
+    } catch (const std::bad_alloc &) { return SICN_ENOMEM; }
+    if (image < 0 || image >= n_images) return SICN_EINVAL;
+    out[0] = cuts[(size_t)image].w;
+    out[1] = cuts[(size_t)image].h;
+    out[2] = cuts[(size_t)image].off;
+    out[3] = bytes;
+    out[4] = live[(size_t)image];
+    return SICN_OK;
+}
+
+static int create_net(const sicn_layer_desc *descs, sicn_weights *const *weights, const sicn_gdn *const *gdn, int n_layers,
+                      const int32_t *widths, const int32_t *heights, int n_images, int rgb_ends, int pixels_in, int pixels_out,
+                      const int32_t *out_widths, const int32_t *out_heights, const sicn_ragged_rect *rects, sicn_ragged_net **out)
 {
     if (!out) return SICN_EINVAL;
     *out = nullptr;
@@ -302,6 +391,13 @@ extern "C" int sicn_ragged_net_create_planar(const sicn_layer_desc *descs, sicn_
         std::vector<PlanarOut> cuts;
         if (int rc = planar_out_plan(net.plan, descs, n_layers, n_images, pixels_out, out_widths, out_heights, &cuts, &net.out_bytes)) return rc;
         net.planar_out = pixels_out == SICN_RAGGED_PIXELS_PLANAR;
+        // rectangles: the same table with the rectangles' sizes, and the origins beside it
+        std::vector<int32_t> origins;
+        if (rects) {
+            if (rgb_ends != SICN_RAGGED_RGB_PACKED || (gdn && gdn[n_layers - 1])) return SICN_EINVAL;
+            if (int rc = rect_out_plan(net.plan, descs, n_layers, n_images, pixels_out, rects, &cuts, &origins, &net.out_bytes, nullptr)) return rc;
+            net.rect_out = true;
+        }
         if ((net.planar_in || net.planar_out) && rgb_ends != SICN_RAGGED_RGB_PACKED) return SICN_EINVAL;
         if (net.planar_in && !(descs[0].transposed == 0 && descs[0].IFM_CH == 3)) return SICN_EINVAL;
         if (net.planar_out && gdn && gdn[n_layers - 1]) return SICN_EINVAL;
@@ -335,7 +431,8 @@ extern "C" int sicn_ragged_net_create_planar(const sicn_layer_desc *descs, sicn_
         }
         net.slot = (mx + 255) / 256 * 256;
         if (!net.d_rows.upload(rows) || !map.upload(net.d_tile_image)) return SICN_ENOMEM;
-        if (net.planar_out && !net.d_cuts.upload(cuts)) return SICN_ENOMEM;
+        if ((net.planar_out || net.rect_out) && !net.d_cuts.upload(cuts)) return SICN_ENOMEM;
+        if (net.rect_out && !net.d_origins.upload(origins)) return SICN_ENOMEM;
         // the weight image: weights of a width the specialised families serve were uploaded without one (sicn_weights_from_finn_tiles
         // packs the images of the family the shape runs on); pack it here from the plain [cout][25 cin] copy every handle has
         for (int l = 0; l < n_layers; l++) {
@@ -368,7 +465,15 @@ extern "C" size_t sicn_ragged_net_workspace_bytes(const sicn_ragged_net *net) { 
 extern "C" int sicn_ragged_net_forward(const sicn_ragged_net *net, int first, int last, const uint8_t *in, uint8_t *out, int tap_layer,
                                        uint8_t *tap_out, void *workspace, size_t workspace_bytes, void *hip_stream)
 {
+    return sicn_ragged_net_forward_at(net, first, last, in, out, tap_layer, tap_out, workspace, workspace_bytes, nullptr, hip_stream);
+}
+
+extern "C" int sicn_ragged_net_forward_at(const sicn_ragged_net *net, int first, int last, const uint8_t *in, uint8_t *out, int tap_layer,
+                                          uint8_t *tap_out, void *workspace, size_t workspace_bytes, const int32_t *origins_dev,
+                                          void *hip_stream)
+{
     if (!net || !in || !out) return SICN_EINVAL;
+    if (origins_dev && (!net->rect_out || last != net->n_layers - 1 || ((uintptr_t)origins_dev & 3u))) return SICN_EINVAL;
     if (first < 0 || last >= net->n_layers || first > last) return SICN_EINVAL;
     if (tap_layer >= 0 && (tap_layer < first || tap_layer > last || !tap_out)) return SICN_EINVAL;
     if (last > first && (!workspace || workspace_bytes < 2 * net->slot)) return SICN_ENOSPC;
@@ -387,12 +492,15 @@ extern "C" int sicn_ragged_net_forward(const sicn_ragged_net *net, int first, in
         const int8_t *wimg = net->wimg[(size_t)l];
         const sicn_gdn *g = net->gdn[(size_t)l];
         const uint32_t floor2 = g ? ACT_FLOOR_RAW : ACT_FLOOR_RELU;
-        const bool planar_out = net->planar_out && l == net->n_layers - 1;
+        const bool planar_out = net->planar_out && l == net->n_layers - 1, rect_out = net->rect_out && l == net->n_layers - 1;
         const size_t in_bytes = (size_t)net->plan.bounds[(size_t)l].off[(size_t)net->n_images];
-        const size_t out_bytes = planar_out ? (size_t)net->out_bytes : (size_t)net->plan.bounds[(size_t)l + 1].off[(size_t)net->n_images];
+        const size_t out_bytes = planar_out || rect_out ? (size_t)net->out_bytes : (size_t)net->plan.bounds[(size_t)l + 1].off[(size_t)net->n_images];
         hipError_t e;
         if (net->planar_in && l == 0)
             e = launch_ragged_rgb_conv_planar(cur, in_bytes, dst, wimg, w->d_bias, rows, map, d.OFM_CH, items, floor2, stream);
+        else if (rect_out)
+            e = launch_ragged_rgb_deconv_rect(planar_out, cur, dst, wimg, w->d_bias, rows, map, net->d_cuts.get(),
+                                              origins_dev ? origins_dev : net->d_origins.get(), d.IFM_CH, items, floor2, stream);
         else if (planar_out)
             e = launch_ragged_rgb_deconv_planar(cur, dst, wimg, w->d_bias, rows, map, net->d_cuts.get(), d.IFM_CH, items, floor2, stream);
         else if (net->plan.layers[(size_t)l].packed)

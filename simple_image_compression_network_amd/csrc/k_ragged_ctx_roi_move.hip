@@ -24,6 +24,7 @@
 #include "../../include/sicn_ctx_stream_length.h"
 #include "ctx_roi_move_host.hpp"
 #include "k_ctx_body.hpp"
+#include "../../include/sicn_ragged_rect.h"
 #include "k_roi_move_common.hpp"
 
 namespace {
@@ -62,13 +63,13 @@ __global__ __launch_bounds__(1024) void k_ctx_roi_scan(const uint8_t *__restrict
 __global__ __launch_bounds__(64) void k_ctx_roi_place(const int32_t *__restrict__ xy, const SlotRow *__restrict__ srows, uint32_t n_slots,
                                                       const CtxRow *__restrict__ rows, uint8_t *__restrict__ workspace,
                                                       MoveRow *__restrict__ mrows, CutRow *__restrict__ lat_rows, CutRow *__restrict__ pix_rows,
-                                                      uint32_t *__restrict__ flags)
+                                                      uint32_t *__restrict__ flags, int32_t *__restrict__ origins)
 {
     const uint32_t slot = blockIdx.x * 64u + threadIdx.x;
     if (slot >= n_slots) return;
     const SlotRow s = srows[slot];
     sicn_roi_move::store_placement(slot, sicn_ctx_roi_move::place_slot(s, xy[2 * (size_t)slot], xy[2 * (size_t)slot + 1]), mrows, lat_rows,
-                                   pix_rows, flags);
+                                   pix_rows, flags, origins);
     const CtxRow *r = rows + s.image;
     CtxWorkspace w;
     ctx_carve(w, workspace + r->ws_off, r->g.nst[0] + r->g.nst[1], wstream_cap(r->g.S));
@@ -236,7 +237,7 @@ extern "C" int sicn_ragged_ctx_roi_move_decode_async(const sicn_ragged_ctx_roi_m
     const unsigned n_slots = (unsigned)mv->n_slots;
     const auto &t = mv->t;
     hipLaunchKernelGGL(k_ctx_roi_place, dim3((n_slots + 63) / 64), dim3(64), 0, stream, xy_dev, t.d_srows.get(), n_slots, mv->d_rows, ws,
-                       t.d_mrows.mut(), t.d_lat_rows.mut(), t.d_pix_rows.mut(), flags_dev);
+                       t.d_mrows.mut(), t.d_lat_rows.mut(), t.d_pix_rows.mut(), flags_dev, t.d_origins.mut());
     // the full decoder's reason: a non-anchor's class reads its neighbours' bytes whatever they hold
     if (hipMemsetAsync(band, 0, (size_t)mv->totals.band, stream) != hipSuccess) return SICN_ENODEV;
     hipLaunchKernelGGL(k_ctx_roi_move_decode<0>, dim3((unsigned)mv->totals.items[0]), dim3(64 * CTX_WPB_DEC), 0, stream, containers, scales, band, ws,
@@ -248,6 +249,11 @@ extern "C" int sicn_ragged_ctx_roi_move_decode_async(const sicn_ragged_ctx_roi_m
                        t.d_mrows.get());
     if (hipGetLastError() != hipSuccess) return SICN_ENODEV;
     return t.cut(false, band, window_latent, hip_stream);
+}
+
+extern "C" const int32_t *sicn_ragged_ctx_roi_move_origins(const sicn_ragged_ctx_roi_move *mv)
+{
+    return mv ? mv->t.d_origins.get() : nullptr;
 }
 
 extern "C" int sicn_ragged_ctx_roi_move_cut_async(const sicn_ragged_ctx_roi_move *mv, const uint8_t *recon, uint8_t *roi_out, void *hip_stream)

@@ -18,6 +18,7 @@
 
 #include "../../include/sicn_ragged_roi_move.h"
 #include "k_codec_body.hpp"
+#include "../../include/sicn_ragged_rect.h"
 #include "k_roi_move_common.hpp"
 
 namespace {
@@ -28,12 +29,12 @@ using sicn_window::CutRow;
 
 __global__ __launch_bounds__(64) void k_roi_place(const int32_t *__restrict__ xy, const SlotRow *__restrict__ srows, uint32_t n_slots,
                                                   MoveRow *__restrict__ mrows, CutRow *__restrict__ lat_rows, CutRow *__restrict__ pix_rows,
-                                                  uint32_t *__restrict__ flags)
+                                                  uint32_t *__restrict__ flags, int32_t *__restrict__ origins)
 {
     const uint32_t slot = blockIdx.x * 64u + threadIdx.x;
     if (slot >= n_slots) return;
     sicn_roi_move::store_placement(slot, sicn_roi_move::place_slot(srows[slot], xy[2 * (size_t)slot], xy[2 * (size_t)slot + 1]), mrows, lat_rows,
-                                   pix_rows, flags);
+                                   pix_rows, flags, origins);
 }
 
 // the slot's image as the stage bodies see it: the coder's row with the slot's own workspace block
@@ -188,7 +189,7 @@ extern "C" int sicn_ragged_roi_move_decode_async(const sicn_ragged_roi_move *mv,
     const unsigned n_slots = (unsigned)mv->n_slots, items = (unsigned)mv->totals.items;
     const auto &t = mv->t;
     hipLaunchKernelGGL(k_roi_place, dim3((n_slots + 63) / 64), dim3(64), 0, stream, xy_dev, t.d_srows.get(), n_slots, t.d_mrows.mut(),
-                       t.d_lat_rows.mut(), t.d_pix_rows.mut(), flags_dev);
+                       t.d_lat_rows.mut(), t.d_pix_rows.mut(), flags_dev, t.d_origins.mut());
     if (mv->bigtab)
         hipLaunchKernelGGL(k_roi_move_decode<true>, dim3(items), dim3(64), 0, stream, containers, valid, band, ws, mv->d_rows, t.d_srows.get(),
                            t.d_mrows.get(), mv->d_item_slot.get());
@@ -200,6 +201,8 @@ extern "C" int sicn_ragged_roi_move_decode_async(const sicn_ragged_roi_move *mv,
     if (hipGetLastError() != hipSuccess) return SICN_ENODEV;
     return t.cut(false, band, window_latent, hip_stream);
 }
+
+extern "C" const int32_t *sicn_ragged_roi_move_origins(const sicn_ragged_roi_move *mv) { return mv ? mv->t.d_origins.get() : nullptr; }
 
 extern "C" int sicn_ragged_roi_move_cut_async(const sicn_ragged_roi_move *mv, const uint8_t *recon, uint8_t *roi_out, void *hip_stream)
 {

@@ -22,6 +22,7 @@
 #pragma once
 #include "k_any_body.hpp"
 #include "ragged_planar_host.hpp"
+#include "ragged_rect_host.hpp"
 #include "ragged_rgb_host.hpp"
 
 namespace sicn {
@@ -160,10 +161,14 @@ __device__ __forceinline__ void rgb_conv_tile_planar(const uint8_t *__restrict__
 // epilogue differs: the lane stores one byte into each plane where its pixel lies inside the cut; the pixels outside are computed
 // and not stored.  Across the 16 lanes of a row group the bytes of a plane are 2 apart and the phase g & 1 fills the gaps: 32
 // consecutive bytes per plane.
-template <bool PLANAR>
+// RECT (include/sicn_ragged_rect.h): om = the image's own 3 OH OW bytes, [OH][OW][3] or planes [3][OH][OW], which hold the rectangle
+// (RX0, RY0, OW, OH) of the [2 IH][2 IW] reconstruction.  Again only the epilogue differs (ragged_rect_host.hpp): a pixel is stored iff
+// it is inside the rectangle, at the address its in-rectangle coordinates give.  The caller has returned already where the tile's
+// 32 x 32 output pixels do not meet the rectangle.
+template <bool PLANAR, bool RECT = false>
 __device__ __forceinline__ void rgb_deconv_tile(const uint8_t *__restrict__ im, uint8_t *__restrict__ om, const int8_t *__restrict__ wimg,
                                                 const int8_t *__restrict__ bias, int IW, int IH, int C, int OW, int OH, int y0, int x0,
-                                                uint32_t floor2, uint8_t *smem)
+                                                uint32_t floor2, uint8_t *smem, int32_t RX0 = 0, int32_t RY0 = 0)
 {
     constexpr int EDGE = ANY_DECONV_EDGE;
     constexpr int UNITS = EDGE * EDGE * 4;                     // 16-byte units of one chunk's patch
@@ -224,7 +229,15 @@ __device__ __forceinline__ void rgb_deconv_tile(const uint8_t *__restrict__ im, 
 #pragma unroll
     for (int c = 0; c < 4; c++) {
         const int my = y0 + 4 * wv + c, mx = x0 + col;
-        if constexpr (PLANAR) {
+        if constexpr (RECT) {
+            const int oy = 2 * my + (g >> 1), ox = 2 * mx + (g & 1);
+            if (!rect_stored(oy, ox, 2 * IW, 2 * IH, RX0, RY0, OW, OH)) continue;
+            const uint32_t ry = rect_rel(oy, RY0), rx = rect_rel(ox, RX0);
+            const uint32_t q = pack4_relu7(acc[c][0], acc[c][1], acc[c][2], acc[c][3], floor2);
+            om[rect_at<PLANAR>(0, ry, rx, OW, OH)] = (uint8_t)q;
+            om[rect_at<PLANAR>(1, ry, rx, OW, OH)] = (uint8_t)(q >> 8);
+            om[rect_at<PLANAR>(2, ry, rx, OW, OH)] = (uint8_t)(q >> 16);
+        } else if constexpr (PLANAR) {
             const int oy = 2 * my + (g >> 1), ox = 2 * mx + (g & 1);
             if (!planar_stored(oy, ox, OW, OH)) continue;
             const uint32_t q = pack4_relu7(acc[c][0], acc[c][1], acc[c][2], acc[c][3], floor2);

@@ -19,6 +19,9 @@ struct MoveTables {
     // changes nothing on the host, and what the device holds is the last placement's by contract
     mutable sicn::DeviceTable<Move> d_mrows;
     mutable sicn::DeviceTable<CutRow> d_lat_rows, d_pix_rows;
+    // [n_slots][2]: the placed rectangle's corner (x, y) inside its window reconstruction — the origins a window net made with
+    // rectangles reads in place of the pixel cut (include/sicn_ragged_rect.h)
+    mutable sicn::DeviceTable<int32_t> d_origins;
 
     // The rows the placement writes start as the placement of (0, 0): a cut that runs before any decode stays in bounds.
     bool build(const std::vector<Slot> &srows)
@@ -26,6 +29,7 @@ struct MoveTables {
         sicn::ItemMap lat_map, pix_map;
         std::vector<Move> mrows;
         std::vector<CutRow> lat_rows, pix_rows;
+        std::vector<int32_t> origins;
         for (size_t k = 0; k < srows.size(); k++) {
             const Slot &s = srows[k];
             lat_map.add((uint32_t)((s.rh_cap + CUT_ROWS - 1) / CUT_ROWS), (uint32_t)k);
@@ -34,11 +38,13 @@ struct MoveTables {
             mrows.push_back(p.win);
             lat_rows.push_back(p.lat_cut);
             pix_rows.push_back(p.pix_cut);
+            origins.push_back(p.ax.inside);
+            origins.push_back(p.ay.inside);
         }
         lat_items = (unsigned)lat_map.size();
         pix_items = (unsigned)pix_map.size();
         return d_srows.upload(srows) && lat_map.upload(d_lat_item_slot) && pix_map.upload(d_pix_item_slot) && d_mrows.upload(mrows) &&
-               d_lat_rows.upload(lat_rows) && d_pix_rows.upload(pix_rows);
+               d_lat_rows.upload(lat_rows) && d_pix_rows.upload(pix_rows) && d_origins.upload(origins);
     }
 
     // k_ragged_cut over the rows of the last placement: band -> window latent, or (pixels) reconstruction -> ROI pixels
@@ -51,11 +57,13 @@ struct MoveTables {
     }
 };
 
-// the four words of a placement that both place kernels store: the streams the slot selects now, the two CutRows, the flags word
+// the five words of a placement that both place kernels store: the streams the slot selects now, the two CutRows, the flags word and
+// the corner inside the window reconstruction (origins: int32 [n_slots][2], 8-byte aligned)
 template <class Placed, class Move>
 __device__ __forceinline__ void store_placement(uint32_t slot, const Placed &p, Move *__restrict__ mrows, CutRow *__restrict__ lat_rows,
-                                                CutRow *__restrict__ pix_rows, uint32_t *__restrict__ flags)
+                                                CutRow *__restrict__ pix_rows, uint32_t *__restrict__ flags, int32_t *__restrict__ origins)
 {
+    reinterpret_cast<int2 *>(origins)[slot] = int2{p.ax.inside, p.ay.inside};
     mrows[slot] = p.win;
     lat_rows[slot] = p.lat_cut;
     pix_rows[slot] = p.pix_cut;

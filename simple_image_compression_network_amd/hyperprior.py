@@ -303,16 +303,16 @@ class RaggedHyperpriorCodec:
         self._scale_map(self.z_hat)
         return y_valid
 
-    def roi(self, rects):
+    def roi(self, rects, roi_layout=None, direct=None):
         """A RaggedHyperpriorRoi over this codec: one pixel rectangle (x0, y0, w, h), or None, per image."""
-        return RaggedHyperpriorRoi(self, rects)
+        return RaggedHyperpriorRoi(self, rects, roi_layout=roi_layout, direct=direct)
 
-    def moving_roi(self, slots):
+    def moving_roi(self, slots, roi_layout=None, direct=None):
         """A MovingHyperpriorRoi over this codec: `slots` = (image, w, h) per slot, positions given per `decode` call, from device
         memory."""
-        return MovingHyperpriorRoi(self, slots)
+        return MovingHyperpriorRoi(self, slots, roi_layout=roi_layout, direct=direct)
 
-    def decode(self, out=None, z_containers=None, y_containers=None, archive=None, images=None, rois=None):
+    def decode(self, out=None, z_containers=None, y_containers=None, archive=None, images=None, rois=None, roi_layout=None, direct=None):
         """Containers (default: the last encode's; else lists of `bytes`, one per image; or `archive`, what `archive()` returned) ->
         the reconstructions, a ragged tensor of main's boundary 7 (`main.cropped(out)` cuts them to the images' sizes; a planar main
         writes them at those sizes).  An archive is
@@ -323,11 +323,12 @@ class RaggedHyperpriorCodec:
         `rois`: one (x0, y0, w, h) per image, or None for that image whole — `roi(rois).decode(...)` in one call: only the y streams,
         latent columns and pixels the rectangles need are decoded, and the result is the ROI pixels as a ragged [h][w][3] tensor
         (`roi_views` gives them per image), the bytes of the full decode cut to the rectangles.  A wrong length or a rectangle outside
-        its image is a ValueError before any launch."""
+        its image is a ValueError before any launch.  `roi_layout`, `direct` (with `rois`): as in RaggedHyperpriorRoi."""
         if rois is not None:
-            key = tuple(None if r is None else tuple(int(v) for v in r) for r in rois)
+            rects = tuple(None if r is None else tuple(int(v) for v in r) for r in rois)
+            key = (rects,) + api._roi_options(self.main, "decode(rois=)", roi_layout, direct)
             if key not in self._rois:
-                self._rois[key] = RaggedHyperpriorRoi(self, key)
+                self._rois[key] = RaggedHyperpriorRoi(self, rects, roi_layout=roi_layout, direct=direct)
             self._last_roi = self._rois[key]
             return self._last_roi.decode(archive=archive, images=images, z_containers=z_containers, y_containers=y_containers, out=out)
         self._last_roi = None
@@ -384,10 +385,12 @@ class RaggedHyperpriorRoi:
 
     Same bytes as `codec.decode` + `main.cropped`, sliced.  rects: one (x0, y0, w, h) per image, or None for that image whole;
     ValueError before anything is made for a wrong length or a rectangle outside its image.  Also `codec.roi(rects)` and, in one
-    call, `codec.decode(..., rois=rects)`."""
+    call, `codec.decode(..., rois=rects)`.
+    roi_layout, direct: see `api._roi_options`.  With `direct`, layer 7 of the window net stores the rectangles itself — [h][w][3]
+    or, planar, [3][h][w] per image — and the last cut is gone; `pixel_cut` is None."""
 
-    def __init__(self, codec_, rects):
-        api._refuse_planar(codec_.main, "RaggedHyperpriorRoi")
+    def __init__(self, codec_, rects, roi_layout=None, direct=None):
+        self.roi_layout, self.direct = api._roi_options(codec_.main, "RaggedHyperpriorRoi", roi_layout, direct)
         n = len(codec_.sizes)
         if len(rects) != n:
             raise ValueError(f"rects: one per image, {n}")
@@ -398,7 +401,7 @@ class RaggedHyperpriorRoi:
         self.window = codec_.y_coder.window([(p["r0"], p["rh"]) for p in self.plans])
         self.latent_cut, self.window_net, self.pixel_cut = api._roi_chain(
             net, self.plans, self.rects, [(int(im.band_rows), int(im.band_offset)) for im in self.window.images[:n]],
-            [p["r0"] - int(im.band_row0) for p, im in zip(self.plans, self.window.images)])
+            [p["r0"] - int(im.band_row0) for p, im in zip(self.plans, self.window.images)], self.roi_layout, self.direct)
         self.status = self.window.status
 
     def decode(self, archive=None, images=None, z_containers=None, y_containers=None, out=None):
@@ -418,11 +421,15 @@ class RaggedHyperpriorRoi:
             c._external += [buf, status]
             self.window.decode(self.band, c.s, slots=buf, valid=status)
         self.latent = self.latent_cut.run(self.band)
+        if self.direct:
+            return self.window_net.run_layers(4, len(c.main.descs) - 1, self.latent, out=out)[0]
         recon, _ = self.window_net.run_layers(4, len(c.main.descs) - 1, self.latent)
         return self.pixel_cut.run(recon, out)
 
     def views(self, roi):
-        """Per-image [h][w][3] views of what `decode` returned."""
+        """Per-image [h][w][3] views of what `decode` returned ([3][h][w] with roi_layout="planar")."""
+        if self.direct:
+            return self.window_net.views(len(self.codec.main.descs) - 1, roi)
         return self.pixel_cut.views(roi)
 
     def check(self):
@@ -452,9 +459,9 @@ class MovingHyperpriorRoi(api._MovingRoiChain):
     Also `codec.moving_roi(slots)`."""
     _free, _abi, _slot_type, _n_totals = "sicn_ragged_ctx_roi_move_free", "sicn_ragged_ctx_roi_move", api._lib.RaggedCtxRoiMoveSlot, 7
 
-    def __init__(self, codec_, slots):
+    def __init__(self, codec_, slots, roi_layout=None, direct=None):
         self.codec = codec_
-        self._check_slots(codec_.main, slots)
+        self._check_slots(codec_.main, slots, roi_layout, direct)
         self._make(codec_.main, codec_.y_coder)
         self._containers = None     # (slot buffer, valid or None) of the last prepare: kept alive, read by every decode
         self._unpacked = False      # the last prepare read an archive: check() reports its verdict first

@@ -37,6 +37,7 @@ from pathlib import Path
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 sys.path.insert(0, str(Path(__file__).resolve().parent))
 
+import roi_direct  # noqa: E402  (--roi-layout, --direct, --permute and the timed --only run)
 from ragged_speed import make_sizes  # noqa: E402  (the same seeded mix)
 
 SELECTIONS = {4: [3, 17, 40, 63], 1: [17]}
@@ -104,7 +105,9 @@ def main():
     ap.add_argument("--kernel-trace", action="append", default=[], metavar="SELECTED@SYMBOLS=PATH")
     ap.add_argument("--trace-only", action="store_true", help="print the --kernel-trace sections alone (no device needed)")
     ap.add_argument("--out", help="also write the table to this file")
+    roi_direct.add_arguments(ap)
     a = ap.parse_args()
+    roi_direct.check(ap, a)
     if a.rounds < 3 and not a.only:
         ap.error("--rounds: at least 3")
     if a.trace_only:
@@ -140,8 +143,8 @@ def main():
             self.positions = [[(int(prng.integers(0, w - rw + 1)), int(prng.integers(0, h - rh + 1))) for (w, h), (rw, rh) in
                                zip(self.codec.sizes, self.side)] for _ in range(POSITIONS)]
             self.rects = [[(x, y, rw, rh) for (x, y), (rw, rh) in zip(p, self.side)] for p in self.positions]
-            self.made = [] if only_move else [self.codec.roi(r) for r in self.rects]
-            self.moving = self.codec.moving_roi([(i, rw, rh) for i, (rw, rh) in enumerate(self.side)])
+            self.made = [] if only_move else [self.codec.roi(r, **roi_direct.keywords(a)) for r in self.rects]
+            self.moving = self.codec.moving_roi([(i, rw, rh) for i, (rw, rh) in enumerate(self.side)], **roi_direct.keywords(a))
             self.xy_all = torch.tensor(self.positions, dtype=torch.int32, device="cuda")
             self.xy = torch.zeros((len(sel), 2), dtype=torch.int32, device="cuda")
             self.pixels = torch.empty(self.moving.roi_bytes, dtype=torch.uint8, device="cuda")
@@ -155,7 +158,7 @@ def main():
             torch.cuda.synchronize()
 
         def by_build(self, k):
-            roi = self.codec.roi(self.rects[k])
+            roi = self.codec.roi(self.rects[k], **roi_direct.keywords(a))
             got = roi.decode(archive=self.resident, images=self.index, out=self.pixels)
             torch.cuda.synchronize()
             del roi
@@ -191,6 +194,12 @@ def main():
         for k in range(a.calls):
             case.by_move(k % POSITIONS)
         case.moving.check()
+        turn = iter(range(10 ** 9))
+
+        def move():                                             # the positions in turn; the last call of a batch is position calls - 1
+            case.xy.copy_(case.xy_all[next(turn) % a.calls % POSITIONS])
+            return case.moving.decode(case.xy, out=case.pixels)
+        roi_direct.timed_only(a, "ragged_hyper_roi_move", move, case.moving.views)
         print(f"{a.only}: {a.calls} moves done, {len(case.sel)} of {len(sizes)} images, y streams of {a.stream_symbols}")
         return 0
 

@@ -35,6 +35,7 @@ from pathlib import Path
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 sys.path.insert(0, str(Path(__file__).resolve().parent))
 
+import roi_direct  # noqa: E402  (--roi-layout, --direct, --permute and the timed --only run)
 from ragged_speed import make_sizes  # noqa: E402  (the same seeded mix)
 
 SELECTIONS = {4: [3, 17, 40, 63], 1: [17]}
@@ -144,7 +145,9 @@ def main():
     ap.add_argument("--kernel-trace", action="append", default=[], metavar="WHAT:SELECTED=PATH")
     ap.add_argument("--trace-only", action="store_true", help="print the --kernel-trace sections alone (no device needed)")
     ap.add_argument("--out", help="also write the table to this file")
+    roi_direct.add_arguments(ap)
     a = ap.parse_args()
+    roi_direct.check(ap, a)
     if a.rounds < 5 and not a.only:
         ap.error("--rounds: at least 5")
     if a.trace_only:
@@ -175,10 +178,10 @@ def main():
             self.codec = hyperprior.RaggedHyperpriorCodec.from_archive(b, seed=a.seed, main_params=params, images=sel)
             self.rects = [centred(s) for s in self.codec.sizes]
             self.index = torch.tensor(sel, dtype=torch.int32, device="cuda")
-            self.roi = self.codec.roi(self.rects)
+            self.roi = self.codec.roi(self.rects, **roi_direct.keywords(a))
             main = self.codec.main
             self.out = torch.empty(main.nbytes(7), dtype=torch.uint8, device="cuda")
-            self.pixels = torch.empty(self.roi.pixel_cut.dst_bytes, dtype=torch.uint8, device="cuda")
+            self.pixels = torch.empty(sum(3 * r[2] * r[3] for r in self.rects), dtype=torch.uint8, device="cuda")
             main.cropped(self.out)                                   # makes the crop object
             self.variants = {"full": self.full, "roi": self.by_roi}
             win = self.roi.window
@@ -219,6 +222,9 @@ def main():
             fn()
         torch.cuda.synchronize()
         (case.roi if a.only == "roi" else case.codec).check()
+        if a.only == "roi":
+            roi_direct.timed_only(a, "ragged_hyper_roi", lambda: case.roi.decode(archive=resident, images=case.index, out=case.pixels),
+                                  case.roi.views)
         print(f"{a.only}: {a.calls} calls done, {len(case.sel)} of {len(sizes)} images")
         return 0
 

@@ -34,6 +34,7 @@ from pathlib import Path
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 sys.path.insert(0, str(Path(__file__).resolve().parent))
 
+import roi_direct  # noqa: E402  (--roi-layout, --direct, --permute and the timed --only run)
 from ragged_speed import make_sizes  # noqa: E402  (the same seeded mix)
 
 SELECTIONS = {4: [3, 17, 40, 63], 1: [17]}
@@ -90,7 +91,9 @@ def main():
     ap.add_argument("--kernel-trace", action="append", default=[], metavar="SELECTED=PATH")
     ap.add_argument("--trace-only", action="store_true", help="print the --kernel-trace sections alone (no device needed)")
     ap.add_argument("--out", help="also write the table to this file")
+    roi_direct.add_arguments(ap)
     a = ap.parse_args()
+    roi_direct.check(ap, a)
     if a.rounds < 3 and not a.only:
         ap.error("--rounds: at least 3")
     if a.trace_only:
@@ -129,8 +132,9 @@ def main():
             self.positions = [[(int(prng.integers(0, w - rw + 1)), int(prng.integers(0, h - rh + 1))) for (w, h), (rw, rh) in
                                zip(self.net.sizes, self.side)] for _ in range(POSITIONS)]
             self.rects = [[(x, y, rw, rh) for (x, y), (rw, rh) in zip(p, self.side)] for p in self.positions]
-            self.made = [api.RaggedRoi(self.net, r, coder=self.coder) for r in self.rects]
-            self.moving = self.net.moving_roi([(i, rw, rh) for i, (rw, rh) in enumerate(self.side)], coder=self.coder)
+            self.made = [] if a.only else [api.RaggedRoi(self.net, r, coder=self.coder, **roi_direct.keywords(a)) for r in self.rects]
+            self.moving = self.net.moving_roi([(i, rw, rh) for i, (rw, rh) in enumerate(self.side)], coder=self.coder,
+                                              **roi_direct.keywords(a))
             self.xy_all = torch.tensor(self.positions, dtype=torch.int32, device="cuda")
             self.xy = torch.zeros((len(sel), 2), dtype=torch.int32, device="cuda")
             self.pixels = torch.empty(self.moving.roi_bytes, dtype=torch.uint8, device="cuda")
@@ -138,7 +142,7 @@ def main():
             self.streams = (self.moving.items, [m.window.selected_streams for m in self.made])
 
         def by_build(self, k):
-            roi = api.RaggedRoi(self.net, self.rects[k], coder=self.coder)
+            roi = api.RaggedRoi(self.net, self.rects[k], coder=self.coder, **roi_direct.keywords(a))
             got = roi.decode(valid=self.valid, out=self.pixels)
             torch.cuda.synchronize()
             del roi
@@ -172,6 +176,12 @@ def main():
         for k in range(a.calls):
             case.by_move(k % POSITIONS)
         assert not case.moving.status[:, 0].any()
+        turn = iter(range(10 ** 9))
+
+        def move():                                             # the positions in turn; the last call of a batch is position calls - 1
+            case.xy.copy_(case.xy_all[next(turn) % a.calls % POSITIONS])
+            return case.moving.decode(case.xy, valid=case.valid, out=case.pixels)
+        roi_direct.timed_only(a, "ragged_roi_move", move, case.moving.views)
         print(f"{a.only}: {a.calls} moves done, {len(case.sel)} of {len(sizes)} images")
         return 0
 

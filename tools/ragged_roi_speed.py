@@ -34,6 +34,7 @@ from pathlib import Path
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 sys.path.insert(0, str(Path(__file__).resolve().parent))
 
+import roi_direct  # noqa: E402  (--roi-layout, --direct, --permute and the timed --only run)
 from ragged_speed import make_sizes  # noqa: E402  (the same seeded mix)
 
 SELECTIONS = {4: [3, 17, 40, 63], 1: [17]}
@@ -100,7 +101,9 @@ def main():
     ap.add_argument("--kernel-trace", action="append", default=[], metavar="WHAT:SELECTED=PATH")
     ap.add_argument("--trace-only", action="store_true", help="print the --kernel-trace sections alone (no device needed)")
     ap.add_argument("--out", help="also write the table to this file")
+    roi_direct.add_arguments(ap)
     a = ap.parse_args()
+    roi_direct.check(ap, a)
     if a.rounds < 5 and not a.only:
         ap.error("--rounds: at least 5")
     if a.trace_only:
@@ -134,10 +137,10 @@ def main():
             self.coder = self.net.latent_coder([lengths[i] for i in sel])
             self.archive = codec.RaggedArchive([self.coder], tag=0)
             self.index = torch.tensor(sel, dtype=torch.int32, device="cuda")
-            self.roi = api.RaggedRoi(self.net, self.rects, coder=self.coder)
+            self.roi = api.RaggedRoi(self.net, self.rects, coder=self.coder, **roi_direct.keywords(a))
             self.latent = torch.empty(self.net.nbytes(3), dtype=torch.uint8, device="cuda")
             self.out = torch.empty(self.net.nbytes(7), dtype=torch.uint8, device="cuda")
-            self.pixels = torch.empty(self.roi.pixel_cut.dst_bytes, dtype=torch.uint8, device="cuda")
+            self.pixels = torch.empty(sum(3 * r[2] * r[3] for r in self.rects), dtype=torch.uint8, device="cuda")
             self.variants = {"full": self.full, "roi": self.by_roi}
             self.streams = (self.roi.window.selected_streams, sum(int(im.n_streams) for im in self.coder.images[:len(sel)]))
             self.latent_positions = (sum(p["cw"] * p["rh"] for p in self.roi.plans), sum(h * w for h, w, _ in self.net.shapes(3)))
@@ -171,6 +174,8 @@ def main():
         valid, = case.archive.unpack(resident, images=case.index)
         torch.cuda.synchronize()
         band = torch.empty(case.roi.window.band_bytes, dtype=torch.uint8, device="cuda")
+        if a.only == "roi":
+            roi_direct.timed_only(a, "ragged_roi", lambda: case.roi.decode(valid=valid, out=case.pixels), case.roi.views)
         for _ in range(a.calls):
             if a.only == "roi":
                 case.roi.decode(valid=valid, out=case.pixels)
